@@ -25,7 +25,7 @@ Extra regions, all in the same ONE JSON line (none of them changes `value` / `ms
                              into N tiles + apron, gathered to rank 0), whatever --scaling the main region used; N = 4 also runs
                              config 4 (Cornell 3840x2160 Reference, 2 x 2 tiles) as `multi_gpu.strong_config4`.
   --no-extras skips them.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line. --dump-outputs DIR also writes the frame of the line's last timed step as DIR/frame.npy (dump_outputs()).
 """
 import argparse
 import json
@@ -104,6 +104,28 @@ def cpu_baseline(args, size):
     return {"value": round(best_rate / 1e6, 3), "unit": "Mray/s", "cores": cores, "kind": "port",
             "ms_per_frame": round(best_dt * 1e3, 1), "mean_ms_per_frame": round(mean_dt * 1e3, 1),
             "sample": f"best of {timed} frame(s) (after 1 warm-up frame) of the same workload — {args.scene} {size[0]}x{size[1]} mode {args.mode} —, OpenMP over {cores} threads"}
+
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(directory, frame):
+    """--dump-outputs DIR: what the timed path hands its caller in its last step — the composed RGBA32F frame (rank 0's gathered frame
+    for N > 1; strong_config5's when that config is the line) — as DIR/frame.npy, float32 [height, width, 4]. A frame over 64 MB is replaced by a fixed sample of its pixels (seed 0,
+    the same pixels for the same frame size): DIR/frame_sample.npy, float32 [n, 4], and the flat pixel index of each row,
+    DIR/frame_sample_index.npy, float64 [n]. Returns the names written."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(directory, "frame.npy"), frame)
+        return ["frame"]
+    pixels = frame.reshape(-1, frame.shape[-1])
+    n = DUMP_LIMIT_BYTES // 2 // (pixels.itemsize * pixels.shape[1] + 8)
+    index = np.sort(np.random.default_rng(0).choice(pixels.shape[0], size=n, replace=False))
+    np.save(os.path.join(directory, "frame_sample.npy"), pixels[index])
+    np.save(os.path.join(directory, "frame_sample_index.npy"), index.astype(np.float64))
+    return ["frame_sample", "frame_sample_index"]
 
 
 def workload_key(scene, width, height, mode):
@@ -415,9 +437,10 @@ class Job:
         self.outs = []; self.full = None
 
 
-def strong_config(torch, dist, args, world, rank, local_rank, debug_shared, scene, mode_name, size, key, steps=None, profile=False):
+def strong_config(torch, dist, args, world, rank, local_rank, debug_shared, scene, mode_name, size, key, steps=None, profile=False, keep_frame=False):
     """A BASELINE.json multi-GPU config as written — ONE frame of `size` split into `world` tiles (st_dist_partition; + apron in Image mode),
-    tiles gathered to rank 0 every frame — timed like the main region (barrier + synchronize on both sides, max over ranks)."""
+    tiles gathered to rank 0 every frame — timed like the main region (barrier + synchronize on both sides, max over ranks).
+    keep_frame: rank 0 also returns the gathered frame of the last timed step, on the host, as out["_frame"]."""
     job = Job(torch, dist, args, scene, mode_name, size, world, rank, local_rank, debug_shared)
     steps = max(2, min(args.steps, 30)) if steps is None else steps   # (as the line's main region: EXACTLY the K steps asked for)
     job.run(min(args.preroll, 48))
@@ -426,6 +449,7 @@ def strong_config(torch, dist, args, world, rank, local_rank, debug_shared, scen
     torch.cuda.synchronize()
     job.engine.ray_count(job.cam, reset=True); job.gather_events.clear()
     elapsed, frame = job.timed_region(steps)
+    last_frame = frame.cpu().numpy() if (keep_frame and rank == 0) else None   # (outside the region; the profile regions render into the same target)
     elapsed, rays_total, per_rank = job.reduce(elapsed, job.counted_rays())
     finite = bool(torch.isfinite(frame).all())
     out = {"workload": f"{scene} {size[0]}x{size[1]} mode {mode_name}, strong: one frame in {world} tiles (st_dist_partition), gathered to rank 0",
@@ -441,6 +465,8 @@ def strong_config(torch, dist, args, world, rank, local_rank, debug_shared, scen
            "n1_ms_reference": n1_reference(key), "n1_ms_reference_source": "profiles/n1_reference.json (builder-run single-GPU figure, not measured by this process)",
            "rays_per_frame": round(rays_total / steps), "width": size[0], "height": size[1],
            "frame_finite": finite}
+    if last_frame is not None:
+        out["_frame"] = last_frame
     if profile and not args.no_profile:
         # this rank's launches of the same K steps again with per-kernel events (as the N = 1 line's regions 2 / 2b / 2c): the `roofline` object of a
         # line whose main region is this config is then this config's own dominant kernel (on rank 0's tile), not the headline scene's
@@ -544,6 +570,10 @@ def main():
                          "and the weak region rides along under multi_gpu.weak_scaling_extra")
     ap.add_argument("--exact", action="store_true", help="run the bit-exact build of the kernels (ST_ARITH_EXACT) instead of the default fast build")
     ap.add_argument("--dump-frame", default=None, help="rank 0 saves the last (gathered) frame as .npy — tests compare it with a single-GPU render")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the frame the line's timed steps computed in their last step — region 1's; on the N > 1 command whose line is "
+                         "BASELINE config 5 (no --scaling, default workload), strong_config5's gathered frame — as DIR/<name>.npy (float32, at most "
+                         "64 MB in all; a fixed sample of the pixels of a larger frame); the inputs depend on the arguments only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel HIP-event timing inside the timed region")
     ap.add_argument("--no-extras", action="store_true", help="skip the extra regions (moving light + camera, moving geometry, present path; N > 1: BASELINE configs 5 / 4 as written)")
@@ -552,6 +582,12 @@ def main():
                     help="one GPU: render the N tile windows (+ apron) of a --width x --height frame one after another and print per-tile ms, max / mean and the speed-up N GPUs could reach at best (prints its own JSON line; no headline)")
     ap.add_argument("--balance-rounds", type=int, default=4, help="N > 1 strong-scaling extras (Image modes) and --emulate-tiles: rounds of cost-weighted tile rebalancing (st_dist_grid_rebalance) before the timed region; 0 = the equal split")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0 or args.preroll < 0:
+        ap.error("--warmup and --preroll cannot be negative")
+    if args.emulate_tiles and args.dump_outputs:
+        ap.error("--dump-outputs writes the main timed region's frame, which --emulate-tiles does not run")
 
     import torch
     import torch.distributed as dist
@@ -615,6 +651,8 @@ def main():
 
     # region 1: EXACTLY K steps, no instrumentation -> value / ms_per_step
     elapsed, frame = timed_region()
+    # --dump-outputs: the frame of the line's timed path — region 1's, or strong_config5's when that is the line (below)
+    last_frame = frame.cpu().numpy() if (rank == 0 and args.dump_outputs and not config5_main) else None   # (outside the region; later regions render into the same target)
     rays = job.counted_rays()
     gather_ms = job.gather_ms()
     # region 2: the same K steps again with HIP events around every run of same-slot launches (on the launch stream, pass
@@ -769,11 +807,16 @@ def main():
         job.close()
         ex = tuple(args.extras_size)
         strong["strong_config5"] = strong_config(torch, dist, args, world, rank, local_rank, debug_shared, "dungeon", "image", ex, "config5_dungeon_3840x2160_image_ms",
-                                                 steps=args.steps if config5_main else None, profile=config5_main)
+                                                 steps=args.steps if config5_main else None, profile=config5_main, keep_frame=config5_main and bool(args.dump_outputs))
+        if config5_main:
+            last_frame = strong["strong_config5"].pop("_frame", None)
         if world == 4 and not args.no_extras:
             strong["strong_config4"] = strong_config(torch, dist, args, world, rank, local_rank, debug_shared, "cornell", "reference", ex, "config4_cornell_3840x2160_reference_ms")
     copy_own, copy_torch = measure_copy_ceiling(torch, dev, None if strong else engine) if (rank == 0 and not debug_shared) else (None, None)
     copy_ceiling = max([c for c in (copy_own, copy_torch) if c], default=None)
+    if last_frame is not None:
+        dump_outputs(args.dump_outputs, last_frame)
+        del last_frame
     key = workload_key(args.scene, width, height, args.mode)
 
     if rank == 0:

@@ -23,3 +23,18 @@ def assert_bits_equal(got: np.ndarray, want: np.ndarray, what: str = ""):
 def psnr(a: np.ndarray, b: np.ndarray, peak: float = 1.0) -> float:
     mse = float(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2))
     return float("inf") if mse == 0 else 10.0 * np.log10(peak * peak / mse)
+
+
+def scene_fingerprint(engine, n_triangles: int) -> dict:
+    """sha256 digests of a ticked engine's scene as the host holds it: the triangles (world space; rows sorted, so the order the
+    tree keeps them in does not enter), the lights and the materials. tests/golden/scene_fingerprints.json holds those of the
+    benchmark scenes as the glTF loader reads the original files."""
+    import hashlib
+    tri = engine.read_scene(1)
+    assert n_triangles > 0 and tri.size % n_triangles == 0, (tri.size, n_triangles)
+    rows = np.ascontiguousarray(tri.view(np.uint32).reshape(n_triangles, -1))
+    rows = rows[np.lexsort(rows.T[::-1])]
+    return {"triangles": int(n_triangles), "triangle_words": int(rows.shape[1]),
+            "triangles_sha256": hashlib.sha256(rows.tobytes()).hexdigest(),
+            "lights_sha256": hashlib.sha256(engine.read_scene(2).tobytes()).hexdigest(),
+            "materials_sha256": hashlib.sha256(engine.read_scene(3).tobytes()).hexdigest()}

@@ -642,7 +642,8 @@ def test_bench_n_gt_1_line_is_config_5_strong(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, ST_BENCH_DEBUG_SHARED_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--preroll", "0", "--extras-size", "160", "96"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--preroll", "0", "--extras-size", "160", "96",
+           "--dump-outputs", str(tmp_path / "outputs")]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     out = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
@@ -658,6 +659,10 @@ def test_bench_n_gt_1_line_is_config_5_strong(tmp_path):
     # the roofline object is this config's own dominant kernel on rank 0's tile
     assert out["roofline"]["bound"] == "hbm" and out["roofline"]["traffic"] is None and out["roofline"]["achieved"] > 0
     assert "kernels" in out and out["config"]["frame_finite"]
+    # --dump-outputs writes the frame of the line's timed path: config 5's gathered 160x96 dungeon frame, not the weak region's 1920x2160 one
+    assert sorted(os.listdir(tmp_path / "outputs")) == ["frame.npy"]
+    dumped = np.load(tmp_path / "outputs" / "frame.npy")
+    assert dumped.dtype == np.float32 and dumped.shape == (96, 160, 4) and np.isfinite(dumped).all() and dumped[..., :3].any()
 
 
 def test_bench_strong_scaling_two_ranks_on_one_gpu(tmp_path):
@@ -687,6 +692,35 @@ def test_bench_strong_scaling_two_ranks_on_one_gpu(tmp_path):
         prod.update_camera(cam, desc); prod.tick(); prod.render_camera(cam, frame.data_ptr(), torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     assert_bits_equal(np.load(dump), frame.cpu().numpy(), "strong-scaling two-band frame vs single-process frame")
+
+
+def test_bench_dump_outputs_is_the_last_timed_frame(tmp_path):
+    """bench.py --dump-outputs DIR writes the frame the timed steps computed in their last step: with --preroll 0, --warmup 1 and
+    --steps 2 that is the third Reference frame of a fresh camera (Reference mode accumulates, so one step more or less is another
+    picture), bit for bit, although the profiled regions render more frames into the same target afterwards."""
+    import json, os, subprocess, sys
+    torch = _torch()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--preroll", "0", "--width", "96", "--height", "64",
+           "--mode", "reference", "--exact", "--no-cpu-baseline", "--no-extras", "--dump-outputs", str(out_dir)]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+    out = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 2 and out["warmup"] == 1
+    assert sorted(os.listdir(out_dir)) == ["frame.npy"]
+    got = np.load(out_dir / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == (64, 96, 4)
+    prod = Engine(device=0, exact=True)
+    scenes.build_cornell(prod); prod.set_seed(0)
+    desc = scenes.cornell_camera((96, 64), CameraMode.REFERENCE, depth=1)
+    cam = prod.create_camera(desc)
+    frame = torch.zeros((64, 96, 4), dtype=torch.float32, device="cuda:0")
+    for _ in range(3):
+        prod.update_camera(cam, desc); prod.tick(); prod.render_camera(cam, frame.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    prod.close()
+    assert_bits_equal(got, frame.cpu().numpy(), "bench.py --dump-outputs frame vs the third frame rendered in-process")
 
 
 def test_two_cameras_on_two_streams_bit_exact():

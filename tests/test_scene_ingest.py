@@ -4,13 +4,13 @@ The loader is checked three ways: (1) the PNG decoder against an independent enc
 bit depth, filter type and Adam7) and against PIL where it is installed; (2) a synthetic glTF exercising the features
 the benchmark assets do not (TRS + matrix hierarchies, strided and normalised accessors, u8/u16/u32 indices, missing
 normals, Mask/Blend materials, the default material, data URIs, external files, skipped primitive modes) against the
-same scene inserted through the Python API; (3) in the build container only, the reference's own benchmark assets
-against the committed .npz conversions of them."""
+same scene inserted through the Python API; (3) the benchmark scenes' committed conversions (assets/*.npz) against digests of
+the engine state the loader reached from the original glTF / GLB files (tests/golden/scene_fingerprints.json, made by
+tests/golden/make_scene_fingerprints.py), both inserted through the API and written back out as glTF / GLB and loaded."""
 import base64
 import json
 import os
 import struct
-import zipfile
 import zlib
 
 import numpy as np
@@ -19,8 +19,6 @@ import pytest
 from parity import assert_bits_equal
 from strolle_amd import Engine, Instance, Material, Mesh, StrolleError, scenes
 from strolle_amd.api import decode_png
-
-REFERENCE = "/root/reference/bevy-strolle/assets"
 
 
 # ------------------------------------------------------------------------------------------------ a PNG encoder for the tests
@@ -490,35 +488,130 @@ def test_loader_survives_random_damage(tmp_path):
     assert outcomes["ok"] and outcomes["error"], outcomes
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="the reference's assets exist in the build container only")
+SCENE_FINGERPRINTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "scene_fingerprints.json")
+# name -> (npz, load_gltf keywords, material overrides of the API route): the settings bench.py's scenes are built with
+CONVERTED_SCENES = {"cornell": ("cornell.npz", {}, None),
+                    "dungeon": ("dungeon.npz", dict(reflectance=0.0, perceptual_roughness=1.0), dict(reflectance=0.0, perceptual_roughness=1.0)),
+                    "dungeon-subdivided": ("dungeon.npz", dict(reflectance=0.0, perceptual_roughness=1.0, subdivide=1), dict(reflectance=0.0, perceptual_roughness=1.0))}
+
+
+def _texel_digests(converted):
+    import hashlib
+    return [hashlib.sha256(np.ascontiguousarray(converted[f"image_{i}"], np.uint8).tobytes()).hexdigest() for i in range(int(converted["n_images"]))]
+
+
 @pytest.mark.parametrize("name", ["cornell", "dungeon", "dungeon-subdivided"])
-def test_reference_assets_load_to_the_committed_conversions(tmp_path, name):
-    """assets/*.npz were converted from these files by tools/convert_assets.py; the C++ loader has to arrive at the same
-    engine state from the original files, and its PNG decoder at the same texels as PIL did for the conversion."""
-    if name == "cornell":
-        zipfile.ZipFile(os.path.join(REFERENCE, "cornell.zip")).extractall(tmp_path)
-        path, kw, npz, overrides = str(tmp_path / "cornell" / "scene.gltf"), {}, "cornell.npz", None
-    else:
-        zipfile.ZipFile(os.path.join(REFERENCE, "demo.zip")).extractall(tmp_path)
-        kw = dict(reflectance=0.0, perceptual_roughness=1.0, subdivide=1 if "sub" in name else 0)
-        path, npz, overrides = str(tmp_path / "demo" / "level.glb"), "dungeon.npz", dict(reflectance=0.0, perceptual_roughness=1.0)
+def test_reference_assets_load_to_the_committed_conversions(name):
+    """assets/*.npz were converted from the original Cornell box (cornell.zip: scene.gltf) and dungeon (demo.zip: level.glb) by
+    tools/convert_assets.py. Inserted through the Python API, a conversion has to give the engine state the C++ loader reached from
+    the original file — triangles, lights and materials equal to the digests in tests/golden/scene_fingerprints.json — and its
+    textures the texels the loader's PNG decoder read from the original (checked there against the PIL conversion)."""
+    from parity import scene_fingerprint
+    want = json.load(open(SCENE_FINGERPRINTS))[name]
+    npz, kw, overrides = CONVERTED_SCENES[name]
     converted = np.load(os.path.join(scenes.ASSETS, npz))
+    e = Engine(device=-1)
+    scenes._insert_gltf(e, converted, material_overrides=overrides, subdivide=kw.get("subdivide", 0))
+    e.tick()
+    assert int(converted["n_meshes"]) == want["meshes"] and int(converted["n_images"]) == want["images"]
+    got = scene_fingerprint(e, want["triangles"])
+    for key in ("triangle_words", "triangles_sha256", "lights_sha256", "materials_sha256"):
+        assert got[key] == want[key], f"{name}: {key} differs from the original scene's"
+    if "textures_sha256" in want:
+        assert _texel_digests(converted) == want["textures_sha256"], f"{name}: texels differ from the original textures'"
+    e.close()
+
+
+def _write_converted_scene(npz, directory, glb):
+    """A committed scene conversion (assets/*.npz) written back out as the kind of file it came from: one mesh per converted mesh
+    (plain triangle list: POSITION, NORMAL, TEXCOORD_0), one root node per mesh carrying its world transform as a `matrix`, the
+    materials (alpha mode 1 as Blend; neither committed conversion has one) and every texture as an RGBA PNG. Returns the path written."""
+    blob = bytearray()
+
+    def view(data):
+        while len(blob) % 4:
+            blob.append(0)
+        blob.extend(data)
+        views.append({"buffer": 0, "byteOffset": len(blob) - len(data), "byteLength": len(data)})
+        return len(views) - 1
+
+    views, accessors, meshes, nodes, materials = [], [], [], [], []
+    n_img = int(npz["n_images"])
+    images = [{"bufferView": view(encode_png(npz[f"image_{i}"].astype(np.int64), 6, 8)), "mimeType": "image/png"} for i in range(n_img)]
+    for i in range(len(npz["material_metallic"])):
+        alpha_mode = int(npz["material_alpha_mode"][i])
+        pbr = {"baseColorFactor": [float(v) for v in npz["material_base_color"][i]], "metallicFactor": float(npz["material_metallic"][i]),
+               "roughnessFactor": float(npz["material_perceptual_roughness"][i])}
+        if int(npz["material_image"][i]) >= 0:
+            pbr["baseColorTexture"] = {"index": int(npz["material_image"][i])}
+        materials.append({"pbrMetallicRoughness": pbr, "emissiveFactor": [float(v) for v in npz["material_emissive"][i]], "alphaMode": "BLEND" if alpha_mode else "OPAQUE"})
+    for i in range(int(npz["n_meshes"])):
+        attributes = {}
+        for name, key, kind in (("POSITION", "positions", "VEC3"), ("NORMAL", "normals", "VEC3"), ("TEXCOORD_0", "uvs", "VEC2")):
+            data = np.ascontiguousarray(npz[f"{key}_{i}"], np.float32)
+            count = data.size // (3 if kind == "VEC3" else 2)
+            accessor = {"bufferView": view(data.tobytes()), "componentType": 5126, "count": count, "type": kind}
+            if name == "POSITION":
+                flat = data.reshape(-1, 3)
+                accessor.update({"min": flat.min(0).tolist(), "max": flat.max(0).tolist()})
+            accessors.append(accessor)
+            attributes[name] = len(accessors) - 1
+        meshes.append({"primitives": [{"attributes": attributes, "material": int(npz[f"material_{i}"])}]})
+        columns = npz[f"xform_{i}"].astype(np.float64).reshape(4, 3)   # [x_axis y_axis z_axis t]
+        nodes.append({"mesh": i, "matrix": np.concatenate([columns, [[0.0], [0.0], [0.0], [1.0]]], axis=1).reshape(-1).tolist()})
+    doc = {"asset": {"version": "2.0"}, "scene": 0, "scenes": [{"nodes": list(range(len(nodes)))}], "nodes": nodes, "meshes": meshes,
+           "materials": materials, "accessors": accessors, "bufferViews": views}
+    if n_img:
+        doc.update({"images": images, "textures": [{"source": i} for i in range(n_img)]})
+    if glb:
+        doc["buffers"] = [{"byteLength": len(blob)}]
+        js = json.dumps(doc).encode()
+        js += b" " * ((-len(js)) % 4)
+        binary = bytes(blob) + b"\0" * ((-len(blob)) % 4)
+        body = struct.pack("<II", len(js), 0x4E4F534A) + js + struct.pack("<II", len(binary), 0x004E4942) + binary
+        path = os.path.join(directory, "level.glb")
+        with open(path, "wb") as f:
+            f.write(struct.pack("<III", 0x46546C67, 2, 12 + len(body)) + body)
+    else:
+        doc["buffers"] = [{"byteLength": len(blob), "uri": "scene.bin"}]
+        with open(os.path.join(directory, "scene.bin"), "wb") as f:
+            f.write(bytes(blob))
+        path = os.path.join(directory, "scene.gltf")
+        with open(path, "w") as f:
+            json.dump(doc, f)
+    return path
+
+
+@pytest.mark.parametrize("name", ["cornell", "dungeon", "dungeon-subdivided"])
+def test_converted_scenes_written_as_gltf_load_to_the_same_state(tmp_path, name):
+    """The conversions written back out as glTF (the Cornell box, external buffer) or GLB (the dungeon: 8,393 triangles, 45 embedded
+    PNG textures): the C++ loader arrives at the engine state of the same conversion inserted through the API — and so at the
+    original scene's digests — and its PNG decoder at the same texels."""
+    from parity import scene_fingerprint
+    npz, kw, overrides = CONVERTED_SCENES[name]
+    converted = np.load(os.path.join(scenes.ASSETS, npz))
+    path = _write_converted_scene(converted, str(tmp_path), glb=name != "cornell")
     a, b = Engine(device=-1), Engine(device=-1)
     summary = a.load_gltf(path, **kw)
     scenes._insert_gltf(b, converted, material_overrides=overrides, subdivide=kw.get("subdivide", 0))
     for e in (a, b):
-        e.tick()   # (the subdivided level is 25 internal nodes deep: the launches take a 25-entry stack, no ST_ERR_BVH_TOO_DEEP)
+        e.tick()
     for what, label in enumerate(("BVH stream", "triangles", "lights", "materials")):
         assert_bits_equal(a.read_scene(what), b.read_scene(what), f"{name}: {label}")
-    assert summary["meshes"] == int(converted["n_meshes"]) and summary["images"] == int(converted["n_images"])
-    if name == "dungeon":
-        glb = open(path, "rb").read()
-        doc = json.loads(glb[20:20 + struct.unpack("<I", glb[12:16])[0]])
-        binary = glb[20 + struct.unpack("<I", glb[12:16])[0] + 8:]
+    want = json.load(open(SCENE_FINGERPRINTS))[name]
+    assert summary["meshes"] == want["meshes"] and summary["images"] == want["images"] and summary["triangles"] == want["triangles"]
+    got = scene_fingerprint(a, want["triangles"])
+    assert all(got[k] == want[k] for k in ("triangles_sha256", "lights_sha256", "materials_sha256")), name
+    if name != "cornell":
+        data = open(path, "rb").read()
+        doc = json.loads(data[20:20 + struct.unpack("<I", data[12:16])[0]])
+        binary = data[20 + struct.unpack("<I", data[12:16])[0] + 8:]
+        assert len(doc["images"]) == 45
         for i, image in enumerate(doc["images"]):
             view = doc["bufferViews"][image["bufferView"]]
             png = binary[view.get("byteOffset", 0): view.get("byteOffset", 0) + view["byteLength"]]
             assert np.array_equal(decode_png(png), converted[f"image_{i}"]), f"texture {i}"
+    a.close(); b.close()
 
 
 # ------------------------------------------------------------------------------------------------ JPEG
