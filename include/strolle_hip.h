@@ -231,6 +231,48 @@ int st_set_blue_noise(StEngine* e, const uint8_t* rgba_256x256x4, size_t bytes);
  * half-resolution passes work on 2x1 cells in tiles of 8) or the frame's right edge. st_camera_set_rows = all columns. */
 int st_camera_set_window(StEngine* e, StHandle camera, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1);
 int st_camera_set_rows(StEngine* e, StHandle camera, uint32_t y0, uint32_t y1);
+
+/* ---- scene queries (NEW seam): rays cast by the application against the scene the renderer draws (k_query.hip).
+ * Scene. A query sees the scene of the last st_tick: edits made since then are not visible. It is enqueued on `hip_stream`
+ *   after that tick's uploads (it waits on them as st_render_camera does) and returns at once, like st_render_camera.
+ * Hits. Both faces of a triangle are hit, as in the reference. Blend materials are honoured as the renderer's rays honour
+ *   them: base-colour alpha < 1 at the hit's uv is not a hit. `t` is in units of |direction| (the direction is used as given,
+ *   not normalised: Ray::new, strolle-gpu/src/ray.rs); a closest hit counts for 0 < t < t_max.
+ * Occlusion. st_scene_occluded writes 1 per ray that has any hit with 0 < t < t_max, else 0 (the shadow rays' walk: ray.rs:84-112).
+ * Picks. st_camera_pick casts the camera ray (Camera::ray) of pixel (x, y) of the camera as its last st_render_camera saw it,
+ *   so that the pick matches the frame on screen; a camera that has not rendered yet uses its current description. Pixels
+ *   outside that viewport are misses.
+ * Misses. A ray with t_max <= 0 or NaN, or with an all-zero direction, is a miss. A miss writes hit = 0, t = FLT_MAX and 0
+ *   everywhere else.
+ * Errors. A host-only engine returns ST_ERR_NO_DEVICE (there is no CPU fallback). count == 0 is a no-op returning ST_OK. Null
+ *   pointers with count > 0, unknown flag bits and a query before the first st_tick are ST_ERR_INVALID_ARGUMENT; an unknown
+ *   camera is ST_ERR_UNKNOWN_CAMERA. In the exact build (ST_ARITH_EXACT) a live scene copy whose tree was built on the device
+ *   has no contract stream: ST_ERR_INVALID_ARGUMENT, as st_render_camera reports it.
+ * Stack overflow. A walk whose stack overflows sets the engine's sticky walk word: the next st_tick reports it and re-arms
+ *   the walks as it does for frames (st_debug_walk_overflow).
+ * Buffers. `rays_device`, `hits_device`, `occluded_device` and `pixels_xy_device` are device memory of the engine's device. */
+typedef struct StRay {            /* 32 B */
+    float origin[3]; float t_max; /* hits count for 0 < t < t_max; FLT_MAX or +inf = unbounded */
+    float direction[3];           /* used as given, not normalised */
+    uint32_t _pad;
+} StRay;
+typedef struct StRayHit {         /* 64 B */
+    float point[3];  float t;             /* t = FLT_MAX on a miss */
+    float normal[3]; uint32_t triangle;   /* shading normal as the renderer resolves it (interpolated, facing the side the ray came
+                                           * from: the sign of 1/det); triangle = index into the mesh's array given to st_mesh_insert */
+    float uv[2]; float barycentric[2];    /* texture coordinates at the hit; Triangle::hit's (u, v): point = (1-u-v) p0 + u p1 + v p2 */
+    StHandle instance;                    /* the st_instance_insert handle */
+    uint32_t hit; uint32_t _pad;          /* 1 = hit */
+} StRayHit;
+enum { ST_RAY_COHERENT = 1 };  /* the caller promises runs of 64 consecutive rays are coherent (camera-like): they are walked as one
+                                * packet per wave. Correct for any rays; the flag changes only speed. */
+int st_scene_trace_rays(StEngine* e, const StRay* rays_device, uint32_t count, StRayHit* hits_device, uint32_t flags, void* hip_stream);
+int st_scene_occluded(StEngine* e, const StRay* rays_device, uint32_t count, uint32_t* occluded_device, void* hip_stream);
+int st_camera_pick(StEngine* e, StHandle camera, const uint32_t* pixels_xy_device /* (x, y) pairs */, uint32_t count,
+                   StRayHit* hits_device, void* hip_stream);
+/* Blocking convenience: host arrays in and out (staged through engine-owned buffers on a stream of the engine's own). */
+int st_scene_trace_rays_host(StEngine* e, const StRay* rays, uint32_t count, StRayHit* hits);
+
 /* ---- multi-GPU behind the boundary (NEW seam; SURVEY.md section 8e, BASELINE.json configs 4 and 5). One process per GPU, one
  * engine per process, the scene replicated; the frame is cut into tiles, every rank renders its tile (+ an apron of redundant
  * pixels in Image mode, whose passes read neighbours) with absolute pixel coordinates, and the ONE collective of the path

@@ -100,6 +100,24 @@ class StGltfSummary(C.Structure):
 assert C.sizeof(StMeshTriangle) == 144 and C.sizeof(StMaterial) == 88 and C.sizeof(StLight) == 52 and C.sizeof(StCamera) == 160
 
 
+class StRay(C.Structure):
+    """include/strolle_hip.h StRay (32 B): hits count for 0 < t < t_max; the direction is used as given (t in units of |direction|)."""
+    _fields_ = [("origin", C.c_float * 3), ("t_max", C.c_float), ("direction", C.c_float * 3), ("_pad", C.c_uint32)]
+
+
+class StRayHit(C.Structure):
+    """include/strolle_hip.h StRayHit (64 B): t = FLT_MAX and everything else 0 on a miss."""
+    _fields_ = [("point", C.c_float * 3), ("t", C.c_float), ("normal", C.c_float * 3), ("triangle", C.c_uint32),
+                ("uv", C.c_float * 2), ("barycentric", C.c_float * 2), ("instance", C.c_uint64), ("hit", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+# numpy records of the same layout (arrays of them are what the scene queries read and write)
+RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_max", "<f4"), ("direction", "<f4", (3,)), ("_pad", "<u4")])
+HIT_DTYPE = np.dtype([("point", "<f4", (3,)), ("t", "<f4"), ("normal", "<f4", (3,)), ("triangle", "<u4"), ("uv", "<f4", (2,)),
+                      ("barycentric", "<f4", (2,)), ("instance", "<u8"), ("hit", "<u4"), ("_pad", "<u4")])
+RAY_COHERENT = 1   # ST_RAY_COHERENT
+
+
 class StrolleError(RuntimeError):
     pass
 
@@ -349,6 +367,11 @@ class _Binding:
             self.camera_buffer_stale = fn("camera_buffer_stale", [vp, u64, i32, P(i32)])
             self.camera_present_copy = fn("camera_present_copy", [vp, u64, vp, vp, sz, vp])
             self.camera_present_ready = fn("camera_present_ready", [vp, u64, vp, i32, P(i32)])
+            if hasattr(lib, prefix + "scene_trace_rays"):   # scene queries (a library built before them, loaded for a same-box A/B, has none)
+                self.scene_trace_rays = fn("scene_trace_rays", [vp, vp, u32, vp, u32, vp])
+                self.scene_occluded = fn("scene_occluded", [vp, vp, u32, vp, vp])
+                self.camera_pick = fn("camera_pick", [vp, u64, vp, u32, vp, vp])
+                self.scene_trace_rays_host = fn("scene_trace_rays_host", [vp, vp, u32, vp])
             self.profile_enable = fn("profile_enable", [vp, i32])
             self.profile_read = fn("profile_read", [vp, P(StKernelProfile), sz, P(sz), i32])
             self.last_error = getattr(lib, prefix + "last_error"); self.last_error.restype = C.c_char_p; self.last_error.argtypes = []
@@ -655,6 +678,28 @@ class Engine(EngineBase):
     def render_camera(self, handle: int, out_device_ptr: int = 0, stream: int = 0):
         """Enqueue CameraController::render; `out_device_ptr` = device address of a W*H RGBA32F buffer (0 = skip composition)."""
         self._check(self._b.render_camera(self._h, handle, out_device_ptr, stream))
+
+    # ---- scene queries (include/strolle_hip.h "scene queries"): the scene of the last tick, enqueued on `stream`
+    def trace_rays(self, rays_ptr: int, count: int, hits_ptr: int, coherent: bool = False, stream: int = 0):
+        """st_scene_trace_rays: `count` StRay at device address `rays_ptr` -> StRayHit at `hits_ptr` (closest hits).
+        coherent=True: ST_RAY_COHERENT (runs of 64 rays are camera-like; changes only speed)."""
+        self._check(self._b.scene_trace_rays(self._h, rays_ptr, count, hits_ptr, RAY_COHERENT if coherent else 0, stream))
+
+    def occluded(self, rays_ptr: int, count: int, out_ptr: int, stream: int = 0):
+        """st_scene_occluded: one uint32 per ray at `out_ptr`, 1 where some triangle is hit at 0 < t < t_max."""
+        self._check(self._b.scene_occluded(self._h, rays_ptr, count, out_ptr, stream))
+
+    def pick(self, camera: int, pixels_ptr: int, count: int, hits_ptr: int, stream: int = 0):
+        """st_camera_pick: `count` (x, y) uint32 pairs at `pixels_ptr` -> StRayHit at `hits_ptr`, through the camera as its last
+        render saw it."""
+        self._check(self._b.camera_pick(self._h, camera, pixels_ptr, count, hits_ptr, stream))
+
+    def trace_rays_host(self, rays: np.ndarray) -> np.ndarray:
+        """st_scene_trace_rays_host: a RAY_DTYPE array in host memory -> a HIT_DTYPE array (blocking)."""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+        hits = np.zeros(rays.shape[0], dtype=HIT_DTYPE)
+        self._check(self._b.scene_trace_rays_host(self._h, rays.ctypes.data, rays.shape[0], hits.ctypes.data))
+        return hits
 
     def set_output_format(self, handle: int, fmt: "OutputFormat"):
         """viewport.format (camera.rs:170-175): what st_render_camera writes into its output buffer."""

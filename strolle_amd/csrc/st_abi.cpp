@@ -247,6 +247,35 @@ int st_render_camera(StEngine* e, StHandle h, void* out, void* stream) {
     return E(e)->render(*it->second, out, static_cast<hipStream_t>(stream));
 }
 
+// ---- scene queries (st_query.cpp): argument checks first, so that a host-only engine answers them too
+int st_scene_trace_rays(StEngine* e, const StRay* rays, uint32_t count, StRayHit* hits, uint32_t flags, void* stream) {
+    ST_REQUIRE(e, "null engine");
+    ST_REQUIRE((flags & ~(uint32_t)ST_RAY_COHERENT) == 0u, "unknown flag bits");
+    if (count == 0u) return ST_OK;
+    ST_REQUIRE(rays && hits, "null argument");
+    return E(e)->trace_rays(rays, count, hits, flags, static_cast<hipStream_t>(stream));
+}
+int st_scene_occluded(StEngine* e, const StRay* rays, uint32_t count, uint32_t* occluded, void* stream) {
+    ST_REQUIRE(e, "null engine");
+    if (count == 0u) return ST_OK;
+    ST_REQUIRE(rays && occluded, "null argument");
+    return E(e)->occluded(rays, count, occluded, static_cast<hipStream_t>(stream));
+}
+int st_camera_pick(StEngine* e, StHandle h, const uint32_t* pixels_xy, uint32_t count, StRayHit* hits, void* stream) {
+    ST_REQUIRE(e, "null engine");
+    if (count == 0u) return ST_OK;
+    ST_REQUIRE(pixels_xy && hits, "null argument");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    return E(e)->pick(*it->second, pixels_xy, count, hits, static_cast<hipStream_t>(stream));
+}
+int st_scene_trace_rays_host(StEngine* e, const StRay* rays, uint32_t count, StRayHit* hits) {
+    ST_REQUIRE(e, "null engine");
+    if (count == 0u) return ST_OK;
+    ST_REQUIRE(rays && hits, "null argument");
+    return E(e)->trace_rays_host(rays, count, hits);
+}
+
 int st_debug_keep_all_planes(StEngine* e, int keep) { ST_REQUIRE(e, "null engine"); E(e)->tuning.lean_frame = keep == 0 ? 1u : 0u; return ST_OK; }
 int st_camera_present_copy(StEngine* e, StHandle h, const void* src_device, void* dst_host, size_t bytes, void* stream) {
     ST_REQUIRE(e && src_device && dst_host && bytes, "null argument");

@@ -275,6 +275,8 @@ struct CameraState {
     hipStream_t present_stream = nullptr;
     PresentSlot present[2];
     uint32_t present_next = 0;
+    // the camera as the last render saw it (st_camera_pick casts through the frame on screen, not a later st_camera_update)
+    GpuCamera shown{}; uint32_t shown_width = 0, shown_height = 0; bool has_shown = false;
 };
 inline size_t plane_texels_per_pixel(int id) {
     if (id >= ST_BUF_DI_RESERVOIRS_0 && id <= ST_BUF_DI_RESERVOIRS_2) return 2;
@@ -438,6 +440,8 @@ struct Engine {
         size_t dirty_lo = SIZE_MAX, dirty_hi = 0; bool tri_full = true;  // what this copy lacks of the host's triangle arrays
         std::vector<uint64_t> pending_moves;   // instances moved on the device whose current transform this copy has not baked yet
         DeviceArray bake_jobs, bake_starts;
+        // per instance slot (tri_attr[4 t + 3].w): {StHandle lo, hi, first triangle slot, 0} — the scene queries' instance and mesh triangle (st_query.cpp)
+        DeviceArray instance_table;
         hipEvent_t free_ev = nullptr; bool busy = false;  // busy: frames reading this copy were enqueued since it was written; free_ev ends the last
         bool valid = false;
     };
@@ -572,6 +576,18 @@ struct Engine {
     }
 
     int render(CameraState& c, void* out, hipStream_t stream);
+    int scene_args(KArgs& a, bool heatmap) const;   // the scene half of KArgs (st_render.cpp): render() and the scene queries
+
+    // ---- scene queries (st_query.cpp; include/strolle_hip.h "scene queries")
+    std::vector<uint32_t> instance_table_;   // host image of SceneSet::instance_table, rebuilt by every scene upload
+    void fill_instance_table();
+    int query_begin(hipStream_t stream, KArgs& a, bool reader);
+    int query_end(hipStream_t stream, bool reader);
+    int trace_rays(const void* rays, uint32_t count, void* hits, uint32_t flags, hipStream_t stream, bool reader = true);
+    int occluded(const void* rays, uint32_t count, uint32_t* out, hipStream_t stream);
+    int pick(const CameraState& c, const uint32_t* pixels, uint32_t count, void* hits, hipStream_t stream);
+    int trace_rays_host(const void* rays, uint32_t count, void* hits);
+    hipStream_t query_stream = nullptr; DeviceArray d_query_rays, d_query_hits; void* query_pinned = nullptr; size_t query_pinned_bytes = 0;
 };
 
 }  // namespace st

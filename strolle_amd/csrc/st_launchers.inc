@@ -62,3 +62,8 @@ ST_LAUNCHER(launch_bvh_bake, (const void* jobs, const uint32_t* job_start, uint3
 // the compact stream (48-B entries, f16 conservative boxes) of the fast build's shadow rays, regenerated from the contract stream (k_bvh.hip)
 ST_LAUNCHER(launch_bvh_compact, (const float4* bvh, uint32_t n_entries, float4* out, hipStream_t s))
 ST_LAUNCHER(launch_bvh_wide, (const float4* bvh, const uint32_t* topo, uint32_t n_nodes, const uint32_t* leaf_entry, uint32_t n_leaves, uint32_t links16, float4* nodes, float4* leaves, hipStream_t s))
+// scene queries (k_query.hip; st_query.cpp): one ray per lane, 256 per block. rays: 2 float4 per StRay; hits: 4 float4 per StRayHit;
+// table: per instance slot {StHandle lo, hi, first triangle slot, 0}; pixels: (x, y) pairs
+ST_LAUNCHER(launch_query_closest, (const KArgs& a, const float4* rays, uint32_t count, float4* hits, const uint4* table, uint32_t packets, hipStream_t s))
+ST_LAUNCHER(launch_query_occluded, (const KArgs& a, const float4* rays, uint32_t count, uint32_t* occluded, hipStream_t s))
+ST_LAUNCHER(launch_query_pick, (const KArgs& a, const uint32_t* pixels, uint32_t count, float4* hits, const uint4* table, hipStream_t s))

@@ -1,0 +1,103 @@
+// st_query.cpp — host engine of libstrolle_hip.so: scene queries (include/strolle_hip.h "scene queries"; k_query.hip). Rays of the
+// application walk the live scene copy the frames walk, with the same scene arguments (scene_args) and the same reader bookkeeping as
+// render(): a tick never refills a copy a query that is still in flight reads. See st_engine.h.
+#include "st_engine.h"
+
+namespace st {
+
+// The handle table of the scene queries: per instance slot {StHandle lo, StHandle hi, first triangle slot, 0}. Instance slot ranges are
+// contiguous (instance_triangles), so `triangle slot - first` is the index into the mesh's own array.
+void Engine::fill_instance_table() {
+    const size_t slots = std::max<size_t>(instance_xforms.size() / 8u, 1u);
+    instance_table_.assign(4 * slots, 0u);
+    for (const auto& inst : instances) {
+        const auto r = instance_triangles.find(inst.id);
+        if (r == instance_triangles.end() || inst.xslot >= slots) continue;
+        uint32_t* w = instance_table_.data() + 4 * (size_t)inst.xslot;
+        w[0] = (uint32_t)inst.id; w[1] = (uint32_t)(inst.id >> 32); w[2] = (uint32_t)r->second.first; w[3] = 0u;
+    }
+}
+
+// The part every query shares with render(): the tick's uploads come first, the scene arguments are the frame's. `reader`: the query stays
+// in flight after the call returns and counts as a reader of sets[live] (render() keeps the same books).
+int Engine::query_begin(hipStream_t stream, KArgs& a, bool reader) {
+    if (!has_device) return fail(ST_ERR_NO_DEVICE, "scene query on a host-only engine");
+    if (!scene_uploaded) return fail(ST_ERR_INVALID_ARGUMENT, "st_tick must precede a scene query");
+    ST_HIP(hipSetDevice(device));
+    if (tick_work_in_flight) ST_HIP(hipStreamWaitEvent(stream, ev_tick, 0));
+    if (copy_in_flight) ST_HIP(hipStreamWaitEvent(stream, ev_copy, 0));
+    a = KArgs{};
+    if (int rc = scene_args(a, false)) return rc;
+    if (reader) {
+        if (rendered_before && last_render_stream != stream) mixed_render_streams = true;
+        last_render_stream = stream; rendered_before = true;
+    }
+    return ST_OK;
+}
+int Engine::query_end(hipStream_t stream, bool reader) {
+    ST_HIP(hipGetLastError());
+    if (reader && alternating) {  // the end of the last launch that reads this copy of the scene (as render() records it)
+        SceneSet& l = sets[live];
+        if (!l.free_ev) ST_HIP(hipEventCreateWithFlags(&l.free_ev, hipEventDisableTiming));
+        ST_HIP(hipEventRecord(l.free_ev, stream)); l.busy = true;
+    }
+    return ST_OK;
+}
+
+int Engine::trace_rays(const void* rays, uint32_t count, void* hits, uint32_t flags, hipStream_t stream, bool reader) {
+    KArgs a;
+    if (int rc = query_begin(stream, a, reader)) return rc;
+    // ST_RAY_COHERENT: the packet walk needs the wide stream, and is given up for good once it overflowed (st_engine.h packets_overflowed)
+    const uint32_t packets = (flags & ST_RAY_COHERENT) && a.bvh_w != nullptr && !packets_overflowed ? 1u : 0u;
+    L.launch_query_closest(a, static_cast<const float4*>(rays), count, static_cast<float4*>(hits), static_cast<const uint4*>(sets[live].instance_table.ptr), packets, stream);
+    return query_end(stream, reader);
+}
+
+int Engine::occluded(const void* rays, uint32_t count, uint32_t* out, hipStream_t stream) {
+    KArgs a;
+    if (int rc = query_begin(stream, a, true)) return rc;
+    L.launch_query_occluded(a, static_cast<const float4*>(rays), count, out, stream);
+    return query_end(stream, true);
+}
+
+int Engine::pick(const CameraState& c, const uint32_t* pixels, uint32_t count, void* hits, hipStream_t stream) {
+    KArgs a;
+    if (int rc = query_begin(stream, a, true)) return rc;
+    a.cam = c.has_shown ? c.shown : serialize_camera(c.desc);
+    a.width = c.has_shown ? c.shown_width : c.desc.width; a.height = c.has_shown ? c.shown_height : c.desc.height;
+    L.launch_query_pick(a, pixels, count, static_cast<float4*>(hits), static_cast<const uint4*>(sets[live].instance_table.ptr), stream);
+    return query_end(stream, true);
+}
+
+// Blocking: host rays -> pinned -> device, the query on the engine's own stream, device -> pinned -> host. The call has finished with the
+// scene copy when it returns, so it does not count as one of its readers (no later tick can overlap it).
+int Engine::trace_rays_host(const void* rays, uint32_t count, void* hits) {
+    if (!has_device) return fail(ST_ERR_NO_DEVICE, "scene query on a host-only engine");
+    if (!scene_uploaded) return fail(ST_ERR_INVALID_ARGUMENT, "st_tick must precede a scene query");
+    ST_HIP(hipSetDevice(device));
+    if (!query_stream) ST_HIP(hipStreamCreateWithFlags(&query_stream, hipStreamNonBlocking));
+    const size_t ray_bytes = (size_t)count * sizeof(StRay), hit_bytes = (size_t)count * sizeof(StRayHit);
+    auto grow = [](DeviceArray& d, size_t bytes) -> int {
+        if (bytes <= d.capacity) return ST_OK;
+        d.release();
+        ST_HIP(hipMalloc(&d.ptr, bytes)); d.capacity = bytes;
+        return ST_OK;
+    };
+    if (int rc = grow(d_query_rays, ray_bytes)) return rc;
+    if (int rc = grow(d_query_hits, hit_bytes)) return rc;
+    if (query_pinned_bytes < hit_bytes) {   // one page-locked buffer serves both directions (the hits are the larger)
+        if (query_pinned) ST_HIP(hipHostFree(query_pinned));
+        query_pinned = nullptr; query_pinned_bytes = 0;
+        ST_HIP(hipHostMalloc(&query_pinned, hit_bytes, hipHostMallocDefault));
+        query_pinned_bytes = hit_bytes;
+    }
+    memcpy(query_pinned, rays, ray_bytes);
+    ST_HIP(hipMemcpyAsync(d_query_rays.ptr, query_pinned, ray_bytes, hipMemcpyHostToDevice, query_stream));
+    if (int rc = trace_rays(d_query_rays.ptr, count, d_query_hits.ptr, 0u, query_stream, false)) { (void)hipStreamSynchronize(query_stream); return rc; }
+    ST_HIP(hipMemcpyAsync(query_pinned, d_query_hits.ptr, hit_bytes, hipMemcpyDeviceToHost, query_stream));
+    ST_HIP(hipStreamSynchronize(query_stream));
+    memcpy(hits, query_pinned, hit_bytes);
+    return ST_OK;
+}
+
+}  // namespace st

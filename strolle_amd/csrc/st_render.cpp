@@ -97,24 +97,14 @@ int Engine::allocate_camera(CameraState& c) {
     return ST_OK;
 }
 
-// ---- render (camera_controller.rs:87-174)
-int Engine::render(CameraState& c, void* out, hipStream_t stream) {
-    if (!has_device) return fail(ST_ERR_NO_DEVICE, "render_camera on a host-only engine");
-    if (!scene_uploaded) return fail(ST_ERR_INVALID_ARGUMENT, "st_tick must precede st_render_camera");
-    ST_HIP(hipSetDevice(device));
-    if (tick_work_in_flight) ST_HIP(hipStreamWaitEvent(stream, ev_tick, 0));  // a no-op when st_tick ran on this stream
-    if (copy_in_flight) ST_HIP(hipStreamWaitEvent(stream, ev_copy, 0));       // likewise (st_tick already queued this wait on its own stream)
-    if (rendered_before && last_render_stream != stream) mixed_render_streams = true;  // the null stream is a stream too
-    last_render_stream = stream; rendered_before = true;
-    const bool alt = c.frame % 2u == 1u;
-    c.last_lean = 0u; c.last_lean_composed = false;
-    KArgs a{};
-    a.cam = c.curr; a.prev_cam = c.prev;
+// The scene half of KArgs (st_engine.h scene_args): what every launch that walks the live scene copy reads — its arrays, the stream its rays
+// walk (contract, compact or wide), the stack they hold and the walk flags. `heatmap`: the launch is a BVH heatmap pass, which observes the
+// contract stream. Shared by render() and the scene queries (st_query.cpp).
+int Engine::scene_args(KArgs& a, bool heatmap) const {
     const SceneSet& scene = sets[live];
     a.bvh = static_cast<const float4*>(scene.bvh.ptr); a.tri_attr = static_cast<const float4*>(scene.tri_attr.ptr); a.instance_xforms = static_cast<const float4*>(scene.xforms.ptr);
-    a.materials = static_cast<const GpuMaterial*>(scene.materials.ptr); a.material_base_packed = tuning.packed_base ? static_cast<const uint32_t*>(scene.base_packed.ptr) : nullptr; a.lights = static_cast<const GpuLight*>(light_sets[live_lights].buf.ptr);
-    a.atlas = static_cast<const uchar4*>(d_atlas.ptr); a.blue_noise = static_cast<const uchar4*>(d_blue_noise.ptr); a.byte_luts = static_cast<const float*>(d_byte_luts.ptr);
-    a.transmittance_lut = static_cast<const float4*>(d_transmittance.ptr); a.sky_lut = static_cast<const float4*>(d_sky.ptr);
+    a.materials = static_cast<const GpuMaterial*>(scene.materials.ptr); a.material_base_packed = tuning.packed_base ? static_cast<const uint32_t*>(scene.base_packed.ptr) : nullptr;
+    a.atlas = static_cast<const uchar4*>(d_atlas.ptr); a.byte_luts = static_cast<const float*>(d_byte_luts.ptr);
     a.tri_slots = (uint32_t)(tri_geo.size() / 3u);
     a.count_bytes = count_bytes ? 1u : 0u;
     a.exp_flags = exp_flags;
@@ -124,7 +114,7 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
     a.bvh_c_root = (compact && device_root_is_leaf) ? 1u : 0u;
     // ... or, preferred, its wide form (k_bvh.hip k_bvh_wide)
     // (ST_BVH_BUILD_DEVICE: this copy's wide stream was built on the device and its contract stream is stale — every ray must walk the wide stream)
-    const bool contract_observer = arithmetic != ST_ARITH_FAST || !tuning.wide_bvh || !tuning.compact_bvh || !tuning.anyhit_fast || count_bytes || c.desc.mode == ST_MODE_BVH_HEATMAP;
+    const bool contract_observer = arithmetic != ST_ARITH_FAST || !tuning.wide_bvh || !tuning.compact_bvh || !tuning.anyhit_fast || count_bytes || heatmap;
     if (scene.device_built && contract_observer)
         return fail(ST_ERR_INVALID_ARGUMENT, "the live scene copy's tree was built on the device (ST_BVH_BUILD_DEVICE) and this frame needs the contract stream (heatmap camera, exact arithmetic, "
                                              "byte counting or a switched-off wide stream): st_tick builds it on the host once it sees the observer");
@@ -149,8 +139,31 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
     // A walk that does find the stack full says so (KArgs::walk_flags) and the next st_tick re-arms the launches with a deeper one (st_engine.h walk_flags_host).
     a.stack_entries = wide ? wide_stack_entries_now() : stack_entries;
     a.bvh_len = scene.device_built ? 0x40000000u : device_bvh_len;   // (device-built: no contract stream; any value that is neither "empty" nor "fits LDS")
-    if (scene.device_built) a.bvh = nullptr; a.n_lights_buf = (uint32_t)gpu_lights.size(); a.light_count = light_count;
-    a.atlas_w = atlas_w; a.atlas_h = atlas_h; a.sun_altitude = sun_altitude;
+    if (scene.device_built) a.bvh = nullptr;
+    a.atlas_w = atlas_w; a.atlas_h = atlas_h;
+    return ST_OK;
+}
+
+// ---- render (camera_controller.rs:87-174)
+int Engine::render(CameraState& c, void* out, hipStream_t stream) {
+    if (!has_device) return fail(ST_ERR_NO_DEVICE, "render_camera on a host-only engine");
+    if (!scene_uploaded) return fail(ST_ERR_INVALID_ARGUMENT, "st_tick must precede st_render_camera");
+    ST_HIP(hipSetDevice(device));
+    if (tick_work_in_flight) ST_HIP(hipStreamWaitEvent(stream, ev_tick, 0));  // a no-op when st_tick ran on this stream
+    if (copy_in_flight) ST_HIP(hipStreamWaitEvent(stream, ev_copy, 0));       // likewise (st_tick already queued this wait on its own stream)
+    if (rendered_before && last_render_stream != stream) mixed_render_streams = true;  // the null stream is a stream too
+    last_render_stream = stream; rendered_before = true;
+    const bool alt = c.frame % 2u == 1u;
+    c.last_lean = 0u; c.last_lean_composed = false;
+    KArgs a{};
+    a.cam = c.curr; a.prev_cam = c.prev;
+    if (int rc = scene_args(a, c.desc.mode == ST_MODE_BVH_HEATMAP)) return rc;
+    c.shown = c.curr; c.shown_width = c.desc.width; c.shown_height = c.desc.height; c.has_shown = true;   // what st_camera_pick casts through
+    a.lights = static_cast<const GpuLight*>(light_sets[live_lights].buf.ptr);
+    a.blue_noise = static_cast<const uchar4*>(d_blue_noise.ptr);
+    a.transmittance_lut = static_cast<const float4*>(d_transmittance.ptr); a.sky_lut = static_cast<const float4*>(d_sky.ptr);
+    a.n_lights_buf = (uint32_t)gpu_lights.size(); a.light_count = light_count;
+    a.sun_altitude = sun_altitude;
     a.sun_dir[0] = sun_dir_.x; a.sun_dir[1] = sun_dir_.y; a.sun_dir[2] = sun_dir_.z;
     auto P = [&](int id) { return c.plane[id]; };
     a.g0 = P(alt ? ST_BUF_PRIM_GBUFFER_D0_B : ST_BUF_PRIM_GBUFFER_D0_A); a.pg0 = P(alt ? ST_BUF_PRIM_GBUFFER_D0_A : ST_BUF_PRIM_GBUFFER_D0_B);

@@ -337,6 +337,9 @@ int Engine::tick(hipStream_t stream) {
             }
             t.dirty_lo = SIZE_MAX; t.dirty_hi = 0; t.tri_full = false; t.valid = true;
             if ((rc = t.xforms.upload(instance_xforms.data(), instance_xforms.size() * sizeof(float4), up, staging, flag))) return rc;
+            // the scene queries' handle table follows the slots of this copy (a spawn, a despawn, a re-inserted mesh move triangle ranges)
+            fill_instance_table();
+            if ((rc = t.instance_table.upload(instance_table_.data(), instance_table_.size() * sizeof(uint32_t), up, staging, flag))) return rc;
             if ((rc = t.materials.upload(gpu_materials.data(), gpu_materials.size() * sizeof(GpuMaterial), up, staging, flag))) return rc;
             if ((rc = t.base_packed.upload(material_base_packed.data(), material_base_packed.size() * sizeof(uint32_t), up, staging, flag))) return rc;
             if (other_copy) copied_now = true;
