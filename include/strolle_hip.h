@@ -273,6 +273,39 @@ int st_camera_pick(StEngine* e, StHandle camera, const uint32_t* pixels_xy_devic
 /* Blocking convenience: host arrays in and out (staged through engine-owned buffers on a stream of the engine's own). */
 int st_scene_trace_rays_host(StEngine* e, const StRay* rays, uint32_t count, StRayHit* hits);
 
+/* ---- per-pixel AOVs (NEW seam): what an external denoiser, a temporal upscaler or an editor asks of each pixel besides its colour
+ * (k_aov.hip). One launch writes every requested plane; each plane is device memory of the engine's device, width x height
+ * elements in row-major order (y * width + x), of the element type given per kind below.
+ * Pixel ray. Pixel (x, y) is the camera ray (Camera::ray, the pixel centre) of the camera as its last st_render_camera saw it, as
+ *   st_camera_pick casts it: the frame on screen, not a later st_camera_update. A camera that has not rendered yet uses its
+ *   current description. width x height is that frame's size.
+ * Previous camera. MOTION compares with the camera of the frame before that one, exactly as that render's velocity plane did.
+ * Scene. The scene of the last st_tick, enqueued on `hip_stream` after that tick's uploads (as queries are); the call returns at
+ *   once, like st_render_camera. It works in every camera mode (Reference and BVH heatmap included): it casts its own rays.
+ * Tiles. The camera's window (st_camera_set_window, st_dist_set_partition) is honoured: only pixels inside it are written, the
+ *   rest of every plane is left as it was, so a rank of a tiled frame produces its own tile's AOVs.
+ * Sky. A pixel whose ray hits nothing gets the value each kind gives for the sky.
+ * Errors. A host-only engine returns ST_ERR_NO_DEVICE. A call before the first st_tick, a null `targets`, a wrong struct_size
+ *   or no plane requested is ST_ERR_INVALID_ARGUMENT; an unknown camera is ST_ERR_UNKNOWN_CAMERA. In the exact build
+ *   (ST_ARITH_EXACT) a live scene copy whose tree was built on the device is ST_ERR_INVALID_ARGUMENT, as for the queries.
+ * Stack overflow. A walk whose stack overflows sets the engine's sticky walk word, as the queries do. */
+enum StAovKind {
+    ST_AOV_DEPTH = 0,     /* f32:  distance from the camera ray's origin to the hit (the G-buffer's depth, d0.x); FLT_MAX on sky */
+    ST_AOV_NORMAL = 1,    /* f32x4: shading normal as StRayHit.normal (xyz), w = 0; 0 on sky */
+    ST_AOV_ALBEDO = 2,    /* f32x4: linear base colour at the hit's uv, texture applied (what primary visibility samples), alpha in w; 0 on sky */
+    ST_AOV_MOTION = 3,    /* f32x2: the renderer's velocity (current minus previous screen position in pixels, instance motion included;
+                           * 0 where its squared length is below 0.001, as the velocity plane); 0 on sky */
+    ST_AOV_INSTANCE = 4,  /* u64:  st_instance_insert handle; 0 on sky */
+    ST_AOV_TRIANGLE = 5,  /* u32:  index into the mesh's st_mesh_insert array; 0xffffffff on sky */
+    ST_AOV_COUNT = 6
+};
+typedef struct StAovTargets {         /* 56 B */
+    uint32_t struct_size;             /* sizeof(StAovTargets) */
+    uint32_t _pad;
+    void* planes[ST_AOV_COUNT];       /* indexed by StAovKind: device pointers, width x height elements each; NULL = not wanted */
+} StAovTargets;
+int st_camera_render_aovs(StEngine* e, StHandle camera, const StAovTargets* targets, void* hip_stream);
+
 /* ---- multi-GPU behind the boundary (NEW seam; SURVEY.md section 8e, BASELINE.json configs 4 and 5). One process per GPU, one
  * engine per process, the scene replicated; the frame is cut into tiles, every rank renders its tile (+ an apron of redundant
  * pixels in Image mode, whose passes read neighbours) with absolute pixel coordinates, and the ONE collective of the path

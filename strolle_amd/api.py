@@ -118,6 +118,47 @@ HIT_DTYPE = np.dtype([("point", "<f4", (3,)), ("t", "<f4"), ("normal", "<f4", (3
 RAY_COHERENT = 1   # ST_RAY_COHERENT
 
 
+class Aov(enum.IntEnum):
+    """StAovKind: the per-pixel AOV planes of st_camera_render_aovs (include/strolle_hip.h "per-pixel AOVs")."""
+    DEPTH = 0      # f32: distance from the camera ray's origin to the hit; FLT_MAX on sky
+    NORMAL = 1     # f32x4: shading normal (xyz), w = 0; 0 on sky
+    ALBEDO = 2     # f32x4: linear base colour at the hit, texture applied, alpha in w; 0 on sky
+    MOTION = 3     # f32x2: the renderer's velocity (current minus previous screen position); 0 on sky
+    INSTANCE = 4   # u64: st_instance_insert handle; 0 on sky
+    TRIANGLE = 5   # u32: index into the mesh's st_mesh_insert array; 0xffffffff on sky
+
+
+AOV_COUNT = 6
+
+
+class StAovTargets(C.Structure):
+    """include/strolle_hip.h StAovTargets (56 B): one device pointer per Aov, width x height elements, row-major; NULL = not wanted."""
+    _fields_ = [("struct_size", C.c_uint32), ("_pad", C.c_uint32), ("planes", C.c_void_p * AOV_COUNT)]
+
+
+# element of one pixel of each plane: (numpy scalar type, components per pixel)
+AOV_ELEMENT = {Aov.DEPTH: (np.float32, 1), Aov.NORMAL: (np.float32, 4), Aov.ALBEDO: (np.float32, 4), Aov.MOTION: (np.float32, 2),
+               Aov.INSTANCE: (np.uint64, 1), Aov.TRIANGLE: (np.uint32, 1)}
+
+
+def aov_planes(size, kinds=tuple(Aov), device="cuda", fill=None) -> dict:
+    """Torch planes for Engine.render_aovs of a camera of `size` = (width, height) (or a Camera): {Aov: tensor of shape (height,
+    width[, components])} on `device`, typed as the header says. fill=None leaves them uninitialised; otherwise every element is `fill`."""
+    import torch
+    w, h = (size.size if isinstance(size, Camera) else size)
+    dtypes = {np.float32: torch.float32, np.uint64: torch.uint64, np.uint32: torch.uint32}
+    out = {}
+    for k in kinds:
+        k = Aov(k)
+        scalar, comps = AOV_ELEMENT[k]
+        shape = (int(h), int(w)) if comps == 1 else (int(h), int(w), comps)
+        t = torch.empty(shape, dtype=dtypes[scalar], device=device)
+        if fill is not None:
+            t.fill_(fill)
+        out[k] = t
+    return out
+
+
 class StrolleError(RuntimeError):
     pass
 
@@ -372,6 +413,8 @@ class _Binding:
                 self.scene_occluded = fn("scene_occluded", [vp, vp, u32, vp, vp])
                 self.camera_pick = fn("camera_pick", [vp, u64, vp, u32, vp, vp])
                 self.scene_trace_rays_host = fn("scene_trace_rays_host", [vp, vp, u32, vp])
+            if hasattr(lib, prefix + "camera_render_aovs"):   # per-pixel AOVs (likewise absent from an older library)
+                self.camera_render_aovs = fn("camera_render_aovs", [vp, u64, P(StAovTargets), vp])
             self.profile_enable = fn("profile_enable", [vp, i32])
             self.profile_read = fn("profile_read", [vp, P(StKernelProfile), sz, P(sz), i32])
             self.last_error = getattr(lib, prefix + "last_error"); self.last_error.restype = C.c_char_p; self.last_error.argtypes = []
@@ -693,6 +736,26 @@ class Engine(EngineBase):
         """st_camera_pick: `count` (x, y) uint32 pairs at `pixels_ptr` -> StRayHit at `hits_ptr`, through the camera as its last
         render saw it."""
         self._check(self._b.camera_pick(self._h, camera, pixels_ptr, count, hits_ptr, stream))
+
+    def render_aovs(self, camera: int, planes: dict, stream=None):
+        """st_camera_render_aovs: {Aov: device address or torch tensor} -> the camera's per-pixel AOVs of the frame on screen, enqueued on
+        `stream` (a HIP stream handle, a torch stream, or None = the null stream). Planes are width x height elements, row-major;
+        aov_planes() allocates them. Only the camera's window is written."""
+        t = StAovTargets(); t.struct_size = C.sizeof(StAovTargets)
+        for k, v in planes.items():
+            k = Aov(k)
+            if v is None:
+                continue
+            if hasattr(v, "data_ptr"):
+                scalar, comps = AOV_ELEMENT[k]
+                per_pixel = v.shape[-1] if comps > 1 and v.dim() > 0 else comps
+                if not v.is_contiguous() or v.element_size() != np.dtype(scalar).itemsize or per_pixel != comps:
+                    raise StrolleError(f"AOV plane {k.name}: expected a contiguous tensor of {comps} x {np.dtype(scalar).name} per pixel")
+                v = v.data_ptr()
+            t.planes[int(k)] = int(v)
+        if stream is not None and hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        self._check(self._b.camera_render_aovs(self._h, camera, C.byref(t), stream or 0))
 
     def trace_rays_host(self, rays: np.ndarray) -> np.ndarray:
         """st_scene_trace_rays_host: a RAY_DTYPE array in host memory -> a HIT_DTYPE array (blocking)."""

@@ -1,0 +1,67 @@
+// k_aov.hip — per-pixel AOVs (include/strolle_hip.h "per-pixel AOVs"; st_query.cpp Engine::render_aovs): depth, shading normal, base colour,
+// motion vector and instance / triangle identity of the camera ray of every owned pixel, in one launch over the frame's 8x8 tiles (each wave
+// holds one tile's 64 coherent primary rays, as in k_prim_visibility). The walk is k_query_pick's, the attributes are closest_resolve's; albedo
+// and motion are k_prim_visibility's own formulas. The three instantiations of ST_LAUNCH_TRACE with the frame's dynamic LDS stack. A plane
+// the caller did not ask for is a null pointer here: its branch is uniform over the launch and costs neither the load nor the store.
+#include "k_common.h"
+
+namespace st {
+namespace ST_KNS {
+
+// KArgs::cam / prev_cam / width / height: the camera of the frame on screen and the one before it; row0..col1: its window (st_query.cpp).
+// The planes are width x height, row-major; only owned pixels are written.
+template <bool LDS_SCENE, class SE>
+__global__ ST_KERNEL_BOUNDS void k_aov(const KArgs a_in, float* depth, float4* normal, float4* albedo, float2* motion, uint64_t* instance,
+                                       uint32_t* triangle, const uint4* table) {
+    ST_QUERY_PROLOGUE
+    ST_STACK_LDS(SE, lds);
+    U2 pos;
+    if (!resolve_gid(a, false, &pos) || !owns_pixel(a, pos)) return;
+    const Ray ray = camera_ray(a.cam, pos);
+    Candidate c; candidate_none(&c);
+    bool any = false;
+#if ST_FAST_DEVICE && !defined(ST_NO_ANYHIT_FAST)
+    if (!LDS_SCENE && a.bvh_w != nullptr && a.primary_packets) any = closest_hit_packet(a, ray, &c);   // the tile's 64 rays as one packet
+    else if (a.bvh_w != nullptr) any = closest_hit_wide<SE, true>(a, ray, lane_stack(a, lds), &c);
+    else if (a.bvh_c != nullptr) any = closest_hit_compact(a, ray, lane_stack(a, lds), &c);
+    else (void)traverse<false>(a, ray, kF32Max, lane_stack(a, lds), &c, &any);
+#else
+    (void)traverse<false>(a, ray, kF32Max, lane_stack(a, lds), &c, &any);
+#endif
+    const TriangleHit h = closest_resolve(a, ray, c, any);
+    const size_t i = (size_t)pos.y * a.width + pos.x;
+    if (depth) depth[i] = any ? distance(ray.origin, h.point) : kF32Max;   // the G-buffer's d0.x (k_prim_visibility g.depth)
+    if (normal) normal[i] = any ? make_float4(h.normal.x, h.normal.y, h.normal.z, 0.0f) : f4z();
+    if (albedo) {
+        float4 base = f4z();
+        if (any) {
+            const GpuMaterial& m = a.materials[h.material_id];
+            base = sample_atlas(a, h.uv, m.base_color, m.base_color_texture);
+        }
+        albedo[i] = base;
+    }
+    if (motion) {   // prim_raster.rs:21-27 as k_prim_visibility computes the velocity plane
+        float2 mv = make_float2(0.0f, 0.0f);
+        if (any) {
+            const float4* xf = a.instance_xforms + 8u * h.xform_slot;
+            const V3 prev_point = affine_point(xf + 4, affine_point(xf, h.point));
+            const V2 velocity = clip_to_screen(a.cam, world_to_clip(a.cam, h.point)) - clip_to_screen(a.prev_cam, world_to_clip(a.prev_cam, prev_point));
+            if (dot(velocity, velocity) >= 0.001f) mv = make_float2(velocity.x, velocity.y);
+        }
+        motion[i] = mv;
+    }
+    if (instance || triangle) {
+        uint4 rec = make_uint4(0u, 0u, 0u, 0u);   // {handle lo, hi, first triangle slot of the instance, 0}
+        if (any) rec = table[h.xform_slot];
+        if (instance) instance[i] = any ? ((uint64_t)rec.y << 32 | rec.x) : 0ull;
+        if (triangle) triangle[i] = any ? c.tri - rec.z : 0xffffffffu;
+    }
+}
+
+void launch_aov(const KArgs& a, float* depth, float4* normal, float4* albedo, float2* motion, uint64_t* instance, uint32_t* triangle, const uint4* table,
+                hipStream_t s) {
+    ST_LAUNCH_TRACE(k_aov, false, s, a, depth, normal, albedo, motion, instance, triangle, table);
+}
+
+}  // namespace ST_KNS
+}  // namespace st

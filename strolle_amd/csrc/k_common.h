@@ -105,6 +105,17 @@ inline bool scene_fits_lds(const KArgs& a) { return a.bvh_len > 0u && a.bvh_len 
         a.lights_lds = s_lights_;                                                                                                \
         if (LDS_SCENE) a.bvh = s_scene_bvh_;                                                                                     \
     }
+// ST_SCENE_PROLOGUE without the light table: the scene queries and the AOVs (k_query.hip, k_aov.hip), which read no light
+#define ST_QUERY_PROLOGUE                                                                                            \
+    __shared__ float4 s_scene_bvh_[LDS_SCENE ? kLdsSceneTexels : 1];                                                 \
+    KArgs a = a_in;                                                                                                  \
+    if (LDS_SCENE) {                                                                                                 \
+        for (uint32_t i_ = threadIdx.x; i_ < a_in.bvh_len; i_ += kBlockThreads) s_scene_bvh_[i_] = a_in.bvh[i_];     \
+        __syncthreads();                                                                                             \
+        a.bvh = s_scene_bvh_;                                                                                        \
+    }
+// the empty closest-hit candidate the queries and the AOVs start their walks from
+ST_D void candidate_none(Candidate* c) { c->t = kF32Max; c->tri = 0xffffffffu; c->material = 0u; c->u = 0.0f; c->v = 0.0f; c->inv_det = 1.0f; }
 // For a kernel that decodes MANY G-buffer texels per lane (GI spatial resampling: every candidate neighbour's): the byte tables of the
 // decode (st_device.h kLut*, 4 KB) staged in LDS as well — seven per-lane table reads per decoded texel leave the texture-address path
 // (dungeon gi_spatial_fused 366 -> 335 us; in the kernels that decode one pixel the staging costs what it saves, measured).

@@ -7,16 +7,6 @@
 namespace st {
 namespace ST_KNS {
 
-// ST_SCENE_PROLOGUE without the light table
-#define ST_QUERY_PROLOGUE                                                                                            \
-    __shared__ float4 s_scene_bvh_[LDS_SCENE ? kLdsSceneTexels : 1];                                                 \
-    KArgs a = a_in;                                                                                                  \
-    if (LDS_SCENE) {                                                                                                 \
-        for (uint32_t i_ = threadIdx.x; i_ < a_in.bvh_len; i_ += kBlockThreads) s_scene_bvh_[i_] = a_in.bvh[i_];     \
-        __syncthreads();                                                                                             \
-        a.bvh = s_scene_bvh_;                                                                                        \
-    }
-
 // StRay (2 float4: origin, t_max; direction, pad) -> Ray with len = t_max. false: a miss by contract (t_max <= 0 or NaN, an all-zero direction).
 ST_D bool query_ray(const float4* rays, uint32_t i, Ray* ray) {
     const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1];
@@ -24,7 +14,6 @@ ST_D bool query_ray(const float4* rays, uint32_t i, Ray* ray) {
     ray->len = r0.w;
     return r0.w > 0.0f && !(r1.x == 0.0f && r1.y == 0.0f && r1.z == 0.0f);
 }
-ST_D void candidate_none(Candidate* c) { c->t = kF32Max; c->tri = 0xffffffffu; c->material = 0u; c->u = 0.0f; c->v = 0.0f; c->inv_det = 1.0f; }
 // StRayHit (4 float4) of ray i, written whole by its lane: {point, t} {normal, triangle} {uv, u, v} {instance lo, hi, hit, 0}
 ST_D void store_hit(float4* hits, uint32_t i, const TriangleHit& h, const Candidate& c, bool hit, const uint4* table) {
     float4 o0 = make_float4(0.0f, 0.0f, 0.0f, kF32Max), o1 = f4z(), o2 = f4z(), o3 = f4z();

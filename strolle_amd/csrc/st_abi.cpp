@@ -275,6 +275,18 @@ int st_scene_trace_rays_host(StEngine* e, const StRay* rays, uint32_t count, StR
     ST_REQUIRE(rays && hits, "null argument");
     return E(e)->trace_rays_host(rays, count, hits);
 }
+// per-pixel AOVs (st_aov.cpp): the argument checks come first here too
+int st_camera_render_aovs(StEngine* e, StHandle h, const StAovTargets* targets, void* stream) {
+    ST_REQUIRE(e, "null engine");
+    ST_REQUIRE(targets, "null targets");
+    ST_REQUIRE(targets->struct_size == sizeof(StAovTargets), "StAovTargets.struct_size is not sizeof(StAovTargets)");
+    bool any = false;
+    for (int k = 0; k < ST_AOV_COUNT; k++) any |= targets->planes[k] != nullptr;
+    ST_REQUIRE(any, "no AOV plane requested");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    return E(e)->render_aovs(*it->second, *targets, static_cast<hipStream_t>(stream));
+}
 
 int st_debug_keep_all_planes(StEngine* e, int keep) { ST_REQUIRE(e, "null engine"); E(e)->tuning.lean_frame = keep == 0 ? 1u : 0u; return ST_OK; }
 int st_camera_present_copy(StEngine* e, StHandle h, const void* src_device, void* dst_host, size_t bytes, void* stream) {

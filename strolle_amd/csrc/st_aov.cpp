@@ -1,0 +1,21 @@
+// st_aov.cpp — host engine of libstrolle_hip.so: per-pixel AOVs (include/strolle_hip.h "per-pixel AOVs"; k_aov.hip). A reader of the live
+// scene copy like the scene queries (query_begin / query_end, st_query.cpp), through the camera of the frame on screen and its window.
+#include "st_engine.h"
+
+namespace st {
+
+int Engine::render_aovs(const CameraState& c, const StAovTargets& t, hipStream_t stream) {
+    KArgs a;
+    if (int rc = query_begin(stream, a, true)) return rc;
+    // the frame on screen (render() records shown / shown_prev); before the first render, what the next render would cast through
+    a.cam = c.has_shown ? c.shown : c.curr; a.prev_cam = c.has_shown ? c.shown_prev : c.prev;
+    a.width = c.has_shown ? c.shown_width : c.desc.width; a.height = c.has_shown ? c.shown_height : c.desc.height;
+    a.row0 = c.row0; a.row1 = c.row1; a.col0 = c.col0; a.col1 = c.col1;
+    a.tile_map = tuning.tile_map;
+    L.launch_aov(a, static_cast<float*>(t.planes[ST_AOV_DEPTH]), static_cast<float4*>(t.planes[ST_AOV_NORMAL]), static_cast<float4*>(t.planes[ST_AOV_ALBEDO]),
+                 static_cast<float2*>(t.planes[ST_AOV_MOTION]), static_cast<uint64_t*>(t.planes[ST_AOV_INSTANCE]), static_cast<uint32_t*>(t.planes[ST_AOV_TRIANGLE]),
+                 static_cast<const uint4*>(sets[live].instance_table.ptr), stream);
+    return query_end(stream, true);
+}
+
+}  // namespace st

@@ -277,6 +277,7 @@ struct CameraState {
     uint32_t present_next = 0;
     // the camera as the last render saw it (st_camera_pick casts through the frame on screen, not a later st_camera_update)
     GpuCamera shown{}; uint32_t shown_width = 0, shown_height = 0; bool has_shown = false;
+    GpuCamera shown_prev{};   // ... and the camera of the frame before it (that render's KArgs::prev_cam: st_camera_render_aovs' MOTION)
 };
 inline size_t plane_texels_per_pixel(int id) {
     if (id >= ST_BUF_DI_RESERVOIRS_0 && id <= ST_BUF_DI_RESERVOIRS_2) return 2;
@@ -587,6 +588,7 @@ struct Engine {
     int occluded(const void* rays, uint32_t count, uint32_t* out, hipStream_t stream);
     int pick(const CameraState& c, const uint32_t* pixels, uint32_t count, void* hits, hipStream_t stream);
     int trace_rays_host(const void* rays, uint32_t count, void* hits);
+    int render_aovs(const CameraState& c, const StAovTargets& t, hipStream_t stream);   // per-pixel AOVs (st_aov.cpp)
     hipStream_t query_stream = nullptr; DeviceArray d_query_rays, d_query_hits; void* query_pinned = nullptr; size_t query_pinned_bytes = 0;
 };
 

@@ -67,3 +67,5 @@ ST_LAUNCHER(launch_bvh_wide, (const float4* bvh, const uint32_t* topo, uint32_t 
 ST_LAUNCHER(launch_query_closest, (const KArgs& a, const float4* rays, uint32_t count, float4* hits, const uint4* table, uint32_t packets, hipStream_t s))
 ST_LAUNCHER(launch_query_occluded, (const KArgs& a, const float4* rays, uint32_t count, uint32_t* occluded, hipStream_t s))
 ST_LAUNCHER(launch_query_pick, (const KArgs& a, const uint32_t* pixels, uint32_t count, float4* hits, const uint4* table, hipStream_t s))
+// per-pixel AOVs (k_aov.hip; st_aov.cpp): over the window's 8x8 tiles like the frame's passes; each plane width x height, nullptr = not requested
+ST_LAUNCHER(launch_aov, (const KArgs& a, float* depth, float4* normal, float4* albedo, float2* motion, uint64_t* instance, uint32_t* triangle, const uint4* table, hipStream_t s))

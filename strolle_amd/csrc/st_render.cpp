@@ -158,7 +158,7 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
     KArgs a{};
     a.cam = c.curr; a.prev_cam = c.prev;
     if (int rc = scene_args(a, c.desc.mode == ST_MODE_BVH_HEATMAP)) return rc;
-    c.shown = c.curr; c.shown_width = c.desc.width; c.shown_height = c.desc.height; c.has_shown = true;   // what st_camera_pick casts through
+    c.shown = c.curr; c.shown_prev = c.prev; c.shown_width = c.desc.width; c.shown_height = c.desc.height; c.has_shown = true;   // what st_camera_pick casts through
     a.lights = static_cast<const GpuLight*>(light_sets[live_lights].buf.ptr);
     a.blue_noise = static_cast<const uchar4*>(d_blue_noise.ptr);
     a.transmittance_lut = static_cast<const float4*>(d_transmittance.ptr); a.sky_lut = static_cast<const float4*>(d_sky.ptr);
