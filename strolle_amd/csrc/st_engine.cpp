@@ -74,7 +74,8 @@ void Engine::note_walk_overflow() {
     if (packet) packets_overflowed = true;
     if (lane) {
         const uint32_t now = wide_stack_entries_now();
-        wide_stack_rearmed = now < 32u ? 32u : (now < 48u ? 48u : 56u);   // 56: what 64 KB of dynamic LDS hold with 32-bit slots
+        // 56: what 64 KB of dynamic LDS hold with 32-bit slots. (finding 3: an overflow at 56 re-arms 56 again, and every later tick reports it)
+        wide_stack_rearmed = now < 32u ? 32u : (now < 48u ? 48u : 56u);
     }
 }
 void Engine::reset_profile_totals() {
@@ -91,10 +92,10 @@ Engine::~Engine() {
     (void)hipDeviceSynchronize();
     for (auto& kv : cameras) release_camera(*kv.second);
     for (DeviceArray* d : {&d_byte_luts, &d_atlas, &d_blue_noise, &d_transmittance, &d_scattering, &d_sky, &d_mesh_store}) d->release();
-    for (LightSet& l : light_sets) { l.buf.release(); if (l.free_ev) (void)hipEventDestroy(l.free_ev); }
+    for (LightSet& l : light_sets) { l.buf.release(); l.fence.release(); }
     for (SceneSet& t : sets) {
         for (DeviceArray* d : {&t.bvh, &t.tri_attr, &t.xforms, &t.materials, &t.base_packed, &t.tri_geo, &t.tri_bounds, &t.entry_of_tri, &t.parent, &t.refit_local, &t.refit_items, &t.refit_batch_off, &t.bvh_compact, &t.tri_info, &t.lb_keys_a, &t.lb_keys_b, &t.lb_temp, &t.lb_seg, &t.lb_children, &t.lb_node_box, &t.lb_small, &t.bvh_wide, &t.wide_topo, &t.wide_leaf_entry, &t.bake_jobs, &t.bake_starts, &t.instance_table}) d->release();
-        if (t.free_ev) (void)hipEventDestroy(t.free_ev);
+        t.fence.release();
     }
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
     if (query_stream) (void)hipStreamDestroy(query_stream);

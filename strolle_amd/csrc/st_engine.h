@@ -32,6 +32,9 @@ namespace st {
 
 extern thread_local std::string g_last_error;  // st_engine.cpp
 inline int fail(int status, const std::string& msg) { g_last_error = msg; return status; }
+// StTuning::tick_timing's clock: the milliseconds between two readings of TickClock::now()
+using TickClock = std::chrono::steady_clock;
+inline double ms_between(TickClock::time_point a, TickClock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
 
 #define ST_HIP(call)                                                                                      \
     do {                                                                                                  \
@@ -218,12 +221,16 @@ struct DeviceArray {
     void* ptr = nullptr; size_t capacity = 0;
     // `pageable` is set when the copy had to be issued straight from `src`: the caller joins the stream before `src` changes
     int upload(const void* src, size_t bytes, hipStream_t stream, StagingRing& ring, bool* pageable) {
-        if (bytes > capacity) {
-            if (ptr) ST_HIP(hipFree(ptr));
-            capacity = std::max<size_t>(bytes * 3 / 2, 4096);
-            ST_HIP(hipMalloc(&ptr, capacity));
-        }
+        if (int rc = reserve(bytes, std::max<size_t>(bytes * 3 / 2, 4096))) return rc;
         return upload_range(src, 0, bytes, stream, ring, pageable);
+    }
+    // room for `bytes`: a smaller allocation is replaced by one of `alloc` bytes (what it held is not kept)
+    int reserve(size_t bytes, size_t alloc) {
+        if (bytes <= capacity) return ST_OK;
+        if (ptr) ST_HIP(hipFree(ptr));
+        ptr = nullptr; capacity = 0;
+        ST_HIP(hipMalloc(&ptr, alloc)); capacity = alloc;
+        return ST_OK;
     }
     // part of an array that is already on the device: bytes [offset, offset + bytes) of `base`
     int upload_range(const void* base, size_t offset, size_t bytes, hipStream_t stream, StagingRing& ring, bool* pageable) {
@@ -235,6 +242,17 @@ struct DeviceArray {
         return ST_OK;
     }
     void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; capacity = 0; }
+};
+
+// The hand-over of a double-buffered device copy (Engine::SceneSet, LightSet): busy = reads were enqueued since it was written; free_ev ends the last.
+struct CopyFence {
+    hipEvent_t free_ev = nullptr; bool busy = false;
+    int mark_read(hipStream_t s) {   // the copy is read up to here on `s` (the writer's side: Engine::pick_copy)
+        if (!free_ev) ST_HIP(hipEventCreateWithFlags(&free_ev, hipEventDisableTiming));
+        ST_HIP(hipEventRecord(free_ev, s)); busy = true;
+        return ST_OK;
+    }
+    void release() { if (free_ev) (void)hipEventDestroy(free_ev); free_ev = nullptr; busy = false; }
 };
 
 // ------------------------------------------------------------------ per-camera state (camera_controller/buffers.rs)
@@ -311,8 +329,6 @@ inline int read_counters(const CameraState& c, unsigned long long* host /* 2*KS_
 
 
 struct ProfileRecord { int slot; hipEvent_t start, stop; double bytes; uint32_t launches; bool owns_start; };
-
-struct Light112 { GpuLight g; };
 
 StTuning default_tuning();  // st_engine.cpp
 struct DistState;           // st_dist.cpp: rank / world, transport, per-camera partition
@@ -443,15 +459,18 @@ struct Engine {
         DeviceArray bake_jobs, bake_starts;
         // per instance slot (tri_attr[4 t + 3].w): {StHandle lo, hi, first triangle slot, 0} — the scene queries' instance and mesh triangle (st_query.cpp)
         DeviceArray instance_table;
-        hipEvent_t free_ev = nullptr; bool busy = false;  // busy: frames reading this copy were enqueued since it was written; free_ev ends the last
+        CopyFence fence;
         bool valid = false;
     };
     SceneSet sets[2]; int live = 0;
     // the light table alternates the same way, on its own schedule (a light that moves every frame does not resend the scene)
-    struct LightSet { DeviceArray buf; hipEvent_t free_ev = nullptr; bool busy = false; };
+    struct LightSet { DeviceArray buf; CopyFence fence; };
     LightSet light_sets[2]; int live_lights = 0; bool lights_uploaded = false, lights_alternating = false;
     bool alternating = false, mixed_render_streams = false;
     hipStream_t copy_stream = nullptr, last_render_stream = nullptr; bool rendered_before = false; hipEvent_t ev_copy = nullptr; bool copy_in_flight = false;
+    struct CopyTarget { int index; hipStream_t up; bool* pageable; bool other; };   // the writer's side: st_tick.cpp pick_copy
+    int reader_begin(hipStream_t stream, bool reader);   // the readers' side: st_render.cpp
+    int reader_end(hipStream_t stream, bool lights);
 
     std::unordered_map<uint64_t, std::unique_ptr<CameraState>> cameras; uint64_t next_camera = 0;
 
@@ -528,6 +547,11 @@ struct Engine {
     // One thread: at 134 k triangles the sweep is about a millisecond, less than starting a worker pool for it would buy back.
     void refit_stream() { refit_span(0, bvh_stream.size()); }
     bool device_refit_possible() const { return bvh_refresh_mode == ST_BVH_REFIT_DEVICE && has_device; }
+    std::vector<uint8_t> blend_flags() const { std::vector<uint8_t> b(materials.size()); for (size_t i = 0; i < materials.size(); i++) b[i] = materials[i].alpha_mode == 1u; return b; }
+    // Nothing observes the contract stream (a device-built tree can replace it) while every ray walks the wide stream: the fast build with the
+    // wide stream and what it rests on, no traversal bytes counted (this part: wide_only_tuning) — and no camera draws the heatmap.
+    bool wide_only_tuning() const { return arithmetic == ST_ARITH_FAST && tuning.wide_bvh && tuning.compact_bvh && tuning.anyhit_fast && !count_bytes; }
+    bool heatmap_camera() const { for (const auto& kv : cameras) if (kv.second->desc.mode == ST_MODE_BVH_HEATMAP) return true; return false; }
     // ST_BVH_BUILD_DEVICE: the tree of a changed scene is built on the device (k_lbvh.hip) while nothing observes the contract stream
     bool host_tree_stale = false;    // the host's binned-SAH tree (bvh_stream and everything derived from it) is behind the scene
     uint64_t device_builds = 0, device_tree_refits = 0;   // ticks answered by a device build / by a refit of the device-built tree (moves only)
@@ -554,8 +578,20 @@ struct Engine {
     int build_on_device(SceneSet& t, hipStream_t up, bool* pageable);
     int reserve_device_builder(SceneSet& t, size_t slots, uint32_t live);
     void rebuild_host_tree(bool timing);
-
+    enum TriArrays : unsigned { TRI_GEO = 1u /* hit-test records + bounds */, TRI_ATTR = 2u /* attribute records */ };   // a copy's triangle-slot arrays
+    bool tri_fits(const SceneSet& t, unsigned arrays) const;
+    int upload_tri_slots(SceneSet& t, unsigned arrays, bool whole, hipStream_t up, bool* pageable);
+    enum class TreePlan { none, host_refit, host_rebuild, device_build, device_refit, host_to_observer };
+    struct TickIo { hipStream_t stream; bool pageable = false, pageable_copy = false, copied = false, uploaded = false; };   // copied: on copy_stream; uploaded: on `stream`
     int tick(hipStream_t stream);
+    TreePlan refresh_scene();
+    void refresh_sun_and_lights();
+    int pick_copy(TickIo& io, int live_index, CopyFence& live_fence, CopyFence& other_fence, bool written_before, bool& alternating_now, CopyTarget& c);
+    int upload_scene(TreePlan plan, TickIo& io);
+    int upload_images(TickIo& io);
+    int upload_lights(TickIo& io);
+    int end_uploads(TickIo& io);
+    int report_deep_bvh();
 
     static GpuCamera serialize_camera(const StCamera& c);
     int allocate_camera(CameraState& c);

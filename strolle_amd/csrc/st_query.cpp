@@ -18,30 +18,18 @@ void Engine::fill_instance_table() {
     }
 }
 
-// The part every query shares with render(): the tick's uploads come first, the scene arguments are the frame's. `reader`: the query stays
-// in flight after the call returns and counts as a reader of sets[live] (render() keeps the same books).
+// What every query shares with render(): the frame's scene arguments and reader books. `reader`: in flight after the call returns (it reads no lights).
 int Engine::query_begin(hipStream_t stream, KArgs& a, bool reader) {
     if (!has_device) return fail(ST_ERR_NO_DEVICE, "scene query on a host-only engine");
     if (!scene_uploaded) return fail(ST_ERR_INVALID_ARGUMENT, "st_tick must precede a scene query");
     ST_HIP(hipSetDevice(device));
-    if (tick_work_in_flight) ST_HIP(hipStreamWaitEvent(stream, ev_tick, 0));
-    if (copy_in_flight) ST_HIP(hipStreamWaitEvent(stream, ev_copy, 0));
     a = KArgs{};
     if (int rc = scene_args(a, false)) return rc;
-    if (reader) {
-        if (rendered_before && last_render_stream != stream) mixed_render_streams = true;
-        last_render_stream = stream; rendered_before = true;
-    }
-    return ST_OK;
+    return reader_begin(stream, reader);
 }
 int Engine::query_end(hipStream_t stream, bool reader) {
     ST_HIP(hipGetLastError());
-    if (reader && alternating) {  // the end of the last launch that reads this copy of the scene (as render() records it)
-        SceneSet& l = sets[live];
-        if (!l.free_ev) ST_HIP(hipEventCreateWithFlags(&l.free_ev, hipEventDisableTiming));
-        ST_HIP(hipEventRecord(l.free_ev, stream)); l.busy = true;
-    }
-    return ST_OK;
+    return reader ? reader_end(stream, false) : ST_OK;
 }
 
 int Engine::trace_rays(const void* rays, uint32_t count, void* hits, uint32_t flags, hipStream_t stream, bool reader) {
@@ -77,14 +65,8 @@ int Engine::trace_rays_host(const void* rays, uint32_t count, void* hits) {
     ST_HIP(hipSetDevice(device));
     if (!query_stream) ST_HIP(hipStreamCreateWithFlags(&query_stream, hipStreamNonBlocking));
     const size_t ray_bytes = (size_t)count * sizeof(StRay), hit_bytes = (size_t)count * sizeof(StRayHit);
-    auto grow = [](DeviceArray& d, size_t bytes) -> int {
-        if (bytes <= d.capacity) return ST_OK;
-        d.release();
-        ST_HIP(hipMalloc(&d.ptr, bytes)); d.capacity = bytes;
-        return ST_OK;
-    };
-    if (int rc = grow(d_query_rays, ray_bytes)) return rc;
-    if (int rc = grow(d_query_hits, hit_bytes)) return rc;
+    if (int rc = d_query_rays.reserve(ray_bytes, ray_bytes)) return rc;
+    if (int rc = d_query_hits.reserve(hit_bytes, hit_bytes)) return rc;
     if (query_pinned_bytes < hit_bytes) {   // one page-locked buffer serves both directions (the hits are the larger)
         if (query_pinned) ST_HIP(hipHostFree(query_pinned));
         query_pinned = nullptr; query_pinned_bytes = 0;

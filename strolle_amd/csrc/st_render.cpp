@@ -114,8 +114,7 @@ int Engine::scene_args(KArgs& a, bool heatmap) const {
     a.bvh_c_root = (compact && device_root_is_leaf) ? 1u : 0u;
     // ... or, preferred, its wide form (k_bvh.hip k_bvh_wide)
     // (ST_BVH_BUILD_DEVICE: this copy's wide stream was built on the device and its contract stream is stale — every ray must walk the wide stream)
-    const bool contract_observer = arithmetic != ST_ARITH_FAST || !tuning.wide_bvh || !tuning.compact_bvh || !tuning.anyhit_fast || count_bytes || heatmap;
-    if (scene.device_built && contract_observer)
+    if (scene.device_built && (!wide_only_tuning() || heatmap))
         return fail(ST_ERR_INVALID_ARGUMENT, "the live scene copy's tree was built on the device (ST_BVH_BUILD_DEVICE) and this frame needs the contract stream (heatmap camera, exact arithmetic, "
                                              "byte counting or a switched-off wide stream): st_tick builds it on the host once it sees the observer");
     const bool wide = scene.device_built || (compact && tuning.wide_bvh && scene.wide_for_entries != 0u && scene.wide_for_entries * 4u == device_bvh_len);
@@ -144,15 +143,28 @@ int Engine::scene_args(KArgs& a, bool heatmap) const {
     return ST_OK;
 }
 
+// The reader side of the double-buffered scene and light copies (st_tick.cpp pick_copy is the writer's), for render() and the scene queries.
+int Engine::reader_begin(hipStream_t stream, bool reader) {
+    if (tick_work_in_flight) ST_HIP(hipStreamWaitEvent(stream, ev_tick, 0));  // a no-op when st_tick ran on this stream
+    if (copy_in_flight) ST_HIP(hipStreamWaitEvent(stream, ev_copy, 0));       // likewise (st_tick already queued this wait on its own stream)
+    if (reader) {
+        if (rendered_before && last_render_stream != stream) mixed_render_streams = true;  // the null stream is a stream too
+        last_render_stream = stream; rendered_before = true;
+    }
+    return ST_OK;
+}
+int Engine::reader_end(hipStream_t stream, bool lights) {
+    if (alternating) if (int rc = sets[live].fence.mark_read(stream)) return rc;
+    if (lights && lights_alternating) if (int rc = light_sets[live_lights].fence.mark_read(stream)) return rc;
+    return ST_OK;
+}
+
 // ---- render (camera_controller.rs:87-174)
 int Engine::render(CameraState& c, void* out, hipStream_t stream) {
     if (!has_device) return fail(ST_ERR_NO_DEVICE, "render_camera on a host-only engine");
     if (!scene_uploaded) return fail(ST_ERR_INVALID_ARGUMENT, "st_tick must precede st_render_camera");
     ST_HIP(hipSetDevice(device));
-    if (tick_work_in_flight) ST_HIP(hipStreamWaitEvent(stream, ev_tick, 0));  // a no-op when st_tick ran on this stream
-    if (copy_in_flight) ST_HIP(hipStreamWaitEvent(stream, ev_copy, 0));       // likewise (st_tick already queued this wait on its own stream)
-    if (rendered_before && last_render_stream != stream) mixed_render_streams = true;  // the null stream is a stream too
-    last_render_stream = stream; rendered_before = true;
+    if (int rc = reader_begin(stream, true)) return rc;
     const bool alt = c.frame % 2u == 1u;
     c.last_lean = 0u; c.last_lean_composed = false;
     KArgs a{};
@@ -442,8 +454,7 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
             if (luts_generated_now) { ST_HIP(hipEventRecord(c.ev_setup, stream)); ST_HIP(hipStreamWaitEvent(c.side_stream, c.ev_setup, 0)); }
             // copies st_tick queued without joining the stream (staged uploads, dynamic images): they sit behind frame N on
             // the tick's stream, so a frame that follows a scene change gives up the prim(N+1) / denoiser(N) overlap
-            if (tick_work_in_flight) ST_HIP(hipStreamWaitEvent(c.side_stream, ev_tick, 0));
-            if (copy_in_flight) ST_HIP(hipStreamWaitEvent(c.side_stream, ev_copy, 0));  // independent of frame N: the overlap stays
+            if (int rc = reader_begin(c.side_stream, false)) return rc;  // the tick's uploads: independent of frame N, the overlap stays
             if (c.have_prev_frame_events) ST_HIP(hipStreamWaitEvent(c.side_stream, c.ev_prim_ok, 0));
             cur = c.side_stream;
             do_prim();
@@ -485,16 +496,7 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
         const float4* gi_diff = (dn && (mode == ST_MODE_IMAGE || mode == ST_MODE_GI_DIFFUSE)) ? a.gi_diff_curr_colors : a.gi_diff_samples;
         run(KS_COMPOSITION, ST_PASS_COMPOSITION, [&] { L.launch_composition(a, mode, di_diff, gi_diff, out, c.out_format, cur); });
     }
-    if (alternating) {  // the end of the last frame that reads this copy of the scene
-        SceneSet& l = sets[live];
-        if (!l.free_ev) ST_HIP(hipEventCreateWithFlags(&l.free_ev, hipEventDisableTiming));
-        ST_HIP(hipEventRecord(l.free_ev, stream)); l.busy = true;
-    }
-    if (lights_alternating) {
-        LightSet& l = light_sets[live_lights];
-        if (!l.free_ev) ST_HIP(hipEventCreateWithFlags(&l.free_ev, hipEventDisableTiming));
-        ST_HIP(hipEventRecord(l.free_ev, stream)); l.busy = true;
-    }
+    if (int rc = reader_end(stream, true)) return rc;   // the end of the last frame that reads these copies of the scene and the lights
     profile_close();
     ST_HIP(hipGetLastError());
     if (mask_split) return fail(ST_ERR_INVALID_ARGUMENT, "the pass mask splits a fused launch (st_debug_last_launches lists the launch groups)");

@@ -131,7 +131,7 @@ void Engine::bake(const StMeshTriangle& t, const InstanceRec& inst, uint32_t mat
 // Baking (instances.rs:100-139) writes disjoint slots and reads nothing it writes, so once every range is assigned — the arrays
 // do not move any more — large refreshes are spread over the BVH builder's worker pool in chunks.
 void Engine::bake_jobs_on_host(const std::vector<BakeJob>& jobs, size_t total) {
-    const auto tb0 = std::chrono::steady_clock::now();
+    const auto tb0 = TickClock::now();
     constexpr size_t kChunk = 2048, kParallelFrom = 16384;
     unsigned threads = std::thread::hardware_concurrency();
     if (threads > 16u) threads = 16u;
@@ -147,7 +147,7 @@ void Engine::bake_jobs_on_host(const std::vector<BakeJob>& jobs, size_t total) {
             }
         pool.finish();
     }
-    if (tuning.tick_timing) fprintf(stderr, "[bake] %zu triangles in %zu jobs: %.2f ms\n", total, jobs.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count());
+    if (tuning.tick_timing) fprintf(stderr, "[bake] %zu triangles in %zu jobs: %.2f ms\n", total, jobs.size(), ms_between(tb0, TickClock::now()));
 }
 
 // Instances the device has moved (StTuning::device_bake) are baked on the host only when the host arrays are needed again: a rebuild
