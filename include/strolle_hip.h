@@ -306,6 +306,39 @@ typedef struct StAovTargets {         /* 56 B */
 } StAovTargets;
 int st_camera_render_aovs(StEngine* e, StHandle camera, const StAovTargets* targets, void* hip_stream);
 
+/* ---- skinned meshes (NEW seam): per-instance joint poses skinned on the device (k_skin.hip, linear blend skinning).
+ * A skin belongs to a mesh, a pose to an instance: instances share a skinned mesh and each has joints of its own (Bevy's SkinnedMesh
+ * per entity; glTF's node with a skin that refers to a mesh). An instance of a skinned mesh without a pose renders the bind pose.
+ * - When a pose takes effect: at the next st_tick, like any scene edit. Frames, scene queries and AOVs see it only after that tick;
+ *   of two poses set before one tick the last wins.
+ * - Joint matrices: joint transform x inverse bind matrix, mapping the bind pose into the INSTANCE's object space; the instance transform
+ *   is applied after it. (Bevy's skin matrices are world-space: a facade passes them relative to the instance transform, or sets the
+ *   instance transform to identity.)
+ * - Lifecycle: st_mesh_insert on a skinned handle drops the skin and the pose of every instance of that mesh; st_mesh_remove drops the
+ *   skin. st_instance_insert on an existing id keeps its pose only if the mesh handle is unchanged; st_instance_remove drops the pose.
+ * - Errors: st_mesh_set_skin returns ST_ERR_INVALID_ARGUMENT for an unknown mesh, a null pointer, a wrong corner_count, a joint_count
+ *   outside 1..256, a joint index >= joint_count, or a weight that is negative, not finite or part of an all-zero set; a host-only
+ *   engine accepts a skin (host work). st_instance_set_pose returns ST_ERR_NO_DEVICE on a host-only engine (there is no CPU skinning)
+ *   and ST_ERR_INVALID_ARGUMENT for an unknown instance, an instance whose mesh has no skin, a joint_count other than the skin's, or
+ *   a matrix element that is not finite.
+ * - Limitation: the velocity plane, reprojection and ST_AOV_MOTION follow instance transforms only. A skinned deformation is not in
+ *   them (the previous pose's positions would have to reach primary visibility). */
+typedef struct StSkinVertex {   /* 24 B */
+    uint16_t joints[4];         /* indices into the skin's joint palette, < joint_count */
+    float weights[4];           /* used as given (not renormalised); finite, >= 0, not all zero */
+} StSkinVertex;
+/* corners[3 t + v] = corner v of triangle t of the mesh as given to st_mesh_insert; corner_count = 3 x its triangles; 1 <= joint_count <= 256 */
+int st_mesh_set_skin(StEngine* e, StHandle mesh, const StSkinVertex* corners, size_t corner_count, uint32_t joint_count);
+/* joint_count x 12 floats, each an Affine3A column-major like st_instance_insert's xform: joint transform x inverse bind matrix,
+ * mapping the bind pose into the INSTANCE's object space (the instance transform is applied after it). NULL / 0 = back to the bind pose. */
+int st_instance_set_pose(StEngine* e, StHandle instance, const float* joint_xforms, uint32_t joint_count);
+/* Skin launches so far (one per tick at most), the triangles they skinned, and the batched read-backs of posed triangles the host
+ * needed (host-path refresh modes, heatmap observers, debug reads of the scene). */
+int st_debug_skinning(StEngine* e, uint64_t* launches, uint64_t* triangles, uint64_t* host_readbacks);
+/* The instance's posed object-space triangles as the device holds them: 24 floats per triangle (positions 9, normals 9, uvs 6: the device
+ * mesh store's layout). Blocking. An instance without a pose is ST_ERR_INVALID_ARGUMENT. out == NULL only reports the size. */
+int st_debug_read_posed(StEngine* e, StHandle instance, float* out, size_t capacity_floats, size_t* written_floats);
+
 /* ---- multi-GPU behind the boundary (NEW seam; SURVEY.md section 8e, BASELINE.json configs 4 and 5). One process per GPU, one
  * engine per process, the scene replicated; the frame is cut into tiles, every rank renders its tile (+ an apron of redundant
  * pixels in Image mode, whose passes read neighbours) with absolute pixel coordinates, and the ONE collective of the path

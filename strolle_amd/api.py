@@ -30,6 +30,14 @@ class StMeshTriangle(C.Structure):
     _fields_ = [("positions", C.c_float * 9), ("normals", C.c_float * 9), ("uvs", C.c_float * 6), ("tangents", C.c_float * 12)]
 
 
+class StSkinVertex(C.Structure):
+    """include/strolle_hip.h "skinned meshes": one corner's joint indices and weights (24 B)."""
+    _fields_ = [("joints", C.c_uint16 * 4), ("weights", C.c_float * 4)]
+
+
+SKIN_VERTEX_DTYPE = np.dtype({"names": ["joints", "weights"], "formats": [(np.uint16, (4,)), (np.float32, (4,))], "offsets": [0, 8], "itemsize": 24})
+
+
 class StMaterial(C.Structure):
     _fields_ = [
         ("base_color", C.c_float * 4), ("emissive", C.c_float * 4),
@@ -393,6 +401,8 @@ class _Binding:
             self.dist_gather = fn("dist_gather", [vp, u64, vp, vp, vp]); self.dist_wait = fn("dist_wait", [vp, u64, vp, vp, i32])
             self.dist_gather_ms = fn("dist_gather_ms", [vp, u64, P(C.c_float)])
         self.image_insert_rgba8 = fn("image_insert_rgba8", [vp, u64, u32, u32, vp, i32]); self.image_remove = fn("image_remove", [vp, u64])
+        if hasattr(lib, prefix + "mesh_set_skin"):
+            self.mesh_set_skin = fn("mesh_set_skin", [vp, u64, vp, sz, u32])
         if has_device:
             self.camera_set_rows = fn("camera_set_rows", [vp, u64, u32, u32])
             self.camera_set_output_format = fn("camera_set_output_format", [vp, u64, i32])
@@ -415,6 +425,10 @@ class _Binding:
                 self.scene_trace_rays_host = fn("scene_trace_rays_host", [vp, vp, u32, vp])
             if hasattr(lib, prefix + "camera_render_aovs"):   # per-pixel AOVs (likewise absent from an older library)
                 self.camera_render_aovs = fn("camera_render_aovs", [vp, u64, P(StAovTargets), vp])
+            if hasattr(lib, prefix + "instance_set_pose"):   # skinned meshes (likewise absent from an older library)
+                self.instance_set_pose = fn("instance_set_pose", [vp, u64, P(C.c_float), u32])
+                self.debug_skinning = fn("debug_skinning", [vp, P(u64), P(u64), P(u64)])
+                self.debug_read_posed = fn("debug_read_posed", [vp, u64, P(C.c_float), sz, P(sz)])
             self.profile_enable = fn("profile_enable", [vp, i32])
             self.profile_read = fn("profile_read", [vp, P(StKernelProfile), sz, P(sz), i32])
             self.last_error = getattr(lib, prefix + "last_error"); self.last_error.restype = C.c_char_p; self.last_error.argtypes = []
@@ -464,6 +478,14 @@ class EngineBase:
 
     def remove_mesh(self, handle: int):
         self._check(self._b.mesh_remove(self._h, handle))
+
+    def set_skin(self, mesh: int, joints, weights, joint_count: int):
+        """st_mesh_set_skin: joints (3n, 4) joint indices and weights (3n, 4) per corner of mesh `mesh`'s n triangles (corner v of
+        triangle t at row 3 t + v); weights are used as given."""
+        joints = np.asarray(joints).reshape(-1, 4); weights = np.asarray(weights, np.float32).reshape(-1, 4)
+        corners = np.zeros(len(joints), SKIN_VERTEX_DTYPE)
+        corners["joints"] = joints; corners["weights"] = weights
+        self._check(self._b.mesh_set_skin(self._h, mesh, corners.ctypes.data if len(corners) else None, len(corners), joint_count))
 
     def insert_material(self, handle: int, material: Material):
         m = material.to_c()
@@ -756,6 +778,30 @@ class Engine(EngineBase):
         if stream is not None and hasattr(stream, "cuda_stream"):
             stream = stream.cuda_stream
         self._check(self._b.camera_render_aovs(self._h, camera, C.byref(t), stream or 0))
+
+    def set_pose(self, instance: int, matrices):
+        """st_instance_set_pose: matrices (J, 3, 4) like Instance.transform — joint transform x inverse bind matrix, into the instance's
+        object space; applied at the next tick. None = back to the bind pose."""
+        if matrices is None:
+            self._check(self._b.instance_set_pose(self._h, instance, None, 0)); return
+        m = np.asarray(matrices, np.float32).reshape(-1, 3, 4)
+        flat = np.ascontiguousarray(m.transpose(0, 2, 1).reshape(-1), dtype=np.float32)   # per joint: columns x, y, z, t
+        self._check(self._b.instance_set_pose(self._h, instance, flat.ctypes.data_as(C.POINTER(C.c_float)), len(m)))
+
+    def skinning_stats(self):
+        """st_debug_skinning: (skin launches, triangles skinned, batched host read-backs of posed triangles)."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self._b.debug_skinning(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def read_posed(self, instance: int) -> np.ndarray:
+        """st_debug_read_posed: the instance's posed object-space triangles as the device holds them, (n, 24) float32 (positions 9,
+        normals 9, uvs 6)."""
+        n = C.c_size_t()
+        self._check(self._b.debug_read_posed(self._h, instance, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.float32)
+        self._check(self._b.debug_read_posed(self._h, instance, out.ctypes.data_as(C.POINTER(C.c_float)), n.value, C.byref(n)))
+        return out.reshape(-1, 24)
 
     def trace_rays_host(self, rays: np.ndarray) -> np.ndarray:
         """st_scene_trace_rays_host: a RAY_DTYPE array in host memory -> a HIT_DTYPE array (blocking)."""

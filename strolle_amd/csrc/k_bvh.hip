@@ -91,14 +91,14 @@ __global__ __launch_bounds__(256) void k_bvh_refit(float4* bvh, const float4* tr
 struct BakeJobDevice { float4 x, y, z, t, r0, r1, r2; uint32_t mesh_first, count, slot_first, xslot; };
 static_assert(sizeof(BakeJobDevice) == 128, "one bake job is 128 B");
 __global__ __launch_bounds__(256) void k_bvh_bake(const BakeJobDevice* jobs, const uint32_t* job_start, uint32_t n_jobs, uint32_t total, const float* mesh,
-                                                  float4* tri_geo, float4* tri_bounds, float4* tri_attr, float4* bvh, const uint32_t* entry_of_tri) {
+                                                  const float* posed, float4* tri_geo, float4* tri_bounds, float4* tri_attr, float4* bvh, const uint32_t* entry_of_tri) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     uint32_t lo = 0u, hi = n_jobs;          // the job whose [job_start[j], job_start[j + 1]) holds i
     while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (job_start[mid] <= i) lo = mid; else hi = mid; }
     const BakeJobDevice j = jobs[lo];
     const uint32_t k = i - job_start[lo];
-    const float* m = mesh + 24u * (size_t)(j.mesh_first + k);
+    const float* m = (f2b(j.x.w) ? posed : mesh) + 24u * (size_t)(j.mesh_first + k);   // x.w != 0: mesh_first indexes the posed store (k_skin.hip), same layout
     const V3 ax = xyz(j.x), ay = xyz(j.y), az = xyz(j.z), at = xyz(j.t), r0 = xyz(j.r0), r1 = xyz(j.r1), r2 = xyz(j.r2);
     V3 p[3], n[3];
 #pragma unroll
@@ -124,9 +124,9 @@ __global__ __launch_bounds__(256) void k_bvh_bake(const BakeJobDevice* jobs, con
         if (e != 0xffffffffu) { bvh[4u * e + 1u] = g0; bvh[4u * e + 2u] = g1; bvh[4u * e + 3u] = g2; }
     }
 }
-void launch_bvh_bake(const void* jobs, const uint32_t* job_start, uint32_t n_jobs, uint32_t total, const float* mesh, float4* tri_geo, float4* tri_bounds, float4* tri_attr,
-                     float4* bvh, const uint32_t* entry_of_tri, hipStream_t s) {
-    if (total) ST_KLAUNCH(k_bvh_bake, dim3((total + 255u) / 256u), dim3(256), s, static_cast<const BakeJobDevice*>(jobs), job_start, n_jobs, total, mesh, tri_geo, tri_bounds, tri_attr, bvh, entry_of_tri);
+void launch_bvh_bake(const void* jobs, const uint32_t* job_start, uint32_t n_jobs, uint32_t total, const float* mesh, const float* posed, float4* tri_geo, float4* tri_bounds,
+                     float4* tri_attr, float4* bvh, const uint32_t* entry_of_tri, hipStream_t s) {
+    if (total) ST_KLAUNCH(k_bvh_bake, dim3((total + 255u) / 256u), dim3(256), s, static_cast<const BakeJobDevice*>(jobs), job_start, n_jobs, total, mesh, posed, tri_geo, tri_bounds, tri_attr, bvh, entry_of_tri);
 }
 
 // ---- the COMPACT stream the fast build's shadow rays walk (st_device.h any_hit_compact; StTuning::compact_bvh).

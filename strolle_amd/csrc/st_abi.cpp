@@ -52,11 +52,12 @@ void st_engine_destroy(StEngine* e) { delete E(e); }
 int st_mesh_insert(StEngine* e, StHandle id, const StMeshTriangle* t, size_t count) {
     ST_REQUIRE(e && (t || count == 0), "null argument");
     if (count == 0) return fail(ST_ERR_EMPTY_MESH, "mesh contains no triangles");
+    E(e)->drop_skin(id);   // skinned meshes: a new mesh drops the skin and the poses of its instances
     E(e)->meshes[id].assign(t, t + count);
     E(e)->mesh_version[id] = E(e)->next_mesh_version++;   // an instance baked from the earlier mesh of this handle is re-baked by the host
     return ST_OK;
 }
-int st_mesh_remove(StEngine* e, StHandle id) { ST_REQUIRE(e, "null engine"); E(e)->meshes.erase(id); E(e)->mesh_version.erase(id); return ST_OK; }
+int st_mesh_remove(StEngine* e, StHandle id) { ST_REQUIRE(e, "null engine"); E(e)->drop_skin(id); E(e)->meshes.erase(id); E(e)->mesh_version.erase(id); return ST_OK; }
 
 int st_material_insert(StEngine* e, StHandle id, const StMaterial* m) {
     ST_REQUIRE(e && m, "null argument");
@@ -158,7 +159,7 @@ int st_instance_insert(StEngine* e, StHandle id, StHandle mesh, StHandle materia
     Engine* en = E(e);
     const Affine x = affine_from12(xform);
     for (auto& r : en->instances)
-        if (r.id == id) { r.prev_xform = r.xform; r.mesh = mesh; r.material = material; r.xform = x; r.xform_inv = affine_inverse(x); r.dirty = true; en->instances_dirty = true; return ST_OK; }
+        if (r.id == id) { if (r.mesh != mesh) en->drop_pose(id, false); r.prev_xform = r.xform; r.mesh = mesh; r.material = material; r.xform = x; r.xform_inv = affine_inverse(x); r.dirty = true; en->instances_dirty = true; return ST_OK; }
     uint32_t xslot;
     if (!en->xslot_free.empty()) { xslot = en->xslot_free.back(); en->xslot_free.pop_back(); }
     else { xslot = (uint32_t)(en->instance_xforms.size() / 8u); en->instance_xforms.resize(en->instance_xforms.size() + 8u, make_float4(0, 0, 0, 0)); }
@@ -172,7 +173,27 @@ int st_instance_remove(StEngine* e, StHandle id) {
     for (size_t i = 0; i < en->instances.size(); i++)
         if (en->instances[i].id == id) { en->xslot_free.push_back(en->instances[i].xslot); en->instances.erase(en->instances.begin() + i); en->instances_dirty = true; en->instance_removed = true; break; }
     en->drop_instance_triangles(id);
+    en->drop_pose(id, false);
     return ST_OK;
+}
+
+// ---- skinned meshes (st_skin.cpp)
+int st_mesh_set_skin(StEngine* e, StHandle mesh, const StSkinVertex* corners, size_t corner_count, uint32_t joint_count) {
+    ST_REQUIRE(e, "null engine");
+    return E(e)->set_skin(mesh, corners, corner_count, joint_count);
+}
+int st_instance_set_pose(StEngine* e, StHandle instance, const float* joint_xforms, uint32_t joint_count) {
+    ST_REQUIRE(e, "null engine");
+    return E(e)->set_pose(instance, joint_xforms, joint_count);
+}
+int st_debug_skinning(StEngine* e, uint64_t* launches, uint64_t* triangles, uint64_t* host_readbacks) {
+    ST_REQUIRE(e && launches && triangles && host_readbacks, "null argument");
+    *launches = E(e)->skin_launches; *triangles = E(e)->skinned_triangles; *host_readbacks = E(e)->posed_readbacks;
+    return ST_OK;
+}
+int st_debug_read_posed(StEngine* e, StHandle instance, float* out, size_t capacity_floats, size_t* written_floats) {
+    ST_REQUIRE(e, "null engine");
+    return E(e)->read_posed(instance, out, capacity_floats, written_floats);
 }
 int st_light_insert(StEngine* e, StHandle id, const StLight* l) { ST_REQUIRE(e && l, "null argument"); E(e)->insert_light(id, *l); return ST_OK; }
 int st_light_remove(StEngine* e, StHandle id) { ST_REQUIRE(e, "null engine"); E(e)->remove_light(id); return ST_OK; }
@@ -446,6 +467,7 @@ int st_debug_read_scene(StEngine* e, int what, void* out, size_t capacity, size_
     Engine* en = E(e);
     const void* p; size_t bytes;
     if ((what == 0 || what == 1 || what == 4 || (what >= 7 && what <= 15)) && en->any_host_stale()) en->bake_stale_on_host();   // instances the device moved: the host arrays catch up
+    if (int rc = en->take_deferred_status()) return rc;   // (their posed triangles could not be read back)
     if (en->host_tree_stale && (what == 0 || what == 4 || (what >= 7 && what <= 15))) en->rebuild_host_tree(false);   // ST_BVH_BUILD_DEVICE left the host's tree behind
     if ((what == 0 || what == 4) && en->host_stream_stale) { en->refit_stream(); en->host_stream_stale = false; }  // device refits since the host copy was current
     switch (what) {

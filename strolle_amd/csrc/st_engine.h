@@ -359,6 +359,36 @@ struct Engine {
     bool any_host_stale() const { for (const auto& i : instances) if (i.host_stale) return true; return false; }
     void bake_stale_on_host();         // brings the host arrays up to date (rebuilds, host refits, full uploads and debug reads need them)
 
+    // Skinned meshes (st_skin.cpp, k_skin.hip; include/strolle_hip.h "skinned meshes"). A skin per mesh: its bind-pose triangles (24 floats each,
+    // the mesh store's layout) and corners go to the skin store once. A pose per instance: the last palette set (12 floats per joint) and a region
+    // of the posed store (24 floats per triangle) that the tick's skin launch fills and k_bvh_bake reads; `host` is its host image (tangents from
+    // the bind mesh), read back only when a host bake needs it. meshes[id] stays the bind pose.
+    struct SkinRec { std::vector<StSkinVertex> corners; uint32_t joints = 0; size_t first = SIZE_MAX; };   // first: its triangles in the skin store (SIZE_MAX: not there yet)
+    std::unordered_map<uint64_t, SkinRec> skins;
+    struct PoseRec {
+        uint64_t mesh = 0; std::vector<float> palette; size_t first = SIZE_MAX, count = 0;   // first: its region of the posed store (SIZE_MAX: none yet)
+        bool reskin = true;          // the device region has to be (re)computed at the next tick: the pose changed, or the posed store was reallocated
+        bool changed = true;         // the pose changed since the last skin launch (that launch makes the host image stale)
+        bool host_current = false;   // `host` holds what the device region holds
+        std::vector<StMeshTriangle> host;
+    };
+    std::unordered_map<uint64_t, PoseRec> poses;
+    // the skin store's host image; ranges of dropped skins go back to skin_free and are reused
+    std::vector<float> skin_bind_host; std::vector<StSkinVertex> skin_corner_host; SlotRanges skin_free;
+    DeviceArray d_skin_bind, d_skin_corners, d_posed, d_skin_jobs, d_skin_starts, d_palettes;
+    SlotRanges posed_free; size_t posed_size = 0;   // triangles of the posed store handed out (its allocation holds at least that many)
+    hipStream_t skin_stream = nullptr; hipEvent_t ev_skinned = nullptr, ev_posed_read = nullptr; bool posed_read_pending = false;
+    uint64_t skin_launches = 0, skinned_triangles = 0, posed_readbacks = 0;
+    int set_skin(uint64_t mesh, const StSkinVertex* corners, size_t corner_count, uint32_t joint_count);
+    int set_pose(uint64_t instance, const float* joint_xforms, uint32_t joint_count);
+    int read_posed(uint64_t instance, float* out, size_t capacity_floats, size_t* written_floats);
+    void drop_pose(uint64_t instance, bool make_dirty);
+    void drop_skin(uint64_t mesh);    // and the poses of the instances of that mesh
+    int skin_tick(hipStream_t stream);   // st_tick, before the refresh: one launch for every pose to (re)compute
+    int read_back_posed();            // host images of every posed region they lag behind: one batch, one synchronisation
+    int deferred_status = ST_OK;      // a read-back that failed inside a refresh or bake_stale_on_host (message in g_last_error): st_tick / st_debug_read_scene return it
+    int take_deferred_status() { const int rc = deferred_status; deferred_status = ST_OK; return rc; }
+
     std::vector<StMaterial> materials; std::unordered_map<uint64_t, uint32_t> material_slot; SlotRanges material_free; bool materials_dirty = false;
     std::vector<GpuMaterial> gpu_materials; std::vector<uint32_t> material_base_packed;
     struct InstanceRec {
@@ -533,6 +563,8 @@ struct Engine {
 
     void drop_instance_triangles(uint64_t id);
     void bake(const StMeshTriangle& t, const InstanceRec& inst, uint32_t material, size_t slot);
+    // what a host bake of `inst` reads: the host image of its posed region (skinned meshes), else its mesh (`mesh`)
+    const std::vector<StMeshTriangle>* bake_source(const InstanceRec& inst, const std::vector<StMeshTriangle>& mesh) const;
     struct BakeJob { const std::vector<StMeshTriangle>* mesh; const InstanceRec* inst; uint32_t material; size_t first, count; };
     bool refresh_instances();
     void bake_jobs_on_host(const std::vector<BakeJob>& jobs, size_t total);

@@ -71,6 +71,15 @@ inline const KernelInfo& kernel_info(int slot) {
     return k[slot];
 }
 
+// Skinning (k_skin.hip): built once with the exact flags, like the device BVH builder. One job per posed instance; job_start (n_jobs + 1
+// entries, in triangles) pads every job to kSkinBlock so that a workgroup serves one job. Triangles index the skin store (skin_first) and the
+// posed store (posed_first), 24 floats each; palette_first counts 12-float joint matrices.
+constexpr uint32_t kSkinBlock = 128u, kSkinMaxJoints = 256u;
+struct SkinJob { uint32_t skin_first, count, posed_first, palette_first, joint_count, pad[3]; };
+static_assert(sizeof(SkinJob) == 32, "one skin job is 32 B");
+void launch_skin(const SkinJob* jobs, const uint32_t* job_start, uint32_t n_jobs, uint32_t padded_total, const float* bind, const void* corners,
+                 const float* palettes, float* posed, hipStream_t s);
+
 // The launchers exist twice, in namespaces st::exact and st::fast (the two arithmetic builds of the kernel files, Makefile);
 // the engine calls them through a table picked per engine (st_engine_set_arithmetic).
 #define ST_LAUNCHER(name, args) void name args;

@@ -57,8 +57,9 @@ ST_LAUNCHER(launch_bvh_refit, (float4* bvh, const float4* tri_bounds, const uint
 ST_LAUNCHER(launch_copy_float4, (float4* dst, const float4* src, size_t n, uint32_t blocks, hipStream_t s))
 // pitched rectangle copy (tile pack / unpack of the multi-GPU gather, st_dist.cpp); row_bytes a multiple of 4
 ST_LAUNCHER(launch_rect_copy, (void* dst, size_t dst_pitch, const void* src, size_t src_pitch, size_t row_bytes, uint32_t rows, hipStream_t s))
-// world-space baking of moved instances on the device (k_bvh.hip; StTuning::device_bake): jobs = 128-B records (xform, inverse rows, mesh / slot ranges)
-ST_LAUNCHER(launch_bvh_bake, (const void* jobs, const uint32_t* job_start, uint32_t n_jobs, uint32_t total, const float* mesh, float4* tri_geo, float4* tri_bounds, float4* tri_attr, float4* bvh, const uint32_t* entry_of_tri, hipStream_t s))
+// world-space baking of moved instances on the device (k_bvh.hip; StTuning::device_bake): jobs = 128-B records (xform, inverse rows, mesh / slot ranges);
+// a job whose x.w is nonzero reads its object-space triangles from `posed` (the posed store of skinned instances, k_skin.hip) instead of `mesh`
+ST_LAUNCHER(launch_bvh_bake, (const void* jobs, const uint32_t* job_start, uint32_t n_jobs, uint32_t total, const float* mesh, const float* posed, float4* tri_geo, float4* tri_bounds, float4* tri_attr, float4* bvh, const uint32_t* entry_of_tri, hipStream_t s))
 // the compact stream (48-B entries, f16 conservative boxes) of the fast build's shadow rays, regenerated from the contract stream (k_bvh.hip)
 ST_LAUNCHER(launch_bvh_compact, (const float4* bvh, uint32_t n_entries, float4* out, hipStream_t s))
 ST_LAUNCHER(launch_bvh_wide, (const float4* bvh, const uint32_t* topo, uint32_t n_nodes, const uint32_t* leaf_entry, uint32_t n_leaves, uint32_t links16, float4* nodes, float4* leaves, hipStream_t s))

@@ -154,6 +154,8 @@ void Engine::bake_jobs_on_host(const std::vector<BakeJob>& jobs, size_t total) {
 // (its primitives), a host refit or a debug read of the stream (tri_bounds), a full upload. Both device copies then receive those slots from
 // the host like any other baked range, and their lists of pending device moves are void.
 void Engine::bake_stale_on_host() {
+    // posed instances bake from their posed regions (st_skin.cpp); a failed read-back is reported by the next st_tick or debug read
+    if (!poses.empty()) if (int rc = read_back_posed()) deferred_status = rc;
     std::vector<BakeJob> jobs; size_t total = 0;
     for (auto& inst : instances) {
         if (!inst.host_stale) continue;
@@ -161,7 +163,7 @@ void Engine::bake_stale_on_host() {
         auto mesh = meshes.find(inst.mesh);
         auto have = instance_triangles.find(inst.id);
         if (mesh == meshes.end() || have == instance_triangles.end() || have->second.second - have->second.first != mesh->second.size()) continue;  // the next refresh re-bakes it as dirty
-        jobs.push_back({&mesh->second, &inst, inst.baked_material, have->second.first, mesh->second.size()});
+        jobs.push_back({bake_source(inst, mesh->second), &inst, inst.baked_material, have->second.first, mesh->second.size()});
         total += mesh->second.size();
         for (SceneSet& t : sets) { t.dirty_lo = std::min(t.dirty_lo, have->second.first); t.dirty_hi = std::max(t.dirty_hi, have->second.second); }
     }
@@ -201,7 +203,9 @@ bool Engine::refresh_instances() {
             return true;
         }
     }
-    // the host bakes this refresh: instances the device moved earlier and that are not dirty now must catch up first (a rebuild reads every primitive)
+    // the host bakes this refresh: posed instances from their posed regions, read back in one batch (st_skin.cpp)
+    if (!poses.empty()) if (int rc = read_back_posed()) deferred_status = rc;
+    // instances the device moved earlier and that are not dirty now must catch up first (a rebuild reads every primitive)
     if (any_host_stale()) {
         // re-baked below anyway — but only those whose bake job WILL be queued: an instance whose mesh or material is missing is retried at a
         // later tick, and until then its host arrays must still count as stale (debug reads catch up through bake_stale_on_host)
@@ -240,7 +244,7 @@ bool Engine::refresh_instances() {
             triangles.resize(e); prims.resize(e); prim_alive.resize(e, 0); tri_geo.resize(3 * e); tri_attr.resize(4 * e); tri_bounds.resize(2 * e);
             for (SceneSet& t : sets) t.tri_full = true;
         }
-        jobs.push_back({&mesh->second, &inst, mat->second, b, count});
+        jobs.push_back({bake_source(inst, mesh->second), &inst, mat->second, b, count});
         total += count;
         for (SceneSet& t : sets) { t.dirty_lo = std::min(t.dirty_lo, b); t.dirty_hi = std::max(t.dirty_hi, e); }  // slots each device copy still has to receive
         mark_info_dirty(b, e);
@@ -263,7 +267,7 @@ int Engine::bake_on_device(SceneSet& t, hipStream_t up, bool* pageable) {
     struct Job { float4 x, y, z, t, r0, r1, r2; uint32_t mesh_first, count, slot_first, xslot; };
     static_assert(sizeof(Job) == 128, "k_bvh.hip BakeJobDevice");
     std::vector<Job> jobs; std::vector<uint32_t> starts{0u};
-    bool store_grew = false;
+    bool store_grew = false, reads_posed = false;
     for (uint64_t id : t.pending_moves) {
         auto it = by_id.find(id);
         if (it == by_id.end()) continue;   // removed since: that tick rebuilt the tree and voided the lists
@@ -271,8 +275,12 @@ int Engine::bake_on_device(SceneSet& t, hipStream_t up, bool* pageable) {
         auto have = instance_triangles.find(id);
         auto mesh = meshes.find(inst.mesh);
         if (have == instance_triangles.end() || mesh == meshes.end()) continue;
+        // a posed instance (skinned mesh) reads its region of the posed store, which this tick's skin launch brought up to date (st_skin.cpp)
+        auto pose = poses.find(id);
+        // (a pose is dropped with its mesh: its triangle count is the one this instance's slots were baked for)
+        const bool posed = pose != poses.end() && pose->second.first != SIZE_MAX && pose->second.count == have->second.second - have->second.first;
         auto dm = device_meshes.find(inst.mesh);
-        if (dm == device_meshes.end() || dm->second.version != inst.baked_mesh_version) {
+        if (!posed && (dm == device_meshes.end() || dm->second.version != inst.baked_mesh_version)) {
             DeviceMeshRec rec{mesh_store_host.size() / 24u, mesh->second.size(), inst.baked_mesh_version};
             mesh_store_host.reserve(mesh_store_host.size() + 24u * rec.count);
             for (const StMeshTriangle& m : mesh->second) {
@@ -286,7 +294,8 @@ int Engine::bake_on_device(SceneSet& t, hipStream_t up, bool* pageable) {
         Job j;
         j.x = f4(inst.xform.x, 0.0f); j.y = f4(inst.xform.y, 0.0f); j.z = f4(inst.xform.z, 0.0f); j.t = f4(inst.xform.t, 0.0f);
         j.r0 = make_float4(inv.x.x, inv.y.x, inv.z.x, 0.0f); j.r1 = make_float4(inv.x.y, inv.y.y, inv.z.y, 0.0f); j.r2 = make_float4(inv.x.z, inv.y.z, inv.z.z, 0.0f);
-        j.mesh_first = (uint32_t)dm->second.first; j.count = (uint32_t)dm->second.count; j.slot_first = (uint32_t)have->second.first; j.xslot = inst.xslot;
+        j.mesh_first = posed ? (uint32_t)pose->second.first : (uint32_t)dm->second.first; j.count = posed ? (uint32_t)pose->second.count : (uint32_t)dm->second.count; j.slot_first = (uint32_t)have->second.first; j.xslot = inst.xslot;
+        if (posed) { j.x.w = b2f(1u); reads_posed = true; }
         jobs.push_back(j); starts.push_back(starts.back() + j.count);
     }
     t.pending_moves.clear();
@@ -301,10 +310,16 @@ int Engine::bake_on_device(SceneSet& t, hipStream_t up, bool* pageable) {
     }
     if ((rc = t.bake_jobs.upload(jobs.data(), jobs.size() * sizeof(Job), up, staging, pageable))) return rc;
     if ((rc = t.bake_starts.upload(starts.data(), starts.size() * sizeof(uint32_t), up, staging, pageable))) return rc;
+    if (reads_posed) ST_HIP(hipStreamWaitEvent(up, ev_skinned, 0));   // the skin launch (skin stream) wrote the posed regions
     // the EXACT build's kernel, whatever arithmetic the frames use: the baked arrays are the host's bits
     launchers_exact().launch_bvh_bake(t.bake_jobs.ptr, static_cast<const uint32_t*>(t.bake_starts.ptr), (uint32_t)jobs.size(), starts.back(), static_cast<const float*>(d_mesh_store.ptr),
-                                      static_cast<float4*>(t.tri_geo.ptr), static_cast<float4*>(t.tri_bounds.ptr), static_cast<float4*>(t.tri_attr.ptr), static_cast<float4*>(t.bvh.ptr),
-                                      t.device_built ? nullptr : static_cast<const uint32_t*>(t.entry_of_tri.ptr), up);
+                                      static_cast<const float*>(d_posed.ptr), static_cast<float4*>(t.tri_geo.ptr), static_cast<float4*>(t.tri_bounds.ptr), static_cast<float4*>(t.tri_attr.ptr),
+                                      static_cast<float4*>(t.bvh.ptr), t.device_built ? nullptr : static_cast<const uint32_t*>(t.entry_of_tri.ptr), up);
+    if (reads_posed) {   // the next skin launch overwrites the regions after this bake — and after an earlier one still pending on another stream:
+        // the event is re-recorded here behind a wait for its previous recording, so that it covers both (the bake itself is not delayed)
+        if (posed_read_pending) ST_HIP(hipStreamWaitEvent(up, ev_posed_read, 0));
+        ST_HIP(hipEventRecord(ev_posed_read, up)); posed_read_pending = true;
+    }
     device_bakes++; device_baked_triangles += starts.back();
     return ST_OK;
 }

@@ -145,6 +145,13 @@ int Engine::build_on_device(SceneSet& t, hipStream_t up, bool* pageable) {
 
 // ---- tick (lib.rs:301-395)
 int Engine::tick(hipStream_t stream) {
+    // skinned meshes: the poses set since the last tick are skinned first — a host bake of this refresh reads their posed triangles back
+    const bool skinning = has_device && !poses.empty();
+    if (skinning) {
+        ST_HIP(hipSetDevice(device));
+        staging.begin_tick();
+        if (int rc = skin_tick(stream)) return rc;
+    }
     const TreePlan plan = refresh_scene();
     refresh_sun_and_lights();
     if (has_device) {
@@ -155,7 +162,7 @@ int Engine::tick(hipStream_t stream) {
         if (tick_work_in_flight && hipEventQuery(ev_tick) == hipSuccess) tick_work_in_flight = false;
         if (copy_in_flight && hipEventQuery(ev_copy) == hipSuccess) copy_in_flight = false;
         (void)hipGetLastError();  // hipErrorNotReady from the queries is not an error
-        staging.begin_tick();
+        if (!skinning) staging.begin_tick();
         TickIo io{stream};
         int rc;
         if ((rc = upload_scene(plan, io)) || (rc = upload_images(io)) || (rc = upload_lights(io)) || (rc = end_uploads(io))) return rc;
@@ -163,6 +170,7 @@ int Engine::tick(hipStream_t stream) {
     atlas_dirty = false;
     for (auto& kv : cameras) kv.second->frame = frame;  // CameraController::flush
     frame += 1;
+    if (int rc = take_deferred_status()) return rc;   // a read-back of posed triangles failed: the host baked their bind pose
     return report_deep_bvh();
 }
 // Materials, instances (baked) and the tree on the host; what upload_scene does with the tree. Every tree decision of a tick and its counter is

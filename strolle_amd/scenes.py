@@ -244,3 +244,52 @@ def sliver_bundle_camera(size, mode=CameraMode.REFERENCE, depth=0) -> Camera:
     w, h = size
     return Camera(mode=mode, denoise=True, depth=depth, size=(w, h), transform=look_at_transform((-3.0, 0.012, -0.012), (0.0, 0.012, -0.012)),
                   projection=perspective_infinite_reverse_rh(math.pi / 60.0, w / h, 0.1))
+
+
+def skinned_tube(segments: int = 128, sides: int = 32, joints: int = 32, radius: float = 0.25, length: float = 2.0):
+    """A skinned tube along +y (include/strolle_hip.h "skinned meshes"): 2 x segments x sides triangles from y = 0 to `length`, radial normals,
+    and `joints` joints evenly spaced along the axis. Each corner has two linear-falloff influences: the joints just below and above it.
+    Returns (Mesh, corner joints (3n, 4) uint16, corner weights (3n, 4) float32) — Engine.set_skin's arguments."""
+    ys = np.arange(segments + 1, dtype=np.float64) * (length / segments)
+    ang = np.arange(sides + 1, dtype=np.float64) * (2.0 * math.pi / sides)
+    ring = np.stack([np.cos(ang), np.zeros_like(ang), np.sin(ang)], -1)                 # (sides + 1, 3) unit radial directions
+    pts = ring[None, :, :] * radius + np.stack([np.zeros_like(ys), ys, np.zeros_like(ys)], -1)[:, None, :]
+    nrm = np.broadcast_to(ring[None, :, :], pts.shape)
+    uv = np.stack(np.meshgrid(ang / (2.0 * math.pi), ys / length, indexing="xy"), -1)    # (segments + 1, sides + 1, 2)
+    i, j = np.meshgrid(np.arange(segments), np.arange(sides), indexing="ij")
+    i, j = i.reshape(-1), j.reshape(-1)
+    tri = [np.stack([(i, j), (i + 1, j + 1), (i, j + 1)], 1), np.stack([(i, j), (i + 1, j), (i + 1, j + 1)], 1)]   # (n, 3 corners, 2)
+    corners = np.concatenate([np.transpose(t, (2, 1, 0)) for t in tri], 0).reshape(-1, 3, 2)   # outward winding, one quad after the other
+    ci, cj = corners[..., 0], corners[..., 1]
+    mesh = Mesh(pts[ci, cj].astype(np.float32), nrm[ci, cj].astype(np.float32), uv[ci, cj].astype(np.float32))
+    u = (ys[ci] / length * max(joints - 1, 1)).reshape(-1) if joints > 1 else np.zeros(ci.size)
+    k0 = np.minimum(np.floor(u), max(joints - 2, 0)).astype(np.int64)
+    f = (u - k0).astype(np.float32) if joints > 1 else np.zeros(ci.size, np.float32)
+    jt = np.zeros((ci.size, 4), np.uint16); wt = np.zeros((ci.size, 4), np.float32)
+    jt[:, 0] = k0; wt[:, 0] = np.float32(1.0) - f
+    if joints > 1:
+        jt[:, 1] = k0 + 1; wt[:, 1] = f
+    return mesh, jt, wt
+
+
+def bend_pose(joints: int, angle: float, phase: float = 0.0, length: float = 2.0) -> np.ndarray:
+    """A pose of skinned_tube's joint chain, (joints, 3, 4) float32 like Instance.transform: joint k turns by angle / (joints - 1) x
+    sin(phase + 0.5 k) about z relative to joint k - 1, and each matrix is the joint's transform x its inverse bind matrix."""
+    seg = length / max(joints - 1, 1)
+
+    def rz(a):
+        m = np.eye(4); c, s = math.cos(a), math.sin(a)
+        m[0, 0], m[0, 1], m[1, 0], m[1, 1] = c, -s, s, c
+        return m
+
+    def ty(y):
+        m = np.eye(4); m[1, 3] = y
+        return m
+
+    world, out = np.eye(4), []
+    for k in range(joints):
+        if k:
+            world = world @ ty(seg)
+        world = world @ rz(angle / max(joints - 1, 1) * math.sin(phase + 0.5 * k))
+        out.append((world @ ty(-k * seg))[:3, :4])
+    return np.asarray(out, np.float32)
