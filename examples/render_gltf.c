@@ -5,7 +5,8 @@
  *
  *   cc -std=c99 -D__HIP_PLATFORM_AMD__ -I include -I /opt/rocm/include examples/render_gltf.c \
  *      -L strolle_amd/csrc -lstrolle_hip -L /opt/rocm/lib -lamdhip64 -lm -Wl,-rpath,$PWD/strolle_amd/csrc -o render_gltf
- *   ./render_gltf scene.glb out.ppm [width height frames]
+ *   ./render_gltf scene.glb out.ppm [width height frames] [--env sky.hdr [intensity]]
+ * --env lights the scene with an equirectangular Radiance .hdr map instead of the atmosphere (st_decode_hdr + st_environment_set).
  */
 #include <hip/hip_runtime_api.h>
 #include <math.h>
@@ -47,13 +48,53 @@ static void perspective_infinite_reverse(float fov_y, float aspect, float z_near
     out[0] = f / aspect; out[5] = f; out[11] = -1.0f; out[14] = z_near;
 }
 
+/* a Radiance .hdr file as the sky: decoded by the library, copied by st_environment_set, live from the next st_tick */
+static int set_environment(StEngine* engine, const char* path, float intensity) {
+    FILE* f = fopen(path, "rb");
+    if (!f) { perror(path); return 1; }
+    fseek(f, 0, SEEK_END);
+    const long size = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    unsigned char* bytes = (unsigned char*)malloc(size > 0 ? (size_t)size : 1u);
+    const int read_ok = bytes && fread(bytes, 1, (size_t)size, f) == (size_t)size;
+    fclose(f);
+    if (!read_ok) { fprintf(stderr, "could not read %s\n", path); free(bytes); return 1; }
+    uint32_t w = 0, h = 0;
+    float* rgb = NULL;
+    int status = st_decode_hdr(bytes, (size_t)size, NULL, 0, &w, &h);
+    if (status == ST_OK) {
+        rgb = (float*)malloc((size_t)w * h * 3u * sizeof(float));
+        status = rgb ? st_decode_hdr(bytes, (size_t)size, rgb, (size_t)w * h * 3u, &w, &h) : ST_ERR_INVALID_ARGUMENT;
+    }
+    if (status == ST_OK) {
+        StEnvironmentDesc desc;
+        memset(&desc, 0, sizeof desc);
+        desc.struct_size = sizeof desc; desc.intensity = intensity;
+        status = st_environment_set(engine, rgb, w, h, 3, &desc);
+    }
+    if (status != ST_OK) fprintf(stderr, "environment %s failed (%d): %s\n", path, status, st_last_error());
+    else fprintf(stderr, "environment %s: %ux%u, intensity %g\n", path, w, h, intensity);
+    free(rgb); free(bytes);
+    return status != ST_OK;
+}
+
 int main(int argc, char** argv) {
-    if (argc < 3) {
-        fprintf(stderr, "usage: %s scene.gltf|scene.glb out.ppm [width height frames]\n", argv[0]);
+    const char* env_path = NULL;
+    float env_intensity = 1.0f;
+    const char* pos[5] = {NULL, NULL, NULL, NULL, NULL};
+    int npos = 0, i;
+    for (i = 1; i < argc; i++) {
+        if (strcmp(argv[i], "--env") == 0 && i + 1 < argc) {
+            env_path = argv[++i];
+            if (i + 1 < argc) { char* end; const float v = strtof(argv[i + 1], &end); if (end != argv[i + 1] && *end == '\0') { env_intensity = v; i++; } }
+        } else if (npos < 5) pos[npos++] = argv[i];
+    }
+    if (npos < 2) {
+        fprintf(stderr, "usage: %s scene.gltf|scene.glb out.ppm [width height frames] [--env sky.hdr [intensity]]\n", argv[0]);
         return 2;
     }
-    const uint32_t width = argc > 3 ? (uint32_t)atoi(argv[3]) : 640u, height = argc > 4 ? (uint32_t)atoi(argv[4]) : 360u;
-    const int frames = argc > 5 ? atoi(argv[5]) : 24;
+    const uint32_t width = npos > 2 ? (uint32_t)atoi(pos[2]) : 640u, height = npos > 3 ? (uint32_t)atoi(pos[3]) : 360u;
+    const int frames = npos > 4 ? atoi(pos[4]) : 24;
 
     StEngine* engine = NULL;
     CHECK(st_engine_create(0, &engine));
@@ -63,7 +104,7 @@ int main(int argc, char** argv) {
     options.first_handle = 1; options.first_image_handle = 1000;
     options.light_radius = 0.15f;                                                       /* cornell.rs:45-54 */
     StGltfSummary scene;
-    CHECK(st_scene_load_gltf(engine, argv[1], &options, &scene));
+    CHECK(st_scene_load_gltf(engine, pos[0], &options, &scene));
     fprintf(stderr, "%u meshes, %u triangles, %u materials, %u images (%u dropped, %u primitives skipped), %u lights\n", scene.meshes,
             scene.triangles, scene.materials, scene.images, scene.images_dropped, scene.primitives_skipped, scene.lights);
 
@@ -75,6 +116,7 @@ int main(int argc, char** argv) {
     light.color[0] = light.color[1] = light.color[2] = 50.0f / (4.0f * 3.14159265f);   /* cornell.rs:45-54 */
     CHECK(st_light_insert(engine, 1 + scene.lights, &light));
     CHECK(st_sun_update(engine, 0.0f, -1.0f));                                          /* night: cornell.rs:87 */
+    if (env_path && set_environment(engine, env_path, env_intensity)) return 1;
 
     StCamera camera;
     memset(&camera, 0, sizeof camera);
@@ -122,12 +164,12 @@ int main(int argc, char** argv) {
     uint64_t rays = 0;
     CHECK(st_camera_ray_count(engine, cam, &rays, 0));
 
-    FILE* f = fopen(argv[2], "wb");
-    if (!f) { perror(argv[2]); return 1; }
+    FILE* f = fopen(pos[1], "wb");
+    if (!f) { perror(pos[1]); return 1; }
     fprintf(f, "P6\n%u %u\n255\n", width, height);
     for (size_t i = 0; i < (size_t)width * height; i++) fwrite(host + 4 * i, 1, 3, f);
     fclose(f);
-    fprintf(stderr, "%d frames (%d presented, %d waited for their copy), %llu rays, wrote %s\n", frames, presented, waited, (unsigned long long)rays, argv[2]);
+    fprintf(stderr, "%d frames (%d presented, %d waited for their copy), %llu rays, wrote %s\n", frames, presented, waited, (unsigned long long)rays, pos[1]);
 
     free(host);
     for (int k = 0; k < 2; k++) { (void)hipFree(frame[k]); (void)hipHostFree(host_frame[k]); }

@@ -339,6 +339,62 @@ int st_debug_skinning(StEngine* e, uint64_t* launches, uint64_t* triangles, uint
  * mesh store's layout). Blocking. An instance without a pose is ST_ERR_INVALID_ARGUMENT. out == NULL only reports the size. */
 int st_debug_read_posed(StEngine* e, StHandle instance, float* out, size_t capacity_floats, size_t* written_floats);
 
+/* ---- environment lighting (NEW seam): an equirectangular HDR map in place of the procedural atmosphere (k_env.hip, st_env.cpp).
+ * - Timing: a change takes effect at the next st_tick, like every scene edit. Frames, scene queries and AOVs before that tick see the old
+ *   sky; a frame already enqueued keeps reading the map it started with. The old map's memory is released only after the frames that read
+ *   it are done (an event recorded behind them; the engine waits for the device instead when cameras render on several streams).
+ * - Mapping: the world direction is rotated by -yaw about +Y, giving d; u = 0.5 + atan2(d.x, -d.z) / 2 pi, v = acos(clamp(d.y)) / pi.
+ *   Row 0 is the zenith, the image centre looks down -Z (Bevy's forward). Look-up is bilinear at texel centres, wrapping in u and clamping
+ *   in v, at full resolution; the value is multiplied by `intensity`.
+ * - What it replaces: the whole atmosphere, the sky LUT and the sun disk with its bloom, wherever a ray leaves the scene (primary sky
+ *   pixels, GI bounces and GI's sky pick, Reference-mode misses). Light 0, the analytic sun, gets zero colour while a map is set unless
+ *   ST_ENV_KEEP_SUN is given. GI's sky pick probability is 0.25 whenever a map is set (for the atmosphere it is 0 while the sun's altitude
+ *   is <= -1). GI draws sky directions from the map's importance table (a Vose alias table over a luminance grid of at most 512 x 256
+ *   cells) mixed one-to-one with its usual draws, so the estimate keeps its expectation; ST_ENV_UNIFORM_SAMPLING draws as for the atmosphere.
+ * - Errors: ST_ERR_INVALID_ARGUMENT for a null pointer, a side outside 1..16384 or width x height > 2^25, channels other than 3 or 4, a
+ *   negative or non-finite host texel, a wrong struct_size, unknown flag bits, a negative or non-finite intensity or yaw, and (device
+ *   variant) a row pitch that is not a multiple of 4 or shorter than a row. The device variant cannot check texels on the host: its upload
+ *   kernel sets NaN, infinite and negative channels to 0 and counts those texels (st_debug_environment_sanitized). A host-only engine
+ *   accepts st_environment_set, _update and _clear (validating and storing is host work; light 0 follows them at st_tick) and returns
+ *   ST_ERR_NO_DEVICE for st_environment_set_device and the debug seams.
+ * - Unaffected: AOVs and StRayHit — "sky" in them means "no hit", as before. History is not reset when the map changes (nor when the sun
+ *   moves). */
+enum { ST_ENV_KEEP_SUN = 1,            /* the analytic sun light (light 0) stays on; by default it is off while a map is set */
+       ST_ENV_UNIFORM_SAMPLING = 2 };  /* no importance sampling: GI draws sky directions exactly as for the atmosphere (tests, A/B) */
+typedef struct StEnvironmentDesc {     /* 16 B */
+    uint32_t struct_size;              /* sizeof(StEnvironmentDesc) */
+    uint32_t flags;                    /* ST_ENV_* */
+    float intensity;                   /* linear scale of every texel; finite, >= 0 */
+    float yaw;                         /* radians, rotation of the map about +Y; finite */
+} StEnvironmentDesc;
+/* texels: width x height x channels floats (3 = RGB, 4 = RGBA with alpha ignored), linear, row 0 the zenith; host memory, copied before the
+ * call returns */
+int st_environment_set(StEngine* e, const float* texels, uint32_t width, uint32_t height, uint32_t channels, const StEnvironmentDesc* desc);
+/* the same from device memory, rows `row_pitch_bytes` apart (0 = packed): the contract of st_image_insert_device_rgba8 for a static image —
+ * the caller keeps the buffer alive and its writes ordered before the next st_tick, which copies it */
+int st_environment_set_device(StEngine* e, const void* texels_device, uint32_t width, uint32_t height, uint32_t channels,
+                              size_t row_pitch_bytes, const StEnvironmentDesc* desc);
+int st_environment_update(StEngine* e, const StEnvironmentDesc* desc);   /* intensity, yaw and flags; no re-upload */
+int st_environment_clear(StEngine* e);                                    /* back to the atmosphere */
+/* Radiance .hdr (RGBE) bytes -> width x height x 3 floats, row 0 the top of the image. Header "#?RADIANCE" or "#?RGBE" with
+ * FORMAT=32-bit_rle_rgbe (other header lines such as EXPOSURE are ignored); resolution "-Y H +X W" only; flat and new-style run-length
+ * scanlines. Texel = m * 2^(e - 136), e == 0 -> 0 (Ward's rgbe.c without the +0.5). Other orientations, 32-bit_rle_xyze and old-style
+ * runs are ST_ERR_UNSUPPORTED, and so is an image of more than 2^26 texels; truncated or malformed data is ST_ERR_PARSE, and so is a
+ * resolution the remaining bytes cannot hold (every scanline takes at least 12 bytes, flat ones 4 per texel). out_rgb == NULL only
+ * reports the size. Needs no engine. */
+int st_decode_hdr(const void* bytes, size_t size, float* out_rgb, size_t capacity_floats, uint32_t* width, uint32_t* height);
+/* Debug seams: the kernels' own functions over device arrays, enqueued on the stream like the scene queries; they read the live map (the
+ * one of the last st_tick; ST_ERR_INVALID_ARGUMENT when there is none). eval: n directions (xyz) -> n rgb; sample: n uniform triples in
+ * [0, 1) -> n (xyz, solid-angle pdf) — the first picks the cell, the other two place the direction across and down it, as GI draws them;
+ * pdf: n directions -> n pdfs. */
+int st_debug_environment_eval(StEngine* e, const float* dirs_device, uint32_t n, float* rgb_device, void* hip_stream);
+int st_debug_environment_sample(StEngine* e, const float* u_device /* triples */, uint32_t n, float* dir_pdf_device, void* hip_stream);
+int st_debug_environment_pdf(StEngine* e, const float* dirs_device, uint32_t n, float* pdf_device, void* hip_stream);
+/* Texels the device uploads have sanitised so far, and the importance table of the live map: cells_x x cells_y cells of (q, alias, p)
+ * (12 B each; table == NULL only reports the size). Blocking. */
+int st_debug_environment_sanitized(StEngine* e, uint64_t* texels);
+int st_debug_environment_table(StEngine* e, void* table, size_t capacity_bytes, uint32_t* cells_x, uint32_t* cells_y);
+
 /* ---- multi-GPU behind the boundary (NEW seam; SURVEY.md section 8e, BASELINE.json configs 4 and 5). One process per GPU, one
  * engine per process, the scene replicated; the frame is cut into tiles, every rank renders its tile (+ an apron of redundant
  * pixels in Image mode, whose passes read neighbours) with absolute pixel coordinates, and the ONE collective of the path

@@ -188,6 +188,30 @@ extern "C" {
     pub fn st_dist_wait(e: *mut StEngine, camera: u64, frame: *const c_void, hip_stream: *mut c_void, host_wait: i32) -> i32;
 }
 
+// ---- environment lighting: an equirectangular HDR map in place of the atmosphere (include/strolle_hip.h "environment lighting")
+pub const ST_ENV_KEEP_SUN: u32 = 1;
+pub const ST_ENV_UNIFORM_SAMPLING: u32 = 2;
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct StEnvironmentDesc {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub intensity: f32,
+    pub yaw: f32,
+}
+extern "C" {
+    pub fn st_environment_set(e: *mut StEngine, texels: *const f32, width: u32, height: u32, channels: u32, desc: *const StEnvironmentDesc) -> i32;
+    pub fn st_environment_set_device(e: *mut StEngine, texels_device: *const c_void, width: u32, height: u32, channels: u32, row_pitch_bytes: usize, desc: *const StEnvironmentDesc) -> i32;
+    pub fn st_environment_update(e: *mut StEngine, desc: *const StEnvironmentDesc) -> i32;
+    pub fn st_environment_clear(e: *mut StEngine) -> i32;
+    pub fn st_decode_hdr(bytes: *const c_void, size: usize, out_rgb: *mut f32, capacity_floats: usize, width: *mut u32, height: *mut u32) -> i32;
+    pub fn st_debug_environment_eval(e: *mut StEngine, dirs_device: *const f32, n: u32, rgb_device: *mut f32, hip_stream: *mut c_void) -> i32;
+    pub fn st_debug_environment_sample(e: *mut StEngine, u_device: *const f32 /* triples */, n: u32, dir_pdf_device: *mut f32, hip_stream: *mut c_void) -> i32;
+    pub fn st_debug_environment_pdf(e: *mut StEngine, dirs_device: *const f32, n: u32, pdf_device: *mut f32, hip_stream: *mut c_void) -> i32;
+    pub fn st_debug_environment_sanitized(e: *mut StEngine, texels: *mut u64) -> i32;
+    pub fn st_debug_environment_table(e: *mut StEngine, table: *mut c_void, capacity_bytes: usize, cells_x: *mut u32, cells_y: *mut u32) -> i32;
+}
+
 // ---- the HIP runtime, as far as the staging-copy present needs it (libamdhip64)
 pub type hipStream_t = *mut c_void;
 extern "C" {

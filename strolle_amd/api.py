@@ -108,6 +108,19 @@ class StGltfSummary(C.Structure):
 assert C.sizeof(StMeshTriangle) == 144 and C.sizeof(StMaterial) == 88 and C.sizeof(StLight) == 52 and C.sizeof(StCamera) == 160
 
 
+class StEnvironmentDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("intensity", C.c_float), ("yaw", C.c_float)]
+
+
+ENV_KEEP_SUN, ENV_UNIFORM_SAMPLING = 1, 2
+ENV_CELL_DTYPE = np.dtype([("q", np.float32), ("alias", np.uint32), ("p", np.float32)])   # one cell of the importance table (12 B)
+
+
+def environment_desc(intensity: float = 1.0, yaw: float = 0.0, keep_sun: bool = False, uniform: bool = False) -> StEnvironmentDesc:
+    return StEnvironmentDesc(C.sizeof(StEnvironmentDesc), (ENV_KEEP_SUN if keep_sun else 0) | (ENV_UNIFORM_SAMPLING if uniform else 0),
+                             float(intensity), float(yaw))
+
+
 class StRay(C.Structure):
     """include/strolle_hip.h StRay (32 B): hits count for 0 < t < t_max; the direction is used as given (t in units of |direction|)."""
     _fields_ = [("origin", C.c_float * 3), ("t_max", C.c_float), ("direction", C.c_float * 3), ("_pad", C.c_uint32)]
@@ -401,6 +414,16 @@ class _Binding:
             self.dist_gather = fn("dist_gather", [vp, u64, vp, vp, vp]); self.dist_wait = fn("dist_wait", [vp, u64, vp, vp, i32])
             self.dist_gather_ms = fn("dist_gather_ms", [vp, u64, P(C.c_float)])
         self.image_insert_rgba8 = fn("image_insert_rgba8", [vp, u64, u32, u32, vp, i32]); self.image_remove = fn("image_remove", [vp, u64])
+        if hasattr(lib, prefix + "environment_set"):   # environment lighting (absent from an older library)
+            self.environment_set = fn("environment_set", [vp, vp, u32, u32, u32, P(StEnvironmentDesc)])
+            self.environment_set_device = fn("environment_set_device", [vp, vp, u32, u32, u32, sz, P(StEnvironmentDesc)])
+            self.environment_update = fn("environment_update", [vp, P(StEnvironmentDesc)])
+            self.environment_clear = fn("environment_clear", [vp])
+            self.debug_environment_eval = fn("debug_environment_eval", [vp, vp, u32, vp, vp])
+            self.debug_environment_sample = fn("debug_environment_sample", [vp, vp, u32, vp, vp])
+            self.debug_environment_pdf = fn("debug_environment_pdf", [vp, vp, u32, vp, vp])
+            self.debug_environment_sanitized = fn("debug_environment_sanitized", [vp, P(u64)])
+            self.debug_environment_table = fn("debug_environment_table", [vp, vp, sz, P(u32), P(u32)])
         if hasattr(lib, prefix + "mesh_set_skin"):
             self.mesh_set_skin = fn("mesh_set_skin", [vp, u64, vp, sz, u32])
         if has_device:
@@ -803,6 +826,73 @@ class Engine(EngineBase):
         self._check(self._b.debug_read_posed(self._h, instance, out.ctypes.data_as(C.POINTER(C.c_float)), n.value, C.byref(n)))
         return out.reshape(-1, 24)
 
+    # ---- environment lighting (include/strolle_hip.h "environment lighting"): takes effect at the next tick
+    def set_environment(self, texels, intensity: float = 1.0, yaw: float = 0.0, keep_sun: bool = False, uniform: bool = False):
+        """st_environment_set / st_environment_set_device: an equirectangular map, (H, W, 3 or 4) float32, row 0 the zenith, the centre looking
+        down -Z. A numpy array is copied by the call; a CUDA tensor is read by the next tick (keep it alive and unchanged until then)."""
+        desc = environment_desc(intensity, yaw, keep_sun, uniform)
+        if hasattr(texels, "data_ptr") and getattr(texels, "is_cuda", False):
+            if texels.dim() != 3 or texels.element_size() != 4 or not texels.is_floating_point():
+                raise StrolleError("environment map: expected an (H, W, 3 or 4) float32 tensor")
+            h, w, ch = texels.shape
+            pitch = texels.stride(0) * 4
+            if texels.stride(2) != 1 or texels.stride(1) != ch:
+                raise StrolleError("environment map: rows must be contiguous")
+            self._check(self._b.environment_set_device(self._h, texels.data_ptr(), w, h, ch, pitch, C.byref(desc)))
+            return
+        a = np.ascontiguousarray(texels, dtype=np.float32)
+        if a.ndim != 3:
+            raise StrolleError("environment map: expected an (H, W, 3 or 4) array")
+        h, w, ch = a.shape
+        self._check(self._b.environment_set(self._h, a.ctypes.data, w, h, ch, C.byref(desc)))
+
+    def update_environment(self, intensity: float = 1.0, yaw: float = 0.0, keep_sun: bool = False, uniform: bool = False):
+        """st_environment_update: intensity, yaw and flags of the map, without re-uploading it."""
+        self._check(self._b.environment_update(self._h, C.byref(environment_desc(intensity, yaw, keep_sun, uniform))))
+
+    def clear_environment(self):
+        """st_environment_clear: back to the atmosphere at the next tick."""
+        self._check(self._b.environment_clear(self._h))
+
+    def _env_seam(self, fn, inp, n, out_cols):
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        x = torch.as_tensor(np.ascontiguousarray(inp, np.float32), device=dev).contiguous()
+        out = torch.zeros((n, out_cols), dtype=torch.float32, device=dev)
+        self._check(fn(self._h, x.data_ptr(), n, out.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+        return out.cpu().numpy()
+
+    def environment_eval(self, dirs) -> np.ndarray:
+        """st_debug_environment_eval: (n, 3) world directions -> (n, 3) radiance of the live map."""
+        d = np.asarray(dirs, np.float32).reshape(-1, 3)
+        return self._env_seam(self._b.debug_environment_eval, d, len(d), 3)
+
+    def environment_sample(self, u) -> np.ndarray:
+        """st_debug_environment_sample: (n, 3) uniforms in [0, 1) -> (n, 4) (direction xyz, solid-angle pdf): the first picks the cell,
+        the other two place the direction across and down it."""
+        u = np.asarray(u, np.float32).reshape(-1, 3)
+        return self._env_seam(self._b.debug_environment_sample, u, len(u), 4)
+
+    def environment_pdf(self, dirs) -> np.ndarray:
+        """st_debug_environment_pdf: (n, 3) world directions -> (n,) solid-angle pdf of the importance sampler."""
+        d = np.asarray(dirs, np.float32).reshape(-1, 3)
+        return self._env_seam(self._b.debug_environment_pdf, d, len(d), 1)[:, 0]
+
+    def environment_table(self) -> np.ndarray:
+        """st_debug_environment_table: the live map's importance table, (cells_y, cells_x) of ENV_CELL_DTYPE."""
+        gx, gy = C.c_uint32(), C.c_uint32()
+        self._check(self._b.debug_environment_table(self._h, None, 0, C.byref(gx), C.byref(gy)))
+        out = np.zeros((gy.value, gx.value), ENV_CELL_DTYPE)
+        self._check(self._b.debug_environment_table(self._h, out.ctypes.data, out.nbytes, C.byref(gx), C.byref(gy)))
+        return out
+
+    def environment_sanitized(self) -> int:
+        """st_debug_environment_sanitized: texels the device uploads set to 0 (NaN, infinite or negative channels)."""
+        n = C.c_uint64()
+        self._check(self._b.debug_environment_sanitized(self._h, C.byref(n)))
+        return n.value
+
     def trace_rays_host(self, rays: np.ndarray) -> np.ndarray:
         """st_scene_trace_rays_host: a RAY_DTYPE array in host memory -> a HIT_DTYPE array (blocking)."""
         rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
@@ -998,6 +1088,30 @@ def dist_unique_id() -> bytes:
         lib.st_last_error.restype = C.c_char_p
         raise StrolleError(lib.st_last_error().decode(errors="replace"))
     return bytes(C.string_at(C.byref(uid), 128))
+
+
+def decode_hdr(data: bytes) -> np.ndarray:
+    """st_decode_hdr: Radiance .hdr bytes -> (H, W, 3) float32, row 0 the top of the image."""
+    lib = load_library()
+    fn = lib.st_decode_hdr
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    w, h = C.c_uint32(), C.c_uint32()
+    data = bytes(data)
+    status = fn(data, len(data), None, 0, C.byref(w), C.byref(h))
+    if status == 0:
+        out = np.empty((h.value, w.value, 3), np.float32)
+        status = fn(data, len(data), out.ctypes.data, out.size, C.byref(w), C.byref(h))
+    if status != 0:
+        lib.st_last_error.restype = C.c_char_p
+        raise StrolleError(f"{_STATUS.get(status, 'error')} (status {status}): {lib.st_last_error().decode(errors='replace')}")
+    return out
+
+
+def load_hdr(path) -> np.ndarray:
+    """A Radiance .hdr file -> (H, W, 3) float32 (st_decode_hdr), ready for Engine.set_environment."""
+    with open(path, "rb") as f:
+        return decode_hdr(f.read())
 
 
 def decode_png(data: bytes) -> np.ndarray:

@@ -138,7 +138,15 @@ ST_D void candidate_none(Candidate* c) { c->t = kF32Max; c->tri = 0xffffffffu; c
         else if (a.bvh_len < stack16_limit(a)) ST_LAUNCH_SMEM(ST_TPL3(kernel_tmpl, false, flag, uint16_t), half, stack_lds_bytes(a, 2), stream, __VA_ARGS__); \
         else ST_LAUNCH_SMEM(ST_TPL3(kernel_tmpl, false, flag, uint32_t), half, stack_lds_bytes(a, 4), stream, __VA_ARGS__);                         \
     } while (0)
+// ... and with two (k_di_resolving: REPROJECT, and ENV = an environment map is set)
+#define ST_LAUNCH_TRACE_BB(kernel_tmpl, flag, flag2, half, stream, ...)                                                 \
+    do {                                                                                                                \
+        if (scene_fits_lds(a)) ST_LAUNCH_SMEM(ST_TPL4(kernel_tmpl, true, flag, flag2, uint16_t), half, stack_lds_bytes(a, 2), stream, __VA_ARGS__);        \
+        else if (a.bvh_len < stack16_limit(a)) ST_LAUNCH_SMEM(ST_TPL4(kernel_tmpl, false, flag, flag2, uint16_t), half, stack_lds_bytes(a, 2), stream, __VA_ARGS__); \
+        else ST_LAUNCH_SMEM(ST_TPL4(kernel_tmpl, false, flag, flag2, uint32_t), half, stack_lds_bytes(a, 4), stream, __VA_ARGS__);                         \
+    } while (0)
 #define ST_TPL(k, t) k<t>
+#define ST_TPL4(k, b, c, d, t) (k<b, c, d, t>)
 #define ST_TPL2(k, b, t) (k<b, t>)
 #define ST_TPL3(k, b, c, t) (k<b, c, t>)
 

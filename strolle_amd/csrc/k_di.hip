@@ -191,7 +191,8 @@ void launch_di_spatial_sample(const KArgs& a, uint32_t seed, hipStream_t s) { ST
 // REPROJECT: the DI half of frame_denoising.rs::reproject is appended (it reads only this pixel's fresh diffuse sample
 // plus previous-frame planes).
 // (76 VGPRs with REPROJECT = 6 waves per SIMD; asking for 7 spills 4 registers and measures 78.2 -> 79.9 us.)
-template <bool LDS_SCENE, bool REPROJECT, class SE>
+// ENV: an environment map is set (its own instance: the kernels without one keep their code and registers)
+template <bool LDS_SCENE, bool REPROJECT, bool ENV, class SE>
 __global__ ST_KERNEL_BOUNDS void k_di_resolving(const KArgs a_in) {
     ST_SCENE_PROLOGUE
     ST_STACK_LDS(SE, lds);
@@ -216,7 +217,7 @@ __global__ ST_KERNEL_BOUNDS void k_di_resolving(const KArgs a_in) {
         else { const LightRadiance lr = light_radiance(light_get(a, res.s.light_id), hit); radiance = lr.radiance * res.w; spec_brdf = lr.spec_brdf; }
     } else {
         confidence = 1.0f;
-        radiance = atmosphere_sample(a, hit.dir);
+        radiance = ENV ? env_eval(a, hit.dir) : atmosphere_sample(a, hit.dir);
         spec_brdf = v3s(0.0f);
     }
     const float diff_brdf = fdivc(1.0f - hit.g.metallic, kPi);
@@ -233,7 +234,11 @@ __global__ ST_KERNEL_BOUNDS void k_di_resolving(const KArgs a_in) {
     }
 }
 void launch_di_resolving(const KArgs& a, bool reproject, hipStream_t s) {
-    if (reproject) ST_LAUNCH_TRACE_B(k_di_resolving, true, false, s, a); else ST_LAUNCH_TRACE_B(k_di_resolving, false, false, s, a);
+    if (a.env_map) {
+        if (reproject) ST_LAUNCH_TRACE_BB(k_di_resolving, true, true, false, s, a); else ST_LAUNCH_TRACE_BB(k_di_resolving, false, true, false, s, a);
+    } else {
+        if (reproject) ST_LAUNCH_TRACE_BB(k_di_resolving, true, false, false, s, a); else ST_LAUNCH_TRACE_BB(k_di_resolving, false, false, false, s, a);
+    }
 }
 
 }  // namespace ST_KNS

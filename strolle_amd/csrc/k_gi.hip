@@ -34,10 +34,40 @@ ST_D bool frame_is_gi_tracing(uint32_t frame) { return frame % 6u < 4u; }  // fr
 // Pass a: what it stores in gi_d0..2 — false when the pass leaves early (nothing stored, stale texels stay, as in the reference).
 // ... in two halves — the cell's bounce ray, and what the pass stores for its hit — so that the trace between them can be somebody else's (round 6's lane-refill
 // pool, measured and archived: tools/experiments/gi_sampling_pool.inc)
-ST_D bool gi_sampling_a_ray(uint32_t seed, bool tracing, U2 pos, const Hit& prim_hit, const GiReservoir& vres, Ray* gi_ray, float* gi_ray_pdf) {
+// ENV (an environment map is set, include/strolle_hip.h "environment lighting"; launched as its own instance so that the kernels without a
+// map keep their code and registers): tracing frames draw the bounce from the map's importance table with probability kEnvAlpha, else from
+// the BRDF as below. The pdf the pass reports is not a density: the diffuse branch reports 1/pi for a uniform-hemisphere draw and each lobe's
+// pdf is divided by its pick probability, so today's samples integrate against kappa(l) = m^2 [q_spec(l) > 0] + (1 - m)^2 / 2 [n.l > 0]
+// (m metallic, q_spec the GGX density of the specular draw). Storing mixture density / kappa keeps that expectation.
+ST_D float gi_env_mis_pdf(const KArgs& a, const GBuffer& g, V3 v, V3 l) {
+    const float m = g.metallic;
+    const V3 n = g.normal;
+    float q_spec = 0.0f;
+    if (m > 0.0f) {
+        const float r = clamped_roughness(g);
+        const V3 h = normalize(l + v);
+        const float n_dot_h = saturate(dot(n, h)), h_dot_v = saturate(dot(h, v));
+        if (n_dot_h > 0.0f && h_dot_v > 0.0f) q_spec = fdiv(ggx_distribution(n_dot_h, r) * n_dot_h, 4.0f * h_dot_v);
+    }
+    const float up = dot(n, l) > 0.0f ? 1.0f : 0.0f;
+    const float kappa = m * m * (q_spec > 0.0f ? 1.0f : 0.0f) + 0.5f * sqr(1.0f - m) * up;
+    if (!(kappa > 0.0f)) return 0.0f;
+    const float mixture = (1.0f - kEnvAlpha) * (m * q_spec + (1.0f - m) * up * (0.5f / kPi)) + kEnvAlpha * env_pdf(a, l);
+    return fdiv(mixture, kappa);
+}
+template <bool ENV>
+ST_D bool gi_sampling_a_ray(const KArgs& a, uint32_t seed, bool tracing, U2 pos, const Hit& prim_hit, const GiReservoir& vres, Ray* gi_ray, float* gi_ray_pdf) {
     if (tracing) {
         WhiteNoise wn = white_noise(seed, pos);
         if (!hit_some(prim_hit)) return false;
+        if (ENV && !a.env_uniform) {
+            V3 dir;
+            if (wn.sample() < kEnvAlpha) { const float u0 = wn.sample(), u1 = wn.sample(), u2 = wn.sample(); dir = env_sample(a, u0, u1, u2).dir; }
+            else dir = layered_brdf_sample(prim_hit.g, wn, -prim_hit.dir).dir;
+            *gi_ray = make_ray(prim_hit.point, dir);
+            *gi_ray_pdf = gi_env_mis_pdf(a, prim_hit.g, -prim_hit.dir, dir);
+            return true;
+        }
         const BrdfSample s = layered_brdf_sample(prim_hit.g, wn, -prim_hit.dir);
         *gi_ray = make_ray(prim_hit.point, s.dir);
         *gi_ray_pdf = s.pdf;
@@ -49,11 +79,11 @@ ST_D bool gi_sampling_a_ray(uint32_t seed, bool tracing, U2 pos, const Hit& prim
     return true;
 }
 ST_D void gi_sampling_a_shade(const KArgs& a, const Ray& gi_ray, float gi_ray_pdf, const TriangleHit& gi_hit, float4* d0, float4* d1, float4* d2);
-template <class SE>
+template <bool ENV, class SE>
 ST_D bool gi_sampling_a_cell(const KArgs& a, uint32_t seed, bool tracing, U2 pos, const Hit& prim_hit, const GiReservoir& vres, SE* stack, uint32_t* used_,
                              float4* d0, float4* d1, float4* d2) {
     Ray gi_ray; float gi_ray_pdf;
-    if (!gi_sampling_a_ray(seed, tracing, pos, prim_hit, vres, &gi_ray, &gi_ray_pdf)) return false;
+    if (!gi_sampling_a_ray<ENV>(a, seed, tracing, pos, prim_hit, vres, &gi_ray, &gi_ray_pdf)) return false;
     const TriangleHit gi_hit = trace_closest(a, gi_ray, stack, used_);
     gi_sampling_a_shade(a, gi_ray, gi_ray_pdf, gi_hit, d0, d1, d2);
     return true;
@@ -74,7 +104,7 @@ ST_D void gi_sampling_a_shade(const KArgs& a, const Ray& gi_ray, float gi_ray_pd
     *d0 = f4(gi_ray.dir, gi_ray_pdf);
     gbuffer_pack_bits(gg, base_bits, d1, d2);
 }
-template <bool LDS_SCENE, class SE>
+template <bool LDS_SCENE, bool ENV, class SE>
 __global__ ST_KERNEL_BOUNDS void k_gi_sampling_a(const KArgs a_in, uint32_t seed) {
     ST_SCENE_PROLOGUE
     ST_STACK_LDS(SE, lds);
@@ -87,17 +117,19 @@ __global__ ST_KERNEL_BOUNDS void k_gi_sampling_a(const KArgs a_in, uint32_t seed
     const Hit prim_hit = tracing ? pixel_hit(a, a.cam, a.g0, a.g1, pos) : hit_zero();
     const GiReservoir vres = tracing ? gi_empty() : gi_read(a.gi_res[2], screen_to_idx(a, pos), a.width * a.height);
     float4 d0, d1, d2;
-    if (!gi_sampling_a_cell(a, seed, tracing, pos, prim_hit, vres, lane_stack(a, lds), &used_, &d0, &d1, &d2)) return;
+    if (!gi_sampling_a_cell<ENV>(a, seed, tracing, pos, prim_hit, vres, lane_stack(a, lds), &used_, &d0, &d1, &d2)) return;
     count_rays(a, used_);
     tex_write(a.gi_d0, a, gid, d0);  // indexed by the half-resolution gid (gi_sampling_a.rs:117-121)
     tex_write(a.gi_d1, a, gid, d1);
     tex_write(a.gi_d2, a, gid, d2);
 }
-void launch_gi_sampling_a(const KArgs& a, uint32_t seed, hipStream_t s) { ST_LAUNCH_TRACE(k_gi_sampling_a, true, s, a, seed); }
+void launch_gi_sampling_a(const KArgs& a, uint32_t seed, hipStream_t s) {
+    if (a.env_map) ST_LAUNCH_TRACE_B(k_gi_sampling_a, true, true, s, a, seed); else ST_LAUNCH_TRACE_B(k_gi_sampling_a, false, true, s, a, seed);
+}
 
 // ---------------------------------------------------------------- gi_sampling_b.rs:3-235
 // d0..2: pass a's texels for this cell. The caller has checked hit_some(prim_hit) and, on validation frames, vres.m != 0.
-template <class SE>
+template <bool ENV, class SE>
 ST_D void gi_sampling_b_cell(const KArgs& a, uint32_t seed, bool tracing, U2 pos, const Hit& prim_hit, const GiReservoir& vres, SE* stack, uint32_t* used_,
                              float4 d0, float4 d1, float4 d2) {
     const uint32_t idx = screen_to_idx(a, pos);
@@ -115,15 +147,26 @@ ST_D void gi_sampling_b_cell(const KArgs& a, uint32_t seed, bool tracing, U2 pos
     uint32_t light_id; float light_pdf; V3 light_rad; V3 light_dir = v3s(0.0f);
     if (!hit_some(gi_hit)) {
         light_id = kLightIdSky; light_pdf = 1.0f;
-        light_rad = atmosphere_sample(a, gi_hit.dir);
+        light_rad = ENV ? env_eval(a, gi_hit.dir) : atmosphere_sample(a, gi_hit.dir);
     } else {
-        const float atmosphere_pdf = a.sun_altitude <= -1.0f ? 0.0f : 0.25f;
+        const float atmosphere_pdf = ENV ? 0.25f : (a.sun_altitude <= -1.0f ? 0.0f : 0.25f);   // (a map lights the scene whatever the sun's altitude)
         bool pick_sky = a.light_count == 0u;
         if (!pick_sky) pick_sky = wn.sample() < atmosphere_pdf;  // `||` short-circuits: no sample is drawn when light_count == 0
         if (pick_sky) {
             light_id = kLightIdSky; light_pdf = atmosphere_pdf;
-            light_dir = wn.sample_hemisphere(gi_hit.g.normal);
-            light_rad = atmosphere_sample(a, light_dir) * dot(gi_hit.g.normal, light_dir);
+            if (ENV && !a.env_uniform) {
+                // the uniform hemisphere mixed with the map's importance table (probability kEnvAlpha): env cos / 2 pi over the mixture's
+                // density keeps the expectation of the uniform draw below
+                const V3 n = gi_hit.g.normal;
+                if (wn.sample() < kEnvAlpha) { const float u0 = wn.sample(), u1 = wn.sample(), u2 = wn.sample(); light_dir = env_sample(a, u0, u1, u2).dir; }
+                else light_dir = wn.sample_hemisphere(n);
+                const float cos_l = dot(n, light_dir);
+                const float mixture = (1.0f - kEnvAlpha) * (0.5f / kPi) + kEnvAlpha * env_pdf(a, light_dir);
+                light_rad = cos_l > 0.0f ? env_eval(a, light_dir) * fdiv(cos_l * (0.5f / kPi), mixture) : v3s(0.0f);
+            } else {
+                light_dir = wn.sample_hemisphere(gi_hit.g.normal);
+                light_rad = (ENV ? env_eval(a, light_dir) : atmosphere_sample(a, light_dir)) * dot(gi_hit.g.normal, light_dir);
+            }
         } else {
             const EphemeralResult res = ephemeral_build(a, wn, gi_hit);
             if (res.w > 0.0f) {
@@ -159,7 +202,7 @@ ST_D void gi_sampling_b_cell(const KArgs& a, uint32_t seed, bool tracing, U2 pos
     }
     gi_write(a.gi_res[1], idx, res);
 }
-template <bool LDS_SCENE, class SE>
+template <bool LDS_SCENE, bool ENV, class SE>
 __global__ ST_KERNEL_BOUNDS void k_gi_sampling_b(const KArgs a_in, uint32_t seed) {
     ST_SCENE_PROLOGUE
     ST_STACK_LDS(SE, lds);
@@ -174,15 +217,17 @@ __global__ ST_KERNEL_BOUNDS void k_gi_sampling_b(const KArgs a_in, uint32_t seed
     const float4 d0 = tex_read(a.gi_d0, a, gid), d1 = tex_read(a.gi_d1, a, gid), d2 = tex_read(a.gi_d2, a, gid);
     GiReservoir vres = gi_empty();
     if (!tracing) { vres = gi_read(a.gi_res[2], screen_to_idx(a, pos), a.width * a.height); if (vres.m == 0.0f) return; }
-    gi_sampling_b_cell(a, seed, tracing, pos, prim_hit, vres, lane_stack(a, lds), &used_, d0, d1, d2);
+    gi_sampling_b_cell<ENV>(a, seed, tracing, pos, prim_hit, vres, lane_stack(a, lds), &used_, d0, d1, d2);
 }
-void launch_gi_sampling_b(const KArgs& a, uint32_t seed, hipStream_t s) { ST_LAUNCH_TRACE(k_gi_sampling_b, true, s, a, seed); }
+void launch_gi_sampling_b(const KArgs& a, uint32_t seed, hipStream_t s) {
+    if (a.env_map) ST_LAUNCH_TRACE_B(k_gi_sampling_b, true, true, s, a, seed); else ST_LAUNCH_TRACE_B(k_gi_sampling_b, false, true, s, a, seed);
+}
 
 // Both sampling passes of a cell in one launch: pass b takes pass a's three texels from registers (they are still stored:
 // gi_d0..2 are planes of the reference), the pixel's G-buffer and, on validation frames, the reprojected reservoir are read once.
 // Wherever pass b runs pass a has run (tracing: both need the pixel's surface; validation: both need a non-empty reservoir).
 // 6 waves per SIMD: the allocator fits 80 VGPRs without a spill where it would take 83 (5 waves): 96.5 -> 93.2 us, dungeon 356 -> 345.
-template <bool LDS_SCENE, class SE>
+template <bool LDS_SCENE, bool ENV, class SE>
 __global__ __launch_bounds__(kBlockThreads, 6) void k_gi_sampling_ab(const KArgs a_in, uint32_t seed_a, uint32_t seed_b, uint32_t reproject) {
     ST_SCENE_PROLOGUE
     ST_STACK_LDS(SE, lds);
@@ -208,16 +253,17 @@ __global__ __launch_bounds__(kBlockThreads, 6) void k_gi_sampling_ab(const KArgs
         } else vres = gi_read(a.gi_res[2], screen_to_idx(a, pos), n);  // a pixel without a surface: the slot gi_reprojection leaves alone
     }
     float4 d0, d1, d2;
-    if (!gi_sampling_a_cell(a, seed_a, tracing, pos, prim_hit, vres, lane_stack(a, lds), &used_, &d0, &d1, &d2)) return;
+    if (!gi_sampling_a_cell<ENV>(a, seed_a, tracing, pos, prim_hit, vres, lane_stack(a, lds), &used_, &d0, &d1, &d2)) return;
     count_rays(a, used_);
     tex_write(a.gi_d0, a, gid, d0);
     tex_write(a.gi_d1, a, gid, d1);
     tex_write(a.gi_d2, a, gid, d2);
     if (!hit_some(prim_hit)) return;  // validation frames: pass a re-traces a reservoir wherever one is, pass b wants a surface too
-    gi_sampling_b_cell(a, seed_b, tracing, pos, prim_hit, vres, lane_stack(a, lds), &used_, d0, d1, d2);
+    gi_sampling_b_cell<ENV>(a, seed_b, tracing, pos, prim_hit, vres, lane_stack(a, lds), &used_, d0, d1, d2);
 }
 void launch_gi_sampling_ab(const KArgs& a, uint32_t seed_a, uint32_t seed_b, bool reproject, hipStream_t s) {
-    ST_LAUNCH_TRACE(k_gi_sampling_ab, true, s, a, seed_a, seed_b, reproject ? 1u : 0u);
+    if (a.env_map) ST_LAUNCH_TRACE_B(k_gi_sampling_ab, true, true, s, a, seed_a, seed_b, reproject ? 1u : 0u);
+    else ST_LAUNCH_TRACE_B(k_gi_sampling_ab, false, true, s, a, seed_a, seed_b, reproject ? 1u : 0u);
 }
 
 // ---------------------------------------------------------------- gi_temporal_resampling.rs:3-156

@@ -99,7 +99,7 @@ __global__ ST_KERNEL_BOUNDS void k_ref_shading(const KArgs a_in, uint32_t seed, 
     const Rec2 packed_hit = rec2_read_own(a.ref_hits, idx, true, true);
     const TriangleHit t_hit = hit_unpack(packed_hit.d0, packed_hit.d1);
     if (!hit_is_some(t_hit)) {
-        color = color + throughput * atmosphere_sample(a, ray.dir);
+        color = color + throughput * sky_radiance(a, ray.dir);
         a.ref_rays[3u * idx] = f4z();
         a.ref_rays[3u * idx + 1u] = f4z();
         a.ref_rays[3u * idx + 2u] = f4(color, 0.0f);

@@ -1239,6 +1239,73 @@ ST_D V3 atmosphere_sample(const KArgs& a, V3 ray_dir) {
     return lum;
 }
 
+// ------------------------------------------------------------------ environment map (include/strolle_hip.h "environment lighting")
+// An equirectangular map replaces the atmosphere while KArgs::env_map is set. The world direction is rotated by -yaw about +Y (d);
+// u = 0.5 + atan2(d.x, -d.z) / 2 pi, v = acos(d.y) / pi: row 0 is the zenith, the image centre looks down -Z. Bilinear at texel
+// centres, wrapping in u and clamping in v, times the intensity.
+constexpr float kEnvAlpha = 0.5f;  // one-sample MIS: the probability that GI's two sky sites draw from the map's importance table
+ST_D V3 env_local(const KArgs& a, V3 w) { return v3(a.env_cos_yaw * w.x - a.env_sin_yaw * w.z, w.y, a.env_sin_yaw * w.x + a.env_cos_yaw * w.z); }
+ST_D V3 env_world(const KArgs& a, V3 d) { return v3(a.env_cos_yaw * d.x + a.env_sin_yaw * d.z, d.y, a.env_cos_yaw * d.z - a.env_sin_yaw * d.x); }
+ST_D V2 env_uv(V3 d) {
+    V2 uv = v2(0.5f + atan2_(d.x, -d.z) * (0.5f / kPi), acos_(clampf(d.y, -1.0f, 1.0f)) * (1.0f / kPi));
+    if (uv.x != uv.x) uv.x = 0.0f;
+    if (uv.y != uv.y) uv.y = 0.0f;
+    return uv;
+}
+ST_D V3 env_texel(const KArgs& a, int32_t x, int32_t y) {
+    const int32_t w = (int32_t)a.env_w, h = (int32_t)a.env_h;
+    x %= w; if (x < 0) x += w;
+    y = y < 0 ? 0 : (y >= h ? h - 1 : y);
+    return xyz(a.env_map[(uint32_t)y * a.env_w + (uint32_t)x]);
+}
+ST_D V3 env_eval(const KArgs& a, V3 dir) {
+    const V2 uv = env_uv(env_local(a, dir));
+    const float fx = uv.x * (float)a.env_w - 0.5f, fy = uv.y * (float)a.env_h - 0.5f;
+    const float x0 = floorf(fx), y0 = floorf(fy);
+    const float tx = fx - x0, ty = fy - y0;
+    const int32_t ix = f2i_sat(x0), iy = f2i_sat(y0);
+    const V3 p00 = env_texel(a, ix, iy), p10 = env_texel(a, ix + 1, iy), p01 = env_texel(a, ix, iy + 1), p11 = env_texel(a, ix + 1, iy + 1);
+    const V3 top = p00 + (p10 - p00) * tx;
+    const V3 bot = p01 + (p11 - p01) * tx;
+    return (top + (bot - top) * ty) * a.env_intensity;
+}
+// what every ray that leaves the scene sees: the map, or the atmosphere when none is set
+ST_D V3 sky_radiance(const KArgs& a, V3 dir) { return a.env_map ? env_eval(a, dir) : atmosphere_sample(a, dir); }
+// Solid-angle density of env_sample: the cell's probability spread uniformly over its (u, v) rectangle, p * cells / (2 pi^2 sin theta).
+// sin theta comes from d.y, which the rotation about +Y leaves as it is: env_sample and env_pdf of its direction agree.
+ST_D float env_pdf_of(const KArgs& a, float p, float cos_theta) {
+    const float sin_theta = fsqrt(fmax_(0.0f, 1.0f - cos_theta * cos_theta));
+    if (!(sin_theta > 0.0f) || !(p > 0.0f)) return 0.0f;
+    return fdiv(p * (float)(a.env_gw * a.env_gh), (2.0f * kPi * kPi) * sin_theta);
+}
+ST_D float env_pdf(const KArgs& a, V3 dir) {
+    const V3 d = env_local(a, dir);
+    const V2 uv = env_uv(d);
+    const uint32_t cx = min(f2u_sat(uv.x * (float)a.env_gw), a.env_gw - 1u), cy = min(f2u_sat(uv.y * (float)a.env_gh), a.env_gh - 1u);
+    return env_pdf_of(a, a.env_table[cy * a.env_gw + cx].p, d.y);
+}
+struct EnvSample { V3 dir; float pdf; };
+// Three uniforms: u0 picks a cell of the alias table (its remainder decides against the alias), u1 and u2 place the sample across and down
+// the cell, each at its full resolution. At most two dependent loads.
+ST_D EnvSample env_sample(const KArgs& a, float u0, float u1, float u2) {
+    const uint32_t cells = a.env_gw * a.env_gh;
+    const float x = u0 * (float)cells;
+    uint32_t i = min(f2u_sat(x), cells - 1u);
+    const EnvCell c = a.env_table[i];
+    float p = c.p;
+    if (!(x - (float)i < c.q)) { i = c.alias; p = a.env_table[i].p; }
+    const uint32_t cy = i / a.env_gw, cx = i - cy * a.env_gw;
+    const float u = fdiv((float)cx + u1, (float)a.env_gw), v = fdiv((float)cy + u2, (float)a.env_gh);
+    float st_, ct_, sp_, cp_;
+    sincos_(v * kPi, &st_, &ct_);
+    sincos_((u - 0.5f) * (2.0f * kPi), &sp_, &cp_);
+    st_ = fsqrt(fmax_(0.0f, 1.0f - ct_ * ct_));
+    EnvSample s;
+    s.dir = env_world(a, v3(st_ * sp_, ct_, -st_ * cp_));
+    s.pdf = env_pdf_of(a, p, ct_);
+    return s;
+}
+
 // ------------------------------------------------------------------ reprojection (reprojection.rs, utils/bilinear_filter.rs)
 struct Reprojection { float prev_x, prev_y, confidence; uint32_t validity; };
 ST_D Reprojection reprojection_read(float4 d) { Reprojection r; r.prev_x = d.x; r.prev_y = d.y; r.confidence = d.z; r.validity = f2b(d.w); return r; }

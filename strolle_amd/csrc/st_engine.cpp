@@ -93,6 +93,10 @@ Engine::~Engine() {
     for (auto& kv : cameras) release_camera(*kv.second);
     for (DeviceArray* d : {&d_byte_luts, &d_atlas, &d_blue_noise, &d_transmittance, &d_scattering, &d_sky, &d_mesh_store, &d_skin_bind, &d_skin_corners, &d_posed, &d_skin_jobs, &d_skin_starts, &d_palettes}) d->release();
     for (LightSet& l : light_sets) { l.buf.release(); l.fence.release(); }
+    if (env_live) { env_live->texels.release(); env_live->table.release(); env_live->fence.release(); }
+    release_environments(true);
+    d_env_grid.release();
+    if (d_env_bad) (void)hipFree(d_env_bad);
     for (SceneSet& t : sets) {
         for (DeviceArray* d : {&t.bvh, &t.tri_attr, &t.xforms, &t.materials, &t.base_packed, &t.tri_geo, &t.tri_bounds, &t.entry_of_tri, &t.parent, &t.refit_local, &t.refit_items, &t.refit_batch_off, &t.bvh_compact, &t.tri_info, &t.lb_keys_a, &t.lb_keys_b, &t.lb_temp, &t.lb_seg, &t.lb_children, &t.lb_node_box, &t.lb_small, &t.bvh_wide, &t.wide_topo, &t.wide_leaf_entry, &t.bake_jobs, &t.bake_starts, &t.instance_table}) d->release();
         t.fence.release();

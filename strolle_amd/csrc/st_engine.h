@@ -464,6 +464,19 @@ struct Engine {
     std::vector<uint8_t> blue_noise; bool blue_noise_dirty = true;
     bool atmosphere_initialized = false, sky_known = false; float known_sun_altitude = 0.0f;  // passes/atmosphere.rs:14-15,78-110
 
+    // environment lighting (include/strolle_hip.h "environment lighting"; st_env.cpp). An edit waits in env_edit / env_desc_next for the next
+    // tick (apply_environment on the host, upload_environment on the device). Every map the device holds is a fresh allocation: frames
+    // enqueued before a replacement keep reading theirs, which is released once its fence says they are done (env_retired).
+    struct EnvMap { DeviceArray texels, table; uint32_t w = 0, h = 0, gw = 0, gh = 0; CopyFence fence; };
+    enum EnvEditKind { ENV_EDIT_NONE, ENV_EDIT_HOST, ENV_EDIT_DEVICE, ENV_EDIT_CLEAR };
+    struct EnvEdit { EnvEditKind kind = ENV_EDIT_NONE; std::vector<float4> texels; const void* src = nullptr; size_t pitch = 0; uint32_t w = 0, h = 0, channels = 0; };
+    EnvEdit env_edit;
+    StEnvironmentDesc env_desc{}, env_desc_next{};
+    bool env_set = false, env_sun_off = false;   // a map is live (host-only engines too: light 0 follows it); light 0 is dark because of it
+    std::unique_ptr<EnvMap> env_live; std::vector<std::unique_ptr<EnvMap>> env_retired;
+    DeviceArray d_env_grid; uint32_t* d_env_bad = nullptr; uint64_t env_sanitized = 0;
+    std::vector<float> env_grid_host; std::vector<EnvCell> env_table_host;
+
     DeviceArray d_byte_luts, d_atlas, d_blue_noise, d_transmittance, d_scattering, d_sky;
     // The arrays a scene change rewrites exist twice. A tick that changes the scene fills the copy no frame in flight reads,
     // on a stream of its own, while the previous frame still renders from the other one; the next frame switches over.
@@ -618,6 +631,12 @@ struct Engine {
     int tick(hipStream_t stream);
     TreePlan refresh_scene();
     void refresh_sun_and_lights();
+    void apply_environment();
+    int upload_environment(TickIo& io);
+    int retire_environment(std::unique_ptr<EnvMap> m);
+    void release_environments(bool all);
+    void environment_args(KArgs& a) const;
+    int environment_debug(uint32_t what, const float* in, uint32_t n, float* out, hipStream_t stream);
     int pick_copy(TickIo& io, int live_index, CopyFence& live_fence, CopyFence& other_fence, bool written_before, bool& alternating_now, CopyTarget& c);
     int upload_scene(TreePlan plan, TickIo& io);
     int upload_images(TickIo& io);

@@ -156,6 +156,7 @@ int Engine::reader_begin(hipStream_t stream, bool reader) {
 int Engine::reader_end(hipStream_t stream, bool lights) {
     if (alternating) if (int rc = sets[live].fence.mark_read(stream)) return rc;
     if (lights && lights_alternating) if (int rc = light_sets[live_lights].fence.mark_read(stream)) return rc;
+    if (lights && env_live) if (int rc = env_live->fence.mark_read(stream)) return rc;   // (frames: the map is freed behind its last reader)
     return ST_OK;
 }
 
@@ -177,6 +178,7 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
     a.n_lights_buf = (uint32_t)gpu_lights.size(); a.light_count = light_count;
     a.sun_altitude = sun_altitude;
     a.sun_dir[0] = sun_dir_.x; a.sun_dir[1] = sun_dir_.y; a.sun_dir[2] = sun_dir_.z;
+    environment_args(a);
     auto P = [&](int id) { return c.plane[id]; };
     a.g0 = P(alt ? ST_BUF_PRIM_GBUFFER_D0_B : ST_BUF_PRIM_GBUFFER_D0_A); a.pg0 = P(alt ? ST_BUF_PRIM_GBUFFER_D0_A : ST_BUF_PRIM_GBUFFER_D0_B);
     a.g1 = P(alt ? ST_BUF_PRIM_GBUFFER_D1_B : ST_BUF_PRIM_GBUFFER_D1_A); a.pg1 = P(alt ? ST_BUF_PRIM_GBUFFER_D1_A : ST_BUF_PRIM_GBUFFER_D1_B);

@@ -153,6 +153,7 @@ int Engine::tick(hipStream_t stream) {
         if (int rc = skin_tick(stream)) return rc;
     }
     const TreePlan plan = refresh_scene();
+    apply_environment();   // (before the lights: a map switches the sun, light 0, off)
     refresh_sun_and_lights();
     if (has_device) {
         ST_HIP(hipSetDevice(device));
@@ -165,7 +166,7 @@ int Engine::tick(hipStream_t stream) {
         if (!skinning) staging.begin_tick();
         TickIo io{stream};
         int rc;
-        if ((rc = upload_scene(plan, io)) || (rc = upload_images(io)) || (rc = upload_lights(io)) || (rc = end_uploads(io))) return rc;
+        if ((rc = upload_scene(plan, io)) || (rc = upload_images(io)) || (rc = upload_lights(io)) || (rc = upload_environment(io)) || (rc = end_uploads(io))) return rc;
     }
     atlas_dirty = false;
     for (auto& kv : cameras) kv.second->frame = frame;  // CameraController::flush
@@ -241,7 +242,8 @@ void Engine::refresh_sun_and_lights() {
     sun_dir_ = v3(ca * sz, sa, -ca * cz);
     if (sun_dirty) {
         sun_dirty = false;
-        const V3 color = sun_transmittance(v3(0.0f, 6.360f + 0.0002f, 0.0f), sun_dir_) * 20.0f * 5.0f;
+        // an environment map replaces the atmosphere, sun included, unless ST_ENV_KEEP_SUN (include/strolle_hip.h "environment lighting")
+        const V3 color = env_sun_off ? v3s(0.0f) : sun_transmittance(v3(0.0f, 6.360f + 0.0002f, 0.0f), sun_dir_) * 20.0f * 5.0f;
         GpuLight sun{};
         sun.d0 = f4(sun_dir_ * 1000.0f, 25.0f); sun.d1 = f4(color, INFINITY); sun.d2 = make_float4(b2f(1u), 0, 0, 0);
         overwrite_light(0, -1, sun);

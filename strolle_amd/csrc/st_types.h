@@ -57,6 +57,11 @@ constexpr uint32_t kLdsSceneTexels = 448;  // device streams up to this many flo
 constexpr uint32_t kLdsLights = 16;  // lights the tracing kernels keep in LDS (k_common.h ST_SCENE_PROLOGUE)
 constexpr uint32_t kCounterLines = 256;  // ray/byte counters are spread over this many 64-B lines per kernel slot
 
+// One cell of the environment map's importance table (Vose alias table, built on the host from the device's luminance grid): with
+// probability q the cell itself, else `alias`; p = the cell's own probability (the solid-angle pdf is p * cells / (2 pi^2 sin theta)).
+struct EnvCell { float q; uint32_t alias; float p; };
+static_assert(sizeof(EnvCell) == 12, "an importance cell is 12 B");
+
 // Everything a per-pixel kernel can touch, passed by value as the kernel argument (scalar loads).
 struct KArgs {
     GpuCamera cam, prev_cam;
@@ -121,6 +126,12 @@ struct KArgs {
     uint32_t col0, col1;                 // st_camera_set_rows / st_camera_set_window); pixels keep their absolute coordinates
     uint32_t frame;
     uint32_t tile_map;  // blockIdx -> tile mapping (st_device.h tile_for_thread)
+    // environment lighting (include/strolle_hip.h "environment lighting"; st_env.cpp): nullptr = no map, the sky is the atmosphere
+    const float4* env_map;      // env_w x env_h texels (rgb, 0), row 0 the zenith, sanitised on upload
+    const EnvCell* env_table;   // env_gw x env_gh alias-table cells over the downsampled luminance grid
+    uint32_t env_w, env_h, env_gw, env_gh;
+    float env_intensity, env_cos_yaw, env_sin_yaw;
+    uint32_t env_uniform;       // ST_ENV_UNIFORM_SAMPLING: GI samples the sky as it does for the atmosphere
 };
 
 }  // namespace st
