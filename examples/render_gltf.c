@@ -6,7 +6,10 @@
  *   cc -std=c99 -D__HIP_PLATFORM_AMD__ -I include -I /opt/rocm/include examples/render_gltf.c \
  *      -L strolle_amd/csrc -lstrolle_hip -L /opt/rocm/lib -lamdhip64 -lm -Wl,-rpath,$PWD/strolle_amd/csrc -o render_gltf
  *   ./render_gltf scene.glb out.ppm [width height frames] [--env sky.hdr [intensity]]
+ *                 [--tonemap none|reinhard|reinhard-lum|aces|neutral] [--exposure EV] [--auto-exposure]
  * --env lights the scene with an equirectangular Radiance .hdr map instead of the atmosphere (st_decode_hdr + st_environment_set).
+ * --tonemap, --exposure and --auto-exposure set the camera's display transform (st_camera_set_display): without them the 8-bit output
+ * clips every channel at 1, as before. With --auto-exposure, --exposure is the compensation in EV.
  */
 #include <hip/hip_runtime_api.h>
 #include <math.h>
@@ -82,15 +85,28 @@ int main(int argc, char** argv) {
     const char* env_path = NULL;
     float env_intensity = 1.0f;
     const char* pos[5] = {NULL, NULL, NULL, NULL, NULL};
-    int npos = 0, i;
+    const char* tonemap_names[5] = {"none", "reinhard", "reinhard-lum", "aces", "neutral"};
+    int npos = 0, i, display = 0, tonemap = ST_TONEMAP_NONE, auto_exposure = 0;
+    float exposure_ev = 0.0f;
     for (i = 1; i < argc; i++) {
-        if (strcmp(argv[i], "--env") == 0 && i + 1 < argc) {
+        if (strcmp(argv[i], "--tonemap") == 0 && i + 1 < argc) {
+            int k, found = 0;
+            ++i;
+            for (k = 0; k < 5; k++) if (strcmp(argv[i], tonemap_names[k]) == 0) { tonemap = k; found = 1; }
+            if (!found) { fprintf(stderr, "unknown tonemap %s\n", argv[i]); return 2; }
+            display = 1;
+        } else if (strcmp(argv[i], "--exposure") == 0 && i + 1 < argc) {
+            exposure_ev = strtof(argv[++i], NULL); display = 1;
+        } else if (strcmp(argv[i], "--auto-exposure") == 0) {
+            auto_exposure = 1; display = 1;
+        } else if (strcmp(argv[i], "--env") == 0 && i + 1 < argc) {
             env_path = argv[++i];
             if (i + 1 < argc) { char* end; const float v = strtof(argv[i + 1], &end); if (end != argv[i + 1] && *end == '\0') { env_intensity = v; i++; } }
         } else if (npos < 5) pos[npos++] = argv[i];
     }
     if (npos < 2) {
-        fprintf(stderr, "usage: %s scene.gltf|scene.glb out.ppm [width height frames] [--env sky.hdr [intensity]]\n", argv[0]);
+        fprintf(stderr, "usage: %s scene.gltf|scene.glb out.ppm [width height frames] [--env sky.hdr [intensity]] "
+                        "[--tonemap none|reinhard|reinhard-lum|aces|neutral] [--exposure EV] [--auto-exposure]\n", argv[0]);
         return 2;
     }
     const uint32_t width = npos > 2 ? (uint32_t)atoi(pos[2]) : 640u, height = npos > 3 ? (uint32_t)atoi(pos[3]) : 360u;
@@ -129,6 +145,16 @@ int main(int argc, char** argv) {
     StHandle cam = 0;
     CHECK(st_camera_create(engine, &camera, &cam));
     CHECK(st_camera_set_output_format(engine, cam, ST_FORMAT_RGBA8_UNORM_SRGB));        /* what a swap chain would hold */
+    if (display) {                                                                      /* exposure + tone mapping before the 8-bit store */
+        StDisplayDesc d;
+        memset(&d, 0, sizeof d);
+        d.struct_size = sizeof d; d.tonemap = (uint32_t)tonemap; d.exposure_ev = exposure_ev;
+        d.flags = auto_exposure ? ST_DISPLAY_AUTO_EXPOSURE : 0u;
+        d.ev_min = -12.0f; d.ev_max = 8.0f; d.low_fraction = 0.1f; d.high_fraction = 0.9f;   /* the metering range and the ranks kept */
+        d.max_ev_step_up = 1.0f; d.max_ev_step_down = 1.0f;                                   /* adaptation: 1 EV per frame at most */
+        CHECK(st_camera_set_display(engine, cam, &d));
+        fprintf(stderr, "display: tonemap %s, %s exposure %g EV\n", tonemap_names[tonemap], auto_exposure ? "auto," : "manual", exposure_ev);
+    }
 
     /* The present path of the Rust facade (rust/strolle-hip/src/present.rs), in C: two device frames and two page-locked
      * host frames alternate; frame N's copy to the host is enqueued behind its composition and runs while frame N+1

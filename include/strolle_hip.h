@@ -395,6 +395,69 @@ int st_debug_environment_pdf(StEngine* e, const float* dirs_device, uint32_t n, 
 int st_debug_environment_sanitized(StEngine* e, uint64_t* texels);
 int st_debug_environment_table(StEngine* e, void* table, size_t capacity_bytes, uint32_t* cells_x, uint32_t* cells_y);
 
+/* ---- display transforms (NEW seam): exposure, tone mapping and auto-exposure of what a camera writes to its output (st_display.cpp,
+ * k_display.hip). What a swap chain, a PPM or an LDR view target shows: without it the 8-bit formats clamp the HDR colour at 1.
+ * - Scope: the setting belongs to the camera and takes effect at its next st_render_camera. Only what is written to `out_device` changes:
+ *   AOVs, scene queries, the internal planes and the HDR history are not affected. BVH-heatmap frames are false colour and stored as
+ *   without a display; every other mode (Reference included) passes through it. desc == NULL turns it off: the output is then exactly
+ *   what it is without a display, and the composing kernels are the same ones. The setting survives st_camera_update and
+ *   st_engine_set_arithmetic.
+ * - Input: c = the composed colour the RGBA32F output holds without a display. Luminance Y = 0.2126 r + 0.7152 g + 0.0722 b, evaluated left
+ *   to right in float32 (no fused multiply-add in either build; so is everything below).
+ * - Exposure: manual: s = 2^exposure_ev, computed on the host in double and rounded to float. Auto: s = 0.18 * 2^(exposure_ev - adapted_ev),
+ *   in float on the device. e = c * s per channel.
+ * - Operators (float32, in this order; every operator except NONE first takes max(x, 0) per channel, which turns NaN into 0):
+ *     NONE: e. The float formats store it unclamped; the 8-bit formats clamp as always.
+ *     REINHARD: e / (1 + e) per channel.   REINHARD_LUMINANCE: e / (1 + Y(e)).
+ *     ACES_FITTED (Hill's RRT + ODT fit): v = M_in e; v = (v (v + 0.0245786) - 0.000090537) / (v (0.983729 v + 0.4329510) + 0.238081);
+ *       clamp(M_out v, 0, 1). Matrices applied row by row, each row's sum left to right: M_in = [[0.59719, 0.35458, 0.04823],
+ *       [0.07600, 0.90834, 0.01566], [0.02840, 0.13383, 0.83777]], M_out = [[1.60475, -0.53108, -0.07367], [-0.10208, 1.10813, -0.00605],
+ *       [-0.00327, -0.07276, 1.07602]].
+ *     PBR_NEUTRAL (Khronos): x = min(r, g, b); offset = x < 0.08 ? x - 6.25 x x : 0.04; e -= offset; peak = max(r, g, b); if peak < 0.76
+ *       the result is e. Else np = 1 - 0.24 * 0.24 / (peak + 0.24 - 0.76); e *= np / peak; g = 1 - 1 / (0.15 (peak - np) + 1); the
+ *       result is e (1 - g) + np g.
+ *   The result then goes through the camera's output format as always (st_camera_set_output_format); alpha stays 1.
+ * - Auto-exposure metering: every pixel the frame composes. Bin k of 64 spans log2 Y in ev_min + [k, k + 1) (ev_max - ev_min) / 64, the
+ *   bin index being floor((log2 Y - ev_min) * (64 / (ev_max - ev_min))) in float; Y not > 0 (NaN included) is bin 0, values out of range
+ *   (+inf included) go to bin 0 or 63. With N pixels sorted by bin, those of rank [floor(low_fraction N), ceil(high_fraction N)) are kept,
+ *   a bin at either end in part; metered_ev = the count-weighted mean of the kept bins' centres (in double, rounded to float). The first
+ *   metered frame after st_camera_set_display turns auto on (from off) sets adapted_ev = metered_ev; later frames move adapted_ev to
+ *   metered_ev, by at most max_ev_step_up up and max_ev_step_down down per rendered frame (0: no limit; a move within the limit lands on
+ *   metered_ev exactly). Frame N's metering sets the s of frame N + 1 (one frame of lag); the first frame after auto is turned on uses
+ *   adapted_ev = log2(0.18), so s = 2^exposure_ev. A frame that keeps no pixel changes nothing. Changing other fields while auto stays on
+ *   keeps the adapted state. The metering is a histogram per workgroup in LDS, added to (one of 64 replicas of) the camera's device histogram
+ *   with integer atomics (reproducible bit for bit), and a one-workgroup kernel behind the frame on the same stream: no host sync, no read-back. Frames of one
+ *   camera finalize in order also when the caller changes streams between them.
+ * - Tiles: manual exposure works with windows (st_camera_set_window, st_dist_set_partition, st_dist_set_grid): gathered tiles equal the
+ *   single-engine frame bit for bit. Auto-exposure would meter each rank's tile on its own, so auto together with a window is
+ *   ST_ERR_INVALID_ARGUMENT from whichever of the two setters comes second. To share one exposure, rank 0 runs auto on a full-frame
+ *   camera, reads st_camera_exposure and hands scale's EV (log2 scale) to the other ranks, which set it manually.
+ * - Errors: ST_ERR_INVALID_ARGUMENT for a null pointer (except desc), a wrong struct_size, an unknown tonemap value or unknown flag bits, a
+ *   non-finite field, and with auto on: ev_min >= ev_max, fractions outside 0 <= low_fraction < high_fraction <= 1, or a negative step
+ *   limit (with auto off those fields are stored unchecked). An unknown camera is ST_ERR_UNKNOWN_CAMERA. Setting and getting are host work
+ *   and valid on a host-only engine; st_camera_exposure and st_debug_camera_histogram return ST_ERR_NO_DEVICE there. */
+enum StTonemap { ST_TONEMAP_NONE = 0, ST_TONEMAP_REINHARD = 1, ST_TONEMAP_REINHARD_LUMINANCE = 2, ST_TONEMAP_ACES_FITTED = 3,
+                 ST_TONEMAP_PBR_NEUTRAL = 4 };
+enum { ST_DISPLAY_AUTO_EXPOSURE = 1 };
+typedef struct StDisplayDesc {             /* 40 B */
+    uint32_t struct_size;                  /* sizeof(StDisplayDesc) */
+    uint32_t tonemap;                      /* StTonemap */
+    uint32_t flags;                        /* ST_DISPLAY_* */
+    float exposure_ev;                     /* manual: s = 2^exposure_ev; auto: compensation in EV */
+    float ev_min, ev_max;                  /* auto: histogram range of log2 luminance */
+    float low_fraction, high_fraction;     /* auto: pixels kept are those ranked in [low, high) of the sorted luminances */
+    float max_ev_step_up, max_ev_step_down;   /* auto: most the adapted EV may rise / fall per rendered frame; 0 = no limit */
+} StDisplayDesc;
+int st_camera_set_display(StEngine* e, StHandle camera, const StDisplayDesc* desc);   /* NULL = off */
+/* the last desc set (a zeroed desc with struct_size when none was) and whether the display is on; either pointer may be NULL */
+int st_camera_get_display(StEngine* e, StHandle camera, StDisplayDesc* out, int* enabled);
+/* Blocking: the camera's exposure as the device holds it after its last render (any pointer may be NULL). Display off: scale 1, metered
+ * and adapted NaN. Manual: 2^exposure_ev, NaN, NaN. Auto: the scale the next frame uses, the last metered EV (NaN before the first
+ * metered frame) and the adapted EV. */
+int st_camera_exposure(StEngine* e, StHandle camera, float* scale, float* metered_ev, float* adapted_ev);
+/* Blocking debug seam: the 64 bins metered from the camera's last rendered auto-exposure frame (zeros before one). */
+int st_debug_camera_histogram(StEngine* e, StHandle camera, uint32_t bins[64]);
+
 /* ---- multi-GPU behind the boundary (NEW seam; SURVEY.md section 8e, BASELINE.json configs 4 and 5). One process per GPU, one
  * engine per process, the scene replicated; the frame is cut into tiles, every rank renders its tile (+ an apron of redundant
  * pixels in Image mode, whose passes read neighbours) with absolute pixel coordinates, and the ONE collective of the path

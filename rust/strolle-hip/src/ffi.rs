@@ -212,6 +212,34 @@ extern "C" {
     pub fn st_debug_environment_table(e: *mut StEngine, table: *mut c_void, capacity_bytes: usize, cells_x: *mut u32, cells_y: *mut u32) -> i32;
 }
 
+// display transforms (include/strolle_hip.h "display transforms"): exposure, tone mapping and auto-exposure of a camera's output
+pub const ST_TONEMAP_NONE: u32 = 0;
+pub const ST_TONEMAP_REINHARD: u32 = 1;
+pub const ST_TONEMAP_REINHARD_LUMINANCE: u32 = 2;
+pub const ST_TONEMAP_ACES_FITTED: u32 = 3;
+pub const ST_TONEMAP_PBR_NEUTRAL: u32 = 4;
+pub const ST_DISPLAY_AUTO_EXPOSURE: u32 = 1;
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct StDisplayDesc {
+    pub struct_size: u32,
+    pub tonemap: u32,
+    pub flags: u32,
+    pub exposure_ev: f32,
+    pub ev_min: f32,
+    pub ev_max: f32,
+    pub low_fraction: f32,
+    pub high_fraction: f32,
+    pub max_ev_step_up: f32,
+    pub max_ev_step_down: f32,
+}
+extern "C" {
+    pub fn st_camera_set_display(e: *mut StEngine, camera: u64, desc: *const StDisplayDesc) -> i32; // null = off
+    pub fn st_camera_get_display(e: *mut StEngine, camera: u64, out: *mut StDisplayDesc, enabled: *mut i32) -> i32;
+    pub fn st_camera_exposure(e: *mut StEngine, camera: u64, scale: *mut f32, metered_ev: *mut f32, adapted_ev: *mut f32) -> i32;
+    pub fn st_debug_camera_histogram(e: *mut StEngine, camera: u64, bins: *mut u32) -> i32;
+}
+
 // ---- the HIP runtime, as far as the staging-copy present needs it (libamdhip64)
 pub type hipStream_t = *mut c_void;
 extern "C" {

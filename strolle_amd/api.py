@@ -121,6 +121,33 @@ def environment_desc(intensity: float = 1.0, yaw: float = 0.0, keep_sun: bool = 
                              float(intensity), float(yaw))
 
 
+class Tonemap(enum.IntEnum):
+    """include/strolle_hip.h StTonemap: the operator of a camera's display transform"""
+    NONE = 0
+    REINHARD = 1
+    REINHARD_LUMINANCE = 2
+    ACES_FITTED = 3
+    PBR_NEUTRAL = 4
+
+
+class StDisplayDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("tonemap", C.c_uint32), ("flags", C.c_uint32), ("exposure_ev", C.c_float),
+                ("ev_min", C.c_float), ("ev_max", C.c_float), ("low_fraction", C.c_float), ("high_fraction", C.c_float),
+                ("max_ev_step_up", C.c_float), ("max_ev_step_down", C.c_float)]
+
+
+DISPLAY_AUTO_EXPOSURE = 1
+DISPLAY_BINS = 64
+
+
+def display_desc(tonemap=Tonemap.NONE, exposure_ev: float = 0.0, auto_exposure: bool = False, ev_min: float = -8.0, ev_max: float = 8.0,
+                 low_fraction: float = 0.1, high_fraction: float = 0.9, max_ev_step_up: float = 0.0, max_ev_step_down: float = 0.0) -> StDisplayDesc:
+    """A StDisplayDesc. Manual: scale = 2^exposure_ev. auto_exposure: exposure_ev is the compensation, the rest meters and adapts
+    (include/strolle_hip.h "display transforms")."""
+    return StDisplayDesc(C.sizeof(StDisplayDesc), int(tonemap), DISPLAY_AUTO_EXPOSURE if auto_exposure else 0, float(exposure_ev),
+                         float(ev_min), float(ev_max), float(low_fraction), float(high_fraction), float(max_ev_step_up), float(max_ev_step_down))
+
+
 class StRay(C.Structure):
     """include/strolle_hip.h StRay (32 B): hits count for 0 < t < t_max; the direction is used as given (t in units of |direction|)."""
     _fields_ = [("origin", C.c_float * 3), ("t_max", C.c_float), ("direction", C.c_float * 3), ("_pad", C.c_uint32)]
@@ -424,6 +451,11 @@ class _Binding:
             self.debug_environment_pdf = fn("debug_environment_pdf", [vp, vp, u32, vp, vp])
             self.debug_environment_sanitized = fn("debug_environment_sanitized", [vp, P(u64)])
             self.debug_environment_table = fn("debug_environment_table", [vp, vp, sz, P(u32), P(u32)])
+        if hasattr(lib, prefix + "camera_set_display"):   # display transforms (likewise absent from an older library)
+            self.camera_set_display = fn("camera_set_display", [vp, u64, P(StDisplayDesc)])
+            self.camera_get_display = fn("camera_get_display", [vp, u64, P(StDisplayDesc), P(i32)])
+            self.camera_exposure = fn("camera_exposure", [vp, u64, P(C.c_float), P(C.c_float), P(C.c_float)])
+            self.debug_camera_histogram = fn("debug_camera_histogram", [vp, u64, P(u32)])
         if hasattr(lib, prefix + "mesh_set_skin"):
             self.mesh_set_skin = fn("mesh_set_skin", [vp, u64, vp, sz, u32])
         if has_device:
@@ -825,6 +857,31 @@ class Engine(EngineBase):
         out = np.zeros(n.value, np.float32)
         self._check(self._b.debug_read_posed(self._h, instance, out.ctypes.data_as(C.POINTER(C.c_float)), n.value, C.byref(n)))
         return out.reshape(-1, 24)
+
+    # ---- display transforms (include/strolle_hip.h "display transforms"): take effect at the camera's next render
+    def set_display(self, camera: int, desc: Optional[StDisplayDesc] = None, **kw):
+        """st_camera_set_display: a StDisplayDesc, or display_desc(**kw) when keywords are given; neither = off (the output as without a display)."""
+        if desc is None and kw:
+            desc = display_desc(**kw)
+        self._check(self._b.camera_set_display(self._h, camera, C.byref(desc) if desc is not None else None))
+
+    def display(self, camera: int):
+        """st_camera_get_display: (the last StDisplayDesc set, whether the display is on)."""
+        d, on = StDisplayDesc(), C.c_int()
+        self._check(self._b.camera_get_display(self._h, camera, C.byref(d), C.byref(on)))
+        return d, bool(on.value)
+
+    def exposure(self, camera: int):
+        """st_camera_exposure (blocking): (scale the next frame uses, metered EV, adapted EV) as the device holds them."""
+        s, m, a = C.c_float(), C.c_float(), C.c_float()
+        self._check(self._b.camera_exposure(self._h, camera, C.byref(s), C.byref(m), C.byref(a)))
+        return s.value, m.value, a.value
+
+    def camera_histogram(self, camera: int) -> np.ndarray:
+        """st_debug_camera_histogram (blocking): the 64 bins metered from the camera's last auto-exposure frame."""
+        out = np.zeros(DISPLAY_BINS, np.uint32)
+        self._check(self._b.debug_camera_histogram(self._h, camera, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
 
     # ---- environment lighting (include/strolle_hip.h "environment lighting"): takes effect at the next tick
     def set_environment(self, texels, intensity: float = 1.0, yaw: float = 0.0, keep_sun: bool = False, uniform: bool = False):

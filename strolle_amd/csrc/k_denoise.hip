@@ -412,21 +412,31 @@ ST_D float4 signal_end(const WaveletSignal& s) { return wavelet_resolve(s.sr, s.
 // byte table -> store sat behind the last round with nothing left to overlap it (measured: 119 us against 48 + 51 us for
 // the two separate launches). The sum's association differs from compose_pixel's, hence fast build only.
 // `keep_colours` == 0 (the lean frame) leaves the pass's own output planes unwritten: nothing but composition reads them.
-struct ComposeArgs { void* out; uint32_t format, camera_mode, keep_colours; };
+struct ComposeArgs { void* out; uint32_t format, camera_mode, keep_colours; DisplayArgs display; };
 #ifndef ST_FAR_COMPOSE_WAVES
 #define ST_FAR_COMPOSE_WAVES 5  // the six floats composition carries through the gather rounds do not fit the 80 registers of 6 waves per SIMD without spilling
 #endif
-template <bool COMPOSE>
+// DISPLAY (with COMPOSE): the camera's display transform and its metering (st_passes.h store_display); the pixel's work then sits in a
+// block every lane leaves by `break`, so that the whole workgroup reaches the metering's barriers. Without it the lanes return where the
+// parent's kernel returns, and the code is the parent's.
+template <bool COMPOSE, bool DISPLAY = false>
 __global__ __launch_bounds__(kBlockThreads, COMPOSE ? ST_FAR_COMPOSE_WAVES : 6) void k_denoise_wavelet_far(const KArgs a, uint32_t stride, float strength, const float4* di_in, float4* di_out, const float4* gi_in, float4* gi_out, const ComposeArgs co) {
+    __shared__ uint32_t s_hist[DISPLAY ? kDisplayBins : 1];
+    const bool meter = DISPLAY && co.display.meter;
+    if (meter) display_meter_begin(s_hist);
+    const float scale = DISPLAY ? display_scale(co.display) : 1.0f;
+    do {
     U2 pos;
-    if (!resolve_gid(a, false, &pos) || !owns_pixel(a, pos)) return;
+    if (!resolve_gid(a, false, &pos) || !owns_pixel(a, pos)) { if (DISPLAY) break; return; }
     const uint32_t center = pos.y * a.width + pos.x;
     const float4 csn = a.sn[center];
     const float4 cdi = di_in[center];
     const bool store = !COMPOSE || co.keep_colours != 0u;
     if (csn.w == 0.0f) {  // sky
         if (store) di_out[center] = cdi;
-        if (COMPOSE) store_output(co.out, center, f4(xyz(cdi), 1.0f), co.format);  // frame_composition.rs: depth == 0 shows the direct colour
+        if (COMPOSE && DISPLAY) store_display<DISPLAY>(co.out, center, f4(xyz(cdi), 1.0f), co.format, co.display, scale, s_hist);
+        else if (COMPOSE) store_output(co.out, center, f4(xyz(cdi), 1.0f), co.format);  // frame_composition.rs: depth == 0 shows the direct colour
+        if (DISPLAY) break;
         return;
     }
     V3 c_base = v3s(0.0f), c_add = v3s(0.0f);
@@ -479,8 +489,11 @@ __global__ __launch_bounds__(kBlockThreads, COMPOSE ? ST_FAR_COMPOSE_WAVES : 6) 
         for (int t = 0; t < 8; t++) if (dw[t] != 0.0f) signal_tap(sg, tap[t], dw[t], nw[t]);
         const float4 res_gi = signal_end(sg);
         if (store) gi_out[center] = res_gi;
-        if (COMPOSE) store_output(co.out, center, f4(c_add + (xyz(res_di) + xyz(res_gi)) * c_base, 1.0f), co.format);
+        if (COMPOSE && DISPLAY) store_display<DISPLAY>(co.out, center, f4(c_add + (xyz(res_di) + xyz(res_gi)) * c_base, 1.0f), co.format, co.display, scale, s_hist);
+        else if (COMPOSE) store_output(co.out, center, f4(c_add + (xyz(res_di) + xyz(res_gi)) * c_base, 1.0f), co.format);
     }
+    } while (false);
+    if (meter) display_meter_end(s_hist, co.display.hist);
 }
 
 void launch_denoise_wavelet(const KArgs& a, uint32_t stride, float strength, const float4* di_in, float4* di_out, const float4* gi_in,
@@ -490,12 +503,14 @@ void launch_denoise_wavelet(const KArgs& a, uint32_t stride, float strength, con
     if (stride == 1u) ST_KLAUNCH((k_denoise_wavelet_lds<1>), dim3(blocks), dim3(kWvThreads), s, a, strength, di_in, di_out, gi_in, gi_out);
     else if (stride == 2u) ST_KLAUNCH((k_denoise_wavelet_lds<2>), dim3(blocks), dim3(kWvThreads), s, a, strength, di_in, di_out, gi_in, gi_out);
     else if (stride == 4u) ST_KLAUNCH((k_denoise_wavelet_lds<4>), dim3(blocks), dim3(kWvThreads), s, a, strength, di_in, di_out, gi_in, gi_out);
-    else ST_LAUNCH(k_denoise_wavelet_far<false>, false, s, a, stride, strength, di_in, di_out, gi_in, gi_out, ComposeArgs{nullptr, 0u, 0u, 1u});
+    else ST_LAUNCH(k_denoise_wavelet_far<false>, false, s, a, stride, strength, di_in, di_out, gi_in, gi_out, ComposeArgs{nullptr, 0u, 0u, 1u, DisplayArgs{}});
 }
 // a gather pass (stride 8 or 16) with frame_composition.rs appended (the last pass of the chain)
 void launch_denoise_wavelet_compose(const KArgs& a, uint32_t stride, float strength, const float4* di_in, float4* di_out, const float4* gi_in, float4* gi_out,
-                                    uint32_t camera_mode, void* out, uint32_t format, bool keep_colours, hipStream_t s) {
-    ST_LAUNCH(k_denoise_wavelet_far<true>, false, s, a, stride, strength, di_in, di_out, gi_in, gi_out, ComposeArgs{out, format, camera_mode, keep_colours ? 1u : 0u});
+                                    uint32_t camera_mode, void* out, uint32_t format, bool keep_colours, const DisplayArgs& d, hipStream_t s) {
+    const ComposeArgs co{out, format, camera_mode, keep_colours ? 1u : 0u, d};
+    if (d.on) ST_LAUNCH((k_denoise_wavelet_far<true, true>), false, s, a, stride, strength, di_in, di_out, gi_in, gi_out, co);
+    else ST_LAUNCH(k_denoise_wavelet_far<true>, false, s, a, stride, strength, di_in, di_out, gi_in, gi_out, co);
 }
 void launch_denoise_wavelet_12(const KArgs& a, float strength0, float strength1, const float4* di_in, float4* di_mid, float4* di_out, const float4* gi_in,
                                float4* gi_mid, float4* gi_out, hipStream_t s) {

@@ -276,14 +276,30 @@ void launch_spatial_trace(const KArgs& a, const float4* buf_d0, const float4* bu
 
 // ---------------------------------------------------------------- frame_composition.rs:18-82 as a compute pass into an RGBA32F buffer
 // `format` (StOutputFormat) is what the reference leaves to the render target's format (camera.rs:170-175 viewport.format).
-__global__ ST_KERNEL_BOUNDS void k_composition(const KArgs a, uint32_t camera_mode, const float4* di_diff, const float4* gi_diff, void* out, uint32_t format) {
+// DISPLAY: the camera's display transform (st_passes.h store_display) between composition and the store, and its metering; without it
+// this is the parent's kernel, and `d` is never read.
+template <bool DISPLAY>
+__global__ ST_KERNEL_BOUNDS void k_composition(const KArgs a, uint32_t camera_mode, const float4* di_diff, const float4* gi_diff, void* out, uint32_t format, const DisplayArgs d) {
+    if (!DISPLAY) {
+        U2 pos;
+        if (!resolve_gid(a, false, &pos) || !owns_pixel(a, pos)) return;
+        const float4 c = compose_pixel(a, pos, camera_mode, tex_read(di_diff, a, pos), tex_read(gi_diff, a, pos));
+        store_output(out, pos.y * a.width + pos.x, c, format);
+        return;
+    }
+    __shared__ uint32_t s_hist[kDisplayBins];
+    const bool meter = DISPLAY && d.meter;
+    if (meter) display_meter_begin(s_hist);
     U2 pos;
-    if (!resolve_gid(a, false, &pos) || !owns_pixel(a, pos)) return;
-    const float4 c = compose_pixel(a, pos, camera_mode, tex_read(di_diff, a, pos), tex_read(gi_diff, a, pos));
-    store_output(out, pos.y * a.width + pos.x, c, format);
+    if (resolve_gid(a, false, &pos) && owns_pixel(a, pos)) {
+        const float4 c = compose_pixel(a, pos, camera_mode, tex_read(di_diff, a, pos), tex_read(gi_diff, a, pos));
+        store_display<DISPLAY>(out, pos.y * a.width + pos.x, c, format, d, display_scale(d), s_hist);
+    }
+    if (meter) display_meter_end(s_hist, d.hist);
 }
-void launch_composition(const KArgs& a, uint32_t camera_mode, const float4* di_diff, const float4* gi_diff, void* out, uint32_t format, hipStream_t s) {
-    ST_LAUNCH(k_composition, false, s, a, camera_mode, di_diff, gi_diff, out, format);
+void launch_composition(const KArgs& a, uint32_t camera_mode, const float4* di_diff, const float4* gi_diff, void* out, uint32_t format, const DisplayArgs& d, hipStream_t s) {
+    if (d.on) ST_LAUNCH(k_composition<true>, false, s, a, camera_mode, di_diff, gi_diff, out, format, d);
+    else ST_LAUNCH(k_composition<false>, false, s, a, camera_mode, di_diff, gi_diff, out, format, d);
 }
 
 }  // namespace ST_KNS

@@ -230,7 +230,7 @@ int st_camera_delete(StEngine* e, StHandle h) {
     Engine* en = E(e);
     auto it = en->cameras.find(h);
     if (it == en->cameras.end()) return ST_OK;
-    if (en->has_device) { ST_HIP(hipSetDevice(en->device)); ST_HIP(hipDeviceSynchronize()); Engine::release_camera(*it->second); }
+    if (en->has_device) { ST_HIP(hipSetDevice(en->device)); ST_HIP(hipDeviceSynchronize()); Engine::release_camera(*it->second); Engine::release_display(*it->second); }
     en->dist_forget_camera(h);
     en->cameras.erase(it);
     return ST_OK;
@@ -246,6 +246,8 @@ int st_camera_set_window(StEngine* e, StHandle h, uint32_t x0, uint32_t y0, uint
     ST_REQUIRE(x0 < x1 && x1 <= s.desc.width, "bad column window");
     // half-resolution passes work on 2x1 cells in tiles of 8 cells: a window starts and ends on a multiple of 16 pixels (or at the frame's edge)
     ST_REQUIRE(x0 % 16u == 0u && (x1 % 16u == 0u || x1 == s.desc.width), "window columns must be multiples of 16 (or the frame's right edge)");
+    const bool full = x0 == 0u && y0 == 0u && x1 == s.desc.width && y1 == s.desc.height;
+    ST_REQUIRE(full || !s.display_auto(), "a window on a camera with auto-exposure would meter the tile alone (include/strolle_hip.h \"display transforms\")");
     s.row0 = y0; s.row1 = y1; s.col0 = x0; s.col1 = x1;
     return ST_OK;
 }
@@ -258,6 +260,35 @@ int st_camera_set_output_format(StEngine* e, StHandle h, int format) {
     ST_REQUIRE(format >= ST_FORMAT_RGBA32F && format <= ST_FORMAT_BGRA8_UNORM_SRGB, "unknown output format");
     it->second->out_format = (uint32_t)format;
     return ST_OK;
+}
+
+// ---- display transforms (st_display.cpp)
+int st_camera_set_display(StEngine* e, StHandle h, const StDisplayDesc* desc) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    return E(e)->set_display(*it->second, desc);
+}
+int st_camera_get_display(StEngine* e, StHandle h, StDisplayDesc* out, int* enabled) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    const CameraState& s = *it->second;
+    if (out) { *out = s.display; out->struct_size = sizeof(StDisplayDesc); }
+    if (enabled) *enabled = s.display_on ? 1 : 0;
+    return ST_OK;
+}
+int st_camera_exposure(StEngine* e, StHandle h, float* scale, float* metered_ev, float* adapted_ev) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    return E(e)->display_exposure(*it->second, scale, metered_ev, adapted_ev);
+}
+int st_debug_camera_histogram(StEngine* e, StHandle h, uint32_t bins[64]) {
+    ST_REQUIRE(e && bins, "null argument");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    return E(e)->display_histogram(*it->second, bins);
 }
 
 int st_tick(StEngine* e, void* stream) { ST_REQUIRE(e, "null engine"); return E(e)->tick(static_cast<hipStream_t>(stream)); }

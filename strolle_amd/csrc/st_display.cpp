@@ -1,0 +1,107 @@
+// st_display.cpp — camera display transforms (include/strolle_hip.h "display transforms"): the setter's checks, the per-frame DisplayArgs
+// and the order of the camera's device exposure state (k_display.hip) across frames and streams. See st_engine.h CameraState.
+#include <cmath>
+
+#include "st_engine.h"
+
+namespace st {
+
+static constexpr double kMidGrey = 0.18;
+
+static int check_display(const StDisplayDesc& d) {
+    if (d.struct_size != sizeof(StDisplayDesc)) return fail(ST_ERR_INVALID_ARGUMENT, "StDisplayDesc.struct_size is not sizeof(StDisplayDesc)");
+    if (d.tonemap > ST_TONEMAP_PBR_NEUTRAL) return fail(ST_ERR_INVALID_ARGUMENT, "unknown tonemap");
+    if ((d.flags & ~(uint32_t)ST_DISPLAY_AUTO_EXPOSURE) != 0u) return fail(ST_ERR_INVALID_ARGUMENT, "unknown display flag bits");
+    for (float v : {d.exposure_ev, d.ev_min, d.ev_max, d.low_fraction, d.high_fraction, d.max_ev_step_up, d.max_ev_step_down})
+        if (!std::isfinite(v)) return fail(ST_ERR_INVALID_ARGUMENT, "a display field is not finite");
+    if (d.flags & ST_DISPLAY_AUTO_EXPOSURE) {
+        if (!(d.ev_min < d.ev_max)) return fail(ST_ERR_INVALID_ARGUMENT, "auto-exposure: ev_min must be below ev_max");
+        if (!(0.0f <= d.low_fraction && d.low_fraction < d.high_fraction && d.high_fraction <= 1.0f))
+            return fail(ST_ERR_INVALID_ARGUMENT, "auto-exposure: fractions must satisfy 0 <= low < high <= 1");
+        if (d.max_ev_step_up < 0.0f || d.max_ev_step_down < 0.0f) return fail(ST_ERR_INVALID_ARGUMENT, "auto-exposure: step limits must be >= 0");
+    }
+    return ST_OK;
+}
+
+int Engine::set_display(CameraState& c, const StDisplayDesc* desc) {
+    if (!desc) { c.display_on = false; return ST_OK; }
+    if (int rc = check_display(*desc)) return rc;
+    const bool auto_now = (desc->flags & ST_DISPLAY_AUTO_EXPOSURE) != 0u;
+    if (auto_now && c.windowed()) return fail(ST_ERR_INVALID_ARGUMENT, "auto-exposure on a camera with a window would meter the tile alone (include/strolle_hip.h \"display transforms\")");
+    if (auto_now && !c.display_auto()) c.display_reset = true;   // off -> on: the adaptation starts over at the next frame
+    c.display = *desc; c.display_on = true;
+    c.display_scale = (float)std::exp2((double)desc->exposure_ev);
+    return ST_OK;
+}
+
+// Before the frame's first launch. Heatmap frames are stored as they are.
+int Engine::display_begin(CameraState& c, hipStream_t stream, bool heatmap, DisplayArgs& d) {
+    d = DisplayArgs{};
+    if (!c.display_on || heatmap) return ST_OK;
+    d.on = 1u; d.tonemap = c.display.tonemap; d.scale = c.display_scale;
+    if (!c.display_auto()) return ST_OK;
+    if (!c.display_state) {
+        if (hipMalloc(&c.display_state, kDisplayBytes) != hipSuccess) { (void)hipGetLastError(); c.display_state = nullptr; return fail(ST_ERR_HIP, "hipMalloc(display state) failed"); }
+        c.display_reset = true;
+    }
+    if (!c.ev_display) ST_HIP(hipEventCreateWithFlags(&c.ev_display, hipEventDisableTiming));
+    // the previous metered frame's finalize ran on another stream: this frame's reads of the state and adds to the histogram come after it
+    if (c.display_pending && c.display_stream != stream) ST_HIP(hipStreamWaitEvent(stream, c.ev_display, 0));
+    if (c.display_reset) {
+        L.launch_display_reset(c.display_state, c.display_scale, (float)std::log2(kMidGrey), stream);
+        c.display_reset = false;
+    }
+    d.meter = 1u;
+    d.state = reinterpret_cast<const float*>(static_cast<const char*>(c.display_state) + kDisplayStateOffset);
+    d.hist = static_cast<uint32_t*>(c.display_state);
+    d.ev_min = c.display.ev_min;
+    d.bins_per_ev = (float)kDisplayBins / (c.display.ev_max - c.display.ev_min);
+    return ST_OK;
+}
+
+int Engine::display_finalize(CameraState& c, hipStream_t stream) {
+    const StDisplayDesc& s = c.display;
+    L.launch_display_finalize(c.display_state, s.ev_min, s.ev_max, s.low_fraction, s.high_fraction, s.max_ev_step_up, s.max_ev_step_down, s.exposure_ev, stream);
+    ST_HIP(hipEventRecord(c.ev_display, stream));
+    c.display_stream = stream; c.display_pending = true;
+    return ST_OK;
+}
+
+int Engine::display_exposure(CameraState& c, float* scale, float* metered_ev, float* adapted_ev) {
+    if (!has_device) return fail(ST_ERR_NO_DEVICE, "st_camera_exposure on a host-only engine");
+    float v[3] = {1.0f, NAN, NAN};
+    if (c.display_on) v[0] = c.display_scale;
+    if (c.display_auto()) {
+        v[2] = (float)std::log2(kMidGrey);
+        if (c.display_state && !c.display_reset) {
+            ST_HIP(hipSetDevice(device));
+            ST_HIP(hipDeviceSynchronize());
+            DisplayState st{};
+            ST_HIP(hipMemcpy(&st, static_cast<const char*>(c.display_state) + kDisplayStateOffset, sizeof(st), hipMemcpyDeviceToHost));
+            v[0] = st.scale; v[1] = st.metered_ev; v[2] = st.adapted_ev;
+        }
+    }
+    if (scale) *scale = v[0];
+    if (metered_ev) *metered_ev = v[1];
+    if (adapted_ev) *adapted_ev = v[2];
+    return ST_OK;
+}
+
+int Engine::display_histogram(CameraState& c, uint32_t* bins) {
+    if (!has_device) return fail(ST_ERR_NO_DEVICE, "st_debug_camera_histogram on a host-only engine");
+    memset(bins, 0, kDisplayBins * sizeof(uint32_t));
+    if (!c.display_state) return ST_OK;
+    ST_HIP(hipSetDevice(device));
+    ST_HIP(hipDeviceSynchronize());
+    ST_HIP(hipMemcpy(bins, static_cast<const char*>(c.display_state) + kDisplayLastOffset, kDisplayBins * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return ST_OK;
+}
+
+// with the device idle (st_camera_delete, ~Engine)
+void Engine::release_display(CameraState& c) {
+    if (c.display_state) (void)hipFree(c.display_state);
+    if (c.ev_display) (void)hipEventDestroy(c.ev_display);
+    c.display_state = nullptr; c.ev_display = nullptr; c.display_stream = nullptr; c.display_pending = false;
+}
+
+}  // namespace st

@@ -283,12 +283,20 @@ static int rect_of(const CameraState& c, const DistState& d, const DistState::Ca
     return dist_partition(c.desc.width, c.desc.height, (uint32_t)d.world, p.cols, (uint32_t)r, out);
 }
 
+// auto-exposure meters the whole frame: a tile window on such a camera is refused (include/strolle_hip.h "display transforms")
+static int display_window_check(const CameraState& c, const StDistRect& w) {
+    const bool full = w.x0 == 0u && w.y0 == 0u && w.x1 == c.desc.width && w.y1 == c.desc.height;
+    if (!full && c.display_auto()) return fail(ST_ERR_INVALID_ARGUMENT, "a tile window on a camera with auto-exposure would meter the tile alone");
+    return ST_OK;
+}
+
 int Engine::dist_set_partition(uint64_t handle, CameraState& c, uint32_t cols, uint32_t apron) {
     if (!dist) return fail(ST_ERR_INVALID_ARGUMENT, "st_dist_init has not been called on this engine");
     // validate first: a request that fails leaves neither a zero rectangle in the map nor the camera's window changed
     StDistRect owned{}, window{};
     if (int rc = dist_partition(c.desc.width, c.desc.height, (uint32_t)dist->world, cols, (uint32_t)dist->rank, &owned)) return rc;
     if (int rc = dist_window(c.desc.width, c.desc.height, &owned, apron, &window)) return rc;
+    if (int rc = display_window_check(c, window)) return rc;
     DistState::CamPart& p = dist->cams[handle];
     p.cols = cols; p.apron = apron; p.owned = owned; p.window = window; p.width = c.desc.width; p.height = c.desc.height; p.has_grid = false;
     c.col0 = p.window.x0; c.col1 = p.window.x1; c.row0 = p.window.y0; c.row1 = p.window.y1;
@@ -303,6 +311,7 @@ int Engine::dist_set_grid(uint64_t handle, CameraState& c, const StDistGrid& gri
     StDistRect owned{}, window{};
     if (int rc = dist_grid_tile(&grid, (uint32_t)dist->rank, &owned)) return rc;
     if (int rc = dist_window(c.desc.width, c.desc.height, &owned, apron, &window)) return rc;
+    if (int rc = display_window_check(c, window)) return rc;
     DistState::CamPart& p = dist->cams[handle];
     p.cols = grid.cols; p.apron = apron; p.owned = owned; p.window = window; p.width = c.desc.width; p.height = c.desc.height; p.has_grid = true; p.grid = grid;
     c.col0 = p.window.x0; c.col1 = p.window.x1; c.row0 = p.window.y0; c.row1 = p.window.y1;

@@ -296,6 +296,17 @@ struct CameraState {
     // the camera as the last render saw it (st_camera_pick casts through the frame on screen, not a later st_camera_update)
     GpuCamera shown{}; uint32_t shown_width = 0, shown_height = 0; bool has_shown = false;
     GpuCamera shown_prev{};   // ... and the camera of the frame before it (that render's KArgs::prev_cam: st_camera_render_aovs' MOTION)
+    // Display transform (st_display.cpp; include/strolle_hip.h "display transforms"). Not part of the per-camera buffers: it survives the
+    // reallocation of st_camera_update. `display_state` (auto-exposure only) is kDisplayBytes of device memory — the histogram the composing
+    // launches add to, the last finalized one, DisplayState — allocated by the first auto frame; `display_reset` asks the next render to
+    // put it back to its first-frame values. `ev_display` is recorded behind each finalize on `display_stream`: a frame on another stream
+    // waits for it first.
+    StDisplayDesc display{}; bool display_on = false, display_reset = false;
+    float display_scale = 1.0f;   // manual: 2^exposure_ev (host double, rounded)
+    void* display_state = nullptr;
+    hipEvent_t ev_display = nullptr; hipStream_t display_stream = nullptr; bool display_pending = false;
+    bool display_auto() const { return display_on && (display.flags & ST_DISPLAY_AUTO_EXPOSURE) != 0u; }
+    bool windowed() const { return row0 != 0u || col0 != 0u || row1 != desc.height || col1 != desc.width; }
 };
 inline size_t plane_texels_per_pixel(int id) {
     if (id >= ST_BUF_DI_RESERVOIRS_0 && id <= ST_BUF_DI_RESERVOIRS_2) return 2;
@@ -664,6 +675,13 @@ struct Engine {
     }
 
     int render(CameraState& c, void* out, hipStream_t stream);
+    // ---- display transforms (st_display.cpp)
+    int set_display(CameraState& c, const StDisplayDesc* desc);
+    int display_begin(CameraState& c, hipStream_t stream, bool heatmap, DisplayArgs& d);   // this frame's DisplayArgs (+ the state's reset / stream order)
+    int display_finalize(CameraState& c, hipStream_t stream);                              // behind a metered frame
+    int display_exposure(CameraState& c, float* scale, float* metered_ev, float* adapted_ev);
+    int display_histogram(CameraState& c, uint32_t* bins);
+    static void release_display(CameraState& c);
     int scene_args(KArgs& a, bool heatmap) const;   // the scene half of KArgs (st_render.cpp): render() and the scene queries
 
     // ---- scene queries (st_query.cpp; include/strolle_hip.h "scene queries")

@@ -43,10 +43,11 @@ ST_LAUNCHER(launch_denoise_variance, (const KArgs& a, float4* di_out, float4* gi
 ST_LAUNCHER(launch_denoise_wavelet, (const KArgs& a, uint32_t stride, float strength, const float4* di_in, float4* di_out, const float4* gi_in, float4* gi_out, hipStream_t s))
 // the last pass of the chain (a gather pass: stride 8 or 16) with frame_composition.rs appended for the same pixel; keep_colours == false:
 // the pass's own output planes stay unwritten (nothing but composition reads them)
-ST_LAUNCHER(launch_denoise_wavelet_compose, (const KArgs& a, uint32_t stride, float strength, const float4* di_in, float4* di_out, const float4* gi_in, float4* gi_out, uint32_t camera_mode, void* out, uint32_t format, bool keep_colours, hipStream_t s))
+ST_LAUNCHER(launch_denoise_wavelet_compose, (const KArgs& a, uint32_t stride, float strength, const float4* di_in, float4* di_out, const float4* gi_in, float4* gi_out, uint32_t camera_mode, void* out, uint32_t format, bool keep_colours, const DisplayArgs& d, hipStream_t s))
 // strides 1 and 2 in one launch: *_mid receive the stride-1 output, *_out the stride-2 output; *_in must not alias either
 ST_LAUNCHER(launch_denoise_wavelet_12, (const KArgs& a, float strength0, float strength1, const float4* di_in, float4* di_mid, float4* di_out, const float4* gi_in, float4* gi_mid, float4* gi_out, hipStream_t s))
-ST_LAUNCHER(launch_composition, (const KArgs& a, uint32_t camera_mode, const float4* di_diff, const float4* gi_diff, void* out, uint32_t format, hipStream_t s))
+// d.on: the camera's display transform (st_passes.h store_display; include/strolle_hip.h "display transforms") in both composing launches
+ST_LAUNCHER(launch_composition, (const KArgs& a, uint32_t camera_mode, const float4* di_diff, const float4* gi_diff, void* out, uint32_t format, const DisplayArgs& d, hipStream_t s))
 // debug seam (st_camera_write_buffer): regenerates the planes this library derives from the reference's — the decoded surface
 // twins (KArgs::sn / psn) from both surface maps
 ST_LAUNCHER(launch_refresh_internal_planes, (const KArgs& a, uint32_t which /* bit 0: sn from sm, bit 1: psn from psm */, hipStream_t s))
@@ -75,3 +76,7 @@ ST_LAUNCHER(launch_aov, (const KArgs& a, float* depth, float4* normal, float4* a
 ST_LAUNCHER(launch_env_upload, (const void* src, size_t pitch, uint32_t w, uint32_t h, uint32_t channels, float4* texels, uint32_t* bad, hipStream_t s))
 ST_LAUNCHER(launch_env_grid, (const float4* texels, uint32_t w, uint32_t h, uint32_t gw, uint32_t gh, float* weights, hipStream_t s))
 ST_LAUNCHER(launch_env_debug, (const KArgs& a, uint32_t what /* 0 eval, 1 sample, 2 pdf */, const float* in, uint32_t n, float* out, hipStream_t s))
+// display transforms (k_display.hip; st_display.cpp): the camera's device exposure state reset to its first-frame values, and the
+// one-workgroup finalize behind a metered frame (histogram -> metered / adapted EV and the next frame's scale; the histogram cleared)
+ST_LAUNCHER(launch_display_reset, (void* state /* kDisplayBytes */, float scale, float adapted_ev, hipStream_t s))
+ST_LAUNCHER(launch_display_finalize, (void* state, float ev_min, float ev_max, float low_fraction, float high_fraction, float step_up, float step_down, float compensation_ev, hipStream_t s))

@@ -176,4 +176,73 @@ ST_D void store_output(void* out, uint32_t at, float4 c, uint32_t format) {
     }
 }
 
+// ---- camera display transform (include/strolle_hip.h "display transforms"; st_display.cpp). Written with FMA contraction off in both
+// builds: the fast build then stores what tests/display_ref.py computes from the same composed colour, as the exact build does.
+ST_D float display_luma(float r, float g, float b) {
+#pragma clang fp contract(off)
+    return 0.2126f * r + 0.7152f * g + 0.0722f * b;
+}
+// the composed colour `c` -> exposed (x `s`) and tone-mapped colour, alpha 1
+ST_D float4 display_transform(float4 c, uint32_t tonemap, float s) {
+#pragma clang fp contract(off)
+    float r = c.x * s, g = c.y * s, b = c.z * s;
+    if (tonemap == 0u) return make_float4(r, g, b, 1.0f);
+    r = fmaxf(r, 0.0f); g = fmaxf(g, 0.0f); b = fmaxf(b, 0.0f);   // (NaN -> 0)
+    if (tonemap == 1u) { r = r / (1.0f + r); g = g / (1.0f + g); b = b / (1.0f + b); }   // Reinhard
+    else if (tonemap == 2u) { const float d = 1.0f + display_luma(r, g, b); r = r / d; g = g / d; b = b / d; }   // Reinhard on luminance
+    else if (tonemap == 3u) {   // ACES fitted (Hill): input matrix, RRT + ODT rational fit, output matrix, clamp
+        const float vr = 0.59719f * r + 0.35458f * g + 0.04823f * b, vg = 0.07600f * r + 0.90834f * g + 0.01566f * b, vb = 0.02840f * r + 0.13383f * g + 0.83777f * b;
+        const float fr = (vr * (vr + 0.0245786f) - 0.000090537f) / (vr * (0.983729f * vr + 0.4329510f) + 0.238081f);
+        const float fg = (vg * (vg + 0.0245786f) - 0.000090537f) / (vg * (0.983729f * vg + 0.4329510f) + 0.238081f);
+        const float fb = (vb * (vb + 0.0245786f) - 0.000090537f) / (vb * (0.983729f * vb + 0.4329510f) + 0.238081f);
+        r = fminf(fmaxf(1.60475f * fr + -0.53108f * fg + -0.07367f * fb, 0.0f), 1.0f);
+        g = fminf(fmaxf(-0.10208f * fr + 1.10813f * fg + -0.00605f * fb, 0.0f), 1.0f);
+        b = fminf(fmaxf(-0.00327f * fr + -0.07276f * fg + 1.07602f * fb, 0.0f), 1.0f);
+    } else {   // Khronos PBR Neutral
+        const float x = fminf(r, fminf(g, b));
+        const float offset = x < 0.08f ? x - 6.25f * x * x : 0.04f;
+        r = r - offset; g = g - offset; b = b - offset;
+        const float peak = fmaxf(r, fmaxf(g, b));
+        if (!(peak < 0.76f)) {
+            const float d = 0.24f;
+            const float np = 1.0f - d * d / (peak + d - 0.76f);
+            const float q = np / peak;
+            r = r * q; g = g * q; b = b * q;
+            const float w = 1.0f - 1.0f / (0.15f * (peak - np) + 1.0f);
+            r = r * (1.0f - w) + np * w; g = g * (1.0f - w) + np * w; b = b * (1.0f - w) + np * w;
+        }
+    }
+    return make_float4(r, g, b, 1.0f);
+}
+// the metering bin of a composed colour: log2 of its luminance over [ev_min, ev_max) in 64 bins; Y not > 0 (NaN too) -> bin 0, out of
+// range (+inf too) -> the end bins
+ST_D uint32_t display_bin(float4 c, const DisplayArgs& d) {
+#pragma clang fp contract(off)
+    const float y = display_luma(c.x, c.y, c.z);
+    if (!(y > 0.0f)) return 0u;
+    const float t = floorf((log2f(y) - d.ev_min) * d.bins_per_ev);
+    return (uint32_t)fminf(fmaxf(t, 0.0f), (float)(kDisplayBins - 1u));
+}
+// The exposure scale of this launch: the host's (manual) or what the previous frame's finalize left in the camera's state (auto).
+ST_D float display_scale(const DisplayArgs& d) { return d.meter ? d.state[0] : d.scale; }
+// Per-workgroup metering: a 64-bin histogram in LDS, added to one replica of the camera's device histogram (st_types.h kDisplayReplicas) by
+// one 64-lane atomic add of 256 contiguous bytes (integer sums: the counts do not depend on arrival order). Every thread of the block calls
+// begin and end.
+ST_D void display_meter_begin(uint32_t* lds) {
+    if (threadIdx.x < kDisplayBins) lds[threadIdx.x] = 0u;
+    __syncthreads();
+}
+ST_D void display_meter_end(uint32_t* lds, uint32_t* hist) {
+    __syncthreads();
+    if (threadIdx.x < kDisplayBins) atomicAdd(hist + (blockIdx.x % kDisplayReplicas) * kDisplayBins + threadIdx.x, lds[threadIdx.x]);
+}
+// what a composing kernel writes for one pixel: the colour as composed (DISPLAY == false: the parent's store), else the display
+// transform of it, metered when the camera runs auto-exposure
+template <bool DISPLAY>
+ST_D void store_display(void* out, uint32_t at, float4 c, uint32_t format, const DisplayArgs& d, float s, uint32_t* lds) {
+    if (!DISPLAY) { store_output(out, at, c, format); return; }
+    if (d.meter) atomicAdd(lds + display_bin(c, d), 1u);
+    store_output(out, at, display_transform(c, d.tonemap, s), format);
+}
+
 }  // namespace st

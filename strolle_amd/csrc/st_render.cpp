@@ -166,6 +166,8 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
     if (!scene_uploaded) return fail(ST_ERR_INVALID_ARGUMENT, "st_tick must precede st_render_camera");
     ST_HIP(hipSetDevice(device));
     if (int rc = reader_begin(stream, true)) return rc;
+    DisplayArgs disp{};   // the camera's display transform (st_display.cpp): both composing launches take it
+    if (int rc = display_begin(c, stream, c.desc.mode == ST_MODE_BVH_HEATMAP, disp)) return rc;
     const bool alt = c.frame % 2u == 1u;
     c.last_lean = 0u; c.last_lean_composed = false;
     KArgs a{};
@@ -414,7 +416,7 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
                 if (nth == 4u && compose_in_wavelet) {
                     present_guard(c, out, cur); dist_guard(c.handle, out, cur);
                     run(KS_DENOISE_WAVELET_COMPOSE, ((uint64_t)ST_PASS_DENOISE_WAVELET_0 << nth) | ST_PASS_COMPOSITION, [&] {
-                        L.launch_denoise_wavelet_compose(a, 1u << nth, (float)(1u + nth), di[in_ix[nth]], di[out_ix[nth]], gi[in_ix[nth]], gi[out_ix[nth]], mode, out, c.out_format, a.lean == 0u, cur); });
+                        L.launch_denoise_wavelet_compose(a, 1u << nth, (float)(1u + nth), di[in_ix[nth]], di[out_ix[nth]], gi[in_ix[nth]], gi[out_ix[nth]], mode, out, c.out_format, a.lean == 0u, disp, cur); });
                     composed = true;
                     continue;
                 }
@@ -426,7 +428,7 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
             present_guard(c, out, cur); dist_guard(c.handle, out, cur);
             const float4* di_diff = (denoise && (mode == ST_MODE_IMAGE || mode == ST_MODE_DI_DIFFUSE)) ? a.di_diff_curr_colors : a.di_diff_samples;
             const float4* gi_diff = (denoise && (mode == ST_MODE_IMAGE || mode == ST_MODE_GI_DIFFUSE)) ? a.gi_diff_curr_colors : a.gi_diff_samples;
-            run(KS_COMPOSITION, ST_PASS_COMPOSITION, [&] { L.launch_composition(a, mode, di_diff, gi_diff, out, c.out_format, cur); });
+            run(KS_COMPOSITION, ST_PASS_COMPOSITION, [&] { L.launch_composition(a, mode, di_diff, gi_diff, out, c.out_format, disp, cur); });
             composed = true;
         };
 
@@ -496,8 +498,9 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
         const bool dn = c.desc.denoise != 0u;
         const float4* di_diff = (dn && (mode == ST_MODE_IMAGE || mode == ST_MODE_DI_DIFFUSE)) ? a.di_diff_curr_colors : a.di_diff_samples;
         const float4* gi_diff = (dn && (mode == ST_MODE_IMAGE || mode == ST_MODE_GI_DIFFUSE)) ? a.gi_diff_curr_colors : a.gi_diff_samples;
-        run(KS_COMPOSITION, ST_PASS_COMPOSITION, [&] { L.launch_composition(a, mode, di_diff, gi_diff, out, c.out_format, cur); });
+        run(KS_COMPOSITION, ST_PASS_COMPOSITION, [&] { L.launch_composition(a, mode, di_diff, gi_diff, out, c.out_format, disp, cur); });
     }
+    if (disp.meter && out) if (int rc = display_finalize(c, stream)) return rc;   // every composing launch ran on `stream`
     if (int rc = reader_end(stream, true)) return rc;   // the end of the last frame that reads these copies of the scene and the lights
     profile_close();
     ST_HIP(hipGetLastError());

@@ -62,6 +62,27 @@ constexpr uint32_t kCounterLines = 256;  // ray/byte counters are spread over th
 struct EnvCell { float q; uint32_t alias; float p; };
 static_assert(sizeof(EnvCell) == 12, "an importance cell is 12 B");
 
+// Camera display transform (include/strolle_hip.h "display transforms"; st_display.cpp, k_display.hip). `on` == 0: the composing kernels
+// are the parent's instantiations, which never read the rest. With `meter` set the kernels take the scale from the camera's device state
+// (DisplayState::scale, written by the previous frame's finalize) and add their pixels to `hist`.
+constexpr uint32_t kDisplayBins = 64;
+struct DisplayArgs {
+    uint32_t on, tonemap, meter;
+    float scale;               // manual: 2^exposure_ev (rounded from double on the host)
+    const float* state;        // meter: the DisplayState below
+    uint32_t* hist;            // meter: kDisplayReplicas x kDisplayBins counters, cleared by the finalize kernel
+    float ev_min, bins_per_ev; // meter: bin = floor((log2 Y - ev_min) * bins_per_ev), clamped to [0, 63]
+};
+// One camera's device exposure state (one allocation: hist[kDisplayReplicas][64], last[64], then this). `scale` is what the next frame
+// multiplies by. Workgroup b adds to replica b % kDisplayReplicas: every workgroup of a frame adding to the same 256 B serialises in the L2
+// (measured: 8,100 adds at 1080p doubled the composing launch), 64 replicas spread them over 64 rows; the finalize sums the replicas.
+constexpr uint32_t kDisplayReplicas = 64;
+struct DisplayState { float scale, metered_ev, adapted_ev; uint32_t primed, frames, pad[3]; };
+static_assert(sizeof(DisplayState) == 32, "the display state is 32 B");
+constexpr size_t kDisplayLastOffset = (size_t)kDisplayReplicas * kDisplayBins * sizeof(uint32_t);
+constexpr size_t kDisplayStateOffset = kDisplayLastOffset + kDisplayBins * sizeof(uint32_t);
+constexpr size_t kDisplayBytes = kDisplayStateOffset + sizeof(DisplayState);
+
 // Everything a per-pixel kernel can touch, passed by value as the kernel argument (scalar loads).
 struct KArgs {
     GpuCamera cam, prev_cam;
