@@ -321,8 +321,23 @@ int st_camera_render_aovs(StEngine* e, StHandle camera, const StAovTargets* targ
  *   engine accepts a skin (host work). st_instance_set_pose returns ST_ERR_NO_DEVICE on a host-only engine (there is no CPU skinning)
  *   and ST_ERR_INVALID_ARGUMENT for an unknown instance, an instance whose mesh has no skin, a joint_count other than the skin's, or
  *   a matrix element that is not finite.
- * - Limitation: the velocity plane, reprojection and ST_AOV_MOTION follow instance transforms only. A skinned deformation is not in
- *   them (the previous pose's positions would have to reach primary visibility). */
+ * - Motion of a deformation (st_engine_set_deformation_motion, OFF by default). Off, the velocity plane, reprojection and ST_AOV_MOTION
+ *   follow instance transforms only: a bending limb reports the motion of its instance. On, a primary hit on an instance whose pose the
+ *   LAST st_tick re-skinned takes its previous position from the previous pose: with the hit on triangle k of the instance's mesh and
+ *   Triangle::hit's barycentrics (u, v) — StRayHit.barycentric —
+ *       prev_point = prev_xform x ((1 - u - v) q0 + u q1 + v q2)
+ *   where q0..q2 are the object-space positions of triangle k as the posed store held them BEFORE that tick (what st_debug_read_posed
+ *   returned then) and prev_xform is the instance's previous transform, the matrix the rigid formula uses. The velocity is
+ *   screen(camera, point) - screen(previous camera, prev_point), with the same 0.001 squared-length threshold, and feeds the reprojection
+ *   map and ST_AOV_MOTION (bit-equal to the velocity plane wherever both are written) the same way.
+ *   Every other hit keeps the rigid formula, bit for bit what the switch off gives: an unskinned instance, a posed instance the last tick
+ *   did not re-skin, and two cases that show ONE frame without a deformation term — the first tick that gives an instance a pose (there
+ *   are no earlier posed positions: the bind pose is not kept as one) and a tick that returns it to the bind pose
+ *   (st_instance_set_pose(NULL) drops the pose and its previous positions with it). Likewise the first tick after the switch is turned
+ *   on only records the poses it skins; deformation terms start with the next re-skin. The previous positions are dropped wherever the
+ *   pose is (see Lifecycle). Scene queries and the other AOVs are unaffected.
+ *   Cost: a second region of the posed store (96 B per triangle) for every instance re-posed while the switch is on, one 4-B table word
+ *   per primary hit, and 4 + 36 B more per deforming hit. st_tick and st_render_camera gain no host synchronisation. */
 typedef struct StSkinVertex {   /* 24 B */
     uint16_t joints[4];         /* indices into the skin's joint palette, < joint_count */
     float weights[4];           /* used as given (not renormalised); finite, >= 0, not all zero */
@@ -338,6 +353,12 @@ int st_debug_skinning(StEngine* e, uint64_t* launches, uint64_t* triangles, uint
 /* The instance's posed object-space triangles as the device holds them: 24 floats per triangle (positions 9, normals 9, uvs 6: the device
  * mesh store's layout). Blocking. An instance without a pose is ST_ERR_INVALID_ARGUMENT. out == NULL only reports the size. */
 int st_debug_read_posed(StEngine* e, StHandle instance, float* out, size_t capacity_floats, size_t* written_floats);
+/* Deformation motion (above). Host work: valid on a host-only engine (which never has a pose). Takes effect at the next st_tick. */
+int st_engine_set_deformation_motion(StEngine* e, int enabled);
+int st_engine_get_deformation_motion(StEngine* e, int* enabled);
+/* What the last st_tick left: the instances whose hits take the deformation term in the frames after it, and the device memory the
+ * second regions of the posed store hold. 0 / 0 while the switch is off. A host-only engine is ST_ERR_NO_DEVICE. */
+int st_debug_deformation(StEngine* e, uint64_t* instances_with_previous, uint64_t* previous_bytes);
 
 /* ---- environment lighting (NEW seam): an equirectangular HDR map in place of the procedural atmosphere (k_env.hip, st_env.cpp).
  * - Timing: a change takes effect at the next st_tick, like every scene edit. Frames, scene queries and AOVs before that tick see the old

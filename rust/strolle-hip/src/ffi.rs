@@ -240,6 +240,13 @@ extern "C" {
     pub fn st_debug_camera_histogram(e: *mut StEngine, camera: u64, bins: *mut u32) -> i32;
 }
 
+// ---- deformation motion (include/strolle_hip.h "skinned meshes"): off by default
+extern "C" {
+    pub fn st_engine_set_deformation_motion(e: *mut StEngine, enabled: i32) -> i32;
+    pub fn st_engine_get_deformation_motion(e: *mut StEngine, enabled: *mut i32) -> i32;
+    pub fn st_debug_deformation(e: *mut StEngine, instances_with_previous: *mut u64, previous_bytes: *mut u64) -> i32;
+}
+
 // ---- the HIP runtime, as far as the staging-copy present needs it (libamdhip64)
 pub type hipStream_t = *mut c_void;
 extern "C" {

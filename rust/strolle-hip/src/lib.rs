@@ -350,6 +350,12 @@ where
         check(unsafe { ffi::st_engine_set_arithmetic(self.raw, exact as i32) });
     }
 
+    /// Not part of the reference's API: motion vectors and reprojection follow skinned deformations too (off by default; a facade that
+    /// forwards `SkinnedMesh` poses turns it on). Takes effect at the next `tick`.
+    pub fn set_deformation_motion(&mut self, enabled: bool) {
+        check(unsafe { ffi::st_engine_set_deformation_motion(self.raw, enabled as i32) });
+    }
+
     /// Not part of the reference's API: refit the BVH instead of rebuilding it while instances only move — on the device
     /// (ST_BVH_REFIT_DEVICE = 2: st_tick sends the moved triangles only; same bits as the host refit). `false` goes back to the library's
     /// default (ST_BVH_AUTO = 4: the first tree on the host unless it hangs long leaf runs on large faces (then the device builder's), every later change answered on the device while nothing observes the contract stream).

@@ -458,6 +458,10 @@ class _Binding:
             self.debug_camera_histogram = fn("debug_camera_histogram", [vp, u64, P(u32)])
         if hasattr(lib, prefix + "mesh_set_skin"):
             self.mesh_set_skin = fn("mesh_set_skin", [vp, u64, vp, sz, u32])
+        if hasattr(lib, prefix + "engine_set_deformation_motion"):   # deformation motion (likewise absent from an older library)
+            self.engine_set_deformation_motion = fn("engine_set_deformation_motion", [vp, i32])
+            self.engine_get_deformation_motion = fn("engine_get_deformation_motion", [vp, P(i32)])
+            self.debug_deformation = fn("debug_deformation", [vp, P(u64), P(u64)])
         if has_device:
             self.camera_set_rows = fn("camera_set_rows", [vp, u64, u32, u32])
             self.camera_set_output_format = fn("camera_set_output_format", [vp, u64, i32])
@@ -857,6 +861,24 @@ class Engine(EngineBase):
         out = np.zeros(n.value, np.float32)
         self._check(self._b.debug_read_posed(self._h, instance, out.ctypes.data_as(C.POINTER(C.c_float)), n.value, C.byref(n)))
         return out.reshape(-1, 24)
+
+    # ---- deformation motion (include/strolle_hip.h "skinned meshes"): takes effect at the next tick
+    def set_deformation_motion(self, enabled: bool):
+        """st_engine_set_deformation_motion: the velocity plane, reprojection and the MOTION AOV follow skinned deformations too."""
+        self._check(self._b.engine_set_deformation_motion(self._h, 1 if enabled else 0))
+
+    @property
+    def deformation_motion(self) -> bool:
+        """st_engine_get_deformation_motion."""
+        on = C.c_int()
+        self._check(self._b.engine_get_deformation_motion(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def deformation_stats(self):
+        """st_debug_deformation: (instances the last tick left a previous pose, bytes of device memory their second regions hold)."""
+        n, b = C.c_uint64(), C.c_uint64()
+        self._check(self._b.debug_deformation(self._h, C.byref(n), C.byref(b)))
+        return n.value, b.value
 
     # ---- display transforms (include/strolle_hip.h "display transforms"): take effect at the camera's next render
     def set_display(self, camera: int, desc: Optional[StDisplayDesc] = None, **kw):

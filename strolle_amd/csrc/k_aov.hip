@@ -12,7 +12,7 @@ namespace ST_KNS {
 // The planes are width x height, row-major; only owned pixels are written.
 template <bool LDS_SCENE, class SE>
 __global__ ST_KERNEL_BOUNDS void k_aov(const KArgs a_in, float* depth, float4* normal, float4* albedo, float2* motion, uint64_t* instance,
-                                       uint32_t* triangle, const uint4* table) {
+                                       uint32_t* triangle, const uint4* table, const float* deform_posed) {
     ST_QUERY_PROLOGUE
     ST_STACK_LDS(SE, lds);
     U2 pos;
@@ -44,14 +44,15 @@ __global__ ST_KERNEL_BOUNDS void k_aov(const KArgs a_in, float* depth, float4* n
         float2 mv = make_float2(0.0f, 0.0f);
         if (any) {
             const float4* xf = a.instance_xforms + 8u * h.xform_slot;
-            const V3 prev_point = affine_point(xf + 4, affine_point(xf, h.point));
+            V3 prev_point = affine_point(xf + 4, affine_point(xf, h.point));
+            if (deform_posed != nullptr) (void)deform_prev_point(a, table, deform_posed, h.xform_slot, c.tri, c.u, c.v, &prev_point);   // deformation motion, as in k_prim_visibility (deform_posed is null while it is off)
             const V2 velocity = clip_to_screen(a.cam, world_to_clip(a.cam, h.point)) - clip_to_screen(a.prev_cam, world_to_clip(a.prev_cam, prev_point));
             if (dot(velocity, velocity) >= 0.001f) mv = make_float2(velocity.x, velocity.y);
         }
         motion[i] = mv;
     }
     if (instance || triangle) {
-        uint4 rec = make_uint4(0u, 0u, 0u, 0u);   // {handle lo, hi, first triangle slot of the instance, 0}
+        uint4 rec = make_uint4(0u, 0u, 0u, 0u);   // {handle lo, hi, first triangle slot of the instance, deformation motion's word}
         if (any) rec = table[h.xform_slot];
         if (instance) instance[i] = any ? ((uint64_t)rec.y << 32 | rec.x) : 0ull;
         if (triangle) triangle[i] = any ? c.tri - rec.z : 0xffffffffu;
@@ -59,8 +60,8 @@ __global__ ST_KERNEL_BOUNDS void k_aov(const KArgs a_in, float* depth, float4* n
 }
 
 void launch_aov(const KArgs& a, float* depth, float4* normal, float4* albedo, float2* motion, uint64_t* instance, uint32_t* triangle, const uint4* table,
-                hipStream_t s) {
-    ST_LAUNCH_TRACE(k_aov, false, s, a, depth, normal, albedo, motion, instance, triangle, table);
+                const float* deform_posed, hipStream_t s) {
+    ST_LAUNCH_TRACE(k_aov, false, s, a, depth, normal, albedo, motion, instance, triangle, table, deform_posed);
 }
 
 }  // namespace ST_KNS

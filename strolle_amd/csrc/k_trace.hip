@@ -164,7 +164,7 @@ ST_D void frame_reprojection_pixel(const KArgs& a, U2 pos, const Surface& surfac
 // REPROJECT: frame_reprojection runs in the same kernel (it needs this pixel's new surface + velocity and the PREVIOUS
 // frame's surfaces only).
 template <bool LDS_SCENE, bool REPROJECT, class SE>
-__global__ ST_KERNEL_BOUNDS void k_prim_visibility(const KArgs a_in) {
+__global__ ST_KERNEL_BOUNDS void k_prim_visibility(const KArgs a_in, const uint4* deform_table, const float* deform_posed) {
     ST_SCENE_PROLOGUE
     ST_STACK_LDS(SE, lds);
     uint32_t used_ = 0u;
@@ -172,14 +172,15 @@ __global__ ST_KERNEL_BOUNDS void k_prim_visibility(const KArgs a_in) {
     if (!resolve_gid(a, false, &pos) || !owns_pixel(a, pos)) return;
     const Ray ray = camera_ray(a.cam, pos);
     TriangleHit hit;
+    Candidate c;   // the winning candidate: the velocity step's deformation term needs its triangle slot and barycentrics
 #if ST_FAST_DEVICE
     // PRIMARY hits are exact in the fast build too (round 6): Triangle::hit, the attribute interpolation and the normal's octahedral code in the island's
     // arithmetic (st_device.h closest_resolve_exact says why: the sign of a decoded normal's z decides every hemisphere sample's tangent frame)
     // (a scene that lives in LDS — the Cornell box — keeps round 5's path: its contract walk is the island's already, its gates have 17 dB to spare, and the
     // exact interpolation + octahedral code would cost its headline 2-3 us per frame)
-    if (LDS_SCENE) hit = trace_closest(a, ray, lane_stack(a, lds), &used_);
+    if (LDS_SCENE) hit = trace_closest(a, ray, lane_stack(a, lds), &used_, &c);
     else {
-        Candidate c; bool any;
+        bool any;
         if (a.bvh_w != nullptr && a.primary_packets) any = closest_hit_packet(a, ray, &c);   // the tile's 64 primary rays as one packet over the wide stream
         else if (a.bvh_w != nullptr) any = closest_hit_wide<SE, true>(a, ray, lane_stack(a, lds), &c);
         else if (a.bvh_c != nullptr) any = closest_hit_compact(a, ray, lane_stack(a, lds), &c);
@@ -187,7 +188,7 @@ __global__ ST_KERNEL_BOUNDS void k_prim_visibility(const KArgs a_in) {
         hit = closest_resolve_exact(a, ray, c, any);
     }
 #else
-    hit = trace_closest(a, ray, lane_stack(a, lds), &used_);
+    hit = trace_closest(a, ray, lane_stack(a, lds), &used_, &c);
 #endif
     count_rays(a, used_);
     if (!hit_is_some(hit)) {  // LoadOp::Clear(TRANSPARENT)
@@ -222,7 +223,9 @@ __global__ ST_KERNEL_BOUNDS void k_prim_visibility(const KArgs a_in) {
     tex_write(a.sn, a, pos, f4(normal_decode(en), g.depth));
     // prim_raster.rs:21-27: where this surface point was under its instance's previous transform
     const float4* xf = a.instance_xforms + 8u * hit.xform_slot;
-    const V3 prev_point = affine_point(xf + 4, affine_point(xf, hit.point));
+    V3 prev_point = affine_point(xf + 4, affine_point(xf, hit.point));
+    // ... or, with deformation motion on (one scalar test of a kernel argument: both pointers are null otherwise. They are arguments of this kernel, not KArgs fields: a larger KArgs slowed unrelated kernels by 2-10 % on the same box), under its previous pose too where the last tick re-skinned the instance
+    if (deform_posed != nullptr) (void)deform_prev_point(a, deform_table, deform_posed, hit.xform_slot, c.tri, c.u, c.v, &prev_point);
     const V2 velocity = clip_to_screen(a.cam, world_to_clip(a.cam, hit.point)) - clip_to_screen(a.prev_cam, world_to_clip(a.prev_cam, prev_point));
     const bool moving = dot(velocity, velocity) >= 0.001f;
     if (!lean) tex_write(a.velocity, a, pos, moving ? make_float4(velocity.x, velocity.y, 0.0f, 0.0f) : f4z());
@@ -231,8 +234,8 @@ __global__ ST_KERNEL_BOUNDS void k_prim_visibility(const KArgs a_in) {
         frame_reprojection_pixel(a, pos, surface, moving ? velocity : v2(0.0f, 0.0f));
     }
 }
-void launch_prim_visibility(const KArgs& a, bool reproject, hipStream_t s) {
-    if (reproject) ST_LAUNCH_TRACE_B(k_prim_visibility, true, false, s, a); else ST_LAUNCH_TRACE_B(k_prim_visibility, false, false, s, a);
+void launch_prim_visibility(const KArgs& a, bool reproject, const uint4* deform_table, const float* deform_posed, hipStream_t s) {
+    if (reproject) ST_LAUNCH_TRACE_B(k_prim_visibility, true, false, s, a, deform_table, deform_posed); else ST_LAUNCH_TRACE_B(k_prim_visibility, false, false, s, a, deform_table, deform_posed);
 }
 
 // Tabulates the byte decodes of st_device.h with the routines themselves (one launch at engine creation).

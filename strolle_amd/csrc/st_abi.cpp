@@ -195,6 +195,12 @@ int st_debug_read_posed(StEngine* e, StHandle instance, float* out, size_t capac
     ST_REQUIRE(e, "null engine");
     return E(e)->read_posed(instance, out, capacity_floats, written_floats);
 }
+int st_engine_set_deformation_motion(StEngine* e, int enabled) { ST_REQUIRE(e, "null engine"); E(e)->deform_on = enabled != 0; return ST_OK; }
+int st_engine_get_deformation_motion(StEngine* e, int* enabled) { ST_REQUIRE(e && enabled, "null argument"); *enabled = E(e)->deform_on ? 1 : 0; return ST_OK; }
+int st_debug_deformation(StEngine* e, uint64_t* instances_with_previous, uint64_t* previous_bytes) {
+    ST_REQUIRE(e && instances_with_previous && previous_bytes, "null argument");
+    return E(e)->deformation_stats(instances_with_previous, previous_bytes);
+}
 int st_light_insert(StEngine* e, StHandle id, const StLight* l) { ST_REQUIRE(e && l, "null argument"); E(e)->insert_light(id, *l); return ST_OK; }
 int st_light_remove(StEngine* e, StHandle id) { ST_REQUIRE(e, "null engine"); E(e)->remove_light(id); return ST_OK; }
 int st_sun_update(StEngine* e, float azimuth, float altitude) { ST_REQUIRE(e, "null engine"); E(e)->sun_azimuth = azimuth; E(e)->sun_altitude = altitude; E(e)->sun_dirty = true; return ST_OK; }

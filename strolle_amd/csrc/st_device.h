@@ -400,9 +400,10 @@ ST_D uint32_t traverse(const KArgs& a, const Ray& ray, float max_t, SE* stack, C
 template <class SE> ST_D bool closest_hit_compact(const KArgs& a, const Ray& ray, SE* stack, Candidate* best);
 template <class SE, bool EXACT_LEAF = false> ST_D bool closest_hit_wide(const KArgs& a, const Ray& ray, SE* stack, Candidate* best);
 ST_D TriangleHit closest_resolve(const KArgs& a, const Ray& ray, const Candidate& c, bool any);
+// `won`: the winning candidate (triangle slot, Triangle::hit's barycentrics) — what closest_resolve read, for callers that need it afterwards
 template <class SE>
-ST_D TriangleHit trace_closest(const KArgs& a, const Ray& ray, SE* stack, uint32_t* used_memory) {
-    Candidate c; bool any;
+ST_D TriangleHit trace_closest(const KArgs& a, const Ray& ray, SE* stack, uint32_t* used_memory, Candidate* won) {
+    Candidate& c = *won; bool any;
 #if ST_FAST_DEVICE && !defined(ST_NO_ANYHIT_FAST)
     // the fast build's closest-hit rays outside the heatmap pass (which calls traverse() itself: its integers are the contract's) walk the
     // compact stream too when there is one: conservative boxes visit a superset of the entries, the triangle records are the same f32
@@ -412,6 +413,11 @@ ST_D TriangleHit trace_closest(const KArgs& a, const Ray& ray, SE* stack, uint32
 #endif
     *used_memory = traverse<false>(a, ray, kF32Max, stack, &c, &any);
     return closest_resolve(a, ray, c, any);
+}
+template <class SE>
+ST_D TriangleHit trace_closest(const KArgs& a, const Ray& ray, SE* stack, uint32_t* used_memory) {
+    Candidate c;
+    return trace_closest(a, ray, stack, used_memory, &c);
 }
 // the winning triangle's attributes (normal, uv, instance slot), fetched once
 ST_D TriangleHit closest_resolve(const KArgs& a, const Ray& ray, const Candidate& c, bool any) {
@@ -430,6 +436,26 @@ ST_D TriangleHit closest_resolve(const KArgs& a, const Ray& ray, const Candidate
 }
 // glam Affine3A::transform_point3 with the transform stored as 4 float4 (x, y, z axes, translation)
 ST_D V3 affine_point(const float4* m, V3 p) { return ((xyz(m[0]) * p.x) + (xyz(m[1]) * p.y) + (xyz(m[2]) * p.z)) + xyz(m[3]); }
+// Deformation motion (include/strolle_hip.h "skinned meshes"): where a primary hit on a skinned instance was before the last tick re-skinned it.
+// `slot` is the hit's instance slot, `tri` its triangle slot, (u, v) Triangle::hit's barycentrics (Candidate::u, v; StRayHit::barycentric). Returns
+// false — and leaves *prev_point alone — for every instance without a previous pose: the caller then keeps prim_raster.rs:21-27's rigid formula.
+// `table` is the scene copy's instance table, `posed` the posed store; called only where the launch got them (deformation motion on). Loads: one table word per hit; for a deforming hit one more word and three positions (36 B).
+// The float32 operations and their order, the same in both arithmetic builds (this island: no contraction; tests/deform_ref.py restates them):
+//   k  = tri - first triangle slot of the instance            (the triangle's index in its mesh)
+//   w  = (1 - u) - v
+//   o  = ((q0 * w) + (q1 * u)) + (q2 * v)     per component   (q0..q2: triangle k's positions in the instance's PREVIOUS region of the posed store)
+//   prev_point = ((x * o.x + y * o.y) + z * o.z) + t          (x, y, z, t: the instance's prev_xform; affine_point)
+ST_D bool deform_prev_point(const KArgs& a, const uint4* table, const float* posed, uint32_t slot, uint32_t tri, float u, float v, V3* prev_point) {
+    const uint32_t* rec = reinterpret_cast<const uint32_t*>(table + slot);
+    const uint32_t prev = rec[3];
+    if (prev == 0u) return false;
+    const float* q = posed + 24u * (size_t)((prev - 1u) + (tri - rec[2]));
+    const V3 q0 = v3(q[0], q[1], q[2]), q1 = v3(q[3], q[4], q[5]), q2 = v3(q[6], q[7], q[8]);
+    const float w = (1.0f - u) - v;
+    const V3 o = xe::add(xe::add(xe::scale(q0, w), xe::scale(q1, u)), xe::scale(q2, v));
+    *prev_point = affine_point(a.instance_xforms + 8u * slot + 4, o);
+    return true;
+}
 // Triangle::hit's accept / reject and (t, u, v, 1 / det) for a hit-test record (p0, e1, e2), in the island's arithmetic: what traverse() computes for a leaf
 // entry, for walks over OTHER streams that owe the contract walk's bits (primary rays over the wide stream: closest_hit_wide<SE, true>, closest_hit_packet)
 ST_D bool triangle_hit_exact(const Ray& ray, V3 p0, V3 e1, V3 e2, float limit, float* t_out, float* u_out, float* v_out, float* inv_det_out) {

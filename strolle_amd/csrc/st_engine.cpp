@@ -105,6 +105,7 @@ Engine::~Engine() {
     if (skin_stream) (void)hipStreamDestroy(skin_stream);
     if (ev_skinned) (void)hipEventDestroy(ev_skinned);
     if (ev_posed_read) (void)hipEventDestroy(ev_posed_read);
+    if (ev_deform_read) (void)hipEventDestroy(ev_deform_read);
     if (query_stream) (void)hipStreamDestroy(query_stream);
     d_query_rays.release(); d_query_hits.release();
     if (query_pinned) (void)hipHostFree(query_pinned);

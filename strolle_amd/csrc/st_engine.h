@@ -382,6 +382,11 @@ struct Engine {
         bool changed = true;         // the pose changed since the last skin launch (that launch makes the host image stale)
         bool host_current = false;   // `host` holds what the device region holds
         std::vector<StMeshTriangle> host;
+        // deformation motion (below): `other` is the pose's second region — a re-skin writes it and swaps it with `first`, so that it then holds the
+        // positions from before that tick; has_previous says the LAST tick did so. `skinned` / `previous` are the palettes the two regions were skinned
+        // with (a posed store that grows re-skins both into the new allocation). All empty while the switch is off.
+        size_t other = SIZE_MAX; bool has_previous = false;
+        std::vector<float> skinned, previous;
     };
     std::unordered_map<uint64_t, PoseRec> poses;
     // the skin store's host image; ranges of dropped skins go back to skin_free and are reused
@@ -390,6 +395,19 @@ struct Engine {
     SlotRanges posed_free; size_t posed_size = 0;   // triangles of the posed store handed out (its allocation holds at least that many)
     hipStream_t skin_stream = nullptr; hipEvent_t ev_skinned = nullptr, ev_posed_read = nullptr; bool posed_read_pending = false;
     uint64_t skin_launches = 0, skinned_triangles = 0, posed_readbacks = 0;
+    // Deformation motion (include/strolle_hip.h "skinned meshes"; st_device.h deform_prev_point): with the switch on, primary visibility and the AOV launch
+    // read the previous region of every instance the last tick re-skinned, through the free word of the scene copy's instance table (fill_instance_table).
+    // deform_live: instances the last tick left a previous pose. Frames read the posed store then: ev_deform_read is recorded behind every reader
+    // that can reach deform_prev_point (reader_end: frames and the MOTION AOV, not the scene queries) — behind a wait for its own earlier recording, so that one event covers readers on several streams — and the next skin launch,
+    // which overwrites previous regions, waits for it on the skin stream. No host wait (DESIGN.md "Deformation motion").
+    bool deform_on = false; uint64_t deform_live = 0;
+    hipEvent_t ev_deform_read = nullptr; bool deform_read_pending = false;
+    // what primary visibility and the MOTION AOV get as kernel arguments: null unless the last tick left some instance a previous pose (that tick wrote the
+    // live copy's table: a re-skin is a scene change). deform_live is that tick's state — the switch itself is read by st_tick alone, so it takes effect at the next tick
+    const uint4* deform_table() const { return deform_live ? static_cast<const uint4*>(sets[live].instance_table.ptr) : nullptr; }
+    const float* deform_posed() const { return deform_live ? static_cast<const float*>(d_posed.ptr) : nullptr; }
+    void deform_begin_tick();         // forgets last tick's previous poses (and, with the switch off, gives the second regions back)
+    int deformation_stats(uint64_t* instances_with_previous, uint64_t* previous_bytes) const;
     int set_skin(uint64_t mesh, const StSkinVertex* corners, size_t corner_count, uint32_t joint_count);
     int set_pose(uint64_t instance, const float* joint_xforms, uint32_t joint_count);
     int read_posed(uint64_t instance, float* out, size_t capacity_floats, size_t* written_floats);
@@ -524,7 +542,7 @@ struct Engine {
     hipStream_t copy_stream = nullptr, last_render_stream = nullptr; bool rendered_before = false; hipEvent_t ev_copy = nullptr; bool copy_in_flight = false;
     struct CopyTarget { int index; hipStream_t up; bool* pageable; bool other; };   // the writer's side: st_tick.cpp pick_copy
     int reader_begin(hipStream_t stream, bool reader);   // the readers' side: st_render.cpp
-    int reader_end(hipStream_t stream, bool lights);
+    int reader_end(hipStream_t stream, bool lights, bool deform = false);   // deform: the reader can reach deform_prev_point (frames, the MOTION AOV)
 
     std::unordered_map<uint64_t, std::unique_ptr<CameraState>> cameras; uint64_t next_camera = 0;
 

@@ -153,10 +153,15 @@ int Engine::reader_begin(hipStream_t stream, bool reader) {
     }
     return ST_OK;
 }
-int Engine::reader_end(hipStream_t stream, bool lights) {
+int Engine::reader_end(hipStream_t stream, bool lights, bool deform) {
     if (alternating) if (int rc = sets[live].fence.mark_read(stream)) return rc;
     if (lights && lights_alternating) if (int rc = light_sets[live_lights].fence.mark_read(stream)) return rc;
     if (lights && env_live) if (int rc = env_live->fence.mark_read(stream)) return rc;   // (frames: the map is freed behind its last reader)
+    if (deform && deform_live) {   // this reader (a frame, a MOTION AOV) may read previous regions of the posed store: the next skin launch waits for it (st_engine.h ev_deform_read)
+        if (!ev_deform_read) ST_HIP(hipEventCreateWithFlags(&ev_deform_read, hipEventDisableTiming));
+        if (deform_read_pending) ST_HIP(hipStreamWaitEvent(stream, ev_deform_read, 0));
+        ST_HIP(hipEventRecord(ev_deform_read, stream)); deform_read_pending = true;
+    }
     return ST_OK;
 }
 
@@ -303,8 +308,8 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
         a.skip_dead_scratch = (tuning.skip_scratch_stores && whole_graph && tuning.fuse && tuning.fuse_spatial && ((((a.width + 7u) / 8u) & 1u) == 0u) && needs_di && denoise && any_objects) ? 1u : 0u;
 
         auto do_prim = [&] {
-            if (tuning.fuse && any_objects) run(KS_PRIM_VISIBILITY_REPROJECTION, ST_PASS_PRIM_VISIBILITY | ST_PASS_FRAME_REPROJECTION, [&] { L.launch_prim_visibility(a, true, cur); });
-            else run(KS_PRIM_VISIBILITY, ST_PASS_PRIM_VISIBILITY, [&] { L.launch_prim_visibility(a, false, cur); });
+            if (tuning.fuse && any_objects) run(KS_PRIM_VISIBILITY_REPROJECTION, ST_PASS_PRIM_VISIBILITY | ST_PASS_FRAME_REPROJECTION, [&] { L.launch_prim_visibility(a, true, deform_table(), deform_posed(), cur); });
+            else run(KS_PRIM_VISIBILITY, ST_PASS_PRIM_VISIBILITY, [&] { L.launch_prim_visibility(a, false, deform_table(), deform_posed(), cur); });
             if (any_objects && !tuning.fuse) run(KS_FRAME_REPROJECTION, ST_PASS_FRAME_REPROJECTION, [&] { L.launch_frame_reprojection(a, cur); });
         };
         // DI up to temporal resampling touches only the DI reservoirs and read-only frame inputs ...
@@ -501,7 +506,7 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
         run(KS_COMPOSITION, ST_PASS_COMPOSITION, [&] { L.launch_composition(a, mode, di_diff, gi_diff, out, c.out_format, disp, cur); });
     }
     if (disp.meter && out) if (int rc = display_finalize(c, stream)) return rc;   // every composing launch ran on `stream`
-    if (int rc = reader_end(stream, true)) return rc;   // the end of the last frame that reads these copies of the scene and the lights
+    if (int rc = reader_end(stream, true, true)) return rc;   // the end of the last frame that reads these copies of the scene and the lights
     profile_close();
     ST_HIP(hipGetLastError());
     if (mask_split) return fail(ST_ERR_INVALID_ARGUMENT, "the pass mask splits a fused launch (st_debug_last_launches lists the launch groups)");

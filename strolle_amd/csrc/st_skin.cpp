@@ -61,6 +61,7 @@ void Engine::drop_pose(uint64_t instance, bool make_dirty) {
     auto it = poses.find(instance);
     if (it == poses.end()) return;
     if (it->second.first != SIZE_MAX) posed_free.give(it->second.first, it->second.first + it->second.count);
+    if (it->second.other != SIZE_MAX) posed_free.give(it->second.other, it->second.other + it->second.count);   // (deformation motion: the previous positions go with the pose)
     poses.erase(it);
     if (make_dirty)
         for (auto& r : instances) if (r.id == instance) { r.dirty = true; instances_dirty = true; break; }
@@ -81,6 +82,27 @@ const std::vector<StMeshTriangle>* Engine::bake_source(const InstanceRec& inst, 
     auto it = poses.find(inst.id);
     if (it != poses.end() && it->second.host_current && it->second.host.size() == mesh.size()) return &it->second.host;
     return &mesh;   // (a pose that no tick has skinned yet: the instance still shows the bind pose)
+}
+
+// Deformation motion: what the last tick left is forgotten before this one skins — an instance has a previous pose for the frames of the tick that
+// re-skinned it, no longer. With the switch off the second regions go back to the free list (frames still reading them: ev_deform_read).
+void Engine::deform_begin_tick() {
+    deform_live = 0;
+    for (auto& kv : poses) {
+        PoseRec& p = kv.second;
+        p.has_previous = false;
+        if (deform_on) continue;
+        if (p.other != SIZE_MAX) { posed_free.give(p.other, p.other + p.count); p.other = SIZE_MAX; }
+        std::vector<float>().swap(p.skinned); std::vector<float>().swap(p.previous);
+    }
+}
+
+int Engine::deformation_stats(uint64_t* instances_with_previous, uint64_t* previous_bytes) const {
+    if (!has_device) return fail(ST_ERR_NO_DEVICE, "deformation motion reads the posed store: a host-only engine has none");
+    uint64_t bytes = 0;
+    for (const auto& kv : poses) if (kv.second.other != SIZE_MAX) bytes += (uint64_t)kv.second.count * 24u * sizeof(float);
+    *instances_with_previous = deform_live; *previous_bytes = bytes;
+    return ST_OK;
 }
 
 int Engine::skin_tick(hipStream_t stream) {
@@ -129,6 +151,21 @@ int Engine::skin_tick(hipStream_t stream) {
         }
         ST_HIP(hipStreamSynchronize(skin_stream));
     }
+    // deformation motion: a pose that changed while its region holds what an earlier tick skinned (with the switch on: `skinned` is that tick's palette)
+    // is skinned into its second region, which becomes the current one — the bake, read-backs and st_debug_read_posed follow `first` — and the old
+    // one keeps the previous positions for this tick's frames. The first tick of a pose has no earlier positions and takes no second region.
+    for (auto& kv : poses) {
+        PoseRec& p = kv.second;
+        if (!deform_on || !p.changed || p.first == SIZE_MAX || p.skinned.empty()) continue;
+        if (p.other == SIZE_MAX) {
+            size_t b, e;
+            if (!posed_free.take(p.count, &b, &e)) { b = posed_size; posed_size += p.count; }
+            p.other = b;
+        }
+        std::swap(p.first, p.other);
+        p.previous.swap(p.skinned);
+        p.has_previous = true; deform_live++;
+    }
     // a region of the posed store for every pose that has none; a store that has to grow is a new allocation: every pose is skinned again
     for (auto& kv : poses) {
         PoseRec& p = kv.second;
@@ -138,10 +175,13 @@ int Engine::skin_tick(hipStream_t stream) {
         p.first = b;
     }
     const size_t posed_bytes = posed_size * 24u * sizeof(float);
+    bool grown = false;
     if (posed_bytes > d_posed.capacity) {
         if (posed_read_pending) { ST_HIP(hipEventSynchronize(ev_posed_read)); posed_read_pending = false; }   // (hipFree waits too; said here)
+        if (deform_read_pending) { ST_HIP(hipEventSynchronize(ev_deform_read)); deform_read_pending = false; }   // (likewise: frames reading previous regions)
         if ((rc = d_posed.reserve(posed_bytes, posed_bytes + posed_bytes / 2))) return rc;
         for (auto& kv : poses) kv.second.reskin = true;   // (the poses themselves are unchanged: host images stay current)
+        grown = true;   // ... and so is every previous region this tick's frames will read, from the palette it was skinned with
     }
     // one job per pose to skin, each padded to a whole workgroup
     std::vector<SkinJob> jobs; std::vector<uint32_t> starts{0u}; std::vector<float> palettes;
@@ -158,12 +198,22 @@ int Engine::skin_tick(hipStream_t stream) {
         triangles += p.count;
         p.reskin = false;
         if (p.changed) { p.changed = false; p.host_current = false; }
+        if (deform_on) p.skinned = p.palette;
+        if (grown && p.has_previous) {   // the previous positions, again, into the new allocation
+            SkinJob q = j;
+            q.posed_first = (uint32_t)p.other; q.palette_first = (uint32_t)(palettes.size() / 12u);
+            jobs.push_back(q);
+            starts.push_back(starts.back() + (uint32_t)((p.count + kSkinBlock - 1u) / kSkinBlock * kSkinBlock));
+            palettes.insert(palettes.end(), p.previous.begin(), p.previous.end());
+            triangles += p.count;
+        }
     }
     bool pageable = false;
     if ((rc = d_skin_jobs.upload(jobs.data(), jobs.size() * sizeof(SkinJob), skin_stream, staging, &pageable)) ||
         (rc = d_skin_starts.upload(starts.data(), starts.size() * sizeof(uint32_t), skin_stream, staging, &pageable)) ||
         (rc = d_palettes.upload(palettes.data(), palettes.size() * sizeof(float), skin_stream, staging, &pageable))) return rc;
     if (posed_read_pending) { ST_HIP(hipStreamWaitEvent(skin_stream, ev_posed_read, 0)); posed_read_pending = false; }   // bakes of earlier ticks still reading the regions
+    if (deform_read_pending) { ST_HIP(hipStreamWaitEvent(skin_stream, ev_deform_read, 0)); deform_read_pending = false; }   // frames still reading previous regions (deformation motion)
     launch_skin(static_cast<const SkinJob*>(d_skin_jobs.ptr), static_cast<const uint32_t*>(d_skin_starts.ptr), (uint32_t)jobs.size(), starts.back(), static_cast<const float*>(d_skin_bind.ptr),
                 d_skin_corners.ptr, static_cast<const float*>(d_palettes.ptr), static_cast<float*>(d_posed.ptr), skin_stream);
     ST_HIP(hipGetLastError());

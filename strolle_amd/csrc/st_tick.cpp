@@ -147,6 +147,7 @@ int Engine::build_on_device(SceneSet& t, hipStream_t up, bool* pageable) {
 int Engine::tick(hipStream_t stream) {
     // skinned meshes: the poses set since the last tick are skinned first — a host bake of this refresh reads their posed triangles back
     const bool skinning = has_device && !poses.empty();
+    deform_begin_tick();   // (deformation motion: a previous pose lasts one tick)
     if (skinning) {
         ST_HIP(hipSetDevice(device));
         staging.begin_tick();
