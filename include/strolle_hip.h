@@ -479,6 +479,78 @@ int st_camera_exposure(StEngine* e, StHandle camera, float* scale, float* metere
 /* Blocking debug seam: the 64 bins metered from the camera's last rendered auto-exposure frame (zeros before one). */
 int st_debug_camera_histogram(StEngine* e, StHandle camera, uint32_t bins[64]);
 
+/* ---- post-processing (NEW seam): FXAA anti-aliasing and resampling of what a camera writes to its output (st_post.cpp, k_post.hip). The
+ * last two nodes of the reference's per-camera graph (bevy-strolle/src/graph.rs: rendering, fxaa, tonemapping, upscaling).
+ * - Order: rendering -> display transform -> FXAA -> resample -> output format. The reference runs its FXAA node before tone mapping;
+ *   FXAA's thresholds are defined for display-referred values in [0, 1], and on unbounded HDR radiance every light-source edge is an "edge
+ *   of contrast infinity", so here (as in Bevy's own main graph) FXAA sees the colour the display transform produced.
+ * - Scope: the setting belongs to the camera and takes effect at its next st_render_camera. It changes only what is written to `out_device`
+ *   and how large that buffer must be (st_camera_output_size). AOVs, picks, scene queries, st_camera_read_buffer, the auto-exposure metering
+ *   (it meters the render-size composed frame) and the HDR history are unchanged; picks and AOVs stay in render-size pixel coordinates.
+ *   desc == NULL, or a desc with no flag and an output size equal to the render size, launches nothing new: the frame is the one the same
+ *   composing kernels write without post-processing. Otherwise the composing launch writes a camera-owned render-size RGBA32F plane and at
+ *   most two launches follow it on the caller's stream (ST_PASS_POST): the frame is complete when that stream has drained, as always. The
+ *   setting survives st_camera_update and st_engine_set_arithmetic; an explicit output size is kept when st_camera_update changes the render
+ *   size. BVH-heatmap frames are false colour: they skip FXAA but are resampled, so the buffer contract does not depend on the mode.
+ * - Arithmetic: float32, evaluated left to right as written, no fused multiply-add, division and square root correctly rounded, in BOTH
+ *   builds: tests/post_ref.py restates all of it in numpy and the kernels match it bit for bit. min(a, b) below is a when a < b or b is
+ *   NaN, else b; max likewise with >. Colours are r, g, b; alpha is written as 1.
+ * - Look-ups: pixel (x, y) has its centre at (x + 0.5, y + 0.5). Along one axis a continuous position p has q = p - 0.5, i0 = floor(q),
+ *   f = q - i0. BILINEAR reads the texels i0 and i0 + 1 (indices clamped to the image) and blends a + (b - a) * f, x first, then y;
+ *   an axis with f == 0 takes texel a itself (so infinities next door do not leak in as NaN). CATMULL_ROM reads i0 - 1 .. i0 + 2 with the
+ *   weights (a = -0.5) w0 = ((-0.5 f + 1) f - 0.5) f, w1 = ((1.5 f - 2.5) f) f + 1, w2 = ((-1.5 f + 2) f + 0.5) f, w3 = ((0.5 f - 0.5) f) f,
+ *   summed ((t0 w0 + t1 w1) + t2 w2) + t3 w3, rows first, then the four row results along y (f == 0: the texel i0 itself); the result is
+ *   clamped per channel to the min / max of the inner 2 x 2 texels (no ringing around light sources): min(max(v, lo), hi). A position
+ *   with f == 0 on both axes takes the texel itself.
+ * - Resampling: output pixel (ox, oy) of OW x OH samples the W x H source at ((ox + 0.5) W / OW, (oy + 0.5) H / OH). Per axis this is
+ *   evaluated in integers, n = (2 ox + 1) W - OW and d = 2 OW: i0 = floor(n / d), f = float(n - i0 d) / float(d) (one rounding; the
+ *   float product (ox + 0.5) * W is not exact above 2^24); NEAREST takes floor((2 ox + 1) W / d). Equal sizes make every filter the
+ *   identity, bit for bit. Downscaling is allowed and is point-sampled reconstruction, without a prefilter (exact 2 : 1 bilinear happens to
+ *   be the 2 x 2 mean); a prefiltered downscale is not offered.
+ * - FXAA (Lottes' FXAA 3.11 quality path, preset 39's 12 steps):
+ *     luma L = sqrt(0.2126 r' + 0.7152 g' + 0.0722 b') with x' = x > 0 ? (x < 1 ? x : 1) : 0 (NaN -> 0). M is the pixel's, N S E W NW NE SW SE
+ *     its neighbours' (indices clamped at the borders; N is y - 1). range = max - min over M, N, S, E, W; when range < max(edge_threshold_min,
+ *     max * edge_threshold) the pixel is copied unchanged. edgeH = |(NW + SW) - 2 W| + 2 |(N + S) - 2 M| + |(NE + SE) - 2 E|, edgeV =
+ *     |(NW + NE) - 2 N| + 2 |(W + E) - 2 M| + |(SW + SE) - 2 S|; horizontal when edgeH >= edgeV. Across the edge (N / S when horizontal, W / E
+ *     else) the steeper of |neg - M| and |pos - M| picks the side, a tie the negative one (N or W); gradient g = that difference, local
+ *     average A = 0.5 (side + M). From the centre moved half a pixel across the edge to that side, walk both ways along the edge to the
+ *     distances 1, 2, 3, 4, 5, 6.5, 8.5, 10.5, 12.5, 14.5, 18.5, 26.5 (steps 1 1 1 1 1 1.5 2 2 2 2 4 8) with bilinear look-ups of L; a side
+ *     ends at the first distance where |L - A| >= 0.25 g (or at 26.5). With d1, d2 the two distances, edge offset = 0.5 - min(d1, d2) /
+ *     (d1 + d2), used only when (L_end - A < 0) differs from (M - A < 0) at the nearer end (d1 < d2: the negative end, else the positive one),
+ *     else 0. Subpixel term: a = |((((N + S) + (E + W)) 2 + ((NW + NE) + (SW + SE))) / 12 - M| / range, clamped to at most 1; s = ((-2 a + 3) a) a;
+ *     offset_sub = (s s) fxaa_subpixel. The result is the bilinear colour look-up at the centre moved across the edge, to the chosen side, by
+ *     max(edge offset, offset_sub).
+ * - Tiles: FXAA's edge search and the resampler read neighbours across tile edges, so a camera cannot have post-processing (any desc) and
+ *   a window (st_camera_set_window, st_dist_set_partition, st_dist_set_grid) at once: ST_ERR_INVALID_ARGUMENT from whichever setter comes
+ *   second. For tiled frames the ranks render RGBA32F without post-processing, st_dist_gather assembles the frame on rank 0, and rank 0
+ *   runs st_post_process on it.
+ * - Errors: ST_ERR_INVALID_ARGUMENT for a wrong struct_size, unknown flags or filter, exactly one of the two output sides 0, a side above
+ *   16384, a threshold that is not finite or is negative, fxaa_subpixel outside [0, 1] (NaN included) and null pointers where they are not
+ *   allowed. An unknown camera is ST_ERR_UNKNOWN_CAMERA. Set, get and st_camera_output_size are host work and valid on a host-only engine;
+ *   st_post_process returns ST_ERR_NO_DEVICE there. */
+enum StResampleFilter { ST_RESAMPLE_NEAREST = 0, ST_RESAMPLE_BILINEAR = 1, ST_RESAMPLE_CATMULL_ROM = 2 };
+enum { ST_POST_FXAA = 1 };
+typedef struct StPostDesc {                /* 32 B */
+    uint32_t struct_size;                  /* sizeof(StPostDesc) */
+    uint32_t flags;                        /* ST_POST_* */
+    uint32_t output_width, output_height;  /* 0, 0 = the camera's render size (no resampling) */
+    uint32_t filter;                       /* StResampleFilter; ignored when the sizes are equal */
+    float fxaa_edge_threshold;             /* 0 = default 0.166 */
+    float fxaa_edge_threshold_min;         /* 0 = default 0.0833 */
+    float fxaa_subpixel;                   /* 0..1; NaN is an error; no "0 = default": the caller writes 0.75 for FXAA 3.11's default */
+} StPostDesc;
+int st_camera_set_post(StEngine* e, StHandle camera, const StPostDesc* desc);   /* NULL = off */
+/* the last desc set (a zeroed desc with struct_size when none was) and whether post-processing is on; either pointer may be NULL */
+int st_camera_get_post(StEngine* e, StHandle camera, StPostDesc* out, int* enabled);
+/* what st_render_camera's buffer must hold, in pixels of the camera's output format; either pointer may be NULL */
+int st_camera_output_size(StEngine* e, StHandle camera, uint32_t* width, uint32_t* height);
+/* Stateless: the same two kernels over any RGBA32F device image of width x height, written to dst_device (the desc's output size, or
+ * width x height) in dst_format. Needs a device engine; no camera, no tick. Enqueued on hip_stream without a host sync. A call
+ * that runs FXAA and then resamples uses an engine-owned intermediate plane: it is allocated (with a device sync) only when a call needs a
+ * larger one than any before it, and calls that use it on different streams are ordered by the engine. src and dst must not overlap. */
+int st_post_process(StEngine* e, const StPostDesc* desc, const void* src_rgba32f_device, uint32_t width, uint32_t height,
+                    void* dst_device, int dst_format /* StOutputFormat */, void* hip_stream);
+
 /* ---- multi-GPU behind the boundary (NEW seam; SURVEY.md section 8e, BASELINE.json configs 4 and 5). One process per GPU, one
  * engine per process, the scene replicated; the frame is cut into tiles, every rank renders its tile (+ an apron of redundant
  * pixels in Image mode, whose passes read neighbours) with absolute pixel coordinates, and the ONE collective of the path
@@ -657,7 +729,8 @@ enum StPassBit {
     ST_PASS_GI_PREVIEW_0 = 1u << 15, ST_PASS_GI_PREVIEW_1 = 1u << 16, ST_PASS_GI_RESOLVING = 1u << 17,
     ST_PASS_DENOISE_REPROJECT_DI = 1u << 18, ST_PASS_DENOISE_REPROJECT_GI = 1u << 19, ST_PASS_DENOISE_VARIANCE = 1u << 20,
     ST_PASS_DENOISE_WAVELET_0 = 1u << 21, /* ... wavelet pass n = ST_PASS_DENOISE_WAVELET_0 << n, n < 5 */
-    ST_PASS_COMPOSITION = 1u << 26, ST_PASS_BVH_HEATMAP = 1u << 27, ST_PASS_REF_TRACING = 1u << 28, ST_PASS_REF_SHADING = 1u << 29
+    ST_PASS_COMPOSITION = 1u << 26, ST_PASS_BVH_HEATMAP = 1u << 27, ST_PASS_REF_TRACING = 1u << 28, ST_PASS_REF_SHADING = 1u << 29,
+    ST_PASS_POST = 1u << 30   /* the post-processing launches behind composition ("post-processing" above): FXAA and / or the resampler, one launch group */
 };
 int st_debug_set_pass_mask(StEngine* e, uint64_t mask);
 /* Measurement only (tools/pair_matrix.py): the frame's graph is built as always — every fusion of the whole frame — but only the launches

@@ -247,6 +247,31 @@ extern "C" {
     pub fn st_debug_deformation(e: *mut StEngine, instances_with_previous: *mut u64, previous_bytes: *mut u64) -> i32;
 }
 
+// output post-processing (include/strolle_hip.h "post-processing"): FXAA and resampling of a camera's output
+pub const ST_RESAMPLE_NEAREST: u32 = 0;
+pub const ST_RESAMPLE_BILINEAR: u32 = 1;
+pub const ST_RESAMPLE_CATMULL_ROM: u32 = 2;
+pub const ST_POST_FXAA: u32 = 1;
+pub const ST_PASS_POST: u64 = 1 << 30;
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct StPostDesc {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub output_width: u32,
+    pub output_height: u32,
+    pub filter: u32,
+    pub fxaa_edge_threshold: f32,
+    pub fxaa_edge_threshold_min: f32,
+    pub fxaa_subpixel: f32,
+}
+extern "C" {
+    pub fn st_camera_set_post(e: *mut StEngine, camera: u64, desc: *const StPostDesc) -> i32; // null = off
+    pub fn st_camera_get_post(e: *mut StEngine, camera: u64, out: *mut StPostDesc, enabled: *mut i32) -> i32;
+    pub fn st_camera_output_size(e: *mut StEngine, camera: u64, width: *mut u32, height: *mut u32) -> i32;
+    pub fn st_post_process(e: *mut StEngine, desc: *const StPostDesc, src_rgba32f_device: *const c_void, width: u32, height: u32, dst_device: *mut c_void, dst_format: i32, hip_stream: *mut c_void) -> i32;
+}
+
 // ---- the HIP runtime, as far as the staging-copy present needs it (libamdhip64)
 pub type hipStream_t = *mut c_void;
 extern "C" {

@@ -148,6 +148,30 @@ def display_desc(tonemap=Tonemap.NONE, exposure_ev: float = 0.0, auto_exposure: 
                          float(ev_min), float(ev_max), float(low_fraction), float(high_fraction), float(max_ev_step_up), float(max_ev_step_down))
 
 
+class ResampleFilter(enum.IntEnum):
+    """include/strolle_hip.h StResampleFilter: how post-processing resamples the frame to the output size"""
+    NEAREST = 0
+    BILINEAR = 1
+    CATMULL_ROM = 2
+
+
+class StPostDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("output_width", C.c_uint32), ("output_height", C.c_uint32),
+                ("filter", C.c_uint32), ("fxaa_edge_threshold", C.c_float), ("fxaa_edge_threshold_min", C.c_float), ("fxaa_subpixel", C.c_float)]
+
+
+POST_FXAA = 1
+
+
+def post_desc(fxaa: bool = False, output_size=None, filter=ResampleFilter.BILINEAR, fxaa_edge_threshold: float = 0.0,
+              fxaa_edge_threshold_min: float = 0.0, fxaa_subpixel: float = 0.75) -> StPostDesc:
+    """A StPostDesc: FXAA on the display-referred colour and / or resampling to output_size = (width, height) (None: the render size);
+    thresholds of 0 are FXAA 3.11's defaults (include/strolle_hip.h "post-processing")."""
+    ow, oh = output_size if output_size else (0, 0)
+    return StPostDesc(C.sizeof(StPostDesc), POST_FXAA if fxaa else 0, int(ow), int(oh), int(filter), float(fxaa_edge_threshold),
+                      float(fxaa_edge_threshold_min), float(fxaa_subpixel))
+
+
 class StRay(C.Structure):
     """include/strolle_hip.h StRay (32 B): hits count for 0 < t < t_max; the direction is used as given (t in units of |direction|)."""
     _fields_ = [("origin", C.c_float * 3), ("t_max", C.c_float), ("direction", C.c_float * 3), ("_pad", C.c_uint32)]
@@ -242,7 +266,7 @@ class PassBit(enum.IntFlag):
     GI_PREVIEW_0 = 1 << 15; GI_PREVIEW_1 = 1 << 16; GI_RESOLVING = 1 << 17
     DENOISE_REPROJECT_DI = 1 << 18; DENOISE_REPROJECT_GI = 1 << 19; DENOISE_VARIANCE = 1 << 20
     DENOISE_WAVELET_0 = 1 << 21; DENOISE_WAVELET_1 = 1 << 22; DENOISE_WAVELET_2 = 1 << 23; DENOISE_WAVELET_3 = 1 << 24; DENOISE_WAVELET_4 = 1 << 25
-    COMPOSITION = 1 << 26; BVH_HEATMAP = 1 << 27; REF_TRACING = 1 << 28; REF_SHADING = 1 << 29
+    COMPOSITION = 1 << 26; BVH_HEATMAP = 1 << 27; REF_TRACING = 1 << 28; REF_SHADING = 1 << 29; POST = 1 << 30
 
 
 # ----------------------------------------------------------------------------- value types mirroring the reference
@@ -456,6 +480,11 @@ class _Binding:
             self.camera_get_display = fn("camera_get_display", [vp, u64, P(StDisplayDesc), P(i32)])
             self.camera_exposure = fn("camera_exposure", [vp, u64, P(C.c_float), P(C.c_float), P(C.c_float)])
             self.debug_camera_histogram = fn("debug_camera_histogram", [vp, u64, P(u32)])
+        if hasattr(lib, prefix + "camera_set_post"):   # output post-processing (likewise)
+            self.camera_set_post = fn("camera_set_post", [vp, u64, P(StPostDesc)])
+            self.camera_get_post = fn("camera_get_post", [vp, u64, P(StPostDesc), P(i32)])
+            self.camera_output_size = fn("camera_output_size", [vp, u64, P(u32), P(u32)])
+            self.post_process = fn("post_process", [vp, P(StPostDesc), vp, u32, u32, vp, i32, vp])
         if hasattr(lib, prefix + "mesh_set_skin"):
             self.mesh_set_skin = fn("mesh_set_skin", [vp, u64, vp, sz, u32])
         if hasattr(lib, prefix + "engine_set_deformation_motion"):   # deformation motion (likewise absent from an older library)
@@ -904,6 +933,29 @@ class Engine(EngineBase):
         out = np.zeros(DISPLAY_BINS, np.uint32)
         self._check(self._b.debug_camera_histogram(self._h, camera, out.ctypes.data_as(C.POINTER(C.c_uint32))))
         return out
+
+    # ---- output post-processing (include/strolle_hip.h "post-processing"): takes effect at the camera's next render
+    def set_post(self, camera: int, desc: Optional[StPostDesc] = None, **kw):
+        """st_camera_set_post: a StPostDesc, or post_desc(**kw) when keywords are given; neither = off."""
+        if desc is None and kw:
+            desc = post_desc(**kw)
+        self._check(self._b.camera_set_post(self._h, camera, C.byref(desc) if desc is not None else None))
+
+    def post(self, camera: int):
+        """st_camera_get_post: (the last StPostDesc set, whether post-processing is on)."""
+        d, on = StPostDesc(), C.c_int()
+        self._check(self._b.camera_get_post(self._h, camera, C.byref(d), C.byref(on)))
+        return d, bool(on.value)
+
+    def output_size(self, camera: int):
+        """st_camera_output_size: (width, height) of the buffer st_render_camera writes."""
+        w, h = C.c_uint32(), C.c_uint32()
+        self._check(self._b.camera_output_size(self._h, camera, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def post_process(self, desc: StPostDesc, src_ptr: int, width: int, height: int, dst_ptr: int, dst_format: int = 0, stream: int = 0):
+        """st_post_process: FXAA and / or resampling of any RGBA32F device image into dst (the desc's output size) in dst_format."""
+        self._check(self._b.post_process(self._h, C.byref(desc), src_ptr, width, height, dst_ptr, int(dst_format), stream))
 
     # ---- environment lighting (include/strolle_hip.h "environment lighting"): takes effect at the next tick
     def set_environment(self, texels, intensity: float = 1.0, yaw: float = 0.0, keep_sun: bool = False, uniform: bool = False):

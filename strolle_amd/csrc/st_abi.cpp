@@ -236,7 +236,7 @@ int st_camera_delete(StEngine* e, StHandle h) {
     Engine* en = E(e);
     auto it = en->cameras.find(h);
     if (it == en->cameras.end()) return ST_OK;
-    if (en->has_device) { ST_HIP(hipSetDevice(en->device)); ST_HIP(hipDeviceSynchronize()); Engine::release_camera(*it->second); Engine::release_display(*it->second); }
+    if (en->has_device) { ST_HIP(hipSetDevice(en->device)); ST_HIP(hipDeviceSynchronize()); Engine::release_camera(*it->second); Engine::release_display(*it->second); Engine::release_post(*it->second); }
     en->dist_forget_camera(h);
     en->cameras.erase(it);
     return ST_OK;
@@ -254,6 +254,7 @@ int st_camera_set_window(StEngine* e, StHandle h, uint32_t x0, uint32_t y0, uint
     ST_REQUIRE(x0 % 16u == 0u && (x1 % 16u == 0u || x1 == s.desc.width), "window columns must be multiples of 16 (or the frame's right edge)");
     const bool full = x0 == 0u && y0 == 0u && x1 == s.desc.width && y1 == s.desc.height;
     ST_REQUIRE(full || !s.display_auto(), "a window on a camera with auto-exposure would meter the tile alone (include/strolle_hip.h \"display transforms\")");
+    ST_REQUIRE(full || !s.post_on, "a window on a camera with post-processing: FXAA and the resampler read across tile edges (include/strolle_hip.h \"post-processing\")");
     s.row0 = y0; s.row1 = y1; s.col0 = x0; s.col1 = x1;
     return ST_OK;
 }
@@ -295,6 +296,35 @@ int st_debug_camera_histogram(StEngine* e, StHandle h, uint32_t bins[64]) {
     auto it = E(e)->cameras.find(h);
     if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
     return E(e)->display_histogram(*it->second, bins);
+}
+
+// ---- output post-processing (st_post.cpp)
+int st_camera_set_post(StEngine* e, StHandle h, const StPostDesc* desc) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    return E(e)->set_post(*it->second, desc);
+}
+int st_camera_get_post(StEngine* e, StHandle h, StPostDesc* out, int* enabled) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    const CameraState& s = *it->second;
+    if (out) { *out = s.post; out->struct_size = sizeof(StPostDesc); }
+    if (enabled) *enabled = s.post_on ? 1 : 0;
+    return ST_OK;
+}
+int st_camera_output_size(StEngine* e, StHandle h, uint32_t* width, uint32_t* height) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    if (width) *width = it->second->out_width();
+    if (height) *height = it->second->out_height();
+    return ST_OK;
+}
+int st_post_process(StEngine* e, const StPostDesc* desc, const void* src, uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
+    ST_REQUIRE(e, "null engine");
+    return E(e)->post_process(desc, src, width, height, dst, dst_format, static_cast<hipStream_t>(stream));
 }
 
 int st_tick(StEngine* e, void* stream) { ST_REQUIRE(e, "null engine"); return E(e)->tick(static_cast<hipStream_t>(stream)); }

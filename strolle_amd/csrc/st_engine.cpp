@@ -90,7 +90,9 @@ Engine::~Engine() {
     if (!has_device) return;
     (void)hipSetDevice(device);
     (void)hipDeviceSynchronize();
-    for (auto& kv : cameras) { release_camera(*kv.second); release_display(*kv.second); }
+    for (auto& kv : cameras) { release_camera(*kv.second); release_display(*kv.second); release_post(*kv.second); }
+    if (post_scratch) (void)hipFree(post_scratch);
+    if (ev_post_scratch) (void)hipEventDestroy(ev_post_scratch);
     for (DeviceArray* d : {&d_byte_luts, &d_atlas, &d_blue_noise, &d_transmittance, &d_scattering, &d_sky, &d_mesh_store, &d_skin_bind, &d_skin_corners, &d_posed, &d_skin_jobs, &d_skin_starts, &d_palettes}) d->release();
     for (LightSet& l : light_sets) { l.buf.release(); l.fence.release(); }
     if (env_live) { env_live->texels.release(); env_live->table.release(); env_live->fence.release(); }

@@ -307,6 +307,18 @@ struct CameraState {
     hipEvent_t ev_display = nullptr; hipStream_t display_stream = nullptr; bool display_pending = false;
     bool display_auto() const { return display_on && (display.flags & ST_DISPLAY_AUTO_EXPOSURE) != 0u; }
     bool windowed() const { return row0 != 0u || col0 != 0u || row1 != desc.height || col1 != desc.width; }
+    // Output post-processing (st_post.cpp; include/strolle_hip.h "post-processing"). Like the display it is not part of the per-camera
+    // buffers and survives st_camera_update. While a frame needs it, the composing launch writes post_plane[0] (render size, RGBA32F)
+    // instead of the caller's buffer; post_plane[1] carries FXAA's output to the resampler when both run. Both are allocated by the first
+    // frame that needs them and again only when the render size changed (post_plane_pixels).
+    StPostDesc post{}; bool post_on = false;
+    void* post_plane[2] = {nullptr, nullptr}; size_t post_plane_pixels[2] = {0, 0};
+    // recorded behind each frame's post launches on `post_stream`: a frame on another stream waits for it before it writes the planes again
+    hipEvent_t ev_post = nullptr; hipStream_t post_stream = nullptr; bool post_pending = false;
+    bool post_resizes() const { return post_on && post.output_width != 0u && (post.output_width != desc.width || post.output_height != desc.height); }
+    bool post_fxaa() const { return post_on && (post.flags & ST_POST_FXAA) != 0u && desc.mode != ST_MODE_BVH_HEATMAP; }   // heatmap frames are false colour
+    uint32_t out_width() const { return post_on && post.output_width != 0u ? post.output_width : desc.width; }
+    uint32_t out_height() const { return post_on && post.output_width != 0u ? post.output_height : desc.height; }
 };
 inline size_t plane_texels_per_pixel(int id) {
     if (id >= ST_BUF_DI_RESERVOIRS_0 && id <= ST_BUF_DI_RESERVOIRS_2) return 2;
@@ -700,6 +712,16 @@ struct Engine {
     int display_exposure(CameraState& c, float* scale, float* metered_ev, float* adapted_ev);
     int display_histogram(CameraState& c, uint32_t* bins);
     static void release_display(CameraState& c);
+    // ---- output post-processing (st_post.cpp)
+    struct PostPlan { bool fxaa = false, resample = false; PostArgs fx{}, rs{}; double fxaa_bytes = 0.0, resample_bytes = 0.0; };
+    static PostPlan post_plan(const StPostDesc& d, bool fxaa, const void* src, uint32_t w, uint32_t h, void* mid, void* dst, uint32_t format);
+    int set_post(CameraState& c, const StPostDesc* desc);
+    int post_planes(CameraState& c, bool second, hipStream_t stream);   // the camera's planes at its render size (allocates only when that changed), ordered behind their last readers
+    int post_done(CameraState& c, hipStream_t stream);                  // behind a frame's post launches
+    int post_process(const StPostDesc* desc, const void* src, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
+    static void release_post(CameraState& c);
+    void* post_scratch = nullptr; size_t post_scratch_pixels = 0;   // st_post_process's intermediate plane (FXAA -> resampler)
+    hipEvent_t ev_post_scratch = nullptr; hipStream_t post_scratch_stream = nullptr; bool post_scratch_pending = false;
     int scene_args(KArgs& a, bool heatmap) const;   // the scene half of KArgs (st_render.cpp): render() and the scene queries
 
     // ---- scene queries (st_query.cpp; include/strolle_hip.h "scene queries")

@@ -80,3 +80,7 @@ ST_LAUNCHER(launch_env_debug, (const KArgs& a, uint32_t what /* 0 eval, 1 sample
 // one-workgroup finalize behind a metered frame (histogram -> metered / adapted EV and the next frame's scale; the histogram cleared)
 ST_LAUNCHER(launch_display_reset, (void* state /* kDisplayBytes */, float scale, float adapted_ev, hipStream_t s))
 ST_LAUNCHER(launch_display_finalize, (void* state, float ev_min, float ev_max, float low_fraction, float high_fraction, float step_up, float step_down, float compensation_ev, hipStream_t s))
+// output post-processing (k_post.hip; st_post.cpp): FXAA over a display-referred RGBA32F image (dst: the same size, any output format) and the
+// resampler (nearest / bilinear / Catmull-Rom to out_width x out_height, any output format); equal sizes make it a format-converting copy
+ST_LAUNCHER(launch_post_fxaa, (const PostArgs& p, hipStream_t s))
+ST_LAUNCHER(launch_post_resample, (const PostArgs& p, hipStream_t s))

@@ -173,6 +173,12 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
     if (int rc = reader_begin(stream, true)) return rc;
     DisplayArgs disp{};   // the camera's display transform (st_display.cpp): both composing launches take it
     if (int rc = display_begin(c, stream, c.desc.mode == ST_MODE_BVH_HEATMAP, disp)) return rc;
+    // Output post-processing (st_post.cpp): while this frame needs it, every composing launch below writes the camera's own render-size
+    // RGBA32F plane instead of `out`, and the post launches at the end of this function write `out` behind it on `stream`.
+    const bool post_fxaa = out && c.post_fxaa(), post_resample = out && c.post_resizes(), post = post_fxaa || post_resample;
+    if (post) if (int rc = post_planes(c, post_fxaa && post_resample, stream)) return rc;
+    void* const comp_out = post ? c.post_plane[0] : out;
+    const uint32_t comp_format = post ? (uint32_t)ST_FORMAT_RGBA32F : c.out_format;
     const bool alt = c.frame % 2u == 1u;
     c.last_lean = 0u; c.last_lean_composed = false;
     KArgs a{};
@@ -220,11 +226,12 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
     last_launches.clear();
     bool mask_split = false;
     uint32_t launch_ordinal = 0u;
+    double post_bytes = -1.0;   // the post launches' bytes depend on the output size and format: set in front of them
     auto run = [&](int slot, uint64_t bits, auto&& launch) {
         if (last_launches.empty() || last_launches.back() != bits) last_launches.push_back(bits);  // a launch group is reported once
         if ((bits & pass_mask) != bits) { mask_split |= (bits & pass_mask) != 0; return; }
         if (launch_filter != ~0ull && !((launch_filter >> (launch_ordinal++ & 63u)) & 1ull)) return;  // measurement only: the frame's state is not meaningful afterwards
-        const double bytes = slot_bytes(slot);
+        const double bytes = post_bytes >= 0.0 ? post_bytes : slot_bytes(slot);
         a.ray_counter = c.counters + kCounterWordsPerSlot * slot;
         if (profiling && profile_kernel_events) {  // the dispatch's own timestamps (what rocprofv3's kernel trace reads)
             (void)profile_close();   // a scope the run-of-launches mode left open belongs to that mode
@@ -421,7 +428,7 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
                 if (nth == 4u && compose_in_wavelet) {
                     present_guard(c, out, cur); dist_guard(c.handle, out, cur);
                     run(KS_DENOISE_WAVELET_COMPOSE, ((uint64_t)ST_PASS_DENOISE_WAVELET_0 << nth) | ST_PASS_COMPOSITION, [&] {
-                        L.launch_denoise_wavelet_compose(a, 1u << nth, (float)(1u + nth), di[in_ix[nth]], di[out_ix[nth]], gi[in_ix[nth]], gi[out_ix[nth]], mode, out, c.out_format, a.lean == 0u, disp, cur); });
+                        L.launch_denoise_wavelet_compose(a, 1u << nth, (float)(1u + nth), di[in_ix[nth]], di[out_ix[nth]], gi[in_ix[nth]], gi[out_ix[nth]], mode, comp_out, comp_format, a.lean == 0u, disp, cur); });
                     composed = true;
                     continue;
                 }
@@ -433,7 +440,7 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
             present_guard(c, out, cur); dist_guard(c.handle, out, cur);
             const float4* di_diff = (denoise && (mode == ST_MODE_IMAGE || mode == ST_MODE_DI_DIFFUSE)) ? a.di_diff_curr_colors : a.di_diff_samples;
             const float4* gi_diff = (denoise && (mode == ST_MODE_IMAGE || mode == ST_MODE_GI_DIFFUSE)) ? a.gi_diff_curr_colors : a.gi_diff_samples;
-            run(KS_COMPOSITION, ST_PASS_COMPOSITION, [&] { L.launch_composition(a, mode, di_diff, gi_diff, out, c.out_format, disp, cur); });
+            run(KS_COMPOSITION, ST_PASS_COMPOSITION, [&] { L.launch_composition(a, mode, di_diff, gi_diff, comp_out, comp_format, disp, cur); });
             composed = true;
         };
 
@@ -503,7 +510,15 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
         const bool dn = c.desc.denoise != 0u;
         const float4* di_diff = (dn && (mode == ST_MODE_IMAGE || mode == ST_MODE_DI_DIFFUSE)) ? a.di_diff_curr_colors : a.di_diff_samples;
         const float4* gi_diff = (dn && (mode == ST_MODE_IMAGE || mode == ST_MODE_GI_DIFFUSE)) ? a.gi_diff_curr_colors : a.gi_diff_samples;
-        run(KS_COMPOSITION, ST_PASS_COMPOSITION, [&] { L.launch_composition(a, mode, di_diff, gi_diff, out, c.out_format, disp, cur); });
+        run(KS_COMPOSITION, ST_PASS_COMPOSITION, [&] { L.launch_composition(a, mode, di_diff, gi_diff, comp_out, comp_format, disp, cur); });
+    }
+    if (post) {   // the composing launch ran on `stream`; one launch group (ST_PASS_POST) of at most two kernels
+        cur = stream;
+        const PostPlan plan = post_plan(c.post, post_fxaa, c.post_plane[0], c.desc.width, c.desc.height, c.post_plane[1], out, c.out_format);
+        if (plan.fxaa) { post_bytes = plan.fxaa_bytes; run(KS_POST_FXAA, ST_PASS_POST, [&] { L.launch_post_fxaa(plan.fx, cur); }); }
+        if (plan.resample) { post_bytes = plan.resample_bytes; run(KS_POST_RESAMPLE, ST_PASS_POST, [&] { L.launch_post_resample(plan.rs, cur); }); }
+        post_bytes = -1.0;
+        if (int rc = post_done(c, stream)) return rc;
     }
     if (disp.meter && out) if (int rc = display_finalize(c, stream)) return rc;   // every composing launch ran on `stream`
     if (int rc = reader_end(stream, true, true)) return rc;   // the end of the last frame that reads these copies of the scene and the lights

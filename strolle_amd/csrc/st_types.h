@@ -83,6 +83,14 @@ constexpr size_t kDisplayLastOffset = (size_t)kDisplayReplicas * kDisplayBins * 
 constexpr size_t kDisplayStateOffset = kDisplayLastOffset + kDisplayBins * sizeof(uint32_t);
 constexpr size_t kDisplayBytes = kDisplayStateOffset + sizeof(DisplayState);
 
+// Output post-processing (include/strolle_hip.h "post-processing"; st_post.cpp, k_post.hip): one launch's arguments. FXAA reads `src`
+// (width x height RGBA32F) and writes `dst` at the same size; the resampler writes out_width x out_height. Both store `format`.
+struct PostArgs {
+    const float4* src; void* dst;
+    uint32_t width, height, out_width, out_height, format, filter;
+    float edge_threshold, edge_threshold_min, subpixel;   // FXAA, defaults resolved by the host
+};
+
 // Everything a per-pixel kernel can touch, passed by value as the kernel argument (scalar loads).
 struct KArgs {
     GpuCamera cam, prev_cam;
