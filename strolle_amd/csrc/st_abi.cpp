@@ -32,14 +32,14 @@ int st_engine_create(int device_ordinal, StEngine** out) {
         // LUT storage (zero until the first non-heatmap render generates them)
         const size_t lut_bytes[3] = {sizeof(float4) * 256 * 64, sizeof(float4) * 32 * 32, sizeof(float4) * 256 * 256};
         DeviceArray* luts[3] = {&e->d_transmittance, &e->d_scattering, &e->d_sky};
-        for (int i = 0; i < 3; i++) { ST_HIP(hipMalloc(&luts[i]->ptr, lut_bytes[i])); luts[i]->capacity = lut_bytes[i]; ST_HIP(hipMemset(luts[i]->ptr, 0, lut_bytes[i])); }
-        ST_HIP(hipMalloc(&e->d_byte_luts.ptr, sizeof(float) * 1024)); e->d_byte_luts.capacity = sizeof(float) * 1024;
+        for (int i = 0; i < 3; i++) { if (int rc = luts[i]->reserve(lut_bytes[i], lut_bytes[i])) return rc; ST_HIP(hipMemset(luts[i]->ptr, 0, lut_bytes[i])); }
+        if (int rc = e->d_byte_luts.reserve(sizeof(float) * 1024, sizeof(float) * 1024)) return rc;
         {   // the wide walks' overflow words (st_engine.h walk_flags_host): page-locked, mapped, written by a kernel only when a push is dropped
-            void* host = nullptr; void* dev = nullptr;
-            ST_HIP(hipHostMalloc(&host, 64, hipHostMallocMapped));
-            memset(host, 0, 64);
-            ST_HIP(hipHostGetDevicePointer(&dev, host, 0));
-            e->walk_flags_host = static_cast<volatile uint32_t*>(host); e->walk_flags_dev = static_cast<uint32_t*>(dev);
+            void* dev = nullptr;
+            if (int rc = e->walk_flags_mem.reserve(64, hipHostMallocMapped)) return rc;
+            memset(e->walk_flags_mem.ptr, 0, 64);
+            ST_HIP(hipHostGetDevicePointer(&dev, e->walk_flags_mem.ptr, 0));
+            e->walk_flags_host = static_cast<volatile uint32_t*>(e->walk_flags_mem.ptr); e->walk_flags_dev = static_cast<uint32_t*>(dev);
         }
         e->L.launch_build_byte_luts(static_cast<float*>(e->d_byte_luts.ptr), nullptr);
         ST_HIP(hipDeviceSynchronize());
@@ -236,9 +236,9 @@ int st_camera_delete(StEngine* e, StHandle h) {
     Engine* en = E(e);
     auto it = en->cameras.find(h);
     if (it == en->cameras.end()) return ST_OK;
-    if (en->has_device) { ST_HIP(hipSetDevice(en->device)); ST_HIP(hipDeviceSynchronize()); Engine::release_camera(*it->second); Engine::release_display(*it->second); Engine::release_post(*it->second); }
+    if (en->has_device) { ST_HIP(hipSetDevice(en->device)); ST_HIP(hipDeviceSynchronize()); }
     en->dist_forget_camera(h);
-    en->cameras.erase(it);
+    en->cameras.erase(it);   // with the device current and idle: what the camera owns goes with it
     return ST_OK;
 }
 int st_camera_set_window(StEngine* e, StHandle h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) {
@@ -467,11 +467,11 @@ int st_debug_variance_flags(StEngine* e, StHandle h, uint64_t* tile_mask_out, si
     if (it == en->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
     if (!en->has_device) return fail(ST_ERR_NO_DEVICE, "host-only engine");
     CameraState& c = *it->second;
-    *tiles = c.tile_mask_tiles;
+    *tiles = c.tile_mask_tiles();
     if (!tile_mask_out) return ST_OK;
-    ST_REQUIRE(capacity_tiles >= c.tile_mask_tiles, "buffer too small");
+    ST_REQUIRE(capacity_tiles >= c.tile_mask_tiles(), "buffer too small");
     ST_HIP(hipSetDevice(en->device)); ST_HIP(hipDeviceSynchronize());
-    ST_HIP(hipMemcpy(tile_mask_out, c.tile_mask, c.tile_mask_tiles * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    ST_HIP(hipMemcpy(tile_mask_out, c.tile_mask.ptr, c.tile_mask_tiles() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return ST_OK;
 }
 int st_debug_set_pass_mask(StEngine* e, uint64_t mask) {
@@ -526,7 +526,7 @@ int st_camera_ray_count(StEngine* e, StHandle h, uint64_t* out, int reset) {
     uint64_t total = 0;
     for (int i = 0; i < KS_COUNT; i++) total += host[2 * i];
     *out = total;
-    if (reset) { ST_HIP(hipMemset(it->second->counters, 0, kCounterBytes)); memset(it->second->profiled_traversal_bytes, 0, sizeof(it->second->profiled_traversal_bytes)); ST_HIP(hipDeviceSynchronize()); }
+    if (reset) { ST_HIP(hipMemset(it->second->counters.ptr, 0, kCounterBytes)); memset(it->second->profiled_traversal_bytes, 0, sizeof(it->second->profiled_traversal_bytes)); ST_HIP(hipDeviceSynchronize()); }
     return ST_OK;
 }
 int st_debug_read_scene(StEngine* e, int what, void* out, size_t capacity, size_t* written) {

@@ -40,20 +40,20 @@ int Engine::display_begin(CameraState& c, hipStream_t stream, bool heatmap, Disp
     if (!c.display_on || heatmap) return ST_OK;
     d.on = 1u; d.tonemap = c.display.tonemap; d.scale = c.display_scale;
     if (!c.display_auto()) return ST_OK;
-    if (!c.display_state) {
-        if (hipMalloc(&c.display_state, kDisplayBytes) != hipSuccess) { (void)hipGetLastError(); c.display_state = nullptr; return fail(ST_ERR_HIP, "hipMalloc(display state) failed"); }
+    if (!c.display_state.ptr) {
+        if (int rc = c.display_state.reserve(kDisplayBytes, kDisplayBytes)) return rc;
         c.display_reset = true;
     }
-    if (!c.ev_display) ST_HIP(hipEventCreateWithFlags(&c.ev_display, hipEventDisableTiming));
     // the previous metered frame's finalize ran on another stream: this frame's reads of the state and adds to the histogram come after it
-    if (c.display_pending && c.display_stream != stream) ST_HIP(hipStreamWaitEvent(stream, c.ev_display, 0));
+    // (on the same stream they do anyway: no event between the two frames' kernels)
+    if (int rc = c.display_done.wait(stream, Fence::OtherStreams, Fence::Keep)) return rc;
     if (c.display_reset) {
-        L.launch_display_reset(c.display_state, c.display_scale, (float)std::log2(kMidGrey), stream);
+        L.launch_display_reset(c.display_state.ptr, c.display_scale, (float)std::log2(kMidGrey), stream);
         c.display_reset = false;
     }
     d.meter = 1u;
-    d.state = reinterpret_cast<const float*>(static_cast<const char*>(c.display_state) + kDisplayStateOffset);
-    d.hist = static_cast<uint32_t*>(c.display_state);
+    d.state = reinterpret_cast<const float*>(c.display_state.as<const char>() + kDisplayStateOffset);
+    d.hist = c.display_state.as<uint32_t>();
     d.ev_min = c.display.ev_min;
     d.bins_per_ev = (float)kDisplayBins / (c.display.ev_max - c.display.ev_min);
     return ST_OK;
@@ -61,10 +61,8 @@ int Engine::display_begin(CameraState& c, hipStream_t stream, bool heatmap, Disp
 
 int Engine::display_finalize(CameraState& c, hipStream_t stream) {
     const StDisplayDesc& s = c.display;
-    L.launch_display_finalize(c.display_state, s.ev_min, s.ev_max, s.low_fraction, s.high_fraction, s.max_ev_step_up, s.max_ev_step_down, s.exposure_ev, stream);
-    ST_HIP(hipEventRecord(c.ev_display, stream));
-    c.display_stream = stream; c.display_pending = true;
-    return ST_OK;
+    L.launch_display_finalize(c.display_state.ptr, s.ev_min, s.ev_max, s.low_fraction, s.high_fraction, s.max_ev_step_up, s.max_ev_step_down, s.exposure_ev, stream);
+    return c.display_done.record(stream);
 }
 
 int Engine::display_exposure(CameraState& c, float* scale, float* metered_ev, float* adapted_ev) {
@@ -73,11 +71,11 @@ int Engine::display_exposure(CameraState& c, float* scale, float* metered_ev, fl
     if (c.display_on) v[0] = c.display_scale;
     if (c.display_auto()) {
         v[2] = (float)std::log2(kMidGrey);
-        if (c.display_state && !c.display_reset) {
+        if (c.display_state.ptr && !c.display_reset) {
             ST_HIP(hipSetDevice(device));
             ST_HIP(hipDeviceSynchronize());
             DisplayState st{};
-            ST_HIP(hipMemcpy(&st, static_cast<const char*>(c.display_state) + kDisplayStateOffset, sizeof(st), hipMemcpyDeviceToHost));
+            ST_HIP(hipMemcpy(&st, c.display_state.as<const char>() + kDisplayStateOffset, sizeof(st), hipMemcpyDeviceToHost));
             v[0] = st.scale; v[1] = st.metered_ev; v[2] = st.adapted_ev;
         }
     }
@@ -90,18 +88,11 @@ int Engine::display_exposure(CameraState& c, float* scale, float* metered_ev, fl
 int Engine::display_histogram(CameraState& c, uint32_t* bins) {
     if (!has_device) return fail(ST_ERR_NO_DEVICE, "st_debug_camera_histogram on a host-only engine");
     memset(bins, 0, kDisplayBins * sizeof(uint32_t));
-    if (!c.display_state) return ST_OK;
+    if (!c.display_state.ptr) return ST_OK;
     ST_HIP(hipSetDevice(device));
     ST_HIP(hipDeviceSynchronize());
-    ST_HIP(hipMemcpy(bins, static_cast<const char*>(c.display_state) + kDisplayLastOffset, kDisplayBins * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    ST_HIP(hipMemcpy(bins, c.display_state.as<const char>() + kDisplayLastOffset, kDisplayBins * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return ST_OK;
-}
-
-// with the device idle (st_camera_delete, ~Engine)
-void Engine::release_display(CameraState& c) {
-    if (c.display_state) (void)hipFree(c.display_state);
-    if (c.ev_display) (void)hipEventDestroy(c.ev_display);
-    c.display_state = nullptr; c.ev_display = nullptr; c.display_stream = nullptr; c.display_pending = false;
 }
 
 }  // namespace st

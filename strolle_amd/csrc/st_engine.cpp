@@ -85,38 +85,12 @@ void Engine::reset_profile_totals() {
     }
 }
 
+// With the device current and idle, every member lets go of what it owns (st_engine.h "Ownership").
 Engine::~Engine() {
     release_dist();
     if (!has_device) return;
     (void)hipSetDevice(device);
     (void)hipDeviceSynchronize();
-    for (auto& kv : cameras) { release_camera(*kv.second); release_display(*kv.second); release_post(*kv.second); }
-    if (post_scratch) (void)hipFree(post_scratch);
-    if (ev_post_scratch) (void)hipEventDestroy(ev_post_scratch);
-    for (DeviceArray* d : {&d_byte_luts, &d_atlas, &d_blue_noise, &d_transmittance, &d_scattering, &d_sky, &d_mesh_store, &d_skin_bind, &d_skin_corners, &d_posed, &d_skin_jobs, &d_skin_starts, &d_palettes}) d->release();
-    for (LightSet& l : light_sets) { l.buf.release(); l.fence.release(); }
-    if (env_live) { env_live->texels.release(); env_live->table.release(); env_live->fence.release(); }
-    release_environments(true);
-    d_env_grid.release();
-    if (d_env_bad) (void)hipFree(d_env_bad);
-    for (SceneSet& t : sets) {
-        for (DeviceArray* d : {&t.bvh, &t.tri_attr, &t.xforms, &t.materials, &t.base_packed, &t.tri_geo, &t.tri_bounds, &t.entry_of_tri, &t.parent, &t.refit_local, &t.refit_items, &t.refit_batch_off, &t.bvh_compact, &t.tri_info, &t.lb_keys_a, &t.lb_keys_b, &t.lb_temp, &t.lb_seg, &t.lb_children, &t.lb_node_box, &t.lb_small, &t.bvh_wide, &t.wide_topo, &t.wide_leaf_entry, &t.bake_jobs, &t.bake_starts, &t.instance_table}) d->release();
-        t.fence.release();
-    }
-    if (copy_stream) (void)hipStreamDestroy(copy_stream);
-    if (skin_stream) (void)hipStreamDestroy(skin_stream);
-    if (ev_skinned) (void)hipEventDestroy(ev_skinned);
-    if (ev_posed_read) (void)hipEventDestroy(ev_posed_read);
-    if (ev_deform_read) (void)hipEventDestroy(ev_deform_read);
-    if (query_stream) (void)hipStreamDestroy(query_stream);
-    d_query_rays.release(); d_query_hits.release();
-    if (query_pinned) (void)hipHostFree(query_pinned);
-    if (ev_copy) (void)hipEventDestroy(ev_copy);
-    for (auto& r : profile_records) { if (r.owns_start) (void)hipEventDestroy(r.start); (void)hipEventDestroy(r.stop); }
-    for (auto e : event_pool) (void)hipEventDestroy(e);
-    if (ev_tick) (void)hipEventDestroy(ev_tick);
-    if (walk_flags_host) (void)hipHostFree(const_cast<uint32_t*>(walk_flags_host));
-    staging.release();
 }
 
 }  // namespace st

@@ -9,6 +9,12 @@
 // Behavioural contract: strolle/src/lib.rs (Engine), camera_controller.rs (pass order), lights.rs / materials.rs /
 // instances.rs / triangles.rs (stores), camera.rs (camera uniform). The wgpu plumbing of the reference (bind groups, mapped
 // buffers, textures) is replaced by plain device allocations and pointer swaps.
+// Ownership: every device allocation, event, stream and page-locked buffer of the host engine is a member of a move-only type that frees it
+// in its destructor (DeviceArray, Event, Stream, PinnedBuffer, below) — teardown lists nothing. A destructor runs with whatever device is
+// current, so whoever lets one of them go first makes the engine's device current and, where work may still use the resource, joins it
+// (~Engine, st_camera_delete, st_camera_update; st_tick for everything a tick replaces). st_dist.cpp keeps its own protocol.
+// Stream order between users of one resource on different streams is a Fence (below): record / record_chained behind the users, wait
+// (from any stream or only from other streams than the recorder; keeping or clearing the recording), host_wait, poll, settled.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -157,14 +163,79 @@ struct SlotRanges {  // utils/allocator.rs
     }
 };
 
+// ------------------------------------------------------------------ owners of HIP resources (the rule: this file's header comment)
+// Each is move-only (a declared move makes a copy a compile error) and lets go in its destructor; `h` / `ptr` stay readable for the calls that use them.
+struct Event {   // made by its first recording, without timing unless told otherwise (the profiler's are timed)
+    hipEvent_t h = nullptr; unsigned flags = hipEventDisableTiming;
+    Event() = default;
+    explicit Event(unsigned f) : flags(f) {}
+    Event(Event&& o) noexcept : h(o.h), flags(o.flags) { o.h = nullptr; }
+    Event& operator=(Event&& o) noexcept { std::swap(h, o.h); std::swap(flags, o.flags); return *this; }
+    ~Event() { reset(); }
+    void reset() { if (h) (void)hipEventDestroy(h); h = nullptr; }
+    hipEvent_t get() { if (!h) (void)hipEventCreateWithFlags(&h, flags); return h; }
+    int record(hipStream_t s) { if (!h) ST_HIP(hipEventCreateWithFlags(&h, flags)); ST_HIP(hipEventRecord(h, s)); return ST_OK; }
+    int wait(hipStream_t s) const { if (h) ST_HIP(hipStreamWaitEvent(s, h, 0)); return ST_OK; }   // (never recorded: nothing to wait for)
+};
+struct Stream {   // created where it is first needed — flags and priority are that site's business — and used as the handle it converts to
+    hipStream_t h = nullptr;
+    Stream() = default;
+    Stream(Stream&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Stream& operator=(Stream&& o) noexcept { std::swap(h, o.h); return *this; }
+    ~Stream() { reset(); }
+    void reset() { if (h) (void)hipStreamDestroy(h); h = nullptr; }   // destroys only: a site that must drain it first says so
+    operator hipStream_t() const { return h; }
+};
+struct PinnedBuffer {   // page-locked host memory
+    void* ptr = nullptr; size_t capacity = 0;
+    PinnedBuffer() = default;
+    PinnedBuffer(PinnedBuffer&& o) noexcept : ptr(o.ptr), capacity(o.capacity) { o.ptr = nullptr; o.capacity = 0; }
+    PinnedBuffer& operator=(PinnedBuffer&& o) noexcept { std::swap(ptr, o.ptr); std::swap(capacity, o.capacity); return *this; }
+    ~PinnedBuffer() { release(); }
+    // room for `bytes`: a smaller buffer is replaced by one of exactly that size (what it held is not kept)
+    int reserve(size_t bytes, unsigned flags = hipHostMallocDefault) {
+        if (bytes <= capacity) return ST_OK;
+        release();
+        ST_HIP(hipHostMalloc(&ptr, bytes, flags)); capacity = bytes;
+        return ST_OK;
+    }
+    void release() { if (ptr) (void)hipHostFree(ptr); ptr = nullptr; capacity = 0; }
+};
+
+// "X is in use up to here on stream S; its next user on another stream comes after that": an event, whether a recording may still have to be
+// waited for (`pending`), and the stream of the last recording. The sites differ in real ways, so each one names its variant:
+//   record(s)            the users of X enqueued on `s` so far end here
+//   record_chained(s)    the same, behind a wait for the fence's own earlier recording: one event then covers users on several streams
+//   wait(s, from, then)  `s` continues behind the recording. from = OtherStreams skips the wait when `s` itself made the recording (stream order
+//                        says as much, and an event between two kernels costs the second one 3-15 us: st_kernels.h); AnyStream queues it
+//                        regardless. then = Clear forgets the recording (its one next user, a writer, has waited); Keep leaves it to later waiters.
+//   host_wait()          the host waits for it; clears
+//   poll()               whether nothing is pending any more; a recording that has completed is cleared (not ready is left in hipGetLastError)
+//   settled()            the caller has joined the whole device: nothing is pending (no HIP call)
+struct Fence {
+    enum From { AnyStream, OtherStreams };
+    enum Then { Keep, Clear };
+    Event ev; hipStream_t last = nullptr; bool pending = false;
+    int record(hipStream_t s) { if (int rc = ev.record(s)) return rc; last = s; pending = true; return ST_OK; }
+    int record_chained(hipStream_t s) { if (int rc = wait(s, AnyStream, Keep)) return rc; return record(s); }
+    int wait(hipStream_t s, From from, Then then) {
+        if (pending && (from == AnyStream || last != s)) ST_HIP(hipStreamWaitEvent(s, ev.h, 0));
+        if (then == Clear) pending = false;
+        return ST_OK;
+    }
+    int host_wait() { if (pending) ST_HIP(hipEventSynchronize(ev.h)); pending = false; return ST_OK; }
+    bool poll() { if (pending && hipEventQuery(ev.h) == hipSuccess) pending = false; return !pending; }
+    void settled() { pending = false; }
+};
+
 // Pinned staging for the uploads of st_tick: what a tick sends is copied into one slot of page-locked memory and goes to
 // the device from there, so st_tick does not have to wait for the stream before the caller may touch the scene again —
 // with a scene that changes every frame the host then runs a frame ahead of the GPU instead of in lock-step with it.
-// Three slots: a slot is reused only after the copies issued from it have finished (its event).
+// Three slots: a slot is reused only after the copies issued from it have finished (its fence).
 struct StagingRing {
     static constexpr int kSlots = 3;
     static constexpr size_t kMaxSlotBytes = (size_t)256 << 20;  // larger ticks go from pageable memory and join the stream
-    struct Slot { char* mem = nullptr; size_t capacity = 0, used = 0; hipEvent_t done = nullptr; bool pending = false; };
+    struct Slot { PinnedBuffer mem; size_t used = 0; Fence done; };
     Slot slots[kSlots];
     int cur = 0;
     size_t wanted = 0;   // bytes the last tick asked for: the next slot is grown to hold that much
@@ -174,16 +245,10 @@ struct StagingRing {
         if (!enabled) return;
         cur = (cur + 1) % kSlots;
         Slot& s = slots[cur];
-        if (s.pending) { (void)hipEventSynchronize(s.done); s.pending = false; }
+        (void)s.done.host_wait();
         s.used = 0;
         const size_t want = std::min(kMaxSlotBytes, std::max<size_t>(wanted + wanted / 4, (size_t)1 << 20));
-        if (s.capacity < want) {
-            if (s.mem) (void)hipHostFree(s.mem);
-            s.mem = nullptr; s.capacity = 0;
-            void* m = nullptr;
-            if (hipHostMalloc(&m, want, hipHostMallocDefault) == hipSuccess) { s.mem = static_cast<char*>(m); s.capacity = want; }
-            else (void)hipGetLastError();
-        }
+        if (s.mem.reserve(want) != ST_OK) (void)hipGetLastError();   // (no slot: this tick's uploads go from pageable memory)
         wanted = 0;
     }
     // a page-locked copy of [src, src + bytes), or nullptr when the slot cannot take it (the caller then uploads from `src`
@@ -193,32 +258,27 @@ struct StagingRing {
         if (!enabled) return nullptr;
         Slot& s = slots[cur];
         const size_t at = (s.used + 255) & ~(size_t)255;
-        if (!s.mem || at + bytes > s.capacity) return nullptr;
-        memcpy(s.mem + at, src, bytes);
+        if (!s.mem.ptr || at + bytes > s.mem.capacity) return nullptr;
+        char* to = static_cast<char*>(s.mem.ptr) + at;
+        memcpy(to, src, bytes);
         s.used = at + bytes;
-        return s.mem + at;
+        return to;
     }
     int end_tick(hipStream_t stream) {
         if (!enabled) return ST_OK;
         Slot& s = slots[cur];
-        if (s.used == 0) return ST_OK;
-        if (!s.done) ST_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-        ST_HIP(hipEventRecord(s.done, stream));
-        s.pending = true;
-        return ST_OK;
+        return s.used == 0 ? ST_OK : s.done.record(stream);
     }
-    void release() {
-        for (Slot& s : slots) {
-            if (s.pending) (void)hipEventSynchronize(s.done);
-            if (s.done) (void)hipEventDestroy(s.done);
-            if (s.mem) (void)hipHostFree(s.mem);
-            s = Slot();
-        }
-    }
+    ~StagingRing() { for (Slot& s : slots) (void)s.done.host_wait(); }   // a slot's copies end before its memory goes
 };
 
 struct DeviceArray {
     void* ptr = nullptr; size_t capacity = 0;
+    DeviceArray() = default;
+    DeviceArray(DeviceArray&& o) noexcept : ptr(o.ptr), capacity(o.capacity) { o.ptr = nullptr; o.capacity = 0; }
+    DeviceArray& operator=(DeviceArray&& o) noexcept { std::swap(ptr, o.ptr); std::swap(capacity, o.capacity); return *this; }
+    ~DeviceArray() { release(); }
+    template <class T> T* as() const { return static_cast<T*>(ptr); }
     // `pageable` is set when the copy had to be issued straight from `src`: the caller joins the stream before `src` changes
     int upload(const void* src, size_t bytes, hipStream_t stream, StagingRing& ring, bool* pageable) {
         if (int rc = reserve(bytes, std::max<size_t>(bytes * 3 / 2, 4096))) return rc;
@@ -244,17 +304,6 @@ struct DeviceArray {
     void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; capacity = 0; }
 };
 
-// The hand-over of a double-buffered device copy (Engine::SceneSet, LightSet): busy = reads were enqueued since it was written; free_ev ends the last.
-struct CopyFence {
-    hipEvent_t free_ev = nullptr; bool busy = false;
-    int mark_read(hipStream_t s) {   // the copy is read up to here on `s` (the writer's side: Engine::pick_copy)
-        if (!free_ev) ST_HIP(hipEventCreateWithFlags(&free_ev, hipEventDisableTiming));
-        ST_HIP(hipEventRecord(free_ev, s)); busy = true;
-        return ST_OK;
-    }
-    void release() { if (free_ev) (void)hipEventDestroy(free_ev); free_ev = nullptr; busy = false; }
-};
-
 // ------------------------------------------------------------------ per-camera state (camera_controller/buffers.rs)
 constexpr int kInternalPlanes = 4;  // decoded-surface twins A/B (KArgs::sn / psn) + the pair the variance pass writes ahead of the strides-1+2 wavelet launch
 struct CameraState {
@@ -263,17 +312,18 @@ struct CameraState {
     uint64_t handle = 0;   // the StHandle this camera is known by (st_dist.cpp keys its partitions by it)
     uint32_t frame = 0, row0 = 0, row1 = 0, col0 = 0, col1 = 0;   // [row0,row1) x [col0,col1): the window this engine renders (st_camera_set_window)
     uint32_t out_format = 0;  // StOutputFormat (camera.rs:170-175 viewport.format)
-    void* slab = nullptr; size_t slab_bytes = 0;
+    DeviceArray slab;   // every plane in one allocation, each at a 256-byte boundary
     float4* plane[ST_BUF_COUNT + kInternalPlanes] = {};   // + the two decoded-surface twins (KArgs::sn / psn), internal only
     size_t plane_bytes[ST_BUF_COUNT + kInternalPlanes] = {};
-    unsigned long long* tile_mask = nullptr; size_t tile_mask_tiles = 0;  // two arrays of one u64 per 8x8 tile (KArgs::tile_mask, KArgs::gi_late_mask)
-    unsigned long long* counters = nullptr;  // KS_COUNT x kCounterLines x 8 u64 (one 64-B line each: {rays, traversal bytes, pad})
+    DeviceArray tile_mask;  // two arrays of one u64 per 8x8 tile (KArgs::tile_mask, KArgs::gi_late_mask)
+    size_t tile_mask_tiles() const { return tile_mask.capacity / (2 * sizeof(unsigned long long)); }
+    DeviceArray counters;   // KS_COUNT x kCounterLines x 8 u64 (one 64-B line each: {rays, traversal bytes, pad})
     unsigned long long profiled_traversal_bytes[KS_COUNT] = {};  // part of counters[..][1] already reported by st_profile_read
     // The two-stream frame pipeline (render()) belongs to the camera: its side stream and the events that order frame N+1's
     // passes behind frame N's are per camera, so cameras rendered on different caller streams never wait on — or race
     // with — each other's frames.
-    hipStream_t side_stream = nullptr;
-    hipEvent_t ev_di_head = nullptr, ev_gi_done = nullptr, ev_prim_ok = nullptr, ev_frame_done = nullptr, ev_setup = nullptr;
+    Stream side_stream;
+    Event ev_di_head, ev_gi_done, ev_prim_ok, ev_frame_done, ev_setup;
     bool have_prev_frame_events = false;
     // GI history hand-over without the copy. gi_resolving ends every frame by copying the frame's source reservoirs into
     // GI_RESERVOIRS_0, next frame's history (gi_resolving.rs:60-66): 128 B per pixel of pure copy. When the source is the
@@ -289,8 +339,8 @@ struct CameraState {
     // Present hand-over (st_camera_present_copy): composed frames leave for host memory on a stream of their own, behind the
     // frame that produced them, while the next frame's kernels run. Two copies may be in flight (the caller alternates two
     // output buffers); a render into a buffer whose copy is still pending is ordered behind that copy.
-    struct PresentSlot { const void* src = nullptr; void* dst = nullptr; hipEvent_t ev_src = nullptr, ev_done = nullptr; bool pending = false; };
-    hipStream_t present_stream = nullptr;
+    struct PresentSlot { const void* src = nullptr; void* dst = nullptr; Event ev_src, ev_done; bool pending = false; };
+    Stream present_stream;
     PresentSlot present[2];
     uint32_t present_next = 0;
     // the camera as the last render saw it (st_camera_pick casts through the frame on screen, not a later st_camera_update)
@@ -299,26 +349,27 @@ struct CameraState {
     // Display transform (st_display.cpp; include/strolle_hip.h "display transforms"). Not part of the per-camera buffers: it survives the
     // reallocation of st_camera_update. `display_state` (auto-exposure only) is kDisplayBytes of device memory — the histogram the composing
     // launches add to, the last finalized one, DisplayState — allocated by the first auto frame; `display_reset` asks the next render to
-    // put it back to its first-frame values. `ev_display` is recorded behind each finalize on `display_stream`: a frame on another stream
-    // waits for it first.
+    // put it back to its first-frame values. `display_done` is recorded behind each finalize: a frame on another stream waits for it first.
     StDisplayDesc display{}; bool display_on = false, display_reset = false;
     float display_scale = 1.0f;   // manual: 2^exposure_ev (host double, rounded)
-    void* display_state = nullptr;
-    hipEvent_t ev_display = nullptr; hipStream_t display_stream = nullptr; bool display_pending = false;
+    DeviceArray display_state; Fence display_done;
     bool display_auto() const { return display_on && (display.flags & ST_DISPLAY_AUTO_EXPOSURE) != 0u; }
     bool windowed() const { return row0 != 0u || col0 != 0u || row1 != desc.height || col1 != desc.width; }
     // Output post-processing (st_post.cpp; include/strolle_hip.h "post-processing"). Like the display it is not part of the per-camera
     // buffers and survives st_camera_update. While a frame needs it, the composing launch writes post_plane[0] (render size, RGBA32F)
     // instead of the caller's buffer; post_plane[1] carries FXAA's output to the resampler when both run. Both are allocated by the first
-    // frame that needs them and again only when the render size changed (post_plane_pixels).
+    // frame that needs them and again only when the render size changed.
     StPostDesc post{}; bool post_on = false;
-    void* post_plane[2] = {nullptr, nullptr}; size_t post_plane_pixels[2] = {0, 0};
-    // recorded behind each frame's post launches on `post_stream`: a frame on another stream waits for it before it writes the planes again
-    hipEvent_t ev_post = nullptr; hipStream_t post_stream = nullptr; bool post_pending = false;
+    DeviceArray post_plane[2];
+    Fence post_read;   // recorded behind each frame's post launches: a frame on another stream waits for it before it writes the planes again
     bool post_resizes() const { return post_on && post.output_width != 0u && (post.output_width != desc.width || post.output_height != desc.height); }
     bool post_fxaa() const { return post_on && (post.flags & ST_POST_FXAA) != 0u && desc.mode != ST_MODE_BVH_HEATMAP; }   // heatmap frames are false colour
     uint32_t out_width() const { return post_on && post.output_width != 0u ? post.output_width : desc.width; }
     uint32_t out_height() const { return post_on && post.output_width != 0u ? post.output_height : desc.height; }
+    // A present copy still in flight writes the caller's host memory: it lands before the stream goes. Everything else goes with its member —
+    // the caller has made the device current and joined it (st_camera_delete, ~Engine).
+    void join_present() { if (present_stream) (void)hipStreamSynchronize(present_stream); }
+    ~CameraState() { join_present(); }
 };
 inline size_t plane_texels_per_pixel(int id) {
     if (id >= ST_BUF_DI_RESERVOIRS_0 && id <= ST_BUF_DI_RESERVOIRS_2) return 2;
@@ -340,7 +391,7 @@ inline int materialize_gi_history(CameraState& c) {
 // sums the per-line counters of every kernel slot into host[2*slot + {0: rays, 1: traversal bytes}]
 inline int read_counters(const CameraState& c, unsigned long long* host /* 2*KS_COUNT */) {
     std::vector<unsigned long long> raw(kCounterWordsPerSlot * KS_COUNT);
-    hipError_t err = hipMemcpy(raw.data(), c.counters, kCounterBytes, hipMemcpyDeviceToHost);
+    hipError_t err = hipMemcpy(raw.data(), c.counters.ptr, kCounterBytes, hipMemcpyDeviceToHost);
     if (err != hipSuccess) return fail(ST_ERR_HIP, std::string("hipMemcpy(counters): ") + hipGetErrorString(err));
     for (int s = 0; s < KS_COUNT; s++) {
         unsigned long long rays = 0, bytes = 0;
@@ -351,7 +402,7 @@ inline int read_counters(const CameraState& c, unsigned long long* host /* 2*KS_
 }
 
 
-struct ProfileRecord { int slot; hipEvent_t start, stop; double bytes; uint32_t launches; bool owns_start; };
+struct ProfileRecord { int slot; hipEvent_t start, stop; double bytes; uint32_t launches; bool owns_start; };   // borrowed from Engine::profile_events
 
 StTuning default_tuning();  // st_engine.cpp
 struct DistState;           // st_dist.cpp: rank / world, transport, per-camera partition
@@ -405,15 +456,16 @@ struct Engine {
     std::vector<float> skin_bind_host; std::vector<StSkinVertex> skin_corner_host; SlotRanges skin_free;
     DeviceArray d_skin_bind, d_skin_corners, d_posed, d_skin_jobs, d_skin_starts, d_palettes;
     SlotRanges posed_free; size_t posed_size = 0;   // triangles of the posed store handed out (its allocation holds at least that many)
-    hipStream_t skin_stream = nullptr; hipEvent_t ev_skinned = nullptr, ev_posed_read = nullptr; bool posed_read_pending = false;
+    Stream skin_stream; Event ev_skinned;
+    Fence posed_read;   // behind the bakes that read the posed regions (bake_on_device), on whichever streams: the next skin launch overwrites them
     uint64_t skin_launches = 0, skinned_triangles = 0, posed_readbacks = 0;
     // Deformation motion (include/strolle_hip.h "skinned meshes"; st_device.h deform_prev_point): with the switch on, primary visibility and the AOV launch
     // read the previous region of every instance the last tick re-skinned, through the free word of the scene copy's instance table (fill_instance_table).
-    // deform_live: instances the last tick left a previous pose. Frames read the posed store then: ev_deform_read is recorded behind every reader
+    // deform_live: instances the last tick left a previous pose. Frames read the posed store then: deform_read is recorded behind every reader
     // that can reach deform_prev_point (reader_end: frames and the MOTION AOV, not the scene queries) — behind a wait for its own earlier recording, so that one event covers readers on several streams — and the next skin launch,
     // which overwrites previous regions, waits for it on the skin stream. No host wait (DESIGN.md "Deformation motion").
     bool deform_on = false; uint64_t deform_live = 0;
-    hipEvent_t ev_deform_read = nullptr; bool deform_read_pending = false;
+    Fence deform_read;
     // what primary visibility and the MOTION AOV get as kernel arguments: null unless the last tick left some instance a previous pose (that tick wrote the
     // live copy's table: a re-skin is a scene change). deform_live is that tick's state — the switch itself is read by st_tick alone, so it takes effect at the next tick
     const uint4* deform_table() const { return deform_live ? static_cast<const uint4*>(sets[live].instance_table.ptr) : nullptr; }
@@ -490,8 +542,7 @@ struct Engine {
     struct DeviceImage { const void* pixels; size_t pitch; bool dynamic, pending; };
     std::map<uint64_t, DeviceImage> device_images;
     StagingRing staging;
-    // a tick queued copies without joining the stream: ev_tick marks their end, the next frame's streams wait for it
-    bool tick_work_in_flight = false; hipEvent_t ev_tick = nullptr;
+    Fence tick_done;   // a tick queued copies without joining the stream: this marks their end, the next frame's streams wait for it
 
     // lights (lights.rs): slot 0 is the sun
     std::vector<GpuLight> light_buffer; std::map<int64_t, uint32_t> light_slot;
@@ -508,14 +559,14 @@ struct Engine {
     // environment lighting (include/strolle_hip.h "environment lighting"; st_env.cpp). An edit waits in env_edit / env_desc_next for the next
     // tick (apply_environment on the host, upload_environment on the device). Every map the device holds is a fresh allocation: frames
     // enqueued before a replacement keep reading theirs, which is released once its fence says they are done (env_retired).
-    struct EnvMap { DeviceArray texels, table; uint32_t w = 0, h = 0, gw = 0, gh = 0; CopyFence fence; };
+    struct EnvMap { DeviceArray texels, table; uint32_t w = 0, h = 0, gw = 0, gh = 0; Fence fence; };
     enum EnvEditKind { ENV_EDIT_NONE, ENV_EDIT_HOST, ENV_EDIT_DEVICE, ENV_EDIT_CLEAR };
     struct EnvEdit { EnvEditKind kind = ENV_EDIT_NONE; std::vector<float4> texels; const void* src = nullptr; size_t pitch = 0; uint32_t w = 0, h = 0, channels = 0; };
     EnvEdit env_edit;
     StEnvironmentDesc env_desc{}, env_desc_next{};
     bool env_set = false, env_sun_off = false;   // a map is live (host-only engines too: light 0 follows it); light 0 is dark because of it
     std::unique_ptr<EnvMap> env_live; std::vector<std::unique_ptr<EnvMap>> env_retired;
-    DeviceArray d_env_grid; uint32_t* d_env_bad = nullptr; uint64_t env_sanitized = 0;
+    DeviceArray d_env_grid, d_env_bad /* one u32: the texels the device upload sanitized */; uint64_t env_sanitized = 0;
     std::vector<float> env_grid_host; std::vector<EnvCell> env_table_host;
 
     DeviceArray d_byte_luts, d_atlas, d_blue_noise, d_transmittance, d_scattering, d_sky;
@@ -543,15 +594,16 @@ struct Engine {
         DeviceArray bake_jobs, bake_starts;
         // per instance slot (tri_attr[4 t + 3].w): {StHandle lo, hi, first triangle slot, 0} — the scene queries' instance and mesh triangle (st_query.cpp)
         DeviceArray instance_table;
-        CopyFence fence;
+        Fence fence;   // reads of this copy enqueued since it was written end here (reader_end; pick_copy waits before it writes the copy again)
         bool valid = false;
     };
     SceneSet sets[2]; int live = 0;
     // the light table alternates the same way, on its own schedule (a light that moves every frame does not resend the scene)
-    struct LightSet { DeviceArray buf; CopyFence fence; };
+    struct LightSet { DeviceArray buf; Fence fence; };
     LightSet light_sets[2]; int live_lights = 0; bool lights_uploaded = false, lights_alternating = false;
     bool alternating = false, mixed_render_streams = false;
-    hipStream_t copy_stream = nullptr, last_render_stream = nullptr; bool rendered_before = false; hipEvent_t ev_copy = nullptr; bool copy_in_flight = false;
+    Stream copy_stream; hipStream_t last_render_stream = nullptr; bool rendered_before = false;
+    Fence copy_done;   // behind a tick's copies on copy_stream, like tick_done
     struct CopyTarget { int index; hipStream_t up; bool* pageable; bool other; };   // the writer's side: st_tick.cpp pick_copy
     int reader_begin(hipStream_t stream, bool reader);   // the readers' side: st_render.cpp
     int reader_end(hipStream_t stream, bool lights, bool deform = false);   // deform: the reader can reach deform_prev_point (frames, the MOTION AOV)
@@ -579,7 +631,8 @@ struct Engine {
     bool count_bytes = false;     // st_profile_enable bit 1: traversal-byte counters
     bool profile_kernel_events = false;  // st_profile_enable bit 3: every launch carries its own start / stop events (hipExtLaunchKernelGGL): no event packets between kernels
     bool profile_group_atrous = false;  // st_profile_enable bit 2: the a-trous chain's back-to-back launches share ONE event pair (an event between two kernels costs the second one 3-15 us)
-    std::vector<ProfileRecord> profile_records; std::vector<hipEvent_t> event_pool;
+    std::vector<ProfileRecord> profile_records;
+    std::vector<Event> profile_events; std::vector<hipEvent_t> event_pool;   // every event take_event() ever made; those of them that are free
     StKernelProfile profile_totals[KS_COUNT];
 
     Engine();
@@ -601,7 +654,7 @@ struct Engine {
     int dist_gather_ms(uint64_t handle, float* ms);
     void reset_profile_totals();
     ~Engine();
-    static void release_camera(CameraState& c);
+    static void release_camera(CameraState& c);   // the per-size resources back to none: allocate_camera makes them again
     int present_copy(CameraState& c, const void* src, void* dst, size_t bytes, hipStream_t stream);
     int present_ready(CameraState& c, const void* dst, int wait, int* ready);
 
@@ -650,7 +703,7 @@ struct Engine {
     // (24 -> 32 -> 48 -> 56 entries: dynamic LDS, fewer waves per SIMD), the packet's (64 entries, one VGPR) hands primary visibility back to the
     // per-lane walk; either way that tick returns ST_ERR_BVH_TOO_DEEP once (StTuning::allow_deep_bvh: a line on stderr) — the frames rendered in
     // between may have missed geometry behind the dropped subtrees.
-    volatile uint32_t* walk_flags_host = nullptr; uint32_t* walk_flags_dev = nullptr;
+    PinnedBuffer walk_flags_mem; volatile uint32_t* walk_flags_host = nullptr; uint32_t* walk_flags_dev = nullptr;   // (the two views of walk_flags_mem)
     uint32_t wide_stack_rearmed = 0u;   // 0: StTuning::wide_stack_entries (0 = 24) as set; otherwise the entries an overflow re-armed the wide walks with
     bool packets_overflowed = false;    // the packet walk overflowed once on this engine: primary rays keep the per-lane walk
     uint64_t walk_overflows = 0; bool walk_overflow_unreported = false;
@@ -675,10 +728,10 @@ struct Engine {
     void apply_environment();
     int upload_environment(TickIo& io);
     int retire_environment(std::unique_ptr<EnvMap> m);
-    void release_environments(bool all);
+    void release_environments();
     void environment_args(KArgs& a) const;
     int environment_debug(uint32_t what, const float* in, uint32_t n, float* out, hipStream_t stream);
-    int pick_copy(TickIo& io, int live_index, CopyFence& live_fence, CopyFence& other_fence, bool written_before, bool& alternating_now, CopyTarget& c);
+    int pick_copy(TickIo& io, int live_index, Fence& live_fence, Fence& other_fence, bool written_before, bool& alternating_now, CopyTarget& c);
     int upload_scene(TreePlan plan, TickIo& io);
     int upload_images(TickIo& io);
     int upload_lights(TickIo& io);
@@ -701,7 +754,7 @@ struct Engine {
     // a composition into a buffer whose present copy has not finished waits for that copy (callers that alternate two
     // buffers never meet this)
     static void present_guard(CameraState& c, const void* out, hipStream_t s) {
-        for (auto& p : c.present) if (p.pending && p.src == out) (void)hipStreamWaitEvent(s, p.ev_done, 0);
+        for (auto& p : c.present) if (p.pending && p.src == out) (void)p.ev_done.wait(s);
     }
 
     int render(CameraState& c, void* out, hipStream_t stream);
@@ -711,7 +764,6 @@ struct Engine {
     int display_finalize(CameraState& c, hipStream_t stream);                              // behind a metered frame
     int display_exposure(CameraState& c, float* scale, float* metered_ev, float* adapted_ev);
     int display_histogram(CameraState& c, uint32_t* bins);
-    static void release_display(CameraState& c);
     // ---- output post-processing (st_post.cpp)
     struct PostPlan { bool fxaa = false, resample = false; PostArgs fx{}, rs{}; double fxaa_bytes = 0.0, resample_bytes = 0.0; };
     static PostPlan post_plan(const StPostDesc& d, bool fxaa, const void* src, uint32_t w, uint32_t h, void* mid, void* dst, uint32_t format);
@@ -719,9 +771,7 @@ struct Engine {
     int post_planes(CameraState& c, bool second, hipStream_t stream);   // the camera's planes at its render size (allocates only when that changed), ordered behind their last readers
     int post_done(CameraState& c, hipStream_t stream);                  // behind a frame's post launches
     int post_process(const StPostDesc* desc, const void* src, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
-    static void release_post(CameraState& c);
-    void* post_scratch = nullptr; size_t post_scratch_pixels = 0;   // st_post_process's intermediate plane (FXAA -> resampler)
-    hipEvent_t ev_post_scratch = nullptr; hipStream_t post_scratch_stream = nullptr; bool post_scratch_pending = false;
+    DeviceArray post_scratch; Fence post_scratch_read;   // st_post_process's intermediate plane (FXAA -> resampler) and the end of its last use
     int scene_args(KArgs& a, bool heatmap) const;   // the scene half of KArgs (st_render.cpp): render() and the scene queries
 
     // ---- scene queries (st_query.cpp; include/strolle_hip.h "scene queries")
@@ -734,7 +784,7 @@ struct Engine {
     int pick(const CameraState& c, const uint32_t* pixels, uint32_t count, void* hits, hipStream_t stream);
     int trace_rays_host(const void* rays, uint32_t count, void* hits);
     int render_aovs(const CameraState& c, const StAovTargets& t, hipStream_t stream);   // per-pixel AOVs (st_aov.cpp)
-    hipStream_t query_stream = nullptr; DeviceArray d_query_rays, d_query_hits; void* query_pinned = nullptr; size_t query_pinned_bytes = 0;
+    Stream query_stream; DeviceArray d_query_rays, d_query_hits; PinnedBuffer query_pinned;
 };
 
 }  // namespace st

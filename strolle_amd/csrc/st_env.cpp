@@ -50,7 +50,7 @@ void Engine::apply_environment() {
 
 // device part: the new map in an allocation of its own, on the tick's stream; the old one is retired behind the frames that read it
 int Engine::upload_environment(TickIo& io) {
-    release_environments(false);
+    release_environments();
     const EnvEditKind kind = env_edit.kind;
     if (kind == ENV_EDIT_NONE) return ST_OK;
     std::unique_ptr<EnvMap> m;
@@ -63,8 +63,8 @@ int Engine::upload_environment(TickIo& io) {
         if (kind == ENV_EDIT_HOST) {
             if (int rc = m->texels.upload_range(env_edit.texels.data(), 0, bytes, io.stream, staging, &io.pageable)) return rc;
         } else {
-            if (!d_env_bad) { ST_HIP(hipMalloc(reinterpret_cast<void**>(&d_env_bad), sizeof(uint32_t))); ST_HIP(hipMemset(d_env_bad, 0, sizeof(uint32_t))); }
-            L.launch_env_upload(env_edit.src, env_edit.pitch, w, h, env_edit.channels, static_cast<float4*>(m->texels.ptr), d_env_bad, io.stream);
+            if (!d_env_bad.ptr) { if (int rc = d_env_bad.reserve(sizeof(uint32_t), sizeof(uint32_t))) return rc; ST_HIP(hipMemset(d_env_bad.ptr, 0, sizeof(uint32_t))); }
+            L.launch_env_upload(env_edit.src, env_edit.pitch, w, h, env_edit.channels, static_cast<float4*>(m->texels.ptr), d_env_bad.as<uint32_t>(), io.stream);
         }
         if (int rc = d_env_grid.reserve(cells * sizeof(float), cells * sizeof(float))) return rc;
         L.launch_env_grid(static_cast<const float4*>(m->texels.ptr), w, h, m->gw, m->gh, static_cast<float*>(d_env_grid.ptr), io.stream);
@@ -73,8 +73,8 @@ int Engine::upload_environment(TickIo& io) {
         ST_HIP(hipMemcpyAsync(env_grid_host.data(), d_env_grid.ptr, cells * sizeof(float), hipMemcpyDeviceToHost, io.stream));
         uint32_t bad = 0;
         if (kind == ENV_EDIT_DEVICE) {
-            ST_HIP(hipMemcpyAsync(&bad, d_env_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, io.stream));
-            ST_HIP(hipMemsetAsync(d_env_bad, 0, sizeof(uint32_t), io.stream));
+            ST_HIP(hipMemcpyAsync(&bad, d_env_bad.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, io.stream));
+            ST_HIP(hipMemsetAsync(d_env_bad.ptr, 0, sizeof(uint32_t), io.stream));
         }
         ST_HIP(hipStreamSynchronize(io.stream));   // maps change rarely: the table is built on the host from the device's grid
         env_sanitized += bad;
@@ -89,23 +89,20 @@ int Engine::upload_environment(TickIo& io) {
     return ST_OK;
 }
 
+// (the map goes when `m` does: at once, unless frames still read it)
 int Engine::retire_environment(std::unique_ptr<EnvMap> m) {
-    if (m->fence.busy) {
+    if (m->fence.pending) {
         if (!mixed_render_streams) { env_retired.push_back(std::move(m)); return ST_OK; }
         ST_HIP(hipDeviceSynchronize());   // cameras render on several streams: no single event ends their reads
     }
-    m->texels.release(); m->table.release(); m->fence.release();
     return ST_OK;
 }
 
-// retired maps whose last reader has finished (all: every one; the caller has synchronised the device)
-void Engine::release_environments(bool all) {
+// retired maps whose last reader has finished (st_tick: the device is current)
+void Engine::release_environments() {
     for (size_t i = 0; i < env_retired.size();) {
-        EnvMap& m = *env_retired[i];
-        if (all || !m.fence.free_ev || hipEventQuery(m.fence.free_ev) == hipSuccess) {
-            m.texels.release(); m.table.release(); m.fence.release();
-            env_retired.erase(env_retired.begin() + (long)i);
-        } else i++;
+        if (env_retired[i]->fence.poll()) env_retired.erase(env_retired.begin() + (long)i);
+        else i++;
     }
     (void)hipGetLastError();   // hipErrorNotReady is not an error
 }
@@ -130,7 +127,7 @@ int Engine::environment_debug(uint32_t what, const float* in, uint32_t n, float*
     environment_args(a);
     L.launch_env_debug(a, what, in, n, out, stream);
     ST_HIP(hipGetLastError());
-    return env_live->fence.mark_read(stream);
+    return env_live->fence.record(stream);
 }
 
 }  // namespace st

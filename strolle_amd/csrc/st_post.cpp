@@ -55,23 +55,20 @@ Engine::PostPlan Engine::post_plan(const StPostDesc& d, bool fxaa, const void* s
 }
 
 int Engine::post_planes(CameraState& c, bool second, hipStream_t stream) {
-    const size_t n = (size_t)c.desc.width * c.desc.height;
+    const size_t bytes = (size_t)c.desc.width * c.desc.height * sizeof(float4);
     for (int i = 0; i < (second ? 2 : 1); i++) {
-        if (c.post_plane[i] && c.post_plane_pixels[i] == n) continue;
-        if (c.post_plane[i]) { ST_HIP(hipDeviceSynchronize()); (void)hipFree(c.post_plane[i]); c.post_plane[i] = nullptr; c.post_plane_pixels[i] = 0; }   // frames in flight may still read it
-        if (hipMalloc(&c.post_plane[i], n * sizeof(float4)) != hipSuccess) { (void)hipGetLastError(); c.post_plane[i] = nullptr; return fail(ST_ERR_HIP, "hipMalloc(post-processing plane) failed"); }
-        c.post_plane_pixels[i] = n;
+        DeviceArray& p = c.post_plane[i];
+        if (p.capacity == bytes) continue;
+        if (p.ptr) { ST_HIP(hipDeviceSynchronize()); p.release(); }   // frames in flight may still read it
+        if (int rc = p.reserve(bytes, bytes)) return rc;
     }
     // the previous frame's post launches ran on another stream: this frame's composing launch overwrites the plane they read
-    if (c.post_pending && c.post_stream != stream) ST_HIP(hipStreamWaitEvent(stream, c.ev_post, 0));
-    return ST_OK;
+    // (on the same stream it follows them anyway: no event between the two frames' kernels)
+    return c.post_read.wait(stream, Fence::OtherStreams, Fence::Keep);
 }
 
 int Engine::post_done(CameraState& c, hipStream_t stream) {
-    if (!c.ev_post) ST_HIP(hipEventCreateWithFlags(&c.ev_post, hipEventDisableTiming));
-    ST_HIP(hipEventRecord(c.ev_post, stream));
-    c.post_stream = stream; c.post_pending = true;
-    return ST_OK;
+    return c.post_read.record(stream);
 }
 
 int Engine::post_process(const StPostDesc* desc, const void* src, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream) {
@@ -85,31 +82,21 @@ int Engine::post_process(const StPostDesc* desc, const void* src, uint32_t w, ui
     const bool resizes = desc->output_width != 0u && (desc->output_width != w || desc->output_height != h);
     void* mid = nullptr;
     if (fxaa && resizes) {   // the engine's intermediate plane: grown only when a call needs a larger one; calls on different streams take turns
-        const size_t n = (size_t)w * h;
-        if (post_scratch_pixels < n) {
-            ST_HIP(hipDeviceSynchronize());
-            if (post_scratch) (void)hipFree(post_scratch);
-            post_scratch = nullptr; post_scratch_pixels = 0; post_scratch_pending = false;
-            if (hipMalloc(&post_scratch, n * sizeof(float4)) != hipSuccess) { (void)hipGetLastError(); post_scratch = nullptr; return fail(ST_ERR_HIP, "hipMalloc(post-processing plane) failed"); }
-            post_scratch_pixels = n;
+        const size_t bytes = (size_t)w * h * sizeof(float4);
+        if (post_scratch.capacity < bytes) {
+            ST_HIP(hipDeviceSynchronize());   // earlier calls may still use the plane that goes
+            post_scratch_read.settled();
+            if (int rc = post_scratch.reserve(bytes, bytes)) return rc;
         }
-        if (!ev_post_scratch) ST_HIP(hipEventCreateWithFlags(&ev_post_scratch, hipEventDisableTiming));
-        if (post_scratch_pending && post_scratch_stream != stream) ST_HIP(hipStreamWaitEvent(stream, ev_post_scratch, 0));
-        mid = post_scratch;
+        if (int rc = post_scratch_read.wait(stream, Fence::OtherStreams, Fence::Keep)) return rc;   // (the same stream takes its turn by stream order)
+        mid = post_scratch.ptr;
     }
     const PostPlan plan = post_plan(*desc, fxaa, src, w, h, mid, dst, (uint32_t)format);
     if (plan.fxaa) L.launch_post_fxaa(plan.fx, stream);
     if (plan.resample) L.launch_post_resample(plan.rs, stream);
-    if (mid) { ST_HIP(hipEventRecord(ev_post_scratch, stream)); post_scratch_stream = stream; post_scratch_pending = true; }
+    if (mid) if (int rc = post_scratch_read.record(stream)) return rc;
     ST_HIP(hipGetLastError());
     return ST_OK;
-}
-
-// with the device idle (st_camera_delete, ~Engine)
-void Engine::release_post(CameraState& c) {
-    for (int i = 0; i < 2; i++) { if (c.post_plane[i]) (void)hipFree(c.post_plane[i]); c.post_plane[i] = nullptr; c.post_plane_pixels[i] = 0; }
-    if (c.ev_post) (void)hipEventDestroy(c.ev_post);
-    c.ev_post = nullptr; c.post_stream = nullptr; c.post_pending = false;
 }
 
 }  // namespace st

@@ -6,7 +6,8 @@ namespace st {
 // ---- profiling
 hipEvent_t Engine::take_event() {
     if (!event_pool.empty()) { hipEvent_t e = event_pool.back(); event_pool.pop_back(); return e; }
-    hipEvent_t e; (void)hipEventCreate(&e); return e;
+    profile_events.emplace_back(hipEventDefault);   // timed
+    return profile_events.back().get();
 }
 
 void Engine::profile_begin(int slot, hipStream_t s, double bytes) {

@@ -68,22 +68,17 @@ int Engine::trace_rays_host(const void* rays, uint32_t count, void* hits) {
     if (!has_device) return fail(ST_ERR_NO_DEVICE, "scene query on a host-only engine");
     if (!scene_uploaded) return fail(ST_ERR_INVALID_ARGUMENT, "st_tick must precede a scene query");
     ST_HIP(hipSetDevice(device));
-    if (!query_stream) ST_HIP(hipStreamCreateWithFlags(&query_stream, hipStreamNonBlocking));
+    if (!query_stream) ST_HIP(hipStreamCreateWithFlags(&query_stream.h, hipStreamNonBlocking));
     const size_t ray_bytes = (size_t)count * sizeof(StRay), hit_bytes = (size_t)count * sizeof(StRayHit);
     if (int rc = d_query_rays.reserve(ray_bytes, ray_bytes)) return rc;
     if (int rc = d_query_hits.reserve(hit_bytes, hit_bytes)) return rc;
-    if (query_pinned_bytes < hit_bytes) {   // one page-locked buffer serves both directions (the hits are the larger)
-        if (query_pinned) ST_HIP(hipHostFree(query_pinned));
-        query_pinned = nullptr; query_pinned_bytes = 0;
-        ST_HIP(hipHostMalloc(&query_pinned, hit_bytes, hipHostMallocDefault));
-        query_pinned_bytes = hit_bytes;
-    }
-    memcpy(query_pinned, rays, ray_bytes);
-    ST_HIP(hipMemcpyAsync(d_query_rays.ptr, query_pinned, ray_bytes, hipMemcpyHostToDevice, query_stream));
+    if (int rc = query_pinned.reserve(hit_bytes)) return rc;   // one page-locked buffer serves both directions (the hits are the larger)
+    memcpy(query_pinned.ptr, rays, ray_bytes);
+    ST_HIP(hipMemcpyAsync(d_query_rays.ptr, query_pinned.ptr, ray_bytes, hipMemcpyHostToDevice, query_stream));
     if (int rc = trace_rays(d_query_rays.ptr, count, d_query_hits.ptr, 0u, query_stream, false)) { (void)hipStreamSynchronize(query_stream); return rc; }
-    ST_HIP(hipMemcpyAsync(query_pinned, d_query_hits.ptr, hit_bytes, hipMemcpyDeviceToHost, query_stream));
+    ST_HIP(hipMemcpyAsync(query_pinned.ptr, d_query_hits.ptr, hit_bytes, hipMemcpyDeviceToHost, query_stream));
     ST_HIP(hipStreamSynchronize(query_stream));
-    memcpy(hits, query_pinned, hit_bytes);
+    memcpy(hits, query_pinned.ptr, hit_bytes);
     return ST_OK;
 }
 

@@ -4,34 +4,29 @@
 namespace st {
 
 void Engine::release_camera(CameraState& c) {
-    if (c.slab) (void)hipFree(c.slab);
-    if (c.counters) (void)hipFree(c.counters);
-    if (c.tile_mask) (void)hipFree(c.tile_mask);
-    c.tile_mask = nullptr;
-    c.slab = nullptr; c.counters = nullptr;
-    if (c.side_stream) (void)hipStreamDestroy(c.side_stream);
-    for (hipEvent_t* e : {&c.ev_di_head, &c.ev_gi_done, &c.ev_prim_ok, &c.ev_frame_done, &c.ev_setup}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
-    c.side_stream = nullptr; c.have_prev_frame_events = false;
-    if (c.present_stream) { (void)hipStreamSynchronize(c.present_stream); (void)hipStreamDestroy(c.present_stream); c.present_stream = nullptr; }
-    for (auto& p : c.present) { for (hipEvent_t* e : {&p.ev_src, &p.ev_done}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; } p = CameraState::PresentSlot(); }
+    c.slab.release(); c.counters.release(); c.tile_mask.release();
+    c.side_stream.reset();
+    for (Event* e : {&c.ev_di_head, &c.ev_gi_done, &c.ev_prim_ok, &c.ev_frame_done, &c.ev_setup}) e->reset();
+    c.have_prev_frame_events = false;
+    c.join_present(); c.present_stream.reset();
+    for (auto& p : c.present) p = CameraState::PresentSlot();
 }
 
 // st_camera_present_copy: `src_device` (what st_render_camera composed into on `stream`) -> `dst_host`, asynchronously
 int Engine::present_copy(CameraState& c, const void* src, void* dst, size_t bytes, hipStream_t stream) {
     if (!has_device) return fail(ST_ERR_NO_DEVICE, "present copy on a host-only engine");
     ST_HIP(hipSetDevice(device));
-    if (!c.present_stream) ST_HIP(hipStreamCreateWithFlags(&c.present_stream, hipStreamNonBlocking));
+    if (!c.present_stream) ST_HIP(hipStreamCreateWithFlags(&c.present_stream.h, hipStreamNonBlocking));
     // the slot that already serves this destination, else the older one
     CameraState::PresentSlot* slot = nullptr;
     for (auto& p : c.present) if (p.dst == dst) slot = &p;
     if (!slot) { slot = &c.present[c.present_next & 1u]; c.present_next++; }
-    if (slot->pending) ST_HIP(hipEventSynchronize(slot->ev_done));  // only when the caller runs more than two frames ahead
-    if (!slot->ev_src) { ST_HIP(hipEventCreateWithFlags(&slot->ev_src, hipEventDisableTiming)); ST_HIP(hipEventCreateWithFlags(&slot->ev_done, hipEventDisableTiming)); }
+    if (slot->pending) ST_HIP(hipEventSynchronize(slot->ev_done.h));  // only when the caller runs more than two frames ahead
     slot->src = src; slot->dst = dst;
-    ST_HIP(hipEventRecord(slot->ev_src, stream));                    // the frame is composed
-    ST_HIP(hipStreamWaitEvent(c.present_stream, slot->ev_src, 0));
+    if (int rc = slot->ev_src.record(stream)) return rc;             // the frame is composed
+    if (int rc = slot->ev_src.wait(c.present_stream)) return rc;
     ST_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c.present_stream));
-    ST_HIP(hipEventRecord(slot->ev_done, c.present_stream));
+    if (int rc = slot->ev_done.record(c.present_stream)) return rc;
     slot->pending = true;
     return ST_OK;
 }
@@ -41,9 +36,9 @@ int Engine::present_ready(CameraState& c, const void* dst, int wait, int* ready)
     *ready = 1;
     for (auto& p : c.present) {
         if (p.dst != dst || !p.pending) continue;
-        if (wait) { ST_HIP(hipEventSynchronize(p.ev_done)); p.pending = false; }
+        if (wait) { ST_HIP(hipEventSynchronize(p.ev_done.h)); p.pending = false; }
         else {
-            const hipError_t q = hipEventQuery(p.ev_done);
+            const hipError_t q = hipEventQuery(p.ev_done.h);
             if (q == hipSuccess) p.pending = false;
             else if (q == hipErrorNotReady) { (void)hipGetLastError(); *ready = 0; }
             else return fail(ST_ERR_HIP, std::string("hipEventQuery: ") + hipGetErrorString(q));
@@ -74,23 +69,17 @@ int Engine::allocate_camera(CameraState& c) {
         c.plane_bytes[i] = i == ST_BUF_DBG_USED_MEMORY ? n * 4 : n * 16 * plane_texels_per_pixel(i);
         total += (c.plane_bytes[i] + 255) & ~size_t(255);
     }
-    ST_HIP(hipMalloc(&c.slab, total));
-    ST_HIP(hipMemset(c.slab, 0, total));  // wgpu zero-initialises resources; stale-data paths depend on it
-    c.slab_bytes = total;
+    if (int rc = c.slab.reserve(total, total)) return rc;
+    ST_HIP(hipMemset(c.slab.ptr, 0, total));  // wgpu zero-initialises resources; stale-data paths depend on it
     size_t off = 0;
-    for (int i = 0; i < ST_BUF_COUNT + kInternalPlanes; i++) { c.plane[i] = reinterpret_cast<float4*>(static_cast<char*>(c.slab) + off); off += (c.plane_bytes[i] + 255) & ~size_t(255); }
+    for (int i = 0; i < ST_BUF_COUNT + kInternalPlanes; i++) { c.plane[i] = reinterpret_cast<float4*>(c.slab.as<char>() + off); off += (c.plane_bytes[i] + 255) & ~size_t(255); }
     c.gi_aliased = false;
-    if (hipMalloc(reinterpret_cast<void**>(&c.counters), kCounterBytes) != hipSuccess) {
-        (void)hipGetLastError(); c.counters = nullptr;
-        release_camera(c);  // do not leak the slab
-        return fail(ST_ERR_HIP, "hipMalloc(camera counters) failed");
-    }
-    ST_HIP(hipMemset(c.counters, 0, kCounterBytes));
+    if (int rc = c.counters.reserve(kCounterBytes, kCounterBytes)) return rc;
+    ST_HIP(hipMemset(c.counters.ptr, 0, kCounterBytes));
     {
-        const size_t tiles = (size_t)((c.desc.width + 7u) / 8u) * ((c.desc.height + 7u) / 8u);
-        if (hipMalloc(reinterpret_cast<void**>(&c.tile_mask), 2 * tiles * sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); c.tile_mask = nullptr; release_camera(c); return fail(ST_ERR_HIP, "hipMalloc(camera tile mask) failed"); }
-        ST_HIP(hipMemset(c.tile_mask, 0, 2 * tiles * sizeof(unsigned long long)));  // [0, tiles): variance's, [tiles, 2 tiles): the GI preview's
-        c.tile_mask_tiles = tiles;
+        const size_t tiles = (size_t)((c.desc.width + 7u) / 8u) * ((c.desc.height + 7u) / 8u), bytes = 2 * tiles * sizeof(unsigned long long);
+        if (int rc = c.tile_mask.reserve(bytes, bytes)) return rc;
+        ST_HIP(hipMemset(c.tile_mask.ptr, 0, bytes));  // [0, tiles): variance's, [tiles, 2 tiles): the GI preview's
     }
     memset(c.profiled_traversal_bytes, 0, sizeof(c.profiled_traversal_bytes));
     ST_HIP(hipDeviceSynchronize());  // the clears run on the null stream; renders may use any stream
@@ -145,8 +134,8 @@ int Engine::scene_args(KArgs& a, bool heatmap) const {
 
 // The reader side of the double-buffered scene and light copies (st_tick.cpp pick_copy is the writer's), for render() and the scene queries.
 int Engine::reader_begin(hipStream_t stream, bool reader) {
-    if (tick_work_in_flight) ST_HIP(hipStreamWaitEvent(stream, ev_tick, 0));  // a no-op when st_tick ran on this stream
-    if (copy_in_flight) ST_HIP(hipStreamWaitEvent(stream, ev_copy, 0));       // likewise (st_tick already queued this wait on its own stream)
+    if (int rc = tick_done.wait(stream, Fence::AnyStream, Fence::Keep)) return rc;  // a no-op when st_tick ran on this stream. Kept: every stream of every frame waits, until st_tick polls it away
+    if (int rc = copy_done.wait(stream, Fence::AnyStream, Fence::Keep)) return rc;  // likewise (st_tick already queued this wait on its own stream)
     if (reader) {
         if (rendered_before && last_render_stream != stream) mixed_render_streams = true;  // the null stream is a stream too
         last_render_stream = stream; rendered_before = true;
@@ -154,14 +143,12 @@ int Engine::reader_begin(hipStream_t stream, bool reader) {
     return ST_OK;
 }
 int Engine::reader_end(hipStream_t stream, bool lights, bool deform) {
-    if (alternating) if (int rc = sets[live].fence.mark_read(stream)) return rc;
-    if (lights && lights_alternating) if (int rc = light_sets[live_lights].fence.mark_read(stream)) return rc;
-    if (lights && env_live) if (int rc = env_live->fence.mark_read(stream)) return rc;   // (frames: the map is freed behind its last reader)
-    if (deform && deform_live) {   // this reader (a frame, a MOTION AOV) may read previous regions of the posed store: the next skin launch waits for it (st_engine.h ev_deform_read)
-        if (!ev_deform_read) ST_HIP(hipEventCreateWithFlags(&ev_deform_read, hipEventDisableTiming));
-        if (deform_read_pending) ST_HIP(hipStreamWaitEvent(stream, ev_deform_read, 0));
-        ST_HIP(hipEventRecord(ev_deform_read, stream)); deform_read_pending = true;
-    }
+    if (alternating) if (int rc = sets[live].fence.record(stream)) return rc;
+    if (lights && lights_alternating) if (int rc = light_sets[live_lights].fence.record(stream)) return rc;
+    if (lights && env_live) if (int rc = env_live->fence.record(stream)) return rc;   // (frames: the map is freed behind its last reader)
+    // this reader (a frame, a MOTION AOV) may read previous regions of the posed store: the next skin launch waits for it (st_engine.h deform_read).
+    // Chained: readers on several streams, one event
+    if (deform && deform_live) if (int rc = deform_read.record_chained(stream)) return rc;
     return ST_OK;
 }
 
@@ -177,7 +164,7 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
     // RGBA32F plane instead of `out`, and the post launches at the end of this function write `out` behind it on `stream`.
     const bool post_fxaa = out && c.post_fxaa(), post_resample = out && c.post_resizes(), post = post_fxaa || post_resample;
     if (post) if (int rc = post_planes(c, post_fxaa && post_resample, stream)) return rc;
-    void* const comp_out = post ? c.post_plane[0] : out;
+    void* const comp_out = post ? c.post_plane[0].ptr : out;
     const uint32_t comp_format = post ? (uint32_t)ST_FORMAT_RGBA32F : c.out_format;
     const bool alt = c.frame % 2u == 1u;
     c.last_lean = 0u; c.last_lean_composed = false;
@@ -232,7 +219,7 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
         if ((bits & pass_mask) != bits) { mask_split |= (bits & pass_mask) != 0; return; }
         if (launch_filter != ~0ull && !((launch_filter >> (launch_ordinal++ & 63u)) & 1ull)) return;  // measurement only: the frame's state is not meaningful afterwards
         const double bytes = post_bytes >= 0.0 ? post_bytes : slot_bytes(slot);
-        a.ray_counter = c.counters + kCounterWordsPerSlot * slot;
+        a.ray_counter = c.counters.as<unsigned long long>() + kCounterWordsPerSlot * slot;
         if (profiling && profile_kernel_events) {  // the dispatch's own timestamps (what rocprofv3's kernel trace reads)
             (void)profile_close();   // a scope the run-of-launches mode left open belongs to that mode
             g_launch_events.start = take_event(); g_launch_events.stop = take_event(); g_launch_events.consumed = false;
@@ -293,12 +280,12 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
         a.gi_skip_history_copy = swap_gi_history ? 1u : 0u;
         // estimate_variance's long-history branch rides in the fused reproject stages (st_passes.h denoise_reproject_finish);
         // the variance launch then serves the short-history pixels only, in place, and the strides-1+2 launch reads curr_colors
-        a.tile_mask = c.tile_mask;
+        a.tile_mask = c.tile_mask.as<unsigned long long>();
         // both GI preview passes + resolving in one launch for the pixels whose second pass draws no neighbour (k_gi.hip
         // k_gi_preview_both); the second-pass launch then serves the flagged rest
-        a.gi_late_mask = c.tile_mask ? c.tile_mask + c.tile_mask_tiles : nullptr; a.gi_preview_late = 0u;
+        a.gi_late_mask = a.tile_mask ? a.tile_mask + c.tile_mask_tiles() : nullptr; a.gi_preview_late = 0u;
         const bool gi_preview_both = tuning.preview_both && whole_graph && tuning.fuse && gi_runs && a.gi_late_mask;
-        a.variance_in_reproject = (tuning.variance_in_reproject && whole_graph && tuning.fuse && tuning.fuse_wavelet && denoise && needs_di && needs_gi && any_objects && c.tile_mask) ? 1u : 0u;
+        a.variance_in_reproject = (tuning.variance_in_reproject && whole_graph && tuning.fuse && tuning.fuse_wavelet && denoise && needs_di && needs_gi && any_objects && a.tile_mask) ? 1u : 0u;
         // di_spatial's scratch records (di_diff_samples / curr_colors / stash as the reference binds them) are dead stores
         // when the fused launch is followed by resolving, denoise-reproject and the a-trous chain of the same frame
         const bool even_tiles_x = (((a.width + 7u) / 8u) & 1u) == 0u;
@@ -461,38 +448,37 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
                 int least = 0, greatest = 0;
                 (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
                 const int priority = tuning.side_priority > 0 ? greatest : (tuning.side_priority < 0 ? least : 0);
-                ST_HIP(hipStreamCreateWithPriority(&c.side_stream, hipStreamNonBlocking, priority));
-                for (hipEvent_t* e : {&c.ev_di_head, &c.ev_gi_done, &c.ev_prim_ok, &c.ev_frame_done, &c.ev_setup}) ST_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+                ST_HIP(hipStreamCreateWithPriority(&c.side_stream.h, hipStreamNonBlocking, priority));
             }
             // LUT generation issued on `stream` in this call must precede the side stream's consumers. (Do NOT do this
             // unconditionally: an event recorded on `stream` here completes only after frame N's denoiser, which would
             // serialise prim(N+1) behind it. Uploads in st_tick are followed by a host-side stream sync.)
-            if (luts_generated_now) { ST_HIP(hipEventRecord(c.ev_setup, stream)); ST_HIP(hipStreamWaitEvent(c.side_stream, c.ev_setup, 0)); }
+            if (luts_generated_now) { if (int rc = c.ev_setup.record(stream)) return rc; if (int rc = c.ev_setup.wait(c.side_stream)) return rc; }
             // copies st_tick queued without joining the stream (staged uploads, dynamic images): they sit behind frame N on
             // the tick's stream, so a frame that follows a scene change gives up the prim(N+1) / denoiser(N) overlap
             if (int rc = reader_begin(c.side_stream, false)) return rc;  // the tick's uploads: independent of frame N, the overlap stays
-            if (c.have_prev_frame_events) ST_HIP(hipStreamWaitEvent(c.side_stream, c.ev_prim_ok, 0));
+            if (c.have_prev_frame_events) { if (int rc = c.ev_prim_ok.wait(c.side_stream)) return rc; }
             cur = c.side_stream;
             do_prim();
             if (!tuning.di_head_on_main) do_di_head();
-            ST_HIP(hipEventRecord(c.ev_di_head, c.side_stream));  // primary visibility (+ DI head) of this frame are through
+            if (int rc = c.ev_di_head.record(c.side_stream)) return rc;  // primary visibility (+ DI head) of this frame are through
             do_gi_head();
-            if (c.have_prev_frame_events) ST_HIP(hipStreamWaitEvent(c.side_stream, c.ev_frame_done, 0));
+            if (c.have_prev_frame_events) { if (int rc = c.ev_frame_done.wait(c.side_stream)) return rc; }
             do_gi_tail();
-            ST_HIP(hipEventRecord(c.ev_gi_done, c.side_stream));
+            if (int rc = c.ev_gi_done.record(c.side_stream)) return rc;
             cur = stream;
-            ST_HIP(hipStreamWaitEvent(stream, c.ev_di_head, 0));
+            if (int rc = c.ev_di_head.wait(stream)) return rc;
             if (tuning.di_head_on_main) do_di_head();
             do_di_tail();
             // stand-alone denoise reprojection kernels (unfused path) still read the reprojection map: prim(N+1) may
             // only start once they are through
             const bool reproject_later = denoise && !tuning.fuse;
-            if (!reproject_later) ST_HIP(hipEventRecord(c.ev_prim_ok, stream));
-            ST_HIP(hipStreamWaitEvent(stream, c.ev_gi_done, 0));
+            if (!reproject_later) { if (int rc = c.ev_prim_ok.record(stream)) return rc; }
+            if (int rc = c.ev_gi_done.wait(stream)) return rc;
             do_denoise();
-            if (reproject_later) ST_HIP(hipEventRecord(c.ev_prim_ok, stream));
+            if (reproject_later) { if (int rc = c.ev_prim_ok.record(stream)) return rc; }
             do_compose();
-            ST_HIP(hipEventRecord(c.ev_frame_done, stream));
+            if (int rc = c.ev_frame_done.record(stream)) return rc;
             c.have_prev_frame_events = true;
         } else {
             do_prim();
@@ -502,7 +488,7 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
             }
             do_denoise();
             do_compose();
-            if (c.side_stream) { ST_HIP(hipEventRecord(c.ev_prim_ok, stream)); ST_HIP(hipEventRecord(c.ev_frame_done, stream)); }
+            if (c.side_stream) { if (int rc = c.ev_prim_ok.record(stream)) return rc; if (int rc = c.ev_frame_done.record(stream)) return rc; }
         }
     }
     if (out && !composed) {
@@ -514,7 +500,7 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
     }
     if (post) {   // the composing launch ran on `stream`; one launch group (ST_PASS_POST) of at most two kernels
         cur = stream;
-        const PostPlan plan = post_plan(c.post, post_fxaa, c.post_plane[0], c.desc.width, c.desc.height, c.post_plane[1], out, c.out_format);
+        const PostPlan plan = post_plan(c.post, post_fxaa, c.post_plane[0].ptr, c.desc.width, c.desc.height, c.post_plane[1].ptr, out, c.out_format);
         if (plan.fxaa) { post_bytes = plan.fxaa_bytes; run(KS_POST_FXAA, ST_PASS_POST, [&] { L.launch_post_fxaa(plan.fx, cur); }); }
         if (plan.resample) { post_bytes = plan.resample_bytes; run(KS_POST_RESAMPLE, ST_PASS_POST, [&] { L.launch_post_resample(plan.rs, cur); }); }
         post_bytes = -1.0;

@@ -310,16 +310,14 @@ int Engine::bake_on_device(SceneSet& t, hipStream_t up, bool* pageable) {
     }
     if ((rc = t.bake_jobs.upload(jobs.data(), jobs.size() * sizeof(Job), up, staging, pageable))) return rc;
     if ((rc = t.bake_starts.upload(starts.data(), starts.size() * sizeof(uint32_t), up, staging, pageable))) return rc;
-    if (reads_posed) ST_HIP(hipStreamWaitEvent(up, ev_skinned, 0));   // the skin launch (skin stream) wrote the posed regions
+    if (reads_posed) if ((rc = ev_skinned.wait(up))) return rc;   // the skin launch (skin stream) wrote the posed regions
     // the EXACT build's kernel, whatever arithmetic the frames use: the baked arrays are the host's bits
     launchers_exact().launch_bvh_bake(t.bake_jobs.ptr, static_cast<const uint32_t*>(t.bake_starts.ptr), (uint32_t)jobs.size(), starts.back(), static_cast<const float*>(d_mesh_store.ptr),
                                       static_cast<const float*>(d_posed.ptr), static_cast<float4*>(t.tri_geo.ptr), static_cast<float4*>(t.tri_bounds.ptr), static_cast<float4*>(t.tri_attr.ptr),
                                       static_cast<float4*>(t.bvh.ptr), t.device_built ? nullptr : static_cast<const uint32_t*>(t.entry_of_tri.ptr), up);
-    if (reads_posed) {   // the next skin launch overwrites the regions after this bake — and after an earlier one still pending on another stream:
-        // the event is re-recorded here behind a wait for its previous recording, so that it covers both (the bake itself is not delayed)
-        if (posed_read_pending) ST_HIP(hipStreamWaitEvent(up, ev_posed_read, 0));
-        ST_HIP(hipEventRecord(ev_posed_read, up)); posed_read_pending = true;
-    }
+    // the next skin launch overwrites the regions after this bake — and after an earlier one still pending on another stream:
+    // the event is re-recorded here behind a wait for its previous recording, so that it covers both (the bake itself is not delayed)
+    if (reads_posed) if ((rc = posed_read.record_chained(up))) return rc;
     device_bakes++; device_baked_triangles += starts.back();
     return ST_OK;
 }

@@ -85,7 +85,7 @@ const std::vector<StMeshTriangle>* Engine::bake_source(const InstanceRec& inst, 
 }
 
 // Deformation motion: what the last tick left is forgotten before this one skins — an instance has a previous pose for the frames of the tick that
-// re-skinned it, no longer. With the switch off the second regions go back to the free list (frames still reading them: ev_deform_read).
+// re-skinned it, no longer. With the switch off the second regions go back to the free list (frames still reading them: deform_read).
 void Engine::deform_begin_tick() {
     deform_live = 0;
     for (auto& kv : poses) {
@@ -109,10 +109,7 @@ int Engine::skin_tick(hipStream_t stream) {
     bool any = false;
     for (const auto& kv : poses) any |= kv.second.reskin;
     if (!any) return ST_OK;
-    if (!skin_stream) {
-        ST_HIP(hipStreamCreateWithFlags(&skin_stream, hipStreamNonBlocking));
-        ST_HIP(hipEventCreateWithFlags(&ev_skinned, hipEventDisableTiming)); ST_HIP(hipEventCreateWithFlags(&ev_posed_read, hipEventDisableTiming));
-    }
+    if (!skin_stream) ST_HIP(hipStreamCreateWithFlags(&skin_stream.h, hipStreamNonBlocking));
     int rc;
     // the skins these poses need, into the skin store (once per skin: bind-pose triangles in the mesh store's layout, then the corners), each
     // into a range a dropped skin gave back or appended; a store that outgrows its device allocation is sent whole into a larger one
@@ -177,8 +174,8 @@ int Engine::skin_tick(hipStream_t stream) {
     const size_t posed_bytes = posed_size * 24u * sizeof(float);
     bool grown = false;
     if (posed_bytes > d_posed.capacity) {
-        if (posed_read_pending) { ST_HIP(hipEventSynchronize(ev_posed_read)); posed_read_pending = false; }   // (hipFree waits too; said here)
-        if (deform_read_pending) { ST_HIP(hipEventSynchronize(ev_deform_read)); deform_read_pending = false; }   // (likewise: frames reading previous regions)
+        if ((rc = posed_read.host_wait())) return rc;    // (hipFree waits too; said here)
+        if ((rc = deform_read.host_wait())) return rc;   // (likewise: frames reading previous regions)
         if ((rc = d_posed.reserve(posed_bytes, posed_bytes + posed_bytes / 2))) return rc;
         for (auto& kv : poses) kv.second.reskin = true;   // (the poses themselves are unchanged: host images stay current)
         grown = true;   // ... and so is every previous region this tick's frames will read, from the palette it was skinned with
@@ -212,14 +209,15 @@ int Engine::skin_tick(hipStream_t stream) {
     if ((rc = d_skin_jobs.upload(jobs.data(), jobs.size() * sizeof(SkinJob), skin_stream, staging, &pageable)) ||
         (rc = d_skin_starts.upload(starts.data(), starts.size() * sizeof(uint32_t), skin_stream, staging, &pageable)) ||
         (rc = d_palettes.upload(palettes.data(), palettes.size() * sizeof(float), skin_stream, staging, &pageable))) return rc;
-    if (posed_read_pending) { ST_HIP(hipStreamWaitEvent(skin_stream, ev_posed_read, 0)); posed_read_pending = false; }   // bakes of earlier ticks still reading the regions
-    if (deform_read_pending) { ST_HIP(hipStreamWaitEvent(skin_stream, ev_deform_read, 0)); deform_read_pending = false; }   // frames still reading previous regions (deformation motion)
+    // the one writer of the regions waits for their readers, wherever they ran (the skin stream runs nothing else), and the recordings are spent
+    if ((rc = posed_read.wait(skin_stream, Fence::AnyStream, Fence::Clear))) return rc;    // bakes of earlier ticks still reading the regions
+    if ((rc = deform_read.wait(skin_stream, Fence::AnyStream, Fence::Clear))) return rc;   // frames still reading previous regions (deformation motion)
     launch_skin(static_cast<const SkinJob*>(d_skin_jobs.ptr), static_cast<const uint32_t*>(d_skin_starts.ptr), (uint32_t)jobs.size(), starts.back(), static_cast<const float*>(d_skin_bind.ptr),
                 d_skin_corners.ptr, static_cast<const float*>(d_palettes.ptr), static_cast<float*>(d_posed.ptr), skin_stream);
     ST_HIP(hipGetLastError());
-    ST_HIP(hipEventRecord(ev_skinned, skin_stream));
+    if ((rc = ev_skinned.record(skin_stream))) return rc;
     // the caller's stream follows the skin: the staging slot's event (end_uploads) comes after these copies, and so does the next frame
-    ST_HIP(hipStreamWaitEvent(stream, ev_skinned, 0));
+    if ((rc = ev_skinned.wait(stream))) return rc;
     if (pageable) ST_HIP(hipStreamSynchronize(skin_stream));   // (staging full or disabled: the copies read the vectors above)
     skin_launches++; skinned_triangles += triangles;
     return ST_OK;

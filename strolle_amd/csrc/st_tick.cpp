@@ -161,8 +161,7 @@ int Engine::tick(hipStream_t stream) {
         if (walk_flags_host && (walk_flags_host[0] | walk_flags_host[1]) != 0u) note_walk_overflow();   // a wide walk of an earlier frame dropped a push
         // Uploads of an earlier tick that no render has waited for yet stay pending until their event has completed: a
         // tick that uploads nothing must not make a later render on another stream forget them.
-        if (tick_work_in_flight && hipEventQuery(ev_tick) == hipSuccess) tick_work_in_flight = false;
-        if (copy_in_flight && hipEventQuery(ev_copy) == hipSuccess) copy_in_flight = false;
+        (void)tick_done.poll(); (void)copy_done.poll();
         (void)hipGetLastError();  // hipErrorNotReady from the queries is not an error
         if (!skinning) staging.begin_tick();
         TickIo io{stream};
@@ -253,16 +252,16 @@ void Engine::refresh_sun_and_lights() {
 }
 // Which copy of a double-buffered resource (the scene, the lights) this tick writes, on which stream: the first upload and ST_NO_DOUBLE_BUFFER=1
 // write the live copy in place on the caller's stream (behind the frames queued there); every later change goes to the other copy on copy_stream.
-int Engine::pick_copy(TickIo& io, int live_index, CopyFence& live_fence, CopyFence& other_fence, bool written_before, bool& alternating_now, CopyTarget& c) {
+int Engine::pick_copy(TickIo& io, int live_index, Fence& live_fence, Fence& other_fence, bool written_before, bool& alternating_now, CopyTarget& c) {
     c = CopyTarget{live_index, io.stream, &io.pageable, false};
     if (tuning.double_buffer && written_before && !mixed_render_streams) {
-        if (!copy_stream) { ST_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking)); ST_HIP(hipEventCreateWithFlags(&ev_copy, hipEventDisableTiming)); }
+        if (!copy_stream) ST_HIP(hipStreamCreateWithFlags(&copy_stream.h, hipStreamNonBlocking));
         if (!alternating_now) {  // frames enqueued so far read the live copy without marking their end: mark it now, behind them
             alternating_now = true;
-            if (int rc = live_fence.mark_read(io.stream)) return rc;
+            if (int rc = live_fence.record(io.stream)) return rc;
         }
         c = CopyTarget{live_index ^ 1, copy_stream, &io.pageable_copy, true};
-        if (other_fence.busy) { ST_HIP(hipStreamWaitEvent(copy_stream, other_fence.free_ev, 0)); other_fence.busy = false; }   // its readers are done first
+        if (int rc = other_fence.wait(copy_stream, Fence::AnyStream, Fence::Clear)) return rc;   // its readers are done first; cleared: the copy is written anew
     } else if (mixed_render_streams) ST_HIP(hipDeviceSynchronize());  // cameras render on several streams: no single event ends their reads
     return ST_OK;
 }
@@ -385,16 +384,11 @@ int Engine::upload_lights(TickIo& io) {
 // copies' events (reader_begin). Only copies that touch pageable host memory directly (staging full or disabled) make the tick wait for their stream.
 int Engine::end_uploads(TickIo& io) {
     if (io.copied) {
-        copy_in_flight = true;
-        ST_HIP(hipEventRecord(ev_copy, copy_stream));
-        ST_HIP(hipStreamWaitEvent(io.stream, ev_copy, 0));  // the caller's stream: the next frame's kernels (and the staging slot's event) come after the copies
+        if (int rc = copy_done.record(copy_stream)) return rc;
+        if (int rc = copy_done.wait(io.stream, Fence::AnyStream, Fence::Keep)) return rc;  // the caller's stream: the next frame's kernels (and the staging slot's event) come after the copies; kept for reader_begin
     }
     if (int rc = staging.end_tick(io.stream)) return rc;
-    if (io.uploaded) {
-        if (!ev_tick) ST_HIP(hipEventCreateWithFlags(&ev_tick, hipEventDisableTiming));
-        ST_HIP(hipEventRecord(ev_tick, io.stream));
-        tick_work_in_flight = true;
-    }
+    if (io.uploaded) if (int rc = tick_done.record(io.stream)) return rc;
     if (io.pageable_copy) ST_HIP(hipStreamSynchronize(copy_stream));
     if ((io.uploaded && io.pageable) || sync_every_tick) ST_HIP(hipStreamSynchronize(io.stream));
     return ST_OK;

@@ -1,0 +1,63 @@
+"""One fixed sequence of ABI calls for comparing the HIP calls two builds of the library issue (STROLLE_HIP_LIB picks the library):
+Cornell, then the dungeon, 1920 x 1080 Image{denoise}, 30 frames each with one spawn, one light move and one re-pose (a skinned tube,
+deformation motion on) in between, auto-exposure display and FXAA + resize for the last 10, then st_camera_delete and st_engine_destroy.
+Run it under `rocprofv3 --hip-trace --stats -- python tools/ownership_trace.py` once per library; with --summarize DIR it prints the
+per-API call counts of the trace under DIR as one JSON object."""
+import csv
+import glob
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def summarize(directory):
+    files = glob.glob(os.path.join(directory, "**", "*hip_api_stats.csv"), recursive=True)
+    assert len(files) == 1, files
+    print(json.dumps({r["Name"]: int(r["Calls"]) for r in csv.DictReader(open(files[0]))}, sort_keys=True))
+
+
+def run():
+    import numpy as np
+    import torch
+    from strolle_amd import CameraMode, Engine, Instance, Light, Material, Tonemap, scenes
+
+    size, out_size, tube = (1920, 1080), (2560, 1440), 7000
+    out = torch.zeros((out_size[1] * out_size[0], 4), dtype=torch.float32, device="cuda:0")
+    stream = torch.cuda.current_stream().cuda_stream
+    mesh, joints, weights = scenes.skinned_tube(24, 12, 6, length=1.2)
+    places = {"cornell": ((-0.4, 0.0, 0.0), (0.4, 0.0, -0.3), (0.0, 1.2, 1.0)), "dungeon": ((-6.1, 0.0, -19.0), (-5.4, 0.0, -19.0), (-5.75, 0.8, -18.0))}
+    at = lambda p: np.array([[1, 0, 0, p[0]], [0, 1, 0, p[1]], [0, 0, 1, p[2]]], np.float32)
+    for scene in ("cornell", "dungeon"):
+        e = Engine(device=0)
+        (scenes.build_cornell if scene == "cornell" else scenes.build_dungeon)(e)
+        e.set_seed(7)
+        first, second, lamp = places[scene]
+        e.insert_material(tube, Material(base_color=(0.2, 0.7, 0.3, 1.0)))
+        e.insert_mesh(tube, mesh); e.set_skin(tube, joints, weights, 6)
+        e.insert_instance(tube, Instance(tube, tube, at(first)))
+        e.insert_light(900, Light.point(lamp, 0.1, (2.0,) * 3, 20.0))
+        e.set_deformation_motion(True)
+        e.set_pose(tube, scenes.bend_pose(6, 1.6, 0.0, length=1.2))
+        cam = e.create_camera((scenes.cornell_camera if scene == "cornell" else scenes.dungeon_camera)(size, CameraMode.IMAGE, denoise=True))
+        for frame in range(30):
+            if frame == 8:
+                e.insert_instance(tube + 1, Instance(tube, tube, at(second)))                       # the spawn
+            if frame == 12:
+                e.insert_light(900, Light.point((lamp[0] + 0.2, lamp[1], lamp[2]), 0.1, (2.0,) * 3, 20.0))   # the light move
+            if frame == 16:
+                e.set_pose(tube, scenes.bend_pose(6, 1.6, 0.7, length=1.2))                         # the re-pose
+            if frame == 20:
+                e.set_display(cam, tonemap=Tonemap.ACES_FITTED, auto_exposure=True)
+                e.set_post(cam, fxaa=True, output_size=out_size)
+            e.tick(stream)
+            e.render_camera(cam, out.data_ptr(), stream)
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(out).all())
+        e.delete_camera(cam)
+        e.close()
+
+
+if __name__ == "__main__":
+    summarize(sys.argv[2]) if len(sys.argv) > 2 and sys.argv[1] == "--summarize" else run()
