@@ -551,6 +551,87 @@ int st_camera_output_size(StEngine* e, StHandle camera, uint32_t* width, uint32_
 int st_post_process(StEngine* e, const StPostDesc* desc, const void* src_rgba32f_device, uint32_t width, uint32_t height,
                     void* dst_device, int dst_format /* StOutputFormat */, void* hip_stream);
 
+/* ---- bloom (NEW seam): an HDR mip-pyramid glow in front of the display transform (st_bloom.cpp, k_bloom.hip). The first node of Bevy's
+ * HDR post chain (bloom -> tonemapping -> FXAA -> upscaling): what tells a viewer how bright a clipped light is.
+ * - Order: rendering -> bloom -> display transform -> FXAA -> resample -> output format.
+ * - Scope: the setting belongs to the camera and takes effect at its next st_render_camera. It changes only what is written to
+ *   `out_device`: AOVs, picks, scene queries, st_camera_read_buffer, the HDR history and the auto-exposure metering (it keeps metering the
+ *   composed frame before bloom: st_camera_exposure is the same with bloom on or off) are unchanged. BVH-heatmap frames are false colour and
+ *   skip bloom; every other mode (Reference included) passes through it. desc == NULL turns it off: the frame then launches the kernels it
+ *   launches without bloom, with the same arguments. The setting survives st_camera_update and st_engine_set_arithmetic. While a frame
+ *   blooms, the composing launch writes the composed colour, untransformed, into a camera-owned render-size RGBA32F plane (and meters it);
+ *   2 L launches (ST_PASS_POST, in front of FXAA and the resampler) follow on the caller's stream: L downsamples, L - 1 upsamples
+ *   and the composite, which also runs the display transform and writes the output format (or the post-processing plane). The pyramid is one
+ *   allocation, made by the first frame that needs it and again only when a larger render size or level count needs a larger one.
+ * - Arithmetic: float32, evaluated left to right as written, no fused multiply-add, division correctly rounded, in BOTH builds;
+ *   tests/bloom_ref.py restates all of it in numpy and the kernels match it bit for bit. min / max are the post-processing section's
+ *   (min(a, b) is a when a < b or b is NaN, else b; max likewise with >). Colours are r, g, b; alpha is written as 1. t(x, y) below is a
+ *   texel with both indices clamped to its image.
+ * - Plan (st_bloom_plan): mip 0 is ceil(W / 2) x ceil(H / 2), mip k halves mip k - 1 the same way. The level count L is the requested one
+ *   (0 = 6) reduced until mip L - 1 has both sides >= 2; a frame that cannot hold one level (a side below 3) has L = 0 and is not bloomed
+ *   (st_bloom_process then only applies the display transform and the format). Blend factor of level k, with x = k / max(L - 1, 1), in double
+ *   on the host and rounded to float: lf = (1 - (1 - x)^(1 / (1 - curvature))) low_frequency_boost, times (1 - intensity) unless
+ *   ST_BLOOM_ADDITIVE; hp = 1 - clamp((x - f) / f, 0, 1) with f = high_pass_frequency; b_k = (intensity + lf) hp.
+ * - Prefilter P of a frame texel: per channel v = min(max(x, 0), clamp) (NaN -> 0, +inf -> clamp: the pyramid is finite whatever the frame
+ *   holds). With threshold > 0: knee = threshold softness, m = max(max(r, g), b), s = min(max(m - (threshold - knee), 0), 2 knee),
+ *   s = (s s) / (4 knee + 1e-4), w = max(m - threshold, s) / max(m, 1e-4), and each channel is v w. (knee, threshold - knee, 2 knee and
+ *   4 knee + 1e-4 are float32 values computed once.)
+ * - Downsample (13 taps on the texel grid): for destination pixel (x, y), S(dx, dy) = ((t(X, Y) + t(X + 1, Y)) + (t(X, Y + 1) + t(X + 1, Y + 1))) 0.25
+ *   with (X, Y) = (2 x + dx, 2 y + dy). a b c = S(-2, -2) S(0, -2) S(2, -2), d e f = S(-2, 0) S(0, 0) S(2, 0), g h i = S(-2, 2) S(0, 2) S(2, 2),
+ *   j k = S(-1, -1) S(1, -1), l m = S(-1, 1) S(1, 1). G0 = (((a + b) + d) + e) 0.25, G1 = (((b + c) + e) + f) 0.25, G2 = (((d + e) + g) + h) 0.25,
+ *   G3 = (((e + f) + h) + i) 0.25, G4 = (((j + k) + l) + m) 0.25, weights W0..3 = 0.125, W4 = 0.5. The result is
+ *   (((G0 W0 + G1 W1) + G2 W2) + G3 W3) + G4 W4. The first downsample (frame -> mip 0) reads P(t). With ST_BLOOM_FIREFLY_SUPPRESS it uses
+ *   Wi' = Wi (1 / (1 + Y(Gi))) (Y: the display section's luminance) and divides that sum by (((W0' + W1') + W2') + W3') + W4'.
+ * - Upsample U(x, y) of a mip to a destination twice its size (or one less): the destination pixel sits at ((x + 0.5) / 2, (y + 0.5) / 2)
+ *   in source texels, so by the post-processing section's look-up rule i0 = floor((x + 1) / 2) - 1 and f = 0.75 for even x, 0.25 for odd x
+ *   (likewise y). B(ox, oy) is the bilinear look-up at texels (i0 + ox, j0 + oy): top = t(i, j) + (t(i + 1, j) - t(i, j)) fx, bottom likewise
+ *   on row j + 1, B = top + (bottom - top) fy. U = B(-1, -1) / 16 + B(0, -1) / 8 + B(1, -1) / 16 + B(-1, 0) / 8 + B(0, 0) / 4 + B(1, 0) / 8 +
+ *   B(-1, 1) / 16 + B(0, 1) / 8 + B(1, 1) / 16, summed left to right in this order.
+ * - Chain: for k = L - 1 .. 1: mip[k - 1] = mip[k - 1] (1 - b_k) + U_k b_k, or mip[k - 1] + U_k b_k with ST_BLOOM_ADDITIVE.
+ * - Composite: c' = c (1 - b_0) + U_0 b_0, or c + U_0 b_0 with ST_BLOOM_ADDITIVE, c being the composed colour as it is: an infinite pixel
+ *   stays infinite and reaches no other pixel. c' goes through the display transform (the camera's operator and its manual or metered
+ *   scale) and the output format.
+ * - Tiles: bloom reads far across tile edges, so a camera cannot have bloom and a window (st_camera_set_window, st_dist_set_partition,
+ *   st_dist_set_grid) at once: ST_ERR_INVALID_ARGUMENT from whichever setter comes second. For tiled frames the ranks render RGBA32F with
+ *   display and bloom off, st_dist_gather assembles the frame on rank 0, and rank 0 runs st_bloom_process (with the display descriptor) and
+ *   then st_post_process on it.
+ * - Errors: ST_ERR_INVALID_ARGUMENT for a wrong struct_size, unknown flags, a field outside the ranges below (NaN included), a null pointer
+ *   where one is not allowed, a frame side above 16384 (st_bloom_plan, st_bloom_process; 0 too for st_bloom_process), and an auto-exposure
+ *   display passed to st_bloom_process. An unknown camera is ST_ERR_UNKNOWN_CAMERA. Set, get
+ *   and st_bloom_plan are host work and valid on a host-only engine; st_bloom_process returns ST_ERR_NO_DEVICE there. */
+enum { ST_BLOOM_ADDITIVE = 1, ST_BLOOM_FIREFLY_SUPPRESS = 2 };
+typedef struct StBloomDesc {               /* 40 B */
+    uint32_t struct_size;                  /* sizeof(StBloomDesc) */
+    uint32_t flags;                        /* ST_BLOOM_* */
+    uint32_t levels;                       /* 1..8; 0 = default 6 */
+    float intensity;                       /* finite, >= 0; <= 1 unless ST_BLOOM_ADDITIVE */
+    float low_frequency_boost;             /* 0..1 */
+    float low_frequency_boost_curvature;   /* 0 <= curvature < 1 */
+    float high_pass_frequency;             /* 0 < f <= 1 */
+    float threshold;                       /* >= 0, finite; 0 = no prefilter threshold */
+    float threshold_softness;              /* 0..1 */
+    float clamp;                           /* > 0, finite; 0 = default 65504 */
+} StBloomDesc;
+int st_camera_set_bloom(StEngine* e, StHandle camera, const StBloomDesc* desc);   /* NULL = off */
+/* the last desc set (a zeroed desc with struct_size when none was) and whether bloom is on; either pointer may be NULL */
+int st_camera_get_bloom(StEngine* e, StHandle camera, StBloomDesc* out, int* enabled);
+/* Pure host arithmetic, no engine: the effective level count, each mip's size (width, height pairs) and the per-level blend factors for a
+ * width x height frame. Entries past the level count are 0. Any of the three outputs may be NULL. */
+int st_bloom_plan(const StBloomDesc* desc, uint32_t width, uint32_t height, uint32_t* levels, uint32_t sizes_wh[16], float factors[8]);
+/* Stateless, like st_post_process: src (RGBA32F, HDR) -> bloom -> the display transform (NULL = none; manual exposure only) -> dst_device
+ * (width x height) in dst_format. Needs a device engine; no camera, no tick. Enqueued on hip_stream without a host sync. The pyramid is
+ * engine-owned: it is allocated (with a device sync) only when a call needs a larger one than any before it, and calls on different
+ * streams are ordered by the engine. src and dst must not overlap. */
+int st_bloom_process(StEngine* e, const StBloomDesc* desc, const StDisplayDesc* display, const void* src_rgba32f_device,
+                     uint32_t width, uint32_t height, void* dst_device, int dst_format /* StOutputFormat */, void* hip_stream);
+/* Debug / measurement seam: the fused tail of the bloom chain, OFF by default (it measured slower than the launches it replaces:
+ * tools/experiments/bloom_fused_tail.md). With it the last levels of the pyramid, those whose mips fit one workgroup's LDS together at three
+ * floats per texel, go down and back up in ONE single-workgroup launch instead of two launches per level; the bits are those of the
+ * straightforward chain. lds_bytes: 0 = no fused tail (the default), -1 = what the device grants, n = at most n bytes. The
+ * environment variable ST_BLOOM_TAIL_BYTES sets the same when an engine is created. *in_force (may be NULL): the byte budget now in force
+ * (0 on a host-only engine). */
+int st_debug_set_bloom_tail(StEngine* e, int lds_bytes, uint32_t* in_force);
+
 /* ---- multi-GPU behind the boundary (NEW seam; SURVEY.md section 8e, BASELINE.json configs 4 and 5). One process per GPU, one
  * engine per process, the scene replicated; the frame is cut into tiles, every rank renders its tile (+ an apron of redundant
  * pixels in Image mode, whose passes read neighbours) with absolute pixel coordinates, and the ONE collective of the path
@@ -730,7 +811,7 @@ enum StPassBit {
     ST_PASS_DENOISE_REPROJECT_DI = 1u << 18, ST_PASS_DENOISE_REPROJECT_GI = 1u << 19, ST_PASS_DENOISE_VARIANCE = 1u << 20,
     ST_PASS_DENOISE_WAVELET_0 = 1u << 21, /* ... wavelet pass n = ST_PASS_DENOISE_WAVELET_0 << n, n < 5 */
     ST_PASS_COMPOSITION = 1u << 26, ST_PASS_BVH_HEATMAP = 1u << 27, ST_PASS_REF_TRACING = 1u << 28, ST_PASS_REF_SHADING = 1u << 29,
-    ST_PASS_POST = 1u << 30   /* the post-processing launches behind composition ("post-processing" above): FXAA and / or the resampler, one launch group */
+    ST_PASS_POST = 1u << 30   /* the launches behind composition, one launch group: bloom ("bloom" above), then FXAA and / or the resampler ("post-processing") */
 };
 int st_debug_set_pass_mask(StEngine* e, uint64_t mask);
 /* Measurement only (tools/pair_matrix.py): the frame's graph is built as always — every fusion of the whole frame — but only the launches

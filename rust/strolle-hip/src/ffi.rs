@@ -272,6 +272,31 @@ extern "C" {
     pub fn st_post_process(e: *mut StEngine, desc: *const StPostDesc, src_rgba32f_device: *const c_void, width: u32, height: u32, dst_device: *mut c_void, dst_format: i32, hip_stream: *mut c_void) -> i32;
 }
 
+// bloom (include/strolle_hip.h "bloom"): an HDR mip-pyramid glow in front of the display transform
+pub const ST_BLOOM_ADDITIVE: u32 = 1;
+pub const ST_BLOOM_FIREFLY_SUPPRESS: u32 = 2;
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct StBloomDesc {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub levels: u32,
+    pub intensity: f32,
+    pub low_frequency_boost: f32,
+    pub low_frequency_boost_curvature: f32,
+    pub high_pass_frequency: f32,
+    pub threshold: f32,
+    pub threshold_softness: f32,
+    pub clamp: f32,
+}
+extern "C" {
+    pub fn st_camera_set_bloom(e: *mut StEngine, camera: u64, desc: *const StBloomDesc) -> i32; // null = off
+    pub fn st_camera_get_bloom(e: *mut StEngine, camera: u64, out: *mut StBloomDesc, enabled: *mut i32) -> i32;
+    pub fn st_bloom_plan(desc: *const StBloomDesc, width: u32, height: u32, levels: *mut u32, sizes_wh: *mut u32, factors: *mut f32) -> i32;
+    pub fn st_debug_set_bloom_tail(e: *mut StEngine, lds_bytes: i32, in_force: *mut u32) -> i32;
+    pub fn st_bloom_process(e: *mut StEngine, desc: *const StBloomDesc, display: *const StDisplayDesc, src_rgba32f_device: *const c_void, width: u32, height: u32, dst_device: *mut c_void, dst_format: i32, hip_stream: *mut c_void) -> i32;
+}
+
 // ---- the HIP runtime, as far as the staging-copy present needs it (libamdhip64)
 pub type hipStream_t = *mut c_void;
 extern "C" {

@@ -172,6 +172,27 @@ def post_desc(fxaa: bool = False, output_size=None, filter=ResampleFilter.BILINE
                       float(fxaa_edge_threshold_min), float(fxaa_subpixel))
 
 
+class StBloomDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("levels", C.c_uint32), ("intensity", C.c_float),
+                ("low_frequency_boost", C.c_float), ("low_frequency_boost_curvature", C.c_float), ("high_pass_frequency", C.c_float),
+                ("threshold", C.c_float), ("threshold_softness", C.c_float), ("clamp", C.c_float)]
+
+
+BLOOM_ADDITIVE = 1
+BLOOM_FIREFLY_SUPPRESS = 2
+BLOOM_MAX_LEVELS = 8
+
+
+def bloom_desc(intensity: float = 0.15, additive: bool = False, firefly_suppress: bool = False, levels: int = 0, low_frequency_boost: float = 0.7,
+               low_frequency_boost_curvature: float = 0.95, high_pass_frequency: float = 1.0, threshold: float = 0.0, threshold_softness: float = 0.0,
+               clamp: float = 0.0) -> StBloomDesc:
+    """A StBloomDesc; the defaults are Bevy's "natural" bloom (energy conserving, no threshold). levels 0 = 6, clamp 0 = 65504
+    (include/strolle_hip.h "bloom")."""
+    return StBloomDesc(C.sizeof(StBloomDesc), (BLOOM_ADDITIVE if additive else 0) | (BLOOM_FIREFLY_SUPPRESS if firefly_suppress else 0), int(levels),
+                       float(intensity), float(low_frequency_boost), float(low_frequency_boost_curvature), float(high_pass_frequency),
+                       float(threshold), float(threshold_softness), float(clamp))
+
+
 class StRay(C.Structure):
     """include/strolle_hip.h StRay (32 B): hits count for 0 < t < t_max; the direction is used as given (t in units of |direction|)."""
     _fields_ = [("origin", C.c_float * 3), ("t_max", C.c_float), ("direction", C.c_float * 3), ("_pad", C.c_uint32)]
@@ -485,6 +506,12 @@ class _Binding:
             self.camera_get_post = fn("camera_get_post", [vp, u64, P(StPostDesc), P(i32)])
             self.camera_output_size = fn("camera_output_size", [vp, u64, P(u32), P(u32)])
             self.post_process = fn("post_process", [vp, P(StPostDesc), vp, u32, u32, vp, i32, vp])
+        if hasattr(lib, prefix + "camera_set_bloom"):   # bloom (likewise)
+            self.camera_set_bloom = fn("camera_set_bloom", [vp, u64, P(StBloomDesc)])
+            self.camera_get_bloom = fn("camera_get_bloom", [vp, u64, P(StBloomDesc), P(i32)])
+            self.bloom_plan = fn("bloom_plan", [P(StBloomDesc), u32, u32, P(u32), P(u32), P(C.c_float)])
+            self.debug_set_bloom_tail = fn("debug_set_bloom_tail", [vp, i32, P(u32)])
+            self.bloom_process = fn("bloom_process", [vp, P(StBloomDesc), P(StDisplayDesc), vp, u32, u32, vp, i32, vp])
         if hasattr(lib, prefix + "mesh_set_skin"):
             self.mesh_set_skin = fn("mesh_set_skin", [vp, u64, vp, sz, u32])
         if hasattr(lib, prefix + "engine_set_deformation_motion"):   # deformation motion (likewise absent from an older library)
@@ -956,6 +983,37 @@ class Engine(EngineBase):
     def post_process(self, desc: StPostDesc, src_ptr: int, width: int, height: int, dst_ptr: int, dst_format: int = 0, stream: int = 0):
         """st_post_process: FXAA and / or resampling of any RGBA32F device image into dst (the desc's output size) in dst_format."""
         self._check(self._b.post_process(self._h, C.byref(desc), src_ptr, width, height, dst_ptr, int(dst_format), stream))
+
+    # ---- bloom (include/strolle_hip.h "bloom"): takes effect at the camera's next render
+    def set_bloom(self, camera: int, desc: Optional[StBloomDesc] = None, **kw):
+        """st_camera_set_bloom: a StBloomDesc, or bloom_desc(**kw) when keywords are given; neither = off."""
+        if desc is None and kw:
+            desc = bloom_desc(**kw)
+        self._check(self._b.camera_set_bloom(self._h, camera, C.byref(desc) if desc is not None else None))
+
+    def bloom(self, camera: int):
+        """st_camera_get_bloom: (the last StBloomDesc set, whether bloom is on)."""
+        d, on = StBloomDesc(), C.c_int()
+        self._check(self._b.camera_get_bloom(self._h, camera, C.byref(d), C.byref(on)))
+        return d, bool(on.value)
+
+    def bloom_plan(self, desc: StBloomDesc, width: int, height: int):
+        """st_bloom_plan (host arithmetic): (levels, [(width, height) per mip], float32 blend factors per level)."""
+        n, sizes, factors = C.c_uint32(), (C.c_uint32 * 16)(), (C.c_float * 8)()
+        self._check(self._b.bloom_plan(C.byref(desc), width, height, C.byref(n), sizes, factors))
+        return n.value, [(sizes[2 * k], sizes[2 * k + 1]) for k in range(n.value)], np.array(factors[:n.value], np.float32)
+
+    def bloom_process(self, desc: StBloomDesc, src_ptr: int, width: int, height: int, dst_ptr: int, dst_format: int = 0,
+                      display: Optional[StDisplayDesc] = None, stream: int = 0):
+        """st_bloom_process: bloom over any RGBA32F device image, then the (manual) display transform, into dst (width x height) in dst_format."""
+        self._check(self._b.bloom_process(self._h, C.byref(desc), C.byref(display) if display is not None else None, src_ptr, width, height,
+                                          dst_ptr, int(dst_format), stream))
+
+    def set_bloom_tail(self, lds_bytes: int = -1) -> int:
+        """st_debug_set_bloom_tail: the LDS budget of the bloom chain's fused tail (-1 the device's, 0 no tail); returns the bytes in force."""
+        out = C.c_uint32()
+        self._check(self._b.debug_set_bloom_tail(self._h, int(lds_bytes), C.byref(out)))
+        return out.value
 
     # ---- environment lighting (include/strolle_hip.h "environment lighting"): takes effect at the next tick
     def set_environment(self, texels, intensity: float = 1.0, yaw: float = 0.0, keep_sun: bool = False, uniform: bool = False):

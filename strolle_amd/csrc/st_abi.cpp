@@ -255,6 +255,7 @@ int st_camera_set_window(StEngine* e, StHandle h, uint32_t x0, uint32_t y0, uint
     const bool full = x0 == 0u && y0 == 0u && x1 == s.desc.width && y1 == s.desc.height;
     ST_REQUIRE(full || !s.display_auto(), "a window on a camera with auto-exposure would meter the tile alone (include/strolle_hip.h \"display transforms\")");
     ST_REQUIRE(full || !s.post_on, "a window on a camera with post-processing: FXAA and the resampler read across tile edges (include/strolle_hip.h \"post-processing\")");
+    ST_REQUIRE(full || !s.bloom_on, "a window on a camera with bloom: the pyramid reads far across tile edges (include/strolle_hip.h \"bloom\")");
     s.row0 = y0; s.row1 = y1; s.col0 = x0; s.col1 = x1;
     return ST_OK;
 }
@@ -325,6 +326,46 @@ int st_camera_output_size(StEngine* e, StHandle h, uint32_t* width, uint32_t* he
 int st_post_process(StEngine* e, const StPostDesc* desc, const void* src, uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
     ST_REQUIRE(e, "null engine");
     return E(e)->post_process(desc, src, width, height, dst, dst_format, static_cast<hipStream_t>(stream));
+}
+
+// ---- bloom (st_bloom.cpp)
+int st_camera_set_bloom(StEngine* e, StHandle h, const StBloomDesc* desc) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    return E(e)->set_bloom(*it->second, desc);
+}
+int st_camera_get_bloom(StEngine* e, StHandle h, StBloomDesc* out, int* enabled) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    const CameraState& s = *it->second;
+    if (out) { *out = s.bloom; out->struct_size = sizeof(StBloomDesc); }
+    if (enabled) *enabled = s.bloom_on ? 1 : 0;
+    return ST_OK;
+}
+int st_bloom_plan(const StBloomDesc* desc, uint32_t width, uint32_t height, uint32_t* levels, uint32_t sizes_wh[16], float factors[8]) {
+    ST_REQUIRE(desc, "null desc");
+    Engine::BloomPlan plan;
+    if (int rc = Engine::bloom_plan(*desc, width, height, plan)) return rc;
+    if (levels) *levels = plan.levels;
+    for (uint32_t k = 0; k < 8u; k++) {
+        if (sizes_wh) { sizes_wh[2u * k] = plan.w[k]; sizes_wh[2u * k + 1u] = plan.h[k]; }
+        if (factors) factors[k] = plan.factor[k];
+    }
+    return ST_OK;
+}
+int st_bloom_process(StEngine* e, const StBloomDesc* desc, const StDisplayDesc* display, const void* src, uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
+    ST_REQUIRE(e, "null engine");
+    return E(e)->bloom_process(desc, display, src, width, height, dst, dst_format, static_cast<hipStream_t>(stream));
+}
+
+int st_debug_set_bloom_tail(StEngine* e, int lds_bytes, uint32_t* in_force) {
+    ST_REQUIRE(e, "null engine");
+    ST_REQUIRE(lds_bytes >= -1, "lds_bytes is -1 (what the device grants), 0 (no fused tail) or a byte count");
+    E(e)->bloom_tail_wanted = lds_bytes;
+    if (in_force) *in_force = E(e)->bloom_tail_bytes();
+    return ST_OK;
 }
 
 int st_tick(StEngine* e, void* stream) { ST_REQUIRE(e, "null engine"); return E(e)->tick(static_cast<hipStream_t>(stream)); }

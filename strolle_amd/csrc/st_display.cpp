@@ -8,7 +8,7 @@ namespace st {
 
 static constexpr double kMidGrey = 0.18;
 
-static int check_display(const StDisplayDesc& d) {
+int check_display(const StDisplayDesc& d) {
     if (d.struct_size != sizeof(StDisplayDesc)) return fail(ST_ERR_INVALID_ARGUMENT, "StDisplayDesc.struct_size is not sizeof(StDisplayDesc)");
     if (d.tonemap > ST_TONEMAP_PBR_NEUTRAL) return fail(ST_ERR_INVALID_ARGUMENT, "unknown tonemap");
     if ((d.flags & ~(uint32_t)ST_DISPLAY_AUTO_EXPOSURE) != 0u) return fail(ST_ERR_INVALID_ARGUMENT, "unknown display flag bits");

@@ -364,6 +364,14 @@ struct CameraState {
     Fence post_read;   // recorded behind each frame's post launches: a frame on another stream waits for it before it writes the planes again
     bool post_resizes() const { return post_on && post.output_width != 0u && (post.output_width != desc.width || post.output_height != desc.height); }
     bool post_fxaa() const { return post_on && (post.flags & ST_POST_FXAA) != 0u && desc.mode != ST_MODE_BVH_HEATMAP; }   // heatmap frames are false colour
+    // Bloom (st_bloom.cpp; include/strolle_hip.h "bloom"). Like the display and post-processing it survives st_camera_update. While a frame
+    // blooms, the composing launch writes bloom_hdr (render size, RGBA32F, untransformed) instead of the caller's buffer or post_plane[0], and
+    // the bloom launches build the pyramid (one allocation of float4 mips) from it; the composite writes where the composing launch would have.
+    // Both are made by the first frame that needs them and again only when the render size (or the pyramid's level count) changes.
+    StBloomDesc bloom{}; bool bloom_on = false;
+    DeviceArray bloom_hdr, bloom_pyramid;
+    Fence bloom_read;   // recorded behind each frame's bloom launches: a frame on another stream waits for it before it writes the two again
+    bool blooms() const { return bloom_on && desc.mode != ST_MODE_BVH_HEATMAP; }   // heatmap frames are false colour
     uint32_t out_width() const { return post_on && post.output_width != 0u ? post.output_width : desc.width; }
     uint32_t out_height() const { return post_on && post.output_width != 0u ? post.output_height : desc.height; }
     // A present copy still in flight writes the caller's host memory: it lands before the stream goes. Everything else goes with its member —
@@ -411,6 +419,8 @@ int dist_window(uint32_t width, uint32_t height, const StDistRect* owned, uint32
 int dist_grid(uint32_t width, uint32_t height, uint32_t world, uint32_t cols, StDistGrid* out);
 int dist_grid_tile(const StDistGrid* g, uint32_t rank, StDistRect* owned);
 int dist_grid_rebalance(uint32_t width, uint32_t height, const StDistGrid* cur, const float* cost, uint32_t max_step, StDistGrid* out);
+
+int check_display(const StDisplayDesc& d);   // st_display.cpp: the setter's checks (st_bloom_process takes a display descriptor too)
 
 struct Engine {
     int device = -1;
@@ -772,6 +782,24 @@ struct Engine {
     int post_done(CameraState& c, hipStream_t stream);                  // behind a frame's post launches
     int post_process(const StPostDesc* desc, const void* src, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
     DeviceArray post_scratch; Fence post_scratch_read;   // st_post_process's intermediate plane (FXAA -> resampler) and the end of its last use
+    // ---- bloom (st_bloom.cpp)
+    struct BloomPlan { uint32_t levels = 0; uint32_t w[8] = {}, h[8] = {}; float factor[8] = {}; size_t offset[8] = {}; size_t texels = 0; };
+    struct BloomStep { int slot; bool first; BloomArgs args; BloomTailArgs tail; double bytes; };
+    struct BloomSteps { BloomStep step[16]; uint32_t count = 0; };
+    static int bloom_plan(const StBloomDesc& d, uint32_t w, uint32_t h, BloomPlan& plan);   // checks the desc; levels == 0: the frame holds no level
+    // the frame's launches in order: `src` (w x h RGBA32F) -> the pyramid -> `dst` in `format` through `display`
+    static BloomSteps bloom_steps(const StBloomDesc& d, const BloomPlan& plan, const void* src, uint32_t w, uint32_t h, float4* pyramid, void* dst, uint32_t format, const DisplayArgs& display, uint32_t tail_lds_bytes);
+    int set_bloom(CameraState& c, const StBloomDesc* desc);
+    int bloom_planes(CameraState& c, const BloomPlan& plan, hipStream_t stream);   // the camera's HDR plane and pyramid (allocates only when their sizes changed), ordered behind their last readers
+    int bloom_done(CameraState& c, hipStream_t stream);                            // behind a frame's bloom launches
+    int bloom_process(const StBloomDesc* desc, const StDisplayDesc* display, const void* src, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
+    // The fused tail (k_bloom.hip k_bloom_tail), an experiment that measured slower and is OFF by default (tools/experiments/bloom_fused_tail.md): the LDS
+    // its one workgroup may use. 0: no tail, the straightforward chain (the default); -1: what the device grants; n: at most n bytes
+    // (ST_BLOOM_TAIL_BYTES in the environment, st_debug_set_bloom_tail). bloom_tail_bytes() is the figure in force.
+    int bloom_tail_wanted = 0;
+    uint32_t bloom_tail_bytes();
+    static uint32_t bloom_tail_first(const BloomPlan& plan, uint32_t tail_lds_bytes);   // the first level the tail takes (== plan.levels: none)
+    DeviceArray bloom_scratch; Fence bloom_scratch_read;   // st_bloom_process's pyramid and the end of its last use
     int scene_args(KArgs& a, bool heatmap) const;   // the scene half of KArgs (st_render.cpp): render() and the scene queries
 
     // ---- scene queries (st_query.cpp; include/strolle_hip.h "scene queries")

@@ -40,6 +40,7 @@ enum KernelSlot {
     KS_GI_PREVIEW_BOTH, KS_GI_PREVIEW_BOTH_NO_REPROJECT, KS_GI_PREVIEW_LATE, KS_DENOISE_WAVELET_COMPOSE, KS_GI_SAMPLING_AB,
     KS_DENOISE_WAVELET_FAMILY,  // profiling only (ST_PROFILE_GROUP_ATROUS): the a-trous chain's launches timed as ONE interval
     KS_POST_FXAA, KS_POST_RESAMPLE,  // output post-processing behind composition (k_post.hip); their bytes depend on the output size and format: render() credits them itself
+    KS_BLOOM_DOWN, KS_BLOOM_UP, KS_BLOOM_COMPOSITE, KS_BLOOM_TAIL,  // bloom in front of the display transform (k_bloom.hip); bytes depend on the level: render() credits them itself
     KS_COUNT
 };
 struct KernelInfo { const char* name; float bytes_per_unit; bool half; };
@@ -69,6 +70,8 @@ inline const KernelInfo& kernel_info(int slot) {
         {"gi_sampling_a+b", 80.f + 144.f, true},
         {"a-trous chain (one timed interval)", 0.f, false},  // bytes: the sum its member launches are credited
         {"post_fxaa", 0.f, false},           {"post_resample", 0.f, false},
+        {"bloom_down", 0.f, false},          {"bloom_up", 0.f, false},             {"bloom_composite", 0.f, false},
+        {"bloom_tail", 0.f, false},
     };
     return k[slot];
 }

@@ -84,3 +84,11 @@ ST_LAUNCHER(launch_display_finalize, (void* state, float ev_min, float ev_max, f
 // resampler (nearest / bilinear / Catmull-Rom to out_width x out_height, any output format); equal sizes make it a format-converting copy
 ST_LAUNCHER(launch_post_fxaa, (const PostArgs& p, hipStream_t s))
 ST_LAUNCHER(launch_post_resample, (const PostArgs& p, hipStream_t s))
+// bloom (k_bloom.hip; st_bloom.cpp): one level down (first: the prefilter, and firefly suppression when asked, on the way), one level up blended in
+// place, and the composite (the last upsample + the blend with the composed frame + the display transform + the output format)
+ST_LAUNCHER(launch_bloom_down, (const BloomArgs& p, bool first, hipStream_t s))
+ST_LAUNCHER(launch_bloom_up, (const BloomArgs& p, hipStream_t s))
+ST_LAUNCHER(launch_bloom_composite, (const BloomArgs& p, hipStream_t s))
+// ... and the fused tail: the last levels down and back up in one single-workgroup launch, in LDS (`limit`: the bytes that launch may use here)
+ST_LAUNCHER(launch_bloom_tail_limit, (uint32_t* bytes))
+ST_LAUNCHER(launch_bloom_tail, (const BloomTailArgs& p, hipStream_t s))

@@ -242,7 +242,7 @@ template <bool DISPLAY>
 ST_D void store_display(void* out, uint32_t at, float4 c, uint32_t format, const DisplayArgs& d, float s, uint32_t* lds) {
     if (!DISPLAY) { store_output(out, at, c, format); return; }
     if (d.meter) atomicAdd(lds + display_bin(c, d), 1u);
-    store_output(out, at, display_transform(c, d.tonemap, s), format);
+    store_output(out, at, d.tonemap == kDisplayRaw ? c : display_transform(c, d.tonemap, s), format);   // (raw: a frame that blooms is transformed behind the bloom)
 }
 
 }  // namespace st

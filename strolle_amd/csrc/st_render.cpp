@@ -164,8 +164,23 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
     // RGBA32F plane instead of `out`, and the post launches at the end of this function write `out` behind it on `stream`.
     const bool post_fxaa = out && c.post_fxaa(), post_resample = out && c.post_resizes(), post = post_fxaa || post_resample;
     if (post) if (int rc = post_planes(c, post_fxaa && post_resample, stream)) return rc;
-    void* const comp_out = post ? c.post_plane[0].ptr : out;
-    const uint32_t comp_format = post ? (uint32_t)ST_FORMAT_RGBA32F : c.out_format;
+    // Bloom (st_bloom.cpp): while this frame blooms, the composing launch writes the composed colour untransformed (and still meters it) into
+    // the camera's HDR plane; the bloom launches behind it end in the composite, which runs the display transform and writes what the composing
+    // launch would have written: `out`, or the post-processing plane.
+    BloomPlan bloom_plan_now;
+    bool bloom = false;
+    if (out && c.blooms()) {
+        if (int rc = bloom_plan(c.bloom, c.desc.width, c.desc.height, bloom_plan_now)) return rc;
+        bloom = bloom_plan_now.levels != 0u;
+    }
+    if (bloom) if (int rc = bloom_planes(c, bloom_plan_now, stream)) return rc;
+    void* const frame_out = post ? c.post_plane[0].ptr : out;
+    const uint32_t frame_format = post ? (uint32_t)ST_FORMAT_RGBA32F : c.out_format;
+    void* const comp_out = bloom ? c.bloom_hdr.ptr : frame_out;
+    const uint32_t comp_format = bloom ? (uint32_t)ST_FORMAT_RGBA32F : frame_format;
+    DisplayArgs frame_disp = disp;   // what the composite applies; no display: NONE at scale 1, which stores the colour's own bits
+    if (!frame_disp.on) frame_disp.scale = 1.0f;
+    if (bloom) { if (disp.meter) disp.tonemap = kDisplayRaw; else disp = DisplayArgs{}; }   // the composing launch: meter, do not transform
     const bool alt = c.frame % 2u == 1u;
     c.last_lean = 0u; c.last_lean_composed = false;
     KArgs a{};
@@ -497,6 +512,20 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
         const float4* di_diff = (dn && (mode == ST_MODE_IMAGE || mode == ST_MODE_DI_DIFFUSE)) ? a.di_diff_curr_colors : a.di_diff_samples;
         const float4* gi_diff = (dn && (mode == ST_MODE_IMAGE || mode == ST_MODE_GI_DIFFUSE)) ? a.gi_diff_curr_colors : a.gi_diff_samples;
         run(KS_COMPOSITION, ST_PASS_COMPOSITION, [&] { L.launch_composition(a, mode, di_diff, gi_diff, comp_out, comp_format, disp, cur); });
+    }
+    if (bloom) {   // the composing launch ran on `stream`; the same launch group as the post launches behind it (ST_PASS_POST)
+        cur = stream;
+        const BloomSteps steps = bloom_steps(c.bloom, bloom_plan_now, c.bloom_hdr.ptr, c.desc.width, c.desc.height, c.bloom_pyramid.as<float4>(), frame_out, frame_format, frame_disp, bloom_tail_bytes());
+        for (uint32_t i = 0; i < steps.count; i++) {
+            const BloomStep& st = steps.step[i];
+            post_bytes = st.bytes;
+            if (st.slot == KS_BLOOM_DOWN) run(KS_BLOOM_DOWN, ST_PASS_POST, [&] { L.launch_bloom_down(st.args, st.first, cur); });
+            else if (st.slot == KS_BLOOM_UP) run(KS_BLOOM_UP, ST_PASS_POST, [&] { L.launch_bloom_up(st.args, cur); });
+            else if (st.slot == KS_BLOOM_TAIL) run(KS_BLOOM_TAIL, ST_PASS_POST, [&] { L.launch_bloom_tail(st.tail, cur); });
+            else run(KS_BLOOM_COMPOSITE, ST_PASS_POST, [&] { L.launch_bloom_composite(st.args, cur); });
+        }
+        post_bytes = -1.0;
+        if (int rc = bloom_done(c, stream)) return rc;
     }
     if (post) {   // the composing launch ran on `stream`; one launch group (ST_PASS_POST) of at most two kernels
         cur = stream;

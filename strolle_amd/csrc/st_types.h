@@ -66,6 +66,7 @@ static_assert(sizeof(EnvCell) == 12, "an importance cell is 12 B");
 // are the parent's instantiations, which never read the rest. With `meter` set the kernels take the scale from the camera's device state
 // (DisplayState::scale, written by the previous frame's finalize) and add their pixels to `hist`.
 constexpr uint32_t kDisplayBins = 64;
+constexpr uint32_t kDisplayRaw = 0xffffffffu;   // DisplayArgs::tonemap of a frame that blooms: meter, store the composed colour as it is (k_bloom.hip transforms it later)
 struct DisplayArgs {
     uint32_t on, tonemap, meter;
     float scale;               // manual: 2^exposure_ev (rounded from double on the host)
@@ -89,6 +90,25 @@ struct PostArgs {
     const float4* src; void* dst;
     uint32_t width, height, out_width, out_height, format, filter;
     float edge_threshold, edge_threshold_min, subpixel;   // FXAA, defaults resolved by the host
+};
+
+// Bloom (include/strolle_hip.h "bloom"; st_bloom.cpp, k_bloom.hip): one launch's arguments. A downsample reads `src` (sw x sh) and writes
+// `dst` (dw x dh float4, ceil(sw / 2) x ceil(sh / 2)); an upsample reads `src` (sw x sh) and blends it into `dst` (dw x dh float4) in place
+// with `factor`; the composite upsamples `src` (mip 0; sw == 0: no level, nothing is added) onto `base` (the dw x dh composed frame), runs
+// the display transform and stores `format` into `dst`. The prefilter's constants are resolved by the host.
+struct BloomArgs {
+    const float4* src; void* dst; const float4* base;
+    uint32_t sw, sh, dw, dh, format, additive, firefly, threshold_on;
+    float factor, clamp, threshold, knee_lo /* threshold - knee */, knee2 /* 2 knee */, knee_div /* 4 knee + 1e-4 */;
+    DisplayArgs display;
+};
+
+// The fused tail of the bloom chain (k_bloom.hip k_bloom_tail): `base` is mip t - 1 (bw x bh, read and blended in place), the n levels below it
+// live in LDS at float offsets `off` (three floats per texel), `factor[i]` blends tail level i into the level above it.
+struct BloomTailArgs {
+    float4* base; uint32_t bw, bh, n, additive, lds_bytes;
+    uint32_t w[8], h[8], off[8];
+    float factor[8];
 };
 
 // Everything a per-pixel kernel can touch, passed by value as the kernel argument (scalar loads).
