@@ -351,7 +351,7 @@ int st_instance_set_pose(StEngine* e, StHandle instance, const float* joint_xfor
  * needed (host-path refresh modes, heatmap observers, debug reads of the scene). */
 int st_debug_skinning(StEngine* e, uint64_t* launches, uint64_t* triangles, uint64_t* host_readbacks);
 /* The instance's posed object-space triangles as the device holds them: 24 floats per triangle (positions 9, normals 9, uvs 6: the device
- * mesh store's layout). Blocking. An instance without a pose is ST_ERR_INVALID_ARGUMENT. out == NULL only reports the size. */
+ * mesh store's layout). Blocking. An instance with neither a pose nor morph weights is ST_ERR_INVALID_ARGUMENT. out == NULL only reports the size. */
 int st_debug_read_posed(StEngine* e, StHandle instance, float* out, size_t capacity_floats, size_t* written_floats);
 /* Deformation motion (above). Host work: valid on a host-only engine (which never has a pose). Takes effect at the next st_tick. */
 int st_engine_set_deformation_motion(StEngine* e, int enabled);
@@ -359,6 +359,51 @@ int st_engine_get_deformation_motion(StEngine* e, int* enabled);
 /* What the last st_tick left: the instances whose hits take the deformation term in the frames after it, and the device memory the
  * second regions of the posed store hold. 0 / 0 while the switch is off. A host-only engine is ST_ERR_NO_DEVICE. */
 int st_debug_deformation(StEngine* e, uint64_t* instances_with_previous, uint64_t* previous_bytes);
+
+/* ---- morph targets (NEW seam): per-instance blend-shape weights applied on the device (k_skin.hip k_morph; glTF `targets` / `weights`).
+ * Targets belong to a mesh, weights to an instance: instances share a morphed mesh and each carries weights of its own (Bevy's
+ * MorphWeights per entity). A mesh may have targets, a skin, both, or neither. An instance without weights renders the base mesh.
+ * - When weights take effect: at the next st_tick, like a pose. Frames, scene queries and AOVs see them only after that tick; of two
+ *   weight sets given before one tick the last wins.
+ * - Arithmetic: float32, evaluated left to right, no fused multiply-add; the kernel is built once with the exact build's flags (like
+ *   skinning), so fast and exact engines give the same bits. The ACTIVE targets are those whose weight is not exactly 0, in ascending
+ *   index; a zero-weight target is skipped, not multiplied in ((-0) + 0 * d would flip a sign bit, and a skipped target costs no
+ *   bandwidth). Per component of every corner:
+ *       p = base position;  for k in active: p = p + w[k] * position delta[k]
+ *       n = base normal;    for k in active: n = n + w[k] * normal delta[k]
+ *   With at least one active target, len = sqrt(dot(n, n)) (st_math.h dot: (x x + y y) + z z); if len is 0 or not finite the normal is
+ *   the base normal as given, else n * (1 / len) (st_math.h normalize). With no active target the triangle is the base triangle, bit
+ *   for bit. uvs are copied. Tangents are not morphed: the device arrays hold none (as for skinning) and tangent deltas are not taken.
+ * - Morph, then skin (glTF's and Bevy's order): if the instance also has a joint pose, the morphed (p, n) replace the bind-pose values
+ *   at the input of the skin stage, which is exactly skinning's blend, position and normal steps; the morphed triangle is never written
+ *   to memory in between. An instance with a pose and no non-zero weight is skinned exactly as without targets.
+ * - Lifecycle (the skin's rules): st_mesh_insert on a morphed handle drops the targets and the weights of every instance of that mesh;
+ *   st_mesh_remove drops the targets. st_mesh_set_morph_targets on a mesh that has targets replaces them and drops those instances'
+ *   weights; their joint poses stay. st_mesh_set_skin keeps weights (it drops poses). st_instance_insert on an existing id keeps its
+ *   weights only if the mesh handle is unchanged; st_instance_remove drops them. Weights NULL / 0, or all exactly zero, on an instance
+ *   without a pose: it returns to the base mesh and its regions of the posed store are freed, as st_instance_set_pose(NULL) does.
+ * - Errors: st_mesh_set_morph_targets returns ST_ERR_INVALID_ARGUMENT for an unknown mesh, a null pointer, a wrong corner_count, a
+ *   target_count outside 1..64, or a delta component that is not finite; a host-only engine accepts targets (host work).
+ *   st_instance_set_morph_weights returns ST_ERR_NO_DEVICE on a host-only engine (there is no CPU morphing) and
+ *   ST_ERR_INVALID_ARGUMENT for an unknown instance, an instance whose mesh has no targets, a target_count other than the mesh's, or a
+ *   weight that is not finite. Negative weights and weights above 1 are valid.
+ * - Deformation motion: a tick that applies changed weights counts as "re-skinned" in the contract above — with the switch on, the
+ *   previous region keeps the positions from before that tick and the velocity formula is the one written there. The one-frame
+ *   exceptions carry over: the first tick that deforms an instance has no previous positions, a tick that returns it to the base shape
+ *   has none either, and the first tick after the switch is turned on only records what it deforms.
+ * - Counters: st_debug_skinning keeps its meaning — ticks and triangles that went through a skin stage, in whichever kernel, at most
+ *   one per tick — and st_debug_morphing counts the morph stage the same way.
+ * - Not here: the glTF loader ignores `targets` as it ignores skins; loading rigged and morphed glTF is a separate piece of work.
+ *   Cost: 72 B of device memory per triangle and target (triangles rounded up to 128 per mesh), sent once when a tick first needs
+ *   them (a one-off upload wait, as for a new skin); per tick and morphed instance 72 B read per triangle and ACTIVE target. */
+typedef struct StMorphDelta { float position[3]; float normal[3]; } StMorphDelta;   /* 24 B */
+/* deltas[k * corner_count + 3 t + v] = target k's displacement of corner v of triangle t of the mesh as given to st_mesh_insert;
+ * corner_count = 3 x its triangles; 1 <= target_count <= 64 */
+int st_mesh_set_morph_targets(StEngine* e, StHandle mesh, const StMorphDelta* deltas, size_t corner_count, uint32_t target_count);
+/* target_count floats; NULL / 0 = back to the base shape */
+int st_instance_set_morph_weights(StEngine* e, StHandle instance, const float* weights, uint32_t target_count);
+/* ticks that ran a morph stage, the triangles morphed, and the bytes of deltas the device store holds (padding included) */
+int st_debug_morphing(StEngine* e, uint64_t* ticks, uint64_t* triangles, uint64_t* delta_bytes);
 
 /* ---- environment lighting (NEW seam): an equirectangular HDR map in place of the procedural atmosphere (k_env.hip, st_env.cpp).
  * - Timing: a change takes effect at the next st_tick, like every scene edit. Frames, scene queries and AOVs before that tick see the old

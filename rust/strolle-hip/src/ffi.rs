@@ -247,6 +247,19 @@ extern "C" {
     pub fn st_debug_deformation(e: *mut StEngine, instances_with_previous: *mut u64, previous_bytes: *mut u64) -> i32;
 }
 
+// ---- morph targets (include/strolle_hip.h "morph targets"): targets per mesh, weights per instance, applied on the device at the next tick
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct StMorphDelta {
+    pub position: [f32; 3],
+    pub normal: [f32; 3],
+}
+extern "C" {
+    pub fn st_mesh_set_morph_targets(e: *mut StEngine, mesh: u64, deltas: *const StMorphDelta, corner_count: usize, target_count: u32) -> i32;
+    pub fn st_instance_set_morph_weights(e: *mut StEngine, instance: u64, weights: *const f32, target_count: u32) -> i32; // null / 0 = the base shape
+    pub fn st_debug_morphing(e: *mut StEngine, ticks: *mut u64, triangles: *mut u64, delta_bytes: *mut u64) -> i32;
+}
+
 // output post-processing (include/strolle_hip.h "post-processing"): FXAA and resampling of a camera's output
 pub const ST_RESAMPLE_NEAREST: u32 = 0;
 pub const ST_RESAMPLE_BILINEAR: u32 = 1;

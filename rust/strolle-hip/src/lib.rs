@@ -356,6 +356,21 @@ where
         check(unsafe { ffi::st_engine_set_deformation_motion(self.raw, enabled as i32) });
     }
 
+    /// Not part of the reference's API: the morph targets of a mesh (glTF `targets`; Bevy's `MorphTargetImage` unpacked). `deltas` holds
+    /// `target_count` runs of one `StMorphDelta` per corner of the mesh as it was inserted (3 per triangle). Replaces earlier targets and
+    /// drops the weights of the mesh's instances.
+    pub fn set_morph_targets(&mut self, handle: P::MeshHandle, deltas: &[ffi::StMorphDelta], target_count: u32) {
+        let corners = if target_count == 0 { 0 } else { deltas.len() / target_count as usize };
+        check(unsafe { ffi::st_mesh_set_morph_targets(self.raw, self.meshes.id(handle), deltas.as_ptr(), corners, target_count) });
+    }
+
+    /// Not part of the reference's API: an instance's morph weights (Bevy's `MorphWeights`, per entity), one per target of its mesh, applied
+    /// on the device at the next `tick` — before its joint pose where it has one. `None` or all zeros: back to the base shape.
+    pub fn set_morph_weights(&mut self, handle: P::InstanceHandle, weights: Option<&[f32]>) {
+        let (ptr, n) = weights.map(|w| (w.as_ptr(), w.len() as u32)).unwrap_or((std::ptr::null(), 0));
+        check(unsafe { ffi::st_instance_set_morph_weights(self.raw, self.instances.id(handle), ptr, n) });
+    }
+
     /// Not part of the reference's API: refit the BVH instead of rebuilding it while instances only move — on the device
     /// (ST_BVH_REFIT_DEVICE = 2: st_tick sends the moved triangles only; same bits as the host refit). `false` goes back to the library's
     /// default (ST_BVH_AUTO = 4: the first tree on the host unless it hangs long leaf runs on large faces (then the device builder's), every later change answered on the device while nothing observes the contract stream).

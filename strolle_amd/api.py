@@ -38,6 +38,14 @@ class StSkinVertex(C.Structure):
 SKIN_VERTEX_DTYPE = np.dtype({"names": ["joints", "weights"], "formats": [(np.uint16, (4,)), (np.float32, (4,))], "offsets": [0, 8], "itemsize": 24})
 
 
+class StMorphDelta(C.Structure):
+    """include/strolle_hip.h "morph targets": one corner's displacement under one target (24 B)."""
+    _fields_ = [("position", C.c_float * 3), ("normal", C.c_float * 3)]
+
+
+MORPH_DELTA_DTYPE = np.dtype({"names": ["position", "normal"], "formats": [(np.float32, (3,)), (np.float32, (3,))], "offsets": [0, 12], "itemsize": 24})
+
+
 class StMaterial(C.Structure):
     _fields_ = [
         ("base_color", C.c_float * 4), ("emissive", C.c_float * 4),
@@ -514,6 +522,10 @@ class _Binding:
             self.bloom_process = fn("bloom_process", [vp, P(StBloomDesc), P(StDisplayDesc), vp, u32, u32, vp, i32, vp])
         if hasattr(lib, prefix + "mesh_set_skin"):
             self.mesh_set_skin = fn("mesh_set_skin", [vp, u64, vp, sz, u32])
+        if hasattr(lib, prefix + "mesh_set_morph_targets"):   # morph targets (likewise absent from an older library)
+            self.mesh_set_morph_targets = fn("mesh_set_morph_targets", [vp, u64, vp, sz, u32])
+            self.instance_set_morph_weights = fn("instance_set_morph_weights", [vp, u64, P(C.c_float), u32])
+            self.debug_morphing = fn("debug_morphing", [vp, P(u64), P(u64), P(u64)])
         if hasattr(lib, prefix + "engine_set_deformation_motion"):   # deformation motion (likewise absent from an older library)
             self.engine_set_deformation_motion = fn("engine_set_deformation_motion", [vp, i32])
             self.engine_get_deformation_motion = fn("engine_get_deformation_motion", [vp, P(i32)])
@@ -601,6 +613,16 @@ class EngineBase:
         corners = np.zeros(len(joints), SKIN_VERTEX_DTYPE)
         corners["joints"] = joints; corners["weights"] = weights
         self._check(self._b.mesh_set_skin(self._h, mesh, corners.ctypes.data if len(corners) else None, len(corners), joint_count))
+
+    def set_morph_targets(self, mesh: int, position_deltas, normal_deltas):
+        """st_mesh_set_morph_targets: position and normal deltas, each (K, n, 3, 3), of K targets over mesh `mesh`'s n triangles (corner v of
+        triangle t of target k at [k, t, v])."""
+        dp = np.asarray(position_deltas, np.float32); dn = np.asarray(normal_deltas, np.float32)
+        if dp.ndim != 4 or dp.shape[2:] != (3, 3) or dn.shape != dp.shape:
+            raise StrolleError("morph deltas: expected two arrays of shape (K, n, 3, 3)")
+        deltas = np.zeros((dp.shape[0], dp.shape[1] * 3), MORPH_DELTA_DTYPE)
+        deltas["position"] = dp.reshape(dp.shape[0], -1, 3); deltas["normal"] = dn.reshape(dp.shape[0], -1, 3)
+        self._check(self._b.mesh_set_morph_targets(self._h, mesh, deltas.ctypes.data if deltas.size else None, deltas.shape[1], deltas.shape[0]))
 
     def insert_material(self, handle: int, material: Material):
         m = material.to_c()
@@ -902,6 +924,19 @@ class Engine(EngineBase):
         m = np.asarray(matrices, np.float32).reshape(-1, 3, 4)
         flat = np.ascontiguousarray(m.transpose(0, 2, 1).reshape(-1), dtype=np.float32)   # per joint: columns x, y, z, t
         self._check(self._b.instance_set_pose(self._h, instance, flat.ctypes.data_as(C.POINTER(C.c_float)), len(m)))
+
+    def set_morph_weights(self, instance: int, weights):
+        """st_instance_set_morph_weights: one weight per target of the instance's mesh, applied at the next tick. None = back to the base shape."""
+        if weights is None:
+            self._check(self._b.instance_set_morph_weights(self._h, instance, None, 0)); return
+        w = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
+        self._check(self._b.instance_set_morph_weights(self._h, instance, w.ctypes.data_as(C.POINTER(C.c_float)), len(w)))
+
+    def morphing_stats(self):
+        """st_debug_morphing: (ticks that ran a morph stage, triangles morphed, bytes of deltas the device store holds)."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self._b.debug_morphing(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def skinning_stats(self):
         """st_debug_skinning: (skin launches, triangles skinned, batched host read-backs of posed triangles)."""

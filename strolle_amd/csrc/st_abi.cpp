@@ -53,11 +53,12 @@ int st_mesh_insert(StEngine* e, StHandle id, const StMeshTriangle* t, size_t cou
     ST_REQUIRE(e && (t || count == 0), "null argument");
     if (count == 0) return fail(ST_ERR_EMPTY_MESH, "mesh contains no triangles");
     E(e)->drop_skin(id);   // skinned meshes: a new mesh drops the skin and the poses of its instances
+    E(e)->drop_morph(id);  // morph targets: likewise the targets and the weights
     E(e)->meshes[id].assign(t, t + count);
     E(e)->mesh_version[id] = E(e)->next_mesh_version++;   // an instance baked from the earlier mesh of this handle is re-baked by the host
     return ST_OK;
 }
-int st_mesh_remove(StEngine* e, StHandle id) { ST_REQUIRE(e, "null engine"); E(e)->drop_skin(id); E(e)->meshes.erase(id); E(e)->mesh_version.erase(id); return ST_OK; }
+int st_mesh_remove(StEngine* e, StHandle id) { ST_REQUIRE(e, "null engine"); E(e)->drop_skin(id); E(e)->drop_morph(id); E(e)->meshes.erase(id); E(e)->mesh_version.erase(id); return ST_OK; }
 
 int st_material_insert(StEngine* e, StHandle id, const StMaterial* m) {
     ST_REQUIRE(e && m, "null argument");
@@ -194,6 +195,19 @@ int st_debug_skinning(StEngine* e, uint64_t* launches, uint64_t* triangles, uint
 int st_debug_read_posed(StEngine* e, StHandle instance, float* out, size_t capacity_floats, size_t* written_floats) {
     ST_REQUIRE(e, "null engine");
     return E(e)->read_posed(instance, out, capacity_floats, written_floats);
+}
+// ---- morph targets (st_skin.cpp)
+int st_mesh_set_morph_targets(StEngine* e, StHandle mesh, const StMorphDelta* deltas, size_t corner_count, uint32_t target_count) {
+    ST_REQUIRE(e, "null engine");
+    return E(e)->set_morph_targets(mesh, deltas, corner_count, target_count);
+}
+int st_instance_set_morph_weights(StEngine* e, StHandle instance, const float* weights, uint32_t target_count) {
+    ST_REQUIRE(e, "null engine");
+    return E(e)->set_morph_weights(instance, weights, target_count);
+}
+int st_debug_morphing(StEngine* e, uint64_t* ticks, uint64_t* triangles, uint64_t* delta_bytes) {
+    ST_REQUIRE(e && ticks && triangles && delta_bytes, "null argument");
+    return E(e)->morphing_stats(ticks, triangles, delta_bytes);
 }
 int st_engine_set_deformation_motion(StEngine* e, int enabled) { ST_REQUIRE(e, "null engine"); E(e)->deform_on = enabled != 0; return ST_OK; }
 int st_engine_get_deformation_motion(StEngine* e, int* enabled) { ST_REQUIRE(e && enabled, "null argument"); *enabled = E(e)->deform_on ? 1 : 0; return ST_OK; }

@@ -449,22 +449,34 @@ struct Engine {
     // the bind mesh), read back only when a host bake needs it. meshes[id] stays the bind pose.
     struct SkinRec { std::vector<StSkinVertex> corners; uint32_t joints = 0; size_t first = SIZE_MAX; };   // first: its triangles in the skin store (SIZE_MAX: not there yet)
     std::unordered_map<uint64_t, SkinRec> skins;
-    struct PoseRec {
-        uint64_t mesh = 0; std::vector<float> palette; size_t first = SIZE_MAX, count = 0;   // first: its region of the posed store (SIZE_MAX: none yet)
-        bool reskin = true;          // the device region has to be (re)computed at the next tick: the pose changed, or the posed store was reallocated
-        bool changed = true;         // the pose changed since the last skin launch (that launch makes the host image stale)
+    // Morph targets (include/strolle_hip.h "morph targets"): a target set per mesh, kept in the device layout (st_kernels.h MorphJob: per target
+    // `padded` triangles of 18 floats as five planes), placed in the target store when a tick first needs it. bind_first: a morph-only mesh's
+    // base triangles in the bind store (no corners there); a mesh that also has a skin uses the skin's range.
+    struct MorphRec { std::vector<float> planes; uint32_t targets = 0; size_t count = 0, padded = 0, first = SIZE_MAX, bind_first = SIZE_MAX; };
+    std::unordered_map<uint64_t, MorphRec> morphs;
+    // A deformation per instance: the last joint palette set (12 floats per joint; empty: none), the last morph weights set (one per target;
+    // empty: none, or all zero), or both — never neither — and the instance's region of the posed store.
+    struct DeformRec {
+        uint64_t mesh = 0; std::vector<float> palette, weights; size_t first = SIZE_MAX, count = 0;   // first: its region of the posed store (SIZE_MAX: none yet)
+        bool reskin = true;          // the device region has to be (re)computed at the next tick: the pose or the weights changed, or the posed store was reallocated
+        bool changed = true;         // they changed since the last launch (that launch makes the host image stale)
         bool host_current = false;   // `host` holds what the device region holds
         std::vector<StMeshTriangle> host;
-        // deformation motion (below): `other` is the pose's second region — a re-skin writes it and swaps it with `first`, so that it then holds the
-        // positions from before that tick; has_previous says the LAST tick did so. `skinned` / `previous` are the palettes the two regions were skinned
-        // with (a posed store that grows re-skins both into the new allocation). All empty while the switch is off.
-        size_t other = SIZE_MAX; bool has_previous = false;
-        std::vector<float> skinned, previous;
+        // deformation motion (below): `other` is the second region — a tick that deforms again writes it and swaps it with `first`, so that it then
+        // holds the positions from before that tick; has_previous says the LAST tick did so. `skinned` / `previous` (+ `_w`) are the palettes and
+        // weights the two regions were computed with (a posed store that grows computes both again into the new allocation); `recorded`: `first`
+        // holds what a tick deformed while the switch was on. All empty / false while the switch is off.
+        size_t other = SIZE_MAX; bool has_previous = false, recorded = false;
+        std::vector<float> skinned, previous, skinned_w, previous_w;
     };
-    std::unordered_map<uint64_t, PoseRec> poses;
+    std::unordered_map<uint64_t, DeformRec> poses;
     // the skin store's host image; ranges of dropped skins go back to skin_free and are reused
     std::vector<float> skin_bind_host; std::vector<StSkinVertex> skin_corner_host; SlotRanges skin_free;
     DeviceArray d_skin_bind, d_skin_corners, d_posed, d_skin_jobs, d_skin_starts, d_palettes;
+    // the target store, in units of 18 floats (its host image is the MorphRecs' planes), and the tick's morph jobs
+    DeviceArray d_morph_targets, d_morph_jobs, d_morph_starts, d_morph_active;
+    SlotRanges morph_free; size_t morph_size = 0;
+    uint64_t morph_ticks = 0, morphed_triangles = 0;
     SlotRanges posed_free; size_t posed_size = 0;   // triangles of the posed store handed out (its allocation holds at least that many)
     Stream skin_stream; Event ev_skinned;
     Fence posed_read;   // behind the bakes that read the posed regions (bake_on_device), on whichever streams: the next skin launch overwrites them
@@ -485,9 +497,16 @@ struct Engine {
     int set_skin(uint64_t mesh, const StSkinVertex* corners, size_t corner_count, uint32_t joint_count);
     int set_pose(uint64_t instance, const float* joint_xforms, uint32_t joint_count);
     int read_posed(uint64_t instance, float* out, size_t capacity_floats, size_t* written_floats);
-    void drop_pose(uint64_t instance, bool make_dirty);
+    int set_morph_targets(uint64_t mesh, const StMorphDelta* deltas, size_t corner_count, uint32_t target_count);
+    int set_morph_weights(uint64_t instance, const float* weights, uint32_t target_count);
+    int morphing_stats(uint64_t* ticks, uint64_t* triangles, uint64_t* delta_bytes) const;
+    void drop_pose(uint64_t instance, bool make_dirty);   // the whole deformation: palette, weights and regions
+    // one part of it; the deformation itself goes when nothing is left. forget: what the part was made for is gone (a skin or target set replaced):
+    // the previous positions and what they were computed from go too
+    void drop_part(uint64_t instance, bool palette, bool weights, bool forget);
     void drop_skin(uint64_t mesh);    // and the poses of the instances of that mesh
-    int skin_tick(hipStream_t stream);   // st_tick, before the refresh: one launch for every pose to (re)compute
+    void drop_morph(uint64_t mesh);   // and the weights of the instances of that mesh
+    int skin_tick(hipStream_t stream);   // st_tick, before the refresh: one launch of each kernel at most for every deformation to (re)compute
     int read_back_posed();            // host images of every posed region they lag behind: one batch, one synchronisation
     int deferred_status = ST_OK;      // a read-back that failed inside a refresh or bake_stale_on_host (message in g_last_error): st_tick / st_debug_read_scene return it
     int take_deferred_status() { const int rc = deferred_status; deferred_status = ST_OK; return rc; }

@@ -84,6 +84,18 @@ struct SkinJob { uint32_t skin_first, count, posed_first, palette_first, joint_c
 static_assert(sizeof(SkinJob) == 32, "one skin job is 32 B");
 void launch_skin(const SkinJob* jobs, const uint32_t* job_start, uint32_t n_jobs, uint32_t padded_total, const float* bind, const void* corners,
                  const float* palettes, float* posed, hipStream_t s);
+// Morph targets (k_skin.hip k_morph; include/strolle_hip.h "morph targets"): the jobs with at least one active target, the skin stage behind
+// the morph stage when joint_count is not 0 (skin_first then names the skin's corners too; without a skin it names bind triangles only).
+// The target store is counted in units of 18 floats (one triangle of one target): target k of a mesh lies at unit target_first + k * padded,
+// `padded` being the mesh's triangles rounded up to kSkinBlock, as four planes of float4 and one of float2 (floats 4q .. 4q + 3 and 16, 17 of
+// each triangle's 18: position deltas 9, normal deltas 9), so that a wave's load for one target is one contiguous run. active_first /
+// active_count: the job's non-zero weights with their target indices, ascending, in the tick's MorphActive list.
+struct MorphJob { uint32_t skin_first, count, posed_first, palette_first, joint_count, target_first, padded, active_first, active_count, pad[3]; };
+static_assert(sizeof(MorphJob) == 48, "one morph job is 48 B");
+struct MorphActive { uint32_t target; float weight; };
+constexpr uint32_t kMorphMaxTargets = 64u, kMorphUnitFloats = 18u;
+void launch_morph(const MorphJob* jobs, const uint32_t* job_start, uint32_t n_jobs, uint32_t padded_total, const float* bind, const void* corners,
+                  const float* palettes, const float* targets, const MorphActive* active, float* posed, hipStream_t s);
 
 // The launchers exist twice, in namespaces st::exact and st::fast (the two arithmetic builds of the kernel files, Makefile);
 // the engine calls them through a table picked per engine (st_engine_set_arithmetic).

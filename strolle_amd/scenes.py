@@ -293,3 +293,30 @@ def bend_pose(joints: int, angle: float, phase: float = 0.0, length: float = 2.0
         world = world @ rz(angle / max(joints - 1, 1) * math.sin(phase + 0.5 * k))
         out.append((world @ ty(-k * seg))[:3, :4])
     return np.asarray(out, np.float32)
+
+
+def tube_morph_targets(mesh: Mesh, radius: float = 0.25, length: float = 2.0, amount: float = 0.5):
+    """Three analytic morph targets for skinned_tube's mesh (include/strolle_hip.h "morph targets"), each with the normal deltas of its
+    displaced surface: a bulge (the radius grows by `amount` x sin(pi y / length)), a twist (a turn about the axis of `amount` x pi y / length)
+    and a taper (the radius shrinks linearly to 1 - `amount` at the far end). Returns (position deltas, normal deltas), each (3, n, 3, 3)
+    float32 — Engine.set_morph_targets' arguments."""
+    p = mesh.positions.astype(np.float64); n0 = mesh.normals.astype(np.float64)
+    y = p[..., 1]; t = y / length
+    radial = np.stack([n0[..., 0], np.zeros_like(y), n0[..., 2]], -1)       # unit, horizontal
+    axis = np.zeros_like(p); axis[..., 1] = 1.0
+
+    def surface(scale, dscale_dy, turn):
+        """The tube with radius x scale(y), turned by turn(y) about +y: positions and unit normals."""
+        c, s = np.cos(turn), np.sin(turn)
+        r = np.stack([c * radial[..., 0] - s * radial[..., 2], np.zeros_like(y), s * radial[..., 0] + c * radial[..., 2]], -1)
+        pos = r * (radius * scale)[..., None] + axis * y[..., None]
+        nrm = r - axis * (radius * dscale_dy)[..., None]                    # a surface of revolution r(y): normal (1, -dr/dy) in (radial, axis)
+        return pos, nrm / np.linalg.norm(nrm, axis=-1, keepdims=True)
+
+    zero = np.zeros_like(y)
+    shapes = [surface(1.0 + amount * np.sin(math.pi * t), amount * math.pi / length * np.cos(math.pi * t), zero),
+              surface(1.0 + zero, zero, amount * math.pi * t),
+              surface(1.0 - amount * t, zero - amount / length, zero)]
+    dp = np.stack([q - p for q, _ in shapes]).astype(np.float32)
+    dn = np.stack([m - n0 for _, m in shapes]).astype(np.float32)
+    return dp, dn
