@@ -773,7 +773,7 @@ typedef struct StTuning {
     uint32_t packed_base;           /* per-material packed base colour (0: primary visibility packs it per pixel) */
     uint32_t tick_timing;           /* 1: host-side cost of a scene refresh on stderr */
     uint32_t anyhit_fast;           /* fast build: shadow rays (boolean result only, ray.rs:84-112) walk with fast arithmetic
-                                     * (st_device.h any_hit_fast); 0: the contract loop. Always 0 while traversal bytes are counted */
+                                     * (st_traverse.h any_hit_fast); 0: the contract loop. Always 0 while traversal bytes are counted */
     uint32_t compact_bvh;           /* fast build: shadow rays walk a second, compact form of the BVH stream (48-B entries with conservative f16 child
                                      * boxes, regenerated on the device after every change: k_bvh.hip k_bvh_compact) — 2 / 3 texels per step instead of 4 */
     uint32_t allow_deep_bvh;        /* 1: a tree deeper than the traversal stack is a warning on stderr, not ST_ERR_BVH_TOO_DEEP */
@@ -784,7 +784,7 @@ typedef struct StTuning {
                                      * the device refills the boxes after every change) — half the dependent round trips and lines of the compact binary stream */
     uint32_t wide_stack_entries;    /* pending entries per ray of the wide walk's stack: 0 = 24 (strolle-gpu/src/lib.rs:76); tests render with 48 to show that 24 drops no push */
     uint32_t primary_packets;       /* with the wide stream: primary visibility walks it as ONE packet per wave — uniform node pointer and stack, scalar node
-                                     * fetches, per-lane box and triangle tests, ballots decide the descent (st_device.h closest_hit_packet) */
+                                     * fetches, per-lane box and triangle tests, ballots decide the descent (st_traverse.h closest_hit_packet) */
 } StTuning;
 int st_engine_get_tuning(StEngine* e, StTuning* out);
 int st_engine_set_tuning(StEngine* e, const StTuning* tuning);

@@ -18,16 +18,10 @@ __global__ ST_KERNEL_BOUNDS void k_aov(const KArgs a_in, float* depth, float4* n
     U2 pos;
     if (!resolve_gid(a, false, &pos) || !owns_pixel(a, pos)) return;
     const Ray ray = camera_ray(a.cam, pos);
-    Candidate c; candidate_none(&c);
-    bool any = false;
-#if ST_FAST_DEVICE && !defined(ST_NO_ANYHIT_FAST)
-    if (!LDS_SCENE && a.bvh_w != nullptr && a.primary_packets) any = closest_hit_packet(a, ray, &c);   // the tile's 64 rays as one packet
-    else if (a.bvh_w != nullptr) any = closest_hit_wide<SE, true>(a, ray, lane_stack(a, lds), &c);
-    else if (a.bvh_c != nullptr) any = closest_hit_compact(a, ray, lane_stack(a, lds), &c);
-    else (void)traverse<false>(a, ray, kF32Max, lane_stack(a, lds), &c, &any);
-#else
-    (void)traverse<false>(a, ray, kF32Max, lane_stack(a, lds), &c, &any);
-#endif
+    Candidate c; candidate_reset(&c, kF32Max);
+    bool any = false; uint32_t used = 0u;   // used: the contract walk's byte count, not reported here
+    // primary visibility's walk: exact leaf test, the tile's 64 rays as one packet where the frame's are; ablatable, as the pick is
+    ST_CLOSEST_WALK(true, true, a, ray, lane_stack(a, lds), !LDS_SCENE && a.bvh_w != nullptr && a.primary_packets, &c, any, used);
     const TriangleHit h = closest_resolve(a, ray, c, any);
     const size_t i = (size_t)pos.y * a.width + pos.x;
     if (depth) depth[i] = any ? distance(ray.origin, h.point) : kF32Max;   // the G-buffer's d0.x (k_prim_visibility g.depth)
@@ -61,7 +55,7 @@ __global__ ST_KERNEL_BOUNDS void k_aov(const KArgs a_in, float* depth, float4* n
 
 void launch_aov(const KArgs& a, float* depth, float4* normal, float4* albedo, float2* motion, uint64_t* instance, uint32_t* triangle, const uint4* table,
                 const float* deform_posed, hipStream_t s) {
-    ST_LAUNCH_TRACE(k_aov, false, s, a, depth, normal, albedo, motion, instance, triangle, table, deform_posed);
+    ST_LAUNCH_TRACE(k_aov, (), false, s, a, depth, normal, albedo, motion, instance, triangle, table, deform_posed);
 }
 
 }  // namespace ST_KNS

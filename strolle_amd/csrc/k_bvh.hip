@@ -129,7 +129,7 @@ void launch_bvh_bake(const void* jobs, const uint32_t* job_start, uint32_t n_job
     if (total) ST_KLAUNCH(k_bvh_bake, dim3((total + 255u) / 256u), dim3(256), s, static_cast<const BakeJobDevice*>(jobs), job_start, n_jobs, total, mesh, posed, tri_geo, tri_bounds, tri_attr, bvh, entry_of_tri);
 }
 
-// ---- the COMPACT stream the fast build's shadow rays walk (st_device.h any_hit_compact; StTuning::compact_bvh).
+// ---- the COMPACT stream the fast build's shadow rays walk (st_traverse.h any_hit_compact; StTuning::compact_bvh).
 // Measured (round 4, ST_EXP probes on the dungeon): one more 64-B line fetched per traversal step — same round trip, no arithmetic —
 // takes `di_sampling+di_temporal` from 194 to 280 us, tripling the box arithmetic only to 233: the loop is bound by what the
 // texture-address path has to serve per step more than by VALU issue. A shadow ray's answer is one boolean, so it may walk
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void k_bvh_compact(const float4* bvh, uint32_t
     auto dn = [](float x) { return (uint32_t)__half_as_ushort(__float2half_rd(x)); };
     auto up = [](float x) { return (uint32_t)__half_as_ushort(__float2half_ru(x)); };
     uint4 t0, t1;
-    // a word per axis and box: (lower bound | upper bound << 16) — st_device.h compact_slab picks the entry plane by rotating the word
+    // a word per axis and box: (lower bound | upper bound << 16) — st_traverse.h compact_slab picks the entry plane by rotating the word
     t0.x = dn(d0.x) | (up(d1.x) << 16); t0.y = dn(d0.y) | (up(d1.y) << 16); t0.z = dn(d0.z) | (up(d1.z) << 16); t0.w = dn(d2.x) | (up(d3.x) << 16);
     t1.x = dn(d2.y) | (up(d3.y) << 16); t1.y = dn(d2.z) | (up(d3.z) << 16); t1.z = (far_entry << 2) | (right_leaf << 1) | left_leaf; t1.w = 0u;
     out[3u * k] = make_float4(b2f(t0.x), b2f(t0.y), b2f(t0.z), b2f(t0.w));
@@ -170,7 +170,7 @@ void launch_bvh_compact(const float4* bvh, uint32_t n_entries, float4* out, hipS
     if (n_entries) ST_KLAUNCH(k_bvh_compact, dim3((n_entries + 255u) / 256u), dim3(256), s, bvh, n_entries, out);
 }
 
-// ---- the WIDE stream (st_device.h any_hit_wide / closest_hit_wide; StTuning::wide_bvh): 4-wide nodes whose child boxes are the contract
+// ---- the WIDE stream (st_traverse.h any_hit_wide / closest_hit_wide; StTuning::wide_bvh): 4-wide nodes whose child boxes are the contract
 // stream's own, read from the device copy as it is NOW (after an upload, leaf patch, device bake or refit), rounded outwards to f16.
 // The topology — which binary nodes were collapsed into which wide node — is the host's (st_bvh_refresh.cpp build_wide_topology, once per
 // build of the tree): topo[8 n + c] = where child c's box lives in the contract stream (entry << 1 | 0: left box, 1: right box; ~0: empty

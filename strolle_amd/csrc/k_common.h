@@ -92,6 +92,8 @@ inline bool scene_fits_lds(const KArgs& a) { return a.bvh_len > 0u && a.bvh_len 
 // ... and every tracing kernel stages the head of the light table in LDS (kLdsLights x 112 B = 1.75 KB per block): RIS over the lights
 // (reservoir/ephemeral.rs:14-55: up to 16 picks per pixel, each a 112-B fetch at a per-lane random index) and the resampling passes'
 // per-sample light look-ups then read LDS instead of going through the texture-address path. Lights beyond kLdsLights keep the global table.
+// (Written out, not built on ST_QUERY_PROLOGUE below: as that one plus the light table, the single barrier moves and 118 tracing kernels' code changes —
+// compared in assembly.)
 #define ST_SCENE_PROLOGUE                                                                                                        \
     __shared__ float4 s_scene_bvh_[LDS_SCENE ? kLdsSceneTexels : 1];                                                             \
     __shared__ GpuLight s_lights_[kLdsLights];                                                                                   \
@@ -105,7 +107,7 @@ inline bool scene_fits_lds(const KArgs& a) { return a.bvh_len > 0u && a.bvh_len 
         a.lights_lds = s_lights_;                                                                                                \
         if (LDS_SCENE) a.bvh = s_scene_bvh_;                                                                                     \
     }
-// ST_SCENE_PROLOGUE without the light table: the scene queries and the AOVs (k_query.hip, k_aov.hip), which read no light
+// ST_SCENE_PROLOGUE without the light table: the scene queries and the AOVs (k_query.hip, k_aov.hip), which read no light.
 #define ST_QUERY_PROLOGUE                                                                                            \
     __shared__ float4 s_scene_bvh_[LDS_SCENE ? kLdsSceneTexels : 1];                                                 \
     KArgs a = a_in;                                                                                                  \
@@ -114,8 +116,6 @@ inline bool scene_fits_lds(const KArgs& a) { return a.bvh_len > 0u && a.bvh_len 
         __syncthreads();                                                                                             \
         a.bvh = s_scene_bvh_;                                                                                        \
     }
-// the empty closest-hit candidate the queries and the AOVs start their walks from
-ST_D void candidate_none(Candidate* c) { c->t = kF32Max; c->tri = 0xffffffffu; c->material = 0u; c->u = 0.0f; c->v = 0.0f; c->inv_det = 1.0f; }
 // For a kernel that decodes MANY G-buffer texels per lane (GI spatial resampling: every candidate neighbour's): the byte tables of the
 // decode (st_device.h kLut*, 4 KB) staged in LDS as well — seven per-lane table reads per decoded texel leave the texture-address path
 // (dungeon gi_spatial_fused 366 -> 335 us; in the kernels that decode one pixel the staging costs what it saves, measured).
@@ -125,30 +125,15 @@ ST_D void candidate_none(Candidate* c) { c->t = kF32Max; c->tri = 0xffffffffu; c
         reinterpret_cast<float4*>(s_byte_luts_)[i_] = reinterpret_cast<const float4*>(a_in.byte_luts)[i_];                       \
     ST_SCENE_PROLOGUE                                                                                                            \
     a.byte_luts = s_byte_luts_;
-#define ST_LAUNCH_TRACE(kernel_tmpl, half, stream, ...)                                                             \
-    do {                                                                                                            \
-        if (scene_fits_lds(a)) ST_LAUNCH_SMEM(ST_TPL2(kernel_tmpl, true, uint16_t), half, stack_lds_bytes(a, 2), stream, __VA_ARGS__);          \
-        else if (a.bvh_len < stack16_limit(a)) ST_LAUNCH_SMEM(ST_TPL2(kernel_tmpl, false, uint16_t), half, stack_lds_bytes(a, 2), stream, __VA_ARGS__);   \
-        else ST_LAUNCH_SMEM(ST_TPL2(kernel_tmpl, false, uint32_t), half, stack_lds_bytes(a, 4), stream, __VA_ARGS__);                           \
+// `flags`: the kernel template's bool arguments between LDS_SCENE and SE, as a parenthesised list — (), (REPROJECT), (REPROJECT, ENV)
+#define ST_TRACE_FLAGS_(...) , ##__VA_ARGS__   // GNU comma swallowing for the empty list: hipcc is clang, which has it at every -std (__VA_OPT__ is C++20)
+#define ST_TRACE_KERNEL_(k, lds, flags, se) (k<lds ST_TRACE_FLAGS_ flags, se>)
+#define ST_LAUNCH_TRACE(kernel_tmpl, flags, half, stream, ...)                                                                                                      \
+    do {                                                                                                                                                            \
+        if (scene_fits_lds(a)) ST_LAUNCH_SMEM(ST_TRACE_KERNEL_(kernel_tmpl, true, flags, uint16_t), half, stack_lds_bytes(a, 2), stream, __VA_ARGS__);              \
+        else if (a.bvh_len < stack16_limit(a)) ST_LAUNCH_SMEM(ST_TRACE_KERNEL_(kernel_tmpl, false, flags, uint16_t), half, stack_lds_bytes(a, 2), stream, __VA_ARGS__); \
+        else ST_LAUNCH_SMEM(ST_TRACE_KERNEL_(kernel_tmpl, false, flags, uint32_t), half, stack_lds_bytes(a, 4), stream, __VA_ARGS__);                               \
     } while (0)
-// the same for kernels with one more leading bool (REPROJECT)
-#define ST_LAUNCH_TRACE_B(kernel_tmpl, flag, half, stream, ...)                                                         \
-    do {                                                                                                                \
-        if (scene_fits_lds(a)) ST_LAUNCH_SMEM(ST_TPL3(kernel_tmpl, true, flag, uint16_t), half, stack_lds_bytes(a, 2), stream, __VA_ARGS__);        \
-        else if (a.bvh_len < stack16_limit(a)) ST_LAUNCH_SMEM(ST_TPL3(kernel_tmpl, false, flag, uint16_t), half, stack_lds_bytes(a, 2), stream, __VA_ARGS__); \
-        else ST_LAUNCH_SMEM(ST_TPL3(kernel_tmpl, false, flag, uint32_t), half, stack_lds_bytes(a, 4), stream, __VA_ARGS__);                         \
-    } while (0)
-// ... and with two (k_di_resolving: REPROJECT, and ENV = an environment map is set)
-#define ST_LAUNCH_TRACE_BB(kernel_tmpl, flag, flag2, half, stream, ...)                                                 \
-    do {                                                                                                                \
-        if (scene_fits_lds(a)) ST_LAUNCH_SMEM(ST_TPL4(kernel_tmpl, true, flag, flag2, uint16_t), half, stack_lds_bytes(a, 2), stream, __VA_ARGS__);        \
-        else if (a.bvh_len < stack16_limit(a)) ST_LAUNCH_SMEM(ST_TPL4(kernel_tmpl, false, flag, flag2, uint16_t), half, stack_lds_bytes(a, 2), stream, __VA_ARGS__); \
-        else ST_LAUNCH_SMEM(ST_TPL4(kernel_tmpl, false, flag, flag2, uint32_t), half, stack_lds_bytes(a, 4), stream, __VA_ARGS__);                         \
-    } while (0)
-#define ST_TPL(k, t) k<t>
-#define ST_TPL4(k, b, c, d, t) (k<b, c, d, t>)
-#define ST_TPL2(k, b, t) (k<b, t>)
-#define ST_TPL3(k, b, c, t) (k<b, c, t>)
 
 #define ST_LAUNCH_SMEM(kernel, half, smem, stream, ...)                                                          \
     do {                                                                                                         \

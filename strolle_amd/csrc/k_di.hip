@@ -19,7 +19,7 @@ __global__ ST_KERNEL_BOUNDS void k_di_sampling(const KArgs a_in, uint32_t seed) 
     if (!hit_some(hit)) return;
     di_write(a.di_res[1], screen_to_idx(a, pos), di_sampling_pixel(a, seed, pos, hit, lane_stack(a, lds)));
 }
-void launch_di_sampling(const KArgs& a, uint32_t seed, hipStream_t s) { ST_LAUNCH_TRACE(k_di_sampling, false, s, a, seed); }
+void launch_di_sampling(const KArgs& a, uint32_t seed, hipStream_t s) { ST_LAUNCH_TRACE(k_di_sampling, (), false, s, a, seed); }
 
 // ---------------------------------------------------------------- di_temporal_resampling.rs:3-112
 __global__ ST_KERNEL_BOUNDS void k_di_temporal(const KArgs a, uint32_t seed) {
@@ -45,7 +45,7 @@ __global__ ST_KERNEL_BOUNDS void k_di_sampling_temporal(const KArgs a_in, uint32
     di_temporal_pixel(a, seed_temporal, pos, hit, di_after_store(di_sampling_pixel(a, seed_sampling, pos, hit, lane_stack(a, lds))), tex_read(a.reprojection, a, pos));
 }
 void launch_di_sampling_temporal(const KArgs& a, uint32_t seed_sampling, uint32_t seed_temporal, hipStream_t s) {
-    ST_LAUNCH_TRACE(k_di_sampling_temporal, false, s, a, seed_sampling, seed_temporal);
+    ST_LAUNCH_TRACE(k_di_sampling_temporal, (), false, s, a, seed_sampling, seed_temporal);
 }
 
 // ---------------------------------------------------------------- di_spatial_resampling.rs:3-147 (pick)
@@ -183,7 +183,7 @@ __global__ ST_KERNEL_BOUNDS void k_di_spatial_fused(const KArgs a_in, uint32_t s
     if (own_lhs) di_spatial_sample_cell(a, seed_sample, gid, lhs_pos, vis[0], vis[1]);
 }
 void launch_di_spatial_fused(const KArgs& a, uint32_t seed_pick, uint32_t seed_sample, hipStream_t s) {
-    ST_LAUNCH_TRACE(k_di_spatial_fused, true, s, a, seed_pick, seed_sample);
+    ST_LAUNCH_TRACE(k_di_spatial_fused, (), true, s, a, seed_pick, seed_sample);
 }
 void launch_di_spatial_sample(const KArgs& a, uint32_t seed, hipStream_t s) { ST_LAUNCH(k_di_spatial_sample, true, s, a, seed); }
 
@@ -235,9 +235,9 @@ __global__ ST_KERNEL_BOUNDS void k_di_resolving(const KArgs a_in) {
 }
 void launch_di_resolving(const KArgs& a, bool reproject, hipStream_t s) {
     if (a.env_map) {
-        if (reproject) ST_LAUNCH_TRACE_BB(k_di_resolving, true, true, false, s, a); else ST_LAUNCH_TRACE_BB(k_di_resolving, false, true, false, s, a);
+        if (reproject) ST_LAUNCH_TRACE(k_di_resolving, (true, true), false, s, a); else ST_LAUNCH_TRACE(k_di_resolving, (false, true), false, s, a);
     } else {
-        if (reproject) ST_LAUNCH_TRACE_BB(k_di_resolving, true, false, false, s, a); else ST_LAUNCH_TRACE_BB(k_di_resolving, false, false, false, s, a);
+        if (reproject) ST_LAUNCH_TRACE(k_di_resolving, (true, false), false, s, a); else ST_LAUNCH_TRACE(k_di_resolving, (false, false), false, s, a);
     }
 }
 

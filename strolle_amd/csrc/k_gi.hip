@@ -124,7 +124,7 @@ __global__ ST_KERNEL_BOUNDS void k_gi_sampling_a(const KArgs a_in, uint32_t seed
     tex_write(a.gi_d2, a, gid, d2);
 }
 void launch_gi_sampling_a(const KArgs& a, uint32_t seed, hipStream_t s) {
-    if (a.env_map) ST_LAUNCH_TRACE_B(k_gi_sampling_a, true, true, s, a, seed); else ST_LAUNCH_TRACE_B(k_gi_sampling_a, false, true, s, a, seed);
+    if (a.env_map) ST_LAUNCH_TRACE(k_gi_sampling_a, (true), true, s, a, seed); else ST_LAUNCH_TRACE(k_gi_sampling_a, (false), true, s, a, seed);
 }
 
 // ---------------------------------------------------------------- gi_sampling_b.rs:3-235
@@ -220,7 +220,7 @@ __global__ ST_KERNEL_BOUNDS void k_gi_sampling_b(const KArgs a_in, uint32_t seed
     gi_sampling_b_cell<ENV>(a, seed, tracing, pos, prim_hit, vres, lane_stack(a, lds), &used_, d0, d1, d2);
 }
 void launch_gi_sampling_b(const KArgs& a, uint32_t seed, hipStream_t s) {
-    if (a.env_map) ST_LAUNCH_TRACE_B(k_gi_sampling_b, true, true, s, a, seed); else ST_LAUNCH_TRACE_B(k_gi_sampling_b, false, true, s, a, seed);
+    if (a.env_map) ST_LAUNCH_TRACE(k_gi_sampling_b, (true), true, s, a, seed); else ST_LAUNCH_TRACE(k_gi_sampling_b, (false), true, s, a, seed);
 }
 
 // Both sampling passes of a cell in one launch: pass b takes pass a's three texels from registers (they are still stored:
@@ -262,8 +262,8 @@ __global__ __launch_bounds__(kBlockThreads, 6) void k_gi_sampling_ab(const KArgs
     gi_sampling_b_cell<ENV>(a, seed_b, tracing, pos, prim_hit, vres, lane_stack(a, lds), &used_, d0, d1, d2);
 }
 void launch_gi_sampling_ab(const KArgs& a, uint32_t seed_a, uint32_t seed_b, bool reproject, hipStream_t s) {
-    if (a.env_map) ST_LAUNCH_TRACE_B(k_gi_sampling_ab, true, true, s, a, seed_a, seed_b, reproject ? 1u : 0u);
-    else ST_LAUNCH_TRACE_B(k_gi_sampling_ab, false, true, s, a, seed_a, seed_b, reproject ? 1u : 0u);
+    if (a.env_map) ST_LAUNCH_TRACE(k_gi_sampling_ab, (true), true, s, a, seed_a, seed_b, reproject ? 1u : 0u);
+    else ST_LAUNCH_TRACE(k_gi_sampling_ab, (false), true, s, a, seed_a, seed_b, reproject ? 1u : 0u);
 }
 
 // ---------------------------------------------------------------- gi_temporal_resampling.rs:3-156
@@ -504,7 +504,7 @@ __global__ __launch_bounds__(kBlockThreads, 5) void k_gi_spatial_fused(const KAr
     if (own_lhs) gi_spatial_sample_cell(a, seed_sample, gid, lhs_pos, vis[0], vis[1]);
 }
 void launch_gi_spatial_fused(const KArgs& a, uint32_t seed_pick, uint32_t seed_sample, hipStream_t s) {
-    ST_LAUNCH_TRACE(k_gi_spatial_fused, true, s, a, seed_pick, seed_sample);
+    ST_LAUNCH_TRACE(k_gi_spatial_fused, (), true, s, a, seed_pick, seed_sample);
 }
 
 // ---------------------------------------------------------------- gi_preview_resampling.rs:3-138

@@ -3,7 +3,7 @@
 // The reference rebuilds its binned-SAH tree on the host whenever an instance appears or disappears (strolle/src/bvh/builder.rs:17-228,
 // bevy-strolle/examples/stress-bvh.rs:111-167); this library's host builder is the same tree bit for bit (st_bvh.h: that is what makes the
 // heatmap's `used_memory` integers the reference's) and costs 26-28 ms per spawn at 208 k triangles. The fast build's rays do not need THAT
-// tree — they owe the reference their hits, not their path (st_device.h closest_hit_wide) — so while no camera observes the contract stream
+// tree — they owe the reference their hits, not their path (st_traverse.h closest_hit_wide) — so while no camera observes the contract stream
 // (no heatmap camera, fast arithmetic, no byte counting) a scene change is followed by this builder instead:
 //
 //   1. centroid bounds of the live triangle slots                                   k_lbvh_bounds      (wave, then workgroup reduction: one ordered-int atomic pair per workgroup)

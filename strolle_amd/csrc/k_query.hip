@@ -39,17 +39,11 @@ __global__ ST_KERNEL_BOUNDS void k_query_closest(const KArgs a_in, const float4*
     if (i >= count) return;
     Ray ray;
     const bool valid = query_ray(rays, i, &ray);
-    Candidate c; candidate_none(&c);
-    bool any = false;
+    Candidate c; candidate_reset(&c, kF32Max);
+    bool any = false; uint32_t used = 0u;   // used: the contract walk's byte count, not reported here
     if (valid) {
-#if ST_FAST_DEVICE
-        if (!LDS_SCENE && packets && a.bvh_w != nullptr) any = closest_hit_packet(a, ray, &c);
-        else if (a.bvh_w != nullptr) any = closest_hit_wide<SE, true>(a, ray, lane_stack(a, lds), &c);
-        else if (a.bvh_c != nullptr) any = closest_hit_compact(a, ray, lane_stack(a, lds), &c);
-        else (void)traverse<false>(a, ray, kF32Max, lane_stack(a, lds), &c, &any);
-#else
-        (void)traverse<false>(a, ray, kF32Max, lane_stack(a, lds), &c, &any);
-#endif
+        // exact leaf test: t carries the contract walk's bits. Not ablatable: the ablation build is about the frame's rays. Packets: the caller's flag (ST_RAY_COHERENT), not the frame's tuning
+        ST_CLOSEST_WALK(true, false, a, ray, lane_stack(a, lds), !LDS_SCENE && packets && a.bvh_w != nullptr, &c, any, used);
     }
     const bool hit = any && c.t < ray.len;
     store_hit(hits, i, closest_resolve(a, ray, c, hit), c, hit, table);
@@ -81,17 +75,11 @@ __global__ ST_KERNEL_BOUNDS void k_query_pick(const KArgs a_in, const uint32_t* 
     if (i >= count) return;
     const uint32_t x = pixels[2 * (size_t)i], y = pixels[2 * (size_t)i + 1];
     const Ray ray = camera_ray(a.cam, u2(x, y));
-    Candidate c; candidate_none(&c);
-    bool any = false;
+    Candidate c; candidate_reset(&c, kF32Max);
+    bool any = false; uint32_t used = 0u;   // used: the contract walk's byte count, not reported here
     if (x < a.width && y < a.height) {
-#if ST_FAST_DEVICE && !defined(ST_NO_ANYHIT_FAST)
-        if (!LDS_SCENE && a.bvh_w != nullptr && a.primary_packets) any = closest_hit_packet(a, ray, &c);
-        else if (a.bvh_w != nullptr) any = closest_hit_wide(a, ray, lane_stack(a, lds), &c);
-        else if (a.bvh_c != nullptr) any = closest_hit_compact(a, ray, lane_stack(a, lds), &c);
-        else (void)traverse<false>(a, ray, kF32Max, lane_stack(a, lds), &c, &any);
-#else
-        (void)traverse<false>(a, ray, kF32Max, lane_stack(a, lds), &c, &any);
-#endif
+        // k_ref_tracing's depth 0, whose bits a pick owes: trace_closest's fast leaf test and ablation switch, the packet where the frame's primary rays take it
+        ST_CLOSEST_WALK(false, true, a, ray, lane_stack(a, lds), !LDS_SCENE && a.bvh_w != nullptr && a.primary_packets, &c, any, used);
     }
     store_hit(hits, i, closest_resolve(a, ray, c, any), c, any, table);
 }

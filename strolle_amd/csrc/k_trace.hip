@@ -38,7 +38,7 @@ __global__ ST_KERNEL_BOUNDS void k_bvh_heatmap(const KArgs a_in) {
     a.dbg_used_memory[screen_to_idx(a, pos)] = used;
     tex_write(a.ref_colors, a, pos, f4(heatmap_gradient((float)used / 8192.0f), 1.0f));
 }
-void launch_bvh_heatmap(const KArgs& a, hipStream_t s) { ST_LAUNCH_TRACE(k_bvh_heatmap, false, s, a); }
+void launch_bvh_heatmap(const KArgs& a, hipStream_t s) { ST_LAUNCH_TRACE(k_bvh_heatmap, (), false, s, a); }
 
 // ---------------------------------------------------------------- ref_tracing.rs:3-60
 template <bool LDS_SCENE, class SE>
@@ -70,7 +70,7 @@ __global__ ST_KERNEL_BOUNDS void k_ref_tracing(const KArgs a_in, uint32_t depth)
     hit_pack(hit, &h0, &h1);
     rec2_write_own(a.ref_hits, idx, h0, h1, true, true);  // quad-transposed 32-B records (st_device.h)
 }
-void launch_ref_tracing(const KArgs& a, uint32_t depth, hipStream_t s) { ST_LAUNCH_TRACE(k_ref_tracing, false, s, a, depth); }
+void launch_ref_tracing(const KArgs& a, uint32_t depth, hipStream_t s) { ST_LAUNCH_TRACE(k_ref_tracing, (), false, s, a, depth); }
 
 // ---------------------------------------------------------------- ref_shading.rs:3-177
 template <bool LDS_SCENE, class SE>
@@ -135,7 +135,7 @@ __global__ ST_KERNEL_BOUNDS void k_ref_shading(const KArgs a_in, uint32_t seed, 
     a.ref_rays[3u * idx + 1u] = f4(rs.dir, throughput.y);
     a.ref_rays[3u * idx + 2u] = f4(color, throughput.z);
 }
-void launch_ref_shading(const KArgs& a, uint32_t seed, uint32_t depth, hipStream_t s) { ST_LAUNCH_TRACE(k_ref_shading, false, s, a, seed, depth); }
+void launch_ref_shading(const KArgs& a, uint32_t seed, uint32_t depth, hipStream_t s) { ST_LAUNCH_TRACE(k_ref_shading, (), false, s, a, seed, depth); }
 
 // ---------------------------------------------------------------- primary visibility (prim_raster.rs:40-128 as one closest-hit ray per pixel)
 // frame_reprojection.rs:6-95 for one pixel, given its own fresh surface and velocity
@@ -175,16 +175,14 @@ __global__ ST_KERNEL_BOUNDS void k_prim_visibility(const KArgs a_in, const uint4
     Candidate c;   // the winning candidate: the velocity step's deformation term needs its triangle slot and barycentrics
 #if ST_FAST_DEVICE
     // PRIMARY hits are exact in the fast build too (round 6): Triangle::hit, the attribute interpolation and the normal's octahedral code in the island's
-    // arithmetic (st_device.h closest_resolve_exact says why: the sign of a decoded normal's z decides every hemisphere sample's tangent frame)
+    // arithmetic (st_traverse.h closest_resolve_exact says why: the sign of a decoded normal's z decides every hemisphere sample's tangent frame)
     // (a scene that lives in LDS — the Cornell box — keeps round 5's path: its contract walk is the island's already, its gates have 17 dB to spare, and the
     // exact interpolation + octahedral code would cost its headline 2-3 us per frame)
     if (LDS_SCENE) hit = trace_closest(a, ray, lane_stack(a, lds), &used_, &c);
     else {
         bool any;
-        if (a.bvh_w != nullptr && a.primary_packets) any = closest_hit_packet(a, ray, &c);   // the tile's 64 primary rays as one packet over the wide stream
-        else if (a.bvh_w != nullptr) any = closest_hit_wide<SE, true>(a, ray, lane_stack(a, lds), &c);
-        else if (a.bvh_c != nullptr) any = closest_hit_compact(a, ray, lane_stack(a, lds), &c);
-        else used_ = traverse<false>(a, ray, kF32Max, lane_stack(a, lds), &c, &any);
+        // exact leaf test; the tile's 64 primary rays as one packet over the wide stream where the tuning says so; not ablatable: primary hits are no shadow rays
+        ST_CLOSEST_WALK(true, false, a, ray, lane_stack(a, lds), a.bvh_w != nullptr && a.primary_packets, &c, any, used_);
         hit = closest_resolve_exact(a, ray, c, any);
     }
 #else
@@ -235,7 +233,7 @@ __global__ ST_KERNEL_BOUNDS void k_prim_visibility(const KArgs a_in, const uint4
     }
 }
 void launch_prim_visibility(const KArgs& a, bool reproject, const uint4* deform_table, const float* deform_posed, hipStream_t s) {
-    if (reproject) ST_LAUNCH_TRACE_B(k_prim_visibility, true, false, s, a, deform_table, deform_posed); else ST_LAUNCH_TRACE_B(k_prim_visibility, false, false, s, a, deform_table, deform_posed);
+    if (reproject) ST_LAUNCH_TRACE(k_prim_visibility, (true), false, s, a, deform_table, deform_posed); else ST_LAUNCH_TRACE(k_prim_visibility, (false), false, s, a, deform_table, deform_posed);
 }
 
 // Tabulates the byte decodes of st_device.h with the routines themselves (one launch at engine creation).
@@ -274,7 +272,7 @@ __global__ ST_KERNEL_BOUNDS void k_spatial_trace(const KArgs a_in, const float4*
     tex_write(buf_d2, a, pos, make_float4(occluded ? 0.0f : 1.0f, ray_d1.z, ray_d1.w, 0.0f));
 }
 void launch_spatial_trace(const KArgs& a, const float4* buf_d0, const float4* buf_d1, float4* buf_d2, hipStream_t s) {
-    ST_LAUNCH_TRACE(k_spatial_trace, false, s, a, buf_d0, buf_d1, buf_d2);
+    ST_LAUNCH_TRACE(k_spatial_trace, (), false, s, a, buf_d0, buf_d1, buf_d2);
 }
 
 // ---------------------------------------------------------------- frame_composition.rs:18-82 as a compute pass into an RGBA32F buffer

@@ -113,7 +113,7 @@ void Engine::index_device_tree() {
     }
 }
 
-// The WIDE stream's topology (k_bvh.hip k_bvh_wide; st_device.h closest_hit_wide): the binary tree of the device stream (bvh_upload_,
+// The WIDE stream's topology (k_bvh.hip k_bvh_wide; st_traverse.h closest_hit_wide): the binary tree of the device stream (bvh_upload_,
 // entries of four texels) collapsed top-down into nodes of up to four children — a node's two children are replaced by their own children,
 // largest surface area first, until there are four or only leaf runs are left (tools/bvh4_sim.py: 3.1 children per node on the dungeon,
 // half the node steps per ray). Wide nodes are numbered in depth-first order, leaf records in stream order (a run's records stay

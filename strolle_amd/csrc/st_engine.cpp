@@ -66,7 +66,7 @@ int Engine::set_tuning(const StTuning& t) {
     staging.enabled = tuning.staging != 0u;
     return ST_OK;
 }
-// st_tick found a wide walk's overflow word set (st_device.h wide_walk_overflowed): see st_engine.h walk_flags_host
+// st_tick found a wide walk's overflow word set (st_traverse.h wide_walk_overflowed): see st_engine.h walk_flags_host
 void Engine::note_walk_overflow() {
     const bool lane = walk_flags_host[0] != 0u, packet = walk_flags_host[1] != 0u;
     walk_flags_host[0] = 0u; walk_flags_host[1] = 0u;   // (a frame still in flight may set them again: the next tick sees that)

@@ -481,7 +481,7 @@ struct Engine {
     Stream skin_stream; Event ev_skinned;
     Fence posed_read;   // behind the bakes that read the posed regions (bake_on_device), on whichever streams: the next skin launch overwrites them
     uint64_t skin_launches = 0, skinned_triangles = 0, posed_readbacks = 0;
-    // Deformation motion (include/strolle_hip.h "skinned meshes"; st_device.h deform_prev_point): with the switch on, primary visibility and the AOV launch
+    // Deformation motion (include/strolle_hip.h "skinned meshes"; st_traverse.h deform_prev_point): with the switch on, primary visibility and the AOV launch
     // read the previous region of every instance the last tick re-skinned, through the free word of the scene copy's instance table (fill_instance_table).
     // deform_live: instances the last tick left a previous pose. Frames read the posed store then: deform_read is recorded behind every reader
     // that can reach deform_prev_point (reader_end: frames and the MOTION AOV, not the scene queries) — behind a wait for its own earlier recording, so that one event covers readers on several streams — and the next skin launch,
@@ -727,7 +727,7 @@ struct Engine {
     size_t info_dirty_lo_ = SIZE_MAX, info_dirty_hi_ = 0; bool info_full_ = true;   // slots whose word may have changed since tri_info_ was listed (spawned, removed); everything (materials changed)
     void mark_info_dirty(size_t b, size_t e) { info_dirty_lo_ = std::min(info_dirty_lo_, b); info_dirty_hi_ = std::max(info_dirty_hi_, e); }
     std::vector<uint32_t> tri_info_; uint32_t tri_info_live_ = 0; uint64_t tri_info_serial_ = 1, tri_info_built_for_ = 0;   // per slot: live | Blend << 1 | material << 2; the serial counts what can change it
-    // A wide walk that found its stack full drops the push and says so in one of two sticky words of page-locked host memory (st_device.h
+    // A wide walk that found its stack full drops the push and says so in one of two sticky words of page-locked host memory (st_traverse.h
     // wide_walk_overflowed; KArgs::walk_flags). st_tick reads them: a per-lane walk's overflow re-arms every later launch with a deeper stack
     // (24 -> 32 -> 48 -> 56 entries: dynamic LDS, fewer waves per SIMD), the packet's (64 entries, one VGPR) hands primary visibility back to the
     // per-lane walk; either way that tick returns ST_ERR_BVH_TOO_DEEP once (StTuning::allow_deep_bvh: a line on stderr) — the frames rendered in

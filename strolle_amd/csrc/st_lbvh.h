@@ -9,7 +9,7 @@ namespace st {
 // Everything is device memory the caller owns. tri_info: one word per triangle slot — bit 0 the slot is live, bit 1 its material is
 // AlphaMode::Blend, bits 2.. its material slot. Output: `nodes` (64 B per node, node index = the head's index in the binary radix tree:
 // live - 1 slots, ALL written — a walk from the root, node 0, reaches about a third of them: k_lbvh.hip k_lbvh_wide_nodes) and `leaves` (48 B per
-// record, sorted order), in the wide stream's format (st_device.h closest_hit_wide). Scratch: keys_in / keys_out (8 B x slots), sort_temp
+// record, sorted order), in the wide stream's format (st_traverse.h closest_hit_wide). Scratch: keys_in / keys_out (8 B x slots), sort_temp
 // (lbvh_sort_temp_bytes(slots)), seg (2 x lbvh_pow2(live) boxes of 32 B), children (8 B x live), node_box (32 B x live), bounds (6 ints).
 // A build cannot fail half-way: no launch of it depends on a count another one produced, none keeps a stack (rounds 5 and 6 collapsed the binary tree
 // frontier by frontier and finished with private stacks that could overflow; see k_lbvh_wide_nodes).

@@ -7,7 +7,7 @@ namespace st {
 
 // The handle table of the scene queries: per instance slot {StHandle lo, StHandle hi, first triangle slot, 0}. Instance slot ranges are
 // contiguous (instance_triangles), so `triangle slot - first` is the index into the mesh's own array. The fourth word belongs to deformation
-// motion (st_device.h deform_prev_point): the first triangle of the instance's previous region of the posed store + 1, for the instances this
+// motion (st_traverse.h deform_prev_point): the first triangle of the instance's previous region of the posed store + 1, for the instances this
 // tick re-skinned while the switch is on; 0 for every other one, and always while it is off.
 void Engine::fill_instance_table() {
     const size_t slots = std::max<size_t>(instance_xforms.size() / 8u, 1u);

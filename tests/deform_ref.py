@@ -1,4 +1,4 @@
-"""Numpy restatement of deformation motion (include/strolle_hip.h "skinned meshes"; strolle_amd/csrc/st_device.h deform_prev_point).
+"""Numpy restatement of deformation motion (include/strolle_hip.h "skinned meshes"; strolle_amd/csrc/st_traverse.h deform_prev_point).
 
 The deformation term is restated in float32, one rounding per operation, in the kernel's order:
     w          = (1 - u) - v

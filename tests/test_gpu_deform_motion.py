@@ -1,4 +1,4 @@
-"""GPU tests of deformation motion (include/strolle_hip.h "skinned meshes", st_engine_set_deformation_motion; st_device.h deform_prev_point).
+"""GPU tests of deformation motion (include/strolle_hip.h "skinned meshes", st_engine_set_deformation_motion; st_traverse.h deform_prev_point).
 
 Skinned tubes (scenes.skinned_tube / bend_pose) stand in the Cornell box, in the dungeon, or alone (a scene small enough to live in LDS) and
 are re-posed every tick. With the switch off — the default — nothing changes; with it on, the velocity plane and ST_AOV_MOTION of the

@@ -294,7 +294,7 @@ def test_report_only_is_not_set():
 
 @pytest.mark.gpu
 def test_axis_parallel_rays_walk_the_compact_stream_like_the_contract_stream():
-    """Rays with a direction component of exactly 0 (an axis-aligned camera's centre column and centre row; st_device.h slab_safe_dir):
+    """Rays with a direction component of exactly 0 (an axis-aligned camera's centre column and centre row; st_traverse.h slab_safe_dir):
     on such an axis the slab planes are (bound - origin) / 0. The fast build's compact walk must still find what the contract walk of the
     exact build finds — same triangle, same distance — and not wander (the launch stays as short as its neighbours'). 33 x 33 pixels so
     that pixel 16 sits on the optical axis; a soup dense enough for the scene to leave LDS and use the compact stream; also with the eye on
@@ -327,7 +327,7 @@ def test_axis_parallel_rays_walk_the_compact_stream_like_the_contract_stream():
 @pytest.mark.gpu
 @pytest.mark.parametrize("triangles,links16", [(3000, True), (40000, False)])
 def test_the_wide_stream_finds_what_the_contract_walk_finds(triangles, links16):
-    """StTuning::wide_bvh (round 5): the fast build's rays walk 4-wide nodes (k_bvh.hip k_bvh_wide, st_device.h closest_hit_wide / any_hit_wide) —
+    """StTuning::wide_bvh (round 5): the fast build's rays walk 4-wide nodes (k_bvh.hip k_bvh_wide, st_traverse.h closest_hit_wide / any_hit_wide) —
     in the 16-bit form (links inside the sort keys, fewer than 32768 nodes and leaf records) and in the 32-bit form. Primary hits of a Reference
     frame against the exact build's contract walk, the same gate as the compact stream's; the device's wide stream read back: every child box
     contains the contract stream's box it was made from (conservative f16), every leaf record is its contract entry's triangle."""
@@ -409,7 +409,7 @@ def test_the_wide_walk_drops_no_push():
 @pytest.mark.gpu
 def test_a_wide_walk_that_overflows_its_stack_says_so_and_rearms():
     """VERDICT r5 item 1b / ADVICE r5: the wide walk keeps 24 pending entries (StTuning::wide_stack_entries) whatever the tree; a push that finds the
-    stack full used to be dropped with ST_OK. Now the walk sets a sticky word (st_device.h wide_walk_overflowed), the next st_tick re-arms every
+    stack full used to be dropped with ST_OK. Now the walk sets a sticky word (st_traverse.h wide_walk_overflowed), the next st_tick re-arms every
     later launch with a deeper stack (24 -> 32 -> 48 -> 56) and returns ST_ERR_BVH_TOO_DEEP once (st_debug_walk_overflow reads the state).
     (a) the sliver bundle (scenes.build_sliver_bundle; 27 pending entries by the host model, tests/test_wide_bvh.py) with the default 24;
     (b) the demo dungeon with an 8-entry stack forced through StTuning. After the re-arm the hits are the exact build's contract walk's."""
@@ -732,7 +732,7 @@ def test_small_trees_built_on_the_device(n_triangles):
 @pytest.mark.parametrize("subdivide,size", [(0, (1920, 1080)), (2, (960, 544)), (0, (200, 120))])
 def test_primary_ray_packets_find_the_per_lane_walks_hits(subdivide, size):
     """StTuning::primary_packets (round 5): primary visibility walks the wide stream as ONE packet per wave — uniform node pointer and stack,
-    scalar node fetches, ballots decide the descent (st_device.h closest_hit_packet). Each lane's closest hit is the per-lane walk's: the G-buffer
+    scalar node fetches, ballots decide the descent (st_traverse.h closest_hit_packet). Each lane's closest hit is the per-lane walk's: the G-buffer
     and the surface map of the first two frames are compared to a part in 5e5 (what may differ beyond that is which of two triangles with the same t wins:
     at most 1e-4 of the pixels), also on a frame whose width is not a multiple of 8 (waves with inactive lanes) and with 32-bit links."""
     torch = _torch()

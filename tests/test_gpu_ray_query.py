@@ -419,3 +419,120 @@ def test_host_call_equals_the_device_call():
         assert prod.trace_rays_host(rays[:100]).tobytes() == dev[:100].tobytes()   # the engine's buffers, reused smaller
     finally:
         prod.close(); orac.close()
+
+
+# ----------------------------------------------------------------------------- the alpha test, over every stream
+# Two layers of ALPHA_GRID x ALPHA_GRID unit quads (z = 0 and z = -1), AlphaMode::Blend, all on ONE 32 x 32 texture whose alpha is a checkerboard of 0 / 255 in
+# 8 x 8-texel blocks (4 x 4 blocks per quad). Rays cross a layer only at "safe points": 2.5 / 5.5 texels into a block, so the four bilinear taps
+# lie in one block (alpha exactly 0 or 1), at least 2.5 texels (0.078 of a quad) from every quad edge and 3 texels off the quad's diagonal. The
+# answer of every ray is therefore decided — by the geometry below, in float64 — and each walk owes the same triangle and the same occlusion bit.
+ALPHA_GRID, ALPHA_BLOCK, ALPHA_TEXELS = 12, 8, 32
+ALPHA_LAYER_SHIFT = ((0.0, 0.0), (0.5, 0.125))      # layer 1 lies (0.5, 0.125) beside layer 0: a ray along ALPHA_COHERENT_DIR arrives one block to the left
+ALPHA_COHERENT_DIR = np.array([0.25, 0.125, -1.0])
+ALPHA_CONFIGS = {"exact": (True, {}), "default": (False, {}), "no_packets": (False, {"primary_packets": 0}), "no_wide": (False, {"wide_bvh": 0}),
+                 "no_compact": (False, {"compact_bvh": 0}), "no_anyhit_fast": (False, {"anyhit_fast": 0})}
+
+
+def _build_alpha_layers(e):
+    e.set_blue_noise(scenes.load_blue_noise())
+    tex = np.full((ALPHA_TEXELS, ALPHA_TEXELS, 4), 200, np.uint8)
+    ty, tx = np.mgrid[0:ALPHA_TEXELS, 0:ALPHA_TEXELS]
+    tex[..., 3] = np.where((tx // ALPHA_BLOCK + ty // ALPHA_BLOCK) % 2 == 0, 255, 0)
+    e.insert_image(900, tex, srgb=True)
+    e.insert_material(1, Material(base_color=(1.0, 1.0, 1.0, 1.0), base_color_texture=900, alpha_mode=1))
+    pos, uv = [], []
+    for layer, (sx, sy) in enumerate(ALPHA_LAYER_SHIFT):
+        for j in range(ALPHA_GRID):
+            for i in range(ALPHA_GRID):
+                x0, y0, z = i - ALPHA_GRID / 2 + sx, j - ALPHA_GRID / 2 + sy, -float(layer)
+                p00, p10, p11, p01 = (x0, y0, z), (x0 + 1, y0, z), (x0 + 1, y0 + 1, z), (x0, y0 + 1, z)
+                pos += [[p00, p10, p11], [p00, p11, p01]]          # triangle 2 q: u > v (below the diagonal), 2 q + 1: above it
+                uv += [[(0, 0), (1, 0), (1, 1)], [(0, 0), (1, 1), (0, 1)]]
+    pos = np.asarray(pos, np.float32)
+    nrm = np.tile(np.array([0, 0, 1], np.float32), (len(pos), 3, 1))
+    e.insert_mesh(7, Mesh(pos, nrm, np.asarray(uv, np.float32)))
+    e.insert_instance(77, Instance(7, 1, np.concatenate([np.eye(3), np.zeros((3, 1))], 1).astype(np.float32)))
+    return len(pos)
+
+
+def _safe_points(layer, rng, n=None):
+    """world positions of safe points on `layer`: one per block in raster order (n = None), or n random ones"""
+    if n is None:
+        j, i, by, bx = [a.reshape(-1) for a in np.mgrid[0:ALPHA_GRID, 0:ALPHA_GRID, 0:4, 0:4]]   # a run of 64 consecutive rays: four neighbouring quads
+    else:
+        i, j, bx, by = (rng.integers(0, ALPHA_GRID, n), rng.integers(0, ALPHA_GRID, n), rng.integers(0, 4, n), rng.integers(0, 4, n))
+    sx, sy = ALPHA_LAYER_SHIFT[layer]
+    x = i - ALPHA_GRID / 2 + sx + (ALPHA_BLOCK * bx + 2.5) / ALPHA_TEXELS
+    y = j - ALPHA_GRID / 2 + sy + (ALPHA_BLOCK * by + 5.5) / ALPHA_TEXELS
+    return np.stack([x, y, np.full(len(x), -float(layer))], 1)
+
+
+def _alpha_expected(rays):
+    """(hit, triangle, occluded) of every ray, from the construction alone"""
+    o, d, t_max = rays["origin"].astype(np.float64), rays["direction"].astype(np.float64), rays["t_max"].astype(np.float64)
+    best_t = np.full(len(rays), np.inf); best_tri = np.zeros(len(rays), np.uint32)
+    for layer, (sx, sy) in enumerate(ALPHA_LAYER_SHIFT):
+        t = (-float(layer) - o[:, 2]) / d[:, 2]
+        lx, ly = o[:, 0] + t * d[:, 0] + ALPHA_GRID / 2 - sx, o[:, 1] + t * d[:, 1] + ALPHA_GRID / 2 - sy
+        inside = (t > 0) & (lx > 0) & (lx < ALPHA_GRID) & (ly > 0) & (ly < ALPHA_GRID)
+        i, j = np.floor(lx), np.floor(ly)
+        u, v = (lx - i) * ALPHA_TEXELS, (ly - j) * ALPHA_TEXELS                                # texel coordinates inside the quad
+        margin = np.minimum.reduce([u % ALPHA_BLOCK - 0.5, ALPHA_BLOCK - 0.5 - u % ALPHA_BLOCK, v % ALPHA_BLOCK - 0.5, ALPHA_BLOCK - 0.5 - v % ALPHA_BLOCK, np.abs(u - v)])
+        outside = np.maximum.reduce([-lx, lx - ALPHA_GRID, -ly, ly - ALPHA_GRID])
+        assert np.all(np.where(inside, margin, outside * ALPHA_TEXELS) > 1.0), "a ray of this test leaves the safe points"
+        opaque = inside & ((u // ALPHA_BLOCK + v // ALPHA_BLOCK) % 2 == 0)
+        tri = (2 * (layer * ALPHA_GRID * ALPHA_GRID + j * ALPHA_GRID + i) + (v > u)).astype(np.int64)
+        closer = opaque & (t < best_t)
+        best_t[closer] = t[closer]; best_tri[closer] = tri[closer]
+    hit = best_t < t_max
+    assert np.all(np.abs(best_t[np.isfinite(best_t)] / t_max[np.isfinite(best_t)] - 1.0) > 0.05), "a t_max of this test is too close to a hit"
+    return hit, np.where(hit, best_tri, 0), hit
+
+
+@pytest.fixture(scope="module")
+def alpha_rays():
+    rng = np.random.default_rng(29)
+    p0 = _safe_points(0, rng)                                    # coherent: parallel rays through every block of layer 0, in raster order
+    coherent = (p0 - 2.0 * ALPHA_COHERENT_DIR, np.tile(ALPHA_COHERENT_DIR, (len(p0), 1)))
+    a, b = _safe_points(0, rng, len(p0)), _safe_points(1, rng, len(p0))   # incoherent: through a random safe point of each layer, either way
+    flip = rng.integers(0, 2, len(p0)).astype(bool)[:, None]
+    a, b = np.where(flip, b, a), np.where(flip, a, b)
+    s = rng.uniform(0.5, 2.0, (len(p0), 1))
+    incoherent = (a - s * (b - a), (b - a) * rng.uniform(0.5, 2.0, (len(p0), 1)))
+    sets = {}
+    for name, (o, d) in (("coherent", coherent), ("incoherent", incoherent)):
+        o32, d32 = o.astype(np.float32), d.astype(np.float32)
+        t1 = (a if name == "incoherent" else p0)[:, 2] - o32[:, 2]; t1 = t1 / d32[:, 2]   # the ray parameter at its first layer ...
+        t2 = t1 + np.abs(1.0 / d32[:, 2])                                                 # ... and at its second
+        k = rng.integers(0, 4, len(o32))
+        t_max = np.select([k == 0, k == 1, k == 2], [0.5 * t1, 0.5 * (t1 + t2), 1.5 * t2], np.inf).astype(np.float32)
+        rays = make_rays(o32, d32, t_max)
+        sets[name] = (rays,) + _alpha_expected(rays)
+    for name, (_, hit, tri, _) in sets.items():
+        assert 0.2 < hit.mean() < 0.8 and len(np.unique(tri[hit] // (2 * ALPHA_GRID * ALPHA_GRID))) == 2, f"{name}: both layers and the holes must be met"
+    return sets
+
+
+@pytest.mark.parametrize("config", list(ALPHA_CONFIGS))
+def test_alpha_test_decides_the_same_in_every_walk(config, alpha_rays):
+    """The alpha test (AlphaMode::Blend: a hit counts where the base colour's alpha is 1) through st_scene_trace_rays and st_scene_occluded, in the
+    exact build and over each stream of the fast build: contract, compact, wide, and the wide stream's packets (ST_RAY_COHERENT)."""
+    exact, tuning = ALPHA_CONFIGS[config]
+    e = Engine(device=0, exact=exact)
+    try:
+        if tuning:
+            e.set_tuning(**tuning)
+        n_tri = _build_alpha_layers(e)
+        e.tick()
+        assert 4 * (2 * n_tri - 1) > 448, "the stream must not fit the LDS scene copy (kLdsSceneTexels), or no compact / wide stream is built"
+        for name, (rays, hit, tri, occ) in alpha_rays.items():
+            for coherent in (False, True):
+                got = gpu_trace(e, rays, coherent=coherent)
+                what = f"{config} {name} coherent={coherent}"
+                assert_misses_are_clean(got)
+                assert np.array_equal(got["hit"] == 1, hit), f"{what}: {int(((got['hit'] == 1) != hit).sum())} hit / miss disagreements"
+                assert np.array_equal(got["triangle"], tri), f"{what}: {int((got['triangle'] != tri).sum())} rays found another triangle"
+                assert np.all(got["instance"][hit] == 77)
+            assert np.array_equal(gpu_occluded(e, rays), occ), f"{config} {name}: occlusion"
+    finally:
+        e.close()

@@ -1,4 +1,4 @@
-"""The WIDE stream (StTuning::wide_bvh; k_bvh.hip k_bvh_wide, st_device.h closest_hit_wide): the host collapses the binary tree of the device
+"""The WIDE stream (StTuning::wide_bvh; k_bvh.hip k_bvh_wide, st_traverse.h closest_hit_wide): the host collapses the binary tree of the device
 stream into nodes of up to four children once per build. CPU tests of that topology (host-only engines): it must be a re-bracketing of the
 SAME tree — every leaf run reachable exactly once, every child box one of the contract stream's own boxes — and a walk over it must find
 what a brute-force search over all triangles finds (strolle-gpu/src/ray.rs:114-266 is the walk being replaced; triangle.rs:64-113 the hit test)."""

@@ -129,7 +129,7 @@ def replay(block, K):
     return work, useful / 64.0
 
 n = union["tiles"]
-print(f"primary rays per 8 x 8 tile (what a wave-wide packet walks, st_device.h closest_hit_packet): node steps {union['node_mean'] / n:.1f} per ray, {union['node_max'] / n:.1f} for the tile's longest ray, "
+print(f"primary rays per 8 x 8 tile (what a wave-wide packet walks, st_traverse.h closest_hit_packet): node steps {union['node_mean'] / n:.1f} per ray, {union['node_max'] / n:.1f} for the tile's longest ray, "
       f"{union['node_union'] / n:.1f} in the UNION of the tile's paths; leaf records {union['leaf_max'] / n:.1f} (longest ray) / {union['leaf_union'] / n:.1f} (union)")
 for name, blocks in groups.items():
     base = [replay(b, 0) for b in blocks]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """How much of the traversal loop's work is lost to lane divergence, and how much of it regrouping rays could win back —
-a host-side model of st_device.h's traverse() over the engine's own device BVH stream (no GPU needed).
+a host-side model of st_traverse.h's traverse() over the engine's own device BVH stream (no GPU needed).
 
 Every ray is traversed with the product's rules (near child first, far child pushed, 24-entry stack, leaf runs) in numpy and its
 sequence of steps is recorded as internal (box pair) / leaf (triangle) steps. A wave of 64 rays walks in lockstep, so step i of
