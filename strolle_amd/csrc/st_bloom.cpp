@@ -1,6 +1,6 @@
 // st_bloom.cpp — bloom (include/strolle_hip.h "bloom"): the setter's checks, the plan (level count, mip sizes, blend factors: host arithmetic
-// that st_bloom_plan reports), the chain of launches (k_bloom.hip) that st_render_camera and st_bloom_process share, and the camera's HDR
-// plane and pyramid. See st_engine.h CameraState.
+// that st_bloom_plan reports) and the chain of launches (k_bloom.hip) that st_render_camera and st_bloom_process share. The HDR plane and
+// the pyramids: st_engine.h CameraState::bloom_planes, Engine::bloom_scratch.
 #include <cmath>
 
 #include "st_engine.h"
@@ -58,8 +58,6 @@ int Engine::set_bloom(CameraState& c, const StBloomDesc* desc) {
     c.bloom = *desc; c.bloom_on = true;
     return ST_OK;
 }
-
-static double bloom_format_bytes(uint32_t format) { return format == ST_FORMAT_RGBA32F ? 16.0 : (format == ST_FORMAT_RGBA16F ? 8.0 : 4.0); }
 
 // The fused tail takes the levels t .. L - 1 whose mips, three floats per texel, fit `tail_lds_bytes` together; t >= 1 (mip t - 1 is its input and
 // output in device memory; the frame and its prefilter stay with the first downsample).
@@ -124,25 +122,15 @@ Engine::BloomSteps Engine::bloom_steps(const StBloomDesc& d, const BloomPlan& pl
     a.src = L ? pyramid + plan.offset[0] : nullptr; a.sw = L ? plan.w[0] : 0u; a.sh = L ? plan.h[0] : 0u;
     a.base = static_cast<const float4*>(src); a.dst = dst; a.dw = w; a.dh = h; a.format = format;
     a.factor = L ? plan.factor[0] : 0.0f;
-    s.step[s.count++] = {KS_BLOOM_COMPOSITE, false, a, BloomTailArgs{}, (double)a.sw * a.sh * 16.0 + (double)w * h * (16.0 + bloom_format_bytes(format))};
+    s.step[s.count++] = {KS_BLOOM_COMPOSITE, false, a, BloomTailArgs{}, (double)a.sw * a.sh * 16.0 + (double)w * h * (16.0 + format_bytes(format))};
     return s;
 }
 
-int Engine::bloom_planes(CameraState& c, const BloomPlan& plan, hipStream_t stream) {
-    const size_t sizes[2] = {(size_t)c.desc.width * c.desc.height * sizeof(float4), plan.texels * sizeof(float4)};
-    DeviceArray* arrays[2] = {&c.bloom_hdr, &c.bloom_pyramid};
-    for (int i = 0; i < 2; i++) {   // grown, never shrunk: a level count that goes down and up again between frames costs no sync and no allocation
-        DeviceArray& p = *arrays[i];
-        if (p.capacity >= sizes[i]) continue;
-        if (p.ptr) { ST_HIP(hipDeviceSynchronize()); c.bloom_read.settled(); }   // frames in flight may still read the one that goes
-        if (int rc = p.reserve(sizes[i], sizes[i])) return rc;
-    }
-    // the previous frame's bloom launches ran on another stream: this frame's composing launch overwrites the plane they read
-    return c.bloom_read.wait(stream, Fence::OtherStreams, Fence::Keep);
-}
-
-int Engine::bloom_done(CameraState& c, hipStream_t stream) {
-    return c.bloom_read.record(stream);
+void Engine::launch_bloom_step(const BloomStep& s, hipStream_t stream) {
+    if (s.slot == KS_BLOOM_DOWN) L.launch_bloom_down(s.args, s.first, stream);
+    else if (s.slot == KS_BLOOM_UP) L.launch_bloom_up(s.args, stream);
+    else if (s.slot == KS_BLOOM_TAIL) L.launch_bloom_tail(s.tail, stream);
+    else L.launch_bloom_composite(s.args, stream);
 }
 
 int Engine::bloom_process(const StBloomDesc* desc, const StDisplayDesc* display, const void* src, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream) {
@@ -160,24 +148,11 @@ int Engine::bloom_process(const StBloomDesc* desc, const StDisplayDesc* display,
     if (format < ST_FORMAT_RGBA32F || format > ST_FORMAT_BGRA8_UNORM_SRGB) return fail(ST_ERR_INVALID_ARGUMENT, "unknown output format");
     if (!has_device) return fail(ST_ERR_NO_DEVICE, "st_bloom_process on a host-only engine");
     ST_HIP(hipSetDevice(device));
-    const size_t bytes = plan.texels * sizeof(float4);
-    if (bytes) {   // the engine's pyramid: grown only when a call needs a larger one; calls on different streams take turns
-        if (bloom_scratch.capacity < bytes) {
-            ST_HIP(hipDeviceSynchronize());   // earlier calls may still use the one that goes
-            bloom_scratch_read.settled();
-            if (int rc = bloom_scratch.reserve(bytes, bytes)) return rc;
-        }
-        if (int rc = bloom_scratch_read.wait(stream, Fence::OtherStreams, Fence::Keep)) return rc;
-    }
-    const BloomSteps steps = bloom_steps(*desc, plan, src, w, h, bloom_scratch.as<float4>(), dst, (uint32_t)format, disp, bloom_tail_bytes());
-    for (uint32_t i = 0; i < steps.count; i++) {
-        const BloomStep& s = steps.step[i];
-        if (s.slot == KS_BLOOM_DOWN) L.launch_bloom_down(s.args, s.first, stream);
-        else if (s.slot == KS_BLOOM_UP) L.launch_bloom_up(s.args, stream);
-        else if (s.slot == KS_BLOOM_TAIL) L.launch_bloom_tail(s.tail, stream);
-        else L.launch_bloom_composite(s.args, stream);
-    }
-    if (bytes) if (int rc = bloom_scratch_read.record(stream)) return rc;
+    const size_t bytes = plan.texels * sizeof(float4);   // the engine's pyramid (0: the image holds no level)
+    if (bytes) if (int rc = bloom_scratch.acquire({bytes}, bloom_scratch.Grow, stream)) return rc;
+    const BloomSteps steps = bloom_steps(*desc, plan, src, w, h, bloom_scratch.plane[0].as<float4>(), dst, (uint32_t)format, disp, bloom_tail_bytes());
+    for (uint32_t i = 0; i < steps.count; i++) launch_bloom_step(steps.step[i], stream);
+    if (bytes) if (int rc = bloom_scratch.done(stream)) return rc;
     ST_HIP(hipGetLastError());
     return ST_OK;
 }

@@ -3,7 +3,16 @@
 //   st_scene.cpp        scene stores: materials, images, lights, instances -> world-space triangles (baking)
 //   st_bvh_refresh.cpp  device form of the BVH stream, refit (host) and the device refit's index arrays, depth check
 //   st_tick.cpp         Engine::tick: refresh + uploads (double-buffered scene / light copies, page-locked staging)
-//   st_render.cpp       per-camera buffers and the per-frame pass graph on two HIP streams, present hand-over
+//   st_render.cpp       per-camera buffers and Engine::render: the per-frame pass graph in phases, on two HIP streams; present hand-over
+//   st_display.cpp      display transforms: exposure, tone mapping, the auto-exposure state
+//   st_post.cpp         output post-processing: FXAA and the resampler
+//   st_bloom.cpp        bloom: the plan, the chain of launches
+//   st_skin.cpp         skinned meshes and morph targets: stores, the tick's skin launch
+//   st_env.cpp          environment lighting: the map, its importance table
+//   st_query.cpp        scene queries: closest hit, occlusion, picks
+//   st_aov.cpp          per-pixel AOVs
+//   st_gltf.cpp         scene ingest: glTF 2.0 (.gltf / .glb), image decoding
+//   st_dist.cpp         multi-GPU: partitions, transport, gather
 //   st_profile.cpp      per-kernel event timing
 //   st_abi.cpp          the C ABI (include/strolle_hip.h)
 // Behavioural contract: strolle/src/lib.rs (Engine), camera_controller.rs (pass order), lights.rs / materials.rs /
@@ -303,6 +312,24 @@ struct DeviceArray {
     }
     void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; capacity = 0; }
 };
+// Scratch planes one frame (or call) writes and the launches behind it read, with the Fence of those last readers: N planes used together share one fence.
+template <int N> struct FencedPlanes {
+    enum Fit { Exact /* replaced whenever the size differs: it shrinks too */, Grow /* replaced only by a larger one */ };
+    DeviceArray plane[N]; Fence read;
+    // Plane i at bytes[i] (0: not needed now, it stays as it is), and `stream` ordered behind the last readers on other streams (on the same stream the next writer follows
+    // them anyway: no event between two frames' kernels). A plane is replaced with the whole device joined — launches in flight may still use the one that goes.
+    int acquire(const size_t (&bytes)[N], Fit fit, hipStream_t stream) {
+        for (int i = 0; i < N; i++) {
+            DeviceArray& p = plane[i];
+            if (!bytes[i] || (fit == Exact ? p.capacity == bytes[i] : p.capacity >= bytes[i])) continue;
+            if (p.ptr) { ST_HIP(hipDeviceSynchronize()); read.settled(); p.release(); }
+            if (int rc = p.reserve(bytes[i], bytes[i])) return rc;
+        }
+        return read.wait(stream, Fence::OtherStreams, Fence::Keep);
+    }
+    int done(hipStream_t stream) { return read.record(stream); }   // behind the launches that read the planes
+};
+inline double format_bytes(uint32_t format) { return format == ST_FORMAT_RGBA32F ? 16.0 : (format == ST_FORMAT_RGBA16F ? 8.0 : 4.0); }   // of one pixel (StOutputFormat)
 
 // ------------------------------------------------------------------ per-camera state (camera_controller/buffers.rs)
 constexpr int kInternalPlanes = 4;  // decoded-surface twins A/B (KArgs::sn / psn) + the pair the variance pass writes ahead of the strides-1+2 wavelet launch
@@ -356,21 +383,19 @@ struct CameraState {
     bool display_auto() const { return display_on && (display.flags & ST_DISPLAY_AUTO_EXPOSURE) != 0u; }
     bool windowed() const { return row0 != 0u || col0 != 0u || row1 != desc.height || col1 != desc.width; }
     // Output post-processing (st_post.cpp; include/strolle_hip.h "post-processing"). Like the display it is not part of the per-camera
-    // buffers and survives st_camera_update. While a frame needs it, the composing launch writes post_plane[0] (render size, RGBA32F)
-    // instead of the caller's buffer; post_plane[1] carries FXAA's output to the resampler when both run. Both are allocated by the first
-    // frame that needs them and again only when the render size changed.
+    // buffers and survives st_camera_update. While a frame needs it, the composing launch writes post_planes.plane[0] (render size, RGBA32F)
+    // instead of the caller's buffer; plane[1] carries FXAA's output to the resampler when both run. Both are allocated by the first
+    // frame that needs them and again only when the render size changed; their fence is recorded behind each frame's post launches.
     StPostDesc post{}; bool post_on = false;
-    DeviceArray post_plane[2];
-    Fence post_read;   // recorded behind each frame's post launches: a frame on another stream waits for it before it writes the planes again
+    FencedPlanes<2> post_planes;
     bool post_resizes() const { return post_on && post.output_width != 0u && (post.output_width != desc.width || post.output_height != desc.height); }
     bool post_fxaa() const { return post_on && (post.flags & ST_POST_FXAA) != 0u && desc.mode != ST_MODE_BVH_HEATMAP; }   // heatmap frames are false colour
     // Bloom (st_bloom.cpp; include/strolle_hip.h "bloom"). Like the display and post-processing it survives st_camera_update. While a frame
-    // blooms, the composing launch writes bloom_hdr (render size, RGBA32F, untransformed) instead of the caller's buffer or post_plane[0], and
+    // blooms, the composing launch writes the HDR plane (render size, RGBA32F, untransformed) instead of the caller's buffer or the post plane, and
     // the bloom launches build the pyramid (one allocation of float4 mips) from it; the composite writes where the composing launch would have.
-    // Both are made by the first frame that needs them and again only when the render size (or the pyramid's level count) changes.
+    // Both are made by the first frame that needs them and again only when one has to grow; their fence is recorded behind each frame's bloom launches.
     StBloomDesc bloom{}; bool bloom_on = false;
-    DeviceArray bloom_hdr, bloom_pyramid;
-    Fence bloom_read;   // recorded behind each frame's bloom launches: a frame on another stream waits for it before it writes the two again
+    FencedPlanes<2> bloom_planes;   // [0] the HDR plane, [1] the pyramid
     bool blooms() const { return bloom_on && desc.mode != ST_MODE_BVH_HEATMAP; }   // heatmap frames are false colour
     uint32_t out_width() const { return post_on && post.output_width != 0u ? post.output_width : desc.width; }
     uint32_t out_height() const { return post_on && post.output_width != 0u ? post.output_height : desc.height; }
@@ -797,10 +822,8 @@ struct Engine {
     struct PostPlan { bool fxaa = false, resample = false; PostArgs fx{}, rs{}; double fxaa_bytes = 0.0, resample_bytes = 0.0; };
     static PostPlan post_plan(const StPostDesc& d, bool fxaa, const void* src, uint32_t w, uint32_t h, void* mid, void* dst, uint32_t format);
     int set_post(CameraState& c, const StPostDesc* desc);
-    int post_planes(CameraState& c, bool second, hipStream_t stream);   // the camera's planes at its render size (allocates only when that changed), ordered behind their last readers
-    int post_done(CameraState& c, hipStream_t stream);                  // behind a frame's post launches
     int post_process(const StPostDesc* desc, const void* src, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
-    DeviceArray post_scratch; Fence post_scratch_read;   // st_post_process's intermediate plane (FXAA -> resampler) and the end of its last use
+    FencedPlanes<1> post_scratch;   // st_post_process's intermediate plane (FXAA -> resampler): it only grows; calls on different streams take turns
     // ---- bloom (st_bloom.cpp)
     struct BloomPlan { uint32_t levels = 0; uint32_t w[8] = {}, h[8] = {}; float factor[8] = {}; size_t offset[8] = {}; size_t texels = 0; };
     struct BloomStep { int slot; bool first; BloomArgs args; BloomTailArgs tail; double bytes; };
@@ -809,8 +832,7 @@ struct Engine {
     // the frame's launches in order: `src` (w x h RGBA32F) -> the pyramid -> `dst` in `format` through `display`
     static BloomSteps bloom_steps(const StBloomDesc& d, const BloomPlan& plan, const void* src, uint32_t w, uint32_t h, float4* pyramid, void* dst, uint32_t format, const DisplayArgs& display, uint32_t tail_lds_bytes);
     int set_bloom(CameraState& c, const StBloomDesc* desc);
-    int bloom_planes(CameraState& c, const BloomPlan& plan, hipStream_t stream);   // the camera's HDR plane and pyramid (allocates only when their sizes changed), ordered behind their last readers
-    int bloom_done(CameraState& c, hipStream_t stream);                            // behind a frame's bloom launches
+    void launch_bloom_step(const BloomStep& s, hipStream_t stream);   // one of bloom_steps' launches
     int bloom_process(const StBloomDesc* desc, const StDisplayDesc* display, const void* src, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
     // The fused tail (k_bloom.hip k_bloom_tail), an experiment that measured slower and is OFF by default (tools/experiments/bloom_fused_tail.md): the LDS
     // its one workgroup may use. 0: no tail, the straightforward chain (the default); -1: what the device grants; n: at most n bytes
@@ -818,8 +840,9 @@ struct Engine {
     int bloom_tail_wanted = 0;
     uint32_t bloom_tail_bytes();
     static uint32_t bloom_tail_first(const BloomPlan& plan, uint32_t tail_lds_bytes);   // the first level the tail takes (== plan.levels: none)
-    DeviceArray bloom_scratch; Fence bloom_scratch_read;   // st_bloom_process's pyramid and the end of its last use
+    FencedPlanes<1> bloom_scratch;   // st_bloom_process's pyramid: likewise
     int scene_args(KArgs& a, bool heatmap) const;   // the scene half of KArgs (st_render.cpp): render() and the scene queries
+    void light_args(KArgs& a) const;                // its lights, LUT and environment half: render()
 
     // ---- scene queries (st_query.cpp; include/strolle_hip.h "scene queries")
     std::vector<uint32_t> instance_table_;   // host image of SceneSet::instance_table, rebuilt by every scene upload

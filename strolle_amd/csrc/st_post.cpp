@@ -1,6 +1,6 @@
 // st_post.cpp — output post-processing (include/strolle_hip.h "post-processing"): the setter's checks, the plan of at most two launches
-// (k_post.hip: FXAA, then the resampler, which also writes the output format) that st_render_camera and st_post_process share, and the
-// planes between them. See st_engine.h CameraState.
+// (k_post.hip: FXAA, then the resampler, which also writes the output format) that st_render_camera and st_post_process share. The planes
+// between them: st_engine.h CameraState::post_planes, Engine::post_scratch.
 #include <cmath>
 
 #include "st_engine.h"
@@ -31,8 +31,6 @@ int Engine::set_post(CameraState& c, const StPostDesc* desc) {
     return ST_OK;
 }
 
-static double format_bytes(uint32_t format) { return format == ST_FORMAT_RGBA32F ? 16.0 : (format == ST_FORMAT_RGBA16F ? 8.0 : 4.0); }
-
 // FXAA (when `fxaa`) over src, then the resampler when the sizes differ — or when nothing else would write dst. FXAA alone writes dst in
 // `format` itself; followed by the resampler it writes `mid` (w x h RGBA32F).
 Engine::PostPlan Engine::post_plan(const StPostDesc& d, bool fxaa, const void* src, uint32_t w, uint32_t h, void* mid, void* dst, uint32_t format) {
@@ -54,23 +52,6 @@ Engine::PostPlan Engine::post_plan(const StPostDesc& d, bool fxaa, const void* s
     return p;
 }
 
-int Engine::post_planes(CameraState& c, bool second, hipStream_t stream) {
-    const size_t bytes = (size_t)c.desc.width * c.desc.height * sizeof(float4);
-    for (int i = 0; i < (second ? 2 : 1); i++) {
-        DeviceArray& p = c.post_plane[i];
-        if (p.capacity == bytes) continue;
-        if (p.ptr) { ST_HIP(hipDeviceSynchronize()); p.release(); }   // frames in flight may still read it
-        if (int rc = p.reserve(bytes, bytes)) return rc;
-    }
-    // the previous frame's post launches ran on another stream: this frame's composing launch overwrites the plane they read
-    // (on the same stream it follows them anyway: no event between the two frames' kernels)
-    return c.post_read.wait(stream, Fence::OtherStreams, Fence::Keep);
-}
-
-int Engine::post_done(CameraState& c, hipStream_t stream) {
-    return c.post_read.record(stream);
-}
-
 int Engine::post_process(const StPostDesc* desc, const void* src, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream) {
     if (!desc || !src || !dst) return fail(ST_ERR_INVALID_ARGUMENT, "null argument");
     if (int rc = check_post(*desc)) return rc;
@@ -81,20 +62,14 @@ int Engine::post_process(const StPostDesc* desc, const void* src, uint32_t w, ui
     const bool fxaa = (desc->flags & ST_POST_FXAA) != 0u;
     const bool resizes = desc->output_width != 0u && (desc->output_width != w || desc->output_height != h);
     void* mid = nullptr;
-    if (fxaa && resizes) {   // the engine's intermediate plane: grown only when a call needs a larger one; calls on different streams take turns
-        const size_t bytes = (size_t)w * h * sizeof(float4);
-        if (post_scratch.capacity < bytes) {
-            ST_HIP(hipDeviceSynchronize());   // earlier calls may still use the plane that goes
-            post_scratch_read.settled();
-            if (int rc = post_scratch.reserve(bytes, bytes)) return rc;
-        }
-        if (int rc = post_scratch_read.wait(stream, Fence::OtherStreams, Fence::Keep)) return rc;   // (the same stream takes its turn by stream order)
-        mid = post_scratch.ptr;
+    if (fxaa && resizes) {   // the engine's intermediate plane
+        if (int rc = post_scratch.acquire({(size_t)w * h * sizeof(float4)}, post_scratch.Grow, stream)) return rc;
+        mid = post_scratch.plane[0].ptr;
     }
     const PostPlan plan = post_plan(*desc, fxaa, src, w, h, mid, dst, (uint32_t)format);
     if (plan.fxaa) L.launch_post_fxaa(plan.fx, stream);
     if (plan.resample) L.launch_post_resample(plan.rs, stream);
-    if (mid) if (int rc = post_scratch_read.record(stream)) return rc;
+    if (mid) if (int rc = post_scratch.done(stream)) return rc;
     ST_HIP(hipGetLastError());
     return ST_OK;
 }
