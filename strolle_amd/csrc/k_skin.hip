@@ -1,4 +1,4 @@
-// k_skin.hip — linear blend skinning of posed instances on the device (include/strolle_hip.h "skinned meshes"; st_skin.cpp).
+// k_skin.hip — linear blend skinning of posed instances on the device (include/strolle_hip.h "skinned meshes"; st_deform.cpp).
 //
 // One launch per tick covers every instance whose pose changed (and, after the posed store was reallocated, every posed instance). It reads
 // the skin store (a skinned mesh's bind-pose triangles in the device mesh store's layout — 24 floats: positions 9, normals 9, uvs 6 — and
@@ -62,17 +62,35 @@ static __device__ __forceinline__ uint32_t job_of(const uint32_t* job_start, uin
     return lo;
 }
 
-__global__ __launch_bounds__(kSkinBlock) void k_skin(const SkinJob* jobs, const uint32_t* job_start, uint32_t n_jobs, const float* bind,
-                                                     const SkinVertexDevice* corners, const float* palettes, float* posed) {
-    __shared__ float pal[kSkinMaxJoints * 12u];
+// What both kernels begin with: the workgroup's job, its palette staged in LDS (`pal`) behind a barrier, and the thread's triangle `k` of the job —
+// false for the threads of the padding, which are done.
+template <class Job>
+static __device__ __forceinline__ bool begin_job(const Job* jobs, const uint32_t* job_start, uint32_t n_jobs, const float* palettes, float* pal, Job* job, uint32_t* k) {
     const uint32_t first = blockIdx.x * kSkinBlock;
     const uint32_t lo = job_of(job_start, n_jobs, first);
-    const SkinJob j = jobs[lo];
+    const Job j = jobs[lo];
     const float* src = palettes + 12u * (size_t)j.palette_first;
     for (uint32_t i = threadIdx.x; i < 12u * j.joint_count; i += kSkinBlock) pal[i] = src[i];
     __syncthreads();
-    const uint32_t k = first - job_start[lo] + threadIdx.x;
-    if (k >= j.count) return;
+    *job = j;
+    *k = first - job_start[lo] + threadIdx.x;
+    return *k < j.count;
+}
+// ... and end with: corner v's position and normal into the posed triangle, and the uvs copied from the bind triangle
+static __device__ __forceinline__ void store_corner(float* out, int v, V3 p, V3 n) {
+    out[3 * v] = p.x; out[3 * v + 1] = p.y; out[3 * v + 2] = p.z;
+    out[9 + 3 * v] = n.x; out[9 + 3 * v + 1] = n.y; out[9 + 3 * v + 2] = n.z;
+}
+static __device__ __forceinline__ void copy_uvs(float* out, const float* m) {
+#pragma unroll
+    for (int u = 0; u < 6; u++) out[18 + u] = m[18 + u];
+}
+
+__global__ __launch_bounds__(kSkinBlock) void k_skin(const SkinJob* jobs, const uint32_t* job_start, uint32_t n_jobs, const float* bind,
+                                                     const SkinVertexDevice* corners, const float* palettes, float* posed) {
+    __shared__ float pal[kSkinMaxJoints * 12u];
+    SkinJob j; uint32_t k;
+    if (!begin_job(jobs, job_start, n_jobs, palettes, pal, &j, &k)) return;
     const float* m = bind + 24u * (size_t)(j.skin_first + k);
     const SkinVertexDevice* sv = corners + 3u * (size_t)(j.skin_first + k);
     float* out = posed + 24u * (size_t)(j.posed_first + k);
@@ -81,11 +99,9 @@ __global__ __launch_bounds__(kSkinBlock) void k_skin(const SkinJob* jobs, const 
         const SkinVertexDevice c = sv[v];
         V3 p, n;
         skin_corner(pal, c, v3(m[3 * v], m[3 * v + 1], m[3 * v + 2]), v3(m[9 + 3 * v], m[9 + 3 * v + 1], m[9 + 3 * v + 2]), &p, &n);
-        out[3 * v] = p.x; out[3 * v + 1] = p.y; out[3 * v + 2] = p.z;
-        out[9 + 3 * v] = n.x; out[9 + 3 * v + 1] = n.y; out[9 + 3 * v + 2] = n.z;
+        store_corner(out, v, p, n);
     }
-#pragma unroll
-    for (int u = 0; u < 6; u++) out[18 + u] = m[18 + u];
+    copy_uvs(out, m);
 }
 
 // Morph targets (include/strolle_hip.h "morph targets"): the jobs of a tick that have at least one active target, the skin stage above behind
@@ -100,14 +116,8 @@ __global__ __launch_bounds__(kSkinBlock) void k_morph(const MorphJob* jobs, cons
                                                       const SkinVertexDevice* corners, const float* palettes, const float* targets,
                                                       const MorphActive* active, float* posed) {
     __shared__ float pal[kSkinMaxJoints * 12u];
-    const uint32_t first = blockIdx.x * kSkinBlock;
-    const uint32_t lo = job_of(job_start, n_jobs, first);
-    const MorphJob j = jobs[lo];
-    const float* src = palettes + 12u * (size_t)j.palette_first;
-    for (uint32_t i = threadIdx.x; i < 12u * j.joint_count; i += kSkinBlock) pal[i] = src[i];
-    __syncthreads();
-    const uint32_t k = first - job_start[lo] + threadIdx.x;
-    if (k >= j.count) return;
+    MorphJob j; uint32_t k;
+    if (!begin_job(jobs, job_start, n_jobs, palettes, pal, &j, &k)) return;
     const float* m = bind + 24u * (size_t)(j.skin_first + k);
     float* out = posed + 24u * (size_t)(j.posed_first + k);
     float x[18];
@@ -145,11 +155,9 @@ __global__ __launch_bounds__(kSkinBlock) void k_morph(const MorphJob* jobs, cons
             const SkinVertexDevice c = sv[v];
             skin_corner(pal, c, p, n, &p, &n);
         }
-        out[3 * v] = p.x; out[3 * v + 1] = p.y; out[3 * v + 2] = p.z;
-        out[9 + 3 * v] = n.x; out[9 + 3 * v + 1] = n.y; out[9 + 3 * v + 2] = n.z;
+        store_corner(out, v, p, n);
     }
-#pragma unroll
-    for (int u = 0; u < 6; u++) out[18 + u] = m[18 + u];
+    copy_uvs(out, m);
 }
 
 void launch_skin(const SkinJob* jobs, const uint32_t* job_start, uint32_t n_jobs, uint32_t padded_total, const float* bind, const void* corners,

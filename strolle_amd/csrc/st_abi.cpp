@@ -52,13 +52,13 @@ void st_engine_destroy(StEngine* e) { delete E(e); }
 int st_mesh_insert(StEngine* e, StHandle id, const StMeshTriangle* t, size_t count) {
     ST_REQUIRE(e && (t || count == 0), "null argument");
     if (count == 0) return fail(ST_ERR_EMPTY_MESH, "mesh contains no triangles");
-    E(e)->drop_skin(id);   // skinned meshes: a new mesh drops the skin and the poses of its instances
-    E(e)->drop_morph(id);  // morph targets: likewise the targets and the weights
+    E(e)->deform.drop_skin(id);   // skinned meshes: a new mesh drops the skin and the poses of its instances
+    E(e)->deform.drop_morph(id);  // morph targets: likewise the targets and the weights
     E(e)->meshes[id].assign(t, t + count);
     E(e)->mesh_version[id] = E(e)->next_mesh_version++;   // an instance baked from the earlier mesh of this handle is re-baked by the host
     return ST_OK;
 }
-int st_mesh_remove(StEngine* e, StHandle id) { ST_REQUIRE(e, "null engine"); E(e)->drop_skin(id); E(e)->drop_morph(id); E(e)->meshes.erase(id); E(e)->mesh_version.erase(id); return ST_OK; }
+int st_mesh_remove(StEngine* e, StHandle id) { ST_REQUIRE(e, "null engine"); E(e)->deform.drop_skin(id); E(e)->deform.drop_morph(id); E(e)->meshes.erase(id); E(e)->mesh_version.erase(id); return ST_OK; }
 
 int st_material_insert(StEngine* e, StHandle id, const StMaterial* m) {
     ST_REQUIRE(e && m, "null argument");
@@ -159,8 +159,11 @@ int st_instance_insert(StEngine* e, StHandle id, StHandle mesh, StHandle materia
     ST_REQUIRE(e && xform, "null argument");
     Engine* en = E(e);
     const Affine x = affine_from12(xform);
-    for (auto& r : en->instances)
-        if (r.id == id) { if (r.mesh != mesh) en->drop_pose(id, false); r.prev_xform = r.xform; r.mesh = mesh; r.material = material; r.xform = x; r.xform_inv = affine_inverse(x); r.dirty = true; en->instances_dirty = true; return ST_OK; }
+    if (Engine::InstanceRec* r = en->find_instance(id)) {
+        if (r->mesh != mesh) en->deform.drop_instance(id, false);
+        r->prev_xform = r->xform; r->mesh = mesh; r->material = material; r->xform = x; r->xform_inv = affine_inverse(x); r->dirty = true; en->instances_dirty = true;
+        return ST_OK;
+    }
     uint32_t xslot;
     if (!en->xslot_free.empty()) { xslot = en->xslot_free.back(); en->xslot_free.pop_back(); }
     else { xslot = (uint32_t)(en->instance_xforms.size() / 8u); en->instance_xforms.resize(en->instance_xforms.size() + 8u, make_float4(0, 0, 0, 0)); }
@@ -174,46 +177,46 @@ int st_instance_remove(StEngine* e, StHandle id) {
     for (size_t i = 0; i < en->instances.size(); i++)
         if (en->instances[i].id == id) { en->xslot_free.push_back(en->instances[i].xslot); en->instances.erase(en->instances.begin() + i); en->instances_dirty = true; en->instance_removed = true; break; }
     en->drop_instance_triangles(id);
-    en->drop_pose(id, false);
+    en->deform.drop_instance(id, false);
     return ST_OK;
 }
 
-// ---- skinned meshes (st_skin.cpp)
+// ---- skinned meshes (st_deform.cpp)
 int st_mesh_set_skin(StEngine* e, StHandle mesh, const StSkinVertex* corners, size_t corner_count, uint32_t joint_count) {
     ST_REQUIRE(e, "null engine");
-    return E(e)->set_skin(mesh, corners, corner_count, joint_count);
+    return E(e)->deform.set_skin(mesh, corners, corner_count, joint_count);
 }
 int st_instance_set_pose(StEngine* e, StHandle instance, const float* joint_xforms, uint32_t joint_count) {
     ST_REQUIRE(e, "null engine");
-    return E(e)->set_pose(instance, joint_xforms, joint_count);
+    return E(e)->deform.set_pose(instance, joint_xforms, joint_count);
 }
 int st_debug_skinning(StEngine* e, uint64_t* launches, uint64_t* triangles, uint64_t* host_readbacks) {
     ST_REQUIRE(e && launches && triangles && host_readbacks, "null argument");
-    *launches = E(e)->skin_launches; *triangles = E(e)->skinned_triangles; *host_readbacks = E(e)->posed_readbacks;
+    E(e)->deform.skinning_stats(launches, triangles, host_readbacks);
     return ST_OK;
 }
 int st_debug_read_posed(StEngine* e, StHandle instance, float* out, size_t capacity_floats, size_t* written_floats) {
     ST_REQUIRE(e, "null engine");
-    return E(e)->read_posed(instance, out, capacity_floats, written_floats);
+    return E(e)->deform.read_posed(instance, out, capacity_floats, written_floats);
 }
-// ---- morph targets (st_skin.cpp)
+// ---- morph targets (st_deform.cpp)
 int st_mesh_set_morph_targets(StEngine* e, StHandle mesh, const StMorphDelta* deltas, size_t corner_count, uint32_t target_count) {
     ST_REQUIRE(e, "null engine");
-    return E(e)->set_morph_targets(mesh, deltas, corner_count, target_count);
+    return E(e)->deform.set_morph_targets(mesh, deltas, corner_count, target_count);
 }
 int st_instance_set_morph_weights(StEngine* e, StHandle instance, const float* weights, uint32_t target_count) {
     ST_REQUIRE(e, "null engine");
-    return E(e)->set_morph_weights(instance, weights, target_count);
+    return E(e)->deform.set_morph_weights(instance, weights, target_count);
 }
 int st_debug_morphing(StEngine* e, uint64_t* ticks, uint64_t* triangles, uint64_t* delta_bytes) {
     ST_REQUIRE(e && ticks && triangles && delta_bytes, "null argument");
-    return E(e)->morphing_stats(ticks, triangles, delta_bytes);
+    return E(e)->deform.morphing_stats(ticks, triangles, delta_bytes);
 }
-int st_engine_set_deformation_motion(StEngine* e, int enabled) { ST_REQUIRE(e, "null engine"); E(e)->deform_on = enabled != 0; return ST_OK; }
-int st_engine_get_deformation_motion(StEngine* e, int* enabled) { ST_REQUIRE(e && enabled, "null argument"); *enabled = E(e)->deform_on ? 1 : 0; return ST_OK; }
+int st_engine_set_deformation_motion(StEngine* e, int enabled) { ST_REQUIRE(e, "null engine"); E(e)->deform.motion_on = enabled != 0; return ST_OK; }
+int st_engine_get_deformation_motion(StEngine* e, int* enabled) { ST_REQUIRE(e && enabled, "null argument"); *enabled = E(e)->deform.motion_on ? 1 : 0; return ST_OK; }
 int st_debug_deformation(StEngine* e, uint64_t* instances_with_previous, uint64_t* previous_bytes) {
     ST_REQUIRE(e && instances_with_previous && previous_bytes, "null argument");
-    return E(e)->deformation_stats(instances_with_previous, previous_bytes);
+    return E(e)->deform.deformation_stats(instances_with_previous, previous_bytes);
 }
 int st_light_insert(StEngine* e, StHandle id, const StLight* l) { ST_REQUIRE(e && l, "null argument"); E(e)->insert_light(id, *l); return ST_OK; }
 int st_light_remove(StEngine* e, StHandle id) { ST_REQUIRE(e, "null engine"); E(e)->remove_light(id); return ST_OK; }

@@ -14,7 +14,7 @@ int Engine::render_aovs(const CameraState& c, const StAovTargets& t, hipStream_t
     a.tile_map = tuning.tile_map;
     L.launch_aov(a, static_cast<float*>(t.planes[ST_AOV_DEPTH]), static_cast<float4*>(t.planes[ST_AOV_NORMAL]), static_cast<float4*>(t.planes[ST_AOV_ALBEDO]),
                  static_cast<float2*>(t.planes[ST_AOV_MOTION]), static_cast<uint64_t*>(t.planes[ST_AOV_INSTANCE]), static_cast<uint32_t*>(t.planes[ST_AOV_TRIANGLE]),
-                 static_cast<const uint4*>(sets[live].instance_table.ptr), t.planes[ST_AOV_MOTION] ? deform_posed() : nullptr, stream);
+                 static_cast<const uint4*>(sets[live].instance_table.ptr), t.planes[ST_AOV_MOTION] ? deform.deform_posed() : nullptr, stream);
     ST_HIP(hipGetLastError());
     return reader_end(stream, false, t.planes[ST_AOV_MOTION] != nullptr);   // (query_end, and the MOTION plane reads previous regions of the posed store)
 }

@@ -7,7 +7,7 @@
 //   st_display.cpp      display transforms: exposure, tone mapping, the auto-exposure state
 //   st_post.cpp         output post-processing: FXAA and the resampler
 //   st_bloom.cpp        bloom: the plan, the chain of launches
-//   st_skin.cpp         skinned meshes and morph targets: stores, the tick's skin launch
+//   st_deform.cpp       mesh deformation (st_deform.h): skinned meshes, morph targets, deformation motion; the tick's launches
 //   st_env.cpp          environment lighting: the map, its importance table
 //   st_query.cpp        scene queries: closest hit, occlusion, picks
 //   st_aov.cpp          per-pixel AOVs
@@ -29,6 +29,7 @@
 #include <cstdio>
 #include <chrono>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <string>
@@ -40,6 +41,7 @@
 #include "st_atlas.h"
 #include "st_bvh.h"
 #include "st_kernels.h"
+#include "st_ranges.h"
 
 #include <thread>
 
@@ -149,28 +151,10 @@ inline V3 sun_transmittance(V3 pos, V3 sun_dir) {
 }
 
 // ------------------------------------------------------------------ small containers
-struct SlotRanges {  // utils/allocator.rs
-    std::vector<std::pair<size_t, size_t>> free_; bool unsorted = false;
-    void give(size_t b, size_t e) { if (!free_.empty()) unsorted |= b <= free_.back().second; free_.push_back({b, e}); }
-    bool take(size_t len, size_t* b, size_t* e) {
-        if (unsorted && !free_.empty()) {
-            std::stable_sort(free_.begin(), free_.end(), [](const auto& l, const auto& r) { return l.first < r.first; });
-            for (size_t i = 0; i + 1 < free_.size();) {
-                if (free_[i].second == free_[i + 1].first) { free_[i].second = free_[i + 1].second; free_.erase(free_.begin() + i + 1); }
-                else i++;
-            }
-        }
-        unsorted = false;
-        for (size_t i = 0; i < free_.size(); i++) {
-            const size_t have = free_[i].second - free_[i].first;
-            if (have < len) continue;
-            *b = free_[i].first; *e = *b + len;
-            if (have == len) free_.erase(free_.begin() + i); else free_[i].first += len;
-            return true;
-        }
-        return false;
-    }
-};
+// The device's object-space triangle (mesh store, bind store, posed store): positions 9, normals 9, uvs 6
+constexpr size_t kTriangleFloats = 24u;
+inline void pack_triangle(const StMeshTriangle& t, float* f) { memcpy(f, t.positions, 9 * sizeof(float)); memcpy(f + 9, t.normals, 9 * sizeof(float)); memcpy(f + 18, t.uvs, 6 * sizeof(float)); }
+inline void unpack_triangle(const float* f, StMeshTriangle& t) { memcpy(t.positions, f, 9 * sizeof(float)); memcpy(t.normals, f + 9, 9 * sizeof(float)); memcpy(t.uvs, f + 18, 6 * sizeof(float)); }   // (tangents stay)
 
 // ------------------------------------------------------------------ owners of HIP resources (the rule: this file's header comment)
 // Each is move-only (a declared move makes a copy a compile error) and lets go in its destructor; `h` / `ptr` stay readable for the calls that use them.
@@ -329,7 +313,19 @@ template <int N> struct FencedPlanes {
     }
     int done(hipStream_t stream) { return read.record(stream); }   // behind the launches that read the planes
 };
+// Room for `bytes` in a store that grows by half: *fresh says it is a new allocation — what the old one held is gone, the caller sends it again.
+// `readers` of the old one are waited for on the host first (hipFree waits too; said there).
+inline int grow_store(DeviceArray& a, size_t bytes, bool* fresh, std::initializer_list<Fence*> readers = {}) {
+    *fresh = bytes > a.capacity;
+    if (!*fresh) return ST_OK;
+    for (Fence* f : readers) if (int rc = f->host_wait()) return rc;
+    return a.reserve(bytes, bytes + bytes / 2);
+}
 inline double format_bytes(uint32_t format) { return format == ST_FORMAT_RGBA32F ? 16.0 : (format == ST_FORMAT_RGBA16F ? 8.0 : 4.0); }   // of one pixel (StOutputFormat)
+
+}  // namespace st
+#include "st_deform.h"
+namespace st {
 
 // ------------------------------------------------------------------ per-camera state (camera_controller/buffers.rs)
 constexpr int kInternalPlanes = 4;  // decoded-surface twins A/B (KArgs::sn / psn) + the pair the variance pass writes ahead of the strides-1+2 wavelet launch
@@ -468,71 +464,8 @@ struct Engine {
     bool any_host_stale() const { for (const auto& i : instances) if (i.host_stale) return true; return false; }
     void bake_stale_on_host();         // brings the host arrays up to date (rebuilds, host refits, full uploads and debug reads need them)
 
-    // Skinned meshes (st_skin.cpp, k_skin.hip; include/strolle_hip.h "skinned meshes"). A skin per mesh: its bind-pose triangles (24 floats each,
-    // the mesh store's layout) and corners go to the skin store once. A pose per instance: the last palette set (12 floats per joint) and a region
-    // of the posed store (24 floats per triangle) that the tick's skin launch fills and k_bvh_bake reads; `host` is its host image (tangents from
-    // the bind mesh), read back only when a host bake needs it. meshes[id] stays the bind pose.
-    struct SkinRec { std::vector<StSkinVertex> corners; uint32_t joints = 0; size_t first = SIZE_MAX; };   // first: its triangles in the skin store (SIZE_MAX: not there yet)
-    std::unordered_map<uint64_t, SkinRec> skins;
-    // Morph targets (include/strolle_hip.h "morph targets"): a target set per mesh, kept in the device layout (st_kernels.h MorphJob: per target
-    // `padded` triangles of 18 floats as five planes), placed in the target store when a tick first needs it. bind_first: a morph-only mesh's
-    // base triangles in the bind store (no corners there); a mesh that also has a skin uses the skin's range.
-    struct MorphRec { std::vector<float> planes; uint32_t targets = 0; size_t count = 0, padded = 0, first = SIZE_MAX, bind_first = SIZE_MAX; };
-    std::unordered_map<uint64_t, MorphRec> morphs;
-    // A deformation per instance: the last joint palette set (12 floats per joint; empty: none), the last morph weights set (one per target;
-    // empty: none, or all zero), or both — never neither — and the instance's region of the posed store.
-    struct DeformRec {
-        uint64_t mesh = 0; std::vector<float> palette, weights; size_t first = SIZE_MAX, count = 0;   // first: its region of the posed store (SIZE_MAX: none yet)
-        bool reskin = true;          // the device region has to be (re)computed at the next tick: the pose or the weights changed, or the posed store was reallocated
-        bool changed = true;         // they changed since the last launch (that launch makes the host image stale)
-        bool host_current = false;   // `host` holds what the device region holds
-        std::vector<StMeshTriangle> host;
-        // deformation motion (below): `other` is the second region — a tick that deforms again writes it and swaps it with `first`, so that it then
-        // holds the positions from before that tick; has_previous says the LAST tick did so. `skinned` / `previous` (+ `_w`) are the palettes and
-        // weights the two regions were computed with (a posed store that grows computes both again into the new allocation); `recorded`: `first`
-        // holds what a tick deformed while the switch was on. All empty / false while the switch is off.
-        size_t other = SIZE_MAX; bool has_previous = false, recorded = false;
-        std::vector<float> skinned, previous, skinned_w, previous_w;
-    };
-    std::unordered_map<uint64_t, DeformRec> poses;
-    // the skin store's host image; ranges of dropped skins go back to skin_free and are reused
-    std::vector<float> skin_bind_host; std::vector<StSkinVertex> skin_corner_host; SlotRanges skin_free;
-    DeviceArray d_skin_bind, d_skin_corners, d_posed, d_skin_jobs, d_skin_starts, d_palettes;
-    // the target store, in units of 18 floats (its host image is the MorphRecs' planes), and the tick's morph jobs
-    DeviceArray d_morph_targets, d_morph_jobs, d_morph_starts, d_morph_active;
-    SlotRanges morph_free; size_t morph_size = 0;
-    uint64_t morph_ticks = 0, morphed_triangles = 0;
-    SlotRanges posed_free; size_t posed_size = 0;   // triangles of the posed store handed out (its allocation holds at least that many)
-    Stream skin_stream; Event ev_skinned;
-    Fence posed_read;   // behind the bakes that read the posed regions (bake_on_device), on whichever streams: the next skin launch overwrites them
-    uint64_t skin_launches = 0, skinned_triangles = 0, posed_readbacks = 0;
-    // Deformation motion (include/strolle_hip.h "skinned meshes"; st_traverse.h deform_prev_point): with the switch on, primary visibility and the AOV launch
-    // read the previous region of every instance the last tick re-skinned, through the free word of the scene copy's instance table (fill_instance_table).
-    // deform_live: instances the last tick left a previous pose. Frames read the posed store then: deform_read is recorded behind every reader
-    // that can reach deform_prev_point (reader_end: frames and the MOTION AOV, not the scene queries) — behind a wait for its own earlier recording, so that one event covers readers on several streams — and the next skin launch,
-    // which overwrites previous regions, waits for it on the skin stream. No host wait (DESIGN.md "Deformation motion").
-    bool deform_on = false; uint64_t deform_live = 0;
-    Fence deform_read;
-    // what primary visibility and the MOTION AOV get as kernel arguments: null unless the last tick left some instance a previous pose (that tick wrote the
-    // live copy's table: a re-skin is a scene change). deform_live is that tick's state — the switch itself is read by st_tick alone, so it takes effect at the next tick
-    const uint4* deform_table() const { return deform_live ? static_cast<const uint4*>(sets[live].instance_table.ptr) : nullptr; }
-    const float* deform_posed() const { return deform_live ? static_cast<const float*>(d_posed.ptr) : nullptr; }
-    void deform_begin_tick();         // forgets last tick's previous poses (and, with the switch off, gives the second regions back)
-    int deformation_stats(uint64_t* instances_with_previous, uint64_t* previous_bytes) const;
-    int set_skin(uint64_t mesh, const StSkinVertex* corners, size_t corner_count, uint32_t joint_count);
-    int set_pose(uint64_t instance, const float* joint_xforms, uint32_t joint_count);
-    int read_posed(uint64_t instance, float* out, size_t capacity_floats, size_t* written_floats);
-    int set_morph_targets(uint64_t mesh, const StMorphDelta* deltas, size_t corner_count, uint32_t target_count);
-    int set_morph_weights(uint64_t instance, const float* weights, uint32_t target_count);
-    int morphing_stats(uint64_t* ticks, uint64_t* triangles, uint64_t* delta_bytes) const;
-    void drop_pose(uint64_t instance, bool make_dirty);   // the whole deformation: palette, weights and regions
-    // one part of it; the deformation itself goes when nothing is left. forget: what the part was made for is gone (a skin or target set replaced):
-    // the previous positions and what they were computed from go too
-    void drop_part(uint64_t instance, bool palette, bool weights, bool forget);
-    void drop_skin(uint64_t mesh);    // and the poses of the instances of that mesh
-    void drop_morph(uint64_t mesh);   // and the weights of the instances of that mesh
-    int skin_tick(hipStream_t stream);   // st_tick, before the refresh: one launch of each kernel at most for every deformation to (re)compute
-    int read_back_posed();            // host images of every posed region they lag behind: one batch, one synchronisation
+    // Mesh deformation — skinned meshes, morph targets, deformation motion — has one owner (st_deform.h)
+    Deformer deform{*this};
     int deferred_status = ST_OK;      // a read-back that failed inside a refresh or bake_stale_on_host (message in g_last_error): st_tick / st_debug_read_scene return it
     int take_deferred_status() { const int rc = deferred_status; deferred_status = ST_OK; return rc; }
 
@@ -545,6 +478,7 @@ struct Engine {
         bool host_stale = false;   // moved on the device since the host arrays (triangles, prims, tri_geo / attr / bounds) were last baked
     };
     std::vector<InstanceRec> instances; bool instances_dirty = false;
+    InstanceRec* find_instance(uint64_t id) { for (auto& r : instances) if (r.id == id) return &r; return nullptr; }
     // per-instance transforms for primary visibility's prev_point (the reference's per-draw push constants,
     // passes/prim_raster.rs:196-230): 8 float4 per stable slot — curr_xform_inv (x, y, z axes, translation), then prev_xform.
     // tri_attr[4 t + 3].w holds the slot of the instance that owns triangle t.
@@ -660,7 +594,7 @@ struct Engine {
     Fence copy_done;   // behind a tick's copies on copy_stream, like tick_done
     struct CopyTarget { int index; hipStream_t up; bool* pageable; bool other; };   // the writer's side: st_tick.cpp pick_copy
     int reader_begin(hipStream_t stream, bool reader);   // the readers' side: st_render.cpp
-    int reader_end(hipStream_t stream, bool lights, bool deform = false);   // deform: the reader can reach deform_prev_point (frames, the MOTION AOV)
+    int reader_end(hipStream_t stream, bool lights, bool reads_previous = false);   // reads_previous: the reader can reach deform_prev_point (frames, the MOTION AOV)
 
     std::unordered_map<uint64_t, std::unique_ptr<CameraState>> cameras; uint64_t next_camera = 0;
 
@@ -724,8 +658,6 @@ struct Engine {
 
     void drop_instance_triangles(uint64_t id);
     void bake(const StMeshTriangle& t, const InstanceRec& inst, uint32_t material, size_t slot);
-    // what a host bake of `inst` reads: the host image of its posed region (skinned meshes), else its mesh (`mesh`)
-    const std::vector<StMeshTriangle>* bake_source(const InstanceRec& inst, const std::vector<StMeshTriangle>& mesh) const;
     struct BakeJob { const std::vector<StMeshTriangle>* mesh; const InstanceRec* inst; uint32_t material; size_t first, count; };
     bool refresh_instances();
     void bake_jobs_on_host(const std::vector<BakeJob>& jobs, size_t total);

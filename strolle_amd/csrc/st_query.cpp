@@ -16,10 +16,8 @@ void Engine::fill_instance_table() {
         const auto r = instance_triangles.find(inst.id);
         if (r == instance_triangles.end() || inst.xslot >= slots) continue;
         uint32_t* w = instance_table_.data() + 4 * (size_t)inst.xslot;
-        w[0] = (uint32_t)inst.id; w[1] = (uint32_t)(inst.id >> 32); w[2] = (uint32_t)r->second.first; w[3] = 0u;
-        if (!deform_live) continue;
-        const auto pose = poses.find(inst.id);
-        if (pose != poses.end() && pose->second.has_previous && pose->second.count == r->second.second - r->second.first) w[3] = (uint32_t)pose->second.other + 1u;
+        w[0] = (uint32_t)inst.id; w[1] = (uint32_t)(inst.id >> 32); w[2] = (uint32_t)r->second.first;
+        w[3] = deform.previous_word(inst.id, r->second.second - r->second.first);
     }
 }
 

@@ -151,13 +151,13 @@ int Engine::reader_begin(hipStream_t stream, bool reader) {
     }
     return ST_OK;
 }
-int Engine::reader_end(hipStream_t stream, bool lights, bool deform) {
+int Engine::reader_end(hipStream_t stream, bool lights, bool reads_previous) {
     if (alternating) if (int rc = sets[live].fence.record(stream)) return rc;
     if (lights && lights_alternating) if (int rc = light_sets[live_lights].fence.record(stream)) return rc;
     if (lights && env_live) if (int rc = env_live->fence.record(stream)) return rc;   // (frames: the map is freed behind its last reader)
-    // this reader (a frame, a MOTION AOV) may read previous regions of the posed store: the next skin launch waits for it (st_engine.h deform_read).
+    // this reader (a frame, a MOTION AOV) may read previous regions of the posed store: the next skin launch waits for it (st_deform.h deform_read).
     // Chained: readers on several streams, one event
-    if (deform && deform_live) if (int rc = deform_read.record_chained(stream)) return rc;
+    if (reads_previous) if (int rc = deform.previous_read_by(stream)) return rc;
     return ST_OK;
 }
 
@@ -350,8 +350,8 @@ struct Frame {
         run(KS_REF_SHADING, ST_PASS_REF_SHADING, [&] { e.L.launch_ref_shading(a, seed(SEED_REF_SHADING + 255u), 255u, cur); });
     }
     void prim() {
-        if (e.tuning.fuse && s.any_objects) run(KS_PRIM_VISIBILITY_REPROJECTION, ST_PASS_PRIM_VISIBILITY | ST_PASS_FRAME_REPROJECTION, [&] { e.L.launch_prim_visibility(a, true, e.deform_table(), e.deform_posed(), cur); });
-        else run(KS_PRIM_VISIBILITY, ST_PASS_PRIM_VISIBILITY, [&] { e.L.launch_prim_visibility(a, false, e.deform_table(), e.deform_posed(), cur); });
+        if (e.tuning.fuse && s.any_objects) run(KS_PRIM_VISIBILITY_REPROJECTION, ST_PASS_PRIM_VISIBILITY | ST_PASS_FRAME_REPROJECTION, [&] { e.L.launch_prim_visibility(a, true, e.deform.deform_table(), e.deform.deform_posed(), cur); });
+        else run(KS_PRIM_VISIBILITY, ST_PASS_PRIM_VISIBILITY, [&] { e.L.launch_prim_visibility(a, false, e.deform.deform_table(), e.deform.deform_posed(), cur); });
         if (s.any_objects && !e.tuning.fuse) run(KS_FRAME_REPROJECTION, ST_PASS_FRAME_REPROJECTION, [&] { e.L.launch_frame_reprojection(a, cur); });
     }
     // DI up to temporal resampling touches only the DI reservoirs and read-only frame inputs ...

@@ -154,8 +154,8 @@ void Engine::bake_jobs_on_host(const std::vector<BakeJob>& jobs, size_t total) {
 // (its primitives), a host refit or a debug read of the stream (tri_bounds), a full upload. Both device copies then receive those slots from
 // the host like any other baked range, and their lists of pending device moves are void.
 void Engine::bake_stale_on_host() {
-    // posed instances bake from their posed regions (st_skin.cpp); a failed read-back is reported by the next st_tick or debug read
-    if (!poses.empty()) if (int rc = read_back_posed()) deferred_status = rc;
+    // posed instances bake from their posed regions (st_deform.cpp); a failed read-back is reported by the next st_tick or debug read
+    if (int rc = deform.read_back()) deferred_status = rc;
     std::vector<BakeJob> jobs; size_t total = 0;
     for (auto& inst : instances) {
         if (!inst.host_stale) continue;
@@ -163,7 +163,7 @@ void Engine::bake_stale_on_host() {
         auto mesh = meshes.find(inst.mesh);
         auto have = instance_triangles.find(inst.id);
         if (mesh == meshes.end() || have == instance_triangles.end() || have->second.second - have->second.first != mesh->second.size()) continue;  // the next refresh re-bakes it as dirty
-        jobs.push_back({bake_source(inst, mesh->second), &inst, inst.baked_material, have->second.first, mesh->second.size()});
+        jobs.push_back({deform.bake_source(inst.id, mesh->second), &inst, inst.baked_material, have->second.first, mesh->second.size()});
         total += mesh->second.size();
         for (SceneSet& t : sets) { t.dirty_lo = std::min(t.dirty_lo, have->second.first); t.dirty_hi = std::max(t.dirty_hi, have->second.second); }
     }
@@ -203,8 +203,8 @@ bool Engine::refresh_instances() {
             return true;
         }
     }
-    // the host bakes this refresh: posed instances from their posed regions, read back in one batch (st_skin.cpp)
-    if (!poses.empty()) if (int rc = read_back_posed()) deferred_status = rc;
+    // the host bakes this refresh: posed instances from their posed regions, read back in one batch (st_deform.cpp)
+    if (int rc = deform.read_back()) deferred_status = rc;
     // instances the device moved earlier and that are not dirty now must catch up first (a rebuild reads every primitive)
     if (any_host_stale()) {
         // re-baked below anyway — but only those whose bake job WILL be queued: an instance whose mesh or material is missing is retried at a
@@ -244,7 +244,7 @@ bool Engine::refresh_instances() {
             triangles.resize(e); prims.resize(e); prim_alive.resize(e, 0); tri_geo.resize(3 * e); tri_attr.resize(4 * e); tri_bounds.resize(2 * e);
             for (SceneSet& t : sets) t.tri_full = true;
         }
-        jobs.push_back({bake_source(inst, mesh->second), &inst, mat->second, b, count});
+        jobs.push_back({deform.bake_source(inst.id, mesh->second), &inst, mat->second, b, count});
         total += count;
         for (SceneSet& t : sets) { t.dirty_lo = std::min(t.dirty_lo, b); t.dirty_hi = std::max(t.dirty_hi, e); }  // slots each device copy still has to receive
         mark_info_dirty(b, e);
@@ -275,26 +275,21 @@ int Engine::bake_on_device(SceneSet& t, hipStream_t up, bool* pageable) {
         auto have = instance_triangles.find(id);
         auto mesh = meshes.find(inst.mesh);
         if (have == instance_triangles.end() || mesh == meshes.end()) continue;
-        // a posed instance (skinned mesh) reads its region of the posed store, which this tick's skin launch brought up to date (st_skin.cpp)
-        auto pose = poses.find(id);
-        // (a pose is dropped with its mesh: its triangle count is the one this instance's slots were baked for)
-        const bool posed = pose != poses.end() && pose->second.first != SIZE_MAX && pose->second.count == have->second.second - have->second.first;
+        // a posed instance (skinned mesh) reads its region of the posed store, which this tick's skin launch brought up to date (st_deform.cpp)
+        size_t posed_first = 0;
+        const bool posed = deform.bake_region(id, have->second.second - have->second.first, &posed_first);
         auto dm = device_meshes.find(inst.mesh);
         if (!posed && (dm == device_meshes.end() || dm->second.version != inst.baked_mesh_version)) {
-            DeviceMeshRec rec{mesh_store_host.size() / 24u, mesh->second.size(), inst.baked_mesh_version};
-            mesh_store_host.reserve(mesh_store_host.size() + 24u * rec.count);
-            for (const StMeshTriangle& m : mesh->second) {
-                for (int v = 0; v < 3; v++) for (int c = 0; c < 3; c++) mesh_store_host.push_back(m.positions[v][c]);
-                for (int v = 0; v < 3; v++) for (int c = 0; c < 3; c++) mesh_store_host.push_back(m.normals[v][c]);
-                for (int v = 0; v < 3; v++) for (int c = 0; c < 2; c++) mesh_store_host.push_back(m.uvs[v][c]);
-            }
+            DeviceMeshRec rec{mesh_store_host.size() / kTriangleFloats, mesh->second.size(), inst.baked_mesh_version};
+            mesh_store_host.resize(kTriangleFloats * (rec.first + rec.count));
+            for (size_t i = 0; i < rec.count; i++) pack_triangle(mesh->second[i], &mesh_store_host[kTriangleFloats * (rec.first + i)]);
             device_meshes[inst.mesh] = rec; dm = device_meshes.find(inst.mesh); store_grew = true;
         }
         const Affine& inv = inst.xform_inv;
         Job j;
         j.x = f4(inst.xform.x, 0.0f); j.y = f4(inst.xform.y, 0.0f); j.z = f4(inst.xform.z, 0.0f); j.t = f4(inst.xform.t, 0.0f);
         j.r0 = make_float4(inv.x.x, inv.y.x, inv.z.x, 0.0f); j.r1 = make_float4(inv.x.y, inv.y.y, inv.z.y, 0.0f); j.r2 = make_float4(inv.x.z, inv.y.z, inv.z.z, 0.0f);
-        j.mesh_first = posed ? (uint32_t)pose->second.first : (uint32_t)dm->second.first; j.count = posed ? (uint32_t)pose->second.count : (uint32_t)dm->second.count; j.slot_first = (uint32_t)have->second.first; j.xslot = inst.xslot;
+        j.mesh_first = posed ? (uint32_t)posed_first : (uint32_t)dm->second.first; j.count = posed ? (uint32_t)(have->second.second - have->second.first) : (uint32_t)dm->second.count; j.slot_first = (uint32_t)have->second.first; j.xslot = inst.xslot;
         if (posed) { j.x.w = b2f(1u); reads_posed = true; }
         jobs.push_back(j); starts.push_back(starts.back() + j.count);
     }
@@ -310,14 +305,14 @@ int Engine::bake_on_device(SceneSet& t, hipStream_t up, bool* pageable) {
     }
     if ((rc = t.bake_jobs.upload(jobs.data(), jobs.size() * sizeof(Job), up, staging, pageable))) return rc;
     if ((rc = t.bake_starts.upload(starts.data(), starts.size() * sizeof(uint32_t), up, staging, pageable))) return rc;
-    if (reads_posed) if ((rc = ev_skinned.wait(up))) return rc;   // the skin launch (skin stream) wrote the posed regions
+    if (reads_posed) if ((rc = deform.wait_skinned(up))) return rc;   // the skin launch (skin stream) wrote the posed regions
     // the EXACT build's kernel, whatever arithmetic the frames use: the baked arrays are the host's bits
     launchers_exact().launch_bvh_bake(t.bake_jobs.ptr, static_cast<const uint32_t*>(t.bake_starts.ptr), (uint32_t)jobs.size(), starts.back(), static_cast<const float*>(d_mesh_store.ptr),
-                                      static_cast<const float*>(d_posed.ptr), static_cast<float4*>(t.tri_geo.ptr), static_cast<float4*>(t.tri_bounds.ptr), static_cast<float4*>(t.tri_attr.ptr),
+                                      deform.posed_store(), static_cast<float4*>(t.tri_geo.ptr), static_cast<float4*>(t.tri_bounds.ptr), static_cast<float4*>(t.tri_attr.ptr),
                                       static_cast<float4*>(t.bvh.ptr), t.device_built ? nullptr : static_cast<const uint32_t*>(t.entry_of_tri.ptr), up);
     // the next skin launch overwrites the regions after this bake — and after an earlier one still pending on another stream:
     // the event is re-recorded here behind a wait for its previous recording, so that it covers both (the bake itself is not delayed)
-    if (reads_posed) if ((rc = posed_read.record_chained(up))) return rc;
+    if (reads_posed) if ((rc = deform.posed_read_by(up))) return rc;
     device_bakes++; device_baked_triangles += starts.back();
     return ST_OK;
 }

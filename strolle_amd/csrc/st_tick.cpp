@@ -146,12 +146,12 @@ int Engine::build_on_device(SceneSet& t, hipStream_t up, bool* pageable) {
 // ---- tick (lib.rs:301-395)
 int Engine::tick(hipStream_t stream) {
     // skinned meshes: the poses set since the last tick are skinned first — a host bake of this refresh reads their posed triangles back
-    const bool skinning = has_device && !poses.empty();
-    deform_begin_tick();   // (deformation motion: a previous pose lasts one tick)
+    const bool skinning = has_device && deform.any();
+    deform.begin_tick();   // (deformation motion: a previous pose lasts one tick)
     if (skinning) {
         ST_HIP(hipSetDevice(device));
         staging.begin_tick();
-        if (int rc = skin_tick(stream)) return rc;
+        if (int rc = deform.tick(stream)) return rc;
     }
     const TreePlan plan = refresh_scene();
     apply_environment();   // (before the lights: a map switches the sun, light 0, off)

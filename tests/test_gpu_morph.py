@@ -1,4 +1,4 @@
-"""GPU tests of morph targets (include/strolle_hip.h "morph targets"; k_skin.hip k_morph, st_skin.cpp).
+"""GPU tests of morph targets (include/strolle_hip.h "morph targets"; k_skin.hip k_morph, st_deform.cpp).
 
 Engine A morphs on the device: targets per mesh, weights per instance. The posed store's bits are tests/morph_ref.py's (and skin_ref's behind
 it where the instance has a pose too); everything downstream is what a second engine gives in which the numpy-morphed triangles were

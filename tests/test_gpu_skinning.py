@@ -1,4 +1,4 @@
-"""GPU tests of skinned meshes (include/strolle_hip.h "skinned meshes"; k_skin.hip, st_skin.cpp).
+"""GPU tests of skinned meshes (include/strolle_hip.h "skinned meshes"; k_skin.hip, st_deform.cpp).
 
 Engine A skins on the device: a skin per mesh, a pose per instance. Engine B is the same scene without skinning: every posed instance has a
 mesh of its own into which B re-inserts A's read-back posed triangles each tick. What A renders, bakes and answers must be what B does."""
