@@ -677,6 +677,79 @@ int st_bloom_process(StEngine* e, const StBloomDesc* desc, const StDisplayDesc* 
  * (0 on a host-only engine). */
 int st_debug_set_bloom_tail(StEngine* e, int lds_bytes, uint32_t* in_force);
 
+/* ---- motion blur (NEW seam): a velocity-driven gather in front of bloom (st_motion_blur.cpp, k_motion_blur.hip). The node Bevy's graph
+ * places directly before bloom (motion blur -> bloom -> tonemapping -> FXAA -> upscaling), and the first user-visible consumer of the
+ * renderer's per-pixel motion (the velocity map, ST_AOV_MOTION, deformation motion).
+ * - Order: rendering -> motion blur -> bloom -> display transform -> FXAA -> resample -> output format.
+ * - Scope: the setting belongs to the camera and takes effect at its next st_render_camera. It changes only what is written to
+ *   `out_device`: AOVs, picks, scene queries, the HDR history, every plane st_camera_read_buffer returns (with the one exception below) and
+ *   the auto-exposure metering (it keeps metering the composed frame in the composing launch, before the blur) are unchanged. desc == NULL
+ *   turns it off: the frame then launches the kernels it launches without the setting, with the same arguments, and st_debug_last_launches
+ *   is unchanged. The setting survives st_camera_update and st_engine_set_arithmetic. Modes without a velocity map skip the blur:
+ *   ST_MODE_REFERENCE and ST_MODE_BVH_HEATMAP run no primary-visibility pass, and their frames are bit for bit the frames without the
+ *   setting. Sky pixels have velocity 0 in the renderer's map, so the sky is not blurred by camera rotation; moving geometry still blurs
+ *   over it (sky velocity from the camera matrices is not offered). The one plane whose contents the setting changes is
+ *   ST_BUF_VELOCITY_MAP: the default frame (fast build, Image{denoise}) keeps the velocity in registers and leaves that plane stale; while
+ *   a camera blurs, primary visibility stores it (16 B per pixel) and st_camera_buffer_stale reports it as current. Nothing else about that
+ *   frame changes. What "at rest" means is per tile neighbourhood (step 4): a static pixel in a tile next to a moving one goes through the
+ *   gather, where its weights make it c(X), so it comes back clamped to [0, 65504] (NaN as 0) with alpha 1, not with C(X)'s own bits;
+ *   only pixels of tiles whose 3 x 3 neighbourhood is at rest pass through untouched. While a frame blurs, the composing launch writes the composed colour, untransformed, into a camera-owned render-size
+ *   RGBA32F plane (and meters it); three launches (ST_PASS_POST) belong to the blur: pack (with the tile maximum) as soon as primary
+ *   visibility is through, and the neighbour maximum and the gather behind the composing launch, in front of bloom, FXAA and the resampler.
+ * - Arithmetic: float32, evaluated left to right as written, no fused multiply-add, division and square root correctly rounded, in BOTH
+ *   builds; tests/motion_blur_ref.py restates all of it in numpy and the kernels match it bit for bit. min, max and
+ *   clamp01(x) = min(max(x, 0), 1) use the post-processing section's NaN rule (min(a, b) is a when a < b or b is NaN, else b; max likewise
+ *   with >). The frame is W x H. C is the composed HDR colour, V the velocity in pixels (current minus previous screen position), Z the
+ *   distance along the camera ray. In a frame, V is the velocity map's xy and Z is PRIM_GBUFFER_D0.x of the frame's parity, with 0 (sky) read
+ *   as FLT_MAX; in st_motion_blur_process V and Z are the given planes as they are. R = max_radius, S = samples, e_s = depth_softness, each
+ *   after its default is applied.
+ * - 1. Pack (per pixel): h = 0.5 shutter (one float). v = (V.x h, V.y h); r = sqrt(v.x v.x + v.y v.y). If not r >= 0.5 (NaN included):
+ *   v = 0, r = 0. Else if r > R: k = R / r; v = (v.x k, v.y k); r = R. (r, Z) is stored as a float2 plane; v feeds step 2.
+ * - 2. Tile maximum: tiles are 32 x 32 pixels, ceil(W / 32) x ceil(H / 32) of them. A tile's vector is the v of its pixel with the largest
+ *   r; among equal r the first pixel in row-major order wins; a tile with all r = 0 has vector 0. (A 64-bit key, r's bits above the complement
+ *   of the pixel's index in the tile, makes this one unsigned max, reduced with cross-lane operations and one LDS step per workgroup.) Pack
+ *   and tile maximum are one launch.
+ * - 3. Neighbour maximum: n(tile) is the tile vector with the largest r over the 3 x 3 tiles around it that exist; ties go to the first in
+ *   row-major order of (dy, dx); r_n is its length as stored, not recomputed. One small launch.
+ * - 4. Gather (per pixel X = (x, y), with n and r_n of its tile): if r_n < 0.5, the result is C(X) with its own bits: NaN and infinities pass
+ *   through. Otherwise let c(Y) be C(Y) with each of r, g, b as min(max(., 0), 65504), so that one infinite pixel cannot poison a streak, and
+ *   (r_X, Z_X), (r_Y, Z_Y) the packed values. j = 0 with ST_MOTION_BLUR_NO_JITTER; otherwise j = (B[y & 3][x & 3] + 0.5) / 16 - 0.5, with B
+ *   the 4 x 4 Bayer matrix {0 8 2 10 / 12 4 14 6 / 3 11 1 9 / 15 7 13 5}. w_0 = 1 / max(r_X, 0.5); sum = c(X) w_0; wsum = w_0. For
+ *   i = 0 .. S - 1, in order: t = ((i + 0.5 + j) 2) / S - 1; p = (x + 0.5 + n.x t, y + 0.5 + n.y t); Y = (floor p.x, floor p.y), each
+ *   clamped to the image (in float, as min(max(floor p, 0), side - 1): NaN reads texel 0); d = |t| r_n; e = max(e_s min(Z_X, Z_Y), 1e-6);
+ *   f = clamp01(1 - (Z_Y - Z_X) / e); b = clamp01(1 - (Z_X - Z_Y) / e); cone(d, r) = r > 0 ? clamp01(1 - d / r) : 0; cyl(d, r) = 0 for
+ *   r = 0, else 1 - q q (3 - 2 q) with q = clamp01((d - 0.95 r) / (1.05 r - 0.95 r));
+ *   w = (f cone(d, r_Y) + b cone(d, r_X)) + (cyl(d, r_Y) cyl(d, r_X)) 2; sum += c(Y) w per channel; wsum += w. The result is sum / wsum per
+ *   channel, alpha 1. This is the reconstruction filter of McGuire et al. 2012 with nearest-texel taps. The result goes through the display
+ *   transform and the output format when the blur is the last HDR node; with bloom on it is stored untransformed as RGBA32F into the plane
+ *   bloom reads.
+ * - Tiles: the gather reads up to 32 pixels across tile edges, and the tile grid is the frame's, so a camera cannot have motion blur and a
+ *   window (st_camera_set_window, st_dist_set_partition, st_dist_set_grid) at once: ST_ERR_INVALID_ARGUMENT from whichever setter comes
+ *   second, as for bloom. For tiled frames rank 0 runs st_motion_blur_process on the gathered colour, MOTION and DEPTH planes.
+ * - Errors: ST_ERR_INVALID_ARGUMENT for a wrong struct_size, unknown flags, an odd samples or one outside 2..32 other than 0, a field
+ *   outside its range (NaN included), null pointers where they are not allowed, a frame side of 0 or above 16384 in the process call, and an
+ *   auto-exposure display passed to the process call. An unknown camera is ST_ERR_UNKNOWN_CAMERA. Set and get are host work and valid on a
+ *   host-only engine; st_motion_blur_process returns ST_ERR_NO_DEVICE there. */
+enum { ST_MOTION_BLUR_NO_JITTER = 1 };
+typedef struct StMotionBlurDesc {          /* 24 B */
+    uint32_t struct_size;                  /* sizeof(StMotionBlurDesc) */
+    uint32_t flags;                        /* ST_MOTION_BLUR_* */
+    uint32_t samples;                      /* even, 2..32; 0 = default 8 */
+    float shutter;                         /* fraction of the frame interval the shutter is open: finite, 0 <= shutter <= 4; Bevy's default is 0.5 */
+    float max_radius;                      /* pixels, 0 < r <= 32; 0 = default 32 */
+    float depth_softness;                  /* relative depth extent of the soft depth test, 0 < s <= 1; 0 = default 0.05 */
+} StMotionBlurDesc;
+int st_camera_set_motion_blur(StEngine* e, StHandle camera, const StMotionBlurDesc* desc);   /* NULL = off */
+/* the last desc set (a zeroed desc with struct_size when none was) and whether the blur is on; either pointer may be NULL */
+int st_camera_get_motion_blur(StEngine* e, StHandle camera, StMotionBlurDesc* out, int* enabled);
+/* Stateless, like st_bloom_process. color: RGBA32F; velocity: f32x2 (ST_AOV_MOTION's layout); depth: f32 (ST_AOV_DEPTH's layout, FLT_MAX on
+ * sky); display NULL = none, manual exposure only; dst in dst_format, width x height. Needs a device engine; no camera, no tick. Enqueued
+ * on hip_stream without a host sync. The packed plane and the tile vectors are engine-owned: allocated (with a device sync) only when a call
+ * needs larger ones than any before it, and calls on different streams are ordered by the engine. No input may overlap dst. */
+int st_motion_blur_process(StEngine* e, const StMotionBlurDesc* desc, const StDisplayDesc* display, const void* color_device,
+                           const void* velocity_device, const void* depth_device, uint32_t width, uint32_t height,
+                           void* dst_device, int dst_format /* StOutputFormat */, void* hip_stream);
+
 /* ---- multi-GPU behind the boundary (NEW seam; SURVEY.md section 8e, BASELINE.json configs 4 and 5). One process per GPU, one
  * engine per process, the scene replicated; the frame is cut into tiles, every rank renders its tile (+ an apron of redundant
  * pixels in Image mode, whose passes read neighbours) with absolute pixel coordinates, and the ONE collective of the path
@@ -856,7 +929,7 @@ enum StPassBit {
     ST_PASS_DENOISE_REPROJECT_DI = 1u << 18, ST_PASS_DENOISE_REPROJECT_GI = 1u << 19, ST_PASS_DENOISE_VARIANCE = 1u << 20,
     ST_PASS_DENOISE_WAVELET_0 = 1u << 21, /* ... wavelet pass n = ST_PASS_DENOISE_WAVELET_0 << n, n < 5 */
     ST_PASS_COMPOSITION = 1u << 26, ST_PASS_BVH_HEATMAP = 1u << 27, ST_PASS_REF_TRACING = 1u << 28, ST_PASS_REF_SHADING = 1u << 29,
-    ST_PASS_POST = 1u << 30   /* the launches behind composition, one launch group: bloom ("bloom" above), then FXAA and / or the resampler ("post-processing") */
+    ST_PASS_POST = 1u << 30   /* the launches behind composition, one launch group: motion blur ("motion blur" above), bloom ("bloom"), then FXAA and / or the resampler ("post-processing") */
 };
 int st_debug_set_pass_mask(StEngine* e, uint64_t mask);
 /* Measurement only (tools/pair_matrix.py): the frame's graph is built as always — every fusion of the whole frame — but only the launches

@@ -310,6 +310,24 @@ extern "C" {
     pub fn st_bloom_process(e: *mut StEngine, desc: *const StBloomDesc, display: *const StDisplayDesc, src_rgba32f_device: *const c_void, width: u32, height: u32, dst_device: *mut c_void, dst_format: i32, hip_stream: *mut c_void) -> i32;
 }
 
+// motion blur (include/strolle_hip.h "motion blur"): a velocity-driven gather in front of bloom
+pub const ST_MOTION_BLUR_NO_JITTER: u32 = 1;
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct StMotionBlurDesc {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub samples: u32,
+    pub shutter: f32,
+    pub max_radius: f32,
+    pub depth_softness: f32,
+}
+extern "C" {
+    pub fn st_camera_set_motion_blur(e: *mut StEngine, camera: u64, desc: *const StMotionBlurDesc) -> i32; // null = off
+    pub fn st_camera_get_motion_blur(e: *mut StEngine, camera: u64, out: *mut StMotionBlurDesc, enabled: *mut i32) -> i32;
+    pub fn st_motion_blur_process(e: *mut StEngine, desc: *const StMotionBlurDesc, display: *const StDisplayDesc, color_device: *const c_void, velocity_device: *const c_void, depth_device: *const c_void, width: u32, height: u32, dst_device: *mut c_void, dst_format: i32, hip_stream: *mut c_void) -> i32;
+}
+
 // ---- the HIP runtime, as far as the staging-copy present needs it (libamdhip64)
 pub type hipStream_t = *mut c_void;
 extern "C" {

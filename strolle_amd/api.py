@@ -180,6 +180,21 @@ def post_desc(fxaa: bool = False, output_size=None, filter=ResampleFilter.BILINE
                       float(fxaa_edge_threshold_min), float(fxaa_subpixel))
 
 
+class StMotionBlurDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("samples", C.c_uint32), ("shutter", C.c_float), ("max_radius", C.c_float),
+                ("depth_softness", C.c_float)]
+
+
+MOTION_BLUR_NO_JITTER = 1
+
+
+def motion_blur_desc(shutter: float = 0.5, samples: int = 0, max_radius: float = 0.0, depth_softness: float = 0.0, jitter: bool = True) -> StMotionBlurDesc:
+    """A StMotionBlurDesc; the defaults are Bevy's shutter angle of 0.5, 8 samples, a 32-pixel radius and a depth softness of 0.05
+    (include/strolle_hip.h "motion blur")."""
+    return StMotionBlurDesc(C.sizeof(StMotionBlurDesc), 0 if jitter else MOTION_BLUR_NO_JITTER, int(samples), float(shutter), float(max_radius),
+                            float(depth_softness))
+
+
 class StBloomDesc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("levels", C.c_uint32), ("intensity", C.c_float),
                 ("low_frequency_boost", C.c_float), ("low_frequency_boost_curvature", C.c_float), ("high_pass_frequency", C.c_float),
@@ -520,6 +535,10 @@ class _Binding:
             self.bloom_plan = fn("bloom_plan", [P(StBloomDesc), u32, u32, P(u32), P(u32), P(C.c_float)])
             self.debug_set_bloom_tail = fn("debug_set_bloom_tail", [vp, i32, P(u32)])
             self.bloom_process = fn("bloom_process", [vp, P(StBloomDesc), P(StDisplayDesc), vp, u32, u32, vp, i32, vp])
+        if hasattr(lib, prefix + "camera_set_motion_blur"):   # motion blur (likewise)
+            self.camera_set_motion_blur = fn("camera_set_motion_blur", [vp, u64, P(StMotionBlurDesc)])
+            self.camera_get_motion_blur = fn("camera_get_motion_blur", [vp, u64, P(StMotionBlurDesc), P(i32)])
+            self.motion_blur_process = fn("motion_blur_process", [vp, P(StMotionBlurDesc), P(StDisplayDesc), vp, vp, vp, u32, u32, vp, i32, vp])
         if hasattr(lib, prefix + "mesh_set_skin"):
             self.mesh_set_skin = fn("mesh_set_skin", [vp, u64, vp, sz, u32])
         if hasattr(lib, prefix + "mesh_set_morph_targets"):   # morph targets (likewise absent from an older library)
@@ -1049,6 +1068,26 @@ class Engine(EngineBase):
         out = C.c_uint32()
         self._check(self._b.debug_set_bloom_tail(self._h, int(lds_bytes), C.byref(out)))
         return out.value
+
+    # ---- motion blur (include/strolle_hip.h "motion blur"): takes effect at the camera's next render
+    def set_motion_blur(self, camera: int, desc: Optional[StMotionBlurDesc] = None, **kw):
+        """st_camera_set_motion_blur: a StMotionBlurDesc, or motion_blur_desc(**kw) when keywords are given; neither = off."""
+        if desc is None and kw:
+            desc = motion_blur_desc(**kw)
+        self._check(self._b.camera_set_motion_blur(self._h, camera, C.byref(desc) if desc is not None else None))
+
+    def get_motion_blur(self, camera: int):
+        """st_camera_get_motion_blur: (the last StMotionBlurDesc set, whether the blur is on)."""
+        d, on = StMotionBlurDesc(), C.c_int()
+        self._check(self._b.camera_get_motion_blur(self._h, camera, C.byref(d), C.byref(on)))
+        return d, bool(on.value)
+
+    def motion_blur_process(self, desc: StMotionBlurDesc, color_ptr: int, velocity_ptr: int, depth_ptr: int, width: int, height: int, dst_ptr: int,
+                            dst_format: int = 0, display: Optional[StDisplayDesc] = None, stream: int = 0):
+        """st_motion_blur_process: the blur over any RGBA32F colour, f32x2 velocity and f32 depth device planes, then the (manual) display
+        transform, into dst (width x height) in dst_format."""
+        self._check(self._b.motion_blur_process(self._h, C.byref(desc), C.byref(display) if display is not None else None, color_ptr, velocity_ptr,
+                                                depth_ptr, width, height, dst_ptr, int(dst_format), stream))
 
     # ---- environment lighting (include/strolle_hip.h "environment lighting"): takes effect at the next tick
     def set_environment(self, texels, intensity: float = 1.0, yaw: float = 0.0, keep_sun: bool = False, uniform: bool = False):

@@ -191,7 +191,8 @@ __global__ ST_KERNEL_BOUNDS void k_prim_visibility(const KArgs a_in, const uint4
     count_rays(a, used_);
     if (!hit_is_some(hit)) {  // LoadOp::Clear(TRANSPARENT)
         tex_write(a.g0, a, pos, f4z()); tex_write(a.g1, a, pos, f4z());
-        if (!(REPROJECT && (a.lean & kLeanPrim))) { tex_write(a.sm, a, pos, f4z()); tex_write(a.velocity, a, pos, f4z()); }
+        if (!(REPROJECT && (a.lean & kLeanPrim))) tex_write(a.sm, a, pos, f4z());
+        if (!(REPROJECT && (a.lean & kLeanPrim)) || (a.lean & kLeanKeepVelocity)) tex_write(a.velocity, a, pos, f4z());
         tex_write(a.sn, a, pos, f4z());
         if (REPROJECT) tex_write(a.reprojection, a, pos, f4z());
         return;
@@ -226,7 +227,7 @@ __global__ ST_KERNEL_BOUNDS void k_prim_visibility(const KArgs a_in, const uint4
     if (deform_posed != nullptr) (void)deform_prev_point(a, deform_table, deform_posed, hit.xform_slot, c.tri, c.u, c.v, &prev_point);
     const V2 velocity = clip_to_screen(a.cam, world_to_clip(a.cam, hit.point)) - clip_to_screen(a.prev_cam, world_to_clip(a.prev_cam, prev_point));
     const bool moving = dot(velocity, velocity) >= 0.001f;
-    if (!lean) tex_write(a.velocity, a, pos, moving ? make_float4(velocity.x, velocity.y, 0.0f, 0.0f) : f4z());
+    if (!lean || (a.lean & kLeanKeepVelocity)) tex_write(a.velocity, a, pos, moving ? make_float4(velocity.x, velocity.y, 0.0f, 0.0f) : f4z());
     if (REPROJECT) {
         Surface surface; surface.normal = normal_decode(en); surface.depth = g.depth; surface.roughness = 0.0f;
         frame_reprojection_pixel(a, pos, surface, moving ? velocity : v2(0.0f, 0.0f));

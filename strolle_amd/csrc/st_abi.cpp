@@ -273,6 +273,7 @@ int st_camera_set_window(StEngine* e, StHandle h, uint32_t x0, uint32_t y0, uint
     ST_REQUIRE(full || !s.display_auto(), "a window on a camera with auto-exposure would meter the tile alone (include/strolle_hip.h \"display transforms\")");
     ST_REQUIRE(full || !s.post_on, "a window on a camera with post-processing: FXAA and the resampler read across tile edges (include/strolle_hip.h \"post-processing\")");
     ST_REQUIRE(full || !s.bloom_on, "a window on a camera with bloom: the pyramid reads far across tile edges (include/strolle_hip.h \"bloom\")");
+    ST_REQUIRE(full || !s.mblur_on, "a window on a camera with motion blur: the gather reads up to 32 pixels across tile edges (include/strolle_hip.h \"motion blur\")");
     s.row0 = y0; s.row1 = y1; s.col0 = x0; s.col1 = x1;
     return ST_OK;
 }
@@ -375,6 +376,28 @@ int st_bloom_plan(const StBloomDesc* desc, uint32_t width, uint32_t height, uint
 int st_bloom_process(StEngine* e, const StBloomDesc* desc, const StDisplayDesc* display, const void* src, uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
     ST_REQUIRE(e, "null engine");
     return E(e)->bloom_process(desc, display, src, width, height, dst, dst_format, static_cast<hipStream_t>(stream));
+}
+
+// ---- motion blur (st_motion_blur.cpp)
+int st_camera_set_motion_blur(StEngine* e, StHandle h, const StMotionBlurDesc* desc) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    return E(e)->set_motion_blur(*it->second, desc);
+}
+int st_camera_get_motion_blur(StEngine* e, StHandle h, StMotionBlurDesc* out, int* enabled) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    const CameraState& s = *it->second;
+    if (out) { *out = s.mblur; out->struct_size = sizeof(StMotionBlurDesc); }
+    if (enabled) *enabled = s.mblur_on ? 1 : 0;
+    return ST_OK;
+}
+int st_motion_blur_process(StEngine* e, const StMotionBlurDesc* desc, const StDisplayDesc* display, const void* color, const void* velocity, const void* depth,
+                           uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
+    ST_REQUIRE(e, "null engine");
+    return E(e)->motion_blur_process(desc, display, color, velocity, depth, width, height, dst, dst_format, static_cast<hipStream_t>(stream));
 }
 
 int st_debug_set_bloom_tail(StEngine* e, int lds_bytes, uint32_t* in_force) {
@@ -494,7 +517,7 @@ int st_camera_buffer_stale(StEngine* e, StHandle h, int id, int* stale) {
     const CameraState& c = *it->second;
     const uint32_t lean = c.last_lean;
     bool s = false;
-    if (lean & kLeanPrim) s |= id == ST_BUF_VELOCITY_MAP || id == ST_BUF_PRIM_SURFACE_MAP_A || id == ST_BUF_PRIM_SURFACE_MAP_B;
+    if (lean & kLeanPrim) s |= (id == ST_BUF_VELOCITY_MAP && !(lean & kLeanKeepVelocity)) || id == ST_BUF_PRIM_SURFACE_MAP_A || id == ST_BUF_PRIM_SURFACE_MAP_B;   // (a frame that blurs keeps the velocity map)
     if (lean & kLeanSamples) s |= id == ST_BUF_DI_DIFF_SAMPLES || id == ST_BUF_GI_DIFF_SAMPLES;
     if (lean & kLeanGiRes2) s |= id == ST_BUF_GI_RESERVOIRS_2;
     if (lean & kLeanGiMid) s |= id == ST_BUF_GI_RESERVOIRS_3;

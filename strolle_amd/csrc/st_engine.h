@@ -7,6 +7,7 @@
 //   st_display.cpp      display transforms: exposure, tone mapping, the auto-exposure state
 //   st_post.cpp         output post-processing: FXAA and the resampler
 //   st_bloom.cpp        bloom: the plan, the chain of launches
+//   st_motion_blur.cpp  motion blur: the plan, its three launches
 //   st_deform.cpp       mesh deformation (st_deform.h): skinned meshes, morph targets, deformation motion; the tick's launches
 //   st_env.cpp          environment lighting: the map, its importance table
 //   st_query.cpp        scene queries: closest hit, occlusion, picks
@@ -393,6 +394,13 @@ struct CameraState {
     StBloomDesc bloom{}; bool bloom_on = false;
     FencedPlanes<2> bloom_planes;   // [0] the HDR plane, [1] the pyramid
     bool blooms() const { return bloom_on && desc.mode != ST_MODE_BVH_HEATMAP; }   // heatmap frames are false colour
+    // Motion blur (st_motion_blur.cpp; include/strolle_hip.h "motion blur"), in front of bloom; it survives st_camera_update like the rest of the
+    // output chain. While a frame blurs, primary visibility keeps the velocity map (kLeanKeepVelocity), the pack launch turns it and the depth
+    // into the packed plane and the tile vectors before the next frame's primary visibility may start, the composing launch writes the HDR plane
+    // and the gather writes where the composing launch would have (or bloom's HDR plane). Grown and fenced like bloom_planes.
+    StMotionBlurDesc mblur{}; bool mblur_on = false;
+    FencedPlanes<4> mblur_planes;   // [0] the HDR plane, [1] (r, Z) per pixel, [2] the tile vectors, [3] their 3 x 3 neighbour maxima
+    bool blurs() const { return mblur_on && desc.mode != ST_MODE_BVH_HEATMAP && desc.mode != ST_MODE_REFERENCE; }   // those two run no primary-visibility pass: no velocity map
     uint32_t out_width() const { return post_on && post.output_width != 0u ? post.output_width : desc.width; }
     uint32_t out_height() const { return post_on && post.output_width != 0u ? post.output_height : desc.height; }
     // A present copy still in flight writes the caller's host memory: it lands before the stream goes. Everything else goes with its member —
@@ -773,6 +781,17 @@ struct Engine {
     uint32_t bloom_tail_bytes();
     static uint32_t bloom_tail_first(const BloomPlan& plan, uint32_t tail_lds_bytes);   // the first level the tail takes (== plan.levels: none)
     FencedPlanes<1> bloom_scratch;   // st_bloom_process's pyramid: likewise
+    // ---- motion blur (st_motion_blur.cpp)
+    struct MBlurPlan { uint32_t tiles_x = 0, tiles_y = 0; size_t packed_bytes = 0, tile_bytes = 0; };
+    struct MBlurStep { int slot; MBlurArgs args; double bytes; };
+    struct MBlurSteps { MBlurStep step[3]; };   // pack (+ tile maximum), neighbour maximum, gather
+    static int mblur_plan(const StMotionBlurDesc& d, uint32_t w, uint32_t h, MBlurPlan& plan);   // checks the desc
+    static MBlurSteps mblur_steps(const StMotionBlurDesc& d, const MBlurPlan& plan, const void* color, const void* velocity, const void* depth, bool frame, uint32_t w, uint32_t h,
+                                  float2* packed, float4* tile_max, float4* tile_n, void* dst, uint32_t format, bool raw, const DisplayArgs& display);
+    int set_motion_blur(CameraState& c, const StMotionBlurDesc* desc);
+    void launch_mblur_step(const MBlurStep& s, hipStream_t stream);
+    int motion_blur_process(const StMotionBlurDesc* desc, const StDisplayDesc* display, const void* color, const void* velocity, const void* depth, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
+    FencedPlanes<3> mblur_scratch;   // st_motion_blur_process's packed plane and tile vectors: grown, never shrunk
     int scene_args(KArgs& a, bool heatmap) const;   // the scene half of KArgs (st_render.cpp): render() and the scene queries
     void light_args(KArgs& a) const;                // its lights, LUT and environment half: render()
 

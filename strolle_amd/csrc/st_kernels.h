@@ -41,6 +41,7 @@ enum KernelSlot {
     KS_DENOISE_WAVELET_FAMILY,  // profiling only (ST_PROFILE_GROUP_ATROUS): the a-trous chain's launches timed as ONE interval
     KS_POST_FXAA, KS_POST_RESAMPLE,  // output post-processing behind composition (k_post.hip); their bytes depend on the output size and format: render() credits them itself
     KS_BLOOM_DOWN, KS_BLOOM_UP, KS_BLOOM_COMPOSITE, KS_BLOOM_TAIL,  // bloom in front of the display transform (k_bloom.hip); bytes depend on the level: render() credits them itself
+    KS_MBLUR_PACK, KS_MBLUR_NEIGHBOUR, KS_MBLUR_GATHER,  // motion blur in front of bloom (k_motion_blur.hip); render() credits their bytes itself
     KS_COUNT
 };
 struct KernelInfo { const char* name; float bytes_per_unit; bool half; };
@@ -72,6 +73,7 @@ inline const KernelInfo& kernel_info(int slot) {
         {"post_fxaa", 0.f, false},           {"post_resample", 0.f, false},
         {"bloom_down", 0.f, false},          {"bloom_up", 0.f, false},             {"bloom_composite", 0.f, false},
         {"bloom_tail", 0.f, false},
+        {"motion_blur_pack", 0.f, false},    {"motion_blur_neighbour", 0.f, false}, {"motion_blur_gather", 0.f, false},
     };
     return k[slot];
 }

@@ -92,3 +92,8 @@ ST_LAUNCHER(launch_bloom_composite, (const BloomArgs& p, hipStream_t s))
 // ... and the fused tail: the last levels down and back up in one single-workgroup launch, in LDS (`limit`: the bytes that launch may use here)
 ST_LAUNCHER(launch_bloom_tail_limit, (uint32_t* bytes))
 ST_LAUNCHER(launch_bloom_tail, (const BloomTailArgs& p, hipStream_t s))
+// motion blur (k_motion_blur.hip; st_motion_blur.cpp): pack + per-tile maximum (one workgroup per 32 x 32 tile), the 3 x 3 neighbour maximum over
+// the tile vectors, and the gather (one workgroup per 32 x 8 pixels: the tile's vector is uniform in it; tiles at rest are a copy)
+ST_LAUNCHER(launch_mblur_pack, (const MBlurArgs& p, hipStream_t s))
+ST_LAUNCHER(launch_mblur_neighbour, (const MBlurArgs& p, hipStream_t s))
+ST_LAUNCHER(launch_mblur_gather, (const MBlurArgs& p, hipStream_t s))

@@ -167,10 +167,12 @@ namespace {
 // The frame's output chain, decided once. Output post-processing (st_post.cpp): while the frame needs it, the composing launch writes the
 // camera's own render-size RGBA32F plane instead of `out`, and the post launches write `out` behind it. Bloom (st_bloom.cpp): while the frame
 // blooms, the composing launch writes the composed colour untransformed (and still meters it) into the camera's HDR plane; the bloom launches
-// behind it end in the composite, which runs the display transform and writes what the composing launch would have written.
+// behind it end in the composite, which runs the display transform and writes what the composing launch would have written. Motion blur
+// (st_motion_blur.cpp) sits in front of bloom in the same way: the composing launch writes the blur's HDR plane, and the gather writes bloom's
+// HDR plane (untransformed) or, without bloom, what the composing launch would have written.
 struct OutputRoute {
-    bool post_fxaa = false, post = false, bloom = false;
-    Engine::BloomPlan bloom_plan;
+    bool post_fxaa = false, post = false, bloom = false, mblur = false;
+    Engine::BloomPlan bloom_plan; Engine::MBlurPlan mblur_plan;
     void* comp_out = nullptr; uint32_t comp_format = 0; DisplayArgs comp_disp{};      // the composing launch (either of the two): target, format, display transform
     void* frame_out = nullptr; uint32_t frame_format = 0; DisplayArgs frame_disp{};   // the bloom composite: `out` or the post plane; no display: NONE at scale 1, which stores the colour's own bits
 };
@@ -184,7 +186,7 @@ struct FrameSwitches {
 // visibility and the GI chain to the camera's side stream); the rest below `s` is launch bookkeeping.
 struct Frame {
     Engine& e; CameraState& c; void* const out; const hipStream_t stream; hipStream_t cur;
-    KArgs a{}; OutputRoute route; FrameSwitches s{};
+    KArgs a{}; OutputRoute route; FrameSwitches s{}; Engine::MBlurSteps blur{};
     const uint32_t mode, pseed;   // pseed: one seed for both preview passes (passes/gi_preview_resampling.rs:60-74)
     bool mask_split = false, di_reprojected = false, gi_reprojected = false, composed = false, luts_generated_now = false; uint32_t launch_ordinal = 0u;
     Frame(Engine& e_, CameraState& c_, void* out_, hipStream_t s_) : e(e_), c(c_), out(out_), stream(s_), cur(s_), mode(c_.desc.mode), pseed(pass_seed(e_.base_seed, c_.frame, SEED_GI_PREVIEW)) {}
@@ -232,10 +234,16 @@ struct Frame {
         }
         // grown, never shrunk: a level count that goes down and up again between frames costs no sync and no allocation
         if (r.bloom) if (int rc = c.bloom_planes.acquire({plane, r.bloom_plan.texels * sizeof(float4)}, c.bloom_planes.Grow, stream)) return rc;
+        if (out && c.blurs()) {
+            if (int rc = Engine::mblur_plan(c.mblur, c.desc.width, c.desc.height, r.mblur_plan)) return rc;
+            r.mblur = true;
+            if (int rc = c.mblur_planes.acquire({plane, r.mblur_plan.packed_bytes, r.mblur_plan.tile_bytes, r.mblur_plan.tile_bytes}, c.mblur_planes.Grow, stream)) return rc;
+        }
         r.frame_out = r.post ? c.post_planes.plane[0].ptr : out; r.frame_format = r.post ? (uint32_t)ST_FORMAT_RGBA32F : c.out_format;
         r.frame_disp = disp; if (!r.frame_disp.on) r.frame_disp.scale = 1.0f;
-        r.comp_out = r.bloom ? c.bloom_planes.plane[0].ptr : r.frame_out; r.comp_format = r.bloom ? (uint32_t)ST_FORMAT_RGBA32F : r.frame_format;
-        if (r.bloom) { if (disp.meter) disp.tonemap = kDisplayRaw; else disp = DisplayArgs{}; }   // the composing launch: meter, do not transform
+        const bool hdr_chain = r.bloom || r.mblur;   // the composing launch feeds an HDR node: it stores the composed colour as it is
+        r.comp_out = r.mblur ? c.mblur_planes.plane[0].ptr : (r.bloom ? c.bloom_planes.plane[0].ptr : r.frame_out); r.comp_format = hdr_chain ? (uint32_t)ST_FORMAT_RGBA32F : r.frame_format;
+        if (hdr_chain) { if (disp.meter) disp.tonemap = kDisplayRaw; else disp = DisplayArgs{}; }   // the composing launch: meter, do not transform
         r.comp_disp = disp;
         return ST_OK;
     }
@@ -306,6 +314,7 @@ struct Frame {
             s.lean = kLeanPrim | kLeanSamples;
             if (t.fuse_gi_reprojection && s.tracing && s.even_tiles) s.lean |= kLeanGiRes2;
             if (s.gi_preview_both) s.lean |= kLeanGiMid;
+            if (route.mblur) s.lean |= kLeanKeepVelocity;   // the pack launch reads the velocity map
         }
         // frame composition rides in the last a-trous pass (k_denoise.hip k_denoise_wavelet_far<true>). (Fast build, Image mode and an output buffer.)
         s.compose_in_wavelet = t.fuse_compose && fast && fused_denoised && out != nullptr && mode == ST_MODE_IMAGE;
@@ -320,6 +329,11 @@ struct Frame {
         // per-kernel profiling runs the graph serially on `stream`: a launch's event pair then times that kernel alone, not the kernels of the other stream it would share the chip with
         s.two_streams = t.overlap && !e.profiling && e.launch_filter == ~0ull && s.needs_di && s.needs_gi && s.any_objects;
         a.gi_skip_history_copy = s.gi_skip_history_copy; a.variance_in_reproject = s.variance_in_reproject; a.lean = s.lean; a.skip_dead_scratch = s.skip_dead_scratch;
+        if (route.mblur) {   // the blur's three launches (blur_pack, finish_output): into bloom's HDR plane, untransformed, when the frame blooms
+            const FencedPlanes<4>& p = c.mblur_planes;
+            blur = Engine::mblur_steps(c.mblur, route.mblur_plan, p.plane[0].ptr, a.velocity, a.g0, true, c.desc.width, c.desc.height, p.plane[1].as<float2>(), p.plane[2].as<float4>(),
+                                       p.plane[3].as<float4>(), route.bloom ? c.bloom_planes.plane[0].ptr : route.frame_out, route.frame_format, route.bloom, route.frame_disp);
+        }
         c.last_lean = s.lean; c.last_lean_composed = s.compose_in_wavelet && s.lean != 0u;   // which planes the frame leaves unwritten: the last a-trous pass's colour planes too
         return ST_OK;
     }
@@ -457,6 +471,12 @@ struct Frame {
             run(KS_DENOISE_WAVELET, (uint64_t)ST_PASS_DENOISE_WAVELET_0 << nth, [&] { e.L.launch_denoise_wavelet(a, 1u << nth, (float)(1u + nth), di[in_ix[nth]], di[out_ix[nth]], gi[in_ix[nth]], gi[out_ix[nth]], cur); });
         }
     }
+    // Motion blur's pack launch: it reads this frame's velocity map and G-buffer, which the NEXT frame's primary visibility overwrites (the
+    // velocity map is single-buffered), so it runs on `stream` before that may start; what it writes is the camera's own.
+    void blur_pack() {
+        if (!route.mblur) return;
+        run(blur.step[0].slot, ST_PASS_POST, [&] { e.launch_mblur_step(blur.step[0], cur); }, blur.step[0].bytes);
+    }
     void compose() {   // every mode's composition, unless the last a-trous pass did it
         if (!out || composed) return;
         Engine::present_guard(c, out, cur); e.dist_guard(c.handle, out, cur);
@@ -503,6 +523,7 @@ struct Frame {
         if (int rc = c.ev_di_head.wait(stream)) return rc;
         if (t.di_head_on_main) di_head();
         di_tail();
+        blur_pack();   // before ev_prim_ok: prim(N+1) rewrites the velocity map
         // stand-alone denoise reprojection kernels (unfused path) still read the reprojection map: prim(N+1) may only start once they are through
         const bool reproject_later = s.denoise && !t.fuse;
         if (!reproject_later) { if (int rc = c.ev_prim_ok.record(stream)) return rc; }
@@ -522,16 +543,21 @@ struct Frame {
             if (s.needs_di) { di_head(); di_tail(); }
             if (s.needs_gi) { gi_head(); gi_tail(); }
         }
+        blur_pack();
         denoise();
         compose();
         // (a camera that has run the two-stream schedule: its next such frame waits for these)
         if (c.side_stream) { if (int rc = c.ev_prim_ok.record(stream)) return rc; if (int rc = c.ev_frame_done.record(stream)) return rc; }
         return ST_OK;
     }
-    // The launches behind the composing launch, which ran on `stream`: bloom, then post-processing — one launch group (ST_PASS_POST) —, then the
+    // The launches behind the composing launch, which ran on `stream`: motion blur, bloom, then post-processing — one launch group (ST_PASS_POST) —, then the
     // meter's finalize; each step's fence is recorded behind its launches.
     int finish_output() {
         cur = stream;
+        if (route.mblur) {   // the neighbour maximum and the gather: they read the camera's packed plane, tile vectors and HDR plane only
+            for (uint32_t i = 1; i < 3u; i++) run(blur.step[i].slot, ST_PASS_POST, [&] { e.launch_mblur_step(blur.step[i], cur); }, blur.step[i].bytes);
+            if (int rc = c.mblur_planes.done(stream)) return rc;
+        }
         if (route.bloom) {
             const FencedPlanes<2>& p = c.bloom_planes;
             const Engine::BloomSteps steps = Engine::bloom_steps(c.bloom, route.bloom_plan, p.plane[0].ptr, c.desc.width, c.desc.height, p.plane[1].as<float4>(), route.frame_out, route.frame_format, route.frame_disp, e.bloom_tail_bytes());

@@ -50,6 +50,8 @@ constexpr uint32_t kLeanGiRes2 = 4u;   // tracing frames: the reprojected GI res
 constexpr uint32_t kLeanGiMid = 8u;    // both GI preview passes in one launch: a first-pass result that is a plain normalisation of its input (the pixel drew
                                        // no neighbour: every pixel once the reservoirs have history) is not stored to GI_RESERVOIRS_3; the few pixels
                                        // whose second pass does resample rebuild such a neighbour's record from the pass's input (KArgs::gi_mid_src)
+constexpr uint32_t kLeanKeepVelocity = 16u;   // with kLeanPrim, while the camera blurs (st_motion_blur.cpp): primary visibility stores the velocity map after all; the
+                                       // pack launch of the motion blur reads it. Nothing else about the lean frame changes
 constexpr int kBvhStackSize = 24;  // strolle-gpu/src/lib.rs:76
 constexpr int kBvhStackSizeDeep = 32;  // trees whose deepest chain of internal nodes exceeds kBvhStackSize (st_bvh_refresh.cpp measure_stack_need)
 constexpr uint32_t kLightIdSky = 0xffffffffu;
@@ -109,6 +111,20 @@ struct BloomTailArgs {
     float4* base; uint32_t bw, bh, n, additive, lds_bytes;
     uint32_t w[8], h[8], off[8];
     float factor[8];
+};
+
+// Motion blur (include/strolle_hip.h "motion blur"; st_motion_blur.cpp, k_motion_blur.hip): the arguments of its three launches. Tiles are
+// kMBlurTile pixels square, tiles_x x tiles_y of them. Pack reads the velocity and the depth — in a frame the velocity map's xy (16 B a
+// pixel) and PRIM_GBUFFER_D0.x with 0 read as FLT_MAX (`frame` != 0), in st_motion_blur_process a float2 and a float plane as they are —
+// and writes `packed` (r, Z) and `tile_max` (v.x, v.y, r, 0 per tile); the neighbour launch writes `tile_n`; the gather reads `color`,
+// `packed` and `tile_n` and stores `dst` in `format` (`raw` != 0: RGBA32F with no display transform, the plane bloom reads).
+constexpr uint32_t kMBlurTile = 32u;
+struct MBlurArgs {
+    const void* velocity; const void* depth; const float4* color;
+    float2* packed; float4* tile_max; float4* tile_n; void* dst;
+    uint32_t width, height, tiles_x, tiles_y, frame, samples, jitter, format, raw;
+    float half_shutter, max_radius, depth_softness;
+    DisplayArgs display;
 };
 
 // Everything a per-pixel kernel can touch, passed by value as the kernel argument (scalar loads).
