@@ -750,6 +750,99 @@ int st_motion_blur_process(StEngine* e, const StMotionBlurDesc* desc, const StDi
                            const void* velocity_device, const void* depth_device, uint32_t width, uint32_t height,
                            void* dst_device, int dst_format /* StOutputFormat */, void* hip_stream);
 
+/* ---- depth of field (NEW seam): a thin-lens circle-of-confusion gather in front of motion blur (st_dof.cpp, k_dof.hip). The HDR node
+ * Bevy's graph places directly before motion blur (DepthOfField -> motion blur -> bloom -> tonemapping -> FXAA -> upscaling): a camera
+ * with a physical lens (focal length from the projection and the sensor height, an aperture in f-stops) focused at a distance or on a
+ * point of the frame.
+ * - Order: rendering -> depth of field -> motion blur -> bloom -> display transform -> FXAA -> resample -> output format.
+ * - Scope: the setting belongs to the camera and takes effect at its next st_render_camera. It changes only what is written to
+ *   `out_device`: AOVs, picks, scene queries, the HDR history, every plane st_camera_read_buffer returns and the auto-exposure metering (it
+ *   keeps metering the composed frame in the composing launch, before the blur) are unchanged. desc == NULL turns it off: the frame then
+ *   launches the kernels it launches without the setting, with the same arguments, and st_debug_last_launches is unchanged. The setting
+ *   survives st_camera_update and st_engine_set_arithmetic. Frames that skip it, bit for bit the frames without the setting:
+ *   ST_MODE_REFERENCE and ST_MODE_BVH_HEATMAP, which have no G-buffer, and a frame whose projection is not a perspective one
+ *   (projection[15] != 0; also a projection whose [5] is not positive and finite or whose [0] is 0 or not finite), because the focal
+ *   length is derived from the projection. Unlike motion blur, the sky is blurred, as geometry at infinity. While a frame focuses, the
+ *   composing launch writes the composed colour, untransformed, into a camera-owned render-size RGBA32F plane (and meters it); three
+ *   launches (ST_PASS_POST) belong to the filter: pack (with the tile maximum) as soon as primary visibility is through, and the neighbour
+ *   maximum and the gather behind the composing launch, in front of motion blur, bloom, FXAA and the resampler. The gather writes motion
+ *   blur's HDR plane (untransformed) when motion blur is on, otherwise bloom's when bloom is on, otherwise what the composing launch would
+ *   have written, through the display transform and the output format. Focus smoothing over time is not offered: with ST_DOF_AUTOFOCUS the
+ *   focus distance is this frame's depth under the focus point, and it jumps when that does.
+ * - Arithmetic: float32, evaluated left to right as written, no fused multiply-add, division and square root correctly rounded, in BOTH
+ *   builds; tests/dof_ref.py restates all of it in numpy and the kernels match it bit for bit. min, max and clamp01 use the post-processing
+ *   section's NaN rule. The frame is W x H. C is the composed HDR colour, D the distance along the camera ray, P the column-major
+ *   projection. In a frame, D is PRIM_GBUFFER_D0.x of the frame's parity (ST_AOV_DEPTH's value), with 0 (sky) read as FLT_MAX, and P is the
+ *   camera's; in st_dof_process D and P are the given ones as they are. N = aperture_f_stops, h_s = sensor_height, R = max_radius,
+ *   S = samples, each after its default is applied.
+ * - 0. Host constants, per frame, in double (every operand converted to double first, left to right), each rounded to float once:
+ *   f_d = 0.5 h_s P[5]; K_d = 0.5 f_d f_d / (N h_s) H; f = (float)f_d, the focal length in metres; K = (float)K_d, in pixel-metres. The
+ *   tap table T[k], k < S: rho = sqrt((k + 0.5) / S), th = k 2.399963229728653 (the golden angle), T[k] = (rho cos th, rho sin th, rho),
+ *   computed in double and rounded to float; st_dof_plan returns it.
+ * - 1. Planar depth (per pixel (x, y)): a lens focuses on a plane and D is radial. The pixel centre maps to NDC as the camera's rays do:
+ *   ndc_x = (x + 0.5) 2 / W - 1; ndc_y = -((y + 0.5) 2 / H - 1), with W and H as floats. ax = (ndc_x + P[8]) / P[0];
+ *   ay = (ndc_y + P[9]) / P[5]; c = 1 / sqrt((ax ax + ay ay) + 1); Z = D c. If D >= FLT_MAX (sky, +inf), Z = FLT_MAX. With
+ *   ST_DOF_PLANAR_DEPTH, which only st_dof_process honours (D is then a planar depth already), c = 1: Z = D.
+ * - 2. Focus: s = focal_distance. With ST_DOF_AUTOFOCUS, let Z_f be the Z of pixel (min(floor(focus_x W), W - 1),
+ *   min(floor(focus_y H), H - 1)) of this same frame (the products in float); if 0 < Z_f < FLT_MAX, s = Z_f, otherwise (sky, NaN) s stays
+ *   focal_distance. Every workgroup of the pack launch reads that pixel with one uniform load: no extra launch, no host read-back.
+ *   m = max(s - f, 1e-6); A = K / m.
+ * - 3. Pack (per pixel): coc = Z > 0 ? A (1 - s / Z) : 0, the signed radius in pixels of the circle of confusion: negative in front of the
+ *   focal plane, tending to A at infinity. coc = min(max(coc, -R), R). (coc, Z) is stored as a float2 plane.
+ * - 4. Near-field tile maximum: tiles are 32 x 32 pixels, ceil(W / 32) x ceil(H / 32) of them. A tile's value is the largest -coc over its
+ *   pixels with coc < 0, or 0 when it has none. (Non-negative floats order like their bits: one unsigned max, reduced with cross-lane
+ *   operations and one LDS step per workgroup; no device atomic.) Pack and tile maximum are one launch.
+ * - 5. Neighbour maximum: n(tile) is the largest tile value over the 3 x 3 tiles around it that exist. One small launch.
+ * - 6. Gather (per pixel X = (x, y)): r_X = |coc_X|; r_g = max(r_X, n(tile of X)). If r_g < 0.5 the result is C(X) with its own four
+ *   words: NaN, infinities and alpha pass through. Otherwise let c(Y) be C(Y) with each of r, g, b as min(max(., 0), 65504).
+ *   sum = c(X); wsum = 1. For k = 0 .. S - 1, in order: p = (x + 0.5 + T[k].x r_g, y + 0.5 + T[k].y r_g); Y = (floor p.x, floor p.y),
+ *   each clamped to the image (in float, as min(max(floor p, 0), side - 1)); d = T[k].z r_g; r_Y = |coc_Y|; if Z_Y > Z_X then
+ *   r_Y = min(r_Y, r_X), so that a blurred background does not bleed over a sharper foreground; q = clamp01((r_Y - d) + 0.5);
+ *   w = q q (3 - 2 q); sum += c(Y) w per channel; wsum += w. The result is sum / wsum per channel, alpha 1. The gather radius is the
+ *   pixel's own, widened only by the near field around it: a tap that is closer than X and has a larger radius than r_X is necessarily in
+ *   front of the focal plane, and that is what n bounds (DESIGN.md "Depth of field").
+ * - Known limits: this is the scatter-as-gather disk filter with nearest-texel taps. Nearest taps undersample large radii at small S (at
+ *   R = 32 a disk holds 3,200 texels: S = 32 visits one in a hundred, which shows as noise on high-contrast bokeh); foreground bleed is
+ *   not area-normalised (a near-field texel weighs the same whatever the area of its own disk, so a thin near object spreads brighter
+ *   than a lens would spread it); Y clamps at the frame's edges, so the border repeats outwards.
+ * - Tiles: the gather reads up to 32 pixels across tile edges, and the tile grid is the frame's, so a camera cannot have depth of field and
+ *   a window (st_camera_set_window, st_dist_set_partition, st_dist_set_grid) at once: ST_ERR_INVALID_ARGUMENT from whichever setter comes
+ *   second. For tiled frames rank 0 runs st_dof_process on the gathered colour and ST_AOV_DEPTH planes, in front of
+ *   st_motion_blur_process, st_bloom_process and st_post_process.
+ * - Errors: ST_ERR_INVALID_ARGUMENT for a wrong struct_size, unknown flag bits, a field outside its range (NaN included), focus_x or
+ *   focus_y outside [0, 1] when ST_DOF_AUTOFOCUS is set (they are not looked at otherwise), null pointers where they are not allowed, a
+ *   side of 0 or above 16384 in the process call, and an auto-exposure display or a non-perspective projection given to the process call.
+ *   An unknown camera is ST_ERR_UNKNOWN_CAMERA. Set, get and plan are host work and valid on a host-only engine; st_dof_process returns
+ *   ST_ERR_NO_DEVICE there. */
+enum { ST_DOF_AUTOFOCUS = 1, ST_DOF_PLANAR_DEPTH = 2 };
+typedef struct StDofDesc {                 /* 40 B */
+    uint32_t struct_size;                  /* sizeof(StDofDesc) */
+    uint32_t flags;                        /* ST_DOF_* */
+    uint32_t samples;                      /* 4..64; 0 = default 32 */
+    float focal_distance;                  /* metres along the optical axis, finite, > 0; Bevy's default is 10 */
+    float aperture_f_stops;                /* N, finite, > 0; 0 = default 1 */
+    float sensor_height;                   /* metres, finite, > 0; 0 = default 0.01866 (Super 35) */
+    float max_radius;                      /* pixels, 0 < R <= 32; 0 = default 32 (Bevy's 64-pixel diameter) */
+    float focus_x, focus_y;                /* ST_DOF_AUTOFOCUS: the focus point in [0, 1]^2 of the frame, (0, 0) the top left corner */
+    uint32_t _pad;                         /* ignored */
+} StDofDesc;
+int st_camera_set_dof(StEngine* e, StHandle camera, const StDofDesc* desc);   /* NULL = off */
+/* the last desc set (a zeroed desc with struct_size when none was) and whether depth of field is on; either pointer may be NULL */
+int st_camera_get_dof(StEngine* e, StHandle camera, StDofDesc* out, int* enabled);
+/* Pure host work, no engine: the sample count after its default, the tile counts of a width x height frame and the tap table (samples x
+ * (x, y, rho); the rest of the 192 floats is 0). Any of the three outputs may be NULL. The desc is checked as in the setter; a side above
+ * 16384 is ST_ERR_INVALID_ARGUMENT. */
+int st_dof_plan(const StDofDesc* desc, uint32_t width, uint32_t height, uint32_t* samples, uint32_t tiles_xy[2], float taps_xyr[64 * 3]);
+/* Stateless, like st_motion_blur_process. color: RGBA32F; depth: f32 (ST_AOV_DEPTH's layout, FLT_MAX on sky; with ST_DOF_PLANAR_DEPTH a
+ * planar depth); projection: the 16 floats of the column-major perspective projection the planes were rendered with (host memory, read
+ * during the call); display NULL = none, manual exposure only; dst in dst_format, width x height. Needs a device engine; no camera, no
+ * tick. Enqueued on hip_stream without a host sync. The packed plane and the tile values are engine-owned: allocated (with a device sync)
+ * only when a call needs larger ones than any before it, and calls on different streams are ordered by the engine. No input may overlap
+ * dst. */
+int st_dof_process(StEngine* e, const StDofDesc* desc, const StDisplayDesc* display, const float projection[16], const void* color_device,
+                   const void* depth_device, uint32_t width, uint32_t height, void* dst_device, int dst_format /* StOutputFormat */,
+                   void* hip_stream);
+
 /* ---- multi-GPU behind the boundary (NEW seam; SURVEY.md section 8e, BASELINE.json configs 4 and 5). One process per GPU, one
  * engine per process, the scene replicated; the frame is cut into tiles, every rank renders its tile (+ an apron of redundant
  * pixels in Image mode, whose passes read neighbours) with absolute pixel coordinates, and the ONE collective of the path
@@ -929,7 +1022,7 @@ enum StPassBit {
     ST_PASS_DENOISE_REPROJECT_DI = 1u << 18, ST_PASS_DENOISE_REPROJECT_GI = 1u << 19, ST_PASS_DENOISE_VARIANCE = 1u << 20,
     ST_PASS_DENOISE_WAVELET_0 = 1u << 21, /* ... wavelet pass n = ST_PASS_DENOISE_WAVELET_0 << n, n < 5 */
     ST_PASS_COMPOSITION = 1u << 26, ST_PASS_BVH_HEATMAP = 1u << 27, ST_PASS_REF_TRACING = 1u << 28, ST_PASS_REF_SHADING = 1u << 29,
-    ST_PASS_POST = 1u << 30   /* the launches behind composition, one launch group: motion blur ("motion blur" above), bloom ("bloom"), then FXAA and / or the resampler ("post-processing") */
+    ST_PASS_POST = 1u << 30   /* the launches behind composition, one launch group: depth of field ("depth of field" above), motion blur ("motion blur"), bloom ("bloom"), then FXAA and / or the resampler ("post-processing") */
 };
 int st_debug_set_pass_mask(StEngine* e, uint64_t mask);
 /* Measurement only (tools/pair_matrix.py): the frame's graph is built as always — every fusion of the whole frame — but only the launches
@@ -1027,7 +1120,7 @@ enum { ST_PROFILE_TIMING = 1, ST_PROFILE_TRAVERSAL_BYTES = 2,
                                       interval under the slot "a-trous chain (one timed interval)" instead of one event pair per slot */,
        ST_PROFILE_KERNEL_EVENTS = 8 /* with TIMING: every launch carries its own start / stop events (hipExtLaunchKernelGGL: the dispatch's
                                        timestamps, what rocprofv3's kernel trace reports) instead of events recorded between kernels */ };
-enum { ST_PROFILE_MAX_KERNELS = 48 };  /* >= the number of kernel slots (st_kernels.h) */
+enum { ST_PROFILE_MAX_KERNELS = 64 };  /* >= the number of kernel slots (st_kernels.h) */
 typedef struct StKernelProfile {
     char name[48];
     uint32_t launches;

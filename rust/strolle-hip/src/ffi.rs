@@ -328,6 +328,30 @@ extern "C" {
     pub fn st_motion_blur_process(e: *mut StEngine, desc: *const StMotionBlurDesc, display: *const StDisplayDesc, color_device: *const c_void, velocity_device: *const c_void, depth_device: *const c_void, width: u32, height: u32, dst_device: *mut c_void, dst_format: i32, hip_stream: *mut c_void) -> i32;
 }
 
+// depth of field (include/strolle_hip.h "depth of field"): a thin-lens circle-of-confusion gather in front of motion blur
+pub const ST_DOF_AUTOFOCUS: u32 = 1;
+pub const ST_DOF_PLANAR_DEPTH: u32 = 2;
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct StDofDesc {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub samples: u32,
+    pub focal_distance: f32,
+    pub aperture_f_stops: f32,
+    pub sensor_height: f32,
+    pub max_radius: f32,
+    pub focus_x: f32,
+    pub focus_y: f32,
+    pub _pad: u32,
+}
+extern "C" {
+    pub fn st_camera_set_dof(e: *mut StEngine, camera: u64, desc: *const StDofDesc) -> i32; // null = off
+    pub fn st_camera_get_dof(e: *mut StEngine, camera: u64, out: *mut StDofDesc, enabled: *mut i32) -> i32;
+    pub fn st_dof_plan(desc: *const StDofDesc, width: u32, height: u32, samples: *mut u32, tiles_xy: *mut u32, taps_xyr: *mut f32) -> i32; // pure host
+    pub fn st_dof_process(e: *mut StEngine, desc: *const StDofDesc, display: *const StDisplayDesc, projection: *const f32, color_device: *const c_void, depth_device: *const c_void, width: u32, height: u32, dst_device: *mut c_void, dst_format: i32, hip_stream: *mut c_void) -> i32;
+}
+
 // ---- the HIP runtime, as far as the staging-copy present needs it (libamdhip64)
 pub type hipStream_t = *mut c_void;
 extern "C" {

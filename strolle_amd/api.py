@@ -99,6 +99,9 @@ class StTuning(C.Structure):
                                           "allow_deep_bvh", "device_bake", "wide_bvh", "wide_stack_entries", "primary_packets")]
 
 
+PROFILE_MAX_KERNELS = 64   # ST_PROFILE_MAX_KERNELS
+
+
 class StKernelProfile(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint32), ("total_ms", C.c_float), ("algorithmic_bytes", C.c_double), ("traversal_bytes", C.c_double)]
 
@@ -193,6 +196,37 @@ def motion_blur_desc(shutter: float = 0.5, samples: int = 0, max_radius: float =
     (include/strolle_hip.h "motion blur")."""
     return StMotionBlurDesc(C.sizeof(StMotionBlurDesc), 0 if jitter else MOTION_BLUR_NO_JITTER, int(samples), float(shutter), float(max_radius),
                             float(depth_softness))
+
+
+class StDofDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("samples", C.c_uint32), ("focal_distance", C.c_float), ("aperture_f_stops", C.c_float),
+                ("sensor_height", C.c_float), ("max_radius", C.c_float), ("focus_x", C.c_float), ("focus_y", C.c_float), ("_pad", C.c_uint32)]
+
+
+DOF_AUTOFOCUS, DOF_PLANAR_DEPTH, DOF_MAX_SAMPLES = 1, 2, 64
+
+
+def dof_desc(focal_distance: float = 10.0, aperture_f_stops: float = 0.0, sensor_height: float = 0.0, samples: int = 0, max_radius: float = 0.0,
+             autofocus=None, planar_depth: bool = False) -> StDofDesc:
+    """A StDofDesc; the defaults are Bevy's focal distance of 10 m, f/1, a Super 35 sensor (18.66 mm), 32 samples and a 32-pixel radius
+    (include/strolle_hip.h "depth of field"). autofocus: None, or the focus point (x, y) in [0, 1]^2 of the frame."""
+    fx, fy = (float(autofocus[0]), float(autofocus[1])) if autofocus is not None else (0.0, 0.0)
+    return StDofDesc(C.sizeof(StDofDesc), (DOF_AUTOFOCUS if autofocus is not None else 0) | (DOF_PLANAR_DEPTH if planar_depth else 0), int(samples), float(focal_distance),
+                     float(aperture_f_stops), float(sensor_height), float(max_radius), fx, fy, 0)
+
+
+def dof_plan(desc: StDofDesc, width: int, height: int):
+    """st_dof_plan (pure host): (samples, (tiles_x, tiles_y), the tap table as a (samples, 3) float32 array of (x, y, rho))."""
+    import numpy as np
+    lib = load_library()
+    lib.st_dof_plan.restype = C.c_int
+    lib.st_dof_plan.argtypes = [C.POINTER(StDofDesc), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+    n, tiles, taps = C.c_uint32(), (C.c_uint32 * 2)(), (C.c_float * (DOF_MAX_SAMPLES * 3))()
+    rc = lib.st_dof_plan(C.byref(desc), width, height, C.byref(n), tiles, taps)
+    if rc != 0:
+        lib.st_last_error.restype = C.c_char_p
+        raise StrolleError(f"{_STATUS.get(rc, 'error')} (status {rc}): {lib.st_last_error().decode(errors='replace')}")
+    return n.value, (tiles[0], tiles[1]), np.array(taps, np.float32).reshape(DOF_MAX_SAMPLES, 3)[:n.value].copy()
 
 
 class StBloomDesc(C.Structure):
@@ -539,6 +573,11 @@ class _Binding:
             self.camera_set_motion_blur = fn("camera_set_motion_blur", [vp, u64, P(StMotionBlurDesc)])
             self.camera_get_motion_blur = fn("camera_get_motion_blur", [vp, u64, P(StMotionBlurDesc), P(i32)])
             self.motion_blur_process = fn("motion_blur_process", [vp, P(StMotionBlurDesc), P(StDisplayDesc), vp, vp, vp, u32, u32, vp, i32, vp])
+        if hasattr(lib, prefix + "camera_set_dof"):   # depth of field (likewise)
+            self.camera_set_dof = fn("camera_set_dof", [vp, u64, P(StDofDesc)])
+            self.camera_get_dof = fn("camera_get_dof", [vp, u64, P(StDofDesc), P(i32)])
+            self.dof_plan = fn("dof_plan", [P(StDofDesc), u32, u32, P(u32), P(u32), P(C.c_float)])
+            self.dof_process = fn("dof_process", [vp, P(StDofDesc), P(StDisplayDesc), P(C.c_float), vp, vp, u32, u32, vp, i32, vp])
         if hasattr(lib, prefix + "mesh_set_skin"):
             self.mesh_set_skin = fn("mesh_set_skin", [vp, u64, vp, sz, u32])
         if hasattr(lib, prefix + "mesh_set_morph_targets"):   # morph targets (likewise absent from an older library)
@@ -1089,6 +1128,27 @@ class Engine(EngineBase):
         self._check(self._b.motion_blur_process(self._h, C.byref(desc), C.byref(display) if display is not None else None, color_ptr, velocity_ptr,
                                                 depth_ptr, width, height, dst_ptr, int(dst_format), stream))
 
+    # ---- depth of field (include/strolle_hip.h "depth of field"): takes effect at the camera's next render
+    def set_dof(self, camera: int, desc: Optional[StDofDesc] = None, **kw):
+        """st_camera_set_dof: a StDofDesc, or dof_desc(**kw) when keywords are given; neither = off."""
+        if desc is None and kw:
+            desc = dof_desc(**kw)
+        self._check(self._b.camera_set_dof(self._h, camera, C.byref(desc) if desc is not None else None))
+
+    def get_dof(self, camera: int):
+        """st_camera_get_dof: (the last StDofDesc set, whether depth of field is on)."""
+        d, on = StDofDesc(), C.c_int()
+        self._check(self._b.camera_get_dof(self._h, camera, C.byref(d), C.byref(on)))
+        return d, bool(on.value)
+
+    def dof_process(self, desc: StDofDesc, projection, color_ptr: int, depth_ptr: int, width: int, height: int, dst_ptr: int, dst_format: int = 0,
+                    display: Optional[StDisplayDesc] = None, stream: int = 0):
+        """st_dof_process: depth of field over any RGBA32F colour and f32 depth device planes rendered with `projection` (16 floats, column
+        major), then the (manual) display transform, into dst (width x height) in dst_format."""
+        proj = (C.c_float * 16)(*[float(v) for v in projection])
+        self._check(self._b.dof_process(self._h, C.byref(desc), C.byref(display) if display is not None else None, proj, color_ptr, depth_ptr, width, height,
+                                        dst_ptr, int(dst_format), stream))
+
     # ---- environment lighting (include/strolle_hip.h "environment lighting"): takes effect at the next tick
     def set_environment(self, texels, intensity: float = 1.0, yaw: float = 0.0, keep_sun: bool = False, uniform: bool = False):
         """st_environment_set / st_environment_set_device: an equirectangular map, (H, W, 3 or 4) float32, row 0 the zenith, the centre looking
@@ -1280,8 +1340,8 @@ class Engine(EngineBase):
         self._check(self._b.profile_enable(self._h, int(flags)))
 
     def profile_read(self, reset: bool = True):
-        arr = (StKernelProfile * 48)(); n = C.c_size_t()
-        self._check(self._b.profile_read(self._h, arr, 48, C.byref(n), 1 if reset else 0))
+        arr = (StKernelProfile * PROFILE_MAX_KERNELS)(); n = C.c_size_t()
+        self._check(self._b.profile_read(self._h, arr, PROFILE_MAX_KERNELS, C.byref(n), 1 if reset else 0))
         return [dict(name=arr[i].name.decode(), launches=arr[i].launches, total_ms=arr[i].total_ms, algorithmic_bytes=arr[i].algorithmic_bytes, traversal_bytes=arr[i].traversal_bytes)
                 for i in range(n.value)]
 

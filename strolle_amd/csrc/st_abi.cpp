@@ -274,6 +274,7 @@ int st_camera_set_window(StEngine* e, StHandle h, uint32_t x0, uint32_t y0, uint
     ST_REQUIRE(full || !s.post_on, "a window on a camera with post-processing: FXAA and the resampler read across tile edges (include/strolle_hip.h \"post-processing\")");
     ST_REQUIRE(full || !s.bloom_on, "a window on a camera with bloom: the pyramid reads far across tile edges (include/strolle_hip.h \"bloom\")");
     ST_REQUIRE(full || !s.mblur_on, "a window on a camera with motion blur: the gather reads up to 32 pixels across tile edges (include/strolle_hip.h \"motion blur\")");
+    ST_REQUIRE(full || !s.dof_on, "a window on a camera with depth of field: the gather reads up to 32 pixels across tile edges (include/strolle_hip.h \"depth of field\")");
     s.row0 = y0; s.row1 = y1; s.col0 = x0; s.col1 = x1;
     return ST_OK;
 }
@@ -398,6 +399,37 @@ int st_motion_blur_process(StEngine* e, const StMotionBlurDesc* desc, const StDi
                            uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
     ST_REQUIRE(e, "null engine");
     return E(e)->motion_blur_process(desc, display, color, velocity, depth, width, height, dst, dst_format, static_cast<hipStream_t>(stream));
+}
+
+// ---- depth of field (st_dof.cpp)
+int st_camera_set_dof(StEngine* e, StHandle h, const StDofDesc* desc) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    return E(e)->set_dof(*it->second, desc);
+}
+int st_camera_get_dof(StEngine* e, StHandle h, StDofDesc* out, int* enabled) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    const CameraState& s = *it->second;
+    if (out) { *out = s.dof; out->struct_size = sizeof(StDofDesc); }
+    if (enabled) *enabled = s.dof_on ? 1 : 0;
+    return ST_OK;
+}
+int st_dof_plan(const StDofDesc* desc, uint32_t width, uint32_t height, uint32_t* samples, uint32_t tiles_xy[2], float taps_xyr[64 * 3]) {
+    ST_REQUIRE(desc, "null desc");
+    Engine::DofPlan plan;
+    if (int rc = Engine::dof_plan(*desc, width, height, plan)) return rc;
+    if (samples) *samples = plan.samples;
+    if (tiles_xy) { tiles_xy[0] = plan.tiles_x; tiles_xy[1] = plan.tiles_y; }
+    if (taps_xyr) for (uint32_t i = 0; i < kDofMaxSamples * 3u; i++) taps_xyr[i] = plan.taps[i];
+    return ST_OK;
+}
+int st_dof_process(StEngine* e, const StDofDesc* desc, const StDisplayDesc* display, const float projection[16], const void* color, const void* depth,
+                   uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
+    ST_REQUIRE(e, "null engine");
+    return E(e)->dof_process(desc, display, projection, color, depth, width, height, dst, dst_format, static_cast<hipStream_t>(stream));
 }
 
 int st_debug_set_bloom_tail(StEngine* e, int lds_bytes, uint32_t* in_force) {

@@ -8,6 +8,7 @@
 //   st_post.cpp         output post-processing: FXAA and the resampler
 //   st_bloom.cpp        bloom: the plan, the chain of launches
 //   st_motion_blur.cpp  motion blur: the plan, its three launches
+//   st_dof.cpp          depth of field: the plan (host constants, tap table), its three launches
 //   st_deform.cpp       mesh deformation (st_deform.h): skinned meshes, morph targets, deformation motion; the tick's launches
 //   st_env.cpp          environment lighting: the map, its importance table
 //   st_query.cpp        scene queries: closest hit, occlusion, picks
@@ -29,6 +30,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <initializer_list>
 #include <map>
@@ -330,6 +332,10 @@ namespace st {
 
 // ------------------------------------------------------------------ per-camera state (camera_controller/buffers.rs)
 constexpr int kInternalPlanes = 4;  // decoded-surface twins A/B (KArgs::sn / psn) + the pair the variance pass writes ahead of the strides-1+2 wavelet launch
+// Depth of field derives the focal length from projection[5] and the view-space slopes from [0], [5], [8], [9]: a perspective projection
+// ([15] == 0) whose [5] is positive and finite and whose [0] is finite and not 0 (include/strolle_hip.h "depth of field")
+inline bool dof_perspective(const float* p) { return p[15] == 0.0f && p[5] > 0.0f && p[5] <= 3.402823466e+38f && std::fabs(p[0]) > 0.0f && std::fabs(p[0]) <= 3.402823466e+38f; }
+
 struct CameraState {
     StCamera desc{};
     GpuCamera curr{}, prev{};
@@ -401,6 +407,14 @@ struct CameraState {
     StMotionBlurDesc mblur{}; bool mblur_on = false;
     FencedPlanes<4> mblur_planes;   // [0] the HDR plane, [1] (r, Z) per pixel, [2] the tile vectors, [3] their 3 x 3 neighbour maxima
     bool blurs() const { return mblur_on && desc.mode != ST_MODE_BVH_HEATMAP && desc.mode != ST_MODE_REFERENCE; }   // those two run no primary-visibility pass: no velocity map
+    // Depth of field (st_dof.cpp; include/strolle_hip.h "depth of field"), in front of motion blur; it survives st_camera_update like the rest of
+    // the output chain. While a frame focuses, the pack launch turns the G-buffer's depth into the packed plane and the tile values before the
+    // next frame's primary visibility may start, the composing launch writes the HDR plane and the gather writes where the composing launch
+    // would have (or the HDR plane of motion blur or bloom). Grown and fenced like mblur_planes.
+    StDofDesc dof{}; bool dof_on = false;
+    FencedPlanes<4> dof_planes;   // [0] the HDR plane, [1] (coc, Z) per pixel, [2] the tiles' near-field maxima, [3] their 3 x 3 neighbour maxima
+    // heatmap and reference frames have no G-buffer; the focal length is derived from a perspective projection
+    bool focuses() const { return dof_on && desc.mode != ST_MODE_BVH_HEATMAP && desc.mode != ST_MODE_REFERENCE && dof_perspective(desc.projection); }
     uint32_t out_width() const { return post_on && post.output_width != 0u ? post.output_width : desc.width; }
     uint32_t out_height() const { return post_on && post.output_width != 0u ? post.output_height : desc.height; }
     // A present copy still in flight writes the caller's host memory: it lands before the stream goes. Everything else goes with its member —
@@ -792,6 +806,17 @@ struct Engine {
     void launch_mblur_step(const MBlurStep& s, hipStream_t stream);
     int motion_blur_process(const StMotionBlurDesc* desc, const StDisplayDesc* display, const void* color, const void* velocity, const void* depth, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
     FencedPlanes<3> mblur_scratch;   // st_motion_blur_process's packed plane and tile vectors: grown, never shrunk
+    // ---- depth of field (st_dof.cpp)
+    struct DofPlan { uint32_t samples = 0, tiles_x = 0, tiles_y = 0; size_t packed_bytes = 0, tile_bytes = 0; float max_radius = 0.0f; float taps[kDofMaxSamples * 3u] = {}; };
+    struct DofStep { int slot; double bytes; };
+    struct DofSteps { DofArgs args; DofStep step[3]; };   // pack (+ tile maximum), neighbour maximum, gather: one argument block
+    static int dof_plan(const StDofDesc& d, uint32_t w, uint32_t h, DofPlan& plan);   // checks the desc
+    static int dof_steps(const StDofDesc& d, const DofPlan& plan, const float projection[16], const void* color, const void* depth, bool frame, uint32_t w, uint32_t h,
+                         float2* packed, float* tile_max, float* tile_n, void* dst, uint32_t format, bool raw, const DisplayArgs& display, DofSteps& out);
+    int set_dof(CameraState& c, const StDofDesc* desc);
+    void launch_dof_step(const DofSteps& s, uint32_t i, hipStream_t stream);
+    int dof_process(const StDofDesc* desc, const StDisplayDesc* display, const float* projection, const void* color, const void* depth, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
+    FencedPlanes<3> dof_scratch;   // st_dof_process's packed plane and tile values: grown, never shrunk
     int scene_args(KArgs& a, bool heatmap) const;   // the scene half of KArgs (st_render.cpp): render() and the scene queries
     void light_args(KArgs& a) const;                // its lights, LUT and environment half: render()
 

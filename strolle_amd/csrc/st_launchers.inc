@@ -97,3 +97,8 @@ ST_LAUNCHER(launch_bloom_tail, (const BloomTailArgs& p, hipStream_t s))
 ST_LAUNCHER(launch_mblur_pack, (const MBlurArgs& p, hipStream_t s))
 ST_LAUNCHER(launch_mblur_neighbour, (const MBlurArgs& p, hipStream_t s))
 ST_LAUNCHER(launch_mblur_gather, (const MBlurArgs& p, hipStream_t s))
+// depth of field (k_dof.hip; st_dof.cpp): pack + the per-tile near-field maximum (one workgroup per 32 x 32 tile), the 3 x 3 neighbour maximum
+// over the tile values, and the gather (one workgroup per 32 x 8 pixels: the tile's value is uniform in it; in-focus pixels are a copy)
+ST_LAUNCHER(launch_dof_pack, (const DofArgs& p, hipStream_t s))
+ST_LAUNCHER(launch_dof_neighbour, (const DofArgs& p, hipStream_t s))
+ST_LAUNCHER(launch_dof_gather, (const DofArgs& p, hipStream_t s))

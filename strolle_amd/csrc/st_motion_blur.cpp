@@ -7,7 +7,7 @@
 
 namespace st {
 
-static_assert(KS_COUNT == ST_PROFILE_MAX_KERNELS, "the three slots of the blur fill the profiler's table (st_profile_read's callers size their arrays with ST_PROFILE_MAX_KERNELS): the next slot has to raise it");
+static_assert(KS_COUNT <= ST_PROFILE_MAX_KERNELS, "st_profile_read's callers size their arrays with ST_PROFILE_MAX_KERNELS");
 static_assert(sizeof(StMotionBlurDesc) == 24, "StMotionBlurDesc is 24 B");
 static_assert(offsetof(StMotionBlurDesc, samples) == 8 && offsetof(StMotionBlurDesc, shutter) == 12 && offsetof(StMotionBlurDesc, depth_softness) == 20, "StMotionBlurDesc's fields are six 4-B words");
 static constexpr uint32_t kMBlurMaxSide = 16384u, kMBlurDefaultSamples = 8u, kMBlurMaxSamples = 32u;

@@ -169,10 +169,12 @@ namespace {
 // blooms, the composing launch writes the composed colour untransformed (and still meters it) into the camera's HDR plane; the bloom launches
 // behind it end in the composite, which runs the display transform and writes what the composing launch would have written. Motion blur
 // (st_motion_blur.cpp) sits in front of bloom in the same way: the composing launch writes the blur's HDR plane, and the gather writes bloom's
-// HDR plane (untransformed) or, without bloom, what the composing launch would have written.
+// HDR plane (untransformed) or, without bloom, what the composing launch would have written. Depth of field (st_dof.cpp) sits in front of
+// motion blur: the composing launch writes its HDR plane, and its gather writes the HDR plane of the next node that is on (motion blur's, else
+// bloom's), or what the composing launch would have written.
 struct OutputRoute {
-    bool post_fxaa = false, post = false, bloom = false, mblur = false;
-    Engine::BloomPlan bloom_plan; Engine::MBlurPlan mblur_plan;
+    bool post_fxaa = false, post = false, bloom = false, mblur = false, dof = false;
+    Engine::BloomPlan bloom_plan; Engine::MBlurPlan mblur_plan; Engine::DofPlan dof_plan;
     void* comp_out = nullptr; uint32_t comp_format = 0; DisplayArgs comp_disp{};      // the composing launch (either of the two): target, format, display transform
     void* frame_out = nullptr; uint32_t frame_format = 0; DisplayArgs frame_disp{};   // the bloom composite: `out` or the post plane; no display: NONE at scale 1, which stores the colour's own bits
 };
@@ -186,7 +188,7 @@ struct FrameSwitches {
 // visibility and the GI chain to the camera's side stream); the rest below `s` is launch bookkeeping.
 struct Frame {
     Engine& e; CameraState& c; void* const out; const hipStream_t stream; hipStream_t cur;
-    KArgs a{}; OutputRoute route; FrameSwitches s{}; Engine::MBlurSteps blur{};
+    KArgs a{}; OutputRoute route; FrameSwitches s{}; Engine::MBlurSteps blur{}; Engine::DofSteps dof{};
     const uint32_t mode, pseed;   // pseed: one seed for both preview passes (passes/gi_preview_resampling.rs:60-74)
     bool mask_split = false, di_reprojected = false, gi_reprojected = false, composed = false, luts_generated_now = false; uint32_t launch_ordinal = 0u;
     Frame(Engine& e_, CameraState& c_, void* out_, hipStream_t s_) : e(e_), c(c_), out(out_), stream(s_), cur(s_), mode(c_.desc.mode), pseed(pass_seed(e_.base_seed, c_.frame, SEED_GI_PREVIEW)) {}
@@ -239,10 +241,15 @@ struct Frame {
             r.mblur = true;
             if (int rc = c.mblur_planes.acquire({plane, r.mblur_plan.packed_bytes, r.mblur_plan.tile_bytes, r.mblur_plan.tile_bytes}, c.mblur_planes.Grow, stream)) return rc;
         }
+        if (out && c.focuses()) {
+            if (int rc = Engine::dof_plan(c.dof, c.desc.width, c.desc.height, r.dof_plan)) return rc;
+            r.dof = true;
+            if (int rc = c.dof_planes.acquire({plane, r.dof_plan.packed_bytes, r.dof_plan.tile_bytes, r.dof_plan.tile_bytes}, c.dof_planes.Grow, stream)) return rc;
+        }
         r.frame_out = r.post ? c.post_planes.plane[0].ptr : out; r.frame_format = r.post ? (uint32_t)ST_FORMAT_RGBA32F : c.out_format;
         r.frame_disp = disp; if (!r.frame_disp.on) r.frame_disp.scale = 1.0f;
-        const bool hdr_chain = r.bloom || r.mblur;   // the composing launch feeds an HDR node: it stores the composed colour as it is
-        r.comp_out = r.mblur ? c.mblur_planes.plane[0].ptr : (r.bloom ? c.bloom_planes.plane[0].ptr : r.frame_out); r.comp_format = hdr_chain ? (uint32_t)ST_FORMAT_RGBA32F : r.frame_format;
+        const bool hdr_chain = r.bloom || r.mblur || r.dof;   // the composing launch feeds an HDR node: it stores the composed colour as it is
+        r.comp_out = r.dof ? c.dof_planes.plane[0].ptr : (r.mblur ? c.mblur_planes.plane[0].ptr : (r.bloom ? c.bloom_planes.plane[0].ptr : r.frame_out)); r.comp_format = hdr_chain ? (uint32_t)ST_FORMAT_RGBA32F : r.frame_format;
         if (hdr_chain) { if (disp.meter) disp.tonemap = kDisplayRaw; else disp = DisplayArgs{}; }   // the composing launch: meter, do not transform
         r.comp_disp = disp;
         return ST_OK;
@@ -333,6 +340,13 @@ struct Frame {
             const FencedPlanes<4>& p = c.mblur_planes;
             blur = Engine::mblur_steps(c.mblur, route.mblur_plan, p.plane[0].ptr, a.velocity, a.g0, true, c.desc.width, c.desc.height, p.plane[1].as<float2>(), p.plane[2].as<float4>(),
                                        p.plane[3].as<float4>(), route.bloom ? c.bloom_planes.plane[0].ptr : route.frame_out, route.frame_format, route.bloom, route.frame_disp);
+        }
+        if (route.dof) {   // depth of field's three launches (dof_pack, finish_output): into the next HDR node's plane, untransformed, when there is one
+            const FencedPlanes<4>& p = c.dof_planes;
+            const bool raw = route.mblur || route.bloom;
+            void* dst = route.mblur ? c.mblur_planes.plane[0].ptr : (route.bloom ? c.bloom_planes.plane[0].ptr : route.frame_out);
+            if (int rc = Engine::dof_steps(c.dof, route.dof_plan, c.desc.projection, p.plane[0].ptr, a.g0, true, c.desc.width, c.desc.height, p.plane[1].as<float2>(), p.plane[2].as<float>(),
+                                           p.plane[3].as<float>(), dst, route.frame_format, raw, route.frame_disp, dof)) return rc;
         }
         c.last_lean = s.lean; c.last_lean_composed = s.compose_in_wavelet && s.lean != 0u;   // which planes the frame leaves unwritten: the last a-trous pass's colour planes too
         return ST_OK;
@@ -477,6 +491,12 @@ struct Frame {
         if (!route.mblur) return;
         run(blur.step[0].slot, ST_PASS_POST, [&] { e.launch_mblur_step(blur.step[0], cur); }, blur.step[0].bytes);
     }
+    // Depth of field's pack launch: it reads this frame's G-buffer depth; the frame after next rewrites that plane, and packing here keeps
+    // every reader of the G-buffer in front of the ev_prim_ok record, like blur_pack.
+    void dof_pack() {
+        if (!route.dof) return;
+        run(dof.step[0].slot, ST_PASS_POST, [&] { e.launch_dof_step(dof, 0u, cur); }, dof.step[0].bytes);
+    }
     void compose() {   // every mode's composition, unless the last a-trous pass did it
         if (!out || composed) return;
         Engine::present_guard(c, out, cur); e.dist_guard(c.handle, out, cur);
@@ -523,7 +543,7 @@ struct Frame {
         if (int rc = c.ev_di_head.wait(stream)) return rc;
         if (t.di_head_on_main) di_head();
         di_tail();
-        blur_pack();   // before ev_prim_ok: prim(N+1) rewrites the velocity map
+        dof_pack(); blur_pack();   // before ev_prim_ok: prim(N+1) rewrites the velocity map
         // stand-alone denoise reprojection kernels (unfused path) still read the reprojection map: prim(N+1) may only start once they are through
         const bool reproject_later = s.denoise && !t.fuse;
         if (!reproject_later) { if (int rc = c.ev_prim_ok.record(stream)) return rc; }
@@ -543,17 +563,21 @@ struct Frame {
             if (s.needs_di) { di_head(); di_tail(); }
             if (s.needs_gi) { gi_head(); gi_tail(); }
         }
-        blur_pack();
+        dof_pack(); blur_pack();
         denoise();
         compose();
         // (a camera that has run the two-stream schedule: its next such frame waits for these)
         if (c.side_stream) { if (int rc = c.ev_prim_ok.record(stream)) return rc; if (int rc = c.ev_frame_done.record(stream)) return rc; }
         return ST_OK;
     }
-    // The launches behind the composing launch, which ran on `stream`: motion blur, bloom, then post-processing — one launch group (ST_PASS_POST) —, then the
+    // The launches behind the composing launch, which ran on `stream`: depth of field, motion blur, bloom, then post-processing — one launch group (ST_PASS_POST) —, then the
     // meter's finalize; each step's fence is recorded behind its launches.
     int finish_output() {
         cur = stream;
+        if (route.dof) {   // depth of field's neighbour maximum and gather: they read the camera's packed plane, tile values and HDR plane only
+            for (uint32_t i = 1; i < 3u; i++) run(dof.step[i].slot, ST_PASS_POST, [&] { e.launch_dof_step(dof, i, cur); }, dof.step[i].bytes);
+            if (int rc = c.dof_planes.done(stream)) return rc;
+        }
         if (route.mblur) {   // the neighbour maximum and the gather: they read the camera's packed plane, tile vectors and HDR plane only
             for (uint32_t i = 1; i < 3u; i++) run(blur.step[i].slot, ST_PASS_POST, [&] { e.launch_mblur_step(blur.step[i], cur); }, blur.step[i].bytes);
             if (int rc = c.mblur_planes.done(stream)) return rc;

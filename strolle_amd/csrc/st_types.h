@@ -127,6 +127,22 @@ struct MBlurArgs {
     DisplayArgs display;
 };
 
+// Depth of field (include/strolle_hip.h "depth of field"; st_dof.cpp, k_dof.hip): the arguments of its three launches. Tiles are kDofTile
+// pixels square, tiles_x x tiles_y of them. Pack reads the depth — in a frame PRIM_GBUFFER_D0.x with 0 read as FLT_MAX (`frame` != 0), in
+// st_dof_process a float plane as it is — and writes `packed` (coc, Z) and `tile_max` (the largest near-field radius of each tile, a
+// non-negative float); the neighbour launch writes `tile_n`; the gather reads `color`, `packed` and `tile_n` and stores `dst` in `format`
+// (`raw` != 0: RGBA32F with no display transform, the plane the next HDR node reads). p0, p5, p8, p9: the projection's entries [0], [5],
+// [8], [9]. `taps` holds (rho cos th, rho sin th, rho) of each of the `samples` taps: by value, so no frame waits for an upload.
+constexpr uint32_t kDofTile = 32u, kDofMaxSamples = 64u;
+struct DofArgs {
+    const void* depth; const float4* color;
+    float2* packed; float* tile_max; float* tile_n; void* dst;
+    uint32_t width, height, tiles_x, tiles_y, frame, samples, format, raw, planar, autofocus, focus_px, focus_py;
+    float p0, p5, p8, p9, focal_length /* f */, k /* K */, focal_distance, max_radius;
+    DisplayArgs display;
+    float taps[kDofMaxSamples * 3u];
+};
+
 // Everything a per-pixel kernel can touch, passed by value as the kernel argument (scalar loads).
 struct KArgs {
     GpuCamera cam, prev_cam;
