@@ -319,7 +319,9 @@ struct Frame {
         // planes nothing reads again are not stored (st_types.h kLean*). (Fast build and Image mode only — like compose_in_wavelet, but with no output buffer too.)
         if (t.lean_frame && fast && fused_denoised && mode == ST_MODE_IMAGE) {
             s.lean = kLeanPrim | kLeanSamples;
-            if (t.fuse_gi_reprojection && s.tracing && s.even_tiles) s.lean |= kLeanGiRes2;
+            // (odd tracing frames count on the spatial pass to rewrite the plane: it leaves the last pixel of a row alone when the width is odd and the
+            // cell's other pixel, the one it resamples, lies past the edge — as it leaves the dropped tile column alone when the tile count is odd)
+            if (t.fuse_gi_reprojection && s.tracing && s.even_tiles && (c.frame % 2u == 0u || a.width % 2u == 0u)) s.lean |= kLeanGiRes2;
             if (s.gi_preview_both) s.lean |= kLeanGiMid;
             if (route.mblur) s.lean |= kLeanKeepVelocity;   // the pack launch reads the velocity map
         }

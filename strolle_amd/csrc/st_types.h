@@ -46,7 +46,7 @@ constexpr uint32_t kLeanPrim = 1u;     // primary visibility + frame reprojectio
                                        // encoded surface map (every kernel reads its decoded twin, KArgs::sn) stay unwritten
 constexpr uint32_t kLeanSamples = 2u;  // di / gi diffuse sample planes: the fused denoise-reproject stages consume them in registers
 constexpr uint32_t kLeanGiRes2 = 4u;   // tracing frames: the reprojected GI reservoirs the fused temporal pass consumes in registers (on odd
-                                       // tracing frames the spatial pass rewrites the whole plane anyway)
+                                       // tracing frames the spatial pass rewrites the whole plane anyway — given an even tile count AND an even width)
 constexpr uint32_t kLeanGiMid = 8u;    // both GI preview passes in one launch: a first-pass result that is a plain normalisation of its input (the pixel drew
                                        // no neighbour: every pixel once the reservoirs have history) is not stored to GI_RESERVOIRS_3; the few pixels
                                        // whose second pass does resample rebuild such a neighbour's record from the pass's input (KArgs::gi_mid_src)

@@ -44,6 +44,7 @@ from oracle_binding import OracleEngine
 from parity import psnr
 from strolle_amd import Buffer, CameraMode, Engine, PassBit, scenes
 from test_gpu_fast_tolerance import ATOL, RTOL, lanes_outside_tolerance
+from test_gpu_parity import _inside_camera as inside_camera
 
 pytestmark = pytest.mark.gpu
 
@@ -135,6 +136,7 @@ def _plane_stats(got, want):
 
 
 _SCENES = {"cornell": (scenes.build_cornell, scenes.cornell_camera), "dungeon": (scenes.build_dungeon, scenes.dungeon_camera),
+           "cornell_inside": (scenes.build_cornell, inside_camera),   # no sky beside the box: every edge tile holds lit surfaces
            # SYNTHETIC: the dungeon with every triangle split into 16 (208 k triangles) — the stand-in for BASELINE.json config 3's "~100k tris" scene
            "dungeon134k": (lambda e: scenes.build_dungeon(e, subdivide=2), scenes.dungeon_camera)}
 _runs = {}
@@ -148,11 +150,20 @@ def _spawned_instance_xform(frame):
     return np.array([[c, -s_, 0.0, -5.75 + 0.01 * frame], [s_, c, 0.0, 0.45], [0.0, 0.0, 0.25, -19.0]], np.float32)
 
 
-def _run(scene, size, plan, moving=False, mode=CameraMode.IMAGE, tree="host"):
+def _pixel_mask(got, want, size, atol=ATOL):
+    """[h, w] bool: pixels with ANY lane of their record outside the per-lane tolerance"""
+    return lanes_outside_tolerance(got, want, atol=atol).reshape(size[1], size[0], -1).any(axis=-1)
+
+
+def _run(scene, size, plan, moving=False, mode=CameraMode.IMAGE, tree="host", masks=False, fill_bits=None):
     """One oracle run of max(plan) frames; frame f (the ENGINE's frame number, which starts at 1 and decides the GI schedule:
     f % 6 < 4 tracing — even f samples, odd f resamples spatially —, else validation) is checked as plan[f] says ("launches" /
-    "whole" / "whole_keep"); other frames only advance the oracle. Returns {"launches": [...], "whole": [...]} of report rows; cached per (scene, size)."""
-    key = (scene, size, moving, int(mode), tree)
+    "whole" / "whole_keep"); other frames only advance the oracle. Returns {"launches": [...], "whole": [...]} of report rows; cached per (scene, size).
+    masks=True (small frames: tests/test_gpu_frame_shapes.py) adds "masks": one row {frame, kind, launch, plane, mask, nonfinite_lanes} per compared plane
+    that has an outlier or a lane that is finite in the oracle and not in the product — `mask` the per-pixel outlier mask (_pixel_mask; VELOCITY_ATOL_PX
+    for the velocity map as in the fractions) — and "compared": the number of planes compared. fill_bits = a 32-bit pattern the output tensor is
+    filled with before every unmasked frame; "unwritten" then lists (frame, lanes that still hold it)."""
+    key = (scene, size, moving, int(mode), tree, masks, fill_bits, tuple(sorted(plan.items())))
     if key in _runs:
         return _runs[key]
     torch = _torch()
@@ -178,7 +189,7 @@ def _run(scene, size, plan, moving=False, mode=CameraMode.IMAGE, tree="host"):
     out = torch.zeros((size[1], size[0], 4), dtype=torch.float32, device="cuda:0")
     stream = torch.cuda.current_stream().cuda_stream
     full_mask = (1 << 64) - 1
-    report = {"launches": [], "whole": []}
+    report = {"launches": [], "whole": [], "masks": [], "compared": 0, "unwritten": []}
     held = {}  # what the product's planes hold right now (arrays it was given or that were read back from it)
 
     def upload(state):
@@ -194,6 +205,26 @@ def _run(scene, size, plan, moving=False, mode=CameraMode.IMAGE, tree="host"):
 
     def read_orac():
         return {b: orac.read_buffer(co, b) for b in FLOAT_BUFFERS}
+
+    def mask_rows(frame, kind, launch, got, want, planes, composed=None):
+        if not masks:
+            return
+        pairs = [(b.name, got[b], want[b], VELOCITY_ATOL_PX if b == Buffer.VELOCITY_MAP else ATOL) for b in planes]
+        if composed is not None:
+            pairs.append(("composed frame", composed[0].reshape(-1), np.ascontiguousarray(composed[1]).reshape(-1), ATOL))
+        for name, g, w, atol in pairs:
+            report["compared"] += 1
+            m = _pixel_mask(g, w, size, atol)
+            bad = np.isfinite(w) & ~np.isfinite(g)
+            if name.startswith("GI_RESERVOIRS_"):
+                # the reference's own octahedral code of a zero normal is (NaN, NaN) (normal.rs encode: n / 0) — every empty reservoir of the oracle holds
+                # it, sky samples too: a pixel whose discrete choice flipped to such a record is an outlier in `mask`, not arithmetic gone wrong
+                rec, codec = bad.reshape(-1, 16), np.isnan(g.reshape(-1, 16)[:, 12:14]).all(axis=1)
+                rec[codec, 12:14] = False
+            nonfinite = int(bad.sum())
+            if m.any() or nonfinite:
+                report["masks"].append({"frame": frame, "kind": kind, "launch": launch, "plane": name, "mask": m, "nonfinite_lanes": nonfinite,
+                                        "diagnose": _diagnose(g, w, g.size // (size[0] * size[1]), size[0])})
 
     for frame in range(1, max(plan) + 1):   # the engine numbers frames from 1 (strolle/src/lib.rs:152)
         if moving:   # what bench.py's `moving` region does: the light of cornell.rs:82-93 (1/60 s per frame), the camera on an orbit
@@ -235,6 +266,7 @@ def _run(scene, size, plan, moving=False, mode=CameraMode.IMAGE, tree="host"):
                 if bits & PassBit.COMPOSITION:
                     frac = _bad_fraction(out.cpu().numpy().reshape(-1), np.ascontiguousarray(ref_frame).reshape(-1))
                     report["launches"].append({"frame": frame, "launch": name, "plane": "composed frame", "bad_fraction": frac})
+                mask_rows(frame, kind, name, got, want, FLOAT_BUFFERS, (out.cpu().numpy(), ref_frame) if bits & PassBit.COMPOSITION else None)
                 before = want
             orac.set_pass_mask(full_mask); prod.set_pass_mask(full_mask)
         else:
@@ -243,9 +275,13 @@ def _run(scene, size, plan, moving=False, mode=CameraMode.IMAGE, tree="host"):
             upload(before)
             prod.set_pass_mask(full_mask)
             prod.keep_all_planes(kind == "whole_keep")
+            if fill_bits is not None:
+                out.view(torch.int32).fill_(fill_bits - (1 << 32) if fill_bits >= 1 << 31 else fill_bits)
             prod.render_camera(cp, out.data_ptr(), stream); torch.cuda.synchronize()
             prod.keep_all_planes(False)
             assert prod.last_launches(), "no launches"
+            if fill_bits is not None:
+                report["unwritten"].append((frame, int((out.view(torch.int32).cpu().numpy().view(np.uint32) == fill_bits).sum())))
             got = read_prod()
             skip = REF_PLANES | (set() if (kind == "whole_keep" or mode != CameraMode.IMAGE) else lean_planes(frame))   # the lean frame is Image mode's
             for b, frac in _bad_fractions(got, want, [b for b in FLOAT_BUFFERS if b not in skip]).items():
@@ -258,6 +294,7 @@ def _run(scene, size, plan, moving=False, mode=CameraMode.IMAGE, tree="host"):
             row = {"frame": frame, "kind": kind, "plane": "composed frame", "bad_fraction": _bad_fraction(out.cpu().numpy().reshape(-1), np.ascontiguousarray(ref_frame).reshape(-1))}
             row.update(_plane_stats(out.cpu().numpy(), ref_frame))
             report["whole"].append(row)
+            mask_rows(frame, kind, None, got, want, [b for b in FLOAT_BUFFERS if b not in skip], (out.cpu().numpy(), ref_frame))
             # reservoir sample counts: the state must be the steady one the benchmark times
             m = want[Buffer.GI_RESERVOIRS_0].reshape(-1, 16)[:, 3]
             lit = want[Buffer.PRIM_SURFACE_MAP_A if frame % 2 == 0 else Buffer.PRIM_SURFACE_MAP_B].reshape(-1, 4)[:, 2] != 0
@@ -265,7 +302,7 @@ def _run(scene, size, plan, moving=False, mode=CameraMode.IMAGE, tree="host"):
                                                   "history_median": float(np.median(want[Buffer.DI_DIFF_MOMENTS_A if frame % 2 == 0 else Buffer.DI_DIFF_MOMENTS_B].reshape(-1, 4)[:, 0][lit])) if lit.any() else None})
     report["tree"] = {"device_builds": prod.device_builds(), "device_tree_refits": prod.device_tree_refits(), "walk_overflow": list(prod.walk_overflow())}
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    suffix = {"host": "", "device": "_devtree", "spawned": "_spawned"}[tree]
+    suffix = {"host": "", "device": "_devtree", "spawned": "_spawned"}[tree] + ("_keep" if set(plan.values()) == {"whole_keep"} else "")
     with open(os.path.join(ROOT, "gpurun_out", f"fast_steady_{scene}{'_moving' if moving else ''}{'' if mode == CameraMode.IMAGE else '_' + mode.name.lower()}_{size[0]}x{size[1]}{suffix}.json"), "w") as f:
         json.dump({"scene": scene, "size": size, "tree": tree, "tree_counters": report["tree"], "plan": {str(k): v for k, v in plan.items()}, "rtol": RTOL, "atol": ATOL,
                    "launch_rows_with_outliers": sorted(report["launches"], key=lambda r: -r["bad_fraction"])[:60],

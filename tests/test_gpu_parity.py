@@ -45,6 +45,11 @@ def _step(torch, prod, orac, desc, cp, co, out):
     return out.cpu().numpy(), ref
 
 
+def _inside_camera(size, mode=CameraMode.IMAGE, denoise=True, depth=0):
+    """inside the Cornell box: no sky beside it in wide frames, every edge tile holds lit surfaces (tests/test_gpu_frame_shapes.py)"""
+    return scenes.camera_for(size, (0.0, 1.0, 0.9), (0.0, 1.0, 0.0), mode, denoise, depth)
+
+
 def _compare_all(prod, orac, cp, co, frame, buffers=ALL_FLOAT_BUFFERS):
     for b in buffers:
         assert_bits_equal(prod.read_buffer(cp, b), orac.read_buffer(co, b), f"frame {frame} buffer {b.name}")
@@ -291,15 +296,18 @@ def _tiled_ranks(torch, build, size, mode, depth, world, cols, apron, group, cam
     return ranks
 
 
-@pytest.mark.parametrize("world,cols", [(4, 0), (8, 0), (2, 0), (4, 4)])
-def test_tiles_gathered_through_the_c_abi_reproduce_the_single_gpu_frame_exactly(world, cols):
+# 272 x 200: tile edges that are not multiples of the frame's halves: st_dist_partition rounds them onto its 16 x 8 grid;
+# 197 x 101: the right window edge is the frame's edge and no multiple of 16, the bottom one no multiple of 8
+@pytest.mark.parametrize("world,cols,size", [pytest.param(4, 0, (272, 200), id="4-0"), pytest.param(8, 0, (272, 200), id="8-0"), pytest.param(2, 0, (272, 200), id="2-0"),
+                                             pytest.param(4, 4, (272, 200), id="4-4"), pytest.param(2, 0, (197, 101), id="2-0-197x101"), pytest.param(4, 2, (197, 101), id="4-2-197x101")])
+def test_tiles_gathered_through_the_c_abi_reproduce_the_single_gpu_frame_exactly(world, cols, size):
     """BASELINE.json config 4's shape — Reference mode, 2 x 2 tiles (also 4 x 2, bands and column strips) — through st_dist_set_partition
     + st_dist_gather on device engines: the frame rank 0 assembles equals the single-engine frame bit for bit, over 3 accumulated frames,
     with the gather of frame N in flight while frame N+1 renders into the other buffer."""
     torch = _torch()
-    size = (272, 200)   # tile edges that are not multiples of the frame's halves: st_dist_partition rounds them onto its 16 x 8 grid
-    single = _render_bands(torch, scenes.build_cornell, size, CameraMode.REFERENCE, 1, 3, 1, 0)
-    ranks = _tiled_ranks(torch, scenes.build_cornell, size, CameraMode.REFERENCE, 1, world, cols, 0, group=4000 + world * 8 + cols)
+    camera_fn = scenes.cornell_camera if size == (272, 200) else _inside_camera
+    single = _render_bands(torch, scenes.build_cornell, size, CameraMode.REFERENCE, 1, 3, 1, 0, camera_fn=camera_fn)
+    ranks = _tiled_ranks(torch, scenes.build_cornell, size, CameraMode.REFERENCE, 1, world, cols, 0, group=4000 + world * 8 + cols + (size[0] % 2) * 64, camera_fn=camera_fn)
     alt = [torch.zeros_like(ranks[0][2]) for _ in ranks]
     full = [torch.zeros_like(ranks[0][2]), torch.zeros_like(ranks[0][2])]
     stream = torch.cuda.current_stream().cuda_stream
@@ -1137,19 +1145,23 @@ def test_profile_flags_timing_and_traversal_bytes():
     e.close()
 
 
-@pytest.mark.parametrize("switches", [
+_SWITCH_SETS = [
     {"ST_NO_FUSE": "1"},
     {"ST_NO_OVERLAP": "1", "ST_NO_FUSE_WAVELET": "1"},
     {"ST_TILE_MAP": "0"},
     {"ST_NO_PREVIEW_BOTH": "1", "ST_NO_VARIANCE_IN_REPROJECT": "1", "ST_KEEP_SCRATCH": "1", "ST_DI_HEAD_ON_MAIN": "0", "ST_NO_FUSE_GI_VALIDATION": "1"},
     {"ST_NO_FUSE_SPATIAL": "1", "ST_NO_FUSE_DI_HEAD": "1", "ST_NO_FUSE_GI_REPROJECTION": "1", "ST_NO_FUSE_GI_SAMPLING": "1"},
-], ids=lambda s: "+".join(sorted(s)))
-def test_every_scheduling_variant_produces_the_same_bits(switches):
+]
+
+
+@pytest.mark.parametrize("switches,size", [pytest.param(s, (160, 96), id="+".join(sorted(s))) for s in _SWITCH_SETS] +
+                                          [pytest.param(s, (72, 40), id="+".join(sorted(s)) + "-72x40") for s in _SWITCH_SETS])
+def test_every_scheduling_variant_produces_the_same_bits(switches, size):
     """The engine's fusion / overlap / mapping switches (read from the environment when an engine is created) select other
     launch structures for the same pass graph: each must leave every plane bit-identical to the oracle's, frame after frame
-    (exact build; Cornell 160x96 Image{denoise}, 8 frames = every GI schedule)."""
+    (exact build; Cornell Image{denoise}, 8 frames = every GI schedule; 160x96, and 72x40 — nine tile columns, where the
+    half-resolution passes drop the last one and the engine's even_tiles switches are off)."""
     torch = _torch()
-    size = (160, 96)
     saved = {k: os.environ.get(k) for k in switches}
     os.environ.update(switches)
     try:
@@ -1163,7 +1175,7 @@ def test_every_scheduling_variant_produces_the_same_bits(switches):
     orac = OracleEngine()
     for e in (prod, orac):
         scenes.build_cornell(e); e.set_seed(17)
-    desc = scenes.cornell_camera(size, CameraMode.IMAGE)
+    desc = scenes.cornell_camera(size, CameraMode.IMAGE) if size == (160, 96) else _inside_camera(size, CameraMode.IMAGE)
     cp, co = prod.create_camera(desc), orac.create_camera(desc)
     out = torch.zeros((size[1], size[0], 4), dtype=torch.float32, device="cuda:0")
     for frame in range(8):
