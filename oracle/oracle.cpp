@@ -306,3 +306,22 @@ extern "C" void or_probe_trace(OrEngine* e, const float* origin3, const float* d
     out11[4] = hit.normal.x; out11[5] = hit.normal.y; out11[6] = hit.normal.z; out11[7] = hit.uv.x; out11[8] = hit.uv.y;
     out11[9] = b2f(hit.material_id); out11[10] = (float)um;
 }
+// or_probe_trace over `count` StRay records (origin, t_max, direction, pad: 8 floats each), as the scene queries' checkers call it one ray at a time:
+// distance[i] / point3[i] = the closest hit of the UNBOUNDED ray (F32_MAX: none), slot[i] = the triangle slot that won (0xffffffff: none),
+// occluded[i] = the any-hit probe with len = t_max answered out[0] < len.
+extern "C" void or_probe_trace_rays(OrEngine* e, const float* rays, size_t count, float* distance, float* point3, uint32_t* slot, uint32_t* occluded) {
+    EngineView v = E(e)->view();
+    for (size_t i = 0; i < count; i++) {
+        const float* q = rays + 8 * i;
+        Ray r = Ray::make(Vec3(q[0], q[1], q[2]), Vec3(q[4], q[5], q[6]));
+        TriangleHit hit = TriangleHit::none();
+        uint32_t id = 0xffffffffu;
+        r.traverse(v.scene, ReturnClosest, &hit, &id);
+        distance[i] = hit.distance; slot[i] = hit.is_some() ? id : 0xffffffffu;
+        point3[3 * i] = hit.is_some() ? hit.point.x : 0.0f; point3[3 * i + 1] = hit.is_some() ? hit.point.y : 0.0f; point3[3 * i + 2] = hit.is_some() ? hit.point.z : 0.0f;
+        TriangleHit any = TriangleHit::none();
+        any.distance = q[3];
+        r.with_len(q[3]).traverse(v.scene, ReturnFirst, &any);
+        occluded[i] = any.distance < q[3] ? 1u : 0u;
+    }
+}

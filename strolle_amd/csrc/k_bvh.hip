@@ -7,6 +7,7 @@
 // and the CPU restatement's refit (tests/test_gpu_parity.py test_bvh_refit_*).
 #include <hip/hip_fp16.h>
 #include "k_common.h"
+#include "st_half_box.h"
 
 namespace st {
 namespace ST_KNS {
@@ -134,14 +135,17 @@ void launch_bvh_bake(const void* jobs, const uint32_t* job_start, uint32_t n_job
 // takes `di_sampling+di_temporal` from 194 to 280 us, tripling the box arithmetic only to 233: the loop is bound by what the
 // texture-address path has to serve per step more than by VALU issue. A shadow ray's answer is one boolean, so it may walk
 // CONSERVATIVE boxes: entry k of the contract stream (64 B at texel 4 k) becomes entry k of this stream, 48 B at texel 3 k —
-//   internal  texel 0: f16 x 8  left min.xyz, left max.xyz, right min.xy        (mins rounded DOWN, maxes UP: a box never shrinks)
+//   internal  texel 0: f16 x 8  left min.xyz, left max.xyz, right min.xy        (mins rounded DOWN, maxes UP, strictly: st_half_box.h)
 //             texel 1: f16 x 4  right min.z, right max.xyz | u32 (far entry << 2 | right child is a leaf << 1 | left child is a leaf) | u32 0
 //   leaf      texel 0: v0.xyz, bits(triangle << 2 | flags)   texel 1: (v1 - v0).xyz, bits(material)   texel 2: (v2 - v0).xyz, 0
 // so an internal step fetches TWO texels and a leaf step three (the kind of a child travels with its pointer) where the contract
 // stream's take four, the stream is a quarter smaller, and the near child still sits right behind its parent (depth-first order:
 // a second form with the nodes and the leaf records in two arrays — 32-B nodes, two to a line — lost that adjacency and measured
 // HALF the gain: 1.413 vs 1.388 ms against 1.435). f16 keeps 11 significant bits: a box grows by at most 2^-10 of its coordinate's
-// magnitude (3 cm at 32 units), i.e. a few more entries are visited and no triangle a ray hits is ever skipped. The triangle records
+// magnitude (3 cm at 32 units), i.e. a few more entries are visited. That no triangle a ray hits is skipped is held against a tree-free
+// float64 brute force by tests/test_gpu_geometry_extremes.py, from 0.05-unit scenes to coordinates of 1e5: beyond +-65504 a bound is +-inf
+// or +-65504 and rejects nothing; a bound f16 holds exactly still moves one step outwards, because the walks' fma slab test errs by an ulp
+// of the ray ORIGIN's coordinate, and a zero-thickness f16 box (a floor at y = 1024) lost its grazing rays before it did. The triangle records
 // stay f32: the same hit test. The stream is a pure function of the contract stream on the device — one thread per entry — and is
 // regenerated after every upload, leaf patch, device bake or refit of it.
 __global__ __launch_bounds__(256) void k_bvh_compact(const float4* bvh, uint32_t n_entries, float4* out) {
@@ -156,8 +160,8 @@ __global__ __launch_bounds__(256) void k_bvh_compact(const float4* bvh, uint32_t
     }
     const uint32_t far_entry = f2b(d1.w) >> 6;
     const uint32_t left_leaf = f2b(bvh[4u * (k + 1u)].w) != 0u ? 1u : 0u, right_leaf = f2b(bvh[4u * far_entry].w) != 0u ? 1u : 0u;
-    auto dn = [](float x) { return (uint32_t)__half_as_ushort(__float2half_rd(x)); };
-    auto up = [](float x) { return (uint32_t)__half_as_ushort(__float2half_ru(x)); };
+    auto dn = [](float x) { return half_below(x); };   // st_half_box.h: strictly outwards
+    auto up = [](float x) { return half_above(x); };
     uint4 t0, t1;
     // a word per axis and box: (lower bound | upper bound << 16) — st_traverse.h compact_slab picks the entry plane by rotating the word
     t0.x = dn(d0.x) | (up(d1.x) << 16); t0.y = dn(d0.y) | (up(d1.y) << 16); t0.z = dn(d0.z) | (up(d1.z) << 16); t0.w = dn(d2.x) | (up(d3.x) << 16);
@@ -179,8 +183,8 @@ void launch_bvh_compact(const float4* bvh, uint32_t n_entries, float4* out, hipS
 __global__ __launch_bounds__(256) void k_bvh_wide(const float4* bvh, const uint32_t* topo, uint32_t n_nodes, const uint32_t* leaf_entry, uint32_t n_leaves, uint32_t links16,
                                                   float4* nodes, float4* leaves) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    auto dn = [](float x) { return (uint32_t)__half_as_ushort(__float2half_rd(x)); };
-    auto up = [](float x) { return (uint32_t)__half_as_ushort(__float2half_ru(x)); };
+    auto dn = [](float x) { return half_below(x); };   // st_half_box.h: strictly outwards
+    auto up = [](float x) { return half_above(x); };
     if (i < n_nodes) {
         uint32_t w[12], link[4];
 #pragma unroll

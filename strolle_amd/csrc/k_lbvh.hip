@@ -29,6 +29,7 @@
 #include <hip/hip_fp16.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include "k_common.h"
+#include "st_half_box.h"
 #include "st_lbvh.h"
 
 namespace st {
@@ -196,8 +197,8 @@ __device__ inline void lb_emit(uint32_t b, const uint2* children, const float4* 
         }
         n++;
     }
-    auto dn = [](float x) { return (uint32_t)__half_as_ushort(__float2half_rd(x)); };
-    auto up = [](float x) { return (uint32_t)__half_as_ushort(__float2half_ru(x)); };
+    auto dn = [](float x) { return half_below(x); };   // st_half_box.h: strictly outwards
+    auto up = [](float x) { return half_above(x); };
     uint32_t w[12], l[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -231,8 +232,8 @@ __global__ __launch_bounds__(kT) void k_lbvh_refit_nodes(const float4* node_box,
     uint32_t l[4];
     if (links16) { l[0] = f2b(lw.x) & 0xffffu; l[1] = f2b(lw.x) >> 16; l[2] = f2b(lw.y) & 0xffffu; l[3] = f2b(lw.y) >> 16; }
     else { l[0] = f2b(lw.x); l[1] = f2b(lw.y); l[2] = f2b(lw.z); l[3] = f2b(lw.w); }
-    auto dn = [](float x) { return (uint32_t)__half_as_ushort(__float2half_rd(x)); };
-    auto up = [](float x) { return (uint32_t)__half_as_ushort(__float2half_ru(x)); };
+    auto dn = [](float x) { return half_below(x); };   // st_half_box.h: strictly outwards
+    auto up = [](float x) { return half_above(x); };
     uint32_t w[12];
 #pragma unroll
     for (int i = 0; i < 4; i++) {

@@ -257,7 +257,10 @@ ST_D bool trace_any_contract(const KArgs& a, const Ray& ray, SE* stack, uint32_t
 // which switches back to the contract loop above). The fast build therefore walks shadow rays with ordinary fast arithmetic:
 //   * the slab test is two FMAs per plane pair against a precomputed -origin * inv_dir (the exact island's (b - o) * inv is a
 //     subtraction and a multiplication: 12 VALU instructions fewer per internal node). In position space the difference is
-//     one ulp of the coordinate's magnitude; direction components are floored at 1e-20 in magnitude (slab_safe_dir says why);
+//     half an ulp of the ray ORIGIN's coordinate, however near the plane is: harmless at unit scale, a whole unit of t for a ray grazing a
+//     zero-thickness box a thousand units out. any_slab widens each axis' interval by that bound (any_slab_origins), the f16 streams' boxes are
+//     never zero-thick (st_half_box.h); tests/test_gpu_geometry_extremes.py holds every walk to brute force from 0.05-unit scenes to
+//     coordinates of 1e5. Direction components are floored at 1e-20 in magnitude (slab_safe_dir says why);
 //   * Möller–Trumbore is contracted into FMAs and divides by v_rcp_f32 (the island's IEEE division alone is 13 instructions);
 //   * near-child-first order is KEPT: tools/packet_sim.py prices "left child first, no near/far sort" at +27 % loop bodies on
 //     the dungeon's DI shadow rays (occluded rays find their occluder later) against the ~15 % of an internal step the sort costs;
@@ -282,10 +285,22 @@ ST_D bool trace_any_contract(const KArgs& a, const Ray& ray, SE* stack, uint32_t
 // and turned a 0.3 ms launch into 3 ms). A floor of 1e-20 keeps the products finite: the planes become (bound - origin) * 1e20, which
 // rejects a slab the ray runs beside and leaves one it runs inside unconstrained, as it should be.
 ST_D float slab_safe_dir(float d) { return fabsf(d) < 1e-20f ? copysignf(1e-20f, d) : d; }
-ST_D float any_slab(V3 lo, V3 hi, V3 inv, V3 oi) {
-    const float ax = fmaf(lo.x, inv.x, oi.x), bx = fmaf(hi.x, inv.x, oi.x);
-    const float ay = fmaf(lo.y, inv.y, oi.y), by = fmaf(hi.y, inv.y, oi.y);
-    const float az = fmaf(lo.z, inv.z, oi.z), bz = fmaf(hi.z, inv.z, oi.z);
+// The planes' error is the rounding of origin * inv — half an ulp of the ORIGIN's coordinate in position space, whatever the distance to the plane — and
+// the contract stream's f32 boxes can have zero thickness (a floor at y = 1000.3: both y planes are the same number). A grazing ray that starts near such
+// a floor computed both planes up to a unit of t off and outside the x and z intervals, and the floor was skipped: light leaked through it (tests/
+// test_gpu_geometry_extremes.py, flat_1000 at 40 triangles). So each axis' interval is widened by that error's bound, 2^-23 |origin * inv|: `oa` goes with
+// the lower bounds and `ob` with the upper ones, each -origin * inv moved by the bound towards the outside of the interval for this ray's direction sign.
+// Two more ray constants per axis and no instruction per box. A widened interval can only enter a box more.
+ST_D void any_slab_origins(V3 inv, V3 origin, V3* oa, V3* ob) {
+    const float ox = -origin.x * inv.x, oy = -origin.y * inv.y, oz = -origin.z * inv.z;
+    const float ex = copysignf(fabsf(ox) * kF32Eps, inv.x), ey = copysignf(fabsf(oy) * kF32Eps, inv.y), ez = copysignf(fabsf(oz) * kF32Eps, inv.z);   // kF32Eps = 2^-23
+    *oa = v3(ox - ex, oy - ey, oz - ez);
+    *ob = v3(ox + ex, oy + ey, oz + ez);
+}
+ST_D float any_slab(V3 lo, V3 hi, V3 inv, V3 oa, V3 ob) {
+    const float ax = fmaf(lo.x, inv.x, oa.x), bx = fmaf(hi.x, inv.x, ob.x);
+    const float ay = fmaf(lo.y, inv.y, oa.y), by = fmaf(hi.y, inv.y, ob.y);
+    const float az = fmaf(lo.z, inv.z, oa.z), bz = fmaf(hi.z, inv.z, ob.z);
     const float tmin = fmax_(fmax_(fmax_(0.0f, fmin_(ax, bx)), fmin_(ay, by)), fmin_(az, bz));
     const float tmax = fmin_(fmin_(fmin_(kF32Max, fmax_(ax, bx)), fmax_(ay, by)), fmax_(az, bz));
     return tmin <= tmax ? tmin : kF32Max;
@@ -309,7 +324,8 @@ ST_D bool any_hit_fast(const KArgs& a, const Ray& ray, SE* stack) {
     if (a.bvh_len == 0u) return false;
     const float limit = ray.len;
     const V3 inv = v3(__builtin_amdgcn_rcpf(slab_safe_dir(ray.dir.x)), __builtin_amdgcn_rcpf(slab_safe_dir(ray.dir.y)), __builtin_amdgcn_rcpf(slab_safe_dir(ray.dir.z)));
-    const V3 oi = v3(-ray.origin.x * inv.x, -ray.origin.y * inv.y, -ray.origin.z * inv.z);
+    V3 oa, ob;
+    any_slab_origins(inv, ray.origin, &oa, &ob);
     // (Loop shape: ONE loop with `continue`s and a single exit, as traverse() has it. A first version returned from inside the loop;
     // the structurizer turned its exits into an inner and an outer loop, lanes waited for each other at the inner one's end, and the
     // dungeon frame went 1.520 -> 1.604 ms although every body had become cheaper.)
@@ -322,8 +338,8 @@ ST_D bool any_hit_fast(const KArgs& a, const Ray& ray, SE* stack) {
         asm volatile("" :: "v"(d1.x), "v"(d2.x), "v"(d3.x));   // one round trip for the four texels (see traverse())
         if (f2b(d0.w) == 0u) {
             uint32_t near_ptr = ptr + 64u, far_ptr = f2b(d1.w);
-            float near_d = any_slab(xyz(d0), xyz(d1), inv, oi);
-            float far_d = any_slab(xyz(d2), xyz(d3), inv, oi);
+            float near_d = any_slab(xyz(d0), xyz(d1), inv, oa, ob);
+            float far_d = any_slab(xyz(d2), xyz(d3), inv, oa, ob);
             if (far_d < near_d) { const uint32_t tp = near_ptr; near_ptr = far_ptr; far_ptr = tp; const float td = near_d; near_d = far_d; far_d = td; }
             if (far_d < limit) { if (sp < (int)a.stack_entries) { stack[sp * 64] = (SE)(far_ptr >> 6); sp++; } }
             if (near_d < limit) { ptr = near_ptr; continue; }

@@ -77,9 +77,9 @@ def test_wide_topology_is_a_rebracketing_of_the_binary_tree(name):
 
 
 def _f16_out(lo, hi):
-    """the conservative f16 rounding k_bvh_wide applies (lower bounds down, upper bounds up)"""
-    lo16 = lo.astype(np.float16); lo16 = np.where(lo16.astype(np.float32) > lo, np.nextafter(lo16, np.float16(-np.inf)), lo16)
-    hi16 = hi.astype(np.float16); hi16 = np.where(hi16.astype(np.float32) < hi, np.nextafter(hi16, np.float16(np.inf)), hi16)
+    """the conservative f16 rounding k_bvh_wide applies (st_half_box.h: lower bounds down, upper bounds up, strictly — also where f16 holds the bound)"""
+    lo16 = lo.astype(np.float16); lo16 = np.where(lo16.astype(np.float32) >= lo, np.nextafter(lo16, np.float16(-np.inf)), lo16)
+    hi16 = hi.astype(np.float16); hi16 = np.where(hi16.astype(np.float32) <= hi, np.nextafter(hi16, np.float16(np.inf)), hi16)
     return lo16.astype(np.float64), hi16.astype(np.float64)
 
 
