@@ -291,7 +291,8 @@ int st_scene_trace_rays_host(StEngine* e, const StRay* rays, uint32_t count, StR
  * Stack overflow. A walk whose stack overflows sets the engine's sticky walk word, as the queries do. */
 enum StAovKind {
     ST_AOV_DEPTH = 0,     /* f32:  distance from the camera ray's origin to the hit (the G-buffer's depth, d0.x); FLT_MAX on sky */
-    ST_AOV_NORMAL = 1,    /* f32x4: shading normal as StRayHit.normal (xyz), w = 0; 0 on sky */
+    ST_AOV_NORMAL = 1,    /* f32x4: shading normal as StRayHit.normal (xyz), w = 0; 0 on sky. Like DEPTH and MOTION it comes from the primary hit as the
+                           * frame resolved it: in the fast build that is the exact arithmetic of primary visibility, an ulp from st_camera_pick's */
     ST_AOV_ALBEDO = 2,    /* f32x4: linear base colour at the hit's uv, texture applied (what primary visibility samples), alpha in w; 0 on sky */
     ST_AOV_MOTION = 3,    /* f32x2: the renderer's velocity (current minus previous screen position in pixels, instance motion included;
                            * 0 where its squared length is below 0.001, as the velocity plane); 0 on sky */

@@ -325,3 +325,33 @@ extern "C" void or_probe_trace_rays(OrEngine* e, const float* rays, size_t count
         occluded[i] = any.distance < q[3] ? 1u : 0u;
     }
 }
+// The surface at the closest hit of each StRay record's unbounded ray, exactly as pass_prim_visibility (prim_raster.rs) forms it before GBufferEntry::pack:
+// out22[i] = distance, point[3], normal[3], uv[2], triangle slot (bits), base colour[4], emissive[3], roughness, metallic, depth, barycentric (u, v) of the
+// winning triangle as Triangle::hit forms them (triangle.rs:64-113). A miss is distance = F32_MAX and zeros.
+extern "C" void or_probe_surface_rays(OrEngine* e, const float* rays, size_t count, float* out22) {
+    EngineView v = E(e)->view();
+    for (size_t i = 0; i < count; i++) {
+        const float* q = rays + 8 * i;
+        float* o = out22 + 22 * i;
+        for (int k = 0; k < 22; k++) o[k] = 0.0f;
+        Ray r = Ray::make(Vec3(q[0], q[1], q[2]), Vec3(q[4], q[5], q[6]));
+        TriangleHit hit = TriangleHit::none();
+        uint32_t id = 0;
+        r.traverse(v.scene, ReturnClosest, &hit, &id);
+        o[0] = hit.distance;
+        if (hit.is_none()) continue;
+        const Material& material = v.scene.materials[hit.material_id];
+        const Vec4 base_color = mat_base_color(material, v.scene.atlas, hit.uv);
+        const Vec2 mr = mat_metallic_roughness(material, v.scene.atlas, hit.uv);
+        const Vec3 emissive = mat_emissive(material, v.scene.atlas, hit.uv);
+        o[1] = hit.point.x; o[2] = hit.point.y; o[3] = hit.point.z; o[4] = hit.normal.x; o[5] = hit.normal.y; o[6] = hit.normal.z;
+        o[7] = hit.uv.x; o[8] = hit.uv.y; o[9] = b2f(id);
+        o[10] = base_color.x; o[11] = base_color.y; o[12] = base_color.z; o[13] = base_color.w;
+        o[14] = emissive.x; o[15] = emissive.y; o[16] = emissive.z; o[17] = mr.y; o[18] = mr.x; o[19] = distance(r.origin, hit.point);
+        const Triangle& t = v.scene.triangles[id];
+        const Vec3 p0 = t.d0.xyz(), v0v1 = t.d3.xyz() - p0, v0v2 = t.d6.xyz() - p0;
+        const Vec3 pvec = cross(r.dir, v0v2), tvec = r.origin - p0;
+        const float inv_det = 1.0f / dot(v0v1, pvec);
+        o[20] = dot(tvec, pvec) * inv_det; o[21] = dot(r.dir, cross(tvec, v0v1)) * inv_det;
+    }
+}

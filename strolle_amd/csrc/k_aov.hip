@@ -1,6 +1,6 @@
 // k_aov.hip — per-pixel AOVs (include/strolle_hip.h "per-pixel AOVs"; st_query.cpp Engine::render_aovs): depth, shading normal, base colour,
 // motion vector and instance / triangle identity of the camera ray of every owned pixel, in one launch over the frame's 8x8 tiles (each wave
-// holds one tile's 64 coherent primary rays, as in k_prim_visibility). The walk is k_query_pick's, the attributes are closest_resolve's; albedo
+// holds one tile's 64 coherent primary rays, as in k_prim_visibility). The walk is k_query_pick's, the attributes are the frame's primary hit's (closest_resolve; the fast build's closest_resolve_exact off LDS); albedo
 // and motion are k_prim_visibility's own formulas. The three instantiations of ST_LAUNCH_TRACE with the frame's dynamic LDS stack. A plane
 // the caller did not ask for is a null pointer here: its branch is uniform over the launch and costs neither the load nor the store.
 #include "k_common.h"
@@ -22,7 +22,13 @@ __global__ ST_KERNEL_BOUNDS void k_aov(const KArgs a_in, float* depth, float4* n
     bool any = false; uint32_t used = 0u;   // used: the contract walk's byte count, not reported here
     // primary visibility's walk: exact leaf test, the tile's 64 rays as one packet where the frame's are; ablatable, as the pick is
     ST_CLOSEST_WALK(true, true, a, ray, lane_stack(a, lds), !LDS_SCENE && a.bvh_w != nullptr && a.primary_packets, &c, any, used);
+#if ST_FAST_DEVICE
+    // the frame's own primary hit: k_prim_visibility resolves it in the island's arithmetic wherever the scene does not live in LDS, so DEPTH and MOTION
+    // are the G-buffer's and the velocity plane's bits in the fast build too (closest_resolve's contracted point differs from it by an ulp)
+    const TriangleHit h = LDS_SCENE ? closest_resolve(a, ray, c, any) : closest_resolve_exact(a, ray, c, any);
+#else
     const TriangleHit h = closest_resolve(a, ray, c, any);
+#endif
     const size_t i = (size_t)pos.y * a.width + pos.x;
     if (depth) depth[i] = any ? distance(ray.origin, h.point) : kF32Max;   // the G-buffer's d0.x (k_prim_visibility g.depth)
     if (normal) normal[i] = any ? make_float4(h.normal.x, h.normal.y, h.normal.z, 0.0f) : f4z();
