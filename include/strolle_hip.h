@@ -844,6 +844,106 @@ int st_dof_process(StEngine* e, const StDofDesc* desc, const StDisplayDesc* disp
                    const void* depth_device, uint32_t width, uint32_t height, void* dst_device, int dst_format /* StOutputFormat */,
                    void* hip_stream);
 
+/* ---- fog (NEW seam): distance and height fog in front of depth of field (st_fog.cpp, k_fog.hip). In Bevy fog (FogSettings / DistanceFog)
+ * is part of the PBR fragment shader, which this engine replaces, so it has to be served here: it needs the primary hit's distance and the
+ * pixel's world-space ray. It is the first node of the output chain: scene-referred radiance along the primary ray, in front of the lens
+ * (depth of field), the shutter (motion blur) and the glare (bloom). A participating medium seen from the camera only.
+ * - Order: rendering -> fog -> depth of field -> motion blur -> bloom -> display transform -> FXAA -> resample -> output format.
+ * - Scope: the setting belongs to the camera and takes effect at its next st_render_camera. It changes only what is written to
+ *   `out_device`: AOVs, picks, scene queries, the HDR history, every plane st_camera_read_buffer returns and the auto-exposure metering are
+ *   unchanged. desc == NULL turns it off: the frame then launches the kernels it launches without the setting, with the same arguments, and
+ *   st_debug_last_launches is unchanged. The setting survives st_camera_update and st_engine_set_arithmetic. Frames that skip it, bit for
+ *   bit the frames without the setting: ST_MODE_REFERENCE and ST_MODE_BVH_HEATMAP, which have no G-buffer, and a frame whose projection is
+ *   not a perspective one (depth of field's test: projection[15] != 0, a [5] that is not positive and finite, a [0] that is 0 or not
+ *   finite). While a frame is fogged, the composing launch writes the composed colour, untransformed, into a camera-owned render-size
+ *   RGBA32F plane (and meters it); one launch (ST_PASS_POST) behind the composing launch writes the HDR plane of the next node that is on
+ *   (depth of field's, else motion blur's, else bloom's), untransformed, or what the composing launch would have written, through the
+ *   display transform and the output format.
+ * - Windows: fog is pointwise, so unlike depth of field, motion blur and post-processing it works on a camera with a window
+ *   (st_camera_set_window, st_dist_set_partition, st_dist_set_grid), in either order of the setters. Pixels keep their absolute
+ *   coordinates and only the pixels inside the window are written; tiled frames keep the fog on the ranks' cameras and need no process call
+ *   on rank 0.
+ * - Arithmetic: float32, evaluated left to right as written, no fused multiply-add, division and square root correctly rounded, in BOTH
+ *   builds; tests/fog_ref.py restates all of it in numpy and the kernel matches it bit for bit. min, max and clamp01 use the
+ *   post-processing section's NaN rule (min(a, b) = a when a < b or b is NaN, else b; max likewise with >). The only transcendentals are
+ *   exp2p and log2p below, in both builds (never the hardware's exponential and logarithm instructions):
+ *   exp(x) = exp2p(x 1.44269504088896341); pow(s, p) = s == 0 ? 0 : exp2p(p log2p(s)).
+ *   exp2p(x): NaN -> x; x > 127.999 -> +inf; x < -150 -> 0; px = floor(x); i = (int)px; x = x - px; if x > 0.5 then i = i + 1, x = x - 1;
+ *   p = (((((1.535336188319500e-4 x + 1.339887440266574e-3) x + 9.618437357674640e-3) x + 5.550332471162809e-2) x
+ *   + 2.402264791363012e-1) x + 6.931472028550421e-1) x + 1; the result is scale2(p, i), where scale2(z, n) = z 2^n in float with two
+ *   multiplications when n leaves [-126, 127]: n > 127: z = z 2^127, n = min(n - 127, 127); n < -126: z = z 2^-126, n = max(n + 126, -126);
+ *   then z 2^n.
+ *   log2p(x), x > 0 finite: if x is subnormal, x = x 2^23 and e = -23, else e = 0; e = e + (biased exponent of x) - 126; m = the
+ *   significand of x in [0.5, 1); if m < 0.707106781186547524 then e = e - 1, m = (m + m) - 1, else m = m - 1; z = m m;
+ *   y = ((((((((7.0376836292e-2 m - 1.1514610310e-1) m + 1.1676998740e-1) m - 1.2420140846e-1) m + 1.4249322787e-1) m - 1.6668057665e-1) m
+ *   + 2.0000714765e-1) m - 2.4999993993e-1) m + 3.3333331174e-1) m z; y = y - 0.5 z; r = y 0.44269504088896340736;
+ *   r = r + m 0.44269504088896340736; r = r + y; r = r + m; r = r + (float)e.
+ *   C is the composed HDR colour, D the distance along the pixel's ray, P the column-major projection, M the column-major camera transform
+ *   (M[12..14] the camera position), b = height_falloff, a = color[3]. In a frame, D is PRIM_GBUFFER_D0.x of the frame's parity
+ *   (ST_AOV_DEPTH's value), with 0 (sky) read as FLT_MAX, and P and M are the camera's; in st_fog_process they are the given ones.
+ * - 0. Host constants, in double, each rounded to float once: L = light_direction normalised (each component converted to double, divided
+ *   by the length); with ST_FOG_FOLLOW_SUN the engine's sun direction of the last st_tick (st_sun_update takes effect at the next tick).
+ *   y0 = M[13]. E0 = exp(clamp(-b (y0 - height_reference), -80, 80)).
+ * - 1. Ray (per pixel (x, y), absolute coordinates in the W x H frame): ndc_x = (x + 0.5) 2 / W - 1; ndc_y = -((y + 0.5) 2 / H - 1);
+ *   ax = (ndc_x + P[8]) / P[0]; ay = (ndc_y + P[9]) / P[5]; c = 1 / sqrt((ax ax + ay ay) + 1), exactly as in depth of field's step 1.
+ *   v = (ax c, ay c, -c). w = M.col0 v.x + M.col1 v.y + M.col2 v.z per component, left to right. w is not normalised again: a camera
+ *   transform with scale scales the height term and the glow's cosine with it, which is the caller's business. dy = w.y.
+ * - 2. Distance: if D is not > 0 (NaN included) the pixel passes through: it keeps its own four words, NaN, infinities and alpha. If
+ *   D >= FLT_MAX (sky, +inf): without ST_FOG_SKY the pixel passes through, with it d = sky_distance. Otherwise d = D.
+ * - 3. Height: if b = 0, d_e = d. Else k = min(max((b dy) d, -80), 80); G = |k| < 0.03125 ? 1 - k (0.5 - k 0.16666667)
+ *   : (1 - exp(-k)) / k; d_e = min(d (E0 G), FLT_MAX). This is the closed-form optical depth, as an equivalent distance at the stated
+ *   density, of a density that falls off as exp(-b (y - height_reference)). With the series switch at 1 / 32, G stays within 4e-6 relative
+ *   of float64 over |k| <= 80.
+ * - 4. Factors: LINEAR: g = clamp01((d_e - start) / (end - start)). EXPONENTIAL: g = 1 - exp(-(density d_e)). EXPONENTIAL_SQUARED:
+ *   u = density d_e; g = 1 - exp(-(u u)). For these three ge = gi = g a, the same for every channel. ATMOSPHERIC, per channel:
+ *   ge = (1 - exp(-(extinction d_e))) a; gi = (1 - exp(-(inscattering d_e))) a. If every ge and gi is 0, the pixel passes through.
+ * - 5. Colour: s = min(max((w.x L.x + w.y L.y) + w.z L.z, 0), 1); F = min(color.rgb + light_color pow(s, light_exponent), FLT_MAX) per
+ *   channel, or color.rgb when light_color is all 0 (the lobe is skipped). c' = min(max(C, 0), 65504) per channel.
+ *   out = c' (1 - ge) + F gi per channel, alpha 1.
+ * - Deviations from the first statement of this arithmetic, found ill-defined while building it: (1) s is also clamped to 1 from above: a
+ *   transform with scale gives w L > 1, pow overflows to +inf and a zero channel of light_color times +inf is NaN; (2) F is held at
+ *   FLT_MAX: color.rgb + light_color may overflow to +inf, and +inf times a zero gi (ATMOSPHERIC with one channel's inscattering 0) is NaN.
+ *   With both, no finite input produces NaN (a non-finite entry of P or M is cleaned by the NaN rule of min and max: s = 0, k = -80).
+ * - Known limits: the ray's origin is taken as the camera position M[12..14], while the renderer's rays start on the near plane, so D is
+ *   short by the near distance along the ray; the auto-exposure metering stays in the composing launch, in front of the fog, so it meters
+ *   the unfogged frame; the medium is seen from the camera only: it neither shadows the glow (no light shafts) nor attenuates the light
+ *   that reaches surfaces or GI paths.
+ * - Errors: ST_ERR_INVALID_ARGUMENT for a wrong struct_size, an unknown falloff or flag bit, a field outside its stated range (NaN
+ *   included; only the fields the falloff and the flags name are looked at: start and end with LINEAR, density with the two exponentials,
+ *   extinction and inscattering with ATMOSPHERIC, sky_distance with ST_FOG_SKY, light_exponent and light_direction when light_color is
+ *   not all 0, light_direction not with ST_FOG_FOLLOW_SUN; height_reference is finite; light_color is finite and >= 0), null pointers where
+ *   they are not allowed, a side of 0 or above 16384, an auto-exposure display, ST_FOG_FOLLOW_SUN (a stateless call has no engine sun) or a
+ *   non-perspective projection given to the process call. An unknown camera is ST_ERR_UNKNOWN_CAMERA. Set and get are host work and valid
+ *   on a host-only engine; st_fog_process returns ST_ERR_NO_DEVICE there. */
+enum StFogFalloff { ST_FOG_LINEAR = 0, ST_FOG_EXPONENTIAL = 1, ST_FOG_EXPONENTIAL_SQUARED = 2, ST_FOG_ATMOSPHERIC = 3 };
+enum { ST_FOG_SKY = 1, ST_FOG_FOLLOW_SUN = 2 };
+typedef struct StFogDesc {                 /* 112 B */
+    uint32_t struct_size, falloff, flags, _pad;   /* sizeof(StFogDesc), StFogFalloff, ST_FOG_*, ignored */
+    float color[4];                        /* linear rgb, finite, >= 0; a in [0, 1] = the most the fog may cover (Bevy's fog colour alpha) */
+    float start, end;                      /* LINEAR: metres, finite, start < end */
+    float density;                         /* EXPONENTIAL, EXPONENTIAL_SQUARED: per metre, finite, >= 0 */
+    float height_falloff;                  /* b, per metre, finite, >= 0; 0 = density does not depend on height */
+    float height_reference;                /* world y at which the density is the stated one */
+    float sky_distance;                    /* ST_FOG_SKY: the distance sky pixels are fogged at, finite, > 0 */
+    float extinction[3];                   /* ATMOSPHERIC: per metre and channel, finite, >= 0 */
+    float inscattering[3];
+    float light_color[3];                  /* the glow towards a directional light; all 0 = none */
+    float light_exponent;                  /* finite, > 0 when light_color is not all 0; Bevy's default 8 */
+    float light_direction[3];              /* towards the light, any non-zero length (normalised on the host in double); ignored with ST_FOG_FOLLOW_SUN */
+    float _pad2;                           /* ignored */
+} StFogDesc;
+int st_camera_set_fog(StEngine* e, StHandle camera, const StFogDesc* desc);   /* NULL = off */
+/* the last desc set (a zeroed desc with struct_size when none was) and whether fog is on; either pointer may be NULL */
+int st_camera_get_fog(StEngine* e, StHandle camera, StFogDesc* out, int* enabled);
+/* Stateless, like st_dof_process. color: RGBA32F; depth: f32 (ST_AOV_DEPTH's layout, FLT_MAX on sky); transform and projection: the 16
+ * floats each of the column-major camera transform and perspective projection the planes were rendered with (host memory, read during the
+ * call); display NULL = none, manual exposure only; dst in dst_format, width x height. Needs a device engine; no camera, no tick.
+ * Enqueued on hip_stream without a host sync; the node needs no scratch memory, so nothing is allocated. ST_FOG_FOLLOW_SUN is refused. No
+ * input may overlap dst. */
+int st_fog_process(StEngine* e, const StFogDesc* desc, const StDisplayDesc* display, const float transform[16], const float projection[16],
+                   const void* color_device, const void* depth_device, uint32_t width, uint32_t height, void* dst_device,
+                   int dst_format /* StOutputFormat */, void* hip_stream);
+
 /* ---- multi-GPU behind the boundary (NEW seam; SURVEY.md section 8e, BASELINE.json configs 4 and 5). One process per GPU, one
  * engine per process, the scene replicated; the frame is cut into tiles, every rank renders its tile (+ an apron of redundant
  * pixels in Image mode, whose passes read neighbours) with absolute pixel coordinates, and the ONE collective of the path
@@ -1023,7 +1123,7 @@ enum StPassBit {
     ST_PASS_DENOISE_REPROJECT_DI = 1u << 18, ST_PASS_DENOISE_REPROJECT_GI = 1u << 19, ST_PASS_DENOISE_VARIANCE = 1u << 20,
     ST_PASS_DENOISE_WAVELET_0 = 1u << 21, /* ... wavelet pass n = ST_PASS_DENOISE_WAVELET_0 << n, n < 5 */
     ST_PASS_COMPOSITION = 1u << 26, ST_PASS_BVH_HEATMAP = 1u << 27, ST_PASS_REF_TRACING = 1u << 28, ST_PASS_REF_SHADING = 1u << 29,
-    ST_PASS_POST = 1u << 30   /* the launches behind composition, one launch group: depth of field ("depth of field" above), motion blur ("motion blur"), bloom ("bloom"), then FXAA and / or the resampler ("post-processing") */
+    ST_PASS_POST = 1u << 30   /* the launches behind composition, one launch group: fog ("fog" above), depth of field ("depth of field"), motion blur ("motion blur"), bloom ("bloom"), then FXAA and / or the resampler ("post-processing") */
 };
 int st_debug_set_pass_mask(StEngine* e, uint64_t mask);
 /* Measurement only (tools/pair_matrix.py): the frame's graph is built as always — every fusion of the whole frame — but only the launches

@@ -352,6 +352,40 @@ extern "C" {
     pub fn st_dof_process(e: *mut StEngine, desc: *const StDofDesc, display: *const StDisplayDesc, projection: *const f32, color_device: *const c_void, depth_device: *const c_void, width: u32, height: u32, dst_device: *mut c_void, dst_format: i32, hip_stream: *mut c_void) -> i32;
 }
 
+// fog (include/strolle_hip.h "fog"): distance and height fog in front of depth of field
+pub const ST_FOG_LINEAR: u32 = 0;
+pub const ST_FOG_EXPONENTIAL: u32 = 1;
+pub const ST_FOG_EXPONENTIAL_SQUARED: u32 = 2;
+pub const ST_FOG_ATMOSPHERIC: u32 = 3;
+pub const ST_FOG_SKY: u32 = 1;
+pub const ST_FOG_FOLLOW_SUN: u32 = 2;
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct StFogDesc {
+    pub struct_size: u32,
+    pub falloff: u32,
+    pub flags: u32,
+    pub _pad: u32,
+    pub color: [f32; 4],
+    pub start: f32,
+    pub end: f32,
+    pub density: f32,
+    pub height_falloff: f32,
+    pub height_reference: f32,
+    pub sky_distance: f32,
+    pub extinction: [f32; 3],
+    pub inscattering: [f32; 3],
+    pub light_color: [f32; 3],
+    pub light_exponent: f32,
+    pub light_direction: [f32; 3],
+    pub _pad2: f32,
+}
+extern "C" {
+    pub fn st_camera_set_fog(e: *mut StEngine, camera: u64, desc: *const StFogDesc) -> i32; // null = off
+    pub fn st_camera_get_fog(e: *mut StEngine, camera: u64, out: *mut StFogDesc, enabled: *mut i32) -> i32;
+    pub fn st_fog_process(e: *mut StEngine, desc: *const StFogDesc, display: *const StDisplayDesc, transform: *const f32, projection: *const f32, color_device: *const c_void, depth_device: *const c_void, width: u32, height: u32, dst_device: *mut c_void, dst_format: i32, hip_stream: *mut c_void) -> i32;
+}
+
 // ---- the HIP runtime, as far as the staging-copy present needs it (libamdhip64)
 pub type hipStream_t = *mut c_void;
 extern "C" {

@@ -229,6 +229,40 @@ def dof_plan(desc: StDofDesc, width: int, height: int):
     return n.value, (tiles[0], tiles[1]), np.array(taps, np.float32).reshape(DOF_MAX_SAMPLES, 3)[:n.value].copy()
 
 
+class FogFalloff(enum.IntEnum):
+    """include/strolle_hip.h StFogFalloff: how the fog factor grows with the distance (Bevy's FogFalloff variants)"""
+    LINEAR = 0
+    EXPONENTIAL = 1
+    EXPONENTIAL_SQUARED = 2
+    ATMOSPHERIC = 3
+
+
+class StFogDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("falloff", C.c_uint32), ("flags", C.c_uint32), ("_pad", C.c_uint32), ("color", C.c_float * 4),
+                ("start", C.c_float), ("end", C.c_float), ("density", C.c_float), ("height_falloff", C.c_float), ("height_reference", C.c_float),
+                ("sky_distance", C.c_float), ("extinction", C.c_float * 3), ("inscattering", C.c_float * 3), ("light_color", C.c_float * 3),
+                ("light_exponent", C.c_float), ("light_direction", C.c_float * 3), ("_pad2", C.c_float)]
+
+
+FOG_SKY, FOG_FOLLOW_SUN = 1, 2
+
+
+def fog_desc(falloff=FogFalloff.EXPONENTIAL, color=(1.0, 1.0, 1.0, 1.0), start: float = 0.0, end: float = 100.0, density: float = 0.0,
+             height_falloff: float = 0.0, height_reference: float = 0.0, sky_distance=None, extinction=(0.0, 0.0, 0.0), inscattering=(0.0, 0.0, 0.0),
+             light_color=(0.0, 0.0, 0.0), light_exponent: float = 8.0, light_direction=(0.0, 1.0, 0.0), follow_sun: bool = False) -> StFogDesc:
+    """A StFogDesc (include/strolle_hip.h "fog"). color: linear rgb and the alpha that bounds how much the fog may cover; start / end with
+    LINEAR, density with the two exponentials, extinction / inscattering with ATMOSPHERIC; height_falloff 0 = no height dependence;
+    sky_distance: None (sky pixels keep their colour) or the distance the sky is fogged at; light_color all 0 = no glow; follow_sun: the
+    glow points at the engine's sun instead of light_direction."""
+    rgba = tuple(float(v) for v in color) + ((1.0,) if len(color) == 3 else ())
+    flags = (FOG_SKY if sky_distance is not None else 0) | (FOG_FOLLOW_SUN if follow_sun else 0)
+    f3 = C.c_float * 3
+    return StFogDesc(C.sizeof(StFogDesc), int(falloff), flags, 0, (C.c_float * 4)(*rgba), float(start), float(end), float(density), float(height_falloff),
+                     float(height_reference), float(sky_distance) if sky_distance is not None else 0.0, f3(*[float(v) for v in extinction]),
+                     f3(*[float(v) for v in inscattering]), f3(*[float(v) for v in light_color]), float(light_exponent),
+                     f3(*[float(v) for v in light_direction]), 0.0)
+
+
 class StBloomDesc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("levels", C.c_uint32), ("intensity", C.c_float),
                 ("low_frequency_boost", C.c_float), ("low_frequency_boost_curvature", C.c_float), ("high_pass_frequency", C.c_float),
@@ -578,6 +612,10 @@ class _Binding:
             self.camera_get_dof = fn("camera_get_dof", [vp, u64, P(StDofDesc), P(i32)])
             self.dof_plan = fn("dof_plan", [P(StDofDesc), u32, u32, P(u32), P(u32), P(C.c_float)])
             self.dof_process = fn("dof_process", [vp, P(StDofDesc), P(StDisplayDesc), P(C.c_float), vp, vp, u32, u32, vp, i32, vp])
+        if hasattr(lib, prefix + "camera_set_fog"):   # fog (likewise)
+            self.camera_set_fog = fn("camera_set_fog", [vp, u64, P(StFogDesc)])
+            self.camera_get_fog = fn("camera_get_fog", [vp, u64, P(StFogDesc), P(i32)])
+            self.fog_process = fn("fog_process", [vp, P(StFogDesc), P(StDisplayDesc), P(C.c_float), P(C.c_float), vp, vp, u32, u32, vp, i32, vp])
         if hasattr(lib, prefix + "mesh_set_skin"):
             self.mesh_set_skin = fn("mesh_set_skin", [vp, u64, vp, sz, u32])
         if hasattr(lib, prefix + "mesh_set_morph_targets"):   # morph targets (likewise absent from an older library)
@@ -1147,6 +1185,27 @@ class Engine(EngineBase):
         major), then the (manual) display transform, into dst (width x height) in dst_format."""
         proj = (C.c_float * 16)(*[float(v) for v in projection])
         self._check(self._b.dof_process(self._h, C.byref(desc), C.byref(display) if display is not None else None, proj, color_ptr, depth_ptr, width, height,
+                                        dst_ptr, int(dst_format), stream))
+
+    # ---- fog (include/strolle_hip.h "fog"): takes effect at the camera's next render
+    def set_fog(self, camera: int, desc: Optional[StFogDesc] = None, **kw):
+        """st_camera_set_fog: a StFogDesc, or fog_desc(**kw) when keywords are given; neither = off."""
+        if desc is None and kw:
+            desc = fog_desc(**kw)
+        self._check(self._b.camera_set_fog(self._h, camera, C.byref(desc) if desc is not None else None))
+
+    def get_fog(self, camera: int):
+        """st_camera_get_fog: (the last StFogDesc set, whether fog is on)."""
+        d, on = StFogDesc(), C.c_int()
+        self._check(self._b.camera_get_fog(self._h, camera, C.byref(d), C.byref(on)))
+        return d, bool(on.value)
+
+    def fog_process(self, desc: StFogDesc, transform, projection, color_ptr: int, depth_ptr: int, width: int, height: int, dst_ptr: int, dst_format: int = 0,
+                    display: Optional[StDisplayDesc] = None, stream: int = 0):
+        """st_fog_process: fog over any RGBA32F colour and f32 depth device planes rendered with `transform` and `projection` (16 floats
+        each, column major), then the (manual) display transform, into dst (width x height) in dst_format."""
+        xf, proj = (C.c_float * 16)(*[float(v) for v in transform]), (C.c_float * 16)(*[float(v) for v in projection])
+        self._check(self._b.fog_process(self._h, C.byref(desc), C.byref(display) if display is not None else None, xf, proj, color_ptr, depth_ptr, width, height,
                                         dst_ptr, int(dst_format), stream))
 
     # ---- environment lighting (include/strolle_hip.h "environment lighting"): takes effect at the next tick

@@ -432,6 +432,28 @@ int st_dof_process(StEngine* e, const StDofDesc* desc, const StDisplayDesc* disp
     return E(e)->dof_process(desc, display, projection, color, depth, width, height, dst, dst_format, static_cast<hipStream_t>(stream));
 }
 
+// ---- fog (st_fog.cpp)
+int st_camera_set_fog(StEngine* e, StHandle h, const StFogDesc* desc) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    return E(e)->set_fog(*it->second, desc);
+}
+int st_camera_get_fog(StEngine* e, StHandle h, StFogDesc* out, int* enabled) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    const CameraState& s = *it->second;
+    if (out) { *out = s.fog; out->struct_size = sizeof(StFogDesc); }
+    if (enabled) *enabled = s.fog_on ? 1 : 0;
+    return ST_OK;
+}
+int st_fog_process(StEngine* e, const StFogDesc* desc, const StDisplayDesc* display, const float transform[16], const float projection[16], const void* color, const void* depth,
+                   uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
+    ST_REQUIRE(e, "null engine");
+    return E(e)->fog_process(desc, display, transform, projection, color, depth, width, height, dst, dst_format, static_cast<hipStream_t>(stream));
+}
+
 int st_debug_set_bloom_tail(StEngine* e, int lds_bytes, uint32_t* in_force) {
     ST_REQUIRE(e, "null engine");
     ST_REQUIRE(lds_bytes >= -1, "lds_bytes is -1 (what the device grants), 0 (no fused tail) or a byte count");

@@ -9,6 +9,7 @@
 //   st_bloom.cpp        bloom: the plan, the chain of launches
 //   st_motion_blur.cpp  motion blur: the plan, its three launches
 //   st_dof.cpp          depth of field: the plan (host constants, tap table), its three launches
+//   st_fog.cpp          fog: the checks, the host constants, its one launch
 //   st_deform.cpp       mesh deformation (st_deform.h): skinned meshes, morph targets, deformation motion; the tick's launches
 //   st_env.cpp          environment lighting: the map, its importance table
 //   st_query.cpp        scene queries: closest hit, occlusion, picks
@@ -415,6 +416,15 @@ struct CameraState {
     FencedPlanes<4> dof_planes;   // [0] the HDR plane, [1] (coc, Z) per pixel, [2] the tiles' near-field maxima, [3] their 3 x 3 neighbour maxima
     // heatmap and reference frames have no G-buffer; the focal length is derived from a perspective projection
     bool focuses() const { return dof_on && desc.mode != ST_MODE_BVH_HEATMAP && desc.mode != ST_MODE_REFERENCE && dof_perspective(desc.projection); }
+    // Fog (st_fog.cpp; include/strolle_hip.h "fog"), the first node of the output chain, in front of depth of field; it survives
+    // st_camera_update like the rest. While a frame is fogged, the composing launch writes the HDR plane and one launch behind it writes where
+    // the composing launch would have (or the HDR plane of the next node that is on). Pointwise, so a window does not exclude it. That launch
+    // reads the G-buffer of the frame's parity, which primary visibility of the frame after next rewrites: fog_depth_read[parity] is recorded
+    // behind it and the next primary-visibility launch of that parity waits for it (DESIGN.md "Fog").
+    StFogDesc fog{}; bool fog_on = false;
+    FencedPlanes<1> fog_planes;   // [0] the HDR plane
+    Fence fog_depth_read[2];
+    bool fogs() const { return fog_on && desc.mode != ST_MODE_BVH_HEATMAP && desc.mode != ST_MODE_REFERENCE && dof_perspective(desc.projection); }
     uint32_t out_width() const { return post_on && post.output_width != 0u ? post.output_width : desc.width; }
     uint32_t out_height() const { return post_on && post.output_width != 0u ? post.output_height : desc.height; }
     // A present copy still in flight writes the caller's host memory: it lands before the stream goes. Everything else goes with its member —
@@ -817,6 +827,13 @@ struct Engine {
     void launch_dof_step(const DofSteps& s, uint32_t i, hipStream_t stream);
     int dof_process(const StDofDesc* desc, const StDisplayDesc* display, const float* projection, const void* color, const void* depth, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
     FencedPlanes<3> dof_scratch;   // st_dof_process's packed plane and tile values: grown, never shrunk
+    // ---- fog (st_fog.cpp)
+    struct FogStep { FogArgs args; int slot; double bytes; };
+    static void fog_step(const StFogDesc& d, const float transform[16], const float projection[16], const float sun[3], const void* color, const void* depth, bool frame,
+                         uint32_t w, uint32_t h, uint32_t row0, uint32_t row1, uint32_t col0, uint32_t col1, void* dst, uint32_t format, bool raw, const DisplayArgs& display, FogStep& out);
+    int set_fog(CameraState& c, const StFogDesc* desc);
+    int fog_process(const StFogDesc* desc, const StDisplayDesc* display, const float* transform, const float* projection, const void* color, const void* depth,
+                    uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
     int scene_args(KArgs& a, bool heatmap) const;   // the scene half of KArgs (st_render.cpp): render() and the scene queries
     void light_args(KArgs& a) const;                // its lights, LUT and environment half: render()
 

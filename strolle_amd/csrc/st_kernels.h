@@ -43,6 +43,7 @@ enum KernelSlot {
     KS_BLOOM_DOWN, KS_BLOOM_UP, KS_BLOOM_COMPOSITE, KS_BLOOM_TAIL,  // bloom in front of the display transform (k_bloom.hip); bytes depend on the level: render() credits them itself
     KS_MBLUR_PACK, KS_MBLUR_NEIGHBOUR, KS_MBLUR_GATHER,  // motion blur in front of bloom (k_motion_blur.hip); render() credits their bytes itself
     KS_DOF_PACK, KS_DOF_NEIGHBOUR, KS_DOF_GATHER,  // depth of field in front of motion blur (k_dof.hip); render() credits their bytes itself
+    KS_FOG,  // fog in front of depth of field (k_fog.hip); render() credits its bytes itself
     KS_COUNT
 };
 struct KernelInfo { const char* name; float bytes_per_unit; bool half; };
@@ -76,6 +77,7 @@ inline const KernelInfo& kernel_info(int slot) {
         {"bloom_tail", 0.f, false},
         {"motion_blur_pack", 0.f, false},    {"motion_blur_neighbour", 0.f, false}, {"motion_blur_gather", 0.f, false},
         {"dof_pack", 0.f, false},            {"dof_neighbour", 0.f, false},        {"dof_gather", 0.f, false},
+        {"fog", 0.f, false},
     };
     return k[slot];
 }

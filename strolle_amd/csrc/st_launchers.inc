@@ -102,3 +102,5 @@ ST_LAUNCHER(launch_mblur_gather, (const MBlurArgs& p, hipStream_t s))
 ST_LAUNCHER(launch_dof_pack, (const DofArgs& p, hipStream_t s))
 ST_LAUNCHER(launch_dof_neighbour, (const DofArgs& p, hipStream_t s))
 ST_LAUNCHER(launch_dof_gather, (const DofArgs& p, hipStream_t s))
+// fog (k_fog.hip; st_fog.cpp): one pointwise launch over the window, one workgroup per 32 x 8 pixels
+ST_LAUNCHER(launch_fog, (const FogArgs& p, hipStream_t s))

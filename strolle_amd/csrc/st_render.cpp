@@ -171,10 +171,19 @@ namespace {
 // (st_motion_blur.cpp) sits in front of bloom in the same way: the composing launch writes the blur's HDR plane, and the gather writes bloom's
 // HDR plane (untransformed) or, without bloom, what the composing launch would have written. Depth of field (st_dof.cpp) sits in front of
 // motion blur: the composing launch writes its HDR plane, and its gather writes the HDR plane of the next node that is on (motion blur's, else
-// bloom's), or what the composing launch would have written.
+// bloom's), or what the composing launch would have written. Fog (st_fog.cpp) is the first node, in front of depth of field. The four HDR
+// nodes form an ordered list: the composing launch writes the plane of the first node that is on, and each node writes the plane of the next
+// one that is on (`node_dst`), the last one what the composing launch would have written.
+enum HdrNode { kNodeFog, kNodeDof, kNodeMBlur, kNodeBloom, kHdrNodes };
 struct OutputRoute {
-    bool post_fxaa = false, post = false, bloom = false, mblur = false, dof = false;
+    bool post_fxaa = false, post = false, bloom = false, mblur = false, dof = false, fog = false;
     Engine::BloomPlan bloom_plan; Engine::MBlurPlan mblur_plan; Engine::DofPlan dof_plan;
+    void* hdr_plane[kHdrNodes] = {};   // the render-size RGBA32F plane each node that is on reads, in chain order
+    // where node `n` writes (n = -1: the composing launch): the next node's plane, raw (RGBA32F, untransformed), or the frame's target
+    void* node_dst(int n, bool* raw) const {
+        for (int k = n + 1; k < kHdrNodes; k++) if (hdr_plane[k]) { *raw = true; return hdr_plane[k]; }
+        *raw = false; return frame_out;
+    }
     void* comp_out = nullptr; uint32_t comp_format = 0; DisplayArgs comp_disp{};      // the composing launch (either of the two): target, format, display transform
     void* frame_out = nullptr; uint32_t frame_format = 0; DisplayArgs frame_disp{};   // the bloom composite: `out` or the post plane; no display: NONE at scale 1, which stores the colour's own bits
 };
@@ -188,7 +197,7 @@ struct FrameSwitches {
 // visibility and the GI chain to the camera's side stream); the rest below `s` is launch bookkeeping.
 struct Frame {
     Engine& e; CameraState& c; void* const out; const hipStream_t stream; hipStream_t cur;
-    KArgs a{}; OutputRoute route; FrameSwitches s{}; Engine::MBlurSteps blur{}; Engine::DofSteps dof{};
+    KArgs a{}; OutputRoute route; FrameSwitches s{}; Engine::MBlurSteps blur{}; Engine::DofSteps dof{}; Engine::FogStep fog{};
     const uint32_t mode, pseed;   // pseed: one seed for both preview passes (passes/gi_preview_resampling.rs:60-74)
     bool mask_split = false, di_reprojected = false, gi_reprojected = false, composed = false, luts_generated_now = false; uint32_t launch_ordinal = 0u;
     Frame(Engine& e_, CameraState& c_, void* out_, hipStream_t s_) : e(e_), c(c_), out(out_), stream(s_), cur(s_), mode(c_.desc.mode), pseed(pass_seed(e_.base_seed, c_.frame, SEED_GI_PREVIEW)) {}
@@ -246,10 +255,18 @@ struct Frame {
             r.dof = true;
             if (int rc = c.dof_planes.acquire({plane, r.dof_plan.packed_bytes, r.dof_plan.tile_bytes, r.dof_plan.tile_bytes}, c.dof_planes.Grow, stream)) return rc;
         }
+        if (out && c.fogs()) {
+            r.fog = true;
+            if (int rc = c.fog_planes.acquire({plane}, c.fog_planes.Grow, stream)) return rc;
+        }
+        if (r.fog) r.hdr_plane[kNodeFog] = c.fog_planes.plane[0].ptr;
+        if (r.dof) r.hdr_plane[kNodeDof] = c.dof_planes.plane[0].ptr;
+        if (r.mblur) r.hdr_plane[kNodeMBlur] = c.mblur_planes.plane[0].ptr;
+        if (r.bloom) r.hdr_plane[kNodeBloom] = c.bloom_planes.plane[0].ptr;
         r.frame_out = r.post ? c.post_planes.plane[0].ptr : out; r.frame_format = r.post ? (uint32_t)ST_FORMAT_RGBA32F : c.out_format;
         r.frame_disp = disp; if (!r.frame_disp.on) r.frame_disp.scale = 1.0f;
-        const bool hdr_chain = r.bloom || r.mblur || r.dof;   // the composing launch feeds an HDR node: it stores the composed colour as it is
-        r.comp_out = r.dof ? c.dof_planes.plane[0].ptr : (r.mblur ? c.mblur_planes.plane[0].ptr : (r.bloom ? c.bloom_planes.plane[0].ptr : r.frame_out)); r.comp_format = hdr_chain ? (uint32_t)ST_FORMAT_RGBA32F : r.frame_format;
+        bool hdr_chain = false;   // the composing launch feeds an HDR node: it stores the composed colour as it is
+        r.comp_out = r.node_dst(-1, &hdr_chain); r.comp_format = hdr_chain ? (uint32_t)ST_FORMAT_RGBA32F : r.frame_format;
         if (hdr_chain) { if (disp.meter) disp.tonemap = kDisplayRaw; else disp = DisplayArgs{}; }   // the composing launch: meter, do not transform
         r.comp_disp = disp;
         return ST_OK;
@@ -340,15 +357,21 @@ struct Frame {
         a.gi_skip_history_copy = s.gi_skip_history_copy; a.variance_in_reproject = s.variance_in_reproject; a.lean = s.lean; a.skip_dead_scratch = s.skip_dead_scratch;
         if (route.mblur) {   // the blur's three launches (blur_pack, finish_output): into bloom's HDR plane, untransformed, when the frame blooms
             const FencedPlanes<4>& p = c.mblur_planes;
+            bool raw = false; void* dst = route.node_dst(kNodeMBlur, &raw);
             blur = Engine::mblur_steps(c.mblur, route.mblur_plan, p.plane[0].ptr, a.velocity, a.g0, true, c.desc.width, c.desc.height, p.plane[1].as<float2>(), p.plane[2].as<float4>(),
-                                       p.plane[3].as<float4>(), route.bloom ? c.bloom_planes.plane[0].ptr : route.frame_out, route.frame_format, route.bloom, route.frame_disp);
+                                       p.plane[3].as<float4>(), dst, route.frame_format, raw, route.frame_disp);
         }
         if (route.dof) {   // depth of field's three launches (dof_pack, finish_output): into the next HDR node's plane, untransformed, when there is one
             const FencedPlanes<4>& p = c.dof_planes;
-            const bool raw = route.mblur || route.bloom;
-            void* dst = route.mblur ? c.mblur_planes.plane[0].ptr : (route.bloom ? c.bloom_planes.plane[0].ptr : route.frame_out);
+            bool raw = false; void* dst = route.node_dst(kNodeDof, &raw);
             if (int rc = Engine::dof_steps(c.dof, route.dof_plan, c.desc.projection, p.plane[0].ptr, a.g0, true, c.desc.width, c.desc.height, p.plane[1].as<float2>(), p.plane[2].as<float>(),
                                            p.plane[3].as<float>(), dst, route.frame_format, raw, route.frame_disp, dof)) return rc;
+        }
+        if (route.fog) {   // fog's one launch (finish_output): into the next HDR node's plane, untransformed, when there is one. Windows are honoured.
+            bool raw = false; void* dst = route.node_dst(kNodeFog, &raw);
+            const float sun[3] = {e.sun_dir_.x, e.sun_dir_.y, e.sun_dir_.z};   // as KArgs::sun_dir carries it (light_args)
+            Engine::fog_step(c.fog, c.desc.transform, c.desc.projection, sun, c.fog_planes.plane[0].ptr, a.g0, true, c.desc.width, c.desc.height, c.row0, c.row1, c.col0, c.col1,
+                             dst, route.frame_format, raw, route.frame_disp, fog);
         }
         c.last_lean = s.lean; c.last_lean_composed = s.compose_in_wavelet && s.lean != 0u;   // which planes the frame leaves unwritten: the last a-trous pass's colour planes too
         return ST_OK;
@@ -380,6 +403,8 @@ struct Frame {
         run(KS_REF_SHADING, ST_PASS_REF_SHADING, [&] { e.L.launch_ref_shading(a, seed(SEED_REF_SHADING + 255u), 255u, cur); });
     }
     void prim() {
+        // the fog launch of the frame before last read the G-buffer this launch rewrites, behind that frame's composing launch (DESIGN.md "Fog")
+        (void)c.fog_depth_read[c.frame % 2u].wait(cur, Fence::OtherStreams, Fence::Clear);
         if (e.tuning.fuse && s.any_objects) run(KS_PRIM_VISIBILITY_REPROJECTION, ST_PASS_PRIM_VISIBILITY | ST_PASS_FRAME_REPROJECTION, [&] { e.L.launch_prim_visibility(a, true, e.deform.deform_table(), e.deform.deform_posed(), cur); });
         else run(KS_PRIM_VISIBILITY, ST_PASS_PRIM_VISIBILITY, [&] { e.L.launch_prim_visibility(a, false, e.deform.deform_table(), e.deform.deform_posed(), cur); });
         if (s.any_objects && !e.tuning.fuse) run(KS_FRAME_REPROJECTION, ST_PASS_FRAME_REPROJECTION, [&] { e.L.launch_frame_reprojection(a, cur); });
@@ -572,10 +597,15 @@ struct Frame {
         if (c.side_stream) { if (int rc = c.ev_prim_ok.record(stream)) return rc; if (int rc = c.ev_frame_done.record(stream)) return rc; }
         return ST_OK;
     }
-    // The launches behind the composing launch, which ran on `stream`: depth of field, motion blur, bloom, then post-processing — one launch group (ST_PASS_POST) —, then the
+    // The launches behind the composing launch, which ran on `stream`: fog, depth of field, motion blur, bloom, then post-processing — one launch group (ST_PASS_POST) —, then the
     // meter's finalize; each step's fence is recorded behind its launches.
     int finish_output() {
         cur = stream;
+        if (route.fog) {   // it reads the camera's HDR plane and this frame's G-buffer depth: the frame after next rewrites that plane, and its primary visibility waits for this
+            run(fog.slot, ST_PASS_POST, [&] { e.L.launch_fog(fog.args, cur); }, fog.bytes);
+            if (int rc = c.fog_planes.done(stream)) return rc;
+            if (int rc = c.fog_depth_read[c.frame % 2u].record(stream)) return rc;
+        }
         if (route.dof) {   // depth of field's neighbour maximum and gather: they read the camera's packed plane, tile values and HDR plane only
             for (uint32_t i = 1; i < 3u; i++) run(dof.step[i].slot, ST_PASS_POST, [&] { e.launch_dof_step(dof, i, cur); }, dof.step[i].bytes);
             if (int rc = c.dof_planes.done(stream)) return rc;

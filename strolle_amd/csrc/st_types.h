@@ -143,6 +143,21 @@ struct DofArgs {
     float taps[kDofMaxSamples * 3u];
 };
 
+// Fog (include/strolle_hip.h "fog"; st_fog.cpp, k_fog.hip): the arguments of its one launch. It reads `color` and the depth — in a frame
+// PRIM_GBUFFER_D0.x with 0 read as FLT_MAX (`frame` != 0), in st_fog_process a float plane as it is — of the pixels of the window
+// [row0, row1) x [col0, col1), at their absolute coordinates in the width x height frame, and stores `dst` in `format` (`raw` != 0: RGBA32F
+// with no display transform, the plane the next HDR node reads). p0, p5, p8, p9: the projection's entries [0], [5], [8], [9]; m0, m1, m2:
+// the first three columns of the camera transform. L, E0 and the desc's fields are the host's (step 0): all of it is wave-uniform.
+struct FogArgs {
+    const float4* color; const void* depth; void* dst;
+    uint32_t width, height, row0, row1, col0, col1, frame, format, raw;
+    uint32_t falloff, sky, height_on /* b != 0 */, lobe_on /* light_color is not all 0 */;
+    float p0, p5, p8, p9, m0[3], m1[3], m2[3];
+    float L[3], E0, b, a /* color[3] */, rgb[3], light_color[3], light_exponent;
+    float start, end, density, sky_distance, extinction[3], inscattering[3];
+    DisplayArgs display;
+};
+
 // Everything a per-pixel kernel can touch, passed by value as the kernel argument (scalar loads).
 struct KArgs {
     GpuCamera cam, prev_cam;
