@@ -848,7 +848,8 @@ int st_dof_process(StEngine* e, const StDofDesc* desc, const StDisplayDesc* disp
  * is part of the PBR fragment shader, which this engine replaces, so it has to be served here: it needs the primary hit's distance and the
  * pixel's world-space ray. It is the first node of the output chain: scene-referred radiance along the primary ray, in front of the lens
  * (depth of field), the shutter (motion blur) and the glare (bloom). A participating medium seen from the camera only.
- * - Order: rendering -> fog -> depth of field -> motion blur -> bloom -> display transform -> FXAA -> resample -> output format.
+ * - Order: rendering -> fog -> (light shafts, below) -> depth of field -> motion blur -> bloom -> display transform -> FXAA -> resample ->
+ *   output format.
  * - Scope: the setting belongs to the camera and takes effect at its next st_render_camera. It changes only what is written to
  *   `out_device`: AOVs, picks, scene queries, the HDR history, every plane st_camera_read_buffer returns and the auto-exposure metering are
  *   unchanged. desc == NULL turns it off: the frame then launches the kernels it launches without the setting, with the same arguments, and
@@ -906,7 +907,7 @@ int st_dof_process(StEngine* e, const StDofDesc* desc, const StDisplayDesc* disp
  *   With both, no finite input produces NaN (a non-finite entry of P or M is cleaned by the NaN rule of min and max: s = 0, k = -80).
  * - Known limits: the ray's origin is taken as the camera position M[12..14], while the renderer's rays start on the near plane, so D is
  *   short by the near distance along the ray; the auto-exposure metering stays in the composing launch, in front of the fog, so it meters
- *   the unfogged frame; the medium is seen from the camera only: it neither shadows the glow (no light shafts) nor attenuates the light
+ *   the unfogged frame; the medium is seen from the camera only: it neither shadows the glow (shadowed in-scattering is the next node's, "light shafts") nor attenuates the light
  *   that reaches surfaces or GI paths.
  * - Errors: ST_ERR_INVALID_ARGUMENT for a wrong struct_size, an unknown falloff or flag bit, a field outside its stated range (NaN
  *   included; only the fields the falloff and the flags name are looked at: start and end with LINEAR, density with the two exponentials,
@@ -943,6 +944,92 @@ int st_camera_get_fog(StEngine* e, StHandle camera, StFogDesc* out, int* enabled
 int st_fog_process(StEngine* e, const StFogDesc* desc, const StDisplayDesc* display, const float transform[16], const float projection[16],
                    const void* color_device, const void* depth_device, uint32_t width, uint32_t height, void* dst_device,
                    int dst_format /* StOutputFormat */, void* hip_stream);
+
+/* ---- light shafts (NEW seam): shadowed single in-scattering marched through the BVH, between fog and depth of field (st_shafts.cpp,
+ * k_shafts.hip). Fog attenuates what lies behind the medium; this node adds the light the medium scatters towards the camera in front of
+ * the surface, with one shadow ray per sample and light, so occluders cut shafts into it. The caller names the lights by handle.
+ * - Order: rendering -> fog -> light shafts -> depth of field -> motion blur -> bloom -> display transform -> FXAA -> resample -> format.
+ * - Scope: as fog's. The setting belongs to the camera, takes effect at its next st_render_camera, survives st_camera_update and
+ *   st_engine_set_arithmetic, and changes only what is written to `out_device` (and st_camera_ray_count, which grows by the march's shadow
+ *   rays). desc == NULL turns it off: the frame then launches the kernels it launches without the setting, with the same arguments.
+ *   Frames that skip it are fog's: ST_MODE_REFERENCE, ST_MODE_BVH_HEATMAP and non-perspective projections. While a frame carries shafts,
+ *   the node in front (fog, else the composing launch) writes a camera-owned render-size RGBA32F plane; two launches (ST_PASS_POST) behind
+ *   it, the march into a camera-owned cell plane and the apply launch, write the next node's plane or what the composing launch would have.
+ * - Windows: the apply launch reads neighbouring cells, so the node is excluded together with a window exactly as depth of field is
+ *   (st_camera_set_window, st_dist_set_partition, st_dist_set_grid refuse, as does the setter on a windowed camera). A tiled frame carries
+ *   no shafts: st_light_shafts_process over the gathered planes needs the whole scene on rank 0, which is a limit.
+ * - Lights: `lights[0 .. light_count)` are StHandles of st_light_insert. A handle that names no light in the light table of the last
+ *   st_tick is skipped and is not an error (a light removed between frames drops out at the tick that removes it). The sun is not a
+ *   table light here: sun_color (all 0 = no sun) arrives from direction L and is shadowed by a ray of unbounded length.
+ * - Arithmetic: fog's discipline. This node's own arithmetic is float32, left to right, no fused multiply-add, division and square root
+ *   correctly rounded, in BOTH builds; min, max, clamp01 with the post-processing section's NaN rule; exp(x) = exp2p(x 1.44269504088896341)
+ *   with fog's exp2p; acos is glam's acos_approx: x = |v|; r = ((((((-0.0012624911 x + 0.0066700901) x - 0.0170881256) x + 0.0308918810) x
+ *   - 0.0501743046) x + 0.0889789874) x - 0.2145988016) x + 1.5707963050; r = r sqrt(max(1 - x, 0)); v >= 0 ? r : 3.14159265358979 - r.
+ *   tests/shafts_ref.py restates all of it in numpy and both builds match it bit for bit GIVEN the visibility bits. A visibility bit V of
+ *   the StRay {origin, t_max, direction} is by definition 1 - (what st_scene_occluded answers for that ray), so alpha-tested materials
+ *   and the t_max <= 0 / zero-direction contract behave as they do there; the fast build's walk is its own st_scene_occluded's.
+ *   C, D, P, M as in fog. o = M[12..14].
+ * - 0. Host constants, in double, each rounded to float once: g = anisotropy; k1 = (1 - g g) / (4 pi); k2 = 1 + g g; k3 = 2 g.
+ *   L = sun_direction normalised as fog normalises its light direction; with ST_SHAFTS_FOLLOW_SUN the engine's sun direction of the last
+ *   st_tick. st_light_shafts_plan returns the cell grid, ceil(W / divisor) x ceil(H / divisor), and the jitter table
+ *   j[cy & 3][cx & 3] = (B + 0.5) / 16 with the 4 x 4 Bayer matrix B = {0 8 2 10 / 12 4 14 6 / 3 11 1 9 / 15 7 13 5}: frame-independent.
+ * - 1. Cell (cx, cy): the pixels [cx divisor, (cx + 1) divisor) x [cy divisor, (cy + 1) divisor) inside the frame. Its depth d_c: over the
+ *   block's pixels with D > 0 (sky counts, as FLT_MAX), the minimum where cx + cy is even and the maximum where it is odd (divisor 1: the
+ *   pixel's D). A block without such a pixel is empty: the cell is (0, 0, 0, 0). Its ray goes through the block's nominal centre,
+ *   (cx divisor + 0.5 divisor, cy divisor + 0.5 divisor) in pixels, with fog's step 1 (w is not renormalised).
+ * - 2. March: d_end = min(d_c, max_distance); delta = d_end / steps; for k = 0 .. steps - 1: t = (k + j) delta; p = o + w t per component;
+ *   A = 0; the sun, then the lights in the desc's order, add E phase to A where the sample sees them; m = (exp(-(density t)) delta) density;
+ *   S = S + (m scatter) A per channel. phase(c) = k1 / (q sqrt(q)), q = k2 - k3 c, c = min(max((w.x l.x + w.y l.y) + w.z l.z, -1), 1).
+ *   Sun: l = L, E = sun_color, ray {p, FLT_MAX, L}. Light: v = centre - p; l2 = (v.x v.x + v.y v.y) + v.z v.z; len = sqrt(l2); a sample
+ *   with len not > radius contributes nothing; l = v / len; f_angle = 1 for a point light, else clamp01(1 - (r r) r) with
+ *   r = acos(((n.x u.x + n.y u.y) + n.z u.z) / sqrt(n2 l2)) / angle, u = -v, n the light's octahedral direction decoded as the renderer
+ *   decodes it but not normalised (the quotient takes the length out), n2 its squared length; f_dist = 1 for an infinite range, else
+ *   (sm sm) / max(l2, 1e-4), sm = clamp01(1 - f f), f = l2 (1 / (range range)); fe = f_angle f_dist, times exp(-(density len)) with
+ *   ST_SHAFTS_LIGHT_EXTINCTION; E phase = (colour fe) phase per channel; ray {p, len - radius, l}. No cosine and no BRDF: the medium
+ *   is isotropic but for the phase function. NO SHADOW RAY IS CAST where E phase is 0 in all three channels (out of range, outside the
+ *   cone, a black light, a sample inside the light): the ray count is part of this specification.
+ *   The cell is (min(max(S, 0), FLT_MAX) per channel, d_c).
+ * - 3. Apply, per pixel: a D that is not > 0 passes the pixel's own four words through. Divisor 1: S_p is the cell's S. Divisor 2:
+ *   u = ((x + 0.5) 0.5 - 0.5, (y + 0.5) 0.5 - 0.5); the four cells around u, clamped to the grid, in the order (0,0) (1,0) (0,1) (1,1);
+ *   d_p = min(D, max_distance); weight = bilinear (1 / (0.001 + |min(d_i, max_distance) - d_p| / d_p)); empty cells are skipped;
+ *   S_p = (sum of weight S_i) / (sum of weights), or 0 when that sum is not > 0. If intensity S_p is 0 in all three channels the pixel
+ *   passes through; otherwise out.rgb = min(min(max(C, 0), 65504) + intensity S_p, FLT_MAX) with the pixel's own alpha.
+ * - Deviations from the first statement, found ill-defined while building it: (1) S is held in [0, FLT_MAX] when the cell is stored (an
+ *   overflowed S times a zero weight is NaN; the NaN rule of max also cleans a NaN from lights of opposite signs); (2) d_p is clamped to
+ *   max_distance like d_i, or a sky pixel would weigh every cell 0; (3) the arccosine is restated with the correctly rounded square root,
+ *   because the renderer's own goes to the hardware's in the fast build. With these no finite input produces NaN.
+ * - Known limits: single scattering in a homogeneous medium; the light reaching a sample is attenuated by the medium only with
+ *   ST_SHAFTS_LIGHT_EXTINCTION and never for the sun; the ray's origin is M[12..14] as in fog; stratified samples with an ordered 4 x 4
+ *   jitter and no temporal filter: banding shows below about 8 steps; tiled frames carry no shafts (above).
+ * - Errors: ST_ERR_INVALID_ARGUMENT for a wrong struct_size, an unknown flag bit, a field outside its stated range (NaN included;
+ *   sun_direction is looked at only when sun_color is not all 0 and ST_SHAFTS_FOLLOW_SUN is not set), null pointers where they are not
+ *   allowed, a side of 0 or above 16384, an auto-exposure display or a non-perspective projection given to the process call, a window
+ *   (above); st_light_shafts_process before the first st_tick. An unknown camera is ST_ERR_UNKNOWN_CAMERA. Set, get and plan are host
+ *   work and valid on a host-only engine; st_light_shafts_process returns ST_ERR_NO_DEVICE there. */
+enum { ST_SHAFTS_FOLLOW_SUN = 1, ST_SHAFTS_LIGHT_EXTINCTION = 2 };
+enum { ST_SHAFTS_MAX_LIGHTS = 8 };
+typedef struct StLightShaftsDesc {         /* 144 B */
+    uint32_t struct_size, flags, steps, divisor;   /* sizeof(StLightShaftsDesc), ST_SHAFTS_*, 1..64 samples per ray, 1 or 2 pixels per cell side */
+    float density;                         /* extinction per metre, finite, >= 0 */
+    float anisotropy;                      /* Henyey-Greenstein g in [-0.95, 0.95]; 0 = isotropic, > 0 = forward */
+    float max_distance;                    /* the march ends there, finite, > 0 */
+    float intensity;                       /* finite, >= 0 */
+    float scatter[3]; float _pad;          /* single-scattering albedo per channel in [0, 1]; ignored */
+    float sun_color[3]; float _pad2;       /* finite, >= 0; all 0 = no sun; ignored */
+    float sun_direction[3];                /* towards the sun, any non-zero length; ignored with ST_SHAFTS_FOLLOW_SUN */
+    uint32_t light_count;                  /* <= 8 */
+    StHandle lights[8];
+} StLightShaftsDesc;
+int st_camera_set_light_shafts(StEngine* e, StHandle camera, const StLightShaftsDesc* desc);   /* NULL = off */
+/* the last desc set (a zeroed desc with struct_size when none was) and whether the node is on; either pointer may be NULL */
+int st_camera_get_light_shafts(StEngine* e, StHandle camera, StLightShaftsDesc* out, int* enabled);
+/* host only: the cell grid and the jitter table (row cy & 3, column cx & 3) of step 0; either pointer may be NULL */
+int st_light_shafts_plan(const StLightShaftsDesc* desc, uint32_t width, uint32_t height, uint32_t cells_wh[2], float jitter[16]);
+/* Like st_fog_process, but it reads the engine's live scene copy and light table: it needs a preceding st_tick, counts as a reader of
+ * that copy as st_scene_occluded does, and takes ST_SHAFTS_FOLLOW_SUN. The cell plane is engine-owned scratch, grown, never shrunk. */
+int st_light_shafts_process(StEngine* e, const StLightShaftsDesc* desc, const StDisplayDesc* display, const float transform[16],
+                            const float projection[16], const void* color_device, const void* depth_device, uint32_t width, uint32_t height,
+                            void* dst_device, int dst_format /* StOutputFormat */, void* hip_stream);
 
 /* ---- multi-GPU behind the boundary (NEW seam; SURVEY.md section 8e, BASELINE.json configs 4 and 5). One process per GPU, one
  * engine per process, the scene replicated; the frame is cut into tiles, every rank renders its tile (+ an apron of redundant

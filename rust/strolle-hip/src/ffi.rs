@@ -386,6 +386,36 @@ extern "C" {
     pub fn st_fog_process(e: *mut StEngine, desc: *const StFogDesc, display: *const StDisplayDesc, transform: *const f32, projection: *const f32, color_device: *const c_void, depth_device: *const c_void, width: u32, height: u32, dst_device: *mut c_void, dst_format: i32, hip_stream: *mut c_void) -> i32;
 }
 
+// light shafts (include/strolle_hip.h "light shafts"): shadowed in-scattering between fog and depth of field
+pub const ST_SHAFTS_FOLLOW_SUN: u32 = 1;
+pub const ST_SHAFTS_LIGHT_EXTINCTION: u32 = 2;
+pub const ST_SHAFTS_MAX_LIGHTS: usize = 8;
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct StLightShaftsDesc {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub steps: u32,
+    pub divisor: u32,
+    pub density: f32,
+    pub anisotropy: f32,
+    pub max_distance: f32,
+    pub intensity: f32,
+    pub scatter: [f32; 3],
+    pub _pad: f32,
+    pub sun_color: [f32; 3],
+    pub _pad2: f32,
+    pub sun_direction: [f32; 3],
+    pub light_count: u32,
+    pub lights: [u64; 8],
+}
+extern "C" {
+    pub fn st_camera_set_light_shafts(e: *mut StEngine, camera: u64, desc: *const StLightShaftsDesc) -> i32; // null = off
+    pub fn st_camera_get_light_shafts(e: *mut StEngine, camera: u64, out: *mut StLightShaftsDesc, enabled: *mut i32) -> i32;
+    pub fn st_light_shafts_plan(desc: *const StLightShaftsDesc, width: u32, height: u32, cells_wh: *mut u32, jitter: *mut f32) -> i32; // pure host
+    pub fn st_light_shafts_process(e: *mut StEngine, desc: *const StLightShaftsDesc, display: *const StDisplayDesc, transform: *const f32, projection: *const f32, color_device: *const c_void, depth_device: *const c_void, width: u32, height: u32, dst_device: *mut c_void, dst_format: i32, hip_stream: *mut c_void) -> i32;
+}
+
 // ---- the HIP runtime, as far as the staging-copy present needs it (libamdhip64)
 pub type hipStream_t = *mut c_void;
 extern "C" {

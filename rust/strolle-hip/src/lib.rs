@@ -267,6 +267,24 @@ where
         slot.camera = camera;
     }
 
+    /// Not part of the reference's API: light shafts on a camera (include/strolle_hip.h "light shafts"). `desc`'s own `lights` and
+    /// `light_count` are replaced by `lights` (at most 8), named by the handles they were inserted with; `None` turns the node off.
+    pub fn set_light_shafts(&mut self, handle: CameraHandle, desc: Option<ffi::StLightShaftsDesc>, lights: &[P::LightHandle]) {
+        let raw = self.cameras.get(&handle).unwrap_or_else(|| panic!("camera does not exist: {:?}", handle)).raw;
+        match desc {
+            None => check(unsafe { ffi::st_camera_set_light_shafts(self.raw, raw, std::ptr::null()) }),
+            Some(mut d) => {
+                d.struct_size = std::mem::size_of::<ffi::StLightShaftsDesc>() as u32;
+                d.lights = [0; ffi::ST_SHAFTS_MAX_LIGHTS];
+                d.light_count = lights.len().min(ffi::ST_SHAFTS_MAX_LIGHTS) as u32;
+                for (slot, light) in d.lights.iter_mut().zip(lights.iter()) {
+                    *slot = self.lights.id(*light);
+                }
+                check(unsafe { ffi::st_camera_set_light_shafts(self.raw, raw, &d) });
+            }
+        }
+    }
+
     /// Renders camera to texture: records the pass that puts the frame `tick` rendered into `view` (present.rs).
     pub fn render_camera(&self, handle: CameraHandle, encoder: &mut wgpu::CommandEncoder, view: &wgpu::TextureView) {
         let slot = self.cameras.get(&handle).unwrap_or_else(|| panic!("camera does not exist: {:?}", handle));

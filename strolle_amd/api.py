@@ -263,6 +263,45 @@ def fog_desc(falloff=FogFalloff.EXPONENTIAL, color=(1.0, 1.0, 1.0, 1.0), start: 
                      f3(*[float(v) for v in light_direction]), 0.0)
 
 
+class StLightShaftsDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("steps", C.c_uint32), ("divisor", C.c_uint32),
+                ("density", C.c_float), ("anisotropy", C.c_float), ("max_distance", C.c_float), ("intensity", C.c_float),
+                ("scatter", C.c_float * 3), ("_pad", C.c_float), ("sun_color", C.c_float * 3), ("_pad2", C.c_float),
+                ("sun_direction", C.c_float * 3), ("light_count", C.c_uint32), ("lights", C.c_uint64 * 8)]
+
+
+SHAFTS_FOLLOW_SUN, SHAFTS_LIGHT_EXTINCTION, SHAFTS_MAX_LIGHTS = 1, 2, 8
+
+
+def light_shafts_desc(steps: int = 16, divisor: int = 2, density: float = 0.05, anisotropy: float = 0.0, max_distance: float = 100.0, intensity: float = 1.0,
+                      scatter=(1.0, 1.0, 1.0), sun_color=(0.0, 0.0, 0.0), sun_direction=(0.0, 1.0, 0.0), lights=(), follow_sun: bool = False,
+                      light_extinction: bool = False) -> StLightShaftsDesc:
+    """A StLightShaftsDesc (include/strolle_hip.h "light shafts"). steps: samples per ray (1..64); divisor: pixels per cell side (1 or 2);
+    density: extinction per metre; anisotropy: Henyey-Greenstein g; scatter: single-scattering albedo; sun_color all 0 = no sun;
+    follow_sun: the sun's direction is the engine's instead of sun_direction; lights: up to 8 light handles; light_extinction: the medium
+    also attenuates the light on its way from a light to the sample."""
+    handles = [int(h) for h in lights]
+    flags = (SHAFTS_FOLLOW_SUN if follow_sun else 0) | (SHAFTS_LIGHT_EXTINCTION if light_extinction else 0)
+    f3 = C.c_float * 3
+    return StLightShaftsDesc(C.sizeof(StLightShaftsDesc), flags, int(steps), int(divisor), float(density), float(anisotropy), float(max_distance), float(intensity),
+                             f3(*[float(v) for v in scatter]), 0.0, f3(*[float(v) for v in sun_color]), 0.0, f3(*[float(v) for v in sun_direction]),
+                             len(handles), (C.c_uint64 * 8)(*(handles[:8] + [0] * (8 - min(len(handles), 8)))))
+
+
+def light_shafts_plan(desc: StLightShaftsDesc, width: int, height: int):
+    """st_light_shafts_plan: ((cells_w, cells_h), the 4 x 4 jitter table, row cy & 3, column cx & 3)."""
+    import numpy as np
+    lib = load_library()
+    lib.st_light_shafts_plan.restype = C.c_int
+    lib.st_light_shafts_plan.argtypes = [C.POINTER(StLightShaftsDesc), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+    cells, jitter = (C.c_uint32 * 2)(), (C.c_float * 16)()
+    rc = lib.st_light_shafts_plan(C.byref(desc), width, height, cells, jitter)
+    if rc != 0:
+        lib.st_last_error.restype = C.c_char_p
+        raise StrolleError(f"{_STATUS.get(rc, 'error')} (status {rc}): {lib.st_last_error().decode(errors='replace')}")
+    return (cells[0], cells[1]), np.array(jitter, np.float32).reshape(4, 4).copy()
+
+
 class StBloomDesc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("levels", C.c_uint32), ("intensity", C.c_float),
                 ("low_frequency_boost", C.c_float), ("low_frequency_boost_curvature", C.c_float), ("high_pass_frequency", C.c_float),
@@ -616,6 +655,10 @@ class _Binding:
             self.camera_set_fog = fn("camera_set_fog", [vp, u64, P(StFogDesc)])
             self.camera_get_fog = fn("camera_get_fog", [vp, u64, P(StFogDesc), P(i32)])
             self.fog_process = fn("fog_process", [vp, P(StFogDesc), P(StDisplayDesc), P(C.c_float), P(C.c_float), vp, vp, u32, u32, vp, i32, vp])
+        if hasattr(lib, prefix + "camera_set_light_shafts"):   # light shafts (likewise)
+            self.camera_set_light_shafts = fn("camera_set_light_shafts", [vp, u64, P(StLightShaftsDesc)])
+            self.camera_get_light_shafts = fn("camera_get_light_shafts", [vp, u64, P(StLightShaftsDesc), P(i32)])
+            self.light_shafts_process = fn("light_shafts_process", [vp, P(StLightShaftsDesc), P(StDisplayDesc), P(C.c_float), P(C.c_float), vp, vp, u32, u32, vp, i32, vp])
         if hasattr(lib, prefix + "mesh_set_skin"):
             self.mesh_set_skin = fn("mesh_set_skin", [vp, u64, vp, sz, u32])
         if hasattr(lib, prefix + "mesh_set_morph_targets"):   # morph targets (likewise absent from an older library)
@@ -1207,6 +1250,27 @@ class Engine(EngineBase):
         xf, proj = (C.c_float * 16)(*[float(v) for v in transform]), (C.c_float * 16)(*[float(v) for v in projection])
         self._check(self._b.fog_process(self._h, C.byref(desc), C.byref(display) if display is not None else None, xf, proj, color_ptr, depth_ptr, width, height,
                                         dst_ptr, int(dst_format), stream))
+
+    # ---- light shafts (include/strolle_hip.h "light shafts"): takes effect at the camera's next render
+    def set_light_shafts(self, camera: int, desc: Optional[StLightShaftsDesc] = None, **kw):
+        """st_camera_set_light_shafts: a StLightShaftsDesc, or light_shafts_desc(**kw) when keywords are given; neither = off."""
+        if desc is None and kw:
+            desc = light_shafts_desc(**kw)
+        self._check(self._b.camera_set_light_shafts(self._h, camera, C.byref(desc) if desc is not None else None))
+
+    def get_light_shafts(self, camera: int):
+        """st_camera_get_light_shafts: (the last StLightShaftsDesc set, whether the node is on)."""
+        d, on = StLightShaftsDesc(), C.c_int()
+        self._check(self._b.camera_get_light_shafts(self._h, camera, C.byref(d), C.byref(on)))
+        return d, bool(on.value)
+
+    def light_shafts_process(self, desc: StLightShaftsDesc, transform, projection, color_ptr: int, depth_ptr: int, width: int, height: int, dst_ptr: int,
+                             dst_format: int = 0, display: Optional[StDisplayDesc] = None, stream: int = 0):
+        """st_light_shafts_process: shafts through the engine's live scene (after a tick) over any RGBA32F colour and f32 depth device planes
+        rendered with `transform` and `projection` (16 floats each, column major), then the (manual) display transform, into dst."""
+        xf, proj = (C.c_float * 16)(*[float(v) for v in transform]), (C.c_float * 16)(*[float(v) for v in projection])
+        self._check(self._b.light_shafts_process(self._h, C.byref(desc), C.byref(display) if display is not None else None, xf, proj, color_ptr, depth_ptr,
+                                                 width, height, dst_ptr, int(dst_format), stream))
 
     # ---- environment lighting (include/strolle_hip.h "environment lighting"): takes effect at the next tick
     def set_environment(self, texels, intensity: float = 1.0, yaw: float = 0.0, keep_sun: bool = False, uniform: bool = False):

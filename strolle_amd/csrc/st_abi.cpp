@@ -275,6 +275,7 @@ int st_camera_set_window(StEngine* e, StHandle h, uint32_t x0, uint32_t y0, uint
     ST_REQUIRE(full || !s.bloom_on, "a window on a camera with bloom: the pyramid reads far across tile edges (include/strolle_hip.h \"bloom\")");
     ST_REQUIRE(full || !s.mblur_on, "a window on a camera with motion blur: the gather reads up to 32 pixels across tile edges (include/strolle_hip.h \"motion blur\")");
     ST_REQUIRE(full || !s.dof_on, "a window on a camera with depth of field: the gather reads up to 32 pixels across tile edges (include/strolle_hip.h \"depth of field\")");
+    ST_REQUIRE(full || !s.shafts_on, "a window on a camera with light shafts: the apply launch reads neighbouring cells across tile edges (include/strolle_hip.h \"light shafts\")");
     s.row0 = y0; s.row1 = y1; s.col0 = x0; s.col1 = x1;
     return ST_OK;
 }
@@ -452,6 +453,36 @@ int st_fog_process(StEngine* e, const StFogDesc* desc, const StDisplayDesc* disp
                    uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
     ST_REQUIRE(e, "null engine");
     return E(e)->fog_process(desc, display, transform, projection, color, depth, width, height, dst, dst_format, static_cast<hipStream_t>(stream));
+}
+
+// ---- light shafts (st_shafts.cpp)
+int st_camera_set_light_shafts(StEngine* e, StHandle h, const StLightShaftsDesc* desc) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    return E(e)->set_shafts(*it->second, desc);
+}
+int st_camera_get_light_shafts(StEngine* e, StHandle h, StLightShaftsDesc* out, int* enabled) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    const CameraState& s = *it->second;
+    if (out) { *out = s.shafts; out->struct_size = sizeof(StLightShaftsDesc); }
+    if (enabled) *enabled = s.shafts_on ? 1 : 0;
+    return ST_OK;
+}
+int st_light_shafts_plan(const StLightShaftsDesc* desc, uint32_t width, uint32_t height, uint32_t cells_wh[2], float jitter[16]) {
+    ST_REQUIRE(desc, "null desc");
+    Engine::ShaftsPlan plan;
+    if (int rc = Engine::shafts_plan(*desc, width, height, plan)) return rc;
+    if (cells_wh) { cells_wh[0] = plan.cells_w; cells_wh[1] = plan.cells_h; }
+    if (jitter) for (int i = 0; i < 16; i++) jitter[i] = plan.jitter[i];
+    return ST_OK;
+}
+int st_light_shafts_process(StEngine* e, const StLightShaftsDesc* desc, const StDisplayDesc* display, const float transform[16], const float projection[16], const void* color,
+                            const void* depth, uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
+    ST_REQUIRE(e, "null engine");
+    return E(e)->shafts_process(desc, display, transform, projection, color, depth, width, height, dst, dst_format, static_cast<hipStream_t>(stream));
 }
 
 int st_debug_set_bloom_tail(StEngine* e, int lds_bytes, uint32_t* in_force) {

@@ -10,6 +10,7 @@
 //   st_motion_blur.cpp  motion blur: the plan, its three launches
 //   st_dof.cpp          depth of field: the plan (host constants, tap table), its three launches
 //   st_fog.cpp          fog: the checks, the host constants, its one launch
+//   st_shafts.cpp       light shafts: the checks, the plan, the host constants, its two launches
 //   st_deform.cpp       mesh deformation (st_deform.h): skinned meshes, morph targets, deformation motion; the tick's launches
 //   st_env.cpp          environment lighting: the map, its importance table
 //   st_query.cpp        scene queries: closest hit, occlusion, picks
@@ -425,6 +426,14 @@ struct CameraState {
     FencedPlanes<1> fog_planes;   // [0] the HDR plane
     Fence fog_depth_read[2];
     bool fogs() const { return fog_on && desc.mode != ST_MODE_BVH_HEATMAP && desc.mode != ST_MODE_REFERENCE && dof_perspective(desc.projection); }
+    // Light shafts (st_shafts.cpp; include/strolle_hip.h "light shafts"), between fog and depth of field; the setting survives st_camera_update
+    // like the rest. While a frame carries shafts, the node in front of it (fog, else the composing launch) writes the HDR plane; the march writes
+    // the cell plane from this frame's G-buffer depth and the live scene copy, and the apply launch behind it writes where the node in front
+    // would have (or the HDR plane of the next node that is on). Both read the G-buffer of the frame's parity: they share fog's fence
+    // (fog_depth_read, recorded behind the last of the three launches). The apply launch reads neighbouring cells: a window excludes the node.
+    StLightShaftsDesc shafts{}; bool shafts_on = false;
+    FencedPlanes<2> shafts_planes;   // [0] the HDR plane, [1] the cell plane (S.rgb, d_c)
+    bool shafted() const { return shafts_on && desc.mode != ST_MODE_BVH_HEATMAP && desc.mode != ST_MODE_REFERENCE && dof_perspective(desc.projection); }
     uint32_t out_width() const { return post_on && post.output_width != 0u ? post.output_width : desc.width; }
     uint32_t out_height() const { return post_on && post.output_width != 0u ? post.output_height : desc.height; }
     // A present copy still in flight writes the caller's host memory: it lands before the stream goes. Everything else goes with its member —
@@ -569,6 +578,7 @@ struct Engine {
     std::vector<int64_t> lights_created, lights_updated; std::map<int64_t, uint32_t> lights_remapped; std::vector<uint32_t> lights_killed;
     uint32_t next_light_id = 1;
     std::vector<GpuLight> gpu_lights, uploaded_lights;
+    std::map<int64_t, uint32_t> light_slot_uploaded;   // light_slot as gpu_lights was snapshot (snapshot_lights): which slot of the device's table a handle has
     bool sync_every_tick = false;
     float sun_azimuth = 0.0f, sun_altitude = 0.35f; bool sun_dirty = true;
     uint32_t light_count = 0; V3 sun_dir_ = v3s(0.0f);
@@ -834,6 +844,17 @@ struct Engine {
     int set_fog(CameraState& c, const StFogDesc* desc);
     int fog_process(const StFogDesc* desc, const StDisplayDesc* display, const float* transform, const float* projection, const void* color, const void* depth,
                     uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
+    // ---- light shafts (st_shafts.cpp)
+    struct ShaftsPlan { uint32_t cells_w = 0, cells_h = 0; size_t cell_bytes = 0; float jitter[16] = {}; };
+    struct ShaftsSteps { ShaftsArgs args; struct { int slot; double bytes; } step[2]; };   // march, apply
+    static int shafts_plan(const StLightShaftsDesc& d, uint32_t w, uint32_t h, ShaftsPlan& out);
+    void shafts_steps(const StLightShaftsDesc& d, const ShaftsPlan& plan, const float transform[16], const float projection[16], const float sun[3], const void* color, const void* depth,
+                      bool frame, uint32_t w, uint32_t h, float4* cells, void* dst, uint32_t format, bool raw, const DisplayArgs& display, bool count, ShaftsSteps& out) const;
+    void launch_shafts_step(const KArgs& scene, const ShaftsSteps& s, uint32_t i, hipStream_t stream);
+    int set_shafts(CameraState& c, const StLightShaftsDesc* desc);
+    int shafts_process(const StLightShaftsDesc* desc, const StDisplayDesc* display, const float* transform, const float* projection, const void* color, const void* depth,
+                       uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
+    FencedPlanes<1> shafts_scratch;   // st_light_shafts_process's cell plane: grown, never shrunk
     int scene_args(KArgs& a, bool heatmap) const;   // the scene half of KArgs (st_render.cpp): render() and the scene queries
     void light_args(KArgs& a) const;                // its lights, LUT and environment half: render()
 

@@ -44,6 +44,7 @@ enum KernelSlot {
     KS_MBLUR_PACK, KS_MBLUR_NEIGHBOUR, KS_MBLUR_GATHER,  // motion blur in front of bloom (k_motion_blur.hip); render() credits their bytes itself
     KS_DOF_PACK, KS_DOF_NEIGHBOUR, KS_DOF_GATHER,  // depth of field in front of motion blur (k_dof.hip); render() credits their bytes itself
     KS_FOG,  // fog in front of depth of field (k_fog.hip); render() credits its bytes itself
+    KS_SHAFTS_MARCH, KS_SHAFTS_APPLY,  // light shafts between fog and depth of field (k_shafts.hip); render() credits their bytes itself
     KS_COUNT
 };
 struct KernelInfo { const char* name; float bytes_per_unit; bool half; };
@@ -78,6 +79,7 @@ inline const KernelInfo& kernel_info(int slot) {
         {"motion_blur_pack", 0.f, false},    {"motion_blur_neighbour", 0.f, false}, {"motion_blur_gather", 0.f, false},
         {"dof_pack", 0.f, false},            {"dof_neighbour", 0.f, false},        {"dof_gather", 0.f, false},
         {"fog", 0.f, false},
+        {"shafts_march", 0.f, false},        {"shafts_apply", 0.f, false},
     };
     return k[slot];
 }

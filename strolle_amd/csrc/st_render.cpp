@@ -171,13 +171,13 @@ namespace {
 // (st_motion_blur.cpp) sits in front of bloom in the same way: the composing launch writes the blur's HDR plane, and the gather writes bloom's
 // HDR plane (untransformed) or, without bloom, what the composing launch would have written. Depth of field (st_dof.cpp) sits in front of
 // motion blur: the composing launch writes its HDR plane, and its gather writes the HDR plane of the next node that is on (motion blur's, else
-// bloom's), or what the composing launch would have written. Fog (st_fog.cpp) is the first node, in front of depth of field. The four HDR
-// nodes form an ordered list: the composing launch writes the plane of the first node that is on, and each node writes the plane of the next
+// bloom's), or what the composing launch would have written. Fog (st_fog.cpp) is the first node, light shafts (st_shafts.cpp) the second, in
+// front of depth of field. The five HDR nodes form an ordered list: the composing launch writes the plane of the first node that is on, and each node writes the plane of the next
 // one that is on (`node_dst`), the last one what the composing launch would have written.
-enum HdrNode { kNodeFog, kNodeDof, kNodeMBlur, kNodeBloom, kHdrNodes };
+enum HdrNode { kNodeFog, kNodeShafts, kNodeDof, kNodeMBlur, kNodeBloom, kHdrNodes };
 struct OutputRoute {
-    bool post_fxaa = false, post = false, bloom = false, mblur = false, dof = false, fog = false;
-    Engine::BloomPlan bloom_plan; Engine::MBlurPlan mblur_plan; Engine::DofPlan dof_plan;
+    bool post_fxaa = false, post = false, bloom = false, mblur = false, dof = false, fog = false, shafts = false;
+    Engine::BloomPlan bloom_plan; Engine::MBlurPlan mblur_plan; Engine::DofPlan dof_plan; Engine::ShaftsPlan shafts_plan;
     void* hdr_plane[kHdrNodes] = {};   // the render-size RGBA32F plane each node that is on reads, in chain order
     // where node `n` writes (n = -1: the composing launch): the next node's plane, raw (RGBA32F, untransformed), or the frame's target
     void* node_dst(int n, bool* raw) const {
@@ -197,7 +197,7 @@ struct FrameSwitches {
 // visibility and the GI chain to the camera's side stream); the rest below `s` is launch bookkeeping.
 struct Frame {
     Engine& e; CameraState& c; void* const out; const hipStream_t stream; hipStream_t cur;
-    KArgs a{}; OutputRoute route; FrameSwitches s{}; Engine::MBlurSteps blur{}; Engine::DofSteps dof{}; Engine::FogStep fog{};
+    KArgs a{}; OutputRoute route; FrameSwitches s{}; Engine::MBlurSteps blur{}; Engine::DofSteps dof{}; Engine::FogStep fog{}; Engine::ShaftsSteps shafts{};
     const uint32_t mode, pseed;   // pseed: one seed for both preview passes (passes/gi_preview_resampling.rs:60-74)
     bool mask_split = false, di_reprojected = false, gi_reprojected = false, composed = false, luts_generated_now = false; uint32_t launch_ordinal = 0u;
     Frame(Engine& e_, CameraState& c_, void* out_, hipStream_t s_) : e(e_), c(c_), out(out_), stream(s_), cur(s_), mode(c_.desc.mode), pseed(pass_seed(e_.base_seed, c_.frame, SEED_GI_PREVIEW)) {}
@@ -259,7 +259,13 @@ struct Frame {
             r.fog = true;
             if (int rc = c.fog_planes.acquire({plane}, c.fog_planes.Grow, stream)) return rc;
         }
+        if (out && c.shafted()) {
+            if (int rc = Engine::shafts_plan(c.shafts, c.desc.width, c.desc.height, r.shafts_plan)) return rc;
+            r.shafts = true;
+            if (int rc = c.shafts_planes.acquire({plane, r.shafts_plan.cell_bytes}, c.shafts_planes.Grow, stream)) return rc;
+        }
         if (r.fog) r.hdr_plane[kNodeFog] = c.fog_planes.plane[0].ptr;
+        if (r.shafts) r.hdr_plane[kNodeShafts] = c.shafts_planes.plane[0].ptr;
         if (r.dof) r.hdr_plane[kNodeDof] = c.dof_planes.plane[0].ptr;
         if (r.mblur) r.hdr_plane[kNodeMBlur] = c.mblur_planes.plane[0].ptr;
         if (r.bloom) r.hdr_plane[kNodeBloom] = c.bloom_planes.plane[0].ptr;
@@ -373,6 +379,12 @@ struct Frame {
             Engine::fog_step(c.fog, c.desc.transform, c.desc.projection, sun, c.fog_planes.plane[0].ptr, a.g0, true, c.desc.width, c.desc.height, c.row0, c.row1, c.col0, c.col1,
                              dst, route.frame_format, raw, route.frame_disp, fog);
         }
+        if (route.shafts) {   // the shafts' two launches (finish_output): into the next HDR node's plane, untransformed, when there is one
+            bool raw = false; void* dst = route.node_dst(kNodeShafts, &raw);
+            const float sun[3] = {e.sun_dir_.x, e.sun_dir_.y, e.sun_dir_.z};
+            e.shafts_steps(c.shafts, route.shafts_plan, c.desc.transform, c.desc.projection, sun, c.shafts_planes.plane[0].ptr, a.g0, true, c.desc.width, c.desc.height,
+                           c.shafts_planes.plane[1].as<float4>(), dst, route.frame_format, raw, route.frame_disp, true, shafts);
+        }
         c.last_lean = s.lean; c.last_lean_composed = s.compose_in_wavelet && s.lean != 0u;   // which planes the frame leaves unwritten: the last a-trous pass's colour planes too
         return ST_OK;
     }
@@ -403,7 +415,7 @@ struct Frame {
         run(KS_REF_SHADING, ST_PASS_REF_SHADING, [&] { e.L.launch_ref_shading(a, seed(SEED_REF_SHADING + 255u), 255u, cur); });
     }
     void prim() {
-        // the fog launch of the frame before last read the G-buffer this launch rewrites, behind that frame's composing launch (DESIGN.md "Fog")
+        // the fog and light-shafts launches of the frame before last read the G-buffer this launch rewrites, behind that frame's composing launch (DESIGN.md "Fog", "Light shafts")
         (void)c.fog_depth_read[c.frame % 2u].wait(cur, Fence::OtherStreams, Fence::Clear);
         if (e.tuning.fuse && s.any_objects) run(KS_PRIM_VISIBILITY_REPROJECTION, ST_PASS_PRIM_VISIBILITY | ST_PASS_FRAME_REPROJECTION, [&] { e.L.launch_prim_visibility(a, true, e.deform.deform_table(), e.deform.deform_posed(), cur); });
         else run(KS_PRIM_VISIBILITY, ST_PASS_PRIM_VISIBILITY, [&] { e.L.launch_prim_visibility(a, false, e.deform.deform_table(), e.deform.deform_posed(), cur); });
@@ -597,14 +609,19 @@ struct Frame {
         if (c.side_stream) { if (int rc = c.ev_prim_ok.record(stream)) return rc; if (int rc = c.ev_frame_done.record(stream)) return rc; }
         return ST_OK;
     }
-    // The launches behind the composing launch, which ran on `stream`: fog, depth of field, motion blur, bloom, then post-processing — one launch group (ST_PASS_POST) —, then the
+    // The launches behind the composing launch, which ran on `stream`: fog, light shafts, depth of field, motion blur, bloom, then post-processing — one launch group (ST_PASS_POST) —, then the
     // meter's finalize; each step's fence is recorded behind its launches.
     int finish_output() {
         cur = stream;
         if (route.fog) {   // it reads the camera's HDR plane and this frame's G-buffer depth: the frame after next rewrites that plane, and its primary visibility waits for this
             run(fog.slot, ST_PASS_POST, [&] { e.L.launch_fog(fog.args, cur); }, fog.bytes);
             if (int rc = c.fog_planes.done(stream)) return rc;
-            if (int rc = c.fog_depth_read[c.frame % 2u].record(stream)) return rc;
+            if (!route.shafts) if (int rc = c.fog_depth_read[c.frame % 2u].record(stream)) return rc;
+        }
+        if (route.shafts) {   // the march reads this frame's G-buffer depth, the live scene copy and the light table; the apply launch the HDR plane, the depth and the cells
+            for (uint32_t i = 0; i < 2u; i++) run(shafts.step[i].slot, ST_PASS_POST, [&] { e.launch_shafts_step(a, shafts, i, cur); }, shafts.step[i].bytes);
+            if (int rc = c.shafts_planes.done(stream)) return rc;
+            if (int rc = c.fog_depth_read[c.frame % 2u].record(stream)) return rc;   // fog's fence, behind the last reader of the depth
         }
         if (route.dof) {   // depth of field's neighbour maximum and gather: they read the camera's packed plane, tile values and HDR plane only
             for (uint32_t i = 1; i < 3u; i++) run(dof.step[i].slot, ST_PASS_POST, [&] { e.launch_dof_step(dof, i, cur); }, dof.step[i].bytes);

@@ -76,7 +76,7 @@ void Engine::remove_light(uint64_t id) {
 void Engine::snapshot_lights() {  // lights.rs:128-154: what the device sees this frame, then commit prev_* for the next one
     for (uint32_t s : lights_killed) light_buffer[s].d3.x = b2f(0xcafebabeu);
     for (auto& kv : lights_remapped) light_buffer[kv.second].d3.x = b2f(light_slot[kv.first] + 1u);
-    gpu_lights = light_buffer;
+    gpu_lights = light_buffer; light_slot_uploaded = light_slot;
     auto commit = [&](int64_t k) { GpuLight& l = light_buffer[light_slot[k]]; l.prev_d0 = l.d0; l.prev_d1 = l.d1; l.prev_d2 = l.d2; };
     for (int64_t k : lights_created) commit(k);
     for (int64_t k : lights_updated) commit(k);

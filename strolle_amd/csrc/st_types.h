@@ -158,6 +158,20 @@ struct FogArgs {
     DisplayArgs display;
 };
 
+// Light shafts (include/strolle_hip.h "light shafts"; st_shafts.cpp, k_shafts.hip): the arguments of its two launches. The march reads the
+// depth (as FogArgs states it) and writes `cells`, cells_w x cells_h float4 (S.rgb, d_c); the apply launch reads `color`, the depth and
+// `cells` and stores `dst` as fog's launch does. origin: M[12..14]; k1, k2, k3: the phase function's constants; L: the sun's direction;
+// lights: slots of the light table the frame's KArgs carries. count: the march adds its rays to KArgs::ray_counter. All wave-uniform.
+constexpr uint32_t kShaftsMaxLights = 8;
+struct ShaftsArgs {
+    const float4* color; const void* depth; float4* cells; void* dst;
+    uint32_t width, height, cells_w, cells_h, divisor, steps, frame, format, raw, count;
+    uint32_t sun_on, light_extinction, light_count, lights[kShaftsMaxLights];
+    float p0, p5, p8, p9, m0[3], m1[3], m2[3], origin[3];
+    float L[3], k1, k2, k3, density, max_distance, intensity, scatter[3], sun_color[3];
+    DisplayArgs display;
+};
+
 // Everything a per-pixel kernel can touch, passed by value as the kernel argument (scalar loads).
 struct KArgs {
     GpuCamera cam, prev_cam;
