@@ -1110,18 +1110,26 @@ class Engine(EngineBase):
         self._check(self._b.debug_deformation(self._h, C.byref(n), C.byref(b)))
         return n.value, b.value
 
+    # ---- the output chain's settings: every st_camera_set_<stage> takes a descriptor or null, every st_camera_get_<stage> returns (descriptor, on)
+    def _set_stage(self, setter, make_desc, camera: int, desc, kw):
+        """a descriptor, or make_desc(**kw) when keywords are given; neither = off"""
+        if desc is None and kw:
+            desc = make_desc(**kw)
+        self._check(setter(self._h, camera, C.byref(desc) if desc is not None else None))
+
+    def _get_stage(self, getter, desc_type, camera: int):
+        d, on = desc_type(), C.c_int()
+        self._check(getter(self._h, camera, C.byref(d), C.byref(on)))
+        return d, bool(on.value)
+
     # ---- display transforms (include/strolle_hip.h "display transforms"): take effect at the camera's next render
     def set_display(self, camera: int, desc: Optional[StDisplayDesc] = None, **kw):
         """st_camera_set_display: a StDisplayDesc, or display_desc(**kw) when keywords are given; neither = off (the output as without a display)."""
-        if desc is None and kw:
-            desc = display_desc(**kw)
-        self._check(self._b.camera_set_display(self._h, camera, C.byref(desc) if desc is not None else None))
+        self._set_stage(self._b.camera_set_display, display_desc, camera, desc, kw)
 
     def display(self, camera: int):
         """st_camera_get_display: (the last StDisplayDesc set, whether the display is on)."""
-        d, on = StDisplayDesc(), C.c_int()
-        self._check(self._b.camera_get_display(self._h, camera, C.byref(d), C.byref(on)))
-        return d, bool(on.value)
+        return self._get_stage(self._b.camera_get_display, StDisplayDesc, camera)
 
     def exposure(self, camera: int):
         """st_camera_exposure (blocking): (scale the next frame uses, metered EV, adapted EV) as the device holds them."""
@@ -1138,15 +1146,11 @@ class Engine(EngineBase):
     # ---- output post-processing (include/strolle_hip.h "post-processing"): takes effect at the camera's next render
     def set_post(self, camera: int, desc: Optional[StPostDesc] = None, **kw):
         """st_camera_set_post: a StPostDesc, or post_desc(**kw) when keywords are given; neither = off."""
-        if desc is None and kw:
-            desc = post_desc(**kw)
-        self._check(self._b.camera_set_post(self._h, camera, C.byref(desc) if desc is not None else None))
+        self._set_stage(self._b.camera_set_post, post_desc, camera, desc, kw)
 
     def post(self, camera: int):
         """st_camera_get_post: (the last StPostDesc set, whether post-processing is on)."""
-        d, on = StPostDesc(), C.c_int()
-        self._check(self._b.camera_get_post(self._h, camera, C.byref(d), C.byref(on)))
-        return d, bool(on.value)
+        return self._get_stage(self._b.camera_get_post, StPostDesc, camera)
 
     def output_size(self, camera: int):
         """st_camera_output_size: (width, height) of the buffer st_render_camera writes."""
@@ -1161,15 +1165,11 @@ class Engine(EngineBase):
     # ---- bloom (include/strolle_hip.h "bloom"): takes effect at the camera's next render
     def set_bloom(self, camera: int, desc: Optional[StBloomDesc] = None, **kw):
         """st_camera_set_bloom: a StBloomDesc, or bloom_desc(**kw) when keywords are given; neither = off."""
-        if desc is None and kw:
-            desc = bloom_desc(**kw)
-        self._check(self._b.camera_set_bloom(self._h, camera, C.byref(desc) if desc is not None else None))
+        self._set_stage(self._b.camera_set_bloom, bloom_desc, camera, desc, kw)
 
     def bloom(self, camera: int):
         """st_camera_get_bloom: (the last StBloomDesc set, whether bloom is on)."""
-        d, on = StBloomDesc(), C.c_int()
-        self._check(self._b.camera_get_bloom(self._h, camera, C.byref(d), C.byref(on)))
-        return d, bool(on.value)
+        return self._get_stage(self._b.camera_get_bloom, StBloomDesc, camera)
 
     def bloom_plan(self, desc: StBloomDesc, width: int, height: int):
         """st_bloom_plan (host arithmetic): (levels, [(width, height) per mip], float32 blend factors per level)."""
@@ -1192,15 +1192,11 @@ class Engine(EngineBase):
     # ---- motion blur (include/strolle_hip.h "motion blur"): takes effect at the camera's next render
     def set_motion_blur(self, camera: int, desc: Optional[StMotionBlurDesc] = None, **kw):
         """st_camera_set_motion_blur: a StMotionBlurDesc, or motion_blur_desc(**kw) when keywords are given; neither = off."""
-        if desc is None and kw:
-            desc = motion_blur_desc(**kw)
-        self._check(self._b.camera_set_motion_blur(self._h, camera, C.byref(desc) if desc is not None else None))
+        self._set_stage(self._b.camera_set_motion_blur, motion_blur_desc, camera, desc, kw)
 
     def get_motion_blur(self, camera: int):
         """st_camera_get_motion_blur: (the last StMotionBlurDesc set, whether the blur is on)."""
-        d, on = StMotionBlurDesc(), C.c_int()
-        self._check(self._b.camera_get_motion_blur(self._h, camera, C.byref(d), C.byref(on)))
-        return d, bool(on.value)
+        return self._get_stage(self._b.camera_get_motion_blur, StMotionBlurDesc, camera)
 
     def motion_blur_process(self, desc: StMotionBlurDesc, color_ptr: int, velocity_ptr: int, depth_ptr: int, width: int, height: int, dst_ptr: int,
                             dst_format: int = 0, display: Optional[StDisplayDesc] = None, stream: int = 0):
@@ -1212,15 +1208,11 @@ class Engine(EngineBase):
     # ---- depth of field (include/strolle_hip.h "depth of field"): takes effect at the camera's next render
     def set_dof(self, camera: int, desc: Optional[StDofDesc] = None, **kw):
         """st_camera_set_dof: a StDofDesc, or dof_desc(**kw) when keywords are given; neither = off."""
-        if desc is None and kw:
-            desc = dof_desc(**kw)
-        self._check(self._b.camera_set_dof(self._h, camera, C.byref(desc) if desc is not None else None))
+        self._set_stage(self._b.camera_set_dof, dof_desc, camera, desc, kw)
 
     def get_dof(self, camera: int):
         """st_camera_get_dof: (the last StDofDesc set, whether depth of field is on)."""
-        d, on = StDofDesc(), C.c_int()
-        self._check(self._b.camera_get_dof(self._h, camera, C.byref(d), C.byref(on)))
-        return d, bool(on.value)
+        return self._get_stage(self._b.camera_get_dof, StDofDesc, camera)
 
     def dof_process(self, desc: StDofDesc, projection, color_ptr: int, depth_ptr: int, width: int, height: int, dst_ptr: int, dst_format: int = 0,
                     display: Optional[StDisplayDesc] = None, stream: int = 0):
@@ -1233,15 +1225,11 @@ class Engine(EngineBase):
     # ---- fog (include/strolle_hip.h "fog"): takes effect at the camera's next render
     def set_fog(self, camera: int, desc: Optional[StFogDesc] = None, **kw):
         """st_camera_set_fog: a StFogDesc, or fog_desc(**kw) when keywords are given; neither = off."""
-        if desc is None and kw:
-            desc = fog_desc(**kw)
-        self._check(self._b.camera_set_fog(self._h, camera, C.byref(desc) if desc is not None else None))
+        self._set_stage(self._b.camera_set_fog, fog_desc, camera, desc, kw)
 
     def get_fog(self, camera: int):
         """st_camera_get_fog: (the last StFogDesc set, whether fog is on)."""
-        d, on = StFogDesc(), C.c_int()
-        self._check(self._b.camera_get_fog(self._h, camera, C.byref(d), C.byref(on)))
-        return d, bool(on.value)
+        return self._get_stage(self._b.camera_get_fog, StFogDesc, camera)
 
     def fog_process(self, desc: StFogDesc, transform, projection, color_ptr: int, depth_ptr: int, width: int, height: int, dst_ptr: int, dst_format: int = 0,
                     display: Optional[StDisplayDesc] = None, stream: int = 0):
@@ -1254,15 +1242,11 @@ class Engine(EngineBase):
     # ---- light shafts (include/strolle_hip.h "light shafts"): takes effect at the camera's next render
     def set_light_shafts(self, camera: int, desc: Optional[StLightShaftsDesc] = None, **kw):
         """st_camera_set_light_shafts: a StLightShaftsDesc, or light_shafts_desc(**kw) when keywords are given; neither = off."""
-        if desc is None and kw:
-            desc = light_shafts_desc(**kw)
-        self._check(self._b.camera_set_light_shafts(self._h, camera, C.byref(desc) if desc is not None else None))
+        self._set_stage(self._b.camera_set_light_shafts, light_shafts_desc, camera, desc, kw)
 
     def get_light_shafts(self, camera: int):
         """st_camera_get_light_shafts: (the last StLightShaftsDesc set, whether the node is on)."""
-        d, on = StLightShaftsDesc(), C.c_int()
-        self._check(self._b.camera_get_light_shafts(self._h, camera, C.byref(d), C.byref(on)))
-        return d, bool(on.value)
+        return self._get_stage(self._b.camera_get_light_shafts, StLightShaftsDesc, camera)
 
     def light_shafts_process(self, desc: StLightShaftsDesc, transform, projection, color_ptr: int, depth_ptr: int, width: int, height: int, dst_ptr: int,
                              dst_format: int = 0, display: Optional[StDisplayDesc] = None, stream: int = 0):

@@ -6,6 +6,17 @@ using namespace st;
 static Engine* E(StEngine* e) { return reinterpret_cast<Engine*>(e); }
 #define ST_REQUIRE(cond, msg) do { if (!(cond)) return fail(ST_ERR_INVALID_ARGUMENT, msg); } while (0)
 
+// st_camera_get_<stage>: the last descriptor set and whether the stage is on, for every stage a CameraState holds as a NodeSetting
+template <class Desc, int N> static int camera_get(StEngine* e, StHandle h, NodeSetting<Desc, N> CameraState::*setting, Desc* out, int* enabled) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    const NodeSetting<Desc, N>& s = (*it->second).*setting;
+    if (out) { *out = s.desc; out->struct_size = sizeof(Desc); }
+    if (enabled) *enabled = s.on ? 1 : 0;
+    return ST_OK;
+}
+
 extern "C" {
 
 const char* st_last_error(void) { return g_last_error.c_str(); }
@@ -271,11 +282,10 @@ int st_camera_set_window(StEngine* e, StHandle h, uint32_t x0, uint32_t y0, uint
     ST_REQUIRE(x0 % 16u == 0u && (x1 % 16u == 0u || x1 == s.desc.width), "window columns must be multiples of 16 (or the frame's right edge)");
     const bool full = x0 == 0u && y0 == 0u && x1 == s.desc.width && y1 == s.desc.height;
     ST_REQUIRE(full || !s.display_auto(), "a window on a camera with auto-exposure would meter the tile alone (include/strolle_hip.h \"display transforms\")");
-    ST_REQUIRE(full || !s.post_on, "a window on a camera with post-processing: FXAA and the resampler read across tile edges (include/strolle_hip.h \"post-processing\")");
-    ST_REQUIRE(full || !s.bloom_on, "a window on a camera with bloom: the pyramid reads far across tile edges (include/strolle_hip.h \"bloom\")");
-    ST_REQUIRE(full || !s.mblur_on, "a window on a camera with motion blur: the gather reads up to 32 pixels across tile edges (include/strolle_hip.h \"motion blur\")");
-    ST_REQUIRE(full || !s.dof_on, "a window on a camera with depth of field: the gather reads up to 32 pixels across tile edges (include/strolle_hip.h \"depth of field\")");
-    ST_REQUIRE(full || !s.shafts_on, "a window on a camera with light shafts: the apply launch reads neighbouring cells across tile edges (include/strolle_hip.h \"light shafts\")");
+    // each stage's own rule (st_output_chain.h), as its setter states it; fog carries none
+    const std::initializer_list<std::pair<bool, const WindowRule*>> stages = {{s.post.on, s.post.window}, {s.bloom.on, s.bloom.window}, {s.mblur.on, s.mblur.window},
+                                                                              {s.dof.on, s.dof.window}, {s.fog.on, s.fog.window}, {s.shafts.on, s.shafts.window}};
+    for (const auto& st : stages) if (!full && st.first && st.second) return fail(ST_ERR_INVALID_ARGUMENT, window_refused_by(*st.second));
     s.row0 = y0; s.row1 = y1; s.col0 = x0; s.col1 = x1;
     return ST_OK;
 }
@@ -326,15 +336,7 @@ int st_camera_set_post(StEngine* e, StHandle h, const StPostDesc* desc) {
     if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
     return E(e)->set_post(*it->second, desc);
 }
-int st_camera_get_post(StEngine* e, StHandle h, StPostDesc* out, int* enabled) {
-    ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    const CameraState& s = *it->second;
-    if (out) { *out = s.post; out->struct_size = sizeof(StPostDesc); }
-    if (enabled) *enabled = s.post_on ? 1 : 0;
-    return ST_OK;
-}
+int st_camera_get_post(StEngine* e, StHandle h, StPostDesc* out, int* enabled) { return camera_get(e, h, &CameraState::post, out, enabled); }
 int st_camera_output_size(StEngine* e, StHandle h, uint32_t* width, uint32_t* height) {
     ST_REQUIRE(e, "null engine");
     auto it = E(e)->cameras.find(h);
@@ -355,15 +357,7 @@ int st_camera_set_bloom(StEngine* e, StHandle h, const StBloomDesc* desc) {
     if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
     return E(e)->set_bloom(*it->second, desc);
 }
-int st_camera_get_bloom(StEngine* e, StHandle h, StBloomDesc* out, int* enabled) {
-    ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    const CameraState& s = *it->second;
-    if (out) { *out = s.bloom; out->struct_size = sizeof(StBloomDesc); }
-    if (enabled) *enabled = s.bloom_on ? 1 : 0;
-    return ST_OK;
-}
+int st_camera_get_bloom(StEngine* e, StHandle h, StBloomDesc* out, int* enabled) { return camera_get(e, h, &CameraState::bloom, out, enabled); }
 int st_bloom_plan(const StBloomDesc* desc, uint32_t width, uint32_t height, uint32_t* levels, uint32_t sizes_wh[16], float factors[8]) {
     ST_REQUIRE(desc, "null desc");
     Engine::BloomPlan plan;
@@ -387,15 +381,7 @@ int st_camera_set_motion_blur(StEngine* e, StHandle h, const StMotionBlurDesc* d
     if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
     return E(e)->set_motion_blur(*it->second, desc);
 }
-int st_camera_get_motion_blur(StEngine* e, StHandle h, StMotionBlurDesc* out, int* enabled) {
-    ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    const CameraState& s = *it->second;
-    if (out) { *out = s.mblur; out->struct_size = sizeof(StMotionBlurDesc); }
-    if (enabled) *enabled = s.mblur_on ? 1 : 0;
-    return ST_OK;
-}
+int st_camera_get_motion_blur(StEngine* e, StHandle h, StMotionBlurDesc* out, int* enabled) { return camera_get(e, h, &CameraState::mblur, out, enabled); }
 int st_motion_blur_process(StEngine* e, const StMotionBlurDesc* desc, const StDisplayDesc* display, const void* color, const void* velocity, const void* depth,
                            uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
     ST_REQUIRE(e, "null engine");
@@ -409,15 +395,7 @@ int st_camera_set_dof(StEngine* e, StHandle h, const StDofDesc* desc) {
     if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
     return E(e)->set_dof(*it->second, desc);
 }
-int st_camera_get_dof(StEngine* e, StHandle h, StDofDesc* out, int* enabled) {
-    ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    const CameraState& s = *it->second;
-    if (out) { *out = s.dof; out->struct_size = sizeof(StDofDesc); }
-    if (enabled) *enabled = s.dof_on ? 1 : 0;
-    return ST_OK;
-}
+int st_camera_get_dof(StEngine* e, StHandle h, StDofDesc* out, int* enabled) { return camera_get(e, h, &CameraState::dof, out, enabled); }
 int st_dof_plan(const StDofDesc* desc, uint32_t width, uint32_t height, uint32_t* samples, uint32_t tiles_xy[2], float taps_xyr[64 * 3]) {
     ST_REQUIRE(desc, "null desc");
     Engine::DofPlan plan;
@@ -440,15 +418,7 @@ int st_camera_set_fog(StEngine* e, StHandle h, const StFogDesc* desc) {
     if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
     return E(e)->set_fog(*it->second, desc);
 }
-int st_camera_get_fog(StEngine* e, StHandle h, StFogDesc* out, int* enabled) {
-    ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    const CameraState& s = *it->second;
-    if (out) { *out = s.fog; out->struct_size = sizeof(StFogDesc); }
-    if (enabled) *enabled = s.fog_on ? 1 : 0;
-    return ST_OK;
-}
+int st_camera_get_fog(StEngine* e, StHandle h, StFogDesc* out, int* enabled) { return camera_get(e, h, &CameraState::fog, out, enabled); }
 int st_fog_process(StEngine* e, const StFogDesc* desc, const StDisplayDesc* display, const float transform[16], const float projection[16], const void* color, const void* depth,
                    uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
     ST_REQUIRE(e, "null engine");
@@ -462,15 +432,7 @@ int st_camera_set_light_shafts(StEngine* e, StHandle h, const StLightShaftsDesc*
     if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
     return E(e)->set_shafts(*it->second, desc);
 }
-int st_camera_get_light_shafts(StEngine* e, StHandle h, StLightShaftsDesc* out, int* enabled) {
-    ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    const CameraState& s = *it->second;
-    if (out) { *out = s.shafts; out->struct_size = sizeof(StLightShaftsDesc); }
-    if (enabled) *enabled = s.shafts_on ? 1 : 0;
-    return ST_OK;
-}
+int st_camera_get_light_shafts(StEngine* e, StHandle h, StLightShaftsDesc* out, int* enabled) { return camera_get(e, h, &CameraState::shafts, out, enabled); }
 int st_light_shafts_plan(const StLightShaftsDesc* desc, uint32_t width, uint32_t height, uint32_t cells_wh[2], float jitter[16]) {
     ST_REQUIRE(desc, "null desc");
     Engine::ShaftsPlan plan;

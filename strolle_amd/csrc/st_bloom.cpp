@@ -1,6 +1,6 @@
 // st_bloom.cpp — bloom (include/strolle_hip.h "bloom"): the setter's checks, the plan (level count, mip sizes, blend factors: host arithmetic
 // that st_bloom_plan reports) and the chain of launches (k_bloom.hip) that st_render_camera and st_bloom_process share. The HDR plane and
-// the pyramids: st_engine.h CameraState::bloom_planes, Engine::bloom_scratch.
+// the pyramids: st_engine.h CameraState::bloom, Engine::bloom_scratch.
 #include <cmath>
 
 #include "st_engine.h"
@@ -9,7 +9,7 @@ namespace st {
 
 static_assert(KS_COUNT <= ST_PROFILE_MAX_KERNELS, "st_profile_read's callers size their arrays with ST_PROFILE_MAX_KERNELS");
 static_assert(sizeof(StBloomDesc) == 40, "StBloomDesc is 40 B");
-static constexpr uint32_t kBloomMaxSide = 16384u, kBloomMaxLevels = 8u, kBloomDefaultLevels = 6u;
+static constexpr uint32_t kBloomMaxLevels = 8u, kBloomDefaultLevels = 6u;
 static constexpr float kBloomDefaultClamp = 65504.0f;
 
 static int check_bloom(const StBloomDesc& d) {
@@ -30,7 +30,7 @@ static int check_bloom(const StBloomDesc& d) {
 int Engine::bloom_plan(const StBloomDesc& d, uint32_t w, uint32_t h, BloomPlan& plan) {
     plan = BloomPlan();
     if (int rc = check_bloom(d)) return rc;
-    if (w > kBloomMaxSide || h > kBloomMaxSide) return fail(ST_ERR_INVALID_ARGUMENT, "a frame side above 16384");
+    if (w > kMaxImageSide || h > kMaxImageSide) return fail(ST_ERR_INVALID_ARGUMENT, "a frame side above 16384");
     const uint32_t wanted = d.levels ? d.levels : kBloomDefaultLevels;
     uint32_t mw = w, mh = h;
     while (plan.levels < wanted) {
@@ -52,11 +52,7 @@ int Engine::bloom_plan(const StBloomDesc& d, uint32_t w, uint32_t h, BloomPlan& 
 }
 
 int Engine::set_bloom(CameraState& c, const StBloomDesc* desc) {
-    if (!desc) { c.bloom_on = false; return ST_OK; }
-    if (int rc = check_bloom(*desc)) return rc;
-    if (c.windowed()) return fail(ST_ERR_INVALID_ARGUMENT, "bloom on a camera with a window: the pyramid reads far across tile edges (include/strolle_hip.h \"bloom\")");
-    c.bloom = *desc; c.bloom_on = true;
-    return ST_OK;
+    return set_node(c.windowed(), c.bloom, desc, check_bloom);
 }
 
 // The fused tail takes the levels t .. L - 1 whose mips, three floats per texel, fit `tail_lds_bytes` together; t >= 1 (mip t - 1 is its input and
@@ -81,7 +77,7 @@ uint32_t Engine::bloom_tail_bytes() {
 // The straightforward chain: L downsamples (frame -> mip 0 -> .. -> mip L - 1), L - 1 upsamples (mip k into mip k - 1, k = L - 1 .. 1) and the
 // composite. With a tail from level t: t downsamples, the tail (levels t .. L - 1 down and back up into mip t - 1), t - 1 upsamples, the composite.
 // Compulsory bytes: every source texel read once, every destination pixel read (where it is blended) and written once.
-Engine::BloomSteps Engine::bloom_steps(const StBloomDesc& d, const BloomPlan& plan, const void* src, uint32_t w, uint32_t h, float4* pyramid, void* dst, uint32_t format, const DisplayArgs& display, uint32_t tail_lds_bytes) {
+Engine::BloomSteps Engine::bloom_steps(const StBloomDesc& d, const BloomPlan& plan, const void* src, uint32_t w, uint32_t h, float4* pyramid, const NodeTarget& target, uint32_t tail_lds_bytes) {
     BloomSteps s;
     BloomArgs base{};
     base.additive = (d.flags & ST_BLOOM_ADDITIVE) ? 1u : 0u;
@@ -90,14 +86,14 @@ Engine::BloomSteps Engine::bloom_steps(const StBloomDesc& d, const BloomPlan& pl
     base.threshold_on = d.threshold > 0.0f ? 1u : 0u;
     const float knee = d.threshold * d.threshold_softness;
     base.threshold = d.threshold; base.knee_lo = d.threshold - knee; base.knee2 = 2.0f * knee; base.knee_div = 4.0f * knee + 1e-4f;
-    base.display = display;
+    base.display = target.display;
     const uint32_t L = plan.levels, T = bloom_tail_first(plan, tail_lds_bytes);
     for (uint32_t k = 0; k < T; k++) {
         BloomArgs a = base;
         a.src = k == 0u ? static_cast<const float4*>(src) : pyramid + plan.offset[k - 1u];
         a.sw = k == 0u ? w : plan.w[k - 1u]; a.sh = k == 0u ? h : plan.h[k - 1u];
         a.dst = pyramid + plan.offset[k]; a.dw = plan.w[k]; a.dh = plan.h[k];
-        s.step[s.count++] = {KS_BLOOM_DOWN, k == 0u, a, BloomTailArgs{}, ((double)a.sw * a.sh + (double)a.dw * a.dh) * 16.0};
+        s.step[s.count++] = {{KS_BLOOM_DOWN, ((double)a.sw * a.sh + (double)a.dw * a.dh) * 16.0}, k == 0u, a, BloomTailArgs{}};
     }
     if (T < L) {
         BloomTailArgs t{};
@@ -109,48 +105,42 @@ Engine::BloomSteps Engine::bloom_steps(const StBloomDesc& d, const BloomPlan& pl
             t.off[i] = floats; floats += t.w[i] * t.h[i] * 3u;
         }
         t.lds_bytes = floats * (uint32_t)sizeof(float);
-        s.step[s.count++] = {KS_BLOOM_TAIL, false, BloomArgs{}, t, (double)t.bw * t.bh * 48.0};   // mip t - 1 read by the downsample, then read and written by the blend
+        s.step[s.count++] = {{KS_BLOOM_TAIL, (double)t.bw * t.bh * 48.0}, false, BloomArgs{}, t};   // mip t - 1 read by the downsample, then read and written by the blend
     }
     for (uint32_t k = T; k-- > 1u;) {
         BloomArgs a = base;
         a.src = pyramid + plan.offset[k]; a.sw = plan.w[k]; a.sh = plan.h[k];
         a.dst = pyramid + plan.offset[k - 1u]; a.dw = plan.w[k - 1u]; a.dh = plan.h[k - 1u];
         a.factor = plan.factor[k];
-        s.step[s.count++] = {KS_BLOOM_UP, false, a, BloomTailArgs{}, (double)a.sw * a.sh * 16.0 + (double)a.dw * a.dh * 32.0};
+        s.step[s.count++] = {{KS_BLOOM_UP, (double)a.sw * a.sh * 16.0 + (double)a.dw * a.dh * 32.0}, false, a, BloomTailArgs{}};
     }
     BloomArgs a = base;
     a.src = L ? pyramid + plan.offset[0] : nullptr; a.sw = L ? plan.w[0] : 0u; a.sh = L ? plan.h[0] : 0u;
-    a.base = static_cast<const float4*>(src); a.dst = dst; a.dw = w; a.dh = h; a.format = format;
+    a.base = static_cast<const float4*>(src); a.dst = target.dst; a.dw = w; a.dh = h; a.format = target.format;
     a.factor = L ? plan.factor[0] : 0.0f;
-    s.step[s.count++] = {KS_BLOOM_COMPOSITE, false, a, BloomTailArgs{}, (double)a.sw * a.sh * 16.0 + (double)w * h * (16.0 + format_bytes(format))};
+    s.step[s.count++] = {{KS_BLOOM_COMPOSITE, (double)a.sw * a.sh * 16.0 + (double)w * h * (16.0 + format_bytes(target.format))}, false, a, BloomTailArgs{}};
     return s;
 }
 
 void Engine::launch_bloom_step(const BloomStep& s, hipStream_t stream) {
-    if (s.slot == KS_BLOOM_DOWN) L.launch_bloom_down(s.args, s.first, stream);
-    else if (s.slot == KS_BLOOM_UP) L.launch_bloom_up(s.args, stream);
-    else if (s.slot == KS_BLOOM_TAIL) L.launch_bloom_tail(s.tail, stream);
+    if (s.step.slot == KS_BLOOM_DOWN) L.launch_bloom_down(s.args, s.first, stream);
+    else if (s.step.slot == KS_BLOOM_UP) L.launch_bloom_up(s.args, stream);
+    else if (s.step.slot == KS_BLOOM_TAIL) L.launch_bloom_tail(s.tail, stream);
     else L.launch_bloom_composite(s.args, stream);
 }
 
 int Engine::bloom_process(const StBloomDesc* desc, const StDisplayDesc* display, const void* src, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream) {
     if (!desc || !src || !dst) return fail(ST_ERR_INVALID_ARGUMENT, "null argument");
-    if (w == 0u || h == 0u || w > kBloomMaxSide || h > kBloomMaxSide) return fail(ST_ERR_INVALID_ARGUMENT, "the image's sides must be in 1..16384");
+    if (w == 0u || h == 0u || w > kMaxImageSide || h > kMaxImageSide) return fail(ST_ERR_INVALID_ARGUMENT, "the image's sides must be in 1..16384");
     BloomPlan plan;
     if (int rc = bloom_plan(*desc, w, h, plan)) return rc;
-    DisplayArgs disp{};   // none: NONE at scale 1, which stores the colour's own bits
-    disp.scale = 1.0f;
-    if (display) {
-        if (int rc = check_display(*display)) return rc;
-        if (display->flags & ST_DISPLAY_AUTO_EXPOSURE) return fail(ST_ERR_INVALID_ARGUMENT, "st_bloom_process takes a manual display: auto-exposure is a camera's state");
-        disp.on = 1u; disp.tonemap = display->tonemap; disp.scale = (float)std::exp2((double)display->exposure_ev);
-    }
-    if (format < ST_FORMAT_RGBA32F || format > ST_FORMAT_BGRA8_UNORM_SRGB) return fail(ST_ERR_INVALID_ARGUMENT, "unknown output format");
+    NodeTarget target;
+    if (int rc = process_target("st_bloom_process", display, dst, format, target)) return rc;
     if (!has_device) return fail(ST_ERR_NO_DEVICE, "st_bloom_process on a host-only engine");
     ST_HIP(hipSetDevice(device));
     const size_t bytes = plan.texels * sizeof(float4);   // the engine's pyramid (0: the image holds no level)
     if (bytes) if (int rc = bloom_scratch.acquire({bytes}, bloom_scratch.Grow, stream)) return rc;
-    const BloomSteps steps = bloom_steps(*desc, plan, src, w, h, bloom_scratch.plane[0].as<float4>(), dst, (uint32_t)format, disp, bloom_tail_bytes());
+    const BloomSteps steps = bloom_steps(*desc, plan, src, w, h, bloom_scratch.plane[0].as<float4>(), target, bloom_tail_bytes());
     for (uint32_t i = 0; i < steps.count; i++) launch_bloom_step(steps.step[i], stream);
     if (bytes) if (int rc = bloom_scratch.done(stream)) return rc;
     ST_HIP(hipGetLastError());

@@ -23,6 +23,19 @@ int check_display(const StDisplayDesc& d) {
     return ST_OK;
 }
 
+// no display: NONE at scale 1, which stores the colour's own bits
+int process_target(const char* call, const StDisplayDesc* display, void* dst, int format, NodeTarget& out) {
+    out = NodeTarget{dst, (uint32_t)format, false, DisplayArgs{}};
+    out.display.scale = 1.0f;
+    if (display) {
+        if (int rc = check_display(*display)) return rc;
+        if (display->flags & ST_DISPLAY_AUTO_EXPOSURE) return fail(ST_ERR_INVALID_ARGUMENT, std::string(call) + " takes a manual display: auto-exposure is a camera's state");
+        out.display.on = 1u; out.display.tonemap = display->tonemap; out.display.scale = (float)std::exp2((double)display->exposure_ev);
+    }
+    if (format < ST_FORMAT_RGBA32F || format > ST_FORMAT_BGRA8_UNORM_SRGB) return fail(ST_ERR_INVALID_ARGUMENT, "unknown output format");
+    return ST_OK;
+}
+
 int Engine::set_display(CameraState& c, const StDisplayDesc* desc) {
     if (!desc) { c.display_on = false; return ST_OK; }
     if (int rc = check_display(*desc)) return rc;

@@ -330,6 +330,7 @@ inline double format_bytes(uint32_t format) { return format == ST_FORMAT_RGBA32F
 
 }  // namespace st
 #include "st_deform.h"
+#include "st_output_chain.h"
 namespace st {
 
 // ------------------------------------------------------------------ per-camera state (camera_controller/buffers.rs)
@@ -387,55 +388,29 @@ struct CameraState {
     DeviceArray display_state; Fence display_done;
     bool display_auto() const { return display_on && (display.flags & ST_DISPLAY_AUTO_EXPOSURE) != 0u; }
     bool windowed() const { return row0 != 0u || col0 != 0u || row1 != desc.height || col1 != desc.width; }
-    // Output post-processing (st_post.cpp; include/strolle_hip.h "post-processing"). Like the display it is not part of the per-camera
-    // buffers and survives st_camera_update. While a frame needs it, the composing launch writes post_planes.plane[0] (render size, RGBA32F)
-    // instead of the caller's buffer; plane[1] carries FXAA's output to the resampler when both run. Both are allocated by the first
-    // frame that needs them and again only when the render size changed; their fence is recorded behind each frame's post launches.
-    StPostDesc post{}; bool post_on = false;
-    FencedPlanes<2> post_planes;
-    bool post_resizes() const { return post_on && post.output_width != 0u && (post.output_width != desc.width || post.output_height != desc.height); }
-    bool post_fxaa() const { return post_on && (post.flags & ST_POST_FXAA) != 0u && desc.mode != ST_MODE_BVH_HEATMAP; }   // heatmap frames are false colour
-    // Bloom (st_bloom.cpp; include/strolle_hip.h "bloom"). Like the display and post-processing it survives st_camera_update. While a frame
-    // blooms, the composing launch writes the HDR plane (render size, RGBA32F, untransformed) instead of the caller's buffer or the post plane, and
-    // the bloom launches build the pyramid (one allocation of float4 mips) from it; the composite writes where the composing launch would have.
-    // Both are made by the first frame that needs them and again only when one has to grow; their fence is recorded behind each frame's bloom launches.
-    StBloomDesc bloom{}; bool bloom_on = false;
-    FencedPlanes<2> bloom_planes;   // [0] the HDR plane, [1] the pyramid
-    bool blooms() const { return bloom_on && desc.mode != ST_MODE_BVH_HEATMAP; }   // heatmap frames are false colour
-    // Motion blur (st_motion_blur.cpp; include/strolle_hip.h "motion blur"), in front of bloom; it survives st_camera_update like the rest of the
-    // output chain. While a frame blurs, primary visibility keeps the velocity map (kLeanKeepVelocity), the pack launch turns it and the depth
-    // into the packed plane and the tile vectors before the next frame's primary visibility may start, the composing launch writes the HDR plane
-    // and the gather writes where the composing launch would have (or bloom's HDR plane). Grown and fenced like bloom_planes.
-    StMotionBlurDesc mblur{}; bool mblur_on = false;
-    FencedPlanes<4> mblur_planes;   // [0] the HDR plane, [1] (r, Z) per pixel, [2] the tile vectors, [3] their 3 x 3 neighbour maxima
-    bool blurs() const { return mblur_on && desc.mode != ST_MODE_BVH_HEATMAP && desc.mode != ST_MODE_REFERENCE; }   // those two run no primary-visibility pass: no velocity map
-    // Depth of field (st_dof.cpp; include/strolle_hip.h "depth of field"), in front of motion blur; it survives st_camera_update like the rest of
-    // the output chain. While a frame focuses, the pack launch turns the G-buffer's depth into the packed plane and the tile values before the
-    // next frame's primary visibility may start, the composing launch writes the HDR plane and the gather writes where the composing launch
-    // would have (or the HDR plane of motion blur or bloom). Grown and fenced like mblur_planes.
-    StDofDesc dof{}; bool dof_on = false;
-    FencedPlanes<4> dof_planes;   // [0] the HDR plane, [1] (coc, Z) per pixel, [2] the tiles' near-field maxima, [3] their 3 x 3 neighbour maxima
-    // heatmap and reference frames have no G-buffer; the focal length is derived from a perspective projection
-    bool focuses() const { return dof_on && desc.mode != ST_MODE_BVH_HEATMAP && desc.mode != ST_MODE_REFERENCE && dof_perspective(desc.projection); }
-    // Fog (st_fog.cpp; include/strolle_hip.h "fog"), the first node of the output chain, in front of depth of field; it survives
-    // st_camera_update like the rest. While a frame is fogged, the composing launch writes the HDR plane and one launch behind it writes where
-    // the composing launch would have (or the HDR plane of the next node that is on). Pointwise, so a window does not exclude it. That launch
-    // reads the G-buffer of the frame's parity, which primary visibility of the frame after next rewrites: fog_depth_read[parity] is recorded
-    // behind it and the next primary-visibility launch of that parity waits for it (DESIGN.md "Fog").
-    StFogDesc fog{}; bool fog_on = false;
-    FencedPlanes<1> fog_planes;   // [0] the HDR plane
-    Fence fog_depth_read[2];
-    bool fogs() const { return fog_on && desc.mode != ST_MODE_BVH_HEATMAP && desc.mode != ST_MODE_REFERENCE && dof_perspective(desc.projection); }
-    // Light shafts (st_shafts.cpp; include/strolle_hip.h "light shafts"), between fog and depth of field; the setting survives st_camera_update
-    // like the rest. While a frame carries shafts, the node in front of it (fog, else the composing launch) writes the HDR plane; the march writes
-    // the cell plane from this frame's G-buffer depth and the live scene copy, and the apply launch behind it writes where the node in front
-    // would have (or the HDR plane of the next node that is on). Both read the G-buffer of the frame's parity: they share fog's fence
-    // (fog_depth_read, recorded behind the last of the three launches). The apply launch reads neighbouring cells: a window excludes the node.
-    StLightShaftsDesc shafts{}; bool shafts_on = false;
-    FencedPlanes<2> shafts_planes;   // [0] the HDR plane, [1] the cell plane (S.rgb, d_c)
-    bool shafted() const { return shafts_on && desc.mode != ST_MODE_BVH_HEATMAP && desc.mode != ST_MODE_REFERENCE && dof_perspective(desc.projection); }
-    uint32_t out_width() const { return post_on && post.output_width != 0u ? post.output_width : desc.width; }
-    uint32_t out_height() const { return post_on && post.output_width != 0u ? post.output_height : desc.height; }
+    // The output chain (st_output_chain.h NodeSetting: descriptor, on, planes; each survives st_camera_update). Post-processing (st_post.cpp):
+    // while a frame needs it, the composing launch writes planes[0] (render size, RGBA32F) instead of the caller's buffer; planes[1] carries
+    // FXAA's output to the resampler when both run; replaced only when the render size changed. In front of it the five HDR nodes, in
+    // chain order (DESIGN.md "The output chain"; the order and what a frame does with each is st_render.cpp's node table): while a node is
+    // on, whatever is in front of it — the composing launch, else the node before — writes the node's HDR plane, and its own last launch
+    // writes where that one would have. Their planes are grown, never shrunk.
+    NodeSetting<StPostDesc, 2> post{&kPostWindow};
+    NodeSetting<StFogDesc, 1> fog{nullptr};                  // st_fog.cpp. [0] the HDR plane. Pointwise: a window does not exclude it
+    NodeSetting<StLightShaftsDesc, 2> shafts{&kShaftsWindow};   // st_shafts.cpp. [0] the HDR plane, [1] the cell plane (S.rgb, d_c)
+    NodeSetting<StDofDesc, 4> dof{&kDofWindow};              // st_dof.cpp. [0] the HDR plane, [1] (coc, Z) per pixel, [2] the tiles' near-field maxima, [3] their 3 x 3 neighbour maxima
+    NodeSetting<StMotionBlurDesc, 4> mblur{&kMBlurWindow};   // st_motion_blur.cpp. [0] the HDR plane, [1] (r, Z) per pixel, [2] the tile vectors, [3] their 3 x 3 neighbour maxima
+    NodeSetting<StBloomDesc, 2> bloom{&kBloomWindow};        // st_bloom.cpp. [0] the HDR plane, [1] the pyramid (one allocation of float4 mips)
+    // Which frames run a node that is on. Heatmap frames are false colour; heatmap and reference frames run no primary-visibility pass, so they
+    // have no G-buffer and no velocity map; the nodes that derive a pixel's ray or the focal length need a perspective projection.
+    bool has_gbuffer() const { return desc.mode != ST_MODE_BVH_HEATMAP && desc.mode != ST_MODE_REFERENCE; }
+    bool post_resizes() const { return post.on && post.desc.output_width != 0u && (post.desc.output_width != desc.width || post.desc.output_height != desc.height); }
+    bool post_fxaa() const { return post.on && (post.desc.flags & ST_POST_FXAA) != 0u && desc.mode != ST_MODE_BVH_HEATMAP; }
+    // The fog and light-shafts launches read the G-buffer of the frame's parity, which primary visibility of the frame after next rewrites:
+    // gbuffer_depth_read[parity] is recorded behind the last of them and the next primary-visibility launch of that parity waits for it
+    // (DESIGN.md "Fog", "Light shafts")
+    Fence gbuffer_depth_read[2];
+    uint32_t out_width() const { return post.on && post.desc.output_width != 0u ? post.desc.output_width : desc.width; }
+    uint32_t out_height() const { return post.on && post.desc.output_width != 0u ? post.desc.output_height : desc.height; }
     // A present copy still in flight writes the caller's host memory: it lands before the stream goes. Everything else goes with its member —
     // the caller has made the device current and joined it (st_camera_delete, ~Engine).
     void join_present() { if (present_stream) (void)hipStreamSynchronize(present_stream); }
@@ -481,8 +456,6 @@ int dist_window(uint32_t width, uint32_t height, const StDistRect* owned, uint32
 int dist_grid(uint32_t width, uint32_t height, uint32_t world, uint32_t cols, StDistGrid* out);
 int dist_grid_tile(const StDistGrid* g, uint32_t rank, StDistRect* owned);
 int dist_grid_rebalance(uint32_t width, uint32_t height, const StDistGrid* cur, const float* cost, uint32_t max_step, StDistGrid* out);
-
-int check_display(const StDisplayDesc& d);   // st_display.cpp: the setter's checks (st_bloom_process takes a display descriptor too)
 
 struct Engine {
     int device = -1;
@@ -798,13 +771,15 @@ struct Engine {
     int set_post(CameraState& c, const StPostDesc* desc);
     int post_process(const StPostDesc* desc, const void* src, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
     FencedPlanes<1> post_scratch;   // st_post_process's intermediate plane (FXAA -> resampler): it only grows; calls on different streams take turns
+    // ---- the HDR nodes (st_output_chain.h). Each has its checks, a plan where frames of a size share host work, `*_steps`: the argument
+    // block(s) and the OutputStep list of its launches from a NodeSource into a NodeTarget, `launch_*_step`, the setter, and the stateless call
     // ---- bloom (st_bloom.cpp)
     struct BloomPlan { uint32_t levels = 0; uint32_t w[8] = {}, h[8] = {}; float factor[8] = {}; size_t offset[8] = {}; size_t texels = 0; };
-    struct BloomStep { int slot; bool first; BloomArgs args; BloomTailArgs tail; double bytes; };
+    struct BloomStep { OutputStep step; bool first; BloomArgs args; BloomTailArgs tail; };
     struct BloomSteps { BloomStep step[16]; uint32_t count = 0; };
     static int bloom_plan(const StBloomDesc& d, uint32_t w, uint32_t h, BloomPlan& plan);   // checks the desc; levels == 0: the frame holds no level
-    // the frame's launches in order: `src` (w x h RGBA32F) -> the pyramid -> `dst` in `format` through `display`
-    static BloomSteps bloom_steps(const StBloomDesc& d, const BloomPlan& plan, const void* src, uint32_t w, uint32_t h, float4* pyramid, void* dst, uint32_t format, const DisplayArgs& display, uint32_t tail_lds_bytes);
+    // the frame's launches in order: `src` (w x h RGBA32F) -> the pyramid -> the target (never raw: bloom is the last node)
+    static BloomSteps bloom_steps(const StBloomDesc& d, const BloomPlan& plan, const void* src, uint32_t w, uint32_t h, float4* pyramid, const NodeTarget& target, uint32_t tail_lds_bytes);
     int set_bloom(CameraState& c, const StBloomDesc* desc);
     void launch_bloom_step(const BloomStep& s, hipStream_t stream);   // one of bloom_steps' launches
     int bloom_process(const StBloomDesc* desc, const StDisplayDesc* display, const void* src, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
@@ -817,39 +792,33 @@ struct Engine {
     FencedPlanes<1> bloom_scratch;   // st_bloom_process's pyramid: likewise
     // ---- motion blur (st_motion_blur.cpp)
     struct MBlurPlan { uint32_t tiles_x = 0, tiles_y = 0; size_t packed_bytes = 0, tile_bytes = 0; };
-    struct MBlurStep { int slot; MBlurArgs args; double bytes; };
-    struct MBlurSteps { MBlurStep step[3]; };   // pack (+ tile maximum), neighbour maximum, gather
+    struct MBlurSteps { MBlurArgs args; OutputStep step[3]; };   // pack (+ tile maximum), neighbour maximum, gather: one argument block
     static int mblur_plan(const StMotionBlurDesc& d, uint32_t w, uint32_t h, MBlurPlan& plan);   // checks the desc
-    static MBlurSteps mblur_steps(const StMotionBlurDesc& d, const MBlurPlan& plan, const void* color, const void* velocity, const void* depth, bool frame, uint32_t w, uint32_t h,
-                                  float2* packed, float4* tile_max, float4* tile_n, void* dst, uint32_t format, bool raw, const DisplayArgs& display);
+    static void mblur_steps(const StMotionBlurDesc& d, const MBlurPlan& plan, const NodeSource& src, float2* packed, float4* tile_max, float4* tile_n, const NodeTarget& target, MBlurSteps& out);
     int set_motion_blur(CameraState& c, const StMotionBlurDesc* desc);
-    void launch_mblur_step(const MBlurStep& s, hipStream_t stream);
+    void launch_mblur_step(const MBlurSteps& s, uint32_t i, hipStream_t stream);
     int motion_blur_process(const StMotionBlurDesc* desc, const StDisplayDesc* display, const void* color, const void* velocity, const void* depth, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
     FencedPlanes<3> mblur_scratch;   // st_motion_blur_process's packed plane and tile vectors: grown, never shrunk
     // ---- depth of field (st_dof.cpp)
     struct DofPlan { uint32_t samples = 0, tiles_x = 0, tiles_y = 0; size_t packed_bytes = 0, tile_bytes = 0; float max_radius = 0.0f; float taps[kDofMaxSamples * 3u] = {}; };
-    struct DofStep { int slot; double bytes; };
-    struct DofSteps { DofArgs args; DofStep step[3]; };   // pack (+ tile maximum), neighbour maximum, gather: one argument block
+    struct DofSteps { DofArgs args; OutputStep step[3]; };   // pack (+ tile maximum), neighbour maximum, gather: one argument block
     static int dof_plan(const StDofDesc& d, uint32_t w, uint32_t h, DofPlan& plan);   // checks the desc
-    static int dof_steps(const StDofDesc& d, const DofPlan& plan, const float projection[16], const void* color, const void* depth, bool frame, uint32_t w, uint32_t h,
-                         float2* packed, float* tile_max, float* tile_n, void* dst, uint32_t format, bool raw, const DisplayArgs& display, DofSteps& out);
+    static void dof_steps(const StDofDesc& d, const DofPlan& plan, const float projection[16], const NodeSource& src, float2* packed, float* tile_max, float* tile_n, const NodeTarget& target, DofSteps& out);
     int set_dof(CameraState& c, const StDofDesc* desc);
     void launch_dof_step(const DofSteps& s, uint32_t i, hipStream_t stream);
     int dof_process(const StDofDesc* desc, const StDisplayDesc* display, const float* projection, const void* color, const void* depth, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
     FencedPlanes<3> dof_scratch;   // st_dof_process's packed plane and tile values: grown, never shrunk
     // ---- fog (st_fog.cpp)
-    struct FogStep { FogArgs args; int slot; double bytes; };
-    static void fog_step(const StFogDesc& d, const float transform[16], const float projection[16], const float sun[3], const void* color, const void* depth, bool frame,
-                         uint32_t w, uint32_t h, uint32_t row0, uint32_t row1, uint32_t col0, uint32_t col1, void* dst, uint32_t format, bool raw, const DisplayArgs& display, FogStep& out);
+    struct FogStep { FogArgs args; OutputStep step; };
+    static void fog_step(const StFogDesc& d, const NodeView& view, const NodeSource& src, uint32_t row0, uint32_t row1, uint32_t col0, uint32_t col1, const NodeTarget& target, FogStep& out);
     int set_fog(CameraState& c, const StFogDesc* desc);
     int fog_process(const StFogDesc* desc, const StDisplayDesc* display, const float* transform, const float* projection, const void* color, const void* depth,
                     uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
     // ---- light shafts (st_shafts.cpp)
     struct ShaftsPlan { uint32_t cells_w = 0, cells_h = 0; size_t cell_bytes = 0; float jitter[16] = {}; };
-    struct ShaftsSteps { ShaftsArgs args; struct { int slot; double bytes; } step[2]; };   // march, apply
+    struct ShaftsSteps { ShaftsArgs args; OutputStep step[2]; };   // march, apply
     static int shafts_plan(const StLightShaftsDesc& d, uint32_t w, uint32_t h, ShaftsPlan& out);
-    void shafts_steps(const StLightShaftsDesc& d, const ShaftsPlan& plan, const float transform[16], const float projection[16], const float sun[3], const void* color, const void* depth,
-                      bool frame, uint32_t w, uint32_t h, float4* cells, void* dst, uint32_t format, bool raw, const DisplayArgs& display, bool count, ShaftsSteps& out) const;
+    void shafts_steps(const StLightShaftsDesc& d, const ShaftsPlan& plan, const NodeView& view, const NodeSource& src, float4* cells, const NodeTarget& target, bool count, ShaftsSteps& out) const;
     void launch_shafts_step(const KArgs& scene, const ShaftsSteps& s, uint32_t i, hipStream_t stream);
     int set_shafts(CameraState& c, const StLightShaftsDesc* desc);
     int shafts_process(const StLightShaftsDesc* desc, const StDisplayDesc* display, const float* transform, const float* projection, const void* color, const void* depth,

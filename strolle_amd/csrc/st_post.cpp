@@ -1,6 +1,6 @@
 // st_post.cpp — output post-processing (include/strolle_hip.h "post-processing"): the setter's checks, the plan of at most two launches
 // (k_post.hip: FXAA, then the resampler, which also writes the output format) that st_render_camera and st_post_process share. The planes
-// between them: st_engine.h CameraState::post_planes, Engine::post_scratch.
+// between them: st_engine.h CameraState::post, Engine::post_scratch.
 #include <cmath>
 
 #include "st_engine.h"
@@ -8,7 +8,6 @@
 namespace st {
 
 static_assert(KS_COUNT <= ST_PROFILE_MAX_KERNELS, "st_profile_read's callers size their arrays with ST_PROFILE_MAX_KERNELS");
-static constexpr uint32_t kPostMaxSide = 16384u;
 static constexpr float kFxaaEdgeThreshold = 0.166f, kFxaaEdgeThresholdMin = 0.0833f;
 
 static int check_post(const StPostDesc& d) {
@@ -16,7 +15,7 @@ static int check_post(const StPostDesc& d) {
     if ((d.flags & ~(uint32_t)ST_POST_FXAA) != 0u) return fail(ST_ERR_INVALID_ARGUMENT, "unknown post-processing flag bits");
     if (d.filter > ST_RESAMPLE_CATMULL_ROM) return fail(ST_ERR_INVALID_ARGUMENT, "unknown resampling filter");
     if ((d.output_width == 0u) != (d.output_height == 0u)) return fail(ST_ERR_INVALID_ARGUMENT, "output_width and output_height are both 0 (the render size) or both set");
-    if (d.output_width > kPostMaxSide || d.output_height > kPostMaxSide) return fail(ST_ERR_INVALID_ARGUMENT, "an output side above 16384");
+    if (d.output_width > kMaxImageSide || d.output_height > kMaxImageSide) return fail(ST_ERR_INVALID_ARGUMENT, "an output side above 16384");
     for (float v : {d.fxaa_edge_threshold, d.fxaa_edge_threshold_min})
         if (!std::isfinite(v) || v < 0.0f) return fail(ST_ERR_INVALID_ARGUMENT, "an FXAA threshold is negative or not finite");
     if (!(d.fxaa_subpixel >= 0.0f && d.fxaa_subpixel <= 1.0f)) return fail(ST_ERR_INVALID_ARGUMENT, "fxaa_subpixel is outside [0, 1]");
@@ -24,11 +23,7 @@ static int check_post(const StPostDesc& d) {
 }
 
 int Engine::set_post(CameraState& c, const StPostDesc* desc) {
-    if (!desc) { c.post_on = false; return ST_OK; }
-    if (int rc = check_post(*desc)) return rc;
-    if (c.windowed()) return fail(ST_ERR_INVALID_ARGUMENT, "post-processing on a camera with a window: FXAA and the resampler read across tile edges (include/strolle_hip.h \"post-processing\")");
-    c.post = *desc; c.post_on = true;
-    return ST_OK;
+    return set_node(c.windowed(), c.post, desc, check_post);
 }
 
 // FXAA (when `fxaa`) over src, then the resampler when the sizes differ — or when nothing else would write dst. FXAA alone writes dst in
@@ -55,7 +50,7 @@ Engine::PostPlan Engine::post_plan(const StPostDesc& d, bool fxaa, const void* s
 int Engine::post_process(const StPostDesc* desc, const void* src, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream) {
     if (!desc || !src || !dst) return fail(ST_ERR_INVALID_ARGUMENT, "null argument");
     if (int rc = check_post(*desc)) return rc;
-    if (w == 0u || h == 0u || w > kPostMaxSide || h > kPostMaxSide) return fail(ST_ERR_INVALID_ARGUMENT, "the image's sides must be in 1..16384");
+    if (w == 0u || h == 0u || w > kMaxImageSide || h > kMaxImageSide) return fail(ST_ERR_INVALID_ARGUMENT, "the image's sides must be in 1..16384");
     if (format < ST_FORMAT_RGBA32F || format > ST_FORMAT_BGRA8_UNORM_SRGB) return fail(ST_ERR_INVALID_ARGUMENT, "unknown output format");
     if (!has_device) return fail(ST_ERR_NO_DEVICE, "st_post_process on a host-only engine");
     ST_HIP(hipSetDevice(device));

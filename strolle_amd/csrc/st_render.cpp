@@ -162,30 +162,46 @@ int Engine::reader_end(hipStream_t stream, bool lights, bool reads_previous) {
 }
 
 // ---- render (camera_controller.rs:87-174). Engine::render, at the end of this file, is a short sequence of phases over one Frame:
-// route_output, bind_args, refresh_inputs, decide_switches, one of the two schedules (two_streams, serial), finish_output.
+// route_output, bind_args, refresh_inputs, decide_switches, arm_output, one of the two schedules (two_streams, serial), finish_output.
 namespace {
-// The frame's output chain, decided once. Output post-processing (st_post.cpp): while the frame needs it, the composing launch writes the
-// camera's own render-size RGBA32F plane instead of `out`, and the post launches write `out` behind it. Bloom (st_bloom.cpp): while the frame
-// blooms, the composing launch writes the composed colour untransformed (and still meters it) into the camera's HDR plane; the bloom launches
-// behind it end in the composite, which runs the display transform and writes what the composing launch would have written. Motion blur
-// (st_motion_blur.cpp) sits in front of bloom in the same way: the composing launch writes the blur's HDR plane, and the gather writes bloom's
-// HDR plane (untransformed) or, without bloom, what the composing launch would have written. Depth of field (st_dof.cpp) sits in front of
-// motion blur: the composing launch writes its HDR plane, and its gather writes the HDR plane of the next node that is on (motion blur's, else
-// bloom's), or what the composing launch would have written. Fog (st_fog.cpp) is the first node, light shafts (st_shafts.cpp) the second, in
-// front of depth of field. The five HDR nodes form an ordered list: the composing launch writes the plane of the first node that is on, and each node writes the plane of the next
-// one that is on (`node_dst`), the last one what the composing launch would have written.
-enum HdrNode { kNodeFog, kNodeShafts, kNodeDof, kNodeMBlur, kNodeBloom, kHdrNodes };
+// ---- the node table: everything the frame knows about the single nodes is between here and "end of the node table" (and in Frame's
+// node_* functions, which switch on the node). A new node: an HdrNode in chain order, a row here, its plan and steps in HdrWork, a case in each node_* function.
+// early: its first `early` launches run in front of the ev_prim_ok record (pack_early): they read planes the NEXT frame's primary visibility
+//        overwrites. Depth of field's pack reads this frame's G-buffer depth; motion blur's the velocity map (single-buffered) and the depth.
+// reads_depth: its launches in finish_output read the G-buffer depth of the frame's parity, which the frame after next rewrites: the camera's
+//        gbuffer_depth_read fence is recorded once, behind the last such node that is on, and prim() of that parity waits for it.
+// reads_velocity: the lean frame keeps the velocity map for it (kLeanKeepVelocity).
+enum HdrNode { kNodeFog, kNodeShafts, kNodeDof, kNodeMBlur, kNodeBloom, kHdrNodes };   // chain order
+struct HdrNodeRow { uint32_t early; bool reads_depth, reads_velocity; };
+constexpr HdrNodeRow kHdrNode[kHdrNodes] = {
+    /* fog (st_fog.cpp): one launch; pointwise, so windows are honoured */       {0u, true, false},
+    /* light shafts (st_shafts.cpp): march, apply */                              {0u, true, false},
+    /* depth of field (st_dof.cpp): pack | neighbour maximum, gather */           {1u, false, false},
+    /* motion blur (st_motion_blur.cpp): pack | neighbour maximum, gather */      {1u, false, true},
+    /* bloom (st_bloom.cpp): the pyramid's chain, the composite */                {0u, false, false},
+};
+struct HdrWork {   // what the nodes that are on hold for one frame: node_plan's plans, node_arm's argument blocks and steps
+    Engine::ShaftsPlan shafts_plan; Engine::DofPlan dof_plan; Engine::MBlurPlan mblur_plan; Engine::BloomPlan bloom_plan;
+    Engine::FogStep fog; Engine::ShaftsSteps shafts; Engine::DofSteps dof; Engine::MBlurSteps mblur; Engine::BloomSteps bloom;
+};
+// ---- end of the node table
+// The frame's output chain, decided once. Output post-processing (st_post.cpp): while the frame needs it, the frame's target is the camera's
+// own render-size RGBA32F plane instead of `out`, and the post launches write `out` behind it. In front of it the HDR nodes (the node table,
+// above) form an ordered list: the composing launch writes the plane of the first node that is on — the composed colour untransformed, and
+// still metered —, each node writes the plane of the next one that is on, and the last one what the composing launch would have written:
+// the frame's target, in its format, through the display transform (`target`).
 struct OutputRoute {
-    bool post_fxaa = false, post = false, bloom = false, mblur = false, dof = false, fog = false, shafts = false;
-    Engine::BloomPlan bloom_plan; Engine::MBlurPlan mblur_plan; Engine::DofPlan dof_plan; Engine::ShaftsPlan shafts_plan;
-    void* hdr_plane[kHdrNodes] = {};   // the render-size RGBA32F plane each node that is on reads, in chain order
-    // where node `n` writes (n = -1: the composing launch): the next node's plane, raw (RGBA32F, untransformed), or the frame's target
-    void* node_dst(int n, bool* raw) const {
-        for (int k = n + 1; k < kHdrNodes; k++) if (hdr_plane[k]) { *raw = true; return hdr_plane[k]; }
-        *raw = false; return frame_out;
+    bool post_fxaa = false, post = false, keep_velocity = false /* a node that is on reads the velocity map */;
+    void* hdr_plane[kHdrNodes] = {};   // the render-size RGBA32F plane each node that is on reads, in chain order; null: the node is off
+    Fence* planes_read[kHdrNodes] = {};   // ... and the fence of the node's planes
+    bool on(int n) const { return hdr_plane[n] != nullptr; }
+    // where node `n` writes (n = -1: the composing launch): the next node's plane, raw, or the frame's target
+    NodeTarget target(int n) const {
+        for (int k = n + 1; k < kHdrNodes; k++) if (hdr_plane[k]) return {hdr_plane[k], frame_format, true, frame_disp};
+        return {frame_out, frame_format, false, frame_disp};
     }
     void* comp_out = nullptr; uint32_t comp_format = 0; DisplayArgs comp_disp{};      // the composing launch (either of the two): target, format, display transform
-    void* frame_out = nullptr; uint32_t frame_format = 0; DisplayArgs frame_disp{};   // the bloom composite: `out` or the post plane; no display: NONE at scale 1, which stores the colour's own bits
+    void* frame_out = nullptr; uint32_t frame_format = 0; DisplayArgs frame_disp{};   // the frame's target: `out` or the post plane; no display: NONE at scale 1, which stores the colour's own bits
 };
 // Every per-frame decision, made once (decide_switches); the stages only read them.
 struct FrameSwitches {
@@ -197,7 +213,7 @@ struct FrameSwitches {
 // visibility and the GI chain to the camera's side stream); the rest below `s` is launch bookkeeping.
 struct Frame {
     Engine& e; CameraState& c; void* const out; const hipStream_t stream; hipStream_t cur;
-    KArgs a{}; OutputRoute route; FrameSwitches s{}; Engine::MBlurSteps blur{}; Engine::DofSteps dof{}; Engine::FogStep fog{}; Engine::ShaftsSteps shafts{};
+    KArgs a{}; OutputRoute route; FrameSwitches s{}; HdrWork work;
     const uint32_t mode, pseed;   // pseed: one seed for both preview passes (passes/gi_preview_resampling.rs:60-74)
     bool mask_split = false, di_reprojected = false, gi_reprojected = false, composed = false, luts_generated_now = false; uint32_t launch_ordinal = 0u;
     Frame(Engine& e_, CameraState& c_, void* out_, hipStream_t s_) : e(e_), c(c_), out(out_), stream(s_), cur(s_), mode(c_.desc.mode), pseed(pass_seed(e_.base_seed, c_.frame, SEED_GI_PREVIEW)) {}
@@ -209,7 +225,7 @@ struct Frame {
         return (double)(c.row1 - c.row0) * (ki.half ? (double)(((cols + 7u) / 8u / 2u) * 8u) : (double)cols) * ki.bytes_per_unit;
     }
     // `bits`: the reference passes this launch executes (StPassBit). Their unfused algorithmic bytes are what kernel_info(slot) credits to the
-    // launch, so fusion shows up as a gain, not as a moved goalpost. `own_bytes`: the post and bloom launches' bytes depend on the
+    // launch, so fusion shows up as a gain, not as a moved goalpost. `own_bytes`: the bytes of the output chain's launches depend on the
     // output size and format, so those launches state them.
     template <class F> void run(int slot, uint64_t bits, F&& launch, double own_bytes = -1.0) {
         if (e.last_launches.empty() || e.last_launches.back() != bits) e.last_launches.push_back(bits);  // a launch group is reported once
@@ -230,6 +246,83 @@ struct Frame {
         e.profile_begin(e.profile_group_atrous && atrous ? (int)KS_DENOISE_WAVELET_FAMILY : slot, cur, bytes);
         launch();
     }
+    // ---- the node table's functions (one case per node; the rest of the frame sees nodes by index only)
+    // whether the camera wants the node this frame. Heatmap frames are false colour; heatmap and reference frames have no G-buffer and no
+    // velocity map; fog, shafts and depth of field derive the pixel's ray or the focal length from a perspective projection
+    bool node_wanted(int n) const {
+        const bool perspective = c.has_gbuffer() && dof_perspective(c.desc.projection);
+        switch (n) {
+        case kNodeFog: return c.fog.on && perspective;
+        case kNodeShafts: return c.shafts.on && perspective;
+        case kNodeDof: return c.dof.on && perspective;
+        case kNodeMBlur: return c.mblur.on && c.has_gbuffer();
+        default: return c.bloom.on && c.desc.mode != ST_MODE_BVH_HEATMAP;
+        }
+    }
+    // the node's plan and its planes ([0]: the HDR plane; grown, never shrunk: a size that goes down and up again between frames costs no sync
+    // and no allocation), `stream` ordered behind their last readers. The node is on when this leaves its HDR plane in the route.
+    template <int N> int node_planes(int n, FencedPlanes<N>& p, const size_t (&bytes)[N]) {
+        if (int rc = p.acquire(bytes, p.Grow, stream)) return rc;
+        route.hdr_plane[n] = p.plane[0].ptr; route.planes_read[n] = &p.read;
+        return ST_OK;
+    }
+    int node_plan(int n) {
+        const uint32_t w = c.desc.width, h = c.desc.height;
+        const size_t plane = (size_t)w * h * sizeof(float4);
+        switch (n) {
+        case kNodeFog: return node_planes(n, c.fog.planes, {plane});
+        case kNodeShafts:
+            if (int rc = Engine::shafts_plan(c.shafts.desc, w, h, work.shafts_plan)) return rc;
+            return node_planes(n, c.shafts.planes, {plane, work.shafts_plan.cell_bytes});
+        case kNodeDof:
+            if (int rc = Engine::dof_plan(c.dof.desc, w, h, work.dof_plan)) return rc;
+            return node_planes(n, c.dof.planes, {plane, work.dof_plan.packed_bytes, work.dof_plan.tile_bytes, work.dof_plan.tile_bytes});
+        case kNodeMBlur:
+            if (int rc = Engine::mblur_plan(c.mblur.desc, w, h, work.mblur_plan)) return rc;
+            return node_planes(n, c.mblur.planes, {plane, work.mblur_plan.packed_bytes, work.mblur_plan.tile_bytes, work.mblur_plan.tile_bytes});
+        default:
+            if (int rc = Engine::bloom_plan(c.bloom.desc, w, h, work.bloom_plan)) return rc;
+            if (work.bloom_plan.levels == 0u) return ST_OK;   // the frame holds no level: off
+            return node_planes(n, c.bloom.planes, {plane, work.bloom_plan.texels * sizeof(float4)});
+        }
+    }
+    // the node's argument blocks and steps: from its HDR plane, this frame's G-buffer depth (and velocity map) into `t`
+    void node_arm(int n, const NodeTarget& t) {
+        const NodeSource src{route.hdr_plane[n], a.g0, a.velocity, true, c.desc.width, c.desc.height};
+        const float sun[3] = {e.sun_dir_.x, e.sun_dir_.y, e.sun_dir_.z};   // as KArgs::sun_dir carries it (light_args)
+        const NodeView view{c.desc.transform, c.desc.projection, sun};
+        switch (n) {
+        case kNodeFog: Engine::fog_step(c.fog.desc, view, src, c.row0, c.row1, c.col0, c.col1, t, work.fog); break;
+        case kNodeShafts: e.shafts_steps(c.shafts.desc, work.shafts_plan, view, src, c.shafts.planes.plane[1].as<float4>(), t, true, work.shafts); break;
+        case kNodeDof: { const auto& p = c.dof.planes.plane; Engine::dof_steps(c.dof.desc, work.dof_plan, c.desc.projection, src, p[1].as<float2>(), p[2].as<float>(), p[3].as<float>(), t, work.dof); break; }
+        case kNodeMBlur: { const auto& p = c.mblur.planes.plane; Engine::mblur_steps(c.mblur.desc, work.mblur_plan, src, p[1].as<float2>(), p[2].as<float4>(), p[3].as<float4>(), t, work.mblur); break; }
+        default: work.bloom = Engine::bloom_steps(c.bloom.desc, work.bloom_plan, src.color, src.w, src.h, c.bloom.planes.plane[1].as<float4>(), t, e.bloom_tail_bytes()); break;
+        }
+    }
+    uint32_t node_steps(int n) const { return n == kNodeFog ? 1u : n == kNodeShafts ? 2u : n == kNodeBloom ? work.bloom.count : 3u; }
+    const OutputStep& node_step(int n, uint32_t i) const {
+        switch (n) {
+        case kNodeFog: return work.fog.step;
+        case kNodeShafts: return work.shafts.step[i];
+        case kNodeDof: return work.dof.step[i];
+        case kNodeMBlur: return work.mblur.step[i];
+        default: return work.bloom.step[i].step;
+        }
+    }
+    void node_launch(int n, uint32_t i) {
+        switch (n) {
+        case kNodeFog: e.L.launch_fog(work.fog.args, cur); break;
+        case kNodeShafts: e.launch_shafts_step(a, work.shafts, i, cur); break;   // the march reads the live scene copy and the light table too
+        case kNodeDof: e.launch_dof_step(work.dof, i, cur); break;
+        case kNodeMBlur: e.launch_mblur_step(work.mblur, i, cur); break;
+        default: e.launch_bloom_step(work.bloom.step[i], cur); break;
+        }
+    }
+    // ---- end of the node table's functions
+    // launches [first, last) of node `n`, in the frame's one launch group behind the composing launch (ST_PASS_POST)
+    void run_node(int n, uint32_t first, uint32_t last) {
+        for (uint32_t i = first; i < last; i++) { const OutputStep& st = node_step(n, i); run(st.slot, ST_PASS_POST, [&] { node_launch(n, i); }, st.bytes); }
+    }
     // ---- phases
     int route_output() {
         OutputRoute& r = route;
@@ -238,41 +331,14 @@ struct Frame {
         const size_t plane = (size_t)c.desc.width * c.desc.height * sizeof(float4);
         const bool post_resample = out && c.post_resizes();
         r.post_fxaa = out && c.post_fxaa(); r.post = r.post_fxaa || post_resample;
-        if (r.post) if (int rc = c.post_planes.acquire({plane, r.post_fxaa && post_resample ? plane : 0}, c.post_planes.Exact, stream)) return rc;
-        if (out && c.blooms()) {
-            if (int rc = Engine::bloom_plan(c.bloom, c.desc.width, c.desc.height, r.bloom_plan)) return rc;
-            r.bloom = r.bloom_plan.levels != 0u;
-        }
-        // grown, never shrunk: a level count that goes down and up again between frames costs no sync and no allocation
-        if (r.bloom) if (int rc = c.bloom_planes.acquire({plane, r.bloom_plan.texels * sizeof(float4)}, c.bloom_planes.Grow, stream)) return rc;
-        if (out && c.blurs()) {
-            if (int rc = Engine::mblur_plan(c.mblur, c.desc.width, c.desc.height, r.mblur_plan)) return rc;
-            r.mblur = true;
-            if (int rc = c.mblur_planes.acquire({plane, r.mblur_plan.packed_bytes, r.mblur_plan.tile_bytes, r.mblur_plan.tile_bytes}, c.mblur_planes.Grow, stream)) return rc;
-        }
-        if (out && c.focuses()) {
-            if (int rc = Engine::dof_plan(c.dof, c.desc.width, c.desc.height, r.dof_plan)) return rc;
-            r.dof = true;
-            if (int rc = c.dof_planes.acquire({plane, r.dof_plan.packed_bytes, r.dof_plan.tile_bytes, r.dof_plan.tile_bytes}, c.dof_planes.Grow, stream)) return rc;
-        }
-        if (out && c.fogs()) {
-            r.fog = true;
-            if (int rc = c.fog_planes.acquire({plane}, c.fog_planes.Grow, stream)) return rc;
-        }
-        if (out && c.shafted()) {
-            if (int rc = Engine::shafts_plan(c.shafts, c.desc.width, c.desc.height, r.shafts_plan)) return rc;
-            r.shafts = true;
-            if (int rc = c.shafts_planes.acquire({plane, r.shafts_plan.cell_bytes}, c.shafts_planes.Grow, stream)) return rc;
-        }
-        if (r.fog) r.hdr_plane[kNodeFog] = c.fog_planes.plane[0].ptr;
-        if (r.shafts) r.hdr_plane[kNodeShafts] = c.shafts_planes.plane[0].ptr;
-        if (r.dof) r.hdr_plane[kNodeDof] = c.dof_planes.plane[0].ptr;
-        if (r.mblur) r.hdr_plane[kNodeMBlur] = c.mblur_planes.plane[0].ptr;
-        if (r.bloom) r.hdr_plane[kNodeBloom] = c.bloom_planes.plane[0].ptr;
-        r.frame_out = r.post ? c.post_planes.plane[0].ptr : out; r.frame_format = r.post ? (uint32_t)ST_FORMAT_RGBA32F : c.out_format;
+        if (r.post) if (int rc = c.post.planes.acquire({plane, r.post_fxaa && post_resample ? plane : 0}, c.post.planes.Exact, stream)) return rc;
+        for (int n = 0; n < kHdrNodes; n++) if (out && node_wanted(n)) if (int rc = node_plan(n)) return rc;
+        for (int n = 0; n < kHdrNodes; n++) r.keep_velocity |= r.on(n) && kHdrNode[n].reads_velocity;
+        r.frame_out = r.post ? c.post.planes.plane[0].ptr : out; r.frame_format = r.post ? (uint32_t)ST_FORMAT_RGBA32F : c.out_format;
         r.frame_disp = disp; if (!r.frame_disp.on) r.frame_disp.scale = 1.0f;
-        bool hdr_chain = false;   // the composing launch feeds an HDR node: it stores the composed colour as it is
-        r.comp_out = r.node_dst(-1, &hdr_chain); r.comp_format = hdr_chain ? (uint32_t)ST_FORMAT_RGBA32F : r.frame_format;
+        const NodeTarget comp = r.target(-1);
+        const bool hdr_chain = comp.raw;   // the composing launch feeds an HDR node: it stores the composed colour as it is
+        r.comp_out = comp.dst; r.comp_format = hdr_chain ? (uint32_t)ST_FORMAT_RGBA32F : r.frame_format;
         if (hdr_chain) { if (disp.meter) disp.tonemap = kDisplayRaw; else disp = DisplayArgs{}; }   // the composing launch: meter, do not transform
         r.comp_disp = disp;
         return ST_OK;
@@ -346,7 +412,7 @@ struct Frame {
             // cell's other pixel, the one it resamples, lies past the edge — as it leaves the dropped tile column alone when the tile count is odd)
             if (t.fuse_gi_reprojection && s.tracing && s.even_tiles && (c.frame % 2u == 0u || a.width % 2u == 0u)) s.lean |= kLeanGiRes2;
             if (s.gi_preview_both) s.lean |= kLeanGiMid;
-            if (route.mblur) s.lean |= kLeanKeepVelocity;   // the pack launch reads the velocity map
+            if (route.keep_velocity) s.lean |= kLeanKeepVelocity;   // a pack launch reads the velocity map
         }
         // frame composition rides in the last a-trous pass (k_denoise.hip k_denoise_wavelet_far<true>). (Fast build, Image mode and an output buffer.)
         s.compose_in_wavelet = t.fuse_compose && fast && fused_denoised && out != nullptr && mode == ST_MODE_IMAGE;
@@ -361,32 +427,12 @@ struct Frame {
         // per-kernel profiling runs the graph serially on `stream`: a launch's event pair then times that kernel alone, not the kernels of the other stream it would share the chip with
         s.two_streams = t.overlap && !e.profiling && e.launch_filter == ~0ull && s.needs_di && s.needs_gi && s.any_objects;
         a.gi_skip_history_copy = s.gi_skip_history_copy; a.variance_in_reproject = s.variance_in_reproject; a.lean = s.lean; a.skip_dead_scratch = s.skip_dead_scratch;
-        if (route.mblur) {   // the blur's three launches (blur_pack, finish_output): into bloom's HDR plane, untransformed, when the frame blooms
-            const FencedPlanes<4>& p = c.mblur_planes;
-            bool raw = false; void* dst = route.node_dst(kNodeMBlur, &raw);
-            blur = Engine::mblur_steps(c.mblur, route.mblur_plan, p.plane[0].ptr, a.velocity, a.g0, true, c.desc.width, c.desc.height, p.plane[1].as<float2>(), p.plane[2].as<float4>(),
-                                       p.plane[3].as<float4>(), dst, route.frame_format, raw, route.frame_disp);
-        }
-        if (route.dof) {   // depth of field's three launches (dof_pack, finish_output): into the next HDR node's plane, untransformed, when there is one
-            const FencedPlanes<4>& p = c.dof_planes;
-            bool raw = false; void* dst = route.node_dst(kNodeDof, &raw);
-            if (int rc = Engine::dof_steps(c.dof, route.dof_plan, c.desc.projection, p.plane[0].ptr, a.g0, true, c.desc.width, c.desc.height, p.plane[1].as<float2>(), p.plane[2].as<float>(),
-                                           p.plane[3].as<float>(), dst, route.frame_format, raw, route.frame_disp, dof)) return rc;
-        }
-        if (route.fog) {   // fog's one launch (finish_output): into the next HDR node's plane, untransformed, when there is one. Windows are honoured.
-            bool raw = false; void* dst = route.node_dst(kNodeFog, &raw);
-            const float sun[3] = {e.sun_dir_.x, e.sun_dir_.y, e.sun_dir_.z};   // as KArgs::sun_dir carries it (light_args)
-            Engine::fog_step(c.fog, c.desc.transform, c.desc.projection, sun, c.fog_planes.plane[0].ptr, a.g0, true, c.desc.width, c.desc.height, c.row0, c.row1, c.col0, c.col1,
-                             dst, route.frame_format, raw, route.frame_disp, fog);
-        }
-        if (route.shafts) {   // the shafts' two launches (finish_output): into the next HDR node's plane, untransformed, when there is one
-            bool raw = false; void* dst = route.node_dst(kNodeShafts, &raw);
-            const float sun[3] = {e.sun_dir_.x, e.sun_dir_.y, e.sun_dir_.z};
-            e.shafts_steps(c.shafts, route.shafts_plan, c.desc.transform, c.desc.projection, sun, c.shafts_planes.plane[0].ptr, a.g0, true, c.desc.width, c.desc.height,
-                           c.shafts_planes.plane[1].as<float4>(), dst, route.frame_format, raw, route.frame_disp, true, shafts);
-        }
         c.last_lean = s.lean; c.last_lean_composed = s.compose_in_wavelet && s.lean != 0u;   // which planes the frame leaves unwritten: the last a-trous pass's colour planes too
         return ST_OK;
+    }
+    // every node that is on gets its argument blocks and steps against where it writes this frame (OutputRoute::target); KArgs is bound by now
+    void arm_output() {
+        for (int n = 0; n < kHdrNodes; n++) if (route.on(n)) node_arm(n, route.target(n));
     }
     // decoded-surface twins and atmosphere LUTs, on `stream`: ordered before the side stream by ev_setup (two_streams)
     void refresh_inputs() {
@@ -415,8 +461,8 @@ struct Frame {
         run(KS_REF_SHADING, ST_PASS_REF_SHADING, [&] { e.L.launch_ref_shading(a, seed(SEED_REF_SHADING + 255u), 255u, cur); });
     }
     void prim() {
-        // the fog and light-shafts launches of the frame before last read the G-buffer this launch rewrites, behind that frame's composing launch (DESIGN.md "Fog", "Light shafts")
-        (void)c.fog_depth_read[c.frame % 2u].wait(cur, Fence::OtherStreams, Fence::Clear);
+        // output-chain launches of the frame before last read the G-buffer this launch rewrites, behind that frame's composing launch (the node table's reads_depth)
+        (void)c.gbuffer_depth_read[c.frame % 2u].wait(cur, Fence::OtherStreams, Fence::Clear);
         if (e.tuning.fuse && s.any_objects) run(KS_PRIM_VISIBILITY_REPROJECTION, ST_PASS_PRIM_VISIBILITY | ST_PASS_FRAME_REPROJECTION, [&] { e.L.launch_prim_visibility(a, true, e.deform.deform_table(), e.deform.deform_posed(), cur); });
         else run(KS_PRIM_VISIBILITY, ST_PASS_PRIM_VISIBILITY, [&] { e.L.launch_prim_visibility(a, false, e.deform.deform_table(), e.deform.deform_posed(), cur); });
         if (s.any_objects && !e.tuning.fuse) run(KS_FRAME_REPROJECTION, ST_PASS_FRAME_REPROJECTION, [&] { e.L.launch_frame_reprojection(a, cur); });
@@ -524,17 +570,10 @@ struct Frame {
             run(KS_DENOISE_WAVELET, (uint64_t)ST_PASS_DENOISE_WAVELET_0 << nth, [&] { e.L.launch_denoise_wavelet(a, 1u << nth, (float)(1u + nth), di[in_ix[nth]], di[out_ix[nth]], gi[in_ix[nth]], gi[out_ix[nth]], cur); });
         }
     }
-    // Motion blur's pack launch: it reads this frame's velocity map and G-buffer, which the NEXT frame's primary visibility overwrites (the
-    // velocity map is single-buffered), so it runs on `stream` before that may start; what it writes is the camera's own.
-    void blur_pack() {
-        if (!route.mblur) return;
-        run(blur.step[0].slot, ST_PASS_POST, [&] { e.launch_mblur_step(blur.step[0], cur); }, blur.step[0].bytes);
-    }
-    // Depth of field's pack launch: it reads this frame's G-buffer depth; the frame after next rewrites that plane, and packing here keeps
-    // every reader of the G-buffer in front of the ev_prim_ok record, like blur_pack.
-    void dof_pack() {
-        if (!route.dof) return;
-        run(dof.step[0].slot, ST_PASS_POST, [&] { e.launch_dof_step(dof, 0u, cur); }, dof.step[0].bytes);
+    // The nodes' early launches (the node table's `early`), in chain order: they read this frame's planes that the NEXT frame's primary
+    // visibility overwrites, so they run on `stream` before that may start; what they write is the camera's own.
+    void pack_early() {
+        for (int n = 0; n < kHdrNodes; n++) if (route.on(n)) run_node(n, 0u, kHdrNode[n].early);
     }
     void compose() {   // every mode's composition, unless the last a-trous pass did it
         if (!out || composed) return;
@@ -582,7 +621,7 @@ struct Frame {
         if (int rc = c.ev_di_head.wait(stream)) return rc;
         if (t.di_head_on_main) di_head();
         di_tail();
-        dof_pack(); blur_pack();   // before ev_prim_ok: prim(N+1) rewrites the velocity map
+        pack_early();   // before ev_prim_ok: prim(N+1) rewrites the velocity map
         // stand-alone denoise reprojection kernels (unfused path) still read the reprojection map: prim(N+1) may only start once they are through
         const bool reproject_later = s.denoise && !t.fuse;
         if (!reproject_later) { if (int rc = c.ev_prim_ok.record(stream)) return rc; }
@@ -602,46 +641,31 @@ struct Frame {
             if (s.needs_di) { di_head(); di_tail(); }
             if (s.needs_gi) { gi_head(); gi_tail(); }
         }
-        dof_pack(); blur_pack();
+        pack_early();
         denoise();
         compose();
         // (a camera that has run the two-stream schedule: its next such frame waits for these)
         if (c.side_stream) { if (int rc = c.ev_prim_ok.record(stream)) return rc; if (int rc = c.ev_frame_done.record(stream)) return rc; }
         return ST_OK;
     }
-    // The launches behind the composing launch, which ran on `stream`: fog, light shafts, depth of field, motion blur, bloom, then post-processing — one launch group (ST_PASS_POST) —, then the
-    // meter's finalize; each step's fence is recorded behind its launches.
+    // The launches behind the composing launch, which ran on `stream`: the rest of every HDR node that is on, in chain order, then
+    // post-processing — one launch group (ST_PASS_POST) —, then the meter's finalize; each stage's fence is recorded behind its launches, and the
+    // G-buffer depth's behind the last node that read it here.
     int finish_output() {
         cur = stream;
-        if (route.fog) {   // it reads the camera's HDR plane and this frame's G-buffer depth: the frame after next rewrites that plane, and its primary visibility waits for this
-            run(fog.slot, ST_PASS_POST, [&] { e.L.launch_fog(fog.args, cur); }, fog.bytes);
-            if (int rc = c.fog_planes.done(stream)) return rc;
-            if (!route.shafts) if (int rc = c.fog_depth_read[c.frame % 2u].record(stream)) return rc;
-        }
-        if (route.shafts) {   // the march reads this frame's G-buffer depth, the live scene copy and the light table; the apply launch the HDR plane, the depth and the cells
-            for (uint32_t i = 0; i < 2u; i++) run(shafts.step[i].slot, ST_PASS_POST, [&] { e.launch_shafts_step(a, shafts, i, cur); }, shafts.step[i].bytes);
-            if (int rc = c.shafts_planes.done(stream)) return rc;
-            if (int rc = c.fog_depth_read[c.frame % 2u].record(stream)) return rc;   // fog's fence, behind the last reader of the depth
-        }
-        if (route.dof) {   // depth of field's neighbour maximum and gather: they read the camera's packed plane, tile values and HDR plane only
-            for (uint32_t i = 1; i < 3u; i++) run(dof.step[i].slot, ST_PASS_POST, [&] { e.launch_dof_step(dof, i, cur); }, dof.step[i].bytes);
-            if (int rc = c.dof_planes.done(stream)) return rc;
-        }
-        if (route.mblur) {   // the neighbour maximum and the gather: they read the camera's packed plane, tile vectors and HDR plane only
-            for (uint32_t i = 1; i < 3u; i++) run(blur.step[i].slot, ST_PASS_POST, [&] { e.launch_mblur_step(blur.step[i], cur); }, blur.step[i].bytes);
-            if (int rc = c.mblur_planes.done(stream)) return rc;
-        }
-        if (route.bloom) {
-            const FencedPlanes<2>& p = c.bloom_planes;
-            const Engine::BloomSteps steps = Engine::bloom_steps(c.bloom, route.bloom_plan, p.plane[0].ptr, c.desc.width, c.desc.height, p.plane[1].as<float4>(), route.frame_out, route.frame_format, route.frame_disp, e.bloom_tail_bytes());
-            for (uint32_t i = 0; i < steps.count; i++) run(steps.step[i].slot, ST_PASS_POST, [&] { e.launch_bloom_step(steps.step[i], cur); }, steps.step[i].bytes);
-            if (int rc = c.bloom_planes.done(stream)) return rc;
+        int last_depth_reader = -1;
+        for (int n = 0; n < kHdrNodes; n++) if (route.on(n) && kHdrNode[n].reads_depth) last_depth_reader = n;
+        for (int n = 0; n < kHdrNodes; n++) {
+            if (!route.on(n)) continue;
+            run_node(n, kHdrNode[n].early, node_steps(n));
+            if (int rc = route.planes_read[n]->record(stream)) return rc;   // the planes' fence, behind the node's last launch
+            if (n == last_depth_reader) if (int rc = c.gbuffer_depth_read[c.frame % 2u].record(stream)) return rc;
         }
         if (route.post) {   // at most two kernels
-            const Engine::PostPlan plan = Engine::post_plan(c.post, route.post_fxaa, c.post_planes.plane[0].ptr, c.desc.width, c.desc.height, c.post_planes.plane[1].ptr, out, c.out_format);
+            const Engine::PostPlan plan = Engine::post_plan(c.post.desc, route.post_fxaa, c.post.planes.plane[0].ptr, c.desc.width, c.desc.height, c.post.planes.plane[1].ptr, out, c.out_format);
             if (plan.fxaa) run(KS_POST_FXAA, ST_PASS_POST, [&] { e.L.launch_post_fxaa(plan.fx, cur); }, plan.fxaa_bytes);
             if (plan.resample) run(KS_POST_RESAMPLE, ST_PASS_POST, [&] { e.L.launch_post_resample(plan.rs, cur); }, plan.resample_bytes);
-            if (int rc = c.post_planes.done(stream)) return rc;
+            if (int rc = c.post.planes.done(stream)) return rc;
         }
         if (route.comp_disp.meter && out) if (int rc = e.display_finalize(c, stream)) return rc;
         return ST_OK;
@@ -655,12 +679,13 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
     ST_HIP(hipSetDevice(device));
     if (int rc = reader_begin(stream, true)) return rc;
     Frame f(*this, c, out, stream);
-    if (int rc = f.route_output()) return rc;      // display, post-processing, bloom: where the composing launch writes
+    if (int rc = f.route_output()) return rc;      // display, post-processing, the HDR nodes that are on: where the composing launch and each node write
     if (int rc = f.bind_args()) return rc;         // KArgs: scene, lights, the camera's planes
     f.refresh_inputs();                            // what they name and this call has to make first: decoded-surface twins, atmosphere LUTs
     if (int rc = f.decide_switches()) return rc;   // which fused variants this frame takes, which schedule
+    f.arm_output();                                // the HDR nodes' argument blocks and steps
     if (int rc = f.s.two_streams ? f.two_streams() : f.serial()) return rc;
-    if (int rc = f.finish_output()) return rc;     // bloom, post-processing, the meter's finalize
+    if (int rc = f.finish_output()) return rc;     // the HDR nodes' launches behind the composing launch, post-processing, the meter's finalize
     if (int rc = reader_end(stream, true, true)) return rc;   // the end of the last frame that reads these copies of the scene and the lights
     profile_close();
     ST_HIP(hipGetLastError());

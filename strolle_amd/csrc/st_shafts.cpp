@@ -1,7 +1,6 @@
 // st_shafts.cpp — light shafts (include/strolle_hip.h "light shafts"): the setter's checks, the plan (cell grid, jitter table), the host
 // constants (step 0) and the two launches (k_shafts.hip) that st_render_camera and st_light_shafts_process share. The camera's HDR and
-// cell planes: st_engine.h CameraState::shafts_planes; the stateless call's cell plane: Engine::shafts_scratch.
-#include <cfloat>
+// cell planes: st_engine.h CameraState::shafts; the stateless call's cell plane: Engine::shafts_scratch.
 #include <cmath>
 
 #include "st_engine.h"
@@ -14,11 +13,7 @@ static_assert(offsetof(StLightShaftsDesc, density) == 16 && offsetof(StLightShaf
               offsetof(StLightShaftsDesc, sun_direction) == 64 && offsetof(StLightShaftsDesc, light_count) == 76 && offsetof(StLightShaftsDesc, lights) == 80,
               "StLightShaftsDesc: twenty 4-B words, then eight handles");
 static_assert(ST_SHAFTS_MAX_LIGHTS == kShaftsMaxLights, "the desc's handle list is the launch's slot list");
-static constexpr uint32_t kShaftsMaxSide = 16384u;
 
-static bool finite(float x) { return x >= -FLT_MAX && x <= FLT_MAX; }
-static bool finite_not_negative(float x) { return x >= 0.0f && x <= FLT_MAX; }
-static bool positive_finite(float x) { return x > 0.0f && x <= FLT_MAX; }
 static bool shafts_sun(const StLightShaftsDesc& d) { return d.sun_color[0] != 0.0f || d.sun_color[1] != 0.0f || d.sun_color[2] != 0.0f; }
 
 static int check_shafts(const StLightShaftsDesc& d) {
@@ -32,18 +27,14 @@ static int check_shafts(const StLightShaftsDesc& d) {
     if (!finite_not_negative(d.intensity)) return fail(ST_ERR_INVALID_ARGUMENT, "intensity must be finite and not negative");
     for (int i = 0; i < 3; i++) if (!(d.scatter[i] >= 0.0f && d.scatter[i] <= 1.0f)) return fail(ST_ERR_INVALID_ARGUMENT, "scatter is outside [0, 1]");
     for (int i = 0; i < 3; i++) if (!finite_not_negative(d.sun_color[i])) return fail(ST_ERR_INVALID_ARGUMENT, "sun_color must be finite and not negative");
-    if (shafts_sun(d) && !(d.flags & ST_SHAFTS_FOLLOW_SUN)) {
-        const float* v = d.sun_direction;
-        if (!(finite(v[0]) && finite(v[1]) && finite(v[2])) || (v[0] == 0.0f && v[1] == 0.0f && v[2] == 0.0f))
-            return fail(ST_ERR_INVALID_ARGUMENT, "sun_direction must be finite and not of length 0");
-    }
+    if (shafts_sun(d) && !(d.flags & ST_SHAFTS_FOLLOW_SUN) && !finite_direction(d.sun_direction)) return fail(ST_ERR_INVALID_ARGUMENT, "sun_direction must be finite and not of length 0");
     if (d.light_count > (uint32_t)ST_SHAFTS_MAX_LIGHTS) return fail(ST_ERR_INVALID_ARGUMENT, "light_count is above 8");
     return ST_OK;
 }
 
 int Engine::shafts_plan(const StLightShaftsDesc& d, uint32_t w, uint32_t h, ShaftsPlan& out) {
     if (int rc = check_shafts(d)) return rc;
-    if (w == 0u || h == 0u || w > kShaftsMaxSide || h > kShaftsMaxSide) return fail(ST_ERR_INVALID_ARGUMENT, "the image's sides must be in 1..16384");
+    if (w == 0u || h == 0u || w > kMaxImageSide || h > kMaxImageSide) return fail(ST_ERR_INVALID_ARGUMENT, "the image's sides must be in 1..16384");
     out.cells_w = (w + d.divisor - 1u) / d.divisor; out.cells_h = (h + d.divisor - 1u) / d.divisor;
     out.cell_bytes = (size_t)out.cells_w * out.cells_h * sizeof(float4);
     static const uint32_t bayer[16] = {0, 8, 2, 10, 12, 4, 14, 6, 3, 11, 1, 9, 15, 7, 13, 5};   // row cy & 3, column cx & 3
@@ -52,34 +43,27 @@ int Engine::shafts_plan(const StLightShaftsDesc& d, uint32_t w, uint32_t h, Shaf
 }
 
 int Engine::set_shafts(CameraState& c, const StLightShaftsDesc* desc) {
-    if (!desc) { c.shafts_on = false; return ST_OK; }
-    if (int rc = check_shafts(*desc)) return rc;
-    if (c.windowed()) return fail(ST_ERR_INVALID_ARGUMENT, "light shafts on a camera with a window: the apply launch reads neighbouring cells across tile edges (include/strolle_hip.h \"light shafts\")");
-    c.shafts = *desc; c.shafts._pad = 0.0f; c.shafts._pad2 = 0.0f; c.shafts_on = true;
-    for (uint32_t i = desc->light_count; i < (uint32_t)ST_SHAFTS_MAX_LIGHTS; i++) c.shafts.lights[i] = 0u;
+    if (int rc = set_node(c.windowed(), c.shafts, desc, check_shafts)) return rc;
+    c.shafts.desc._pad = 0.0f; c.shafts.desc._pad2 = 0.0f;
+    for (uint32_t i = c.shafts.desc.light_count; i < (uint32_t)ST_SHAFTS_MAX_LIGHTS; i++) c.shafts.desc.lights[i] = 0u;
     return ST_OK;
 }
 
-// Both launches' arguments. `frame`, `raw`: as in fog_step. `sun`: the direction ST_SHAFTS_FOLLOW_SUN takes. The handles become slots of
+// Both launches' arguments. view.sun: the direction ST_SHAFTS_FOLLOW_SUN takes. The handles become slots of
 // the light table of the last st_tick (light_slot_uploaded); a handle without a light there is skipped. Bytes: the march reads a pixel's
 // depth and writes 16 B a cell (its time is the walks'); the apply launch reads 16 B of colour, the depth and a cell's 16 B that
 // divisor^2 pixels share, and writes the format's bytes.
-void Engine::shafts_steps(const StLightShaftsDesc& d, const ShaftsPlan& plan, const float transform[16], const float projection[16], const float sun[3], const void* color,
-                          const void* depth, bool frame, uint32_t w, uint32_t h, float4* cells, void* dst, uint32_t format, bool raw, const DisplayArgs& display, bool count, ShaftsSteps& out) const {
+void Engine::shafts_steps(const StLightShaftsDesc& d, const ShaftsPlan& plan, const NodeView& view, const NodeSource& src, float4* cells, const NodeTarget& target, bool count, ShaftsSteps& out) const {
     ShaftsArgs& a = out.args;
     a = ShaftsArgs{};
-    a.color = static_cast<const float4*>(color); a.depth = depth; a.cells = cells; a.dst = dst;
-    a.width = w; a.height = h; a.cells_w = plan.cells_w; a.cells_h = plan.cells_h; a.divisor = d.divisor; a.steps = d.steps; a.frame = frame ? 1u : 0u;
-    a.format = raw ? (uint32_t)ST_FORMAT_RGBA32F : format; a.raw = raw ? 1u : 0u; a.count = count ? 1u : 0u;
+    a.color = static_cast<const float4*>(src.color); a.depth = src.depth; a.cells = cells;
+    a.width = src.w; a.height = src.h; a.cells_w = plan.cells_w; a.cells_h = plan.cells_h; a.divisor = d.divisor; a.steps = d.steps; a.frame = src.frame ? 1u : 0u;
+    apply_target(target, a); a.count = count ? 1u : 0u;
     a.light_extinction = (d.flags & ST_SHAFTS_LIGHT_EXTINCTION) ? 1u : 0u;
-    a.p0 = projection[0]; a.p5 = projection[5]; a.p8 = projection[8]; a.p9 = projection[9];
-    for (int i = 0; i < 3; i++) { a.m0[i] = transform[i]; a.m1[i] = transform[4 + i]; a.m2[i] = transform[8 + i]; a.origin[i] = transform[12 + i]; }
+    apply_projection(view.projection, a); apply_axes(view.transform, a);
+    for (int i = 0; i < 3; i++) a.origin[i] = view.transform[12 + i];
     // the host constants, in double, rounded once
-    if (shafts_sun(d)) {
-        const float* v = (d.flags & ST_SHAFTS_FOLLOW_SUN) ? sun : d.sun_direction;
-        const double x = (double)v[0], y = (double)v[1], z = (double)v[2], len = std::sqrt(x * x + y * y + z * z);
-        if (len > 0.0) { a.L[0] = (float)(x / len); a.L[1] = (float)(y / len); a.L[2] = (float)(z / len); a.sun_on = 1u; }
-    }
+    if (shafts_sun(d) && unit_direction((d.flags & ST_SHAFTS_FOLLOW_SUN) ? view.sun : d.sun_direction, a.L)) a.sun_on = 1u;
     const double g = (double)d.anisotropy;
     a.k1 = (float)((1.0 - g * g) / (4.0 * 3.14159265358979323846)); a.k2 = (float)(1.0 + g * g); a.k3 = (float)(2.0 * g);
     a.density = d.density; a.max_distance = d.max_distance; a.intensity = d.intensity;
@@ -89,8 +73,7 @@ void Engine::shafts_steps(const StLightShaftsDesc& d, const ShaftsPlan& plan, co
         if (it ==light_slot_uploaded.end() || it->second >= gpu_lights.size()) continue;
         a.lights[a.light_count++] = it->second;
     }
-    a.display = display;
-    const double n = (double)w * h, cells_n = (double)plan.cells_w * plan.cells_h;
+    const double n = (double)src.w * src.h, cells_n = (double)plan.cells_w * plan.cells_h;
     out.step[0] = {KS_SHAFTS_MARCH, n * 4.0 + cells_n * 16.0};
     out.step[1] = {KS_SHAFTS_APPLY, n * (20.0 + format_bytes(a.format)) + cells_n * 16.0};
 }
@@ -110,14 +93,8 @@ int Engine::shafts_process(const StLightShaftsDesc* desc, const StDisplayDesc* d
     ShaftsPlan plan;
     if (int rc = shafts_plan(*desc, w, h, plan)) return rc;
     if (!dof_perspective(projection)) return fail(ST_ERR_INVALID_ARGUMENT, "st_light_shafts_process takes a perspective projection: the cell's ray is derived from it");
-    DisplayArgs disp{};   // none: the colour's own bits
-    disp.scale = 1.0f;
-    if (display) {
-        if (int rc = check_display(*display)) return rc;
-        if (display->flags & ST_DISPLAY_AUTO_EXPOSURE) return fail(ST_ERR_INVALID_ARGUMENT, "st_light_shafts_process takes a manual display: auto-exposure is a camera's state");
-        disp.on = 1u; disp.tonemap = display->tonemap; disp.scale = (float)std::exp2((double)display->exposure_ev);
-    }
-    if (format < ST_FORMAT_RGBA32F || format > ST_FORMAT_BGRA8_UNORM_SRGB) return fail(ST_ERR_INVALID_ARGUMENT, "unknown output format");
+    NodeTarget target;
+    if (int rc = process_target("st_light_shafts_process", display, dst, format, target)) return rc;
     // the live scene copy and light table, with the scene queries' reader bookkeeping (st_query.cpp)
     KArgs scene;
     if (int rc = query_begin(stream, scene, true)) return rc;
@@ -126,7 +103,7 @@ int Engine::shafts_process(const StLightShaftsDesc* desc, const StDisplayDesc* d
     if (int rc = shafts_scratch.acquire({plan.cell_bytes}, shafts_scratch.Grow, stream)) return rc;
     const float sun[3] = {sun_dir_.x, sun_dir_.y, sun_dir_.z};
     ShaftsSteps steps;
-    shafts_steps(*desc, plan, transform, projection, sun, color, depth, false, w, h, shafts_scratch.plane[0].as<float4>(), dst, (uint32_t)format, false, disp, false, steps);
+    shafts_steps(*desc, plan, {transform, projection, sun}, {color, depth, nullptr, false, w, h}, shafts_scratch.plane[0].as<float4>(), target, false, steps);
     for (uint32_t i = 0; i < 2u; i++) launch_shafts_step(scene, steps, i, stream);
     if (int rc = shafts_scratch.done(stream)) return rc;
     ST_HIP(hipGetLastError());

@@ -1,13 +1,18 @@
 """GPU test of the frame's pass graph (st_render.cpp Engine::render): which launch groups a frame considers, in which order, and how often
 each kernel is launched, for one factor at a time around the default on the Cornell scene — against tests/golden/render_launches.json,
-which tests/golden/make_render_launches.py wrote with the library as it was before Engine::render was split into phases.
+which tests/golden/make_render_launches.py wrote. Two commits wrote its entries: every case outside CHAIN_CASES with the library as it was
+before Engine::render was split into phases (the parent of "Split Engine::render into phases; one owner for output scratch planes"), the
+CHAIN_CASES — motion blur, depth of field, fog and light shafts did not exist then — with the library of abb0108 ("Add light shafts"),
+the parent of the commit that put the HDR output chain into one node table.
 
 Per configuration and per frame 1..6 (one cycle: both parities, the tracing frames `frame % 6 < 4` and the validation frames):
   full      last_launches() and the status of st_render_camera with every pass enabled
   mask0     the same with pass mask 0: every launch group is listed, none runs, and the frame is not a whole graph — the other half of
             every switch that asks for one
   profiled  a serial frame under profile_enable(1 | 8): launches per kernel name (last_launches merges consecutive equal groups)
-Each of the three is a fresh engine's frames 1..6; an engine is closed before the next one is made. A render that returns a HIP error fails
+  bytes     (CHAIN_CASES only) the algorithmic bytes per kernel name of that profiled frame: what each launch is credited, host arithmetic
+            on integer-valued doubles, so it compares exactly
+The test compares whichever recordings a case's golden entry holds. Each of the three engines is fresh and renders frames 1..6; an engine is closed before the next one is made. A render that returns a HIP error fails
 its case, and every later case fails without touching the device.
 
 Not a case: a bloom descriptor whose plan holds no level at this size — st_bloom_plan keeps a level while both sides of its mip are at
@@ -18,7 +23,8 @@ import os
 import pytest
 import torch
 
-from strolle_amd import CameraMode, Engine, ResampleFilter, Tonemap, bloom_desc, display_desc, post_desc, scenes
+from strolle_amd import (CameraMode, Engine, ResampleFilter, Tonemap, bloom_desc, display_desc, dof_desc, fog_desc, light_shafts_desc, motion_blur_desc, post_desc,
+                         scenes)
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "render_launches.json")
@@ -51,7 +57,34 @@ def _cases():
     return c
 
 
+# the HDR nodes in chain order: the case's key, the setter, the descriptor
+CHAIN = (("fog", "set_fog", lambda: fog_desc(density=0.1, height_falloff=0.25)),
+         ("shafts", "set_light_shafts", lambda: light_shafts_desc(steps=4, lights=(1,), sun_color=(1.0, 1.0, 1.0), sun_direction=(0.35, 0.8, 0.3))),
+         ("dof", "set_dof", lambda: dof_desc(focal_distance=3.0, sensor_height=0.5)),
+         ("mblur", "set_motion_blur", lambda: motion_blur_desc()),
+         ("bloom", "set_bloom", lambda: bloom_desc()))
+
+
+def _chain_cases():
+    """the output chain: each later node alone (bloom alone is above), all five, all five under a display, FXAA and a resize, the subsets in
+    which a node's target skips the nodes that are off, and all five in the frames that differ in what runs around the chain"""
+    nodes = lambda *names: {n: True for n in names}   # noqa: E731
+    every = nodes("fog", "shafts", "dof", "mblur", "bloom")
+    c = {"chain_" + n: nodes(n) for n in ("mblur", "dof", "fog", "shafts")}
+    c["chain_all"] = dict(every)
+    c["chain_all_display_post"] = dict(every, display=dict(tonemap=Tonemap.ACES_FITTED, auto_exposure=True), post=dict(fxaa=True, output_size=(96, 72)))
+    c["chain_fog_bloom"] = nodes("fog", "bloom")
+    c["chain_shafts_mblur"] = nodes("shafts", "mblur")
+    c["chain_dof_bloom"] = nodes("dof", "bloom")
+    c["chain_fog_dof"] = nodes("fog", "dof")
+    for name in ("mode_reference_depth_2", "mode_bvh_heatmap", "no_output", "denoise_0", "flip_overlap"):
+        c["chain_all_" + name] = dict(every, **CASES[name])
+    return c
+
+
 CASES = _cases()
+CHAIN_CASES = _chain_cases()
+CASES.update(CHAIN_CASES)
 _hip_error = []   # the first render that returned a HIP error: nothing is started after it
 
 
@@ -73,8 +106,11 @@ def make_engine(case, lib_engine=Engine):
         e.set_display(cam, display_desc(**case["display"]))
     if "post" in case:
         e.set_post(cam, post_desc(**case["post"]))
-    if "bloom" in case:
+    if "bloom" in case and case["bloom"] is not True:
         e.set_bloom(cam, bloom_desc(**case["bloom"]))
+    for key, setter, desc in CHAIN:
+        if case.get(key) is True:
+            getattr(e, setter)(cam, desc())
     if "bloom_tail" in case:
         e.set_bloom_tail(case["bloom_tail"])
     out = None
@@ -85,9 +121,10 @@ def make_engine(case, lib_engine=Engine):
 
 
 def _frames(name, case, what):
-    """frames 1..6 of a fresh engine: per frame (status, last_launches) — `what` = "profiled": (status, {kernel: launches})"""
+    """frames 1..6 of a fresh engine: per frame (status, last_launches) — `what` = "profiled": (status, {kernel: launches}), and beside
+    them (status, {kernel: algorithmic bytes})"""
     e, cam, out = make_engine(case)
-    rows = []
+    rows, credited = [], []
     try:
         if what == "mask0":
             e.set_pass_mask(0)
@@ -102,17 +139,23 @@ def _frames(name, case, what):
                 pytest.fail(_hip_error[0])
             torch.cuda.synchronize()
             if what == "profiled":
-                rows.append([status, {p["name"]: p["launches"] for p in e.profile_read(reset=True) if p["launches"]}])
+                prof = [p for p in e.profile_read(reset=True) if p["launches"]]
+                rows.append([status, {p["name"]: p["launches"] for p in prof}])
+                credited.append([status, {p["name"]: p["algorithmic_bytes"] for p in prof}])
             else:
                 rows.append([status, e.last_launches()])
     finally:
         e.close()
-    return rows
+    return rows, credited
 
 
 def record(name):
     case = CASES[name]
-    return {what: _frames(name, case, what) for what in ("full", "mask0", "profiled")}
+    rec = {what: _frames(name, case, what)[0] for what in ("full", "mask0")}
+    rec["profiled"], credited = _frames(name, case, "profiled")
+    if name in CHAIN_CASES:
+        rec["bytes"] = credited
+    return rec
 
 
 @pytest.fixture(scope="module")
@@ -130,6 +173,7 @@ def test_a_frame_considers_and_launches_what_it_did_before_the_split(name, golde
     assert not _hip_error, f"not started: an earlier render returned a HIP error ({_hip_error[0]})"
     got = json.loads(json.dumps(record(name)))   # (as JSON holds it: lists, string keys)
     want = golden[name]
-    for what in ("full", "mask0", "profiled"):
+    assert set(want) >= {"full", "mask0", "profiled"} and set(want) <= set(got), sorted(want)
+    for what in want:
         for frame in range(FRAMES):
             assert got[what][frame] == want[what][frame], f"{name}: {what}, frame {frame + 1}"
