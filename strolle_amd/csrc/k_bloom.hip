@@ -5,6 +5,7 @@
 // per workgroup, one pixel per thread, and stages the source texels the tile reads (clamped at the image's edges, so the clamping is done
 // once per texel) in LDS with one 16-B load per texel.
 #include "k_common.h"
+#include "k_output.h"
 
 #pragma clang fp contract(off)
 
@@ -16,20 +17,17 @@ constexpr uint32_t kBloomDownW = 2u * kBloomW + 4u, kBloomDownH = 2u * kBloomH +
 constexpr uint32_t kBloomUpW = kBloomW / 2u + 4u, kBloomUpH = kBloomH / 2u + 4u;       // ... and source texels floor((x + 1) / 2) - 2 .. + 1
 static_assert(kBloomW * kBloomH == (uint32_t)kBlockThreads, "one destination pixel per thread");
 
-ST_D float bloom_min(float a, float b) { return (a < b || b != b) ? a : b; }
-ST_D float bloom_max(float a, float b) { return (a > b || b != b) ? a : b; }
-ST_D int bloom_clampi(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
 ST_D V3 bloom_add(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
 ST_D V3 bloom_mul(V3 a, float s) { return v3(a.x * s, a.y * s, a.z * s); }
 ST_D V3 bloom_lerp(V3 a, V3 b, float f) { return v3(a.x + (b.x - a.x) * f, a.y + (b.y - a.y) * f, a.z + (b.z - a.z) * f); }
 
 ST_D V3 bloom_prefilter(const BloomArgs& p, float4 t) {
-    V3 c = v3(bloom_min(bloom_max(t.x, 0.0f), p.clamp), bloom_min(bloom_max(t.y, 0.0f), p.clamp), bloom_min(bloom_max(t.z, 0.0f), p.clamp));
+    V3 c = v3(out_min(out_max(t.x, 0.0f), p.clamp), out_min(out_max(t.y, 0.0f), p.clamp), out_min(out_max(t.z, 0.0f), p.clamp));
     if (p.threshold_on) {
-        const float m = bloom_max(bloom_max(c.x, c.y), c.z);
-        float s = bloom_min(bloom_max(m - p.knee_lo, 0.0f), p.knee2);
+        const float m = out_max(out_max(c.x, c.y), c.z);
+        float s = out_min(out_max(m - p.knee_lo, 0.0f), p.knee2);
         s = (s * s) / p.knee_div;
-        const float w = bloom_max(m - p.threshold, s) / bloom_max(m, 1e-4f);
+        const float w = out_max(m - p.threshold, s) / out_max(m, 1e-4f);
         c = bloom_mul(c, w);
     }
     return c;
@@ -91,7 +89,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_bloom_down(const BloomArgs p)
     const uint32_t t = threadIdx.x, tx = t % kBloomW, ty = t / kBloomW;
     for (uint32_t i = t; i < kBloomDownW * kBloomDownH; i += (uint32_t)kBlockThreads) {
         const uint32_t lx = i % kBloomDownW, ly = i / kBloomDownW;
-        const int sx = bloom_clampi(2 * tile_x - 2 + (int)lx, (int)p.sw), sy = bloom_clampi(2 * tile_y - 2 + (int)ly, (int)p.sh);
+        const int sx = out_clampi(2 * tile_x - 2 + (int)lx, (int)p.sw), sy = out_clampi(2 * tile_y - 2 + (int)ly, (int)p.sh);
         const float4 v = p.src[(size_t)sy * p.sw + (size_t)sx];
         if (FIRST) { const V3 c = bloom_prefilter(p, v); s_t[ly][lx] = make_float4(c.x, c.y, c.z, 1.0f); }
         else s_t[ly][lx] = v;
@@ -122,7 +120,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_bloom_up(const BloomArgs p) {
     const bool any = !COMPOSITE || p.sw != 0u;
     if (any && t < kBloomUpW * kBloomUpH) {
         const uint32_t lx = t % kBloomUpW, ly = t / kBloomUpW;
-        const int sx = bloom_clampi(tile_x / 2 - 2 + (int)lx, (int)p.sw), sy = bloom_clampi(tile_y / 2 - 2 + (int)ly, (int)p.sh);
+        const int sx = out_clampi(tile_x / 2 - 2 + (int)lx, (int)p.sw), sy = out_clampi(tile_y / 2 - 2 + (int)ly, (int)p.sh);
         s_t[ly][lx] = p.src[(size_t)sy * p.sw + (size_t)sx];
     }
     __syncthreads();
@@ -156,7 +154,7 @@ void launch_bloom_composite(const BloomArgs& p, hipStream_t s) {
 constexpr uint32_t kBloomTailThreads = 1024u;   // the one workgroup is all the parallelism this launch has (its 244 B of scratch per lane is the argument struct, indexed by level)
 struct BloomTailFetch {   // texel (x, y) of an LDS level, clamped
     const float* s; int w, h;
-    ST_D V3 operator()(int x, int y) const { const float* q = s + 3 * (bloom_clampi(y, h) * w + bloom_clampi(x, w)); return v3(q[0], q[1], q[2]); }
+    ST_D V3 operator()(int x, int y) const { const float* q = s + 3 * (out_clampi(y, h) * w + out_clampi(x, w)); return v3(q[0], q[1], q[2]); }
 };
 __global__ __launch_bounds__(kBloomTailThreads) void k_bloom_tail(const BloomTailArgs p) {
     extern __shared__ __align__(16) float s_tail[];
@@ -166,7 +164,7 @@ __global__ __launch_bounds__(kBloomTailThreads) void k_bloom_tail(const BloomTai
         for (int at = (int)t; at < w * h; at += (int)kBloomTailThreads) {
             const int x = at % w, y = at / w;
             const V3 r = bloom_down13([&](int i, int j) {
-                return xyz(p.base[(size_t)bloom_clampi(2 * y - 2 + j, (int)p.bh) * p.bw + (size_t)bloom_clampi(2 * x - 2 + i, (int)p.bw)]); }, false);
+                return xyz(p.base[(size_t)out_clampi(2 * y - 2 + j, (int)p.bh) * p.bw + (size_t)out_clampi(2 * x - 2 + i, (int)p.bw)]); }, false);
             float* q = s_tail + p.off[0] + 3 * at;
             q[0] = r.x; q[1] = r.y; q[2] = r.z;
         }

@@ -3,6 +3,7 @@
 // texel taps). tests/dof_ref.py is the specification: everything here is float32, left to right, without FMA contraction and with
 // correctly rounded division and square root in BOTH builds, like k_motion_blur.hip.
 #include "k_common.h"
+#include "k_output.h"
 
 #pragma clang fp contract(off)
 
@@ -11,21 +12,10 @@ namespace ST_KNS {
 
 constexpr uint32_t kDofW = 32u, kDofH = 8u;   // a workgroup's pixels: one quarter of a tile, inside one tile
 static_assert(kDofW * kDofH == (uint32_t)kBlockThreads && kDofW == kDofTile && kDofTile % kDofH == 0u, "a workgroup lies inside one tile");
-constexpr float kDofFltMax = 3.402823466e+38f;
 
-ST_D float dof_min(float a, float b) { return (a < b || b != b) ? a : b; }
-ST_D float dof_max(float a, float b) { return (a > b || b != b) ? a : b; }
-ST_D float dof_clamp01(float x) { return dof_min(dof_max(x, 0.0f), 1.0f); }
-
-// D of a pixel: in a frame PRIM_GBUFFER_D0.x alone (4 of the texel's 16 B), 0 (sky) read as FLT_MAX
-template <bool FRAME>
-ST_D float dof_depth(const DofArgs& p, size_t at) {
-    if (FRAME) { const float d = reinterpret_cast<const float*>(static_cast<const float4*>(p.depth) + at)[0]; return d == 0.0f ? kDofFltMax : d; }
-    return static_cast<const float*>(p.depth)[at];
-}
 // Z: the distance along the optical axis of the point at distance d along pixel (x, y)'s ray. FLT_MAX (and +inf) stay FLT_MAX.
 ST_D float dof_planar(const DofArgs& p, uint32_t x, uint32_t y, float d) {
-    if (d >= kDofFltMax) return kDofFltMax;
+    if (d >= kFltMax) return kFltMax;
     if (p.planar) return d;
     const float ndc_x = ((float)x + 0.5f) * 2.0f / (float)p.width - 1.0f;
     const float ndc_y = -(((float)y + 0.5f) * 2.0f / (float)p.height - 1.0f);
@@ -46,10 +36,10 @@ __global__ __launch_bounds__(kBlockThreads) void k_dof_pack(const DofArgs p) {
     const uint32_t x = tile_x * kDofTile + tx;
     float s = p.focal_distance;
     if (p.autofocus) {
-        const float zf = dof_planar(p, p.focus_px, p.focus_py, dof_depth<FRAME>(p, (size_t)p.focus_py * p.width + p.focus_px));
-        if (zf > 0.0f && zf < kDofFltMax) s = zf;
+        const float zf = dof_planar(p, p.focus_px, p.focus_py, out_frame_depth(p.depth, (size_t)p.focus_py * p.width + p.focus_px, FRAME));
+        if (zf > 0.0f && zf < kFltMax) s = zf;
     }
-    const float m = dof_max(s - p.focal_length, 1e-6f);
+    const float m = out_max(s - p.focal_length, 1e-6f);
     const float A = p.k / m;
     uint32_t best = 0u;
 #pragma unroll
@@ -57,9 +47,9 @@ __global__ __launch_bounds__(kBlockThreads) void k_dof_pack(const DofArgs p) {
         const uint32_t y = tile_y * kDofTile + ty + kDofH * k;
         if (x >= p.width || y >= p.height) continue;
         const size_t at = (size_t)y * p.width + x;
-        const float z = dof_planar(p, x, y, dof_depth<FRAME>(p, at));
+        const float z = dof_planar(p, x, y, out_frame_depth(p.depth, at, FRAME));
         float coc = z > 0.0f ? A * (1.0f - s / z) : 0.0f;
-        coc = dof_min(dof_max(coc, -p.max_radius), p.max_radius);
+        coc = out_min(out_max(coc, -p.max_radius), p.max_radius);
         p.packed[at] = make_float2(coc, z);
         if (coc < 0.0f) { const uint32_t b = __float_as_uint(-coc); best = b > best ? b : best; }
     }
@@ -105,12 +95,6 @@ void launch_dof_neighbour(const DofArgs& p, hipStream_t s) {
 // disk of a wave's 64 pixels (two rows of 32) overlaps almost entirely from lane to lane, so the taps of one k are two rows of consecutive
 // texels shifted by one offset when r_g is uniform, and cache lines are shared among the k; a +-32-pixel apron around 32 x 8 pixels at 24 B a
 // texel (96 x 72 x 24 B = 166 KB) does not fit the LDS (DESIGN.md "depth of field").
-ST_D V3 dof_colour(float4 c) { return v3(dof_min(dof_max(c.x, 0.0f), 65504.0f), dof_min(dof_max(c.y, 0.0f), 65504.0f), dof_min(dof_max(c.z, 0.0f), 65504.0f)); }
-ST_D void dof_store(const DofArgs& p, size_t at, float4 c) {
-    if (p.raw) static_cast<float4*>(p.dst)[at] = c;
-    else if (!p.display.on) store_output(p.dst, (uint32_t)at, c, p.format);
-    else store_output(p.dst, (uint32_t)at, display_transform(c, p.display.tonemap, display_scale(p.display)), p.format);
-}
 __global__ __launch_bounds__(kBlockThreads) void k_dof_gather(const DofArgs p) {
     const uint32_t groups_x = (p.width + kDofW - 1u) / kDofW;
     const uint32_t gx = blockIdx.x % groups_x, gy = blockIdx.x / groups_x;   // row-major: consecutive workgroups stream consecutive 512-B runs of the same eight rows
@@ -121,28 +105,28 @@ __global__ __launch_bounds__(kBlockThreads) void k_dof_gather(const DofArgs p) {
     const float4 cx = p.color[at];
     const float2 px = p.packed[at];
     const float r_x = fabsf(px.x), z_x = px.y;
-    const float r_g = dof_max(r_x, n);
-    if (r_g < 0.5f) { dof_store(p, at, cx); return; }
-    const V3 c0 = dof_colour(cx);
+    const float r_g = out_max(r_x, n);
+    if (r_g < 0.5f) { out_store(p, at, cx); return; }
+    const V3 c0 = out_colour(cx);
     float sr = c0.x, sg = c0.y, sb = c0.z, wsum = 1.0f;
     const float fx = (float)x + 0.5f, fy = (float)y + 0.5f;
     const float xmax = (float)(p.width - 1u), ymax = (float)(p.height - 1u);
     for (uint32_t k = 0; k < p.samples; k++) {
         const float tx = p.taps[3u * k], ty = p.taps[3u * k + 1u], tr = p.taps[3u * k + 2u];
         const float qx = fx + tx * r_g, qy = fy + ty * r_g;
-        const uint32_t yx = (uint32_t)dof_min(dof_max(floorf(qx), 0.0f), xmax), yy = (uint32_t)dof_min(dof_max(floorf(qy), 0.0f), ymax);
+        const uint32_t yx = (uint32_t)out_min(out_max(floorf(qx), 0.0f), xmax), yy = (uint32_t)out_min(out_max(floorf(qy), 0.0f), ymax);
         const size_t ay = (size_t)yy * p.width + yx;
         const float2 py = p.packed[ay];
         const float4 cy4 = p.color[ay];
         const float d = tr * r_g;
         float r_y = fabsf(py.x);
-        if (py.y > z_x) r_y = dof_min(r_y, r_x);   // a blurred background does not bleed over a sharper foreground
-        const float q = dof_clamp01((r_y - d) + 0.5f);
+        if (py.y > z_x) r_y = out_min(r_y, r_x);   // a blurred background does not bleed over a sharper foreground
+        const float q = out_clamp01((r_y - d) + 0.5f);
         const float w = q * q * (3.0f - 2.0f * q);
-        const V3 cy = dof_colour(cy4);
+        const V3 cy = out_colour(cy4);
         sr = sr + cy.x * w; sg = sg + cy.y * w; sb = sb + cy.z * w; wsum = wsum + w;
     }
-    dof_store(p, at, make_float4(sr / wsum, sg / wsum, sb / wsum, 1.0f));
+    out_store(p, at, make_float4(sr / wsum, sg / wsum, sb / wsum, 1.0f));
 }
 void launch_dof_gather(const DofArgs& p, hipStream_t s) {
     const uint32_t blocks = ((p.width + kDofW - 1u) / kDofW) * ((p.height + kDofH - 1u) / kDofH);

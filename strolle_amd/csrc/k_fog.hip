@@ -4,6 +4,7 @@
 // contraction and with correctly rounded division and square root in BOTH builds, like k_dof.hip; the only transcendentals are st_math.h's
 // exp2_poly_ and log2_poly_ (never the hardware's v_exp_f32 / v_log_f32), so the two builds and numpy agree bit for bit.
 #include "k_common.h"
+#include "k_output.h"
 
 #pragma clang fp contract(off)
 
@@ -12,24 +13,8 @@ namespace ST_KNS {
 
 constexpr uint32_t kFogW = 32u, kFogH = 8u;   // a workgroup's pixels: each wave reads two 512-B runs of colour, consecutive workgroups consecutive runs
 static_assert(kFogW * kFogH == (uint32_t)kBlockThreads, "one pixel per thread");
-constexpr float kFogFltMax = 3.402823466e+38f;
 
-ST_D float fog_min(float a, float b) { return (a < b || b != b) ? a : b; }
-ST_D float fog_max(float a, float b) { return (a > b || b != b) ? a : b; }
-ST_D float fog_exp(float x) { return exp2_poly_(x * 1.44269504088896341f); }
 ST_D float fog_pow(float s, float p) { return s == 0.0f ? 0.0f : exp2_poly_(p * log2_poly_(s)); }
-
-// D of a pixel: in a frame PRIM_GBUFFER_D0.x alone (4 of the texel's 16 B), 0 (sky) read as FLT_MAX
-template <bool FRAME>
-ST_D float fog_depth(const FogArgs& p, size_t at) {
-    if (FRAME) { const float d = reinterpret_cast<const float*>(static_cast<const float4*>(p.depth) + at)[0]; return d == 0.0f ? kFogFltMax : d; }
-    return static_cast<const float*>(p.depth)[at];
-}
-ST_D void fog_store(const FogArgs& p, size_t at, float4 c) {
-    if (p.raw) static_cast<float4*>(p.dst)[at] = c;
-    else if (!p.display.on) store_output(p.dst, (uint32_t)at, c, p.format);
-    else store_output(p.dst, (uint32_t)at, display_transform(c, p.display.tonemap, display_scale(p.display)), p.format);
-}
 
 // One workgroup per 32 x 8 pixels of the window, row-major: consecutive workgroups stream consecutive 512-B runs of the same eight rows.
 // Per pixel one 16-B colour load, one 4-B depth read and one store; everything else arrives by value and is wave-uniform, so the falloff,
@@ -42,12 +27,12 @@ __global__ __launch_bounds__(kBlockThreads) void k_fog(const FogArgs p) {
     if (x >= p.col1 || y >= p.row1) return;
     const size_t at = (size_t)y * p.width + x;
     const float4 cx = p.color[at];
-    const float D = fog_depth<FRAME>(p, at);
+    const float D = out_frame_depth(p.depth, at, FRAME);
     // 2. distance
-    if (!(D > 0.0f)) { fog_store(p, at, cx); return; }
+    if (!(D > 0.0f)) { out_store(p, at, cx); return; }
     float d = D;
-    if (D >= kFogFltMax) {
-        if (!p.sky) { fog_store(p, at, cx); return; }
+    if (D >= kFltMax) {
+        if (!p.sky) { out_store(p, at, cx); return; }
         d = p.sky_distance;
     }
     // 1. ray
@@ -65,42 +50,42 @@ __global__ __launch_bounds__(kBlockThreads) void k_fog(const FogArgs p) {
     // 3. height
     float de = d;
     if (p.height_on) {
-        const float k = fog_min(fog_max((p.b * wy) * d, -80.0f), 80.0f);
-        const float G = fabsf(k) < 0.03125f ? 1.0f - k * (0.5f - k * 0.16666667f) : (1.0f - fog_exp(-k)) / k;
-        de = fog_min(d * (p.E0 * G), kFogFltMax);
+        const float k = out_min(out_max((p.b * wy) * d, -80.0f), 80.0f);
+        const float G = fabsf(k) < 0.03125f ? 1.0f - k * (0.5f - k * 0.16666667f) : (1.0f - out_exp(-k)) / k;
+        de = out_min(d * (p.E0 * G), kFltMax);
     }
     // 4. factors
     float ge[3], gi[3];
     if (p.falloff == 3u) {
 #pragma unroll
         for (int i = 0; i < 3; i++) {
-            ge[i] = (1.0f - fog_exp(-(p.extinction[i] * de))) * p.a;
-            gi[i] = (1.0f - fog_exp(-(p.inscattering[i] * de))) * p.a;
+            ge[i] = (1.0f - out_exp(-(p.extinction[i] * de))) * p.a;
+            gi[i] = (1.0f - out_exp(-(p.inscattering[i] * de))) * p.a;
         }
     } else {
         float g;
-        if (p.falloff == 0u) g = fog_min(fog_max((de - p.start) / (p.end - p.start), 0.0f), 1.0f);
-        else if (p.falloff == 1u) g = 1.0f - fog_exp(-(p.density * de));
-        else { const float u = p.density * de; g = 1.0f - fog_exp(-(u * u)); }
+        if (p.falloff == 0u) g = out_min(out_max((de - p.start) / (p.end - p.start), 0.0f), 1.0f);
+        else if (p.falloff == 1u) g = 1.0f - out_exp(-(p.density * de));
+        else { const float u = p.density * de; g = 1.0f - out_exp(-(u * u)); }
         ge[0] = ge[1] = ge[2] = gi[0] = gi[1] = gi[2] = g * p.a;
     }
-    if (ge[0] == 0.0f && ge[1] == 0.0f && ge[2] == 0.0f && gi[0] == 0.0f && gi[1] == 0.0f && gi[2] == 0.0f) { fog_store(p, at, cx); return; }
+    if (ge[0] == 0.0f && ge[1] == 0.0f && ge[2] == 0.0f && gi[0] == 0.0f && gi[1] == 0.0f && gi[2] == 0.0f) { out_store(p, at, cx); return; }
     // 5. colour
     float F[3] = {p.rgb[0], p.rgb[1], p.rgb[2]};
     if (p.lobe_on) {
-        const float s = fog_min(fog_max((wx * p.L[0] + wy * p.L[1]) + wz * p.L[2], 0.0f), 1.0f);
+        const float s = out_min(out_max((wx * p.L[0] + wy * p.L[1]) + wz * p.L[2], 0.0f), 1.0f);
         const float lobe = fog_pow(s, p.light_exponent);
 #pragma unroll
-        for (int i = 0; i < 3; i++) F[i] = fog_min(p.rgb[i] + p.light_color[i] * lobe, kFogFltMax);
+        for (int i = 0; i < 3; i++) F[i] = out_min(p.rgb[i] + p.light_color[i] * lobe, kFltMax);
     }
     const float c3[3] = {cx.x, cx.y, cx.z};
     float o[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) {
-        const float cc = fog_min(fog_max(c3[i], 0.0f), 65504.0f);
+        const float cc = out_min(out_max(c3[i], 0.0f), kColourMax);
         o[i] = cc * (1.0f - ge[i]) + F[i] * gi[i];
     }
-    fog_store(p, at, make_float4(o[0], o[1], o[2], 1.0f));
+    out_store(p, at, make_float4(o[0], o[1], o[2], 1.0f));
 }
 void launch_fog(const FogArgs& p, hipStream_t s) {
     if (p.col1 <= p.col0 || p.row1 <= p.row0) return;

@@ -3,6 +3,7 @@
 // texel taps). tests/motion_blur_ref.py is the specification: everything here is float32, left to right, without FMA contraction and with
 // correctly rounded division and square root in BOTH builds, like k_post.hip and k_bloom.hip.
 #include "k_common.h"
+#include "k_output.h"
 
 #pragma clang fp contract(off)
 
@@ -12,9 +13,6 @@ namespace ST_KNS {
 constexpr uint32_t kMBlurW = 32u, kMBlurH = 8u;   // a workgroup's pixels: one quarter of a tile, inside one tile
 static_assert(kMBlurW * kMBlurH == (uint32_t)kBlockThreads && kMBlurW == kMBlurTile && kMBlurTile % kMBlurH == 0u, "a workgroup lies inside one tile");
 
-ST_D float mb_min(float a, float b) { return (a < b || b != b) ? a : b; }
-ST_D float mb_max(float a, float b) { return (a > b || b != b) ? a : b; }
-ST_D float mb_clamp01(float x) { return mb_min(mb_max(x, 0.0f), 1.0f); }
 ST_D unsigned long long mb_max64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 
 // ---- pack + tile maximum: one workgroup per tile, thread (tx, ty) takes the pixels (tx, ty + 8 k), k = 0..3, of it. A pixel's key is r's
@@ -38,7 +36,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_mblur_pack(const MBlurArgs p)
             const float2 v = *reinterpret_cast<const float2*>(static_cast<const float4*>(p.velocity) + at);
             vx = v.x; vy = v.y;
             z = static_cast<const float4*>(p.depth)[at].x;
-            if (z == 0.0f) z = 3.402823466e+38f;   // sky
+            if (z == 0.0f) z = kFltMax;   // sky
         } else {
             const float2 v = static_cast<const float2*>(p.velocity)[at];
             vx = v.x; vy = v.y;
@@ -90,19 +88,11 @@ void launch_mblur_neighbour(const MBlurArgs& p, hipStream_t s) {
 // ---- gather: one workgroup per 32 x 8 pixels of one tile, so the tile's (n, r_n) is one uniform load and "at rest" is a uniform branch that
 // moves the pixel's 16 B in and the output format's bytes out. The taps of a wave lie along one direction; they are read from global memory
 // (a +-32-pixel apron around 32 x 8 pixels in LDS would be mostly texels no tap reads): 16 B of colour and 8 B of (r, Z) each.
-ST_D float mb_cone(float d, float r) { return r > 0.0f ? mb_clamp01(1.0f - d / r) : 0.0f; }
+ST_D float mb_cone(float d, float r) { return r > 0.0f ? out_clamp01(1.0f - d / r) : 0.0f; }
 ST_D float mb_cyl(float d, float r) {
     if (!(r > 0.0f)) return 0.0f;
-    const float q = mb_clamp01((d - 0.95f * r) / (1.05f * r - 0.95f * r));
+    const float q = out_clamp01((d - 0.95f * r) / (1.05f * r - 0.95f * r));
     return 1.0f - q * q * (3.0f - 2.0f * q);
-}
-ST_D V3 mb_colour(float4 c) { return v3(mb_min(mb_max(c.x, 0.0f), 65504.0f), mb_min(mb_max(c.y, 0.0f), 65504.0f), mb_min(mb_max(c.z, 0.0f), 65504.0f)); }
-// (Without a display the colour is stored as it is, not through display_transform at NONE and scale 1 as the bloom composite does: that path
-// writes alpha 1, and a pixel at rest keeps C(X)'s own four words, alpha included.)
-ST_D void mb_store(const MBlurArgs& p, size_t at, float4 c) {
-    if (p.raw) static_cast<float4*>(p.dst)[at] = c;
-    else if (!p.display.on) store_output(p.dst, (uint32_t)at, c, p.format);
-    else store_output(p.dst, (uint32_t)at, display_transform(c, p.display.tonemap, display_scale(p.display)), p.format);
 }
 __global__ __launch_bounds__(kBlockThreads) void k_mblur_gather(const MBlurArgs p) {
     const uint32_t groups_x = (p.width + kMBlurW - 1u) / kMBlurW;
@@ -113,7 +103,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_mblur_gather(const MBlurArgs 
     const size_t at = (size_t)y * p.width + x;
     const float4 cx = p.color[at];
     const float rn = n.z;
-    if (rn < 0.5f) { mb_store(p, at, cx); return; }
+    if (rn < 0.5f) { out_store(p, at, cx); return; }
     const float2 px = p.packed[at];
     const float r_x = px.x, z_x = px.y;
     float j = 0.0f;
@@ -122,28 +112,28 @@ __global__ __launch_bounds__(kBlockThreads) void k_mblur_gather(const MBlurArgs 
         const unsigned long long bayer = 0x5D7F91B36E4CA280ull;
         j = ((float)((uint32_t)(bayer >> (16u * (y & 3u) + 4u * (x & 3u))) & 15u) + 0.5f) / 16.0f - 0.5f;
     }
-    const float w0 = 1.0f / mb_max(r_x, 0.5f);
-    const V3 c0 = mb_colour(cx);
+    const float w0 = 1.0f / out_max(r_x, 0.5f);
+    const V3 c0 = out_colour(cx);
     float sr = c0.x * w0, sg = c0.y * w0, sb = c0.z * w0, wsum = w0;
     const float fx = (float)x + 0.5f, fy = (float)y + 0.5f, fs = (float)p.samples;
     const float xmax = (float)(p.width - 1u), ymax = (float)(p.height - 1u);
     for (uint32_t i = 0; i < p.samples; i++) {
         const float tt = (((float)i + 0.5f + j) * 2.0f) / fs - 1.0f;
         const float qx = fx + n.x * tt, qy = fy + n.y * tt;
-        const uint32_t yx = (uint32_t)mb_min(mb_max(floorf(qx), 0.0f), xmax), yy = (uint32_t)mb_min(mb_max(floorf(qy), 0.0f), ymax);
+        const uint32_t yx = (uint32_t)out_min(out_max(floorf(qx), 0.0f), xmax), yy = (uint32_t)out_min(out_max(floorf(qy), 0.0f), ymax);
         const size_t ay = (size_t)yy * p.width + yx;
         const float2 py = p.packed[ay];
         const float4 cy4 = p.color[ay];
         const float r_y = py.x, z_y = py.y;
         const float d = fabsf(tt) * rn;
-        const float e = mb_max(p.depth_softness * mb_min(z_x, z_y), 1e-6f);
-        const float f = mb_clamp01(1.0f - (z_y - z_x) / e);
-        const float b = mb_clamp01(1.0f - (z_x - z_y) / e);
+        const float e = out_max(p.depth_softness * out_min(z_x, z_y), 1e-6f);
+        const float f = out_clamp01(1.0f - (z_y - z_x) / e);
+        const float b = out_clamp01(1.0f - (z_x - z_y) / e);
         const float w = (f * mb_cone(d, r_y) + b * mb_cone(d, r_x)) + (mb_cyl(d, r_y) * mb_cyl(d, r_x)) * 2.0f;
-        const V3 cy = mb_colour(cy4);
+        const V3 cy = out_colour(cy4);
         sr = sr + cy.x * w; sg = sg + cy.y * w; sb = sb + cy.z * w; wsum = wsum + w;
     }
-    mb_store(p, at, make_float4(sr / wsum, sg / wsum, sb / wsum, 1.0f));
+    out_store(p, at, make_float4(sr / wsum, sg / wsum, sb / wsum, 1.0f));
 }
 void launch_mblur_gather(const MBlurArgs& p, hipStream_t s) {
     const uint32_t blocks = ((p.width + kMBlurW - 1u) / kMBlurW) * ((p.height + kMBlurH - 1u) / kMBlurH);

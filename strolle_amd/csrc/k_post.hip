@@ -4,17 +4,14 @@
 // correctly rounded division and square root in BOTH builds (plain `/` and sqrtf, like the display transform and the ray chain's exact
 // islands), so that a branchy algorithm (edge or no edge, horizontal or vertical) cannot flip on an ulp between the builds or against numpy.
 #include "k_common.h"
+#include "k_output.h"
 
 #pragma clang fp contract(off)
 
 namespace st {
 namespace ST_KNS {
 
-// min / max as the header defines them: the first operand unless the second is smaller / larger or NaN
-ST_D float post_min(float a, float b) { return (a < b || b != b) ? a : b; }
-ST_D float post_max(float a, float b) { return (a > b || b != b) ? a : b; }
-ST_D int post_clampi(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
-ST_D float4 post_texel(const PostArgs& p, int x, int y) { return p.src[(size_t)post_clampi(y, (int)p.height) * p.width + (size_t)post_clampi(x, (int)p.width)]; }
+ST_D float4 post_texel(const PostArgs& p, int x, int y) { return p.src[(size_t)out_clampi(y, (int)p.height) * p.width + (size_t)out_clampi(x, (int)p.width)]; }
 ST_D float post_unit(float x) { return x > 0.0f ? (x < 1.0f ? x : 1.0f) : 0.0f; }   // NaN -> 0
 ST_D float post_luma(float4 c) { return sqrtf(display_luma(post_unit(c.x), post_unit(c.y), post_unit(c.z))); }
 ST_D float post_blend(float a, float b, float f) { return f == 0.0f ? a : a + (b - a) * f; }
@@ -157,8 +154,8 @@ ST_D float4 post_cr4(float4 t0, float4 t1, float4 t2, float4 t3, const CrWeights
     return make_float4(post_cr1(t0.x, t1.x, t2.x, t3.x, w, f), post_cr1(t0.y, t1.y, t2.y, t3.y, w, f), post_cr1(t0.z, t1.z, t2.z, t3.z, w, f), 1.0f);
 }
 ST_D float post_box(float v, float a, float b, float c, float d) {
-    const float lo = post_min(post_min(post_min(a, b), c), d), hi = post_max(post_max(post_max(a, b), c), d);
-    return post_min(post_max(v, lo), hi);
+    const float lo = out_min(out_min(out_min(a, b), c), d), hi = out_max(out_max(out_max(a, b), c), d);
+    return out_min(out_max(v, lo), hi);
 }
 
 template <int FILTER>

@@ -8,6 +8,7 @@
 // square root in the fast build). The pragma stands behind the includes on purpose: the walk inlined from st_traverse.h stays compiled as
 // k_query.hip compiles it, so a shadow ray's answer here is st_scene_occluded's for the same ray.
 #include "k_common.h"
+#include "k_output.h"
 
 #pragma clang fp contract(off)
 
@@ -17,12 +18,7 @@ namespace ST_KNS {
 constexpr uint32_t kShaftsW = 32u, kShaftsH = 8u;   // the apply launch's workgroup, as k_fog's
 static_assert(kShaftsW * kShaftsH == (uint32_t)kBlockThreads, "one pixel per thread");
 static_assert(sizeof(KArgs) + sizeof(ShaftsArgs) <= 4096u, "both structs travel as kernel arguments");
-constexpr float kShaftsFltMax = 3.402823466e+38f;
 
-ST_D float sh_min(float a, float b) { return (a < b || b != b) ? a : b; }
-ST_D float sh_max(float a, float b) { return (a > b || b != b) ? a : b; }
-ST_D float sh_clamp01(float x) { return sh_min(sh_max(x, 0.0f), 1.0f); }
-ST_D float sh_exp(float x) { return exp2_poly_(x * 1.44269504088896341f); }
 // glam's acos_approx (st_math.h glam_acos_approx), with the correctly rounded square root in both builds
 ST_D float sh_acos(float v) {
     const float x = fabsf(v);
@@ -32,11 +28,6 @@ ST_D float sh_acos(float v) {
     float r = ((((((-0.0012624911f * x + 0.0066700901f) * x - 0.0170881256f) * x + 0.0308918810f) * x - 0.0501743046f) * x + 0.0889789874f) * x - 0.2145988016f) * x + 1.5707963050f;
     r = r * root;
     return v >= 0.0f ? r : 3.14159265358979323846f - r;
-}
-// D of a pixel: in a frame PRIM_GBUFFER_D0.x, 0 (sky) read as FLT_MAX; otherwise the float plane as it is
-ST_D float sh_depth(const ShaftsArgs& p, size_t at) {
-    if (p.frame) { const float d = reinterpret_cast<const float*>(static_cast<const float4*>(p.depth) + at)[0]; return d == 0.0f ? kShaftsFltMax : d; }
-    return static_cast<const float*>(p.depth)[at];
 }
 // the ray through (fx, fy) in pixels: fog's step 1
 ST_D void sh_ray(const ShaftsArgs& p, float fx, float fy, float* wx, float* wy, float* wz) {
@@ -79,7 +70,7 @@ __global__ ST_KERNEL_BOUNDS void k_shafts_march(const KArgs a_in, const ShaftsAr
     for (uint32_t by = 0u; by < div; by++) for (uint32_t bx = 0u; bx < div; bx++) {
         const uint32_t x = cx * div + bx, y = cy * div + by;
         if (x >= p.width || y >= p.height) continue;
-        const float D = sh_depth(p, (size_t)y * p.width + x);
+        const float D = out_frame_depth(p.depth, (size_t)y * p.width + x, p.frame);
         if (!(D > 0.0f)) continue;
         if (!any) d_c = D; else if (take_max ? D > d_c : D < d_c) d_c = D;
         any = true;
@@ -89,14 +80,14 @@ __global__ ST_KERNEL_BOUNDS void k_shafts_march(const KArgs a_in, const ShaftsAr
     out->w = d_c;   // now: d_c is not carried through the walks
     float wx, wy, wz;
     sh_ray(p, (float)(cx * div) + 0.5f * (float)div, (float)(cy * div) + 0.5f * (float)div, &wx, &wy, &wz);
-    const float d_end = sh_min(d_c, p.max_distance);
+    const float d_end = out_min(d_c, p.max_distance);
     const float delta = d_end / (float)p.steps;
     const unsigned long long bayer = 0x5D7F91B36E4CA280ull;   // the 4 x 4 Bayer matrix {0 8 2 10 / 12 4 14 6 / 3 11 1 9 / 15 7 13 5}, as in k_motion_blur.hip
     const float j = ((float)((uint32_t)(bayer >> (16u * (cy & 3u) + 4u * (cx & 3u))) & 15u) + 0.5f) / 16.0f;
     // the sun's term does not depend on the sample: its phase is the one value carried (sun_color is wave-uniform)
     float sun_ph = 0.0f; bool sun_on = false;
     if (p.sun_on) {
-        const float c = sh_min(sh_max((wx * p.L[0] + wy * p.L[1]) + wz * p.L[2], -1.0f), 1.0f);
+        const float c = out_min(out_max((wx * p.L[0] + wy * p.L[1]) + wz * p.L[2], -1.0f), 1.0f);
         sun_ph = sh_phase(p, c);
         sun_on = !(p.sun_color[0] * sun_ph == 0.0f && p.sun_color[1] * sun_ph == 0.0f && p.sun_color[2] * sun_ph == 0.0f);
     }
@@ -109,7 +100,7 @@ __global__ ST_KERNEL_BOUNDS void k_shafts_march(const KArgs a_in, const ShaftsAr
         float A[3] = {0.0f, 0.0f, 0.0f};
         if (sun_on) {
             rays++;
-            if (!sh_occluded(a, px, py, pz, p.L[0], p.L[1], p.L[2], kShaftsFltMax, stack)) { A[0] = A[0] + p.sun_color[0] * sun_ph; A[1] = A[1] + p.sun_color[1] * sun_ph; A[2] = A[2] + p.sun_color[2] * sun_ph; }
+            if (!sh_occluded(a, px, py, pz, p.L[0], p.L[1], p.L[2], kFltMax, stack)) { A[0] = A[0] + p.sun_color[0] * sun_ph; A[1] = A[1] + p.sun_color[1] * sun_ph; A[2] = A[2] + p.sun_color[2] * sun_ph; }
         }
         for (uint32_t li = 0u; li < p.light_count; li++) {
             const GpuLight l = light_get(a, p.lights[li]);
@@ -126,47 +117,41 @@ __global__ ST_KERNEL_BOUNDS void k_shafts_march(const KArgs a_in, const ShaftsAr
                 const float ex = l.d2.y * 2.0f - 1.0f, ey = l.d2.z * 2.0f - 1.0f;
                 float nx = ex, ny = ey;
                 const float nz = (1.0f - fabsf(ex)) - fabsf(ey);
-                const float tt = sh_max(-nz, 0.0f);
+                const float tt = out_max(-nz, 0.0f);
                 nx = nx - copysignf(tt, nx); ny = ny - copysignf(tt, ny);
                 const float ux = -vx, uy = -vy, uz = -vz;
                 const float n2 = (nx * nx + ny * ny) + nz * nz;
                 const float angle = sh_acos(((nx * ux + ny * uy) + nz * uz) / sqrtf(n2 * l2));
                 const float r = angle / l.d2.w;
-                f_angle = sh_clamp01(1.0f - (r * r) * r);
+                f_angle = out_clamp01(1.0f - (r * r) * r);
             }
             float f_dist = 1.0f;
             if (l.d1.w != INFINITY) {
                 const float inv_r2 = 1.0f / (l.d1.w * l.d1.w);
                 const float factor = l2 * inv_r2;
-                const float sm = sh_clamp01(1.0f - factor * factor);
-                f_dist = (sm * sm) / sh_max(l2, 0.0001f);
+                const float sm = out_clamp01(1.0f - factor * factor);
+                f_dist = (sm * sm) / out_max(l2, 0.0001f);
             }
             float fe = f_angle * f_dist;
-            if (p.light_extinction) fe = fe * sh_exp(-(p.density * len));
-            const float c = sh_min(sh_max((wx * dx + wy * dy) + wz * dz, -1.0f), 1.0f);
+            if (p.light_extinction) fe = fe * out_exp(-(p.density * len));
+            const float c = out_min(out_max((wx * dx + wy * dy) + wz * dz, -1.0f), 1.0f);
             const float ph = sh_phase(p, c);
             const float e0 = (l.d1.x * fe) * ph, e1 = (l.d1.y * fe) * ph, e2 = (l.d1.z * fe) * ph;
             if (e0 == 0.0f && e1 == 0.0f && e2 == 0.0f) continue;   // no ray: out of range, outside the cone, a black light
             rays++;
             if (!sh_occluded(a, px, py, pz, dx, dy, dz, len - l.d0.w, stack)) { A[0] = A[0] + e0; A[1] = A[1] + e1; A[2] = A[2] + e2; }
         }
-        const float m = (sh_exp(-(p.density * t)) * delta) * p.density;
+        const float m = (out_exp(-(p.density * t)) * delta) * p.density;
 #pragma unroll
         for (int i = 0; i < 3; i++) S[i] = S[i] + (m * p.scatter[i]) * A[i];
     }
     // held in [0, FLT_MAX]: the apply launch multiplies S by weights that may be 0
-    out->x = sh_min(sh_max(S[0], 0.0f), kShaftsFltMax); out->y = sh_min(sh_max(S[1], 0.0f), kShaftsFltMax); out->z = sh_min(sh_max(S[2], 0.0f), kShaftsFltMax);
+    out->x = out_min(out_max(S[0], 0.0f), kFltMax); out->y = out_min(out_max(S[1], 0.0f), kFltMax); out->z = out_min(out_max(S[2], 0.0f), kFltMax);
     if (p.count && rays) count_rays_many(a, rays, 0ull);
 }
 void launch_shafts_march(const KArgs& a, const ShaftsArgs& p, hipStream_t s) {
     if (p.cells_w == 0u || p.cells_h == 0u) return;
     ST_LAUNCH_TRACE(k_shafts_march, (), false, s, a, p);
-}
-
-ST_D void sh_store(const ShaftsArgs& p, size_t at, float4 c) {
-    if (p.raw) static_cast<float4*>(p.dst)[at] = c;
-    else if (!p.display.on) store_output(p.dst, (uint32_t)at, c, p.format);
-    else store_output(p.dst, (uint32_t)at, display_transform(c, p.display.tonemap, display_scale(p.display)), p.format);
 }
 
 // One workgroup per 32 x 8 pixels, row-major. Per pixel one 16-B colour load, one depth read, one (divisor 1) or four (divisor 2) 16-B cell
@@ -178,14 +163,14 @@ __global__ __launch_bounds__(kBlockThreads) void k_shafts_apply(const ShaftsArgs
     if (x >= p.width || y >= p.height) return;
     const size_t at = (size_t)y * p.width + x;
     const float4 cx = p.color[at];
-    const float D = sh_depth(p, at);
-    if (!(D > 0.0f)) { sh_store(p, at, cx); return; }
+    const float D = out_frame_depth(p.depth, at, p.frame);
+    if (!(D > 0.0f)) { out_store(p, at, cx); return; }
     float S[3] = {0.0f, 0.0f, 0.0f};
     if (p.divisor == 1u) {
         const float4 c = p.cells[at];
         S[0] = c.x; S[1] = c.y; S[2] = c.z;
     } else {
-        const float d_p = sh_min(D, p.max_distance);
+        const float d_p = out_min(D, p.max_distance);
         const float ux = ((float)x + 0.5f) * 0.5f - 0.5f, uy = ((float)y + 0.5f) * 0.5f - 0.5f;
         const float flx = floorf(ux), fly = floorf(uy);
         const float fx = ux - flx, fy = uy - fly;
@@ -199,7 +184,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_shafts_apply(const ShaftsArgs
             const float4 c = p.cells[(size_t)ccy * p.cells_w + ccx];
             if (!(c.w > 0.0f)) continue;   // an empty cell
             const float b = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
-            const float wgt = b * (1.0f / (0.001f + fabsf(sh_min(c.w, p.max_distance) - d_p) / d_p));
+            const float wgt = b * (1.0f / (0.001f + fabsf(out_min(c.w, p.max_distance) - d_p) / d_p));
             S[0] = S[0] + wgt * c.x; S[1] = S[1] + wgt * c.y; S[2] = S[2] + wgt * c.z;
             total = total + wgt;
         }
@@ -207,9 +192,9 @@ __global__ __launch_bounds__(kBlockThreads) void k_shafts_apply(const ShaftsArgs
         else { S[0] = 0.0f; S[1] = 0.0f; S[2] = 0.0f; }
     }
     const float a0 = p.intensity * S[0], a1 = p.intensity * S[1], a2 = p.intensity * S[2];
-    if (a0 == 0.0f && a1 == 0.0f && a2 == 0.0f) { sh_store(p, at, cx); return; }
-    sh_store(p, at, make_float4(sh_min(sh_min(sh_max(cx.x, 0.0f), 65504.0f) + a0, kShaftsFltMax), sh_min(sh_min(sh_max(cx.y, 0.0f), 65504.0f) + a1, kShaftsFltMax),
-                                sh_min(sh_min(sh_max(cx.z, 0.0f), 65504.0f) + a2, kShaftsFltMax), cx.w));
+    if (a0 == 0.0f && a1 == 0.0f && a2 == 0.0f) { out_store(p, at, cx); return; }
+    out_store(p, at, make_float4(out_min(out_min(out_max(cx.x, 0.0f), kColourMax) + a0, kFltMax), out_min(out_min(out_max(cx.y, 0.0f), kColourMax) + a1, kFltMax),
+                                out_min(out_min(out_max(cx.z, 0.0f), kColourMax) + a2, kFltMax), cx.w));
 }
 void launch_shafts_apply(const ShaftsArgs& p, hipStream_t s) {
     if (p.width == 0u || p.height == 0u) return;

@@ -3,20 +3,13 @@ downsample, the 3 x 3 tent upsample, the chain and the composite. Everything tha
 order; the blend factors are host arithmetic in double and are passed in (a test feeds what st_bloom_plan reports, or `factors` below)."""
 import numpy as np
 
+from ref_num import max2, min2  # noqa: F401  (re-exported)
+
 F = np.float32
 ADDITIVE, FIREFLY_SUPPRESS = 1, 2
 DEFAULT_LEVELS, MAX_LEVELS, DEFAULT_CLAMP = 6, 8, 65504.0
 GROUP_WEIGHTS = (0.125, 0.125, 0.125, 0.125, 0.5)
 TENT = ((0.0625, 0.125, 0.0625), (0.125, 0.25, 0.125), (0.0625, 0.125, 0.0625))
-
-
-def min2(a, b):
-    """the header's min: a when a < b or b is NaN, else b"""
-    return np.where((a < b) | (b != b), a, b).astype(np.float32)
-
-
-def max2(a, b):
-    return np.where((a > b) | (b != b), a, b).astype(np.float32)
 
 
 def luma(c):

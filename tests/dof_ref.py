@@ -4,24 +4,12 @@ post-processing section's NaN rule. The tap table is the library's (st_dof_plan)
 so `taps_double` below is only what that table is checked against, to within one float ulp."""
 import numpy as np
 
+from ref_num import COLOUR_CLAMP, FLT_MAX, clamp01, colour, frame_depth, max2, min2  # noqa: F401  (re-exported)
+
 F = np.float32
 AUTOFOCUS, PLANAR_DEPTH = 1, 2
-TILE, DEFAULT_SAMPLES, DEFAULT_RADIUS, DEFAULT_STOPS, DEFAULT_SENSOR, COLOUR_CLAMP = 32, 32, 32.0, 1.0, 0.01866, 65504.0
+TILE, DEFAULT_SAMPLES, DEFAULT_RADIUS, DEFAULT_STOPS, DEFAULT_SENSOR = 32, 32, 32.0, 1.0, 0.01866
 GOLDEN_ANGLE = 2.399963229728653
-FLT_MAX = np.finfo(np.float32).max
-
-
-def min2(a, b):
-    """the header's min: a when a < b or b is NaN, else b"""
-    return np.where((a < b) | (b != b), a, b).astype(np.float32)
-
-
-def max2(a, b):
-    return np.where((a > b) | (b != b), a, b).astype(np.float32)
-
-
-def clamp01(x):
-    return min2(max2(x, F(0)), F(1))
 
 
 def taps_double(samples):
@@ -38,12 +26,6 @@ def constants(projection, height, aperture_f_stops=0.0, sensor_height=0.0):
     f = 0.5 * hs * float(F(projection[5]))
     k = 0.5 * f * f / (n * hs) * float(height)
     return F(f), F(k)
-
-
-def frame_depth(g0x):
-    """D of a frame: PRIM_GBUFFER_D0.x with 0 (sky) read as FLT_MAX"""
-    g0x = np.asarray(g0x, np.float32)
-    return np.where(g0x == 0, FLT_MAX, g0x).astype(np.float32)
 
 
 def planar(depth, projection, flags=0):
@@ -107,10 +89,6 @@ def neighbour_max(tiles):
         for i in range(tx):
             out[j, i] = tiles[max(j - 1, 0):j + 2, max(i - 1, 0):i + 2].max()
     return out
-
-
-def colour(c):
-    return min2(max2(np.asarray(c, np.float32)[..., :3], F(0)), F(COLOUR_CLAMP))
 
 
 def gather(color, coc, z, nb, taps, details=None):

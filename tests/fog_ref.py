@@ -7,26 +7,11 @@
 (the k and E0 clamps at +-80, clamp01 of the linear ramp, the cosine's [0, 1], the colour clamp)."""
 import numpy as np
 
+from ref_num import COLOUR_CLAMP, FLT_MAX, clamp01, frame_depth, max2, min2  # noqa: F401  (re-exported)
+
 F = np.float32
 LINEAR, EXPONENTIAL, EXPONENTIAL_SQUARED, ATMOSPHERIC = 0, 1, 2, 3
 SKY, FOLLOW_SUN = 1, 2
-FLT_MAX = np.finfo(np.float32).max
-COLOUR_CLAMP = 65504.0
-
-
-def min2(a, b):
-    """the header's min: a when a < b or b is NaN, else b"""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return np.where((a < b) | (b != b), a, b).astype(np.float32)
-
-
-def max2(a, b):
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return np.where((a > b) | (b != b), a, b).astype(np.float32)
-
-
-def clamp01(x):
-    return min2(max2(x, F(0)), F(1))
 
 
 # ---------------------------------------------------------------- the two polynomials, from the header text
@@ -113,12 +98,6 @@ def host_constants(d, transform, sun=None):
         L = (v / np.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2])).astype(np.float32)
     arg = -float(F(d.height_falloff)) * (float(F(transform[13])) - float(F(d.height_reference)))
     return L, F(np.exp(min(max(arg, -80.0), 80.0)))
-
-
-def frame_depth(g0x):
-    """D of a frame: PRIM_GBUFFER_D0.x with 0 (sky) read as FLT_MAX"""
-    g0x = np.asarray(g0x, np.float32)
-    return np.where(g0x == 0, FLT_MAX, g0x).astype(np.float32)
 
 
 # ---------------------------------------------------------------- the restatement

@@ -2,36 +2,18 @@
 float32, evaluated in the header's order; min, max and clamp01 follow the post-processing section's NaN rule."""
 import numpy as np
 
+from ref_num import COLOUR_CLAMP, FLT_MAX, clamp01, colour, frame_depth, max2, min2  # noqa: F401  (re-exported)
+
 F = np.float32
 NO_JITTER = 1
-TILE, DEFAULT_SAMPLES, DEFAULT_RADIUS, DEFAULT_SOFTNESS, COLOUR_CLAMP = 32, 8, 32.0, 0.05, 65504.0
-FLT_MAX = np.finfo(np.float32).max
+TILE, DEFAULT_SAMPLES, DEFAULT_RADIUS, DEFAULT_SOFTNESS = 32, 8, 32.0, 0.05
 BAYER = np.array([[0, 8, 2, 10], [12, 4, 14, 6], [3, 11, 1, 9], [15, 7, 13, 5]], np.float32)
-
-
-def min2(a, b):
-    """the header's min: a when a < b or b is NaN, else b"""
-    return np.where((a < b) | (b != b), a, b).astype(np.float32)
-
-
-def max2(a, b):
-    return np.where((a > b) | (b != b), a, b).astype(np.float32)
-
-
-def clamp01(x):
-    return min2(max2(x, F(0)), F(1))
 
 
 def resolve(samples=0, max_radius=0.0, depth_softness=0.0):
     """the descriptor's defaults applied: (S, R, e_s)"""
     return (int(samples) or DEFAULT_SAMPLES, F(max_radius) if F(max_radius) != 0 else F(DEFAULT_RADIUS),
             F(depth_softness) if F(depth_softness) != 0 else F(DEFAULT_SOFTNESS))
-
-
-def frame_depth(g0x):
-    """Z of a frame: PRIM_GBUFFER_D0.x with 0 (sky) read as FLT_MAX"""
-    g0x = np.asarray(g0x, np.float32)
-    return np.where(g0x == 0, FLT_MAX, g0x).astype(np.float32)
 
 
 def pack(velocity, shutter, max_radius=0.0):
@@ -96,10 +78,6 @@ def cyl(d, r):
         rs = np.where(r > 0, r, F(1)).astype(np.float32)
         q = clamp01((d - F(0.95) * rs) / (F(1.05) * rs - F(0.95) * rs))
         return np.where(r > 0, F(1) - q * q * (F(3) - F(2) * q), F(0)).astype(np.float32)
-
-
-def colour(c):
-    return min2(max2(np.asarray(c, np.float32)[..., :3], F(0)), F(COLOUR_CLAMP))
 
 
 def gather(color, r, z, nb, samples=0, depth_softness=0.0, flags=0, details=None):

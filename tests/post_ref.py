@@ -6,19 +6,12 @@ below; a tie between the two gradients goes to the negative side (N or W), a tie
 import numpy as np
 
 import display_ref
+from ref_num import max2, min2  # noqa: F401  (re-exported)
 
 F = np.float32
 NEAREST, BILINEAR, CATMULL_ROM = range(3)
 EDGE_THRESHOLD, EDGE_THRESHOLD_MIN, SUBPIXEL = 0.166, 0.0833, 0.75
 WALK = (1.0, 2.0, 3.0, 4.0, 5.0, 6.5, 8.5, 10.5, 12.5, 14.5, 18.5, 26.5)   # steps of 1 1 1 1 1 1.5 2 2 2 2 4 8 pixels
-
-
-def min2(a, b):
-    return np.where((a < b) | np.isnan(b), a, b).astype(np.float32)
-
-
-def max2(a, b):
-    return np.where((a > b) | np.isnan(b), a, b).astype(np.float32)
 
 
 def axis_float(p):

@@ -8,12 +8,12 @@ probe, an engine's st_scene_occluded, or walk_ref's brute force. Given those bit
 polynomial, visibility by brute force over all triangles (walk_ref.trace), whose per-ray decision margin says which cells are ambiguous."""
 import numpy as np
 
-from fog_ref import FLT_MAX, clamp01, exp_, max2, min2
+from fog_ref import exp_
 from geometry_extremes import RAY_DTYPE
+from ref_num import COLOUR_CLAMP, FLT_MAX, clamp01, max2, min2  # noqa: F401  (re-exported)
 
 F = np.float32
 FOLLOW_SUN, LIGHT_EXTINCTION = 1, 2
-COLOUR_CLAMP = 65504.0
 BAYER = np.array([[0, 8, 2, 10], [12, 4, 14, 6], [3, 11, 1, 9], [15, 7, 13, 5]], np.float32)
 JITTER = ((BAYER + F(0.5)) / F(16)).astype(np.float32)   # [cy & 3][cx & 3]
 PI32 = F(3.14159265358979323846)

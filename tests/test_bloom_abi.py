@@ -5,19 +5,18 @@ needs a device, and the numpy restatement (bloom_ref.py) at hand-computed cases.
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import bloom_ref as R
+import output_chain_abi as A
 from parity import bits_equal_mask
 from strolle_amd import Engine, StrolleError, Tonemap, bloom_desc, display_desc, scenes
+from output_chain_abi import ST_ERR_INVALID_ARGUMENT, ST_ERR_NO_DEVICE, ST_OK, host_camera as _host_camera
 from strolle_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ST_OK, ST_ERR_INVALID_ARGUMENT, ST_ERR_NO_DEVICE, ST_ERR_UNKNOWN_CAMERA = 0, 1, 2, 3
 ENTRY_POINTS = ("st_camera_set_bloom", "st_camera_get_bloom", "st_bloom_plan", "st_bloom_process", "st_debug_set_bloom_tail")
 FIELDS = ["struct_size", "flags", "levels", "intensity", "low_frequency_boost", "low_frequency_boost_curvature", "high_pass_frequency",
           "threshold", "threshold_softness", "clamp"]
@@ -25,36 +24,14 @@ F = np.float32
 
 
 def test_entry_points_are_exported_declared_and_bound():
-    lib = api.load_library()
-    header = open(os.path.join(ROOT, "include", "strolle_hip.h")).read()
-    ffi = open(os.path.join(ROOT, "rust", "strolle-hip", "src", "ffi.rs")).read()
-    for name in ENTRY_POINTS:
-        assert hasattr(lib, name), name
-        assert re.search(r"\bint %s\(" % name, header), name
-        assert re.search(r"pub fn %s\(" % name, ffi), name
-    c_body = re.search(r"typedef struct StBloomDesc \{(.*?)\} StBloomDesc;", re.sub(r"/\*.*?\*/", "", header, flags=re.S), re.S).group(1)
-    c_fields = [n.strip() for d in c_body.split(";") if d.strip() for n in d.strip().split(None, 1)[1].split(",")]
-    r_fields = re.findall(r"pub (\w+):", re.search(r"pub struct StBloomDesc \{(.*?)\n\}", ffi, re.S).group(1))
-    assert c_fields == r_fields == [f for f, _ in api.StBloomDesc._fields_] == FIELDS
+    header, _ = A.exports_header_and_ffi_agree("StBloomDesc", FIELDS, ENTRY_POINTS, [("ST_BLOOM_ADDITIVE", 1), ("ST_BLOOM_FIREFLY_SUPPRESS", 2)])
     assert re.search(r"ST_BLOOM_ADDITIVE = 1, ST_BLOOM_FIREFLY_SUPPRESS = 2\b", header)
-    assert "pub const ST_BLOOM_ADDITIVE: u32 = 1;" in ffi and "pub const ST_BLOOM_FIREFLY_SUPPRESS: u32 = 2;" in ffi
     assert (api.BLOOM_ADDITIVE, api.BLOOM_FIREFLY_SUPPRESS) == (R.ADDITIVE, R.FIREFLY_SUPPRESS) == (1, 2)
 
 
 def test_desc_layout_agrees_between_c_and_ctypes(tmp_path):
-    gcc = shutil.which("gcc") or shutil.which("cc")
-    if gcc is None:
-        pytest.fail("no C compiler on PATH")
-    src = tmp_path / "layout.c"
-    offs = ", ".join("offsetof(StBloomDesc, %s)" % f for f in FIELDS)
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "strolle_hip.h"\nint main(void) { printf("%zu' + " %zu" * len(FIELDS)
-                   + ' %d %d\\n", sizeof(StBloomDesc), ' + offs + ', ST_BLOOM_ADDITIVE, ST_BLOOM_FIREFLY_SUPPRESS); return 0; }\n')
-    exe = tmp_path / "layout"
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = list(map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()))
-    D = api.StBloomDesc
+    got = A.c_layout(tmp_path, "StBloomDesc", FIELDS, ["ST_BLOOM_ADDITIVE", "ST_BLOOM_FIREFLY_SUPPRESS"])
     assert got == [40] + [4 * k for k in range(len(FIELDS))] + [1, 2]
-    assert got[:1 + len(FIELDS)] == [C.sizeof(D)] + [getattr(D, f).offset for f in FIELDS]
 
 
 def _d(**kw):
@@ -62,12 +39,6 @@ def _d(**kw):
     for k, v in kw.items():
         setattr(d, k, v)
     return d
-
-
-def _host_camera(size=(64, 48)):
-    e = Engine(device=-1)
-    scenes.build_cornell(e)
-    return e, e.create_camera(scenes.cornell_camera(size))
 
 
 inf, nan = float("inf"), float("nan")
@@ -83,26 +54,17 @@ GOOD = [dict(levels=0), dict(levels=1), dict(levels=8), dict(intensity=0.0), dic
         dict(threshold=0.0), dict(threshold_softness=0.0), dict(threshold_softness=1.0), dict(clamp=0.0)]
 
 
+def _plan_status(b, kw, status):
+    assert b.bloom_plan(C.byref(_d(**kw)), 64, 48, None, None, None) == status, kw
+
+
 def test_argument_errors_on_a_host_only_engine():
     e, cam = _host_camera()
-    b, h = e._b, e._h
-
-    def st(d, camera=cam, engine=h):
-        return b.camera_set_bloom(engine, camera, C.byref(d) if d is not None else None)
-
-    assert st(_d()) == ST_OK and st(None) == ST_OK
-    assert st(_d(), engine=None) == ST_ERR_INVALID_ARGUMENT
-    assert st(_d(), camera=cam + 99) == ST_ERR_UNKNOWN_CAMERA and st(None, camera=cam + 99) == ST_ERR_UNKNOWN_CAMERA
-    for kw in BAD:
-        assert st(_d(**kw)) == ST_ERR_INVALID_ARGUMENT, kw
-        assert b.bloom_plan(C.byref(_d(**kw)), 64, 48, None, None, None) == ST_ERR_INVALID_ARGUMENT, kw
-    for kw in GOOD:
-        assert st(_d(**kw)) == ST_OK, kw
-        assert b.bloom_plan(C.byref(_d(**kw)), 64, 48, None, None, None) == ST_OK, kw
+    b = e._b
+    A.argument_errors(e, cam, "camera_set_bloom", "camera_get_bloom", _d, BAD, GOOD,
+                      each_bad=lambda kw: _plan_status(b, kw, ST_ERR_INVALID_ARGUMENT),
+                      each_good=lambda kw: _plan_status(b, kw, ST_OK))
     assert b.bloom_plan(None, 64, 48, None, None, None) == ST_ERR_INVALID_ARGUMENT
-    assert b.camera_get_bloom(h, cam, None, None) == ST_OK
-    assert b.camera_get_bloom(h, cam + 99, None, None) == ST_ERR_UNKNOWN_CAMERA
-    assert b.camera_get_bloom(None, cam, None, None) == ST_ERR_INVALID_ARGUMENT
     with pytest.raises(StrolleError):
         e.set_bloom(cam, levels=12)
     e.close()
@@ -154,20 +116,8 @@ def test_set_get_round_trip_and_survival_on_a_host_only_engine():
 
 def test_bloom_and_a_window_exclude_each_other_on_a_host_only_engine():
     e, cam = _host_camera()
-    b, h = e._b, e._h
     d = _d()
-    assert b.camera_set_window(h, cam, 0, 0, 32, 48) == ST_OK
-    assert b.camera_set_bloom(h, cam, C.byref(d)) == ST_ERR_INVALID_ARGUMENT   # the window came first
-    assert not e.bloom(cam)[1]
-    assert b.camera_set_bloom(h, cam, None) == ST_OK                            # turning it off is always fine
-    assert b.camera_set_window(h, cam, 0, 0, 0, 0) == ST_OK                     # back to the whole frame
-    assert b.camera_set_bloom(h, cam, C.byref(d)) == ST_OK
-    assert b.camera_set_window(h, cam, 16, 0, 64, 48) == ST_ERR_INVALID_ARGUMENT   # bloom came first
-    assert b.camera_set_window(h, cam, 0, 8, 64, 48) == ST_ERR_INVALID_ARGUMENT
-    assert b.camera_set_rows(h, cam, 0, 24) == ST_ERR_INVALID_ARGUMENT
-    assert b.camera_set_window(h, cam, 0, 0, 64, 48) == ST_OK                   # the whole frame is no tile
-    assert b.camera_set_bloom(h, cam, None) == ST_OK
-    assert b.camera_set_window(h, cam, 16, 0, 64, 48) == ST_OK                  # off: windows work again
+    A.node_and_window_exclude_each_other(e, cam, "camera_set_bloom", d, lambda: e.bloom(cam)[1])
     e.close()
 
 

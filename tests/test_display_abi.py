@@ -4,55 +4,29 @@ round-trip there, the device-only calls say so, and the numpy restatement (displ
 import ctypes as C
 import math
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import display_ref as R
-from strolle_amd import Engine, StrolleError, Tonemap, display_desc, scenes
+import output_chain_abi as A
+from strolle_amd import StrolleError, Tonemap, display_desc, scenes
+from output_chain_abi import ST_ERR_INVALID_ARGUMENT, ST_ERR_NO_DEVICE, ST_ERR_UNKNOWN_CAMERA, ST_OK, host_camera as _host_camera
 from strolle_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ST_OK, ST_ERR_INVALID_ARGUMENT, ST_ERR_NO_DEVICE, ST_ERR_UNKNOWN_CAMERA = 0, 1, 2, 3
 ENTRY_POINTS = ("st_camera_set_display", "st_camera_get_display", "st_camera_exposure", "st_debug_camera_histogram")
 FIELDS = ["struct_size", "tonemap", "flags", "exposure_ev", "ev_min", "ev_max", "low_fraction", "high_fraction", "max_ev_step_up", "max_ev_step_down"]
 
 
 def test_entry_points_are_exported_declared_and_bound():
-    lib = api.load_library()
-    header = open(os.path.join(ROOT, "include", "strolle_hip.h")).read()
-    ffi = open(os.path.join(ROOT, "rust", "strolle-hip", "src", "ffi.rs")).read()
-    for name in ENTRY_POINTS:
-        assert hasattr(lib, name), name
-        assert re.search(r"\bint %s\(" % name, header), name
-        assert re.search(r"pub fn %s\(" % name, ffi), name
-    c_body = re.search(r"typedef struct StDisplayDesc \{(.*?)\} StDisplayDesc;", re.sub(r"/\*.*?\*/", "", header, flags=re.S), re.S).group(1)
-    c_fields = [n.strip() for d in c_body.split(";") if d.strip() for n in d.strip().split(None, 1)[1].split(",")]
-    r_fields = re.findall(r"pub (\w+):", re.search(r"pub struct StDisplayDesc \{(.*?)\n\}", ffi, re.S).group(1))
-    assert c_fields == r_fields == [f for f, _ in api.StDisplayDesc._fields_] == FIELDS
-    for k, t in enumerate(Tonemap):
-        assert re.search(r"ST_TONEMAP_%s = %d\b" % (t.name, t.value), header), t
-        assert re.search(r"pub const ST_TONEMAP_%s: u32 = %d;" % (t.name, t.value), ffi), t
+    _, ffi = A.exports_header_and_ffi_agree("StDisplayDesc", FIELDS, ENTRY_POINTS, [("ST_TONEMAP_%s" % t.name, t.value) for t in Tonemap])
     assert "pub const ST_DISPLAY_AUTO_EXPOSURE: u32 = 1;" in ffi
 
 
 def test_desc_layout_agrees_between_c_and_ctypes(tmp_path):
-    gcc = shutil.which("gcc") or shutil.which("cc")
-    if gcc is None:
-        pytest.fail("no C compiler on PATH")
-    src = tmp_path / "layout.c"
-    offs = ", ".join("offsetof(StDisplayDesc, %s)" % f for f in FIELDS)
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "strolle_hip.h"\nint main(void) { printf("%zu' + " %zu" * len(FIELDS)
-                   + ' %d %d %d\\n", sizeof(StDisplayDesc), ' + offs + ', ST_DISPLAY_AUTO_EXPOSURE, ST_TONEMAP_ACES_FITTED, ST_TONEMAP_PBR_NEUTRAL); return 0; }\n')
-    exe = tmp_path / "layout"
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = list(map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()))
-    D = api.StDisplayDesc
+    got = A.c_layout(tmp_path, "StDisplayDesc", FIELDS, ["ST_DISPLAY_AUTO_EXPOSURE", "ST_TONEMAP_ACES_FITTED", "ST_TONEMAP_PBR_NEUTRAL"])
     assert got == [40] + [4 * k for k in range(len(FIELDS))] + [1, 3, 4]
-    assert got[:1 + len(FIELDS)] == [C.sizeof(D)] + [getattr(D, f).offset for f in FIELDS]
     assert got[-3:] == [api.DISPLAY_AUTO_EXPOSURE, Tonemap.ACES_FITTED, Tonemap.PBR_NEUTRAL]
 
 
@@ -64,10 +38,8 @@ def _d(**kw):
 
 
 def test_argument_errors_on_a_host_only_engine():
-    e = Engine(device=-1)
+    e, cam = _host_camera()
     b, h = e._b, e._h
-    scenes.build_cornell(e)
-    cam = e.create_camera(scenes.cornell_camera((64, 48)))
 
     def st(d, camera=cam, engine=h):
         return b.camera_set_display(engine, camera, C.byref(d) if d is not None else None)
@@ -113,9 +85,7 @@ def test_argument_errors_on_a_host_only_engine():
 
 
 def test_set_get_round_trip_on_a_host_only_engine():
-    e = Engine(device=-1)
-    scenes.build_cornell(e)
-    cam = e.create_camera(scenes.cornell_camera((64, 48)))
+    e, cam = _host_camera()
     d0, on0 = e.display(cam)
     assert not on0 and d0.struct_size == C.sizeof(api.StDisplayDesc) and all(getattr(d0, f) == 0 for f in FIELDS[1:])
     want = display_desc(Tonemap.PBR_NEUTRAL, exposure_ev=-1.25, auto_exposure=True, ev_min=-10.0, ev_max=6.0, low_fraction=0.05,
@@ -138,10 +108,8 @@ def test_set_get_round_trip_on_a_host_only_engine():
 
 
 def test_auto_exposure_and_a_window_exclude_each_other_on_a_host_only_engine():
-    e = Engine(device=-1)
+    e, cam = _host_camera()
     b, h = e._b, e._h
-    scenes.build_cornell(e)
-    cam = e.create_camera(scenes.cornell_camera((64, 48)))
     auto = _d()
     assert b.camera_set_window(h, cam, 0, 0, 32, 48) == ST_OK
     assert b.camera_set_display(h, cam, C.byref(auto)) == ST_ERR_INVALID_ARGUMENT   # the window came first

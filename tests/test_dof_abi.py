@@ -6,19 +6,18 @@ at cases worked out by hand."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import dof_ref as R
+import output_chain_abi as A
 from strolle_amd import Engine, StrolleError, Tonemap, display_desc, dof_desc, dof_plan, scenes
+from output_chain_abi import ST_ERR_INVALID_ARGUMENT, ST_ERR_NO_DEVICE, ST_OK, host_camera as _host_camera
 from strolle_amd import api
 from strolle_amd.api import dist_grid
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ST_OK, ST_ERR_INVALID_ARGUMENT, ST_ERR_NO_DEVICE, ST_ERR_UNKNOWN_CAMERA = 0, 1, 2, 3
 ENTRY_POINTS = ("st_camera_set_dof", "st_camera_get_dof", "st_dof_plan", "st_dof_process")
 FIELDS = ["struct_size", "flags", "samples", "focal_distance", "aperture_f_stops", "sensor_height", "max_radius", "focus_x", "focus_y", "_pad"]
 F = np.float32
@@ -27,38 +26,15 @@ ORTHOGRAPHIC = [0.5, 0, 0, 0, 0, 0.5, 0, 0, 0, 0, -0.01, 0, 0, 0, 1.0, 1.0]
 
 
 def test_entry_points_are_exported_declared_and_bound():
-    lib = api.load_library()
-    header = open(os.path.join(ROOT, "include", "strolle_hip.h")).read()
-    ffi = open(os.path.join(ROOT, "rust", "strolle-hip", "src", "ffi.rs")).read()
-    for name in ENTRY_POINTS:
-        assert hasattr(lib, name), name
-        assert re.search(r"\bint %s\(" % name, header), name
-        assert re.search(r"pub fn %s\(" % name, ffi), name
-    c_body = re.search(r"typedef struct StDofDesc \{(.*?)\} StDofDesc;", re.sub(r"/\*.*?\*/", "", header, flags=re.S), re.S).group(1)
-    c_fields = [n.strip() for d in c_body.split(";") if d.strip() for n in d.strip().split(None, 1)[1].split(",")]
-    r_fields = re.findall(r"pub (\w+):", re.search(r"pub struct StDofDesc \{(.*?)\n\}", ffi, re.S).group(1))
-    assert c_fields == r_fields == [f for f, _ in api.StDofDesc._fields_] == FIELDS
-    assert re.search(r"ST_DOF_AUTOFOCUS = 1\b", header) and re.search(r"ST_DOF_PLANAR_DEPTH = 2\b", header)
-    assert "pub const ST_DOF_AUTOFOCUS: u32 = 1;" in ffi and "pub const ST_DOF_PLANAR_DEPTH: u32 = 2;" in ffi
+    header, _ = A.exports_header_and_ffi_agree("StDofDesc", FIELDS, ENTRY_POINTS, [("ST_DOF_AUTOFOCUS", 1), ("ST_DOF_PLANAR_DEPTH", 2)])
     assert api.DOF_AUTOFOCUS == R.AUTOFOCUS == 1 and api.DOF_PLANAR_DEPTH == R.PLANAR_DEPTH == 2
     # the three new kernel slots need a larger profiler table, and api.py sizes its array with the constant
     assert re.search(r"ST_PROFILE_MAX_KERNELS = 64\b", header) and api.PROFILE_MAX_KERNELS == 64
 
 
 def test_desc_layout_agrees_between_c_and_ctypes(tmp_path):
-    gcc = shutil.which("gcc") or shutil.which("cc")
-    if gcc is None:
-        pytest.fail("no C compiler on PATH")
-    src = tmp_path / "layout.c"
-    offs = ", ".join("offsetof(StDofDesc, %s)" % f for f in FIELDS)
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "strolle_hip.h"\nint main(void) { printf("%zu' + " %zu" * len(FIELDS)
-                   + ' %d %d\\n", sizeof(StDofDesc), ' + offs + ', ST_DOF_AUTOFOCUS, ST_DOF_PLANAR_DEPTH); return 0; }\n')
-    exe = tmp_path / "layout"
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = list(map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()))
-    D = api.StDofDesc
+    got = A.c_layout(tmp_path, "StDofDesc", FIELDS, ["ST_DOF_AUTOFOCUS", "ST_DOF_PLANAR_DEPTH"])
     assert got == [40, 0, 4, 8, 12, 16, 20, 24, 28, 32, 36, 1, 2]
-    assert got[:1 + len(FIELDS)] == [C.sizeof(D)] + [getattr(D, f).offset for f in FIELDS]
 
 
 def _d(**kw):
@@ -66,12 +42,6 @@ def _d(**kw):
     for k, v in kw.items():
         setattr(d, k, v)
     return d
-
-
-def _host_camera(size=(64, 48)):
-    e = Engine(device=-1)
-    scenes.build_cornell(e)
-    return e, e.create_camera(scenes.cornell_camera(size))
 
 
 inf, nan = float("inf"), float("nan")
@@ -85,25 +55,16 @@ GOOD = [dict(flags=1), dict(flags=2), dict(flags=3, focus_x=1.0, focus_y=0.0), d
         dict(max_radius=0.0), dict(max_radius=32.0), dict(max_radius=0.25), dict(focus_x=7.0, focus_y=nan), dict(_pad=123)]   # without AUTOFOCUS the point is not looked at
 
 
+def _plan_status(b, kw, status):
+    assert b.dof_plan(C.byref(_d(**kw)), 64, 48, None, None, None) == status, kw
+
+
 def test_argument_errors_on_a_host_only_engine():
     e, cam = _host_camera()
-    b, h = e._b, e._h
-
-    def st(d, camera=cam, engine=h):
-        return b.camera_set_dof(engine, camera, C.byref(d) if d is not None else None)
-
-    assert st(_d()) == ST_OK and st(None) == ST_OK
-    assert st(_d(), engine=None) == ST_ERR_INVALID_ARGUMENT
-    assert st(_d(), camera=cam + 99) == ST_ERR_UNKNOWN_CAMERA and st(None, camera=cam + 99) == ST_ERR_UNKNOWN_CAMERA
-    for kw in BAD:
-        assert st(_d(**kw)) == ST_ERR_INVALID_ARGUMENT, kw
-        assert b.dof_plan(C.byref(_d(**kw)), 64, 48, None, None, None) == ST_ERR_INVALID_ARGUMENT, kw
-    for kw in GOOD:
-        assert st(_d(**kw)) == ST_OK, kw
-        assert b.dof_plan(C.byref(_d(**kw)), 64, 48, None, None, None) == ST_OK, kw
-    assert b.camera_get_dof(h, cam, None, None) == ST_OK
-    assert b.camera_get_dof(h, cam + 99, None, None) == ST_ERR_UNKNOWN_CAMERA
-    assert b.camera_get_dof(None, cam, None, None) == ST_ERR_INVALID_ARGUMENT
+    b = e._b
+    A.argument_errors(e, cam, "camera_set_dof", "camera_get_dof", _d, BAD, GOOD,
+                      each_bad=lambda kw: _plan_status(b, kw, ST_ERR_INVALID_ARGUMENT),
+                      each_good=lambda kw: _plan_status(b, kw, ST_OK))
     assert b.dof_plan(None, 64, 48, None, None, None) == ST_ERR_INVALID_ARGUMENT
     assert b.dof_plan(C.byref(_d()), 16385, 48, None, None, None) == ST_ERR_INVALID_ARGUMENT
     assert b.dof_plan(C.byref(_d()), 64, 16385, None, None, None) == ST_ERR_INVALID_ARGUMENT
@@ -176,20 +137,8 @@ def test_set_get_round_trip_defaults_and_survival_on_a_host_only_engine():
 
 def test_depth_of_field_and_a_window_exclude_each_other_on_a_host_only_engine():
     e, cam = _host_camera()
-    b, h = e._b, e._h
     d = _d()
-    assert b.camera_set_window(h, cam, 0, 0, 32, 48) == ST_OK
-    assert b.camera_set_dof(h, cam, C.byref(d)) == ST_ERR_INVALID_ARGUMENT   # the window came first
-    assert not e.get_dof(cam)[1]
-    assert b.camera_set_dof(h, cam, None) == ST_OK                            # turning it off is always fine
-    assert b.camera_set_window(h, cam, 0, 0, 0, 0) == ST_OK                   # back to the whole frame
-    assert b.camera_set_dof(h, cam, C.byref(d)) == ST_OK
-    assert b.camera_set_window(h, cam, 16, 0, 64, 48) == ST_ERR_INVALID_ARGUMENT   # depth of field came first
-    assert b.camera_set_window(h, cam, 0, 8, 64, 48) == ST_ERR_INVALID_ARGUMENT
-    assert b.camera_set_rows(h, cam, 0, 24) == ST_ERR_INVALID_ARGUMENT
-    assert b.camera_set_window(h, cam, 0, 0, 64, 48) == ST_OK                 # the whole frame is no tile
-    assert b.camera_set_dof(h, cam, None) == ST_OK
-    assert b.camera_set_window(h, cam, 16, 0, 64, 48) == ST_OK                # off: windows work again
+    A.node_and_window_exclude_each_other(e, cam, "camera_set_dof", d, lambda: e.get_dof(cam)[1])
     e.close()
     # st_dist_set_partition and st_dist_set_grid: two ranks through the in-process transport
     ranks = []

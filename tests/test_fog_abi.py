@@ -8,20 +8,19 @@ import json
 import math
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import fog_cases as K
 import fog_ref as R
+import output_chain_abi as A
 from strolle_amd import Engine, FogFalloff, StrolleError, Tonemap, display_desc, fog_desc, scenes
+from output_chain_abi import ST_ERR_INVALID_ARGUMENT, ST_ERR_NO_DEVICE, ST_OK, host_camera as _host_camera
 from strolle_amd import api
 from strolle_amd.api import dist_grid
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ST_OK, ST_ERR_INVALID_ARGUMENT, ST_ERR_NO_DEVICE, ST_ERR_UNKNOWN_CAMERA = 0, 1, 2, 3
 ENTRY_POINTS = ("st_camera_set_fog", "st_camera_get_fog", "st_fog_process")
 FIELDS = ["struct_size", "falloff", "flags", "_pad", "color", "start", "end", "density", "height_falloff", "height_reference", "sky_distance", "extinction",
           "inscattering", "light_color", "light_exponent", "light_direction", "_pad2"]
@@ -31,43 +30,19 @@ inf, nan = float("inf"), float("nan")
 PERSPECTIVE = [1.5, 0, 0, 0, 0, 2.0, 0, 0, 0, 0, 0, -1.0, 0, 0, 0.1, 0]   # column major, infinite reverse-z: [15] == 0
 ORTHOGRAPHIC = [0.5, 0, 0, 0, 0, 0.5, 0, 0, 0, 0, -0.01, 0, 0, 0, 1.0, 1.0]
 IDENTITY = [1.0, 0, 0, 0, 0, 1.0, 0, 0, 0, 0, 1.0, 0, 0, 0, 0, 1.0]
+FALLOFFS = ("LINEAR", "EXPONENTIAL", "EXPONENTIAL_SQUARED", "ATMOSPHERIC")
 
 
 def test_entry_points_are_exported_declared_and_bound():
-    lib = api.load_library()
-    header = open(os.path.join(ROOT, "include", "strolle_hip.h")).read()
-    ffi = open(os.path.join(ROOT, "rust", "strolle-hip", "src", "ffi.rs")).read()
-    for name in ENTRY_POINTS:
-        assert hasattr(lib, name), name
-        assert re.search(r"\bint %s\(" % name, header), name
-        assert re.search(r"pub fn %s\(" % name, ffi), name
-    c_body = re.search(r"typedef struct StFogDesc \{(.*?)\} StFogDesc;", re.sub(r"/\*.*?\*/", "", header, flags=re.S), re.S).group(1)
-    c_fields = [re.sub(r"\[\d+\]", "", n.strip()) for d in c_body.split(";") if d.strip() for n in d.strip().split(None, 1)[1].split(",")]
-    r_fields = re.findall(r"pub (\w+):", re.search(r"pub struct StFogDesc \{(.*?)\n\}", ffi, re.S).group(1))
-    assert c_fields == r_fields == [f for f, _ in api.StFogDesc._fields_] == FIELDS
-    for k, name in enumerate(("LINEAR", "EXPONENTIAL", "EXPONENTIAL_SQUARED", "ATMOSPHERIC")):
-        assert re.search(r"ST_FOG_%s = %d\b" % (name, k), header) and "pub const ST_FOG_%s: u32 = %d;" % (name, k) in ffi
+    A.exports_header_and_ffi_agree("StFogDesc", FIELDS, ENTRY_POINTS, [("ST_FOG_%s" % n, k) for k, n in enumerate(FALLOFFS)] + [("ST_FOG_SKY", 1), ("ST_FOG_FOLLOW_SUN", 2)])
+    for k, name in enumerate(FALLOFFS):
         assert int(FogFalloff[name]) == getattr(R, name) == k
-    assert re.search(r"ST_FOG_SKY = 1\b", header) and re.search(r"ST_FOG_FOLLOW_SUN = 2\b", header)
-    assert "pub const ST_FOG_SKY: u32 = 1;" in ffi and "pub const ST_FOG_FOLLOW_SUN: u32 = 2;" in ffi
     assert api.FOG_SKY == R.SKY == 1 and api.FOG_FOLLOW_SUN == R.FOLLOW_SUN == 2
 
 
 def test_desc_layout_agrees_between_c_and_ctypes(tmp_path):
-    gcc = shutil.which("gcc") or shutil.which("cc")
-    if gcc is None:
-        pytest.fail("no C compiler on PATH")
-    src = tmp_path / "layout.c"
-    offs = ", ".join("offsetof(StFogDesc, %s)" % f for f in FIELDS)
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "strolle_hip.h"\nint main(void) { printf("%zu' + " %zu" * len(FIELDS)
-                   + ' %d %d %d %d %d %d\\n", sizeof(StFogDesc), ' + offs + ', ST_FOG_LINEAR, ST_FOG_EXPONENTIAL, ST_FOG_EXPONENTIAL_SQUARED, ST_FOG_ATMOSPHERIC, '
-                   'ST_FOG_SKY, ST_FOG_FOLLOW_SUN); return 0; }\n')
-    exe = tmp_path / "layout"
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = list(map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()))
-    D = api.StFogDesc
+    got = A.c_layout(tmp_path, "StFogDesc", FIELDS, ["ST_FOG_%s" % n for n in FALLOFFS] + ["ST_FOG_SKY", "ST_FOG_FOLLOW_SUN"])
     assert got == [112] + OFFSETS + [0, 1, 2, 3, 1, 2]
-    assert got[:1 + len(FIELDS)] == [C.sizeof(D)] + [getattr(D, f).offset for f in FIELDS]
 
 
 def _d(**kw):
@@ -84,12 +59,6 @@ def _d(**kw):
         else:
             setattr(d, k, v)
     return d
-
-
-def _host_camera(size=(64, 48)):
-    e = Engine(device=-1)
-    scenes.build_cornell(e)
-    return e, e.create_camera(scenes.cornell_camera(size))
 
 
 BAD = [dict(struct_size=108), dict(struct_size=116), dict(struct_size=0), dict(falloff=4), dict(falloff=0xffffffff), dict(flags=4), dict(flags=0x80000001),
@@ -113,22 +82,10 @@ GOOD = [dict(falloff=f) for f in range(4)] + [dict(flags=1), dict(flags=2), dict
 
 def test_argument_errors_on_a_host_only_engine():
     e, cam = _host_camera()
-    b, h = e._b, e._h
-
-    def st(d, camera=cam, engine=h):
-        return b.camera_set_fog(engine, camera, C.byref(d) if d is not None else None)
-
-    assert st(_d()) == ST_OK and st(None) == ST_OK
-    assert st(_d(), engine=None) == ST_ERR_INVALID_ARGUMENT
-    assert st(_d(), camera=cam + 99) == ST_ERR_UNKNOWN_CAMERA and st(None, camera=cam + 99) == ST_ERR_UNKNOWN_CAMERA
-    for kw in BAD:
-        assert st(_d(**kw)) == ST_ERR_INVALID_ARGUMENT, kw
+    def still_off(kw):
         assert not e.get_fog(cam)[1], kw   # a refused desc leaves the setting as it was
-    for kw in GOOD:
-        assert st(_d(**kw)) == ST_OK, kw
-    assert b.camera_get_fog(h, cam, None, None) == ST_OK
-    assert b.camera_get_fog(h, cam + 99, None, None) == ST_ERR_UNKNOWN_CAMERA
-    assert b.camera_get_fog(None, cam, None, None) == ST_ERR_INVALID_ARGUMENT
+
+    A.argument_errors(e, cam, "camera_set_fog", "camera_get_fog", _d, BAD, GOOD, each_bad=still_off)
     with pytest.raises(StrolleError):
         e.set_fog(cam, falloff=7)
     e.close()

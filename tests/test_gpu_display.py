@@ -9,58 +9,23 @@ import pytest
 import torch
 
 import display_ref as R
+from output_chain import Out as _Out, _engine, _frame
 from parity import assert_bits_equal
-from strolle_amd import CameraMode, Engine, OutputFormat, Sun, Tonemap, display_desc, scenes
+from strolle_amd import CameraMode, OutputFormat, Tonemap, display_desc, scenes
 
 pytestmark = pytest.mark.gpu
 SIZE = (64, 48)
 AWAY = ((0.0, 1.0, 3.2), (0.0, 1.0, 10.0))   # from the Cornell camera's eye, looking away from the box: every pixel is sky
-BPP = {0: 16, 1: 8, 2: 4, 3: 4}
 MODES = [("image_denoise", CameraMode.IMAGE, True, 0), ("image", CameraMode.IMAGE, False, 0), ("di_diffuse", CameraMode.DI_DIFFUSE, True, 0),
          ("reference", CameraMode.REFERENCE, False, 1)]
-
-
-def _engine(exact, scene="cornell"):
-    e = Engine(device=0, exact=exact)
-    if scene == "cornell":
-        scenes.build_cornell(e)
-    else:
-        scenes.build_dungeon(e)
-        e.update_sun(Sun(azimuth=0.6, altitude=0.5))   # the sun up: lit areas far above 1
-    e.set_seed(7)
-    return e
 
 
 def _camera(scene, mode=CameraMode.IMAGE, denoise=True, depth=0, size=SIZE):
     return (scenes.cornell_camera if scene == "cornell" else scenes.dungeon_camera)(size, mode, denoise=denoise, depth=depth)
 
 
-class Out:
-    """a device output buffer of one format"""
-
-    def __init__(self, fmt, size=SIZE):
-        self.fmt, self.size = int(fmt), size
-        self.t = torch.zeros(size[1] * size[0] * BPP[self.fmt], dtype=torch.uint8, device="cuda:0")
-
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def get(self):
-        a = self.t.cpu().numpy()
-        w, h = self.size
-        if self.fmt == 0:
-            return a.view(np.float32).reshape(h, w, 4).copy()
-        if self.fmt == 1:
-            return a.view(np.float16).reshape(h, w, 4).copy()
-        return a.reshape(h, w, 4).copy()
-
-
-def _frame(e, cam, out, stream=None):
-    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-    e.tick(s)
-    e.render_camera(cam, out.ptr(), s)
-    torch.cuda.synchronize()
-    return out.get()
+def Out(fmt, size=SIZE):
+    return _Out(fmt, size)
 
 
 def _check(got, hdr, op, s, fmt, exact, what):

@@ -13,32 +13,20 @@ import torch
 
 import display_ref
 import dof_ref as R
-from parity import assert_bits_equal
-from strolle_amd import (Aov, Buffer, Camera, CameraMode, Engine, OutputFormat, PassBit, ResampleFilter, Tonemap, aov_planes, bloom_desc, display_desc, dof_desc,
+import output_chain as C
+from output_chain import Depth, Out, _bits, _check, _engine, _image, _moving, _proj, _scene_camera
+from strolle_amd import (Buffer, Engine, OutputFormat, PassBit, ResampleFilter, Tonemap, bloom_desc, display_desc, dof_desc,
                          dof_plan, motion_blur_desc, post_desc, scenes)
-from test_gpu_bloom import Out, _check, _engine, _image
 
 pytestmark = pytest.mark.gpu
 SIZE = (72, 52)
 SIZES = [(72, 52), (33, 21), (32, 32), (5, 5)]
 F = np.float32
 nan, inf = float("nan"), float("inf")
-_REFS = {}
 
 
 def _ref(key, make):
-    if key not in _REFS:   # computed once, shared by the two builds
-        _REFS[key] = make()
-    return _REFS[key]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _proj(cam: Camera):
-    """the 16 floats of a camera's projection, column major"""
-    return np.asarray(cam.projection, np.float32).T.reshape(-1).copy()
+    return C._ref(__name__, key, make)
 
 
 def _projection(w, h):
@@ -47,6 +35,9 @@ def _projection(w, h):
 
 # A lens that blurs at these sizes: a 0.5 m sensor at f/1 focused at 3 m. At 45 degrees f = 0.60 m, and at H = 52 K = 18.9 px m, A = 7.9 px.
 LENS = dict(focal_distance=3.0, sensor_height=0.5, aperture_f_stops=1.0)
+AUTO = dict(samples=32, autofocus=(0.5, 0.5), sensor_height=0.5, focal_distance=3.0)
+NODE = C.Node("set_dof", "get_dof", "depth of field", "the focused frame differs", ("dof_pack", "dof_neighbour", "dof_gather"), AUTO,
+              cleared=dict(samples=4, **LENS), skipped=dict(samples=4, autofocus=(0.5, 0.5), **LENS), recreated=LENS)
 
 
 # ---------------------------------------------------------------- synthetic inputs
@@ -192,29 +183,6 @@ def test_properties_of_the_filter(exact):
 
 
 # ---------------------------------------------------------------- 3. whole frames
-class Depth:
-    """D of the frame just rendered: PRIM_GBUFFER_D0.x of the frame's parity. Which of the two G-buffers the frame wrote is found by what
-    changed since the last look (under a static camera the two are equal anyway)."""
-
-    def __init__(self):
-        self.prev = {}
-
-    def read(self, e, cam, size):
-        g = {b: e.read_buffer(cam, b) for b in (Buffer.PRIM_GBUFFER_D0_A, Buffer.PRIM_GBUFFER_D0_B)}
-        changed = [b for b in g if b not in self.prev or not np.array_equal(_bits(self.prev[b]), _bits(g[b]))]
-        if len(self.prev) == 0:   # the first frame: the other plane is still zero
-            changed = [b for b in g if _bits(g[b]).any()]
-        self.prev = g
-        assert len(changed) <= 1, "a frame writes one of the two G-buffers"
-        cur = g[changed[0]] if changed else g[Buffer.PRIM_GBUFFER_D0_A]
-        w, h = size
-        return R.frame_depth(cur.reshape(h, w, 4)[..., 0])
-
-
-def _scene_camera(scene, size, mode=CameraMode.IMAGE, denoise=True):
-    return (scenes.cornell_camera if scene == "cornell" else scenes.dungeon_camera)(size, mode, denoise=denoise)
-
-
 CORNELL, DUNGEON = (64, 48), (72, 48)
 FRAME_CASES = [
     # name, exact, scene, size, keep all planes, lens
@@ -261,15 +229,6 @@ def test_a_focused_frame_equals_the_restatement_of_the_frame_without(case):
 
 
 # ---------------------------------------------------------------- 4. the chain
-MOVES = (0.07, 0.05, 0.09, 0.06)
-
-
-def _moving(scene, k, size=SIZE, mode=CameraMode.IMAGE):
-    base, target = ((0.0, 1.0, 3.2), (0.0, 1.0, 0.0)) if scene == "cornell" else ((-5.75, 0.5, -16.8), (-5.75, 0.5, -17.0))
-    dx = sum(MOVES[:k]) * (5.0 if scene == "cornell" else 1.0)
-    return scenes.camera_for(size, (base[0] + dx, base[1] + 0.4 * dx, base[2]), (target[0] + 0.3 * dx, target[1], target[2]), mode, True)
-
-
 @pytest.mark.parametrize("exact,scene", [(False, "dungeon"), (True, "cornell")])
 def test_the_whole_chain_equals_the_four_process_calls(exact, scene):
     """depth of field, motion blur, bloom, ACES and FXAA (with a resample) in one frame against st_dof_process, st_motion_blur_process,
@@ -309,126 +268,23 @@ def test_the_whole_chain_equals_the_four_process_calls(exact, scene):
 
 
 # ---------------------------------------------------------------- 5. off is off; nothing else changes
-def _all_planes(e, cam):
-    return {b: e.read_buffer(cam, b) for b in Buffer}
-
-
 @pytest.mark.parametrize("exact", [False, True])
 def test_a_cleared_setting_renders_like_a_camera_that_never_had_one(exact):
-    a, b = _engine(exact), _engine(exact)
-    ca, cb = a.create_camera(_moving("cornell", 0)), b.create_camera(_moving("cornell", 0))
-    b.set_dof(cb, samples=4, **LENS)
-    oa, ob = Out(0), Out(0)
-    stream = torch.cuda.current_stream().cuda_stream
-    for k in range(4):
-        if k == 2:
-            b.set_dof(cb, None)
-        for e, cam, o in ((a, ca, oa), (b, cb, ob)):
-            e.update_camera(cam, _moving("cornell", k)); e.tick(stream); e.render_camera(cam, o.ptr(), stream)
-        torch.cuda.synchronize()
-        if k < 2:
-            assert any(l & PassBit.POST for l in b.last_launches()) and not np.array_equal(_bits(oa.get()), _bits(ob.get()))
-            continue
-        assert np.array_equal(_bits(oa.get()), _bits(ob.get())), (exact, k)
-        assert b.last_launches() == a.last_launches() and not any(l & PassBit.POST for l in b.last_launches())
-        pa, pb = _all_planes(a, ca), _all_planes(b, cb)
-        for buf in Buffer:
-            assert a.buffer_stale(ca, buf) == b.buffer_stale(cb, buf), (k, buf)
-            assert np.array_equal(_bits(pa[buf]), _bits(pb[buf])), (exact, k, buf)
-    a.close(); b.close()
+    C.cleared_setting_renders_like_none(NODE, exact)
 
 
 def test_aovs_picks_planes_and_the_exposure_do_not_depend_on_the_setting():
-    a, b = _engine(False, "dungeon"), _engine(False, "dungeon")
-    ca, cb = a.create_camera(_moving("dungeon", 0)), b.create_camera(_moving("dungeon", 0))
-    for e, cam in ((a, ca), (b, cb)):
-        e.set_display(cam, tonemap=Tonemap.ACES_FITTED, auto_exposure=True, ev_min=-12.0, ev_max=8.0)
-    b.set_dof(cb, samples=32, autofocus=(0.5, 0.5), sensor_height=0.5, focal_distance=3.0)
-    oa, ob = Out(0), Out(0)
-    pixels = torch.tensor([[0, 0], [36, 26], [71, 51], [10, 40], [60, 5]], dtype=torch.uint32, device="cuda:0")
-    stream = torch.cuda.current_stream().cuda_stream
-    for k in range(3):
-        for e, cam, o in ((a, ca, oa), (b, cb, ob)):
-            e.update_camera(cam, _moving("dungeon", k)); e.tick(stream); e.render_camera(cam, o.ptr(), stream)
-        pa, pb = aov_planes(SIZE, fill=0), aov_planes(SIZE, fill=0)
-        a.render_aovs(ca, pa); b.render_aovs(cb, pb)
-        ha, hb = torch.zeros(5 * 64, dtype=torch.uint8, device="cuda:0"), torch.zeros(5 * 64, dtype=torch.uint8, device="cuda:0")
-        a.pick(ca, pixels.data_ptr(), 5, ha.data_ptr()); b.pick(cb, pixels.data_ptr(), 5, hb.data_ptr())
-        torch.cuda.synchronize()
-        assert not np.array_equal(_bits(oa.get()), _bits(ob.get())), "the focused frame differs"
-        for kind in Aov:
-            assert np.array_equal(pa[kind].cpu().view(torch.uint8).numpy(), pb[kind].cpu().view(torch.uint8).numpy()), (k, kind)
-        assert np.array_equal(ha.cpu().numpy(), hb.cpu().numpy()), k
-        for buf in Buffer:
-            assert a.buffer_stale(ca, buf) == b.buffer_stale(cb, buf), (k, buf)
-            assert np.array_equal(_bits(a.read_buffer(ca, buf)), _bits(b.read_buffer(cb, buf))), (k, buf)
-        ea, eb = a.exposure(ca), b.exposure(cb)
-        assert ea == eb and np.isfinite(ea[1]), (k, ea, eb)
-        assert np.array_equal(a.camera_histogram(ca), b.camera_histogram(cb))
-    a.close(); b.close()
-
-
-def _orthographic(size):
-    cam = scenes.cornell_camera(size)
-    cam.projection = np.array([[0.8, 0, 0, 0], [0, 0.8, 0, 0], [0, 0, 0.01, 1.0], [0, 0, 0, 1.0]], np.float32)   # [15] = 1: no focal length to derive
-    return cam
+    C.nothing_else_depends_on_the_setting(NODE)
 
 
 @pytest.mark.parametrize("what", ["reference", "heatmap", "orthographic"])
 def test_frames_that_skip_depth_of_field(what):
-    a, b = _engine(True), _engine(True)
-    cam = {"reference": lambda: scenes.cornell_camera(CORNELL, CameraMode.REFERENCE, denoise=False, depth=1),
-           "heatmap": lambda: scenes.cornell_camera(CORNELL, CameraMode.BVH_HEATMAP, denoise=False), "orthographic": lambda: _orthographic(CORNELL)}[what]()
-    ca, cb = a.create_camera(cam), b.create_camera(cam)
-    b.set_dof(cb, samples=4, autofocus=(0.5, 0.5), **LENS)
-    oa, ob = Out(0, CORNELL), Out(0, CORNELL)
-    stream = torch.cuda.current_stream().cuda_stream
-    for k in range(2):
-        for e, c, o in ((a, ca, oa), (b, cb, ob)):
-            e.tick(stream); e.render_camera(c, o.ptr(), stream)
-        torch.cuda.synchronize()
-        assert_bits_equal(ob.get(), oa.get(), f"{what} with depth of field set, frame {k}")
-        assert _bits(oa.get()).any()
-        assert b.last_launches() == a.last_launches() and not any(l & PassBit.POST for l in b.last_launches())
-    a.close(); b.close()
+    C.frames_that_skip(NODE, what, CORNELL)
 
 
 # ---------------------------------------------------------------- 6. pipelining
-def _pipeline(sync_every_frame, streams=1, profiling=False, frames=8):
-    e = _engine(False, "dungeon")
-    if profiling:
-        e.profile_enable(1)   # per-kernel timing: the serial schedule
-    cam = e.create_camera(_moving("dungeon", 0))
-    e.set_output_format(cam, OutputFormat.RGBA8_UNORM_SRGB)
-    e.set_display(cam, tonemap=Tonemap.ACES_FITTED, exposure_ev=0.5)
-    e.set_dof(cam, samples=32, autofocus=(0.5, 0.5), sensor_height=0.5, focal_distance=3.0)
-    ss = [torch.cuda.Stream() for _ in range(streams)]
-    outs = [Out(2) for _ in range(frames)]
-    torch.cuda.synchronize()
-    for k in range(frames):
-        s = ss[k % streams].cuda_stream
-        e.update_camera(cam, _moving("dungeon", k % 4))   # another view every frame: frame k + 1's depths are not frame k's
-        e.tick(s)
-        e.render_camera(cam, outs[k].ptr(), s)
-        if sync_every_frame:
-            torch.cuda.synchronize()
-    torch.cuda.synchronize()
-    got = [o.get() for o in outs]
-    names = {p["name"]: p["launches"] for p in e.profile_read()} if profiling else None
-    e.close()
-    return got, names
-
-
 def test_frames_in_flight_read_their_own_depths():
-    base, _ = _pipeline(True)
-    assert any(not np.array_equal(base[k], base[k + 1]) for k in range(7))
-    for kw in (dict(), dict(streams=2), dict(profiling=True)):
-        for sync in ((False,) if not kw else (True, False)):
-            other, names = _pipeline(sync, **kw)
-            for k, (x, y) in enumerate(zip(other, base)):
-                assert np.array_equal(x, y), (kw, sync, k)
-            if names is not None:   # the three slots report themselves
-                assert names["dof_pack"] == names["dof_neighbour"] == names["dof_gather"] == 8, names
+    C.frames_in_flight_read_their_own_inputs(NODE)
 
 
 # ---------------------------------------------------------------- 7. lifecycle
@@ -474,15 +330,6 @@ def test_resizes_toggles_arithmetic_switches_two_cameras_and_teardown():
     _check(oa.get(), _restate(d1, ia, za, pa), 0, "stream a")
     _check(ob.get(), _restate(d2, ib, zb, pb), 0, "stream b")
     # delete a camera with the setting on and a frame in flight; a new camera starts clean; destroy the engine with a focused frame in flight
-    keep = Out(0)
     b.update_camera(cb, scenes.cornell_camera(SIZE))
-    b.tick(stream); b.render_camera(cb, keep.ptr(), stream)
-    b.delete_camera(cb)
-    c3 = b.create_camera(scenes.cornell_camera(SIZE))
-    assert not b.get_dof(c3)[1]
-    b.set_dof(c3, **LENS)
-    b.tick(stream); b.render_camera(c3, keep.ptr(), stream)
-    torch.cuda.synchronize()
-    assert np.isfinite(keep.get()).all()
-    b.tick(stream); b.render_camera(c3, keep.ptr(), stream)
+    C.teardown_with_the_setting_on(NODE, b, cb)
     a.close(); b.close()

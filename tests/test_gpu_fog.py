@@ -12,37 +12,22 @@ import torch
 import display_ref
 import fog_cases as K
 import fog_ref as R
+import output_chain as C
+from output_chain import Depth, Out, _bits, _check, _engine, _moving, _proj, _scene_camera, _xf
 from parity import assert_bits_equal
-from strolle_amd import (Aov, Buffer, CameraMode, Engine, FogFalloff, OutputFormat, PassBit, ResampleFilter, Sun, Tonemap, aov_planes, bloom_desc, display_desc, dof_desc,
+from strolle_amd import (Buffer, Engine, FogFalloff, OutputFormat, PassBit, ResampleFilter, Sun, Tonemap, bloom_desc, display_desc, dof_desc,
                          fog_desc, motion_blur_desc, post_desc, scenes)
-from test_gpu_bloom import Out as _Out, _check, _engine
-from test_gpu_dof import Depth, _moving, _proj, _scene_camera
 
 pytestmark = pytest.mark.gpu
 SIZE = K.SIZE
 F = np.float32
-_REFS = {}
 FOG = dict(falloff=FogFalloff.EXPONENTIAL, color=(0.5, 0.6, 0.7, 0.9), density=0.12, height_falloff=0.25, height_reference=0.5, sky_distance=60.0,
            light_color=(1.0, 0.7, 0.0), light_exponent=8.0, light_direction=(0.3, 0.5, -0.8))
-
-
-def Out(fmt=0, size=K.SIZE, fill=0):
-    return _Out(fmt, size, fill)
+NODE = C.Node("set_fog", "get_fog", "fog", "the fogged frame differs", ("fog",), FOG)
 
 
 def _ref(key, make):
-    if key not in _REFS:   # computed once, shared by the two builds
-        _REFS[key] = make()
-    return _REFS[key]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _xf(cam):
-    """the 16 floats of a camera's transform, column major"""
-    return np.asarray(cam.transform, np.float32).T.reshape(-1).copy()
+    return C._ref(__name__, key, make)
 
 
 def _process(e, d, color, depth, M, P, fmt=0, display=None, stream=None):
@@ -250,90 +235,19 @@ def test_follow_sun_takes_the_direction_of_the_last_tick():
 
 
 # ---------------------------------------------------------------- 4. off is off; nothing else changes
-def _all_planes(e, cam):
-    return {b: e.read_buffer(cam, b) for b in Buffer}
-
-
 @pytest.mark.parametrize("exact", [False, True])
 def test_a_cleared_setting_renders_like_a_camera_that_never_had_one(exact):
-    a, b = _engine(exact), _engine(exact)
-    ca, cb = a.create_camera(_moving("cornell", 0)), b.create_camera(_moving("cornell", 0))
-    b.set_fog(cb, **FOG)
-    oa, ob = Out(0), Out(0)
-    stream = torch.cuda.current_stream().cuda_stream
-    for k in range(4):
-        if k == 2:
-            b.set_fog(cb, None)
-        for e, cam, o in ((a, ca, oa), (b, cb, ob)):
-            e.update_camera(cam, _moving("cornell", k)); e.tick(stream); e.render_camera(cam, o.ptr(), stream)
-        torch.cuda.synchronize()
-        if k < 2:
-            assert any(l & PassBit.POST for l in b.last_launches()) and not np.array_equal(_bits(oa.get()), _bits(ob.get()))
-            continue
-        assert np.array_equal(_bits(oa.get()), _bits(ob.get())), (exact, k)
-        assert b.last_launches() == a.last_launches() and not any(l & PassBit.POST for l in b.last_launches())
-        pa, pb = _all_planes(a, ca), _all_planes(b, cb)
-        for buf in Buffer:
-            assert a.buffer_stale(ca, buf) == b.buffer_stale(cb, buf), (k, buf)
-            assert np.array_equal(_bits(pa[buf]), _bits(pb[buf])), (exact, k, buf)
-    a.close(); b.close()
+    C.cleared_setting_renders_like_none(NODE, exact)
 
 
 def test_aovs_picks_planes_and_the_exposure_do_not_depend_on_the_setting():
-    a, b = _engine(False, "dungeon"), _engine(False, "dungeon")
-    ca, cb = a.create_camera(_moving("dungeon", 0)), b.create_camera(_moving("dungeon", 0))
-    for e, cam in ((a, ca), (b, cb)):
-        e.set_display(cam, tonemap=Tonemap.ACES_FITTED, auto_exposure=True, ev_min=-12.0, ev_max=8.0)
-    b.set_fog(cb, **FOG)
-    oa, ob = Out(0), Out(0)
-    pixels = torch.tensor([[0, 0], [36, 26], [71, 51], [10, 40], [60, 5]], dtype=torch.uint32, device="cuda:0")
-    stream = torch.cuda.current_stream().cuda_stream
-    for k in range(3):
-        for e, cam, o in ((a, ca, oa), (b, cb, ob)):
-            e.update_camera(cam, _moving("dungeon", k)); e.tick(stream); e.render_camera(cam, o.ptr(), stream)
-        pa, pb = aov_planes(SIZE, fill=0), aov_planes(SIZE, fill=0)
-        a.render_aovs(ca, pa); b.render_aovs(cb, pb)
-        ha, hb = torch.zeros(5 * 64, dtype=torch.uint8, device="cuda:0"), torch.zeros(5 * 64, dtype=torch.uint8, device="cuda:0")
-        a.pick(ca, pixels.data_ptr(), 5, ha.data_ptr()); b.pick(cb, pixels.data_ptr(), 5, hb.data_ptr())
-        torch.cuda.synchronize()
-        assert not np.array_equal(_bits(oa.get()), _bits(ob.get())), "the fogged frame differs"
-        for kind in Aov:
-            assert np.array_equal(pa[kind].cpu().view(torch.uint8).numpy(), pb[kind].cpu().view(torch.uint8).numpy()), (k, kind)
-        assert np.array_equal(ha.cpu().numpy(), hb.cpu().numpy()), k
-        for buf in Buffer:
-            assert a.buffer_stale(ca, buf) == b.buffer_stale(cb, buf), (k, buf)
-            assert np.array_equal(_bits(a.read_buffer(ca, buf)), _bits(b.read_buffer(cb, buf))), (k, buf)
-        ea, eb = a.exposure(ca), b.exposure(cb)
-        assert ea == eb and np.isfinite(ea[1]), (k, ea, eb)
-        assert np.array_equal(a.camera_histogram(ca), b.camera_histogram(cb))
-    a.close(); b.close()
+    C.nothing_else_depends_on_the_setting(NODE)
 
 
 # ---------------------------------------------------------------- 5. the frames that skip it
-def _orthographic(size):
-    cam = scenes.cornell_camera(size)
-    cam.projection = np.array([[0.8, 0, 0, 0], [0, 0.8, 0, 0], [0, 0, 0.01, 1.0], [0, 0, 0, 1.0]], np.float32)   # [15] = 1: no perspective ray to derive
-    return cam
-
-
 @pytest.mark.parametrize("what", ["reference", "heatmap", "orthographic"])
 def test_frames_that_skip_fog(what):
-    size = (64, 48)
-    a, b = _engine(True), _engine(True)
-    cam = {"reference": lambda: scenes.cornell_camera(size, CameraMode.REFERENCE, denoise=False, depth=1),
-           "heatmap": lambda: scenes.cornell_camera(size, CameraMode.BVH_HEATMAP, denoise=False), "orthographic": lambda: _orthographic(size)}[what]()
-    ca, cb = a.create_camera(cam), b.create_camera(cam)
-    b.set_fog(cb, **FOG)
-    oa, ob = Out(0, size), Out(0, size)
-    stream = torch.cuda.current_stream().cuda_stream
-    for k in range(2):
-        for e, c, o in ((a, ca, oa), (b, cb, ob)):
-            e.tick(stream); e.render_camera(c, o.ptr(), stream)
-        torch.cuda.synchronize()
-        assert_bits_equal(ob.get(), oa.get(), f"{what} with fog set, frame {k}")
-        assert _bits(oa.get()).any()
-        assert b.last_launches() == a.last_launches() and not any(l & PassBit.POST for l in b.last_launches())
-    a.close(); b.close()
+    C.frames_that_skip(NODE, what, (64, 48))
 
 
 # ---------------------------------------------------------------- 6. tiles
@@ -419,41 +333,8 @@ def test_fogged_tiles_gather_to_the_fogged_frame(world):
 
 
 # ---------------------------------------------------------------- 7. pipelining
-def _pipeline(sync_every_frame, streams=1, profiling=False, frames=8):
-    e = _engine(False, "dungeon")
-    if profiling:
-        e.profile_enable(1)   # per-kernel timing: the serial schedule
-    cam = e.create_camera(_moving("dungeon", 0))
-    e.set_output_format(cam, OutputFormat.RGBA8_UNORM_SRGB)
-    e.set_display(cam, tonemap=Tonemap.ACES_FITTED, exposure_ev=0.5)
-    e.set_fog(cam, **FOG)
-    ss = [torch.cuda.Stream() for _ in range(streams)]
-    outs = [Out(2) for _ in range(frames)]
-    torch.cuda.synchronize()
-    for k in range(frames):
-        s = ss[k % streams].cuda_stream
-        e.update_camera(cam, _moving("dungeon", k % 4))   # another view every frame: frame k + 2's depths are not frame k's
-        e.tick(s)
-        e.render_camera(cam, outs[k].ptr(), s)
-        if sync_every_frame:
-            torch.cuda.synchronize()
-    torch.cuda.synchronize()
-    got = [o.get() for o in outs]
-    names = {p["name"]: p["launches"] for p in e.profile_read()} if profiling else None
-    e.close()
-    return got, names
-
-
 def test_frames_in_flight_read_their_own_depths():
-    base, _ = _pipeline(True)
-    assert any(not np.array_equal(base[k], base[k + 1]) for k in range(7))
-    for kw in (dict(), dict(streams=2), dict(profiling=True)):
-        for sync in ((False,) if not kw else (True, False)):
-            other, names = _pipeline(sync, **kw)
-            for k, (x, y) in enumerate(zip(other, base)):
-                assert np.array_equal(x, y), (kw, sync, k)
-            if names is not None:   # the slot reports itself
-                assert names["fog"] == 8, names
+    C.frames_in_flight_read_their_own_inputs(NODE)
 
 
 # ---------------------------------------------------------------- 8. lifecycle
@@ -483,14 +364,5 @@ def test_resizes_toggles_arithmetic_switches_tiny_frames_and_teardown():
             _check(ob.get(), _restate(d, oa.get(), p.read(b, cb, size), _xf(cam), _proj(cam)), 0, f"size {size} step {step}")
             step += 1
     # delete a camera with the setting on and a frame in flight; a new camera starts clean; destroy the engine with a fogged frame in flight
-    keep = Out(0)
-    b.tick(stream); b.render_camera(cb, keep.ptr(), stream)
-    b.delete_camera(cb)
-    c3 = b.create_camera(scenes.cornell_camera(SIZE))
-    assert not b.get_fog(c3)[1]
-    b.set_fog(c3, **FOG)
-    b.tick(stream); b.render_camera(c3, keep.ptr(), stream)
-    torch.cuda.synchronize()
-    assert np.isfinite(keep.get()).all()
-    b.tick(stream); b.render_camera(c3, keep.ptr(), stream)
+    C.teardown_with_the_setting_on(NODE, b, cb)
     a.close(); b.close()

@@ -13,31 +13,24 @@ import torch
 import bloom_ref
 import display_ref
 import motion_blur_ref as R
+import output_chain as C
 import post_ref
 import test_gpu_deform_motion as deform
+from output_chain import Out, _all_planes, _bits, _check, _engine, _image
 from parity import assert_bits_equal
-from strolle_amd import (Aov, Buffer, CameraMode, Engine, Instance, OutputFormat, PassBit, ResampleFilter, Tonemap, aov_planes, bloom_desc, display_desc,
+from strolle_amd import (Buffer, CameraMode, Engine, Instance, OutputFormat, PassBit, ResampleFilter, Tonemap, bloom_desc, display_desc,
                          motion_blur_desc, post_desc, scenes)
-from test_gpu_bloom import Out, _check, _engine, _image
 
 pytestmark = pytest.mark.gpu
 SIZE = (72, 52)
 SIZES = [(72, 52), (64, 64), (33, 9), (5, 5)]
 F = np.float32
-_REFS = {}
 
 
 def _ref(key, make):
-    if key not in _REFS:   # computed once, shared by the two builds
-        _REFS[key] = make()
-    return _REFS[key]
+    return C._ref(__name__, key, make)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-# ---------------------------------------------------------------- synthetic inputs
 def _velocity(kind, w, h, seed=5):
     rng = np.random.default_rng(seed)
     if kind == "zero":
@@ -303,35 +296,14 @@ def test_a_blurred_frame_equals_the_restatement_of_the_frame_without(case):
 
 
 # ---------------------------------------------------------------- 4. off is off
-def _all_planes(e, cam):
-    return {b: e.read_buffer(cam, b) for b in Buffer}
+NODE = C.Node("set_motion_blur", "get_motion_blur", "the blur", "the camera moves: the blurred frame differs", (), dict(shutter=1.0),
+              pipelined=dict(shutter=1.0, samples=8), recreated=dict(shutter=0.5))
 
 
 @pytest.mark.parametrize("exact", [False, True])
 def test_a_cleared_blur_renders_like_a_camera_that_never_had_one(exact):
-    a, b = _engine(exact), _engine(exact)
-    ca, cb = a.create_camera(_cam("cornell", 0)), b.create_camera(_cam("cornell", 0))
-    b.set_motion_blur(cb, shutter=1.0)
-    oa, ob = Out(0), Out(0)
-    stream = torch.cuda.current_stream().cuda_stream
-    for k in range(5):
-        if k == 2:
-            b.set_motion_blur(cb, None)
-        for e, cam, o in ((a, ca, oa), (b, cb, ob)):
-            e.update_camera(cam, _cam("cornell", k)); e.tick(stream); e.render_camera(cam, o.ptr(), stream)
-        torch.cuda.synchronize()
-        if k < 2:
-            assert any(l & PassBit.POST for l in b.last_launches())
-            continue
-        assert np.array_equal(_bits(oa.get()), _bits(ob.get())), (exact, k)
-        assert b.last_launches() == a.last_launches() and not any(l & PassBit.POST for l in b.last_launches())
-        pa, pb = _all_planes(a, ca), _all_planes(b, cb)
-        for buf in Buffer:
-            assert a.buffer_stale(ca, buf) == b.buffer_stale(cb, buf), (k, buf)
-            if buf == Buffer.VELOCITY_MAP and a.buffer_stale(ca, buf):
-                continue   # (unwritten by these frames in both: b's still holds what its last blurred frame kept)
-            assert np.array_equal(_bits(pa[buf]), _bits(pb[buf])), (exact, k, buf)
-    a.close(); b.close()
+    # five frames of this file's own camera path; a frame whose step is small need not differ; b's velocity map outlives the setting
+    C.cleared_setting_renders_like_none(NODE, exact, camera=lambda k: _cam("cornell", k), frames=5, differs=False, unwritten_velocity=True)
 
 
 @pytest.mark.parametrize("exact", [False, True])
@@ -363,35 +335,8 @@ def test_the_blur_over_a_static_scene_and_camera_changes_only_the_velocity_map(e
 
 # ---------------------------------------------------------------- 5. nothing else changes
 def test_aovs_picks_and_the_exposure_do_not_depend_on_the_blur():
-    a, b = _engine(False, "dungeon"), _engine(False, "dungeon")
-    ca, cb = a.create_camera(_cam("dungeon", 0)), b.create_camera(_cam("dungeon", 0))
-    for e, cam in ((a, ca), (b, cb)):
-        e.set_display(cam, tonemap=Tonemap.ACES_FITTED, auto_exposure=True, ev_min=-12.0, ev_max=8.0)
-    b.set_motion_blur(cb, shutter=1.0)
-    oa, ob = Out(0), Out(0)
-    pixels = torch.tensor([[0, 0], [36, 26], [71, 51], [10, 40], [60, 5]], dtype=torch.uint32, device="cuda:0")
-    stream = torch.cuda.current_stream().cuda_stream
-    for k in range(3):
-        for e, cam, o in ((a, ca, oa), (b, cb, ob)):
-            e.update_camera(cam, _cam("dungeon", k)); e.tick(stream); e.render_camera(cam, o.ptr(), stream)
-        pa, pb = aov_planes(SIZE, fill=0), aov_planes(SIZE, fill=0)
-        a.render_aovs(ca, pa); b.render_aovs(cb, pb)
-        ha, hb = torch.zeros(5 * 64, dtype=torch.uint8, device="cuda:0"), torch.zeros(5 * 64, dtype=torch.uint8, device="cuda:0")
-        a.pick(ca, pixels.data_ptr(), 5, ha.data_ptr()); b.pick(cb, pixels.data_ptr(), 5, hb.data_ptr())
-        torch.cuda.synchronize()
-        if k:
-            assert not np.array_equal(_bits(oa.get()), _bits(ob.get())), "the camera moves: the blurred frame differs"
-        for kind in Aov:
-            assert np.array_equal(pa[kind].cpu().view(torch.uint8).numpy(), pb[kind].cpu().view(torch.uint8).numpy()), (k, kind)
-        assert np.array_equal(ha.cpu().numpy(), hb.cpu().numpy()), k
-        for buf in Buffer:
-            if buf != Buffer.VELOCITY_MAP:
-                assert a.buffer_stale(ca, buf) == b.buffer_stale(cb, buf)
-                assert np.array_equal(_bits(a.read_buffer(ca, buf)), _bits(b.read_buffer(cb, buf))), (k, buf)
-        ea, eb = a.exposure(ca), b.exposure(cb)
-        assert ea == eb and np.isfinite(ea[1]), (k, ea, eb)
-        assert np.array_equal(a.camera_histogram(ca), b.camera_histogram(cb))
-    a.close(); b.close()
+    # nothing moves in front of frame 0; the blur makes the frame keep its velocity map
+    C.nothing_else_depends_on_the_setting(NODE, camera=lambda k: _cam("dungeon", k), differs_from=1, velocity_map=False)
 
 
 @pytest.mark.parametrize("mode", [CameraMode.REFERENCE, CameraMode.BVH_HEATMAP])
@@ -411,38 +356,8 @@ def test_modes_without_a_velocity_map_skip_the_blur(mode):
 
 
 # ---------------------------------------------------------------- 6. pipelining
-def _pipeline(sync_every_frame, streams=1, profiling=False, frames=8):
-    e = _engine(False, "dungeon")
-    if profiling:
-        e.profile_enable(1)   # per-kernel timing: the serial schedule
-    cam = e.create_camera(_cam("dungeon", 0))
-    e.set_output_format(cam, OutputFormat.RGBA8_UNORM_SRGB)
-    e.set_display(cam, tonemap=Tonemap.ACES_FITTED, exposure_ev=0.5)
-    e.set_motion_blur(cam, shutter=1.0, samples=8)
-    ss = [torch.cuda.Stream() for _ in range(streams)]
-    outs = [Out(2) for _ in range(frames)]
-    torch.cuda.synchronize()
-    for k in range(frames):
-        s = ss[k % streams].cuda_stream
-        e.update_camera(cam, _cam("dungeon", k))   # a different amount every frame: frame k + 1's velocities are not frame k's
-        e.tick(s)
-        e.render_camera(cam, outs[k].ptr(), s)
-        if sync_every_frame:
-            torch.cuda.synchronize()
-    torch.cuda.synchronize()
-    got = [o.get() for o in outs]
-    e.close()
-    return got
-
-
 def test_frames_in_flight_read_their_own_velocities():
-    base = _pipeline(True)
-    assert any(not np.array_equal(base[k], base[k + 1]) for k in range(7))
-    for kw in (dict(), dict(streams=2), dict(profiling=True)):
-        for sync in ((False,) if not kw else (True, False)):
-            other = _pipeline(sync, **kw)
-            for k, (x, y) in enumerate(zip(other, base)):
-                assert np.array_equal(x, y), (kw, sync, k)
+    C.frames_in_flight_read_their_own_inputs(NODE, camera=lambda k: _cam("dungeon", k))   # a different amount every frame: frame k + 1's velocities are not frame k's
 
 
 # ---------------------------------------------------------------- 7. lifecycle
@@ -490,14 +405,5 @@ def test_updates_arithmetic_switches_two_cameras_and_teardown():
         _check(oa.get(), _restate(d1, ia, va, za), 0, "stream a")
         _check(ob.get(), _restate(d2, ib, vb, zb), 0, "stream b")
     # delete a camera with the blur on and a frame in flight; a new camera starts clean; destroy the engine with a blurred frame in flight
-    keep = Out(0)
-    b.tick(stream); b.render_camera(cb, keep.ptr(), stream)
-    b.delete_camera(cb)
-    c3 = b.create_camera(_cam("cornell", 0))
-    assert not b.get_motion_blur(c3)[1]
-    b.set_motion_blur(c3, shutter=0.5)
-    b.tick(stream); b.render_camera(c3, keep.ptr(), stream)
-    torch.cuda.synchronize()
-    assert np.isfinite(keep.get()).all()
-    b.tick(stream); b.render_camera(c3, keep.ptr(), stream)
+    C.teardown_with_the_setting_on(NODE, b, cb, _cam("cornell", 0))
     a.close(); b.close()

@@ -17,10 +17,8 @@ import pytest
 import torch
 
 import display_ref
+from output_chain import MEDIUM, SUN, Depth, Out, _bits, _check, _engine, _moving, _proj, _xf
 from strolle_amd import Buffer, OutputFormat, Tonemap, bloom_desc, display_desc, dof_desc, fog_desc, light_shafts_desc, motion_blur_desc
-from test_gpu_bloom import Out, _check, _engine
-from test_gpu_dof import Depth, _moving, _proj
-from test_gpu_shafts import MEDIUM, SUN, _bits, _xf
 
 pytestmark = pytest.mark.gpu
 SIZE = (64, 48)

@@ -9,73 +9,13 @@ import pytest
 import torch
 
 import post_ref as R
+from output_chain import SIZE, Out, _camera, _check, _engine, _frame
 from parity import assert_bits_equal, bits_equal_mask
-from strolle_amd import (Aov, Buffer, CameraMode, Engine, Instance, Material, OutputFormat, PassBit, ResampleFilter, Sun, Tonemap, aov_planes, post_desc,
+from strolle_amd import (Aov, Buffer, CameraMode, Engine, Instance, Material, OutputFormat, PassBit, ResampleFilter, Tonemap, aov_planes, post_desc,
                          scenes)
 
 pytestmark = pytest.mark.gpu
-SIZE = (72, 52)   # not a multiple of the FXAA tile (64 x 8) or of the resampler's (64 x 4)
-BPP = {0: 16, 1: 8, 2: 4, 3: 4}
-
-
-def _engine(exact, scene="cornell"):
-    e = Engine(device=0, exact=exact)
-    if scene == "cornell":
-        scenes.build_cornell(e)
-    else:
-        scenes.build_dungeon(e)
-        e.update_sun(Sun(azimuth=0.6, altitude=0.5))
-    e.set_seed(7)
-    return e
-
-
-def _camera(scene="cornell", mode=CameraMode.IMAGE, denoise=True, depth=0, size=SIZE):
-    return (scenes.cornell_camera if scene == "cornell" else scenes.dungeon_camera)(size, mode, denoise=denoise, depth=depth)
-
-
-class Out:
-    """a device output buffer of one format"""
-
-    def __init__(self, fmt, size=SIZE, fill=0):
-        self.fmt, self.size = int(fmt), size
-        self.t = torch.full((size[1] * size[0] * BPP[self.fmt],), fill, dtype=torch.uint8, device="cuda:0")
-
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def get(self):
-        a = self.t.cpu().numpy()
-        w, h = self.size
-        if self.fmt == 0:
-            return a.view(np.float32).reshape(h, w, 4).copy()
-        if self.fmt == 1:
-            return a.view(np.float16).reshape(h, w, 4).copy()
-        return a.reshape(h, w, 4).copy()
-
-
-def _frame(e, cam, out, stream=None):
-    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-    e.tick(s)
-    e.render_camera(cam, out.ptr(), s)
-    torch.cuda.synchronize()
-    return out.get()
-
-
-def _check(got, ref32, fmt, what):
-    """`got` in format `fmt` against the restatement's float32 result: RGBA32F bit for bit, RGBA16F bit for bit its round-to-nearest-even,
-    the 8-bit formats by tests/test_gpu_display.py's criterion (within 1, 99.9 % exact, alpha 255)"""
-    want = R.to_format(ref32, fmt)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    if fmt == 0:
-        assert_bits_equal(got, want, what)
-    elif fmt == 1:
-        ok = (got.view(np.uint16) == want.view(np.uint16)) | (np.isnan(got) & np.isnan(want))
-        assert ok.all(), f"{what}: {np.count_nonzero(~ok)} half channels differ"
-    else:
-        d = np.abs(got[..., :3].astype(np.int32) - want[..., :3].astype(np.int32))
-        assert d.max() <= 1, f"{what}: 8-bit channel off by {d.max()}"
-        assert (d == 0).mean() >= 0.999, f"{what}: only {(d == 0).mean():.5f} of the 8-bit channels exact"
-        assert (got[..., 3] == 255).all(), what
+# SIZE (72 x 52) is not a multiple of the FXAA tile (64 x 8) or of the resampler's (64 x 4)
 
 
 def _kw(d):

@@ -24,19 +24,15 @@ import shafts_cases as K
 import shafts_ref as R
 from geometry_extremes import oracle_trace
 from oracle_binding import OracleEngine
-from parity import assert_bits_equal
-from strolle_amd import (Aov, Buffer, CameraMode, Engine, Light, OutputFormat, PassBit, ResampleFilter, Sun, Tonemap, aov_planes, bloom_desc, display_desc, dof_desc, fog_desc,
+import output_chain as C
+from output_chain import MEDIUM, SUN, Depth, Out, _bits, _check, _engine, _moving, _proj, _scene_camera, _xf
+from strolle_amd import (Buffer, Engine, Light, OutputFormat, PassBit, ResampleFilter, Sun, Tonemap, bloom_desc, display_desc, dof_desc, fog_desc,
                          light_shafts_desc, motion_blur_desc, post_desc, scenes)
-from test_gpu_bloom import Out as _Out, _check, _engine
-from test_gpu_dof import Depth, _moving, _proj, _scene_camera
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZE = (72, 52)
 F = np.float32
-_REFS = {}
-MEDIUM = dict(density=0.08, anisotropy=0.6, max_distance=30.0, intensity=1.5, scatter=(0.9, 0.8, 0.6))
-SUN = dict(sun_color=(6.0, 5.0, 4.0), sun_direction=(0.35, 0.8, 0.3))
 CORNELL_LIGHTS = {1: Light.point((math.sin(0.0) / 2.0, 1.5, math.cos(0.0) / 2.0), 0.15, (50.0 / (4.0 * math.pi),) * 3, 20.0)}
 DUNGEON_LIGHTS = {1 + i: Light.point(p, 0.15, (5000.0 / (4.0 * math.pi),) * 3, 35.0)
                   for i, p in enumerate([(-3.0, 0.75, -23.0), (-23.5, 0.75, -31.0), (1.25, 0.75, -10.5), (-3.15, 0.75, 1.25), (-3.25, 0.75, 20.25), (13.25, 0.75, -28.25)])}
@@ -49,22 +45,8 @@ def _tool():
     return m
 
 
-def Out(fmt=0, size=SIZE, fill=0):
-    return _Out(fmt, size, fill)
-
-
 def _ref(key, make):
-    if key not in _REFS:   # computed once, shared, left unchanged
-        _REFS[key] = make()
-    return _REFS[key]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _xf(cam):
-    return np.asarray(cam.transform, np.float32).T.reshape(-1).copy()
+    return C._ref(__name__, key, make)
 
 
 def _own_occlusion(e):
@@ -124,7 +106,7 @@ def test_the_exact_build_matches_the_restatement_with_the_checkers_occlusion(sce
     # the four output formats, without a display and with a manual ACES one
     name, size, kind, d = K.cases()[0]
     img, z, M, P = K.inputs(size, kind)
-    plain, _ = _REFS[("probe", scene, name)]
+    plain, _ = C._REFS[__name__, ("probe", scene, name)]
     for op in (None, Tonemap.ACES_FITTED):
         disp = display_desc(tonemap=op, exposure_ev=-1.5) if op is not None else None
         want = plain if op is None else display_ref.transform(plain[..., :3], int(op), display_ref.manual_scale(-1.5))
@@ -245,6 +227,10 @@ FRAME_CASES = [("cornell_fast", False, "cornell", 2, 8), ("cornell_exact", True,
 
 def _frame_desc(scene, divisor, steps, **more):
     return light_shafts_desc(steps=steps, divisor=divisor, lights=(1,) if scene == "cornell" else (3, 1), **dict(MEDIUM, **SUN, **more))
+
+
+NODE = C.Node("set_light_shafts", "get_light_shafts", "shafts", "the frame with shafts differs", ("shafts_march", "shafts_apply"), _frame_desc("cornell", 2, 8),
+              independent=_frame_desc("dungeon", 2, 8), pipelined=_frame_desc("dungeon", 2, 8), recreated=_frame_desc("cornell", 2, 4), counts_rays=True)
 
 
 @pytest.mark.parametrize("case", FRAME_CASES, ids=[c[0] for c in FRAME_CASES])
@@ -386,129 +372,23 @@ def test_follow_sun_takes_the_direction_of_the_last_tick_and_a_removed_light_dro
 
 
 # ---------------------------------------------------------------- 4. off is off; nothing else changes
-def _all_planes(e, cam):
-    return {b: e.read_buffer(cam, b) for b in Buffer}
-
-
 @pytest.mark.parametrize("exact", [False, True])
 def test_a_cleared_setting_renders_like_a_camera_that_never_had_one(exact):
-    a, b = _engine(exact), _engine(exact)
-    ca, cb = a.create_camera(_moving("cornell", 0)), b.create_camera(_moving("cornell", 0))
-    b.set_light_shafts(cb, _frame_desc("cornell", 2, 8))
-    oa, ob = Out(0), Out(0)
-    stream = torch.cuda.current_stream().cuda_stream
-    for k in range(4):
-        if k == 2:
-            b.set_light_shafts(cb, None)
-        for e, cam, o in ((a, ca, oa), (b, cb, ob)):
-            e.update_camera(cam, _moving("cornell", k)); e.tick(stream); e.render_camera(cam, o.ptr(), stream)
-        torch.cuda.synchronize()
-        if k < 2:
-            assert any(l & PassBit.POST for l in b.last_launches()) and not np.array_equal(_bits(oa.get()), _bits(ob.get()))
-            continue
-        assert np.array_equal(_bits(oa.get()), _bits(ob.get())), (exact, k)
-        assert b.last_launches() == a.last_launches() and not any(l & PassBit.POST for l in b.last_launches())
-        pa, pb = _all_planes(a, ca), _all_planes(b, cb)
-        for buf in Buffer:
-            assert a.buffer_stale(ca, buf) == b.buffer_stale(cb, buf), (k, buf)
-            assert np.array_equal(_bits(pa[buf]), _bits(pb[buf])), (exact, k, buf)
-    a.close(); b.close()
+    C.cleared_setting_renders_like_none(NODE, exact)
 
 
 def test_aovs_picks_planes_and_the_exposure_do_not_depend_on_the_setting():
-    a, b = _engine(False, "dungeon"), _engine(False, "dungeon")
-    ca, cb = a.create_camera(_moving("dungeon", 0)), b.create_camera(_moving("dungeon", 0))
-    for e, cam in ((a, ca), (b, cb)):
-        e.set_display(cam, tonemap=Tonemap.ACES_FITTED, auto_exposure=True, ev_min=-12.0, ev_max=8.0)
-    b.set_light_shafts(cb, _frame_desc("dungeon", 2, 8))
-    oa, ob = Out(0), Out(0)
-    pixels = torch.tensor([[0, 0], [36, 26], [71, 51], [10, 40], [60, 5]], dtype=torch.uint32, device="cuda:0")
-    stream = torch.cuda.current_stream().cuda_stream
-    for k in range(3):
-        for e, cam, o in ((a, ca, oa), (b, cb, ob)):
-            e.update_camera(cam, _moving("dungeon", k)); e.tick(stream); e.render_camera(cam, o.ptr(), stream)
-        pa, pb = aov_planes(SIZE, fill=0), aov_planes(SIZE, fill=0)
-        a.render_aovs(ca, pa); b.render_aovs(cb, pb)
-        ha, hb = torch.zeros(5 * 64, dtype=torch.uint8, device="cuda:0"), torch.zeros(5 * 64, dtype=torch.uint8, device="cuda:0")
-        a.pick(ca, pixels.data_ptr(), 5, ha.data_ptr()); b.pick(cb, pixels.data_ptr(), 5, hb.data_ptr())
-        torch.cuda.synchronize()
-        assert not np.array_equal(_bits(oa.get()), _bits(ob.get())), "the frame with shafts differs"
-        for kind in Aov:
-            assert np.array_equal(pa[kind].cpu().view(torch.uint8).numpy(), pb[kind].cpu().view(torch.uint8).numpy()), (k, kind)
-        assert np.array_equal(ha.cpu().numpy(), hb.cpu().numpy()), k
-        for buf in Buffer:
-            assert a.buffer_stale(ca, buf) == b.buffer_stale(cb, buf), (k, buf)
-            assert np.array_equal(_bits(a.read_buffer(ca, buf)), _bits(b.read_buffer(cb, buf))), (k, buf)
-        ea, eb = a.exposure(ca), b.exposure(cb)
-        assert ea == eb and np.isfinite(ea[1]), (k, ea, eb)
-        assert np.array_equal(a.camera_histogram(ca), b.camera_histogram(cb))
-    a.close(); b.close()
-
-
-def _orthographic(size):
-    cam = scenes.cornell_camera(size)
-    cam.projection = np.array([[0.8, 0, 0, 0], [0, 0.8, 0, 0], [0, 0, 0.01, 1.0], [0, 0, 0, 1.0]], np.float32)
-    return cam
+    C.nothing_else_depends_on_the_setting(NODE)
 
 
 @pytest.mark.parametrize("what", ["reference", "heatmap", "orthographic"])
 def test_frames_that_skip_the_shafts(what):
-    size = (64, 48)
-    a, b = _engine(True), _engine(True)
-    cam = {"reference": lambda: scenes.cornell_camera(size, CameraMode.REFERENCE, denoise=False, depth=1),
-           "heatmap": lambda: scenes.cornell_camera(size, CameraMode.BVH_HEATMAP, denoise=False), "orthographic": lambda: _orthographic(size)}[what]()
-    ca, cb = a.create_camera(cam), b.create_camera(cam)
-    b.set_light_shafts(cb, _frame_desc("cornell", 2, 8))
-    oa, ob = Out(0, size), Out(0, size)
-    stream = torch.cuda.current_stream().cuda_stream
-    for k in range(2):
-        for e, c, o in ((a, ca, oa), (b, cb, ob)):
-            e.ray_count(c, reset=True)
-            e.tick(stream); e.render_camera(c, o.ptr(), stream)
-        torch.cuda.synchronize()
-        assert_bits_equal(ob.get(), oa.get(), f"{what} with shafts set, frame {k}")
-        assert _bits(oa.get()).any()
-        assert b.last_launches() == a.last_launches() and not any(l & PassBit.POST for l in b.last_launches())
-        assert a.ray_count(ca) == b.ray_count(cb)
-    a.close(); b.close()
+    C.frames_that_skip(NODE, what, (64, 48))
 
 
 # ---------------------------------------------------------------- 5. pipelining
-def _pipeline(sync_every_frame, streams=1, profiling=False, frames=8):
-    e = _engine(False, "dungeon")
-    if profiling:
-        e.profile_enable(1)   # per-kernel timing: the serial schedule
-    cam = e.create_camera(_moving("dungeon", 0))
-    e.set_output_format(cam, OutputFormat.RGBA8_UNORM_SRGB)
-    e.set_display(cam, tonemap=Tonemap.ACES_FITTED, exposure_ev=0.5)
-    e.set_light_shafts(cam, _frame_desc("dungeon", 2, 8))
-    ss = [torch.cuda.Stream() for _ in range(streams)]
-    outs = [Out(2) for _ in range(frames)]
-    torch.cuda.synchronize()
-    for k in range(frames):
-        s = ss[k % streams].cuda_stream
-        e.update_camera(cam, _moving("dungeon", k % 4))   # another view every frame: frame k + 2's depths are not frame k's
-        e.tick(s)
-        e.render_camera(cam, outs[k].ptr(), s)
-        if sync_every_frame:
-            torch.cuda.synchronize()
-    torch.cuda.synchronize()
-    got = [o.get() for o in outs]
-    names = {p["name"]: p["launches"] for p in e.profile_read()} if profiling else None
-    e.close()
-    return got, names
-
-
 def test_frames_in_flight_read_their_own_depths():
-    base, _ = _pipeline(True)
-    assert any(not np.array_equal(base[k], base[k + 1]) for k in range(7))
-    for kw in (dict(), dict(streams=2), dict(profiling=True)):
-        for sync in ((False,) if not kw else (True, False)):
-            other, names = _pipeline(sync, **kw)
-            for k, (x, y) in enumerate(zip(other, base)):
-                assert np.array_equal(x, y), (kw, sync, k)
-            if names is not None:   # the two slots report themselves
-                assert names["shafts_march"] == names["shafts_apply"] == 8, names
+    C.frames_in_flight_read_their_own_inputs(NODE)
 
 
 # ---------------------------------------------------------------- 6. lifecycle
@@ -540,14 +420,5 @@ def test_resizes_toggles_arithmetic_switches_tiny_frames_and_teardown():
             _check(ob.get(), ref, 0, f"size {size} step {step}")
             step += 1
     # delete a camera with the setting on and a frame in flight; a new camera starts clean; destroy the engine with such a frame in flight
-    keep = Out(0)
-    b.tick(stream); b.render_camera(cb, keep.ptr(), stream)
-    b.delete_camera(cb)
-    c3 = b.create_camera(scenes.cornell_camera(SIZE))
-    assert not b.get_light_shafts(c3)[1]
-    b.set_light_shafts(c3, d)
-    b.tick(stream); b.render_camera(c3, keep.ptr(), stream)
-    torch.cuda.synchronize()
-    assert np.isfinite(keep.get()).all()
-    b.tick(stream); b.render_camera(c3, keep.ptr(), stream)
+    C.teardown_with_the_setting_on(NODE, b, cb)
     a.close(); b.close()

@@ -4,55 +4,30 @@ there (also across st_camera_update), a window and the blur exclude each other i
 device, and the numpy restatement (motion_blur_ref.py) at cases worked out by hand."""
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import motion_blur_ref as R
-from strolle_amd import Engine, StrolleError, Tonemap, display_desc, motion_blur_desc, scenes
+import output_chain_abi as A
+from strolle_amd import StrolleError, Tonemap, display_desc, motion_blur_desc, scenes
+from output_chain_abi import ST_ERR_INVALID_ARGUMENT, ST_ERR_NO_DEVICE, host_camera as _host_camera
 from strolle_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ST_OK, ST_ERR_INVALID_ARGUMENT, ST_ERR_NO_DEVICE, ST_ERR_UNKNOWN_CAMERA = 0, 1, 2, 3
 ENTRY_POINTS = ("st_camera_set_motion_blur", "st_camera_get_motion_blur", "st_motion_blur_process")
 FIELDS = ["struct_size", "flags", "samples", "shutter", "max_radius", "depth_softness"]
 F = np.float32
 
 
 def test_entry_points_are_exported_declared_and_bound():
-    lib = api.load_library()
-    header = open(os.path.join(ROOT, "include", "strolle_hip.h")).read()
-    ffi = open(os.path.join(ROOT, "rust", "strolle-hip", "src", "ffi.rs")).read()
-    for name in ENTRY_POINTS:
-        assert hasattr(lib, name), name
-        assert re.search(r"\bint %s\(" % name, header), name
-        assert re.search(r"pub fn %s\(" % name, ffi), name
-    c_body = re.search(r"typedef struct StMotionBlurDesc \{(.*?)\} StMotionBlurDesc;", re.sub(r"/\*.*?\*/", "", header, flags=re.S), re.S).group(1)
-    c_fields = [n.strip() for d in c_body.split(";") if d.strip() for n in d.strip().split(None, 1)[1].split(",")]
-    r_fields = re.findall(r"pub (\w+):", re.search(r"pub struct StMotionBlurDesc \{(.*?)\n\}", ffi, re.S).group(1))
-    assert c_fields == r_fields == [f for f, _ in api.StMotionBlurDesc._fields_] == FIELDS
-    assert re.search(r"ST_MOTION_BLUR_NO_JITTER = 1\b", header)
-    assert "pub const ST_MOTION_BLUR_NO_JITTER: u32 = 1;" in ffi
+    A.exports_header_and_ffi_agree("StMotionBlurDesc", FIELDS, ENTRY_POINTS, [("ST_MOTION_BLUR_NO_JITTER", 1)])
     assert api.MOTION_BLUR_NO_JITTER == R.NO_JITTER == 1
 
 
 def test_desc_layout_agrees_between_c_and_ctypes(tmp_path):
-    gcc = shutil.which("gcc") or shutil.which("cc")
-    if gcc is None:
-        pytest.fail("no C compiler on PATH")
-    src = tmp_path / "layout.c"
-    offs = ", ".join("offsetof(StMotionBlurDesc, %s)" % f for f in FIELDS)
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "strolle_hip.h"\nint main(void) { printf("%zu' + " %zu" * len(FIELDS)
-                   + ' %d\\n", sizeof(StMotionBlurDesc), ' + offs + ', ST_MOTION_BLUR_NO_JITTER); return 0; }\n')
-    exe = tmp_path / "layout"
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = list(map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()))
-    D = api.StMotionBlurDesc
+    got = A.c_layout(tmp_path, "StMotionBlurDesc", FIELDS, ["ST_MOTION_BLUR_NO_JITTER"])
     assert got == [24, 0, 4, 8, 12, 16, 20, 1]
-    assert got[:1 + len(FIELDS)] == [C.sizeof(D)] + [getattr(D, f).offset for f in FIELDS]
 
 
 def _d(**kw):
@@ -60,12 +35,6 @@ def _d(**kw):
     for k, v in kw.items():
         setattr(d, k, v)
     return d
-
-
-def _host_camera(size=(64, 48)):
-    e = Engine(device=-1)
-    scenes.build_cornell(e)
-    return e, e.create_camera(scenes.cornell_camera(size))
 
 
 inf, nan = float("inf"), float("nan")
@@ -79,21 +48,7 @@ GOOD = [dict(flags=1), dict(samples=0), dict(samples=2), dict(samples=32), dict(
 
 def test_argument_errors_on_a_host_only_engine():
     e, cam = _host_camera()
-    b, h = e._b, e._h
-
-    def st(d, camera=cam, engine=h):
-        return b.camera_set_motion_blur(engine, camera, C.byref(d) if d is not None else None)
-
-    assert st(_d()) == ST_OK and st(None) == ST_OK
-    assert st(_d(), engine=None) == ST_ERR_INVALID_ARGUMENT
-    assert st(_d(), camera=cam + 99) == ST_ERR_UNKNOWN_CAMERA and st(None, camera=cam + 99) == ST_ERR_UNKNOWN_CAMERA
-    for kw in BAD:
-        assert st(_d(**kw)) == ST_ERR_INVALID_ARGUMENT, kw
-    for kw in GOOD:
-        assert st(_d(**kw)) == ST_OK, kw
-    assert b.camera_get_motion_blur(h, cam, None, None) == ST_OK
-    assert b.camera_get_motion_blur(h, cam + 99, None, None) == ST_ERR_UNKNOWN_CAMERA
-    assert b.camera_get_motion_blur(None, cam, None, None) == ST_ERR_INVALID_ARGUMENT
+    A.argument_errors(e, cam, "camera_set_motion_blur", "camera_get_motion_blur", _d, BAD, GOOD)
     with pytest.raises(StrolleError):
         e.set_motion_blur(cam, samples=5)
     e.close()
@@ -147,20 +102,8 @@ def test_set_get_round_trip_and_survival_on_a_host_only_engine():
 
 def test_the_blur_and_a_window_exclude_each_other_on_a_host_only_engine():
     e, cam = _host_camera()
-    b, h = e._b, e._h
     d = _d()
-    assert b.camera_set_window(h, cam, 0, 0, 32, 48) == ST_OK
-    assert b.camera_set_motion_blur(h, cam, C.byref(d)) == ST_ERR_INVALID_ARGUMENT   # the window came first
-    assert not e.get_motion_blur(cam)[1]
-    assert b.camera_set_motion_blur(h, cam, None) == ST_OK                            # turning it off is always fine
-    assert b.camera_set_window(h, cam, 0, 0, 0, 0) == ST_OK                           # back to the whole frame
-    assert b.camera_set_motion_blur(h, cam, C.byref(d)) == ST_OK
-    assert b.camera_set_window(h, cam, 16, 0, 64, 48) == ST_ERR_INVALID_ARGUMENT      # the blur came first
-    assert b.camera_set_window(h, cam, 0, 8, 64, 48) == ST_ERR_INVALID_ARGUMENT
-    assert b.camera_set_rows(h, cam, 0, 24) == ST_ERR_INVALID_ARGUMENT
-    assert b.camera_set_window(h, cam, 0, 0, 64, 48) == ST_OK                         # the whole frame is no tile
-    assert b.camera_set_motion_blur(h, cam, None) == ST_OK
-    assert b.camera_set_window(h, cam, 16, 0, 64, 48) == ST_OK                        # off: windows work again
+    A.node_and_window_exclude_each_other(e, cam, "camera_set_motion_blur", d, lambda: e.get_motion_blur(cam)[1])
     e.close()
 
 

@@ -5,57 +5,32 @@ says that it needs a device, and the numpy restatement (post_ref.py) gives hand-
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import output_chain_abi as A
 import post_ref as R
 from parity import bits_equal_mask
-from strolle_amd import Engine, PassBit, ResampleFilter, StrolleError, post_desc, scenes
+from strolle_amd import PassBit, ResampleFilter, StrolleError, post_desc, scenes
+from output_chain_abi import ST_ERR_INVALID_ARGUMENT, ST_ERR_NO_DEVICE, ST_ERR_UNKNOWN_CAMERA, ST_OK, host_camera as _host_camera
 from strolle_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ST_OK, ST_ERR_INVALID_ARGUMENT, ST_ERR_NO_DEVICE, ST_ERR_UNKNOWN_CAMERA = 0, 1, 2, 3
 ENTRY_POINTS = ("st_camera_set_post", "st_camera_get_post", "st_camera_output_size", "st_post_process")
 FIELDS = ["struct_size", "flags", "output_width", "output_height", "filter", "fxaa_edge_threshold", "fxaa_edge_threshold_min", "fxaa_subpixel"]
 F = np.float32
 
 
 def test_entry_points_are_exported_declared_and_bound():
-    lib = api.load_library()
-    header = open(os.path.join(ROOT, "include", "strolle_hip.h")).read()
-    ffi = open(os.path.join(ROOT, "rust", "strolle-hip", "src", "ffi.rs")).read()
-    for name in ENTRY_POINTS:
-        assert hasattr(lib, name), name
-        assert re.search(r"\bint %s\(" % name, header), name
-        assert re.search(r"pub fn %s\(" % name, ffi), name
-    c_body = re.search(r"typedef struct StPostDesc \{(.*?)\} StPostDesc;", re.sub(r"/\*.*?\*/", "", header, flags=re.S), re.S).group(1)
-    c_fields = [n.strip() for d in c_body.split(";") if d.strip() for n in d.strip().split(None, 1)[1].split(",")]
-    r_fields = re.findall(r"pub (\w+):", re.search(r"pub struct StPostDesc \{(.*?)\n\}", ffi, re.S).group(1))
-    assert c_fields == r_fields == [f for f, _ in api.StPostDesc._fields_] == FIELDS
-    for t in ResampleFilter:
-        assert re.search(r"ST_RESAMPLE_%s = %d\b" % (t.name, t.value), header), t
-        assert re.search(r"pub const ST_RESAMPLE_%s: u32 = %d;" % (t.name, t.value), ffi), t
+    header, ffi = A.exports_header_and_ffi_agree("StPostDesc", FIELDS, ENTRY_POINTS, [("ST_RESAMPLE_%s" % t.name, t.value) for t in ResampleFilter])
     assert "pub const ST_POST_FXAA: u32 = 1;" in ffi and "pub const ST_PASS_POST: u64 = 1 << 30;" in ffi
     assert re.search(r"ST_PASS_POST = 1u << 30\b", header) and PassBit.POST == 1 << 30
 
 
 def test_desc_layout_agrees_between_c_and_ctypes(tmp_path):
-    gcc = shutil.which("gcc") or shutil.which("cc")
-    if gcc is None:
-        pytest.fail("no C compiler on PATH")
-    src = tmp_path / "layout.c"
-    offs = ", ".join("offsetof(StPostDesc, %s)" % f for f in FIELDS)
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "strolle_hip.h"\nint main(void) { printf("%zu' + " %zu" * len(FIELDS)
-                   + ' %d %d %d %u\\n", sizeof(StPostDesc), ' + offs + ', ST_POST_FXAA, ST_RESAMPLE_BILINEAR, ST_RESAMPLE_CATMULL_ROM, (unsigned)ST_PASS_POST); return 0; }\n')
-    exe = tmp_path / "layout"
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = list(map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()))
-    D = api.StPostDesc
+    got = A.c_layout(tmp_path, "StPostDesc", FIELDS, ["ST_POST_FXAA", "ST_RESAMPLE_BILINEAR", "ST_RESAMPLE_CATMULL_ROM", "(int)ST_PASS_POST"])
     assert got == [32] + [4 * k for k in range(len(FIELDS))] + [1, 1, 2, 1 << 30]
-    assert got[:1 + len(FIELDS)] == [C.sizeof(D)] + [getattr(D, f).offset for f in FIELDS]
     assert got[-4:-1] == [api.POST_FXAA, ResampleFilter.BILINEAR, ResampleFilter.CATMULL_ROM]
 
 
@@ -64,12 +39,6 @@ def _d(**kw):
     for k, v in kw.items():
         setattr(d, k, v)
     return d
-
-
-def _host_camera(size=(64, 48)):
-    e = Engine(device=-1)
-    scenes.build_cornell(e)
-    return e, e.create_camera(scenes.cornell_camera(size))
 
 
 def test_argument_errors_on_a_host_only_engine():
@@ -158,18 +127,7 @@ def test_post_and_a_window_exclude_each_other_on_a_host_only_engine():
     e, cam = _host_camera()
     b, h = e._b, e._h
     for d in (_d(), post_desc(fxaa=True), post_desc(output_size=(128, 96))):
-        assert b.camera_set_window(h, cam, 0, 0, 32, 48) == ST_OK
-        assert b.camera_set_post(h, cam, C.byref(d)) == ST_ERR_INVALID_ARGUMENT   # the window came first
-        assert not e.post(cam)[1]
-        assert b.camera_set_post(h, cam, None) == ST_OK                            # turning it off is always fine
-        assert b.camera_set_window(h, cam, 0, 0, 0, 0) == ST_OK                    # back to the whole frame
-        assert b.camera_set_post(h, cam, C.byref(d)) == ST_OK
-        assert b.camera_set_window(h, cam, 16, 0, 64, 48) == ST_ERR_INVALID_ARGUMENT   # post-processing came first
-        assert b.camera_set_window(h, cam, 0, 8, 64, 48) == ST_ERR_INVALID_ARGUMENT
-        assert b.camera_set_rows(h, cam, 0, 24) == ST_ERR_INVALID_ARGUMENT
-        assert b.camera_set_window(h, cam, 0, 0, 64, 48) == ST_OK                  # the whole frame is no tile
-        assert b.camera_set_post(h, cam, None) == ST_OK
-        assert b.camera_set_window(h, cam, 16, 0, 64, 48) == ST_OK                 # off: windows work again
+        A.node_and_window_exclude_each_other(e, cam, "camera_set_post", d, lambda: e.post(cam)[1])
         assert b.camera_set_window(h, cam, 0, 0, 0, 0) == ST_OK
     e.close()
 

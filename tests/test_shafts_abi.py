@@ -10,21 +10,20 @@ import json
 import math
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import shafts_cases as K
 import shafts_ref as R
+import output_chain_abi as A
 from fog_ref import exp_
 from strolle_amd import Engine, Light, StrolleError, Tonemap, display_desc, light_shafts_desc, light_shafts_plan, scenes
+from output_chain_abi import ST_ERR_INVALID_ARGUMENT, ST_ERR_NO_DEVICE, host_camera as _host_camera
 from strolle_amd import api
 from strolle_amd.api import dist_grid
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ST_OK, ST_ERR_INVALID_ARGUMENT, ST_ERR_NO_DEVICE, ST_ERR_UNKNOWN_CAMERA = 0, 1, 2, 3
 ENTRY_POINTS = ("st_camera_set_light_shafts", "st_camera_get_light_shafts", "st_light_shafts_plan", "st_light_shafts_process")
 FIELDS = ["struct_size", "flags", "steps", "divisor", "density", "anisotropy", "max_distance", "intensity", "scatter", "_pad", "sun_color", "_pad2", "sun_direction",
           "light_count", "lights"]
@@ -43,38 +42,15 @@ def _tool():
 
 
 def test_entry_points_are_exported_declared_and_bound():
-    lib = api.load_library()
-    header = open(os.path.join(ROOT, "include", "strolle_hip.h")).read()
-    ffi = open(os.path.join(ROOT, "rust", "strolle-hip", "src", "ffi.rs")).read()
+    A.exports_header_and_ffi_agree("StLightShaftsDesc", FIELDS, ENTRY_POINTS, [("ST_SHAFTS_FOLLOW_SUN", 1), ("ST_SHAFTS_LIGHT_EXTINCTION", 2)])
     facade = open(os.path.join(ROOT, "rust", "strolle-hip", "src", "lib.rs")).read()
-    for name in ENTRY_POINTS:
-        assert hasattr(lib, name), name
-        assert re.search(r"\bint %s\(" % name, header), name
-        assert re.search(r"pub fn %s\(" % name, ffi), name
     assert "pub fn set_light_shafts(" in facade and "ffi::st_camera_set_light_shafts(" in facade
-    c_body = re.search(r"typedef struct StLightShaftsDesc \{(.*?)\} StLightShaftsDesc;", re.sub(r"/\*.*?\*/", "", header, flags=re.S), re.S).group(1)
-    c_fields = [re.sub(r"\[\d+\]", "", n.strip()) for d in c_body.split(";") if d.strip() for n in d.strip().split(None, 1)[1].split(",")]
-    r_fields = re.findall(r"pub (\w+):", re.search(r"pub struct StLightShaftsDesc \{(.*?)\n\}", ffi, re.S).group(1))
-    assert c_fields == r_fields == [f for f, _ in api.StLightShaftsDesc._fields_] == FIELDS
-    assert re.search(r"ST_SHAFTS_FOLLOW_SUN = 1\b", header) and re.search(r"ST_SHAFTS_LIGHT_EXTINCTION = 2\b", header)
-    assert "pub const ST_SHAFTS_FOLLOW_SUN: u32 = 1;" in ffi and "pub const ST_SHAFTS_LIGHT_EXTINCTION: u32 = 2;" in ffi
     assert api.SHAFTS_FOLLOW_SUN == R.FOLLOW_SUN == 1 and api.SHAFTS_LIGHT_EXTINCTION == R.LIGHT_EXTINCTION == 2
 
 
 def test_desc_layout_agrees_between_c_and_ctypes(tmp_path):
-    gcc = shutil.which("gcc") or shutil.which("cc")
-    if gcc is None:
-        pytest.fail("no C compiler on PATH")
-    src = tmp_path / "layout.c"
-    offs = ", ".join("offsetof(StLightShaftsDesc, %s)" % f for f in FIELDS)
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "strolle_hip.h"\nint main(void) { printf("%zu' + " %zu" * len(FIELDS)
-                   + ' %d %d %d\\n", sizeof(StLightShaftsDesc), ' + offs + ', ST_SHAFTS_FOLLOW_SUN, ST_SHAFTS_LIGHT_EXTINCTION, ST_SHAFTS_MAX_LIGHTS); return 0; }\n')
-    exe = tmp_path / "layout"
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = list(map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()))
-    D = api.StLightShaftsDesc
+    got = A.c_layout(tmp_path, "StLightShaftsDesc", FIELDS, ["ST_SHAFTS_FOLLOW_SUN", "ST_SHAFTS_LIGHT_EXTINCTION", "ST_SHAFTS_MAX_LIGHTS"])
     assert got == [144] + OFFSETS + [1, 2, 8]
-    assert got[:1 + len(FIELDS)] == [C.sizeof(D)] + [getattr(D, f).offset for f in FIELDS]
 
 
 def _d(**kw):
@@ -92,12 +68,6 @@ def _d(**kw):
     return d
 
 
-def _host_camera(size=(64, 48)):
-    e = Engine(device=-1)
-    scenes.build_cornell(e)
-    return e, e.create_camera(scenes.cornell_camera(size))
-
-
 BAD = [dict(struct_size=140), dict(struct_size=148), dict(struct_size=0), dict(flags=4), dict(flags=0x80000001), dict(steps=0), dict(steps=65), dict(divisor=0), dict(divisor=3),
        dict(divisor=4), dict(density=-0.1), dict(density=nan), dict(density=inf), dict(anisotropy=0.96), dict(anisotropy=-0.96), dict(anisotropy=nan),
        dict(max_distance=0.0), dict(max_distance=-1.0), dict(max_distance=inf), dict(max_distance=nan), dict(intensity=-1.0), dict(intensity=nan), dict(intensity=inf),
@@ -111,22 +81,10 @@ GOOD = [dict(flags=f) for f in range(4)] + [dict(steps=1), dict(steps=64), dict(
 
 def test_argument_errors_on_a_host_only_engine():
     e, cam = _host_camera()
-    b, h = e._b, e._h
-
-    def st(d, camera=cam, engine=h):
-        return b.camera_set_light_shafts(engine, camera, C.byref(d) if d is not None else None)
-
-    assert st(_d()) == ST_OK and st(None) == ST_OK
-    assert st(_d(), engine=None) == ST_ERR_INVALID_ARGUMENT
-    assert st(_d(), camera=cam + 99) == ST_ERR_UNKNOWN_CAMERA and st(None, camera=cam + 99) == ST_ERR_UNKNOWN_CAMERA
-    for kw in BAD:
-        assert st(_d(**kw)) == ST_ERR_INVALID_ARGUMENT, kw
+    def still_off(kw):
         assert not e.get_light_shafts(cam)[1], kw   # a refused desc leaves the setting as it was
-    for kw in GOOD:
-        assert st(_d(**kw)) == ST_OK, kw
-    assert b.camera_get_light_shafts(h, cam, None, None) == ST_OK
-    assert b.camera_get_light_shafts(h, cam + 99, None, None) == ST_ERR_UNKNOWN_CAMERA
-    assert b.camera_get_light_shafts(None, cam, None, None) == ST_ERR_INVALID_ARGUMENT
+
+    A.argument_errors(e, cam, "camera_set_light_shafts", "camera_get_light_shafts", _d, BAD, GOOD, each_bad=still_off)
     with pytest.raises(StrolleError):
         e.set_light_shafts(cam, steps=100)
     e.close()
@@ -193,20 +151,8 @@ def test_set_get_round_trip_and_survival_on_a_host_only_engine():
 
 def test_light_shafts_and_a_window_exclude_each_other_on_a_host_only_engine():
     e, cam = _host_camera()
-    b, h = e._b, e._h
     d = _d()
-    assert b.camera_set_window(h, cam, 0, 0, 32, 48) == ST_OK
-    assert b.camera_set_light_shafts(h, cam, C.byref(d)) == ST_ERR_INVALID_ARGUMENT   # the window came first
-    assert not e.get_light_shafts(cam)[1]
-    assert b.camera_set_light_shafts(h, cam, None) == ST_OK
-    assert b.camera_set_window(h, cam, 0, 0, 0, 0) == ST_OK
-    assert b.camera_set_light_shafts(h, cam, C.byref(d)) == ST_OK
-    assert b.camera_set_window(h, cam, 16, 0, 64, 48) == ST_ERR_INVALID_ARGUMENT       # the node came first
-    assert b.camera_set_window(h, cam, 0, 8, 64, 48) == ST_ERR_INVALID_ARGUMENT
-    assert b.camera_set_rows(h, cam, 0, 24) == ST_ERR_INVALID_ARGUMENT
-    assert b.camera_set_window(h, cam, 0, 0, 64, 48) == ST_OK                          # the whole frame is no tile
-    assert b.camera_set_light_shafts(h, cam, None) == ST_OK
-    assert b.camera_set_window(h, cam, 16, 0, 64, 48) == ST_OK
+    A.node_and_window_exclude_each_other(e, cam, "camera_set_light_shafts", d, lambda: e.get_light_shafts(cam)[1])
     e.close()
     ranks = []
     for r in range(2):

@@ -18,7 +18,6 @@ import argparse
 import csv
 import json
 import os
-import subprocess
 import sys
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -26,17 +25,11 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402,F401  (before the library: torch's bundled HIP runtime has to be the first one loaded)
 
-WARMUP, FRAMES, HD, UHD = 20, 120, (1920, 1080), (3840, 2160)
-BLOOM = dict(intensity=0.15, levels=6)
+from chain_bench import BLOOM, FRAMES, HD, WARMUP, abab, merge  # noqa: E402
+
+UHD = (3840, 2160)
 # name: (bloom, post, tail budget: -1 the device's, 0 the straightforward chain)
 VARIANTS = {"off": (False, False, 0), "bloom": (True, False, 0), "bloom_fused_tail": (True, False, -1), "post": (False, True, 0), "bloom_post": (True, True, 0)}
-
-
-def merge(path, rec):
-    old = json.load(open(path)) if os.path.exists(path) else {}
-    old.update(rec)
-    json.dump(old, open(path, "w"), indent=1)
-    print(json.dumps(rec, indent=1))
 
 
 def frame_ms(scene, bloom, post, tail, frames=FRAMES):
@@ -121,14 +114,7 @@ def main():
     ap.add_argument("--chains-only", action="store_true", help="only (b) and (c)")
     args = ap.parse_args()
     if args.abab:
-        series = {"parent": [], "this": []}
-        for _ in range(2):
-            for name, root in (("parent", args.abab), ("this", ROOT)):
-                r = subprocess.run([sys.executable, os.path.join(os.path.abspath(root), "bench.py"), "--gpus", "1", "--steps", "60", "--warmup", "15"], cwd=os.path.abspath(root), capture_output=True, text=True, check=True, timeout=300)
-                series[name].append(json.loads(r.stdout.strip().splitlines()[-1])["ms_per_step"])
-        mean = {k: sum(v) / len(v) for k, v in series.items()}
-        merge(args.out, {"bench_py_1080p_bloom_off_abab_ms_per_step": {"order": "parent this parent this", **series, "mean_difference": round(mean["this"] - mean["parent"], 5),
-                                                                        "parent_spread": round(max(series["parent"]) - min(series["parent"]), 5)}})
+        merge(args.out, abab(args.abab, "bloom_off", (("bench_py_1080p", []),), flags=()))
         return
     from strolle_amd import Engine, bloom_desc
     if args.profile_child:

@@ -16,80 +16,27 @@
   python tools/fog_bench.py [--out profiles/fog.json] [--restatement | --kernel-stats | --profile-child | --abab DIR]
 """
 import argparse
-import csv
-import glob
 import json
 import os
-import subprocess
 import sys
-import tempfile
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))   # fog_ref.py, fog_cases.py, test_fog_abi.py: the restatement's deviation
 
-WARMUP, FRAMES, HD = 20, 120, (1920, 1080)
+from chain_bench import BLOOM, BLUR, DOF, FRAMES, HD, WARMUP, abab, kernel_stats, merge, run_frames  # noqa: E402
+
 FOG = dict(falloff=1, color=(0.55, 0.62, 0.7, 1.0), density=0.06, height_falloff=0.3, height_reference=0.0, light_color=(1.0, 0.8, 0.5), light_exponent=8.0,
            light_direction=(0.3, 0.5, -0.8))
 FOG_SKY = dict(FOG, sky_distance=200.0)
-DOF = dict(samples=32, aperture_f_stops=0.25, autofocus=(0.5, 0.5))
 SHARP = dict(samples=32, aperture_f_stops=1000.0, autofocus=(0.5, 0.5))   # |coc| < 0.5 everywhere: depth of field's copy path
-BLUR = dict(shutter=0.5, samples=8)
-BLOOM = dict(intensity=0.15, levels=6)
 # name: (fog, depth of field + motion blur + bloom + FXAA under a moving camera)
 VARIANTS = {"off": (None, False), "fog": (FOG, False), "fog_sky": (FOG_SKY, False), "fog_dof_motion_blur_bloom_fxaa": (FOG, True)}
-EYES = {"cornell": ((0.0, 1.0, 3.2), (0.0, 1.0, 0.0)), "dungeon": ((-5.75, 0.5, -16.8), (-5.75, 0.5, -17.0))}
+CHAIN = dict(set_dof=DOF, set_motion_blur=BLUR, set_bloom=BLOOM, set_post=dict(fxaa=True))
 
 
-def merge(path, rec):
-    old = json.load(open(path)) if os.path.exists(path) else {}
-    old.update(rec)
-    json.dump(old, open(path, "w"), indent=1)
-    print(json.dumps(rec, indent=1))
-
-
-def camera(scene, k, moving):
-    import math
-    from strolle_amd import CameraMode, scenes
-    (ex, ey, ez), (tx, ty, tz) = EYES[scene]
-    dx = 0.25 * math.sin(0.35 * k) if moving else 0.0
-    return scenes.camera_for(HD, (ex + dx, ey + 0.3 * dx, ez), (tx + 0.5 * dx, ty, tz), CameraMode.IMAGE)
-
-
-def run_frames(scene, fog, chain, frames=FRAMES, warmup=WARMUP, serial=False, dof=None):
-    import torch
-    from strolle_amd import Engine, OutputFormat, Tonemap, scenes
-    e = Engine(device=0)
-    if serial:
-        e.set_tuning(overlap=0)   # one stream: a launch's time is its own, not that of a launch sharing the chip with the side stream's
-    (scenes.build_cornell if scene == "cornell" else scenes.build_dungeon)(e)
-    e.set_seed(7)
-    cam = e.create_camera(camera(scene, 0, chain))
-    e.set_output_format(cam, OutputFormat.RGBA8_UNORM_SRGB)
-    e.set_display(cam, tonemap=Tonemap.ACES_FITTED)
-    if fog:
-        e.set_fog(cam, **fog)
-    if dof:
-        e.set_dof(cam, **dof)
-    if chain:
-        e.set_dof(cam, **DOF)
-        e.set_motion_blur(cam, **BLUR)
-        e.set_bloom(cam, **BLOOM)
-        e.set_post(cam, fxaa=True)
-    w, h = e.output_size(cam)
-    out = torch.zeros((h, w, 4), dtype=torch.uint8, device="cuda:0")
-    s = torch.cuda.Stream()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for k in range(warmup + frames):
-        if k == warmup:
-            torch.cuda.synchronize(); a.record(s)
-        if chain:
-            e.update_camera(cam, camera(scene, k, True))
-        e.tick(s.cuda_stream)
-        e.render_camera(cam, out.data_ptr(), s.cuda_stream)
-    b.record(s); torch.cuda.synchronize()
-    e.close()
-    return a.elapsed_time(b) / frames
+def frames_ms(scene, fog, chain, **kw):
+    return run_frames(scene, dict(set_fog=fog, **(CHAIN if chain else {})), moving=chain, **kw)
 
 
 def launch_bytes(w, h, out_bytes=4):
@@ -113,39 +60,15 @@ def main():
         return
     import torch  # noqa: F401  (before the library: torch's bundled HIP runtime has to be the first one loaded)
     if args.abab:
-        rec = {}
-        for key, extra in (("bench_py_headline", []), ("bench_py_dungeon_1080p", ["--scene", "dungeon"])):
-            series = {"parent": [], "this": []}
-            for _ in range(2):
-                for name, root in (("parent", args.abab), ("this", ROOT)):
-                    r = subprocess.run([sys.executable, os.path.join(os.path.abspath(root), "bench.py"), "--gpus", "1", "--steps", "60", "--warmup", "15", "--no-extras", "--no-cpu-baseline"] + extra,
-                                       cwd=os.path.abspath(root), capture_output=True, text=True, check=True, timeout=300)
-                    series[name].append(json.loads(r.stdout.strip().splitlines()[-1])["ms_per_step"])
-            mean = {k: sum(v) / len(v) for k, v in series.items()}
-            rec[key + "_fog_off_abab_ms_per_step"] = {"order": "parent this parent this", **series, "mean_difference": round(mean["this"] - mean["parent"], 5),
-                                                     "parent_spread": round(max(series["parent"]) - min(series["parent"]), 5)}
-        merge(args.out, rec)
+        merge(args.out, abab(args.abab, "fog_off"))
         return
     if args.profile_child:   # the dungeon on the serial schedule, 30 frames each: fog, then depth of field with everything in focus
-        run_frames("dungeon", FOG_SKY, False, frames=30, warmup=10, serial=True)
-        run_frames("dungeon", None, False, frames=30, warmup=10, serial=True, dof=SHARP)
+        frames_ms("dungeon", FOG_SKY, False, frames=30, warmup=10, serial=True)
+        run_frames("dungeon", dict(set_dof=SHARP), frames=30, warmup=10, serial=True)
         return
     if args.kernel_stats:
         ceiling = json.load(open(args.out))["copy_ceiling_gb_s"]
-        with tempfile.TemporaryDirectory() as tmp:
-            subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "fog", "--", sys.executable, os.path.abspath(__file__), "--profile-child"],
-                           check=True, timeout=600, capture_output=True, text=True)
-            trace = glob.glob(os.path.join(tmp, "**", "*kernel_trace.csv"), recursive=True)[0]
-            with open(trace) as f:
-                rows = list(csv.DictReader(f))
-        out = {}
-        for kernel, nbytes in launch_bytes(*HD).items():
-            us = sorted((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if kernel in r["Kernel_Name"])
-            if not us:
-                continue
-            med = us[len(us) // 2]
-            out[kernel] = {"median_us": round(med, 2), "dispatches": len(us), "compulsory_bytes": nbytes, "bytes_over_copy_ceiling_us": round(nbytes / (ceiling * 1e3), 2),
-                           "time_over_that": round(med / (nbytes / (ceiling * 1e3)), 2)}
+        out = kernel_stats(__file__, ["--profile-child"], launch_bytes(*HD), ceiling, "fog")
         merge(args.out, {"kernel_stats_dungeon_1080p_serial_schedule": out})
         return
     from strolle_amd import Engine
@@ -156,7 +79,7 @@ def main():
         rec[scene + "_ms_per_frame"] = {}
         for _ in range(2):   # interleaved twice: the spread of one box
             for name, (fog, chain) in VARIANTS.items():
-                rec[scene + "_ms_per_frame"].setdefault(name, []).append(round(run_frames(scene, fog, chain), 4))
+                rec[scene + "_ms_per_frame"].setdefault(name, []).append(round(frames_ms(scene, fog, chain), 4))
     e = Engine(device=0)
     rec["copy_ceiling_gb_s"] = round(float(e.copy_bandwidth()), 1)
     e.close()

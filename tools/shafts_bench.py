@@ -17,27 +17,23 @@
   python tools/shafts_bench.py [--out profiles/light_shafts.json] [--reference | --yardstick | --kernel-stats | --profile-child | --abab DIR]
 """
 import argparse
-import csv
-import glob
-import json
 import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))   # (the tests load this file by its path)
+
+from chain_bench import BLOOM, BLUR, DOF, FOG, FRAMES, HD, WARMUP, abab, camera, kernel_stats, merge, run_frames  # noqa: E402
 
 PROFILE = os.path.join(ROOT, "profiles", "light_shafts.json")
 THRESHOLD_FLOOR = 16 * 2.0 ** -24
-WARMUP, FRAMES, HD = 20, 120, (1920, 1080)
-EYES = {"cornell": ((0.0, 1.0, 3.2), (0.0, 1.0, 0.0)), "dungeon": ((-5.75, 0.5, -16.8), (-5.75, 0.5, -17.0))}
 MEDIUM = dict(density=0.05, anisotropy=0.6, max_distance=40.0, intensity=1.0, scatter=(0.9, 0.9, 0.9))
 SUN = dict(sun_color=(4.0, 3.5, 3.0), sun_direction=(0.3, 0.8, 0.2))
-CHAIN = dict(dof=dict(samples=32, aperture_f_stops=0.25, autofocus=(0.5, 0.5)), blur=dict(shutter=0.5, samples=8), bloom=dict(intensity=0.15, levels=6))
+CHAIN = dict(set_fog=FOG, set_dof=DOF, set_motion_blur=BLUR, set_bloom=BLOOM, set_post=dict(fxaa=True))
 # name: (desc keywords or None, lights taken from the scene, the chain behind it)
 VARIANTS = {
     "off": (None, 0, False),
@@ -49,13 +45,6 @@ VARIANTS = {
     "sun_2lights_d2_s16_fog_dof_motion_blur_bloom_fxaa": (dict(steps=16, divisor=2, **MEDIUM, **SUN), 2, True),
 }
 SCENE_LIGHTS = {"cornell": (1,), "dungeon": (1, 3)}
-
-
-def merge(path, rec):
-    old = json.load(open(path)) if os.path.exists(path) else {}
-    old.update(rec)
-    json.dump(old, open(path, "w"), indent=1)
-    print(json.dumps(rec, indent=1))
 
 
 def round_up(x, digits=3):
@@ -150,44 +139,9 @@ def measure_reference(scene):
 
 
 # ---------------------------------------------------------------- the cost (GPU)
-def camera(scene, k, moving):
-    import math
-    from strolle_amd import CameraMode, scenes
-    (ex, ey, ez), (tx, ty, tz) = EYES[scene]
-    dx = 0.25 * math.sin(0.35 * k) if moving else 0.0
-    return scenes.camera_for(HD, (ex + dx, ey + 0.3 * dx, ez), (tx + 0.5 * dx, ty, tz), CameraMode.IMAGE)
-
-
-def run_frames(scene, shafts, n_lights, chain, frames=FRAMES, warmup=WARMUP, serial=False):
-    import torch
-    from strolle_amd import Engine, OutputFormat, Tonemap, scenes
-    e = Engine(device=0)
-    if serial:
-        e.set_tuning(overlap=0)
-    (scenes.build_cornell if scene == "cornell" else scenes.build_dungeon)(e)
-    e.set_seed(7)
-    cam = e.create_camera(camera(scene, 0, chain))
-    e.set_output_format(cam, OutputFormat.RGBA8_UNORM_SRGB)
-    e.set_display(cam, tonemap=Tonemap.ACES_FITTED)
-    if shafts:
-        e.set_light_shafts(cam, lights=SCENE_LIGHTS[scene][:n_lights], **shafts)
-    if chain:
-        e.set_fog(cam, falloff=1, color=(0.55, 0.62, 0.7, 1.0), density=0.06)
-        e.set_dof(cam, **CHAIN["dof"]); e.set_motion_blur(cam, **CHAIN["blur"]); e.set_bloom(cam, **CHAIN["bloom"]); e.set_post(cam, fxaa=True)
-    w, h = e.output_size(cam)
-    out = torch.zeros((h, w, 4), dtype=torch.uint8, device="cuda:0")
-    s = torch.cuda.Stream()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for k in range(warmup + frames):
-        if k == warmup:
-            torch.cuda.synchronize(); a.record(s)
-        if chain:
-            e.update_camera(cam, camera(scene, k, True))
-        e.tick(s.cuda_stream)
-        e.render_camera(cam, out.data_ptr(), s.cuda_stream)
-    b.record(s); torch.cuda.synchronize()
-    e.close()
-    return a.elapsed_time(b) / frames
+def frames_ms(scene, shafts, n_lights, chain, **kw):
+    settings = dict(set_light_shafts=dict(shafts, lights=SCENE_LIGHTS[scene][:n_lights]) if shafts else None, **(CHAIN if chain else {}))
+    return run_frames(scene, settings, moving=chain, **kw)
 
 
 def yardstick():
@@ -242,39 +196,18 @@ def main():
                                            "|shafts_f32 (probe visibility) - shafts_f64 (brute force)| / max(1, |shafts_f64|) over the pixels none of whose cells is ambiguous."})
         return
     import torch  # noqa: F401  (before the library: torch's bundled HIP runtime has to be the first one loaded)
-    if args.abab:
-        rec = {}
-        for key, extra in (("bench_py_headline", []), ("bench_py_dungeon_1080p", ["--scene", "dungeon"])):
-            series = {"parent": [], "this": []}
-            for name, root in [("parent", args.abab), ("this", ROOT), ("this", ROOT), ("parent", args.abab)] * 3:   # A B B A three times: neither side always runs second
-                if True:
-                    r = subprocess.run([sys.executable, os.path.join(os.path.abspath(root), "bench.py"), "--gpus", "1", "--steps", "60", "--warmup", "15", "--no-extras", "--no-cpu-baseline"] + extra,
-                                       cwd=os.path.abspath(root), capture_output=True, text=True, check=True, timeout=300)
-                    series[name].append(json.loads(r.stdout.strip().splitlines()[-1])["ms_per_step"])
-            mean = {k: sum(v) / len(v) for k, v in series.items()}
-            rec[key + "_shafts_off_abab_ms_per_step"] = {"order": "parent this this parent, three times", **series, "mean_difference": round(mean["this"] - mean["parent"], 5),
-                                                        "parent_spread": round(max(series["parent"]) - min(series["parent"]), 5)}
-        merge(args.out, rec)
+    if args.abab:   # A B B A three times: neither side always runs second
+        merge(args.out, abab(args.abab, "shafts_off", order=("parent", "this", "this", "parent") * 3, order_note="parent this this parent, three times"))
         return
     if args.yardstick:
         merge(args.out, yardstick())
         return
     if args.profile_child:
         shafts, n, _ = VARIANTS["sun_2lights_d2_s16"]
-        run_frames("dungeon", shafts, n, False, frames=30, warmup=10, serial=True)
+        frames_ms("dungeon", shafts, n, False, frames=30, warmup=10, serial=True)
         return
     if args.kernel_stats:
-        with tempfile.TemporaryDirectory() as tmp:
-            subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "shafts", "--", sys.executable, os.path.abspath(__file__), "--profile-child"],
-                           check=True, timeout=600, capture_output=True, text=True)
-            trace = glob.glob(os.path.join(tmp, "**", "*kernel_trace.csv"), recursive=True)[0]
-            with open(trace) as f:
-                rows = list(csv.DictReader(f))
-        out = {}
-        for kernel in ("k_shafts_march", "k_shafts_apply"):
-            us = sorted((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if kernel in r["Kernel_Name"])
-            if us:
-                out[kernel] = {"median_us": round(us[len(us) // 2], 2), "dispatches": len(us)}
+        out = kernel_stats(__file__, ["--profile-child"], {"k_shafts_march": None, "k_shafts_apply": None}, None, "shafts")
         merge(args.out, {"kernel_stats_dungeon_1080p_sun_2lights_d2_s16_serial_schedule": out})
         return
     rec = {"render_size": list(HD), "mode": "Image{denoise}", "format": "RGBA8_UNORM_SRGB", "display": "ACES_FITTED", "build": "fast", "frames": FRAMES, "warmup": WARMUP,
@@ -283,7 +216,7 @@ def main():
         rec[scene + "_ms_per_frame"] = {}
         for _ in range(2):   # interleaved twice: the spread of one box
             for name, (shafts, n, chain) in VARIANTS.items():
-                rec[scene + "_ms_per_frame"].setdefault(name, []).append(round(run_frames(scene, shafts, n, chain), 4))
+                rec[scene + "_ms_per_frame"].setdefault(name, []).append(round(frames_ms(scene, shafts, n, chain), 4))
     merge(args.out, rec)
 
 
