@@ -607,7 +607,8 @@ int st_post_process(StEngine* e, const StPostDesc* desc, const void* src_rgba32f
  *   launches without bloom, with the same arguments. The setting survives st_camera_update and st_engine_set_arithmetic. While a frame
  *   blooms, the composing launch writes the composed colour, untransformed, into a camera-owned render-size RGBA32F plane (and meters it);
  *   2 L launches (ST_PASS_POST, in front of FXAA and the resampler) follow on the caller's stream: L downsamples, L - 1 upsamples
- *   and the composite, which also runs the display transform and writes the output format (or the post-processing plane). The pyramid is one
+ *   and the composite, which also runs the display transform and writes the output format (or the post-processing plane; with colour
+ *   grading on, below, the composite stores its colour untransformed into the grade's RGBA32F plane instead). The pyramid is one
  *   allocation, made by the first frame that needs it and again only when a larger render size or level count needs a larger one.
  * - Arithmetic: float32, evaluated left to right as written, no fused multiply-add, division correctly rounded, in BOTH builds;
  *   tests/bloom_ref.py restates all of it in numpy and the kernels match it bit for bit. min / max are the post-processing section's
@@ -1030,6 +1031,118 @@ int st_light_shafts_plan(const StLightShaftsDesc* desc, uint32_t width, uint32_t
 int st_light_shafts_process(StEngine* e, const StLightShaftsDesc* desc, const StDisplayDesc* display, const float transform[16],
                             const float projection[16], const void* color_device, const void* depth_device, uint32_t width, uint32_t height,
                             void* dst_device, int dst_format /* StOutputFormat */, void* hip_stream);
+
+/* ---- colour grading (NEW seam): white balance, contrast, saturation, an ASC CDL, a 3-D look-up table and deband dither around the display
+ * transform (st_grade.cpp, k_grade.hip, st_cube.h). What Bevy's tone-mapping node does around the operator itself: ColorGrading in front
+ * of it, the LUT-based tone mappers (AgX, BlenderFilmic, TonyMcMapface: 3-D tables over a log2 shaper) in place of it, DebandDither behind
+ * it. The sixth and last HDR node: it reads its render-size RGBA32F plane, grades the scene-referred colour (A), applies the camera's
+ * display transform as the last node of the chain always does (B), grades the display-referred result (C) and writes the frame's target
+ * in its format: `out`, or the post-processing plane in front of FXAA. One pointwise launch (ST_PASS_POST, profile slot "color_grading").
+ * - Order: rendering -> fog -> light shafts -> depth of field -> motion blur -> bloom -> colour grading (A, display transform, C) -> FXAA
+ *   -> resample -> output format.
+ * - Scope: as fog's. The setting belongs to the camera, takes effect at its next st_render_camera, survives st_camera_update and
+ *   st_engine_set_arithmetic and changes only what is written to `out_device`: AOVs, picks, scene queries, st_camera_read_buffer, the HDR
+ *   history and the auto-exposure metering (it meters the composed frame) are unchanged. desc == NULL turns it off: the frame then launches
+ *   the kernels it launches without the setting, with the same arguments. ST_MODE_BVH_HEATMAP frames skip the node (false colour);
+ *   ST_MODE_REFERENCE frames and non-perspective projections pass through it: nothing here depends on a G-buffer or on the projection.
+ * - Windows and tiles: the node is pointwise in frame coordinates (dither takes the pixel's coordinates in the whole frame), so a camera
+ *   with a window may grade, in either order of the setters, and gathered graded tiles are the grade of the gathered tiles bit for bit
+ *   (the single engine's frame wherever the renderer's own taps do not cross a tile border). When rank 0 blooms the gathered
+ *   frame instead (bloom excludes windows), the ranks render without a display and without grading and rank 0 calls
+ *   st_color_grading_process behind st_bloom_process: bloom without a display into an RGBA32F plane, then grading with the display.
+ * - Look-up tables: st_lut_insert keeps a table of side N (2..65), N^3 rgb triples, red fastest as in a .cube file; the next st_tick copies
+ *   it to the device on its stream without a host sync, one float4 per texel so that a corner is one 16-B load. A descriptor names a table
+ *   by handle; a handle that names no live table (0, never inserted, removed, or inserted after the last st_tick) skips the LUT step and is
+ *   not an error. Inserting over a live id replaces the table at the next tick. A table removed or replaced while frames that read it are in
+ *   flight stays alive until they have drained (a fence, no host sync in st_render_camera).
+ * - Arithmetic: everything is float32, evaluated left to right as written, no fused multiply-add, division correctly rounded, in BOTH
+ *   builds; tests/grade_ref.py restates all of it in numpy (grade_f32) and the kernel matches it bit for bit. min, max and clamp01 are the
+ *   post-processing section's (NaN rule), Y(r, g, b) = 0.2126 r + 0.7152 g + 0.0722 b is the display section's luminance,
+ *   pw(x, p) = x == 0 ? 0 : exp2p(p log2p(x)) for x >= 0 and lg(x) = log2p(x) with fog's two polynomials (never the hardware's exponential
+ *   and logarithm instructions). A step whose parameters are neutral is skipped and leaves the value's bits untouched: a descriptor that is
+ *   neutral everywhere is on but writes exactly what off writes. Alpha is written as 1 by every step that runs. c is the node's texel.
+ * - A. Scene-referred; runs only when one of its three steps is active, each of which is skipped on its own when neutral.
+ *   v = min(max(c, 0), 65504) per channel (NaN becomes 0).
+ *   White balance (temperature or tint != 0): v = M v, each row summed left to right, then max(., 0). The host computes M in double and
+ *   rounds it once: M = LMS2LIN diag(k) LIN2LMS (the two products formed in that order), k = w1 / w2 per component,
+ *   w1 = (0.949237, 1.03542, 1.08728), w2 the CAT02 LMS of the CIE xy point x = 0.31271 - t (t < 0 ? 0.1 : 0.05),
+ *   y = 2.87 x - 3 x^2 - 0.27509507 + 0.05 u with t = temperature, u = tint: with Y = 1, X = x / y, Z = (1 - x - y) / y,
+ *   L = 0.7328 X + 0.4296 Y - 0.1624 Z, M = -0.7036 X + 1.6975 Y + 0.0061 Z, S = 0.0030 X + 0.0136 Y + 0.9834 Z.
+ *   LIN2LMS = {0.390405 0.549941 0.00892632 / 0.0708416 0.963172 0.00135775 / 0.0231082 0.128021 0.936245},
+ *   LMS2LIN = {2.85847 -1.62879 -0.0248910 / -0.210182 1.15820 0.000324281 / -0.0418120 -0.118169 1.06867} (Unity's and Bevy's).
+ *   Contrast (!= 1), about mid-grey: v = 0.18 pw(v / 0.18, contrast).
+ *   Saturation (!= 1): y = Y(v); v = max(y + (v - y) saturation, 0).
+ *   Stage A ends with min(v, 65504).
+ * - B. Display transform: the camera's operator and its manual or metered scale, exactly the transform every node's last store applies
+ *   (alpha 1). Without a display the colour passes as it is.
+ * - C. Display-referred.
+ *   CDL (skipped when slope = 1, offset = 0, power = 1 in all channels and cdl_saturation = 1): per channel v = max(v slope + offset, 0);
+ *   v = pw(v, power) in the channels whose power != 1; then, when cdl_saturation != 1, y = Y(v); v = max(y + (v - y) cdl_saturation, 0).
+ *   LUT (a handle that names a live table of side N): per channel u = clamp01(v) in ST_LUT_DOMAIN_UNIT (NaN becomes 0); in
+ *   ST_LUT_DOMAIN_LOG2 u = v > 0 ? clamp01((lg(v) - lut_ev_min) inv_range) : 0 with inv_range = 1 / (lut_ev_max - lut_ev_min) computed in
+ *   double and rounded once. p = u float(N - 1); i = min(int(floor(p)), N - 2); f = p - float(i). Texel (ir, ig, ib) lies at index
+ *   (ib N + ig) N + ir. The interpolation is tetrahedral: the three axes ordered by descending f, ties in the order r, g, b, give a, b, c;
+ *   t0 is the cell's low corner, t1 = t0 stepped along a, t2 = t1 stepped along b, t3 the high corner;
+ *   L = ((t0 (1 - fa) + t1 (fa - fb)) + t2 (fb - fc)) + t3 fc per channel. The result is L when lut_strength == 1, else
+ *   v + (L - v) lut_strength.
+ *   Dither (ST_GRADE_DITHER; Bevy's screen_space_dither): (x, y) the pixel's coordinates in the whole frame; n = 171 x + 231 y in integers
+ *   (exact in float up to 16384^2); d = float(n); for channel k with q = (103, 71, 97): t = d / q; t = t - floor(t);
+ *   delta = (t - 0.5) / 255; v = pw(max(pw(max(v, 0), g1) + delta, 0), 2.2f) with g1 the float nearest 1 / 2.2.
+ *   Then the target's format.
+ * - Reading of the first statement where it left a choice: (1) the CDL's power is looked at per channel, so a channel whose power is 1
+ *   keeps the bits of max(v slope + offset, 0); (2) i is also held at 0 from below, which changes no value (u is in [0, 1]) and keeps a
+ *   corner load inside the table whatever the arithmetic in front of it does; (3) st_lut_insert after the last st_tick is "no live table"
+ *   for the frames until the next one, like every other scene edit.
+ * - Known limits: the LOG2 domain takes lut_strength 1 only (a blend of display-referred L with the scene-referred v has no meaning);
+ *   with ST_TONEMAP_NONE and no stage A an exposed value may overflow to +inf before stage C, and a half-strength LUT then gives NaN;
+ *   dither is sized for 8-bit targets (1 / 255) whatever the format; no 1-D or shaper LUT other than log2; no table data ships.
+ * - Errors: ST_ERR_INVALID_ARGUMENT for a wrong struct_size, unknown flags or an unknown domain, any non-finite field, temperature or tint
+ *   outside [-1, 1], contrast outside (0, 4], saturation or cdl_saturation outside [0, 4], a slope outside [0, 16], an offset outside
+ *   [-1, 1], a power outside (0, 8], lut_strength outside [0, 1], in the LOG2 domain lut_ev_min >= lut_ev_max or lut_strength != 1, null
+ *   pointers where they are not allowed, image sides outside 1..16384, a LUT side outside 2..65 or a non-finite LUT value, an
+ *   auto-exposure display given to the process call. An unknown camera is ST_ERR_UNKNOWN_CAMERA. Set, get, plan, st_lut_insert and
+ *   st_lut_remove are host work and valid on a host-only engine; st_color_grading_process returns ST_ERR_NO_DEVICE there. */
+enum { ST_GRADE_DITHER = 1 };
+enum StLutDomain { ST_LUT_DOMAIN_UNIT = 0, ST_LUT_DOMAIN_LOG2 = 1 };
+enum { ST_GRADE_STEP_WHITE_BALANCE = 1, ST_GRADE_STEP_CONTRAST = 2, ST_GRADE_STEP_SATURATION = 4, ST_GRADE_STEP_CDL = 8, ST_GRADE_STEP_LUT = 16,
+       ST_GRADE_STEP_DITHER = 32 };
+typedef struct StColorGradingDesc {        /* 96 B */
+    uint32_t struct_size, flags;           /* sizeof(StColorGradingDesc), ST_GRADE_* */
+    float temperature, tint;               /* [-1, 1]; 0 = neutral (Bevy's ColorGrading / Unity's white balance, divided by 100) */
+    float contrast, saturation;            /* (0, 4] and [0, 4]; 1 = neutral; scene-referred */
+    float slope[3], offset[3], power[3];   /* ASC CDL, display-referred: [0, 16], [-1, 1], (0, 8]; 1, 0, 1 = neutral */
+    float cdl_saturation;                  /* [0, 4]; 1 = neutral */
+    StHandle lut;                          /* of st_lut_insert; 0 = none */
+    uint32_t lut_domain;                   /* StLutDomain */
+    float lut_ev_min, lut_ev_max;          /* LOG2: the table spans log2(v) in [lut_ev_min, lut_ev_max], finite, min < max */
+    float lut_strength;                    /* [0, 1]; LOG2: 1 */
+    uint32_t _pad[2];                      /* ignored */
+} StColorGradingDesc;
+typedef struct StColorGradingPlan {        /* 48 B */
+    uint32_t steps;                        /* ST_GRADE_STEP_*: the steps a frame with this descriptor runs (LUT: the handle is not 0) */
+    float white_balance[9];                /* M, row major; the identity when the step is not active */
+    float lut_inv_range;                   /* 1 / (lut_ev_max - lut_ev_min) in the LOG2 domain, else 0 */
+    uint32_t _pad;
+} StColorGradingPlan;
+int st_camera_set_color_grading(StEngine* e, StHandle camera, const StColorGradingDesc* desc);   /* NULL = off */
+/* the last desc set (a zeroed desc with struct_size when none was) and whether the node is on; either pointer may be NULL */
+int st_camera_get_color_grading(StEngine* e, StHandle camera, StColorGradingDesc* out, int* enabled);
+/* rgb: size^3 x 3 floats in host memory, red fastest, copied during the call; size in 2..65; every value finite */
+int st_lut_insert(StEngine* e, StHandle id, uint32_t size, const float* rgb);
+int st_lut_remove(StEngine* e, StHandle id);   /* an id that names no table is not an error */
+/* host only: the host constants of a descriptor */
+int st_color_grading_plan(const StColorGradingDesc* desc, StColorGradingPlan* out);
+/* Stateless, like st_bloom_process: the same launch over any RGBA32F device plane. lut_rgba_device: lut_size^3 float4 (rgb, anything) in
+ * device memory, red fastest, or NULL for no LUT step; the desc's handle is not consulted. display NULL = none, manual exposure only.
+ * Needs a device engine; no camera, no tick, no scratch memory. Enqueued on hip_stream without a host sync. src may not overlap dst. */
+int st_color_grading_process(StEngine* e, const StColorGradingDesc* desc, const StDisplayDesc* display, const void* lut_rgba_device,
+                             uint32_t lut_size, const void* src_rgba32f_device, uint32_t width, uint32_t height, void* dst_device,
+                             int dst_format /* StOutputFormat */, void* hip_stream);
+/* A .cube file's 3-D table, shaped like st_decode_hdr: out_rgb NULL reports lut_size only; else lut_size^3 x 3 floats, red fastest. Reads
+ * TITLE, # comments, blank lines, LUT_3D_SIZE N, DOMAIN_MIN 0 0 0 / DOMAIN_MAX 1 1 1, then exactly N^3 rows of three numbers; CR LF and
+ * tabs are fine. ST_ERR_UNSUPPORTED: LUT_1D_SIZE, any other domain, an unknown keyword. ST_ERR_PARSE: too few or too many rows, a
+ * non-number, a non-finite value, a size outside 2..65. Own code (st_cube.h); no engine needed. */
+int st_decode_cube(const void* bytes, size_t size, float* out_rgb, size_t capacity_floats, uint32_t* lut_size);
 
 /* ---- multi-GPU behind the boundary (NEW seam; SURVEY.md section 8e, BASELINE.json configs 4 and 5). One process per GPU, one
  * engine per process, the scene replicated; the frame is cut into tiles, every rank renders its tile (+ an apron of redundant

@@ -416,6 +416,54 @@ extern "C" {
     pub fn st_light_shafts_process(e: *mut StEngine, desc: *const StLightShaftsDesc, display: *const StDisplayDesc, transform: *const f32, projection: *const f32, color_device: *const c_void, depth_device: *const c_void, width: u32, height: u32, dst_device: *mut c_void, dst_format: i32, hip_stream: *mut c_void) -> i32;
 }
 
+// colour grading (include/strolle_hip.h "colour grading"): white balance, contrast, CDL, a 3-D LUT and dither around the display transform
+pub const ST_GRADE_DITHER: u32 = 1;
+pub const ST_LUT_DOMAIN_UNIT: u32 = 0;
+pub const ST_LUT_DOMAIN_LOG2: u32 = 1;
+pub const ST_GRADE_STEP_WHITE_BALANCE: u32 = 1;
+pub const ST_GRADE_STEP_CONTRAST: u32 = 2;
+pub const ST_GRADE_STEP_SATURATION: u32 = 4;
+pub const ST_GRADE_STEP_CDL: u32 = 8;
+pub const ST_GRADE_STEP_LUT: u32 = 16;
+pub const ST_GRADE_STEP_DITHER: u32 = 32;
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct StColorGradingDesc {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub temperature: f32,
+    pub tint: f32,
+    pub contrast: f32,
+    pub saturation: f32,
+    pub slope: [f32; 3],
+    pub offset: [f32; 3],
+    pub power: [f32; 3],
+    pub cdl_saturation: f32,
+    pub lut: u64,
+    pub lut_domain: u32,
+    pub lut_ev_min: f32,
+    pub lut_ev_max: f32,
+    pub lut_strength: f32,
+    pub _pad: [u32; 2],
+}
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct StColorGradingPlan {
+    pub steps: u32,
+    pub white_balance: [f32; 9],
+    pub lut_inv_range: f32,
+    pub _pad: u32,
+}
+extern "C" {
+    pub fn st_camera_set_color_grading(e: *mut StEngine, camera: u64, desc: *const StColorGradingDesc) -> i32; // null = off
+    pub fn st_camera_get_color_grading(e: *mut StEngine, camera: u64, out: *mut StColorGradingDesc, enabled: *mut i32) -> i32;
+    pub fn st_lut_insert(e: *mut StEngine, id: u64, size: u32, rgb: *const f32) -> i32;
+    pub fn st_lut_remove(e: *mut StEngine, id: u64) -> i32;
+    pub fn st_color_grading_plan(desc: *const StColorGradingDesc, out: *mut StColorGradingPlan) -> i32; // pure host
+    pub fn st_color_grading_process(e: *mut StEngine, desc: *const StColorGradingDesc, display: *const StDisplayDesc, lut_rgba_device: *const c_void, lut_size: u32, src_rgba32f_device: *const c_void, width: u32, height: u32, dst_device: *mut c_void, dst_format: i32, hip_stream: *mut c_void) -> i32;
+    pub fn st_decode_cube(bytes: *const c_void, size: usize, out_rgb: *mut f32, capacity_floats: usize, lut_size: *mut u32) -> i32;
+}
+
 // ---- the HIP runtime, as far as the staging-copy present needs it (libamdhip64)
 pub type hipStream_t = *mut c_void;
 extern "C" {

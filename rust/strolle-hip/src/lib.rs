@@ -285,6 +285,29 @@ where
         }
     }
 
+    /// Not part of the reference's API: colour grading on a camera (include/strolle_hip.h "colour grading"); `None` turns the node off.
+    /// `desc.lut` names a table by the id `insert_lut` was given (0: none); Bevy's `ColorGrading` / `DebandDither` map as INTEGRATION.md says.
+    pub fn set_color_grading(&mut self, handle: CameraHandle, desc: Option<ffi::StColorGradingDesc>) {
+        let raw = self.cameras.get(&handle).unwrap_or_else(|| panic!("camera does not exist: {:?}", handle)).raw;
+        match desc {
+            None => check(unsafe { ffi::st_camera_set_color_grading(self.raw, raw, std::ptr::null()) }),
+            Some(mut d) => {
+                d.struct_size = std::mem::size_of::<ffi::StColorGradingDesc>() as u32;
+                check(unsafe { ffi::st_camera_set_color_grading(self.raw, raw, &d) });
+            }
+        }
+    }
+
+    /// A 3-D look-up table of side `size` (2..65): `rgb` holds size^3 triples, red fastest, a .cube file's order. The next `tick` uploads it.
+    pub fn insert_lut(&mut self, id: u64, size: u32, rgb: &[f32]) {
+        assert_eq!(rgb.len(), (size as usize).pow(3) * 3, "a LUT of side {} holds side^3 rgb triples", size);
+        check(unsafe { ffi::st_lut_insert(self.raw, id, size, rgb.as_ptr()) });
+    }
+
+    pub fn remove_lut(&mut self, id: u64) {
+        check(unsafe { ffi::st_lut_remove(self.raw, id) });
+    }
+
     /// Renders camera to texture: records the pass that puts the frame `tick` rendered into `view` (present.rs).
     pub fn render_camera(&self, handle: CameraHandle, encoder: &mut wgpu::CommandEncoder, view: &wgpu::TextureView) {
         let slot = self.cameras.get(&handle).unwrap_or_else(|| panic!("camera does not exist: {:?}", handle));

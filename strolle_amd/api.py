@@ -263,6 +263,54 @@ def fog_desc(falloff=FogFalloff.EXPONENTIAL, color=(1.0, 1.0, 1.0, 1.0), start: 
                      f3(*[float(v) for v in light_direction]), 0.0)
 
 
+class StColorGradingDesc(C.Structure):
+    """include/strolle_hip.h "colour grading": 96 B"""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("temperature", C.c_float), ("tint", C.c_float), ("contrast", C.c_float),
+                ("saturation", C.c_float), ("slope", C.c_float * 3), ("offset", C.c_float * 3), ("power", C.c_float * 3), ("cdl_saturation", C.c_float),
+                ("lut", C.c_uint64), ("lut_domain", C.c_uint32), ("lut_ev_min", C.c_float), ("lut_ev_max", C.c_float), ("lut_strength", C.c_float),
+                ("_pad", C.c_uint32 * 2)]
+
+
+class StColorGradingPlan(C.Structure):
+    _fields_ = [("steps", C.c_uint32), ("white_balance", C.c_float * 9), ("lut_inv_range", C.c_float), ("_pad", C.c_uint32)]
+
+
+class LutDomain(enum.IntEnum):
+    """include/strolle_hip.h StLutDomain: what a table's axes span"""
+    UNIT = 0
+    LOG2 = 1
+
+
+GRADE_DITHER = 1
+GRADE_STEP_WHITE_BALANCE, GRADE_STEP_CONTRAST, GRADE_STEP_SATURATION, GRADE_STEP_CDL, GRADE_STEP_LUT, GRADE_STEP_DITHER = 1, 2, 4, 8, 16, 32
+
+
+def color_grading_desc(temperature: float = 0.0, tint: float = 0.0, contrast: float = 1.0, saturation: float = 1.0, slope=(1.0, 1.0, 1.0),
+                       offset=(0.0, 0.0, 0.0), power=(1.0, 1.0, 1.0), cdl_saturation: float = 1.0, lut: int = 0, lut_domain=LutDomain.UNIT,
+                       lut_ev_min: float = -12.0, lut_ev_max: float = 4.0, lut_strength: float = 1.0, dither: bool = False) -> StColorGradingDesc:
+    """A StColorGradingDesc (include/strolle_hip.h "colour grading"); the defaults are neutral. temperature, tint: [-1, 1]; contrast and
+    saturation grade the scene-referred colour; slope, offset, power, cdl_saturation: an ASC CDL on the display-referred one; lut: a handle
+    of Engine.insert_lut (0 = none) read over [0, 1] (UNIT) or over log2 in [lut_ev_min, lut_ev_max] (LOG2); dither: Bevy's DebandDither."""
+    f3 = C.c_float * 3
+    return StColorGradingDesc(C.sizeof(StColorGradingDesc), GRADE_DITHER if dither else 0, float(temperature), float(tint), float(contrast), float(saturation),
+                              f3(*[float(v) for v in slope]), f3(*[float(v) for v in offset]), f3(*[float(v) for v in power]), float(cdl_saturation), int(lut),
+                              int(lut_domain), float(lut_ev_min), float(lut_ev_max), float(lut_strength), (C.c_uint32 * 2)(0, 0))
+
+
+def color_grading_plan(desc: StColorGradingDesc):
+    """st_color_grading_plan: (the ST_GRADE_STEP_* bits a frame runs, the white-balance matrix as (3, 3) float32, the LOG2 domain's 1 / range)."""
+    import numpy as np
+    lib = load_library()
+    lib.st_color_grading_plan.restype = C.c_int
+    lib.st_color_grading_plan.argtypes = [C.POINTER(StColorGradingDesc), C.POINTER(StColorGradingPlan)]
+    plan = StColorGradingPlan()
+    rc = lib.st_color_grading_plan(C.byref(desc), C.byref(plan))
+    if rc != 0:
+        lib.st_last_error.restype = C.c_char_p
+        raise StrolleError(f"{_STATUS.get(rc, 'error')} (status {rc}): {lib.st_last_error().decode(errors='replace')}")
+    return int(plan.steps), np.array(plan.white_balance, np.float32).reshape(3, 3).copy(), np.float32(plan.lut_inv_range)
+
+
 class StLightShaftsDesc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("steps", C.c_uint32), ("divisor", C.c_uint32),
                 ("density", C.c_float), ("anisotropy", C.c_float), ("max_distance", C.c_float), ("intensity", C.c_float),
@@ -655,6 +703,12 @@ class _Binding:
             self.camera_set_fog = fn("camera_set_fog", [vp, u64, P(StFogDesc)])
             self.camera_get_fog = fn("camera_get_fog", [vp, u64, P(StFogDesc), P(i32)])
             self.fog_process = fn("fog_process", [vp, P(StFogDesc), P(StDisplayDesc), P(C.c_float), P(C.c_float), vp, vp, u32, u32, vp, i32, vp])
+        if hasattr(lib, prefix + "camera_set_color_grading"):   # colour grading (likewise)
+            self.camera_set_color_grading = fn("camera_set_color_grading", [vp, u64, P(StColorGradingDesc)])
+            self.camera_get_color_grading = fn("camera_get_color_grading", [vp, u64, P(StColorGradingDesc), P(i32)])
+            self.color_grading_plan = fn("color_grading_plan", [P(StColorGradingDesc), P(StColorGradingPlan)])
+            self.color_grading_process = fn("color_grading_process", [vp, P(StColorGradingDesc), P(StDisplayDesc), vp, u32, vp, u32, u32, vp, i32, vp])
+            self.lut_insert = fn("lut_insert", [vp, u64, u32, P(C.c_float)]); self.lut_remove = fn("lut_remove", [vp, u64])
         if hasattr(lib, prefix + "camera_set_light_shafts"):   # light shafts (likewise)
             self.camera_set_light_shafts = fn("camera_set_light_shafts", [vp, u64, P(StLightShaftsDesc)])
             self.camera_get_light_shafts = fn("camera_get_light_shafts", [vp, u64, P(StLightShaftsDesc), P(i32)])
@@ -1239,6 +1293,36 @@ class Engine(EngineBase):
         self._check(self._b.fog_process(self._h, C.byref(desc), C.byref(display) if display is not None else None, xf, proj, color_ptr, depth_ptr, width, height,
                                         dst_ptr, int(dst_format), stream))
 
+    # ---- colour grading (include/strolle_hip.h "colour grading"): takes effect at the camera's next render; tables at the next tick
+    def set_color_grading(self, camera: int, desc: Optional[StColorGradingDesc] = None, **kw):
+        """st_camera_set_color_grading: a StColorGradingDesc, or color_grading_desc(**kw) when keywords are given; neither = off."""
+        self._set_stage(self._b.camera_set_color_grading, color_grading_desc, camera, desc, kw)
+
+    def get_color_grading(self, camera: int):
+        """st_camera_get_color_grading: (the last StColorGradingDesc set, whether the node is on)."""
+        return self._get_stage(self._b.camera_get_color_grading, StColorGradingDesc, camera)
+
+    def insert_lut(self, handle: int, rgb):
+        """st_lut_insert: an (N, N, N, 3) float32 table indexed [b, g, r] (red fastest, a .cube file's order; load_cube returns it so)."""
+        t = np.ascontiguousarray(rgb, np.float32)
+        if t.ndim != 4 or t.shape[3] != 3 or not (t.shape[0] == t.shape[1] == t.shape[2]):
+            raise StrolleError("LUT: expected an (N, N, N, 3) array")
+        self._check(self._b.lut_insert(self._h, handle, t.shape[0], t.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def remove_lut(self, handle: int):
+        self._check(self._b.lut_remove(self._h, handle))
+
+    def color_grading_plan(self, desc: StColorGradingDesc):
+        """st_color_grading_plan (the module's color_grading_plan)."""
+        return color_grading_plan(desc)
+
+    def color_grading_process(self, desc: StColorGradingDesc, src_ptr: int, width: int, height: int, dst_ptr: int, dst_format: int = 0,
+                              display: Optional[StDisplayDesc] = None, lut_ptr: int = 0, lut_size: int = 0, stream: int = 0):
+        """st_color_grading_process: the node's launch over any RGBA32F device plane, with the (manual) display transform between its two
+        halves, into dst (width x height) in dst_format. lut_ptr: lut_size^3 float4 in device memory, or 0 for no LUT step."""
+        self._check(self._b.color_grading_process(self._h, C.byref(desc), C.byref(display) if display is not None else None, lut_ptr or None, lut_size, src_ptr, width,
+                                                  height, dst_ptr, int(dst_format), stream))
+
     # ---- light shafts (include/strolle_hip.h "light shafts"): takes effect at the camera's next render
     def set_light_shafts(self, camera: int, desc: Optional[StLightShaftsDesc] = None, **kw):
         """st_camera_set_light_shafts: a StLightShaftsDesc, or light_shafts_desc(**kw) when keywords are given; neither = off."""
@@ -1536,6 +1620,30 @@ def decode_hdr(data: bytes) -> np.ndarray:
         lib.st_last_error.restype = C.c_char_p
         raise StrolleError(f"{_STATUS.get(status, 'error')} (status {status}): {lib.st_last_error().decode(errors='replace')}")
     return out
+
+
+def decode_cube(data: bytes) -> np.ndarray:
+    """st_decode_cube: the text of a .cube file -> (N, N, N, 3) float32 indexed [b, g, r], ready for Engine.insert_lut."""
+    lib = load_library()
+    fn = lib.st_decode_cube
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+    n = C.c_uint32()
+    data = bytes(data)
+    status = fn(data, len(data), None, 0, C.byref(n))
+    if status == 0:
+        out = np.empty((n.value, n.value, n.value, 3), np.float32)
+        status = fn(data, len(data), out.ctypes.data, out.size, C.byref(n))
+    if status != 0:
+        lib.st_last_error.restype = C.c_char_p
+        raise StrolleError(f"{_STATUS.get(status, 'error')} (status {status}): {lib.st_last_error().decode(errors='replace')}")
+    return out
+
+
+def load_cube(path) -> np.ndarray:
+    """A .cube file -> (N, N, N, 3) float32 (st_decode_cube)."""
+    with open(path, "rb") as f:
+        return decode_cube(f.read())
 
 
 def load_hdr(path) -> np.ndarray:

@@ -282,9 +282,9 @@ int st_camera_set_window(StEngine* e, StHandle h, uint32_t x0, uint32_t y0, uint
     ST_REQUIRE(x0 % 16u == 0u && (x1 % 16u == 0u || x1 == s.desc.width), "window columns must be multiples of 16 (or the frame's right edge)");
     const bool full = x0 == 0u && y0 == 0u && x1 == s.desc.width && y1 == s.desc.height;
     ST_REQUIRE(full || !s.display_auto(), "a window on a camera with auto-exposure would meter the tile alone (include/strolle_hip.h \"display transforms\")");
-    // each stage's own rule (st_output_chain.h), as its setter states it; fog carries none
+    // each stage's own rule (st_output_chain.h), as its setter states it; fog and colour grading carry none
     const std::initializer_list<std::pair<bool, const WindowRule*>> stages = {{s.post.on, s.post.window}, {s.bloom.on, s.bloom.window}, {s.mblur.on, s.mblur.window},
-                                                                              {s.dof.on, s.dof.window}, {s.fog.on, s.fog.window}, {s.shafts.on, s.shafts.window}};
+                                                                              {s.dof.on, s.dof.window}, {s.fog.on, s.fog.window}, {s.shafts.on, s.shafts.window}, {s.grade.on, s.grade.window}};
     for (const auto& st : stages) if (!full && st.first && st.second) return fail(ST_ERR_INVALID_ARGUMENT, window_refused_by(*st.second));
     s.row0 = y0; s.row1 = y1; s.col0 = x0; s.col1 = x1;
     return ST_OK;
@@ -423,6 +423,38 @@ int st_fog_process(StEngine* e, const StFogDesc* desc, const StDisplayDesc* disp
                    uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
     ST_REQUIRE(e, "null engine");
     return E(e)->fog_process(desc, display, transform, projection, color, depth, width, height, dst, dst_format, static_cast<hipStream_t>(stream));
+}
+
+// ---- colour grading (st_grade.cpp)
+int st_camera_set_color_grading(StEngine* e, StHandle h, const StColorGradingDesc* desc) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    return E(e)->set_grade(*it->second, desc);
+}
+int st_camera_get_color_grading(StEngine* e, StHandle h, StColorGradingDesc* out, int* enabled) { return camera_get(e, h, &CameraState::grade, out, enabled); }
+int st_color_grading_plan(const StColorGradingDesc* desc, StColorGradingPlan* out) {
+    ST_REQUIRE(desc, "null desc");
+    Engine::GradePlan plan;
+    if (int rc = Engine::grade_plan(*desc, plan)) return rc;
+    if (out) {
+        out->steps = plan.steps; out->lut_inv_range = plan.inv_range; out->_pad = 0u;
+        for (int i = 0; i < 9; i++) out->white_balance[i] = plan.M[i];
+    }
+    return ST_OK;
+}
+int st_color_grading_process(StEngine* e, const StColorGradingDesc* desc, const StDisplayDesc* display, const void* lut, uint32_t lut_size, const void* src, uint32_t width,
+                             uint32_t height, void* dst, int dst_format, void* stream) {
+    ST_REQUIRE(e, "null engine");
+    return E(e)->grade_process(desc, display, lut, lut_size, src, width, height, dst, dst_format, static_cast<hipStream_t>(stream));
+}
+int st_lut_insert(StEngine* e, StHandle id, uint32_t size, const float* rgb) {
+    ST_REQUIRE(e, "null engine");
+    return E(e)->lut_insert(id, size, rgb);
+}
+int st_lut_remove(StEngine* e, StHandle id) {
+    ST_REQUIRE(e, "null engine");
+    return E(e)->lut_remove(id);
 }
 
 // ---- light shafts (st_shafts.cpp)

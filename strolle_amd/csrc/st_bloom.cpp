@@ -86,7 +86,11 @@ Engine::BloomSteps Engine::bloom_steps(const StBloomDesc& d, const BloomPlan& pl
     base.threshold_on = d.threshold > 0.0f ? 1u : 0u;
     const float knee = d.threshold * d.threshold_softness;
     base.threshold = d.threshold; base.knee_lo = d.threshold - knee; base.knee2 = 2.0f * knee; base.knee_div = 4.0f * knee + 1e-4f;
+    // a raw target (colour grading behind bloom reads the plane): the colour untransformed, which is this composite's store at NONE and scale 1 —
+    // st_bloom_process without a display — into RGBA32F; the grade applies the display transform
+    const uint32_t format = target.raw ? (uint32_t)ST_FORMAT_RGBA32F : target.format;
     base.display = target.display;
+    if (target.raw) { base.display = DisplayArgs{}; base.display.scale = 1.0f; }
     const uint32_t L = plan.levels, T = bloom_tail_first(plan, tail_lds_bytes);
     for (uint32_t k = 0; k < T; k++) {
         BloomArgs a = base;
@@ -116,9 +120,9 @@ Engine::BloomSteps Engine::bloom_steps(const StBloomDesc& d, const BloomPlan& pl
     }
     BloomArgs a = base;
     a.src = L ? pyramid + plan.offset[0] : nullptr; a.sw = L ? plan.w[0] : 0u; a.sh = L ? plan.h[0] : 0u;
-    a.base = static_cast<const float4*>(src); a.dst = target.dst; a.dw = w; a.dh = h; a.format = target.format;
+    a.base = static_cast<const float4*>(src); a.dst = target.dst; a.dw = w; a.dh = h; a.format = format;
     a.factor = L ? plan.factor[0] : 0.0f;
-    s.step[s.count++] = {{KS_BLOOM_COMPOSITE, (double)a.sw * a.sh * 16.0 + (double)w * h * (16.0 + format_bytes(target.format))}, false, a, BloomTailArgs{}};
+    s.step[s.count++] = {{KS_BLOOM_COMPOSITE, (double)a.sw * a.sh * 16.0 + (double)w * h * (16.0 + format_bytes(format))}, false, a, BloomTailArgs{}};
     return s;
 }
 

@@ -400,6 +400,7 @@ struct CameraState {
     NodeSetting<StDofDesc, 4> dof{&kDofWindow};              // st_dof.cpp. [0] the HDR plane, [1] (coc, Z) per pixel, [2] the tiles' near-field maxima, [3] their 3 x 3 neighbour maxima
     NodeSetting<StMotionBlurDesc, 4> mblur{&kMBlurWindow};   // st_motion_blur.cpp. [0] the HDR plane, [1] (r, Z) per pixel, [2] the tile vectors, [3] their 3 x 3 neighbour maxima
     NodeSetting<StBloomDesc, 2> bloom{&kBloomWindow};        // st_bloom.cpp. [0] the HDR plane, [1] the pyramid (one allocation of float4 mips)
+    NodeSetting<StColorGradingDesc, 1> grade{nullptr};       // st_grade.cpp. [0] the HDR plane. Pointwise: a window does not exclude it
     // Which frames run a node that is on. Heatmap frames are false colour; heatmap and reference frames run no primary-visibility pass, so they
     // have no G-buffer and no velocity map; the nodes that derive a pixel's ray or the focal length need a perspective projection.
     bool has_gbuffer() const { return desc.mode != ST_MODE_BVH_HEATMAP && desc.mode != ST_MODE_REFERENCE; }
@@ -571,6 +572,14 @@ struct Engine {
     std::unique_ptr<EnvMap> env_live; std::vector<std::unique_ptr<EnvMap>> env_retired;
     DeviceArray d_env_grid, d_env_bad /* one u32: the texels the device upload sanitized */; uint64_t env_sanitized = 0;
     std::vector<float> env_grid_host; std::vector<EnvCell> env_table_host;
+
+    // colour grading's look-up tables (include/strolle_hip.h "colour grading"; st_grade.cpp). st_lut_insert / st_lut_remove leave an edit
+    // per id for the next tick (a host-only engine drops them there). Every table the device holds is a fresh allocation of size^3 float4:
+    // frames enqueued before a replacement or removal keep reading theirs, which is released once its fence says they are done (luts_retired).
+    struct Lut { DeviceArray texels; uint32_t size = 0; Fence fence; };
+    struct LutEdit { uint32_t size = 0; std::vector<float4> texels; };   // size 0: remove
+    std::map<StHandle, LutEdit> lut_edits;
+    std::map<StHandle, std::unique_ptr<Lut>> luts_live; std::vector<std::unique_ptr<Lut>> luts_retired;
 
     DeviceArray d_byte_luts, d_atlas, d_blue_noise, d_transmittance, d_scattering, d_sky;
     // The arrays a scene change rewrites exist twice. A tick that changes the scene fills the copy no frame in flight reads,
@@ -778,7 +787,7 @@ struct Engine {
     struct BloomStep { OutputStep step; bool first; BloomArgs args; BloomTailArgs tail; };
     struct BloomSteps { BloomStep step[16]; uint32_t count = 0; };
     static int bloom_plan(const StBloomDesc& d, uint32_t w, uint32_t h, BloomPlan& plan);   // checks the desc; levels == 0: the frame holds no level
-    // the frame's launches in order: `src` (w x h RGBA32F) -> the pyramid -> the target (never raw: bloom is the last node)
+    // the frame's launches in order: `src` (w x h RGBA32F) -> the pyramid -> the target (raw when colour grading follows: untransformed RGBA32F)
     static BloomSteps bloom_steps(const StBloomDesc& d, const BloomPlan& plan, const void* src, uint32_t w, uint32_t h, float4* pyramid, const NodeTarget& target, uint32_t tail_lds_bytes);
     int set_bloom(CameraState& c, const StBloomDesc* desc);
     void launch_bloom_step(const BloomStep& s, hipStream_t stream);   // one of bloom_steps' launches
@@ -814,6 +823,20 @@ struct Engine {
     int set_fog(CameraState& c, const StFogDesc* desc);
     int fog_process(const StFogDesc* desc, const StDisplayDesc* display, const float* transform, const float* projection, const void* color, const void* depth,
                     uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
+    // ---- colour grading (st_grade.cpp)
+    struct GradePlan { uint32_t steps = 0; float M[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f}; float inv_range = 0.0f; };
+    struct GradeStep { GradeArgs args; OutputStep step; };
+    static int grade_plan(const StColorGradingDesc& d, GradePlan& out);   // checks the desc
+    // `lut`: size^3 float4 or null (the step is then skipped, whatever the plan says)
+    static void grade_step(const StColorGradingDesc& d, const GradePlan& plan, const float4* lut, uint32_t lut_size, const NodeSource& src, uint32_t row0, uint32_t row1,
+                           uint32_t col0, uint32_t col1, const NodeTarget& target, GradeStep& out);
+    int set_grade(CameraState& c, const StColorGradingDesc* desc);
+    int grade_process(const StColorGradingDesc* desc, const StDisplayDesc* display, const void* lut, uint32_t lut_size, const void* src, uint32_t w, uint32_t h, void* dst,
+                      int format, hipStream_t stream);
+    int lut_insert(StHandle id, uint32_t size, const float* rgb);
+    int lut_remove(StHandle id);
+    int upload_luts(TickIo& io);   // the tick's: edits -> fresh device tables; retired ones are released behind their readers
+    Lut* live_lut(StHandle id) const { auto it = luts_live.find(id); return it == luts_live.end() ? nullptr : it->second.get(); }
     // ---- light shafts (st_shafts.cpp)
     struct ShaftsPlan { uint32_t cells_w = 0, cells_h = 0; size_t cell_bytes = 0; float jitter[16] = {}; };
     struct ShaftsSteps { ShaftsArgs args; OutputStep step[2]; };   // march, apply

@@ -45,6 +45,7 @@ enum KernelSlot {
     KS_DOF_PACK, KS_DOF_NEIGHBOUR, KS_DOF_GATHER,  // depth of field in front of motion blur (k_dof.hip); render() credits their bytes itself
     KS_FOG,  // fog in front of depth of field (k_fog.hip); render() credits its bytes itself
     KS_SHAFTS_MARCH, KS_SHAFTS_APPLY,  // light shafts between fog and depth of field (k_shafts.hip); render() credits their bytes itself
+    KS_GRADE,  // colour grading behind bloom (k_grade.hip); render() credits its bytes itself
     KS_COUNT
 };
 struct KernelInfo { const char* name; float bytes_per_unit; bool half; };
@@ -80,6 +81,7 @@ inline const KernelInfo& kernel_info(int slot) {
         {"dof_pack", 0.f, false},            {"dof_neighbour", 0.f, false},        {"dof_gather", 0.f, false},
         {"fog", 0.f, false},
         {"shafts_march", 0.f, false},        {"shafts_apply", 0.f, false},
+        {"color_grading", 0.f, false},
     };
     return k[slot];
 }

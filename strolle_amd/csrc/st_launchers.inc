@@ -107,3 +107,5 @@ ST_LAUNCHER(launch_fog, (const FogArgs& p, hipStream_t s))
 // light shafts (k_shafts.hip; st_shafts.cpp): the march over the cell grid (a tracing launch: KArgs::width x height is the cell grid), then one pointwise launch
 ST_LAUNCHER(launch_shafts_march, (const KArgs& a, const ShaftsArgs& p, hipStream_t s))
 ST_LAUNCHER(launch_shafts_apply, (const ShaftsArgs& p, hipStream_t s))
+// colour grading (k_grade.hip; st_grade.cpp): one pointwise launch over the window, one workgroup per 32 x 8 pixels; the last HDR node
+ST_LAUNCHER(launch_grade, (const GradeArgs& p, hipStream_t s))

@@ -171,7 +171,7 @@ namespace {
 // reads_depth: its launches in finish_output read the G-buffer depth of the frame's parity, which the frame after next rewrites: the camera's
 //        gbuffer_depth_read fence is recorded once, behind the last such node that is on, and prim() of that parity waits for it.
 // reads_velocity: the lean frame keeps the velocity map for it (kLeanKeepVelocity).
-enum HdrNode { kNodeFog, kNodeShafts, kNodeDof, kNodeMBlur, kNodeBloom, kHdrNodes };   // chain order
+enum HdrNode { kNodeFog, kNodeShafts, kNodeDof, kNodeMBlur, kNodeBloom, kNodeGrade, kHdrNodes };   // chain order
 struct HdrNodeRow { uint32_t early; bool reads_depth, reads_velocity; };
 constexpr HdrNodeRow kHdrNode[kHdrNodes] = {
     /* fog (st_fog.cpp): one launch; pointwise, so windows are honoured */       {0u, true, false},
@@ -179,10 +179,12 @@ constexpr HdrNodeRow kHdrNode[kHdrNodes] = {
     /* depth of field (st_dof.cpp): pack | neighbour maximum, gather */           {1u, false, false},
     /* motion blur (st_motion_blur.cpp): pack | neighbour maximum, gather */      {1u, false, true},
     /* bloom (st_bloom.cpp): the pyramid's chain, the composite */                {0u, false, false},
+    /* colour grading (st_grade.cpp): one launch; pointwise, windows honoured */  {0u, false, false},
 };
 struct HdrWork {   // what the nodes that are on hold for one frame: node_plan's plans, node_arm's argument blocks and steps
-    Engine::ShaftsPlan shafts_plan; Engine::DofPlan dof_plan; Engine::MBlurPlan mblur_plan; Engine::BloomPlan bloom_plan;
-    Engine::FogStep fog; Engine::ShaftsSteps shafts; Engine::DofSteps dof; Engine::MBlurSteps mblur; Engine::BloomSteps bloom;
+    Engine::ShaftsPlan shafts_plan; Engine::DofPlan dof_plan; Engine::MBlurPlan mblur_plan; Engine::BloomPlan bloom_plan; Engine::GradePlan grade_plan;
+    Engine::Lut* grade_lut = nullptr;   // the live table the descriptor names, if any: its fence is recorded behind the launch
+    Engine::GradeStep grade; Engine::FogStep fog; Engine::ShaftsSteps shafts; Engine::DofSteps dof; Engine::MBlurSteps mblur; Engine::BloomSteps bloom;
 };
 // ---- end of the node table
 // The frame's output chain, decided once. Output post-processing (st_post.cpp): while the frame needs it, the frame's target is the camera's
@@ -256,6 +258,7 @@ struct Frame {
         case kNodeShafts: return c.shafts.on && perspective;
         case kNodeDof: return c.dof.on && perspective;
         case kNodeMBlur: return c.mblur.on && c.has_gbuffer();
+        case kNodeGrade: return c.grade.on && c.desc.mode != ST_MODE_BVH_HEATMAP;   // (needs neither a G-buffer nor a projection)
         default: return c.bloom.on && c.desc.mode != ST_MODE_BVH_HEATMAP;
         }
     }
@@ -280,6 +283,10 @@ struct Frame {
         case kNodeMBlur:
             if (int rc = Engine::mblur_plan(c.mblur.desc, w, h, work.mblur_plan)) return rc;
             return node_planes(n, c.mblur.planes, {plane, work.mblur_plan.packed_bytes, work.mblur_plan.tile_bytes, work.mblur_plan.tile_bytes});
+        case kNodeGrade:
+            if (int rc = Engine::grade_plan(c.grade.desc, work.grade_plan)) return rc;
+            work.grade_lut = e.live_lut(c.grade.desc.lut);
+            return node_planes(n, c.grade.planes, {plane});
         default:
             if (int rc = Engine::bloom_plan(c.bloom.desc, w, h, work.bloom_plan)) return rc;
             if (work.bloom_plan.levels == 0u) return ST_OK;   // the frame holds no level: off
@@ -295,14 +302,19 @@ struct Frame {
         case kNodeFog: Engine::fog_step(c.fog.desc, view, src, c.row0, c.row1, c.col0, c.col1, t, work.fog); break;
         case kNodeShafts: e.shafts_steps(c.shafts.desc, work.shafts_plan, view, src, c.shafts.planes.plane[1].as<float4>(), t, true, work.shafts); break;
         case kNodeDof: { const auto& p = c.dof.planes.plane; Engine::dof_steps(c.dof.desc, work.dof_plan, c.desc.projection, src, p[1].as<float2>(), p[2].as<float>(), p[3].as<float>(), t, work.dof); break; }
+        case kNodeGrade:
+            Engine::grade_step(c.grade.desc, work.grade_plan, work.grade_lut ? work.grade_lut->texels.as<float4>() : nullptr, work.grade_lut ? work.grade_lut->size : 0u, src,
+                               c.row0, c.row1, c.col0, c.col1, t, work.grade);
+            break;
         case kNodeMBlur: { const auto& p = c.mblur.planes.plane; Engine::mblur_steps(c.mblur.desc, work.mblur_plan, src, p[1].as<float2>(), p[2].as<float4>(), p[3].as<float4>(), t, work.mblur); break; }
         default: work.bloom = Engine::bloom_steps(c.bloom.desc, work.bloom_plan, src.color, src.w, src.h, c.bloom.planes.plane[1].as<float4>(), t, e.bloom_tail_bytes()); break;
         }
     }
-    uint32_t node_steps(int n) const { return n == kNodeFog ? 1u : n == kNodeShafts ? 2u : n == kNodeBloom ? work.bloom.count : 3u; }
+    uint32_t node_steps(int n) const { return (n == kNodeFog || n == kNodeGrade) ? 1u : n == kNodeShafts ? 2u : n == kNodeBloom ? work.bloom.count : 3u; }
     const OutputStep& node_step(int n, uint32_t i) const {
         switch (n) {
         case kNodeFog: return work.fog.step;
+        case kNodeGrade: return work.grade.step;
         case kNodeShafts: return work.shafts.step[i];
         case kNodeDof: return work.dof.step[i];
         case kNodeMBlur: return work.mblur.step[i];
@@ -312,6 +324,7 @@ struct Frame {
     void node_launch(int n, uint32_t i) {
         switch (n) {
         case kNodeFog: e.L.launch_fog(work.fog.args, cur); break;
+        case kNodeGrade: e.L.launch_grade(work.grade.args, cur); break;
         case kNodeShafts: e.launch_shafts_step(a, work.shafts, i, cur); break;   // the march reads the live scene copy and the light table too
         case kNodeDof: e.launch_dof_step(work.dof, i, cur); break;
         case kNodeMBlur: e.launch_mblur_step(work.mblur, i, cur); break;
@@ -659,6 +672,7 @@ struct Frame {
             if (!route.on(n)) continue;
             run_node(n, kHdrNode[n].early, node_steps(n));
             if (int rc = route.planes_read[n]->record(stream)) return rc;   // the planes' fence, behind the node's last launch
+            if (n == kNodeGrade && work.grade_lut) if (int rc = work.grade_lut->fence.record(stream)) return rc;   // the table leaves behind its last reader (st_grade.cpp upload_luts)
             if (n == last_depth_reader) if (int rc = c.gbuffer_depth_read[c.frame % 2u].record(stream)) return rc;
         }
         if (route.post) {   // at most two kernels

@@ -155,6 +155,7 @@ int Engine::tick(hipStream_t stream) {
     }
     const TreePlan plan = refresh_scene();
     apply_environment();   // (before the lights: a map switches the sun, light 0, off)
+    if (!has_device) lut_edits.clear();   // (a host-only engine holds no table)
     refresh_sun_and_lights();
     if (has_device) {
         ST_HIP(hipSetDevice(device));
@@ -166,7 +167,7 @@ int Engine::tick(hipStream_t stream) {
         if (!skinning) staging.begin_tick();
         TickIo io{stream};
         int rc;
-        if ((rc = upload_scene(plan, io)) || (rc = upload_images(io)) || (rc = upload_lights(io)) || (rc = upload_environment(io)) || (rc = end_uploads(io))) return rc;
+        if ((rc = upload_scene(plan, io)) || (rc = upload_images(io)) || (rc = upload_lights(io)) || (rc = upload_environment(io)) || (rc = upload_luts(io)) || (rc = end_uploads(io))) return rc;
     }
     atlas_dirty = false;
     for (auto& kv : cameras) kv.second->frame = frame;  // CameraController::flush

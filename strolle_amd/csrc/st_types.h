@@ -172,6 +172,21 @@ struct ShaftsArgs {
     DisplayArgs display;
 };
 
+// Colour grading (include/strolle_hip.h "colour grading"; st_grade.cpp, k_grade.hip): the arguments of its one launch. It reads `color`
+// over the window [row0, row1) x [col0, col1) at absolute coordinates in the width x height frame and stores `dst` in `format` behind the
+// display transform (it is the last node: `raw` is never set by a frame). `steps`: ST_GRADE_STEP_* of the steps that run; cdl_pow: bit k
+// set when channel k's power is not 1. lut: lut_n^3 float4, red fastest (lut_n == 0: no table). M: white balance, row major; inv_range:
+// the LOG2 domain's 1 / (ev_max - ev_min). All wave-uniform.
+constexpr uint32_t kGradeWhiteBalance = 1u, kGradeContrast = 2u, kGradeSaturation = 4u, kGradeCdl = 8u, kGradeLut = 16u, kGradeDither = 32u;   // ST_GRADE_STEP_*
+constexpr uint32_t kGradeStageA = kGradeWhiteBalance | kGradeContrast | kGradeSaturation;
+struct GradeArgs {
+    const float4* color; const float4* lut; void* dst;
+    uint32_t width, height, row0, row1, col0, col1, format, raw;
+    uint32_t steps, cdl_pow, cdl_sat_on, lut_n, lut_log2, lut_blend;
+    float M[9], contrast, saturation, slope[3], offset[3], power[3], cdl_saturation, ev_min, inv_range, lut_strength;
+    DisplayArgs display;
+};
+
 // Everything a per-pixel kernel can touch, passed by value as the kernel argument (scalar loads).
 struct KArgs {
     GpuCamera cam, prev_cam;
