@@ -693,54 +693,17 @@ int st_debug_read_scene(StEngine* e, int what, void* out, size_t capacity, size_
     ST_REQUIRE(e, "null engine");
     Engine* en = E(e);
     const void* p; size_t bytes;
-    if ((what == 0 || what == 1 || what == 4 || (what >= 7 && what <= 15)) && en->any_host_stale()) en->bake_stale_on_host();   // instances the device moved: the host arrays catch up
-    if (int rc = en->take_deferred_status()) return rc;   // (their posed triangles could not be read back)
-    if (en->host_tree_stale && (what == 0 || what == 4 || (what >= 7 && what <= 15))) en->rebuild_host_tree(false);   // ST_BVH_BUILD_DEVICE left the host's tree behind
-    if ((what == 0 || what == 4) && en->host_stream_stale) { en->refit_stream(); en->host_stream_stale = false; }  // device refits since the host copy was current
-    switch (what) {
-        case 0: p = en->bvh_stream.data(); bytes = en->bvh_stream.size() * sizeof(float4); break;
-        case 1: p = en->triangles.data(); bytes = en->triangles.size() * sizeof(HostTriangle); break;
-        case 2: p = en->gpu_lights.data(); bytes = en->gpu_lights.size() * sizeof(GpuLight); break;
-        case 3: p = en->gpu_materials.data(); bytes = en->gpu_materials.size() * sizeof(GpuMaterial); break;
-        case 4: en->expand_stream(); p = en->bvh_upload_.data(); bytes = (size_t)en->device_bvh_len * sizeof(float4); break;  // as st_tick would upload it now
-        case 6: {  // the device stream as it is on the device right now (the live copy): what a device refit left there
-            if (!en->has_device || !en->scene_uploaded) return fail(ST_ERR_NO_DEVICE, "no device copy of the scene");
-            const size_t n = en->sets[en->live].bvh.capacity ? (size_t)en->live_bvh_texels : 0;
-            en->readback_.resize(n);
-            ST_HIP(hipSetDevice(en->device)); ST_HIP(hipDeviceSynchronize());
-            if (n) ST_HIP(hipMemcpy(en->readback_.data(), en->sets[en->live].bvh.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
-            p = en->readback_.data(); bytes = n * sizeof(float4); break;
+    if (SceneTree::debug_reads(what)) {   // the tree's buffers (0, 4, 6 - 17): it brings them up to date itself
+        if (int rc = en->tree.debug_read(what, &p, &bytes)) return rc;
+    } else {
+        if (what == 1 && en->any_host_stale()) en->bake_stale_on_host();   // instances the device moved: the host arrays catch up
+        if (int rc = en->take_deferred_status()) return rc;   // (their posed triangles could not be read back)
+        switch (what) {
+            case 1: p = en->triangles.data(); bytes = en->triangles.size() * sizeof(HostTriangle); break;
+            case 2: p = en->gpu_lights.data(); bytes = en->gpu_lights.size() * sizeof(GpuLight); break;
+            case 3: p = en->gpu_materials.data(); bytes = en->gpu_materials.size() * sizeof(GpuMaterial); break;
+            default: return fail(ST_ERR_INVALID_ARGUMENT, "unknown scene buffer");
         }
-        case 7: case 8: case 9: case 10: case 11: case 12: case 13: {  // the device refit's inputs (k_bvh.hip), built here for a host-side emulation
-            if (en->host_stream_stale) { en->refit_stream(); en->host_stream_stale = false; }
-            en->expand_stream(); en->index_device_tree();
-            en->readback_levels_.clear();
-            for (const auto& l : en->refit_levels_) { en->readback_levels_.push_back(l.first); en->readback_levels_.push_back(l.second); }
-            const std::vector<uint32_t>* v = what == 7 ? &en->parent_ : what == 8 ? &en->refit_local_ : what == 9 ? &en->refit_items_ : what == 10 ? &en->refit_batch_off_
-                                           : what == 11 ? &en->readback_levels_ : &en->entry_of_tri_;
-            if (what == 13) { p = en->tri_bounds.data(); bytes = en->tri_bounds.size() * sizeof(float4); }
-            else { p = v->data(); bytes = v->size() * sizeof(uint32_t); }
-            break;
-        }
-        case 14: case 15: {  // the wide stream's topology (k_bvh.hip k_bvh_wide), built here: 14 = 8 words per node (4 box sources, 4 links), preceded by
-                             // one word holding the root's link; 15 = the contract entry of every leaf record
-            if (en->host_stream_stale) { en->refit_stream(); en->host_stream_stale = false; }
-            en->expand_stream(); en->build_wide_topology(); en->wide_built_for_ = ~0ull;   // (a later tick builds its own)
-            en->readback_levels_.assign(1, en->wide_root_ | (en->wide_stack_need_ << 8));   // (bits 8..: the most entries a wide walk can have pending)
-            en->readback_levels_.insert(en->readback_levels_.end(), en->wide_topo_.begin(), en->wide_topo_.end());
-            const std::vector<uint32_t>* v = what == 14 ? &en->readback_levels_ : &en->wide_leaf_entry_;
-            p = v->data(); bytes = v->size() * sizeof(uint32_t); break;
-        }
-        case 16: case 17: {  // the wide stream as it is on the device right now (the live copy): 16 = nodes (64 B each), 17 = leaf records (48 B each)
-            if (!en->has_device || !en->scene_uploaded) return fail(ST_ERR_NO_DEVICE, "no device copy of the scene");
-            const auto& t = en->sets[en->live];
-            const size_t n = (t.wide_for_entries || t.device_built) ? (what == 16 ? (size_t)t.wide_nodes * 4u : (size_t)t.wide_leaves * 3u) : 0;
-            en->readback_.resize(n);
-            ST_HIP(hipSetDevice(en->device)); ST_HIP(hipDeviceSynchronize());
-            if (n) ST_HIP(hipMemcpy(en->readback_.data(), what == 16 ? t.bvh_wide.ptr : static_cast<const void*>(static_cast<const float4*>(t.bvh_wide.ptr) + 4u * (size_t)t.wide_nodes), n * sizeof(float4), hipMemcpyDeviceToHost));
-            p = en->readback_.data(); bytes = n * sizeof(float4); break;
-        }
-        default: return fail(ST_ERR_INVALID_ARGUMENT, "unknown scene buffer");
     }
     if (written) *written = bytes;
     if (!out) return ST_OK;
@@ -757,15 +720,14 @@ int st_debug_world(StEngine* e, uint32_t* light_count, uint32_t* next_frame) {
 int st_set_bvh_refresh(StEngine* e, int mode) {
     ST_REQUIRE(e, "null engine");
     ST_REQUIRE(mode == ST_BVH_REBUILD || mode == ST_BVH_REFIT || mode == ST_BVH_REFIT_DEVICE || mode == ST_BVH_BUILD_DEVICE || mode == ST_BVH_AUTO, "unknown refresh mode");
-    Engine* en = E(e);
-    if (en->bvh_refresh_mode != mode) { en->bvh_refresh_mode = mode; en->have_topology = false; }
+    E(e)->tree.set_refresh_mode(mode);
     return ST_OK;
 }
-int st_debug_device_builds(StEngine* e, uint64_t* ticks) { ST_REQUIRE(e && ticks, "null argument"); *ticks = E(e)->device_builds; return ST_OK; }
-int st_debug_device_tree_refits(StEngine* e, uint64_t* ticks) { ST_REQUIRE(e && ticks, "null argument"); *ticks = E(e)->device_tree_refits; return ST_OK; }
+int st_debug_device_builds(StEngine* e, uint64_t* ticks) { ST_REQUIRE(e && ticks, "null argument"); *ticks = E(e)->tree.device_build_ticks(); return ST_OK; }
+int st_debug_device_tree_refits(StEngine* e, uint64_t* ticks) { ST_REQUIRE(e && ticks, "null argument"); *ticks = E(e)->tree.device_tree_refit_ticks(); return ST_OK; }
 int st_debug_bvh_depth(StEngine* e, uint32_t* deepest_internal_chain, uint32_t* stack_entries) {
     ST_REQUIRE(e && deepest_internal_chain && stack_entries, "null argument");
-    *deepest_internal_chain = E(e)->bvh_stack_need; *stack_entries = E(e)->stack_entries;
+    E(e)->tree.depth(deepest_internal_chain, stack_entries);
     return ST_OK;
 }
 int st_debug_walk_overflow(StEngine* e, uint64_t* overflows, uint32_t* wide_stack_entries, uint32_t* packets_off) {
@@ -779,17 +741,17 @@ int st_debug_walk_overflow(StEngine* e, uint64_t* overflows, uint32_t* wide_stac
 }
 int st_debug_auto_tree(StEngine* e, float* leaf_run_weight, uint32_t* first_tree_on_device) {
     ST_REQUIRE(e && leaf_run_weight && first_tree_on_device, "null argument");
-    *leaf_run_weight = E(e)->host_leaf_run_weight; *first_tree_on_device = E(e)->auto_first_on_device ? 1u : 0u;
+    E(e)->tree.auto_tree(leaf_run_weight, first_tree_on_device);
     return ST_OK;
 }
 int st_debug_bvh_refits(StEngine* e, uint64_t* rebuilds, uint64_t* refits) {
     ST_REQUIRE(e && rebuilds && refits, "null argument");
-    *rebuilds = E(e)->rebuilds; *refits = E(e)->refits;
+    E(e)->tree.refit_stats(rebuilds, refits);
     return ST_OK;
 }
 int st_debug_bvh_device_refits(StEngine* e, uint64_t* device_refits) {
     ST_REQUIRE(e && device_refits, "null argument");
-    *device_refits = E(e)->device_refits;
+    *device_refits = E(e)->tree.device_refit_ticks();
     return ST_OK;
 }
 int st_debug_device_bakes(StEngine* e, uint64_t* ticks, uint64_t* triangles) {
@@ -799,7 +761,7 @@ int st_debug_device_bakes(StEngine* e, uint64_t* ticks, uint64_t* triangles) {
 }
 int st_debug_bvh_refresh(StEngine* e, uint64_t* primitives, uint64_t* reused) {
     ST_REQUIRE(e && primitives && reused, "null argument");
-    *primitives = E(e)->bvh.prims.size(); *reused = E(e)->bvh.reused_primitives();
+    E(e)->tree.refresh_stats(primitives, reused);
     return ST_OK;
 }
 

@@ -1,8 +1,8 @@
 // st_engine.h — the host engine of libstrolle_hip.so: state and interfaces shared by its translation units
 //   st_engine.cpp       construction, tuning (StTuning + environment), destruction
 //   st_scene.cpp        scene stores: materials, images, lights, instances -> world-space triangles (baking)
-//   st_bvh_refresh.cpp  device form of the BVH stream, refit (host) and the device refit's index arrays, depth check
-//   st_tick.cpp         Engine::tick: refresh + uploads (double-buffered scene / light copies, page-locked staging)
+//   st_bvh_refresh.cpp  the scene's BVH (st_bvh_refresh.h): the host's tree and its streams, refits, the wide topology, the device builder's input, the tick's tree plan
+//   st_tick.cpp         Engine::tick: refresh of the stores + uploads (double-buffered scene / light copies, page-locked staging)
 //   st_render.cpp       per-camera buffers and Engine::render: the per-frame pass graph in phases, on two HIP streams; present hand-over
 //   st_display.cpp      display transforms: exposure, tone mapping, the auto-exposure state
 //   st_post.cpp         output post-processing: FXAA and the resampler
@@ -330,6 +330,7 @@ inline double format_bytes(uint32_t format) { return format == ST_FORMAT_RGBA32F
 
 }  // namespace st
 #include "st_deform.h"
+#include "st_bvh_refresh.h"
 #include "st_output_chain.h"
 namespace st {
 
@@ -458,6 +459,23 @@ int dist_grid(uint32_t width, uint32_t height, uint32_t world, uint32_t cols, St
 int dist_grid_tile(const StDistGrid* g, uint32_t rank, StDistRect* owned);
 int dist_grid_rebalance(uint32_t width, uint32_t height, const StDistGrid* cur, const float* cost, uint32_t max_step, StDistGrid* out);
 
+// The arrays a scene change rewrites exist twice. A tick that changes the scene fills the copy no frame in flight reads,
+// on a stream of its own, while the previous frame still renders from the other one; the next frame switches over.
+// (Updating in place would have to wait for the previous frame, and the next frame's primary rays with it.)
+struct SceneSet {
+    DeviceArray tri_attr, xforms, materials, base_packed;
+    TreeCopy tree;   // the tree's half (st_bvh_refresh.h): the streams, the refit's index arrays, the device builder's scratch
+    // per triangle slot the hit-test record and the bounds (ST_BVH_REFIT_DEVICE, ST_BVH_BUILD_DEVICE: k_bvh.hip and k_lbvh.hip read them)
+    DeviceArray tri_geo, tri_bounds;
+    size_t dirty_lo = SIZE_MAX, dirty_hi = 0; bool tri_full = true;  // what this copy lacks of the host's triangle arrays
+    std::vector<uint64_t> pending_moves;   // instances moved on the device whose current transform this copy has not baked yet
+    DeviceArray bake_jobs, bake_starts;
+    // per instance slot (tri_attr[4 t + 3].w): {StHandle lo, hi, first triangle slot, 0} — the scene queries' instance and mesh triangle (st_query.cpp)
+    DeviceArray instance_table;
+    Fence fence;   // reads of this copy enqueued since it was written end here (reader_end; pick_copy waits before it writes the copy again)
+    bool valid = false;
+};
+
 struct Engine {
     int device = -1;
     bool has_device = false;
@@ -501,38 +519,10 @@ struct Engine {
     std::map<uint64_t, std::pair<size_t, size_t>> instance_triangles; SlotRanges triangle_free;
     std::vector<HostTriangle> triangles; std::vector<BuildPrim> prims; std::vector<uint8_t> prim_alive;
     size_t live_prims_ = 0;   // how many of prim_alive are set (kept by refresh_instances / drop_instance_triangles: device_build_possible asks every tick)
-    std::vector<float4> tri_geo, tri_attr, tri_bounds, bvh_stream, bvh_upload_;  // tri_bounds: (lo, hi) per triangle slot (device refit)
-    BvhBuild bvh;
+    std::vector<float4> tri_geo, tri_attr, tri_bounds;  // tri_bounds: (lo, hi) per triangle slot (device refit)
+    // The scene's BVH — the host's tree, its streams, refits, the device builder, the tick's plan — has one owner (st_bvh_refresh.h)
+    SceneTree tree{*this};
     bool scene_uploaded = false;
-    // BVH refresh policy (st_set_bvh_refresh). Refit: while the set of (triangle slot, material) pairs and the Blend flags
-    // are what the last build saw — i.e. instances only moved — keep the tree and recompute the boxes bottom-up.
-    int bvh_refresh_mode = ST_BVH_AUTO;   // (host-only engines, the exact build and observed contract streams: what ST_BVH_REBUILD does)
-    bool have_topology = false; uint64_t topology_signature = 0;
-    std::vector<uint32_t> internal_positions;  // stream offsets of the internal nodes, ascending (parents before children)
-    uint64_t refits = 0, rebuilds = 0;
-    uint64_t device_refits = 0;    // ticks whose boxes were recomputed on the device
-    uint64_t tree_version = 0;     // bumped by every rebuild (ST_BVH_REFIT_DEVICE: a scene copy whose arrays are of this version can be refitted in place)
-    bool host_stream_stale = false;  // device refits happened since bvh_stream's boxes were last recomputed (debug reads and full uploads refit it first)
-    std::vector<float4> readback_; uint32_t live_bvh_texels = 0;  // st_debug_read_scene(6)
-    std::vector<uint32_t> entry_of_tri_, parent_, refit_local_, refit_items_, refit_batch_off_;  // host images of the device refit's index arrays (index_device_tree)
-    std::vector<uint32_t> readback_levels_;
-    std::vector<std::pair<uint32_t, uint32_t>> refit_levels_;  // (first batch, batches) of each launch, leaves first
-    // Deepest chain of internal nodes in the uploaded stream = the most entries a traversal can have pending (every internal
-    // node on the path may push its far child). The kernels' per-lane stack holds kBvhStackSize entries (strolle-gpu/src/lib.rs:76;
-    // the reference indexes past the end there, here a push beyond the end is dropped): a deeper tree is reported, not hidden.
-    // (round 5) Up to kBvhStackSizeDeep the launches take a deeper stack instead (dynamic LDS): `stack_entries` is what this tree's launches hold.
-    uint32_t bvh_stack_need = 0, stack_entries = (uint32_t)kBvhStackSize; bool bvh_depth_warned = false, bvh_too_deep_unreported = false;
-    void measure_stack_need();
-    // Device form of the stream (st_types.h "device BVH stream"): every entry four texels — an internal node as the
-    // serializer wrote it (far pointer remapped), a leaf entry followed by its triangle's hit-test record — so that one
-    // four-texel fetch serves a traversal step of either kind. Entry k starts at texel 4 k.
-    std::vector<uint32_t> expand_map_;  // scratch: offset in bvh_stream -> texel pointer in bvh_upload_ (entry starts only)
-    uint32_t device_bvh_len = 0; bool device_root_is_leaf = false;
-    void expand_stream();
-    void index_device_tree();
-    std::vector<uint8_t> internal_start_;  // scratch of measure_stack_need: 1 where an internal node begins
-    bool is_internal_start(size_t p) const { return p < internal_start_.size() && internal_start_[p]; }
-    void mark_internal_starts();
 
     // images: a single linear RGBA8 atlas of the reference's extent (images.rs:28-29); rectangles from st_atlas.h
     static constexpr uint32_t kAtlasW = 8192, kAtlasMaxH = 8192;
@@ -582,33 +572,6 @@ struct Engine {
     std::map<StHandle, std::unique_ptr<Lut>> luts_live; std::vector<std::unique_ptr<Lut>> luts_retired;
 
     DeviceArray d_byte_luts, d_atlas, d_blue_noise, d_transmittance, d_scattering, d_sky;
-    // The arrays a scene change rewrites exist twice. A tick that changes the scene fills the copy no frame in flight reads,
-    // on a stream of its own, while the previous frame still renders from the other one; the next frame switches over.
-    // (Updating in place would have to wait for the previous frame, and the next frame's primary rays with it.)
-    struct SceneSet {
-        DeviceArray bvh, tri_attr, xforms, materials, base_packed;
-        DeviceArray bvh_compact; uint32_t compact_entries = 0;   // k_bvh.hip k_bvh_compact: 48 B per entry, regenerated whenever `bvh` changed
-        // k_bvh.hip k_bvh_wide: 4-wide nodes (64 B) + leaf records (48 B), regenerated whenever `bvh` changed; the topology arrays only when the tree was rebuilt
-        DeviceArray bvh_wide /* the nodes, then the leaf records */, wide_topo, wide_leaf_entry; uint32_t wide_nodes = 0, wide_leaves = 0, wide_root = 0, wide_links16 = 0, wide_for_entries = 0;
-        uint64_t wide_topology_serial = 0;   // which build_wide_topology() result this copy holds
-        // ST_BVH_BUILD_DEVICE (k_lbvh.hip): this copy's wide stream was built on the device from its own triangle arrays; `bvh` (the contract
-        // stream) is then stale and no launch may read it. lb_live: live triangles of that build. The rest is the builder's scratch.
-        bool device_built = false; uint32_t lb_live = 0; uint64_t tri_info_serial = 0;
-        uint64_t lb_serial = ~0ull; uint32_t lb_slots = 0;   // tri_info_serial_ / triangle slots of the copy's last device BUILD (a refit needs both unchanged)
-        DeviceArray tri_info, lb_keys_a, lb_keys_b, lb_temp, lb_seg, lb_children, lb_node_box, lb_small;
-        // ST_BVH_REFIT_DEVICE: what k_bvh.hip needs beside the stream — per triangle slot the hit-test record, the bounds and the
-        // device entry that holds it; per entry its parent (entry << 1 | child slot); the leaf runs; an arrival counter per entry.
-        // tree_version says which build of the tree these (and the stream's topology) belong to.
-        DeviceArray tri_geo, tri_bounds, entry_of_tri, parent, refit_local, refit_items, refit_batch_off;
-        uint64_t tree_version = 0;
-        size_t dirty_lo = SIZE_MAX, dirty_hi = 0; bool tri_full = true;  // what this copy lacks of the host's triangle arrays
-        std::vector<uint64_t> pending_moves;   // instances moved on the device whose current transform this copy has not baked yet
-        DeviceArray bake_jobs, bake_starts;
-        // per instance slot (tri_attr[4 t + 3].w): {StHandle lo, hi, first triangle slot, 0} — the scene queries' instance and mesh triangle (st_query.cpp)
-        DeviceArray instance_table;
-        Fence fence;   // reads of this copy enqueued since it was written end here (reader_end; pick_copy waits before it writes the copy again)
-        bool valid = false;
-    };
     SceneSet sets[2]; int live = 0;
     // the light table alternates the same way, on its own schedule (a light that moves every frame does not resend the scene)
     struct LightSet { DeviceArray buf; Fence fence; };
@@ -653,11 +616,6 @@ struct Engine {
     DistState* dist = nullptr;
     void release_dist();
     void dist_forget_camera(uint64_t handle);
-    // the wide stream's topology (st_bvh_refresh.cpp build_wide_topology), from bvh_upload_: 8 words per node (4 box sources, 4 links) and the
-    // contract entry of every leaf record; wide_serial_ counts the builds
-    std::vector<uint32_t> wide_topo_, wide_leaf_entry_; uint32_t wide_root_ = 0, wide_stack_need_ = 0; uint64_t wide_serial_ = 0; uint64_t wide_built_for_ = ~0ull;
-    void build_wide_topology();
-    int refresh_wide_stream(SceneSet& t, hipStream_t up, bool topology_changed, bool* pageable);
     int dist_set_partition(uint64_t handle, CameraState& c, uint32_t cols, uint32_t apron);
     int dist_set_grid(uint64_t handle, CameraState& c, const StDistGrid& grid, uint32_t apron);
     int dist_gather(uint64_t handle, CameraState& c, const void* frame, void* full, hipStream_t stream);
@@ -686,28 +644,12 @@ struct Engine {
     bool refresh_instances();
     void bake_jobs_on_host(const std::vector<BakeJob>& jobs, size_t total);
     int bake_on_device(SceneSet& t, hipStream_t up, bool* pageable);
-    int refresh_compact_stream(SceneSet& t, hipStream_t up);
 
-    uint64_t topology_of(const std::vector<uint8_t>& blend) const;
-    void index_stream();
-    Aabb subtree_box(size_t p) const;
-    void refit_node(size_t p);
-    void refit_span(size_t begin, size_t end);
-    // One thread: at 134 k triangles the sweep is about a millisecond, less than starting a worker pool for it would buy back.
-    void refit_stream() { refit_span(0, bvh_stream.size()); }
-    bool device_refit_possible() const { return bvh_refresh_mode == ST_BVH_REFIT_DEVICE && has_device; }
     std::vector<uint8_t> blend_flags() const { std::vector<uint8_t> b(materials.size()); for (size_t i = 0; i < materials.size(); i++) b[i] = materials[i].alpha_mode == 1u; return b; }
     // Nothing observes the contract stream (a device-built tree can replace it) while every ray walks the wide stream: the fast build with the
     // wide stream and what it rests on, no traversal bytes counted (this part: wide_only_tuning) — and no camera draws the heatmap.
     bool wide_only_tuning() const { return arithmetic == ST_ARITH_FAST && tuning.wide_bvh && tuning.compact_bvh && tuning.anyhit_fast && !count_bytes; }
     bool heatmap_camera() const { for (const auto& kv : cameras) if (kv.second->desc.mode == ST_MODE_BVH_HEATMAP) return true; return false; }
-    // ST_BVH_BUILD_DEVICE: the tree of a changed scene is built on the device (k_lbvh.hip) while nothing observes the contract stream
-    bool host_tree_stale = false;    // the host's binned-SAH tree (bvh_stream and everything derived from it) is behind the scene
-    uint64_t device_builds = 0, device_tree_refits = 0;   // ticks answered by a device build / by a refit of the device-built tree (moves only)
-    bool device_tree_refit_now = false; uint32_t device_refits_since_build = 0;
-    size_t info_dirty_lo_ = SIZE_MAX, info_dirty_hi_ = 0; bool info_full_ = true;   // slots whose word may have changed since tri_info_ was listed (spawned, removed); everything (materials changed)
-    void mark_info_dirty(size_t b, size_t e) { info_dirty_lo_ = std::min(info_dirty_lo_, b); info_dirty_hi_ = std::max(info_dirty_hi_, e); }
-    std::vector<uint32_t> tri_info_; uint32_t tri_info_live_ = 0; uint64_t tri_info_serial_ = 1, tri_info_built_for_ = 0;   // per slot: live | Blend << 1 | material << 2; the serial counts what can change it
     // A wide walk that found its stack full drops the push and says so in one of two sticky words of page-locked host memory (st_traverse.h
     // wide_walk_overflowed; KArgs::walk_flags). st_tick reads them: a per-lane walk's overflow re-arms every later launch with a deeper stack
     // (24 -> 32 -> 48 -> 56 entries: dynamic LDS, fewer waves per SIMD), the packet's (64 entries, one VGPR) hands primary visibility back to the
@@ -719,18 +661,9 @@ struct Engine {
     uint64_t walk_overflows = 0; bool walk_overflow_unreported = false;
     uint32_t wide_stack_entries_now() const { return wide_stack_rearmed ? wide_stack_rearmed : (tuning.wide_stack_entries ? tuning.wide_stack_entries : (uint32_t)kBvhStackSize); }
     void note_walk_overflow();
-    // ST_BVH_AUTO's choice of a scene's FIRST tree (st_tick.cpp device_build_possible): host_leaf_run_weight = the surface-area-weighted mean length of the host
-    // tree's leaf runs (rebuild_host_tree); above kAutoLeafRunLimit the device builder's tree renders faster (profiles/r06_tree_choice*.txt)
-    static constexpr float kAutoLeafRunLimit = 3.4f;
-    float host_leaf_run_weight = 1.0f; bool auto_first_on_device = false;
-    bool device_build_possible() const;
-    int build_on_device(SceneSet& t, hipStream_t up, bool* pageable);
-    int reserve_device_builder(SceneSet& t, size_t slots, uint32_t live);
-    void rebuild_host_tree(bool timing);
     enum TriArrays : unsigned { TRI_GEO = 1u /* hit-test records + bounds */, TRI_ATTR = 2u /* attribute records */ };   // a copy's triangle-slot arrays
     bool tri_fits(const SceneSet& t, unsigned arrays) const;
     int upload_tri_slots(SceneSet& t, unsigned arrays, bool whole, hipStream_t up, bool* pageable);
-    enum class TreePlan { none, host_refit, host_rebuild, device_build, device_refit, host_to_observer };
     struct TickIo { hipStream_t stream; bool pageable = false, pageable_copy = false, copied = false, uploaded = false; };   // copied: on copy_stream; uploaded: on `stream`
     int tick(hipStream_t stream);
     TreePlan refresh_scene();

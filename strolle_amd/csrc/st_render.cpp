@@ -87,47 +87,19 @@ int Engine::allocate_camera(CameraState& c) {
 }
 
 // The scene half of KArgs (st_engine.h scene_args): what every launch that walks the live scene copy reads — its arrays, the stream its rays
-// walk (contract, compact or wide), the stack they hold and the walk flags. `heatmap`: the launch is a BVH heatmap pass, which observes the
+// walk (contract, compact or wide) and the stack they hold (SceneTree::walk_args), the walk flags. `heatmap`: the launch is a BVH heatmap pass, which observes the
 // contract stream. Shared by render() and the scene queries (st_query.cpp).
 int Engine::scene_args(KArgs& a, bool heatmap) const {
     const SceneSet& scene = sets[live];
-    a.bvh = static_cast<const float4*>(scene.bvh.ptr); a.tri_attr = static_cast<const float4*>(scene.tri_attr.ptr); a.instance_xforms = static_cast<const float4*>(scene.xforms.ptr);
+    a.tri_attr = static_cast<const float4*>(scene.tri_attr.ptr); a.instance_xforms = static_cast<const float4*>(scene.xforms.ptr);
     a.materials = static_cast<const GpuMaterial*>(scene.materials.ptr); a.material_base_packed = tuning.packed_base ? static_cast<const uint32_t*>(scene.base_packed.ptr) : nullptr;
     a.atlas = static_cast<const uchar4*>(d_atlas.ptr); a.byte_luts = static_cast<const float*>(d_byte_luts.ptr);
     a.tri_slots = (uint32_t)(tri_geo.size() / 3u);
     a.count_bytes = count_bytes ? 1u : 0u;
     a.exp_flags = exp_flags;
-    // the fast build's shadow rays walk the compact stream of this scene copy when it has one (k_bvh.hip k_bvh_compact)
-    const bool compact = arithmetic == ST_ARITH_FAST && tuning.compact_bvh && tuning.anyhit_fast && !count_bytes && scene.compact_entries != 0u && scene.compact_entries * 4u == device_bvh_len;
-    a.bvh_c = compact ? static_cast<const float4*>(scene.bvh_compact.ptr) : nullptr;
-    a.bvh_c_root = (compact && device_root_is_leaf) ? 1u : 0u;
-    // ... or, preferred, its wide form (k_bvh.hip k_bvh_wide)
-    // (ST_BVH_BUILD_DEVICE: this copy's wide stream was built on the device and its contract stream is stale — every ray must walk the wide stream)
-    if (scene.device_built && (!wide_only_tuning() || heatmap))
-        return fail(ST_ERR_INVALID_ARGUMENT, "the live scene copy's tree was built on the device (ST_BVH_BUILD_DEVICE) and this frame needs the contract stream (heatmap camera, exact arithmetic, "
-                                             "byte counting or a switched-off wide stream): st_tick builds it on the host once it sees the observer");
-    const bool wide = scene.device_built || (compact && tuning.wide_bvh && scene.wide_for_entries != 0u && scene.wide_for_entries * 4u == device_bvh_len);
-    a.bvh_w = wide ? static_cast<const float4*>(scene.bvh_wide.ptr) : nullptr;
-    a.bvh_w_leaf_off = wide ? scene.wide_nodes * 64u : 0u;
-    a.bvh_w_root = wide ? scene.wide_root : 0u; a.bvh_w_links16 = wide ? scene.wide_links16 : 0u;
-    a.primary_packets = wide && tuning.primary_packets && !packets_overflowed ? 1u : 0u;
+    if (int rc = tree.walk_args(scene.tree, a, heatmap)) return rc;   // which stream its rays walk, and with what stack
     a.walk_flags = walk_flags_dev;
-    {   // the largest link of this stream: (max(nodes, leaf records) - 1) << 1 | 1
-        uint32_t bits = 16u;
-        const uint32_t top = std::max(scene.wide_nodes, scene.wide_leaves);
-        while (bits < 31u && (1ull << bits) <= (unsigned long long)top * 2ull + 1ull) bits++;
-        a.bvh_w_link_mask = (1u << bits) - 1u;
-    }
     a.anyhit_contract = (count_bytes || !tuning.anyhit_fast) ? 1u : 0u;   // the reference's used_memory is the contract loop's
-    // Walks over the CONTRACT stream (exact build, heatmap pass, byte-counting mode, the compact binary stream: the contract's tree) hold what
-    // that tree's deepest chain can need — proven drop-free up to kBvhStackSizeDeep. The WIDE stream is another tree: its worst case (every
-    // child of every node on a path hit: 35 pending entries for the 13 k-triangle dungeon, 45 at 208 k) does not fit LDS at full occupancy and
-    // no ray comes near it (deepest stack measured: 11-13); it keeps kBvhStackSize entries, and test_the_wide_walk_drops_no_push renders
-    // BASELINE config 3's scene with 24 and with 48 entries (StTuning::wide_stack_entries) and finds the same bits.
-    // A walk that does find the stack full says so (KArgs::walk_flags) and the next st_tick re-arms the launches with a deeper one (st_engine.h walk_flags_host).
-    a.stack_entries = wide ? wide_stack_entries_now() : stack_entries;
-    a.bvh_len = scene.device_built ? 0x40000000u : device_bvh_len;   // (device-built: no contract stream; any value that is neither "empty" nor "fits LDS")
-    if (scene.device_built) a.bvh = nullptr;
     a.atlas_w = atlas_w; a.atlas_h = atlas_h;
     return ST_OK;
 }

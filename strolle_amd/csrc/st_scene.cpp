@@ -91,7 +91,7 @@ void Engine::drop_instance_triangles(uint64_t id) {
     if (it == instance_triangles.end()) return;
     triangle_free.give(it->second.first, it->second.second);
     for (size_t i = it->second.first; i < it->second.second; i++) { live_prims_ -= prim_alive[i]; prim_alive[i] = 0; }
-    mark_info_dirty(it->second.first, it->second.second);
+    tree.slots_changed(it->second.first, it->second.second);
     instance_triangles.erase(it);
 }
 
@@ -178,9 +178,8 @@ bool Engine::refresh_instances() {
     // Device bake: when every dirty instance only MOVED — same mesh (and version of it), same material, its slots already assigned —
     // under ST_BVH_REFIT_DEVICE with the tree's topology on record, the host bakes nothing: the device copies do (Engine::bake_on_device).
     const bool removed = instance_removed; instance_removed = false;
-    // (ST_BVH_BUILD_DEVICE: the same, with the tree rebuilt on the device from the device-baked arrays instead of refitted)
-    const bool build_mode = device_build_possible() && scene_uploaded;
-    if (tuning.device_bake && ((device_refit_possible() && have_topology) || build_mode) && !materials_changed_this_tick && !removed) {
+    const bool tree_follows = tree.moves_stay_on_device();
+    if (tuning.device_bake && tree_follows && !materials_changed_this_tick && !removed) {
         bool only_moves = true; size_t moved = 0;
         for (const auto& inst : instances) {
             if (!inst.dirty) continue;
@@ -247,7 +246,7 @@ bool Engine::refresh_instances() {
         jobs.push_back({deform.bake_source(inst.id, mesh->second), &inst, mat->second, b, count});
         total += count;
         for (SceneSet& t : sets) { t.dirty_lo = std::min(t.dirty_lo, b); t.dirty_hi = std::max(t.dirty_hi, e); }  // slots each device copy still has to receive
-        mark_info_dirty(b, e);
+        tree.slots_changed(b, e);
         if (have == instance_triangles.end()) live_prims_ += count;   // (the bake below sets prim_alive for the whole range)
         instance_triangles[inst.id] = {b, e};
         auto mv = mesh_version.find(inst.mesh);
@@ -309,7 +308,7 @@ int Engine::bake_on_device(SceneSet& t, hipStream_t up, bool* pageable) {
     // the EXACT build's kernel, whatever arithmetic the frames use: the baked arrays are the host's bits
     launchers_exact().launch_bvh_bake(t.bake_jobs.ptr, static_cast<const uint32_t*>(t.bake_starts.ptr), (uint32_t)jobs.size(), starts.back(), static_cast<const float*>(d_mesh_store.ptr),
                                       deform.posed_store(), static_cast<float4*>(t.tri_geo.ptr), static_cast<float4*>(t.tri_bounds.ptr), static_cast<float4*>(t.tri_attr.ptr),
-                                      static_cast<float4*>(t.bvh.ptr), t.device_built ? nullptr : static_cast<const uint32_t*>(t.entry_of_tri.ptr), up);
+                                      t.tree.patch_stream(), t.tree.patch_index(), up);
     // the next skin launch overwrites the regions after this bake — and after an earlier one still pending on another stream:
     // the event is re-recorded here behind a wait for its previous recording, so that it covers both (the bake itself is not delayed)
     if (reads_posed) if ((rc = deform.posed_read_by(up))) return rc;
