@@ -1214,7 +1214,7 @@ int st_camera_set_output_format(StEngine* e, StHandle camera, int format);
  *   ST_NO_FUSE_GI_REPROJECTION ST_NO_FUSE_WAVELET ST_NO_FUSE_COMPOSE ST_NO_PREVIEW_BOTH ST_NO_VARIANCE_IN_REPROJECT
  *   ST_KEEP_ALL_PLANES ST_KEEP_SCRATCH ST_NO_GI_ALIAS ST_NO_STAGING ST_NO_DOUBLE_BUFFER ST_NO_PACKED_BASE
  *   ST_NO_ANYHIT_FAST ST_NO_COMPACT_BVH (=1 clears the field), ST_ALLOW_DEEP_BVH ST_DI_HEAD_ON_MAIN ST_TILE_MAP ST_TILE_MAP_DENOISE ST_SIDE_PRIORITY
- *   ST_TICK_TIMING ST_DEVICE_BAKE (= value). */
+ *   ST_TICK_TIMING ST_DEVICE_BAKE ST_SIDE_START (= value). */
 typedef struct StTuning {
     uint32_t struct_size;
     uint32_t overlap;               /* 1: two HIP streams per camera, software-pipelined across frames */
@@ -1252,6 +1252,10 @@ typedef struct StTuning {
     uint32_t wide_stack_entries;    /* pending entries per ray of the wide walk's stack: 0 = 24 (strolle-gpu/src/lib.rs:76); tests render with 48 to show that 24 drops no push */
     uint32_t primary_packets;       /* with the wide stream: primary visibility walks it as ONE packet per wave — uniform node pointer and stack, scalar node
                                      * fetches, per-lane box and triangle tests, ballots decide the descent (st_traverse.h closest_hit_packet) */
+    uint32_t side_start;            /* two streams: where the NEXT frame's side-stream work (primary visibility, the GI chain) may start. 0: behind this frame's DI
+                                     * passes; 1 / 2 (default) / 3: also behind the a-trous launch of strides 1+2 / stride 4 / stride 8 — the LDS-staged launches fill a CU's
+                                     * LDS, and a tracing block beside them waits for a CU instead of sharing one. Only waits move: the same launches in the same
+                                     * order, the same bits. Frames without the fused a-trous chain behave as 0 */
 } StTuning;
 int st_engine_get_tuning(StEngine* e, StTuning* out);
 int st_engine_set_tuning(StEngine* e, const StTuning* tuning);

@@ -104,6 +104,7 @@ pub struct StTuning {
     pub wide_bvh: u32,
     pub wide_stack_entries: u32,
     pub primary_packets: u32,
+    pub side_start: u32,
 }
 
 /// [x0, x1) x [y0, y1) in pixels (st_dist_partition / st_dist_window)

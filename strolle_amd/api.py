@@ -96,7 +96,7 @@ class StTuning(C.Structure):
                                           "lean_frame", "skip_scratch_stores", "di_head_on_main", "alias_gi_history", "tile_map", "tile_map_denoise")] + \
                [("side_priority", C.c_int32)] + \
                [(n, C.c_uint32) for n in ("staging", "double_buffer", "packed_base", "tick_timing", "anyhit_fast", "compact_bvh",
-                                          "allow_deep_bvh", "device_bake", "wide_bvh", "wide_stack_entries", "primary_packets")]
+                                          "allow_deep_bvh", "device_bake", "wide_bvh", "wide_stack_entries", "primary_packets", "side_start")]
 
 
 PROFILE_MAX_KERNELS = 64   # ST_PROFILE_MAX_KERNELS

@@ -17,6 +17,7 @@ StTuning default_tuning() {
     t.staging = t.double_buffer = t.packed_base = 1u; t.tick_timing = 0u;
     t.anyhit_fast = 1u; t.compact_bvh = 1u; t.wide_bvh = 1u; t.primary_packets = 1u;
     t.allow_deep_bvh = 0u; t.device_bake = 1u;
+    t.side_start = 2u;   // the next frame's side stream starts behind the stride-4 a-trous launch (profiles/side_schedule.json)
     return t;
 }
 static void tuning_from_environment(StTuning& t) {
@@ -35,7 +36,7 @@ static void tuning_from_environment(StTuning& t) {
     struct Value { const char* name; uint32_t StTuning::*field; };
     static const Value values[] = {
         {"ST_DI_HEAD_ON_MAIN", &StTuning::di_head_on_main}, {"ST_TILE_MAP_DENOISE", &StTuning::tile_map_denoise}, {"ST_TICK_TIMING", &StTuning::tick_timing},
-        {"ST_ALLOW_DEEP_BVH", &StTuning::allow_deep_bvh}, {"ST_DEVICE_BAKE", &StTuning::device_bake},
+        {"ST_ALLOW_DEEP_BVH", &StTuning::allow_deep_bvh}, {"ST_DEVICE_BAKE", &StTuning::device_bake}, {"ST_SIDE_START", &StTuning::side_start},
     };
     if (const char* v = getenv("ST_TILE_MAP")) t.tile_map = t.tile_map_denoise = (uint32_t)atoi(v);
     for (const Value& c : values) if (const char* v = getenv(c.name)) t.*c.field = (uint32_t)atoi(v);
@@ -60,6 +61,7 @@ Engine::Engine() {
 int Engine::set_tuning(const StTuning& t) {
     if (t.struct_size != sizeof(StTuning)) return fail(ST_ERR_INVALID_ARGUMENT, "StTuning::struct_size does not match this library");
     if (t.tile_map > 2u || t.tile_map_denoise > 2u) return fail(ST_ERR_INVALID_ARGUMENT, "tile_map is 0, 1 or 2");
+    if (t.side_start > 3u) return fail(ST_ERR_INVALID_ARGUMENT, "side_start is 0 ... 3");
     if (t.wide_stack_entries != 0u && (t.wide_stack_entries < 8u || t.wide_stack_entries > 56u)) return fail(ST_ERR_INVALID_ARGUMENT, "wide_stack_entries is 0 (default) or 8 ... 56");
     if (t.wide_stack_entries != tuning.wide_stack_entries) wide_stack_rearmed = 0u;   // the caller's figure stands until a walk overflows it
     tuning = t;

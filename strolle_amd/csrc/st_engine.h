@@ -357,8 +357,9 @@ struct CameraState {
     // passes behind frame N's are per camera, so cameras rendered on different caller streams never wait on — or race
     // with — each other's frames.
     Stream side_stream;
-    Event ev_di_head, ev_gi_done, ev_prim_ok, ev_frame_done, ev_setup;
+    Event ev_di_head, ev_gi_done, ev_prim_ok, ev_frame_done, ev_setup, ev_lds_done;
     bool have_prev_frame_events = false;
+    bool have_lds_done = false;   // the last frame recorded ev_lds_done inside its a-trous chain (StTuning::side_start): the next primary visibility waits for it too
     // GI history hand-over without the copy. gi_resolving ends every frame by copying the frame's source reservoirs into
     // GI_RESERVOIRS_0, next frame's history (gi_resolving.rs:60-66): 128 B per pixel of pure copy. When the source is the
     // temporal pass's output (GI_RESERVOIRS_1, four frames in six) and the whole pass graph runs, the engine swaps the two

@@ -6,8 +6,8 @@ namespace st {
 void Engine::release_camera(CameraState& c) {
     c.slab.release(); c.counters.release(); c.tile_mask.release();
     c.side_stream.reset();
-    for (Event* e : {&c.ev_di_head, &c.ev_gi_done, &c.ev_prim_ok, &c.ev_frame_done, &c.ev_setup}) e->reset();
-    c.have_prev_frame_events = false;
+    for (Event* e : {&c.ev_di_head, &c.ev_gi_done, &c.ev_prim_ok, &c.ev_frame_done, &c.ev_setup, &c.ev_lds_done}) e->reset();
+    c.have_prev_frame_events = c.have_lds_done = false;
     c.join_present(); c.present_stream.reset();
     for (auto& p : c.present) p = CameraState::PresentSlot();
 }
@@ -190,6 +190,7 @@ struct Frame {
     KArgs a{}; OutputRoute route; FrameSwitches s{}; HdrWork work;
     const uint32_t mode, pseed;   // pseed: one seed for both preview passes (passes/gi_preview_resampling.rs:60-74)
     bool mask_split = false, di_reprojected = false, gi_reprojected = false, composed = false, luts_generated_now = false; uint32_t launch_ordinal = 0u;
+    int side_rc = ST_OK;   // of recording ev_lds_done inside denoise()
     Frame(Engine& e_, CameraState& c_, void* out_, hipStream_t s_) : e(e_), c(c_), out(out_), stream(s_), cur(s_), mode(c_.desc.mode), pseed(pass_seed(e_.base_seed, c_.frame, SEED_GI_PREVIEW)) {}
     uint32_t seed(uint32_t pass) const { return pass_seed(e.base_seed, c.frame, pass); }
     auto gi_preview_src() const { return s.gi_source == 0 ? a.gi_res[1] : a.gi_res[2]; }
@@ -533,6 +534,12 @@ struct Frame {
         float4* gi[3] = {a.gi_diff_stash, a.gi_diff_prev_colors, a.gi_diff_curr_colors};
         const int in_ix[5] = {0, 1, 0, 2, 0}, out_ix[5] = {1, 0, 2, 0, 2};
         uint32_t first = 0;
+        // StTuning::side_start: behind which launch of the chain the NEXT frame's primary visibility may start (two_streams). The LDS-staged launches
+        // (strides 1+2, stride 4) fill a CU's LDS, so a tracing block beside them waits for a CU instead of sharing one.
+        auto side_point = [&](uint32_t point) {
+            if (!s.two_streams || first != 2u || e.tuning.side_start != point) return;
+            side_rc = c.ev_lds_done.record(stream); c.have_lds_done = side_rc == ST_OK;
+        };
         if (e.tuning.fuse && e.tuning.fuse_wavelet) {
             // variance estimation + strides 1 and 2 form one launch group of two kernels: the variance pass hands its output over in an internal pair of planes
             // (k_denoise.hip k_denoise_wavelet_12 says why), so the stash planes receive the stride-2 result directly. One group = one set of pass bits (st_debug_set_pass_mask).
@@ -543,6 +550,7 @@ struct Frame {
             run(KS_DENOISE_VARIANCE, group, [&] { e.L.launch_denoise_variance(a, tmp_di, tmp_gi, cur); });
             run(KS_DENOISE_WAVELET_12, group, [&] { e.L.launch_denoise_wavelet_12(a, 1.0f, 2.0f, tmp_di, di[1], di[0], tmp_gi, gi[1], gi[0], cur); });
             first = 2;
+            side_point(1u);
         } else run(KS_DENOISE_VARIANCE, ST_PASS_DENOISE_VARIANCE, [&] { e.L.launch_denoise_variance(a, a.di_diff_stash, a.gi_diff_stash, cur); });
         for (uint32_t nth = first; nth < 5; nth++) {
             if (nth == 4u && s.compose_in_wavelet) {
@@ -553,6 +561,7 @@ struct Frame {
                 continue;
             }
             run(KS_DENOISE_WAVELET, (uint64_t)ST_PASS_DENOISE_WAVELET_0 << nth, [&] { e.L.launch_denoise_wavelet(a, 1u << nth, (float)(1u + nth), di[in_ix[nth]], di[out_ix[nth]], gi[in_ix[nth]], gi[out_ix[nth]], cur); });
+            side_point(nth);   // 2: behind stride 4, 3: behind stride 8
         }
     }
     // The nodes' early launches (the node table's `early`), in chain order: they read this frame's planes that the NEXT frame's primary
@@ -579,6 +588,11 @@ struct Frame {
     //   DI head(N+1)   after prim(N+1)        (ev_di_head)
     //   DI tail(N+1)   after DI head(N+1)     (and after frame N's composition by stream order: its scratch aliases the denoiser's planes)
     //   denoiser(N+1)  after GI tail(N+1)
+    // StTuning::side_start = 1 ... 3 adds one wait in front of prim(N+1): for ev_lds_done(N), recorded on `stream` inside frame N's a-trous chain (denoise()
+    // side_point: behind strides 1+2, stride 4 or stride 8). That point is enqueued on `stream` later than ev_prim_ok(N), so the extra wait can only strengthen
+    // the order above. No cycle: `stream` waits for ev_di_head(N+1), recorded on `side` behind prim(N+1); `side` waits for ev_lds_done(N), which the previous
+    // render call enqueued completely, behind launches that wait for nothing of frame N+1. A frame that records no such point (no denoiser, the unfused
+    // a-trous chain, serial()) leaves have_lds_done clear, and the next frame starts behind ev_prim_ok alone, as with side_start = 0.
     int two_streams() {
         const StTuning& t = e.tuning;
         if (!c.side_stream) {
@@ -594,6 +608,8 @@ struct Frame {
         // follows a scene change gives up the prim(N+1) / denoiser(N) overlap
         if (int rc = e.reader_begin(c.side_stream, false)) return rc;  // the tick's uploads: independent of frame N, the overlap stays
         if (c.have_prev_frame_events) { if (int rc = c.ev_prim_ok.wait(c.side_stream)) return rc; }
+        if (c.have_prev_frame_events && c.have_lds_done) { if (int rc = c.ev_lds_done.wait(c.side_stream)) return rc; }
+        c.have_lds_done = false;   // this frame's denoise() sets it again
         cur = c.side_stream;
         prim();
         if (!t.di_head_on_main) di_head();
@@ -612,6 +628,7 @@ struct Frame {
         if (!reproject_later) { if (int rc = c.ev_prim_ok.record(stream)) return rc; }
         if (int rc = c.ev_gi_done.wait(stream)) return rc;
         denoise();
+        if (side_rc) return side_rc;
         if (reproject_later) { if (int rc = c.ev_prim_ok.record(stream)) return rc; }
         compose();
         if (int rc = c.ev_frame_done.record(stream)) return rc;
@@ -629,7 +646,8 @@ struct Frame {
         pack_early();
         denoise();
         compose();
-        // (a camera that has run the two-stream schedule: its next such frame waits for these)
+        // (a camera that has run the two-stream schedule: its next such frame waits for these — and for them alone: ev_prim_ok stands behind the whole chain here)
+        c.have_lds_done = false;
         if (c.side_stream) { if (int rc = c.ev_prim_ok.record(stream)) return rc; if (int rc = c.ev_frame_done.record(stream)) return rc; }
         return ST_OK;
     }
