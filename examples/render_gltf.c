@@ -6,7 +6,8 @@
  *   cc -std=c99 -D__HIP_PLATFORM_AMD__ -I include -I /opt/rocm/include examples/render_gltf.c \
  *      -L strolle_amd/csrc -lstrolle_hip -L /opt/rocm/lib -lamdhip64 -lm -Wl,-rpath,$PWD/strolle_amd/csrc -o render_gltf
  *   ./render_gltf scene.glb out.ppm [width height frames] [--env sky.hdr [intensity]]
- *                 [--tonemap none|reinhard|reinhard-lum|aces|neutral] [--exposure EV] [--auto-exposure]
+ *                 [--tonemap none|reinhard|reinhard-lum|aces|neutral] [--exposure EV] [--auto-exposure] [--normal-maps]
+ * --normal-maps turns normal mapping on (st_engine_set_normal_mapping): the materials' normalTexture bends the primary hits' normals.
  * --env lights the scene with an equirectangular Radiance .hdr map instead of the atmosphere (st_decode_hdr + st_environment_set).
  * --tonemap, --exposure and --auto-exposure set the camera's display transform (st_camera_set_display): without them the 8-bit output
  * clips every channel at 1, as before. With --auto-exposure, --exposure is the compensation in EV.
@@ -86,7 +87,7 @@ int main(int argc, char** argv) {
     float env_intensity = 1.0f;
     const char* pos[5] = {NULL, NULL, NULL, NULL, NULL};
     const char* tonemap_names[5] = {"none", "reinhard", "reinhard-lum", "aces", "neutral"};
-    int npos = 0, i, display = 0, tonemap = ST_TONEMAP_NONE, auto_exposure = 0;
+    int npos = 0, i, display = 0, tonemap = ST_TONEMAP_NONE, auto_exposure = 0, normal_maps = 0;
     float exposure_ev = 0.0f;
     for (i = 1; i < argc; i++) {
         if (strcmp(argv[i], "--tonemap") == 0 && i + 1 < argc) {
@@ -99,6 +100,8 @@ int main(int argc, char** argv) {
             exposure_ev = strtof(argv[++i], NULL); display = 1;
         } else if (strcmp(argv[i], "--auto-exposure") == 0) {
             auto_exposure = 1; display = 1;
+        } else if (strcmp(argv[i], "--normal-maps") == 0) {
+            normal_maps = 1;
         } else if (strcmp(argv[i], "--env") == 0 && i + 1 < argc) {
             env_path = argv[++i];
             if (i + 1 < argc) { char* end; const float v = strtof(argv[i + 1], &end); if (end != argv[i + 1] && *end == '\0') { env_intensity = v; i++; } }
@@ -106,7 +109,7 @@ int main(int argc, char** argv) {
     }
     if (npos < 2) {
         fprintf(stderr, "usage: %s scene.gltf|scene.glb out.ppm [width height frames] [--env sky.hdr [intensity]] "
-                        "[--tonemap none|reinhard|reinhard-lum|aces|neutral] [--exposure EV] [--auto-exposure]\n", argv[0]);
+                        "[--tonemap none|reinhard|reinhard-lum|aces|neutral] [--exposure EV] [--auto-exposure] [--normal-maps]\n", argv[0]);
         return 2;
     }
     const uint32_t width = npos > 2 ? (uint32_t)atoi(pos[2]) : 640u, height = npos > 3 ? (uint32_t)atoi(pos[3]) : 360u;
@@ -114,6 +117,7 @@ int main(int argc, char** argv) {
 
     StEngine* engine = NULL;
     CHECK(st_engine_create(0, &engine));
+    if (normal_maps) CHECK(st_engine_set_normal_mapping(engine, 1));                    /* off by default: the picture without the flag is unchanged */
 
     StGltfOptions options;
     memset(&options, 0, sizeof options);

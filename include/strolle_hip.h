@@ -264,8 +264,11 @@ typedef struct StRayHit {         /* 64 B */
     StHandle instance;                    /* the st_instance_insert handle */
     uint32_t hit; uint32_t _pad;          /* 1 = hit */
 } StRayHit;
-enum { ST_RAY_COHERENT = 1 };  /* the caller promises runs of 64 consecutive rays are coherent (camera-like): they are walked as one
+enum { ST_RAY_COHERENT = 1,    /* the caller promises runs of 64 consecutive rays are coherent (camera-like): they are walked as one
                                 * packet per wave. Correct for any rays; the flag changes only speed. */
+       ST_RAY_MAPPED_NORMAL = 2 }; /* StRayHit.normal is the normal bent by the material's normal map ("normal mapping" below: n'), whatever the
+                                * engine's switch says; every other field is as without the flag. st_scene_trace_rays_host takes no flags.
+                                * A host-only engine, which has nothing to map with, answers the bit as an unknown one (ST_ERR_INVALID_ARGUMENT). */
 int st_scene_trace_rays(StEngine* e, const StRay* rays_device, uint32_t count, StRayHit* hits_device, uint32_t flags, void* hip_stream);
 int st_scene_occluded(StEngine* e, const StRay* rays_device, uint32_t count, uint32_t* occluded_device, void* hip_stream);
 int st_camera_pick(StEngine* e, StHandle camera, const uint32_t* pixels_xy_device /* (x, y) pairs */, uint32_t count,
@@ -292,7 +295,8 @@ int st_scene_trace_rays_host(StEngine* e, const StRay* rays, uint32_t count, StR
 enum StAovKind {
     ST_AOV_DEPTH = 0,     /* f32:  distance from the camera ray's origin to the hit (the G-buffer's depth, d0.x); FLT_MAX on sky */
     ST_AOV_NORMAL = 1,    /* f32x4: shading normal as StRayHit.normal (xyz), w = 0; 0 on sky. Like DEPTH and MOTION it comes from the primary hit as the
-                           * frame resolved it: in the fast build that is the exact arithmetic of primary visibility, an ulp from st_camera_pick's */
+                           * frame resolved it: in the fast build that is the exact arithmetic of primary visibility, an ulp from st_camera_pick's;
+                           * with st_engine_set_normal_mapping on it is the mapped normal ("normal mapping") */
     ST_AOV_ALBEDO = 2,    /* f32x4: linear base colour at the hit's uv, texture applied (what primary visibility samples), alpha in w; 0 on sky */
     ST_AOV_MOTION = 3,    /* f32x2: the renderer's velocity (current minus previous screen position in pixels, instance motion included;
                            * 0 where its squared length is below 0.001, as the velocity plane); 0 on sky */
@@ -360,6 +364,44 @@ int st_engine_get_deformation_motion(StEngine* e, int* enabled);
 /* What the last st_tick left: the instances whose hits take the deformation term in the frames after it, and the device memory the
  * second regions of the posed store hold. 0 / 0 while the switch is off. A host-only engine is ST_ERR_NO_DEVICE. */
 int st_debug_deformation(StEngine* e, uint64_t* instances_with_previous, uint64_t* previous_bytes);
+
+/* ---- normal mapping (NEW seam): StMaterial.normal_map_texture bends the normal of PRIMARY hits (st_traverse.h normal_map_apply).
+ * OFF by default (st_engine_set_normal_mapping). Off — and on, while no material's normal_map_texture resolves to a live image — every
+ * frame, AOV, pick and query is what it was before the seam existed, bit for bit: the launches get the same null argument.
+ * - When it takes effect: the switch with the next st_render_camera, st_camera_render_aovs, st_camera_pick or query; a material's map, or
+ *   an image that is inserted or removed, with the next st_tick like any scene edit.
+ * - Where it applies: primary visibility (the G-buffer's normal, the surface planes the denoiser's edge-stopping and the reprojection read —
+ *   they must carry the mapped normal, or the denoiser blurs the bump shading away), ST_AOV_NORMAL and st_camera_pick follow the switch;
+ *   st_scene_trace_rays follows ST_RAY_MAPPED_NORMAL and not the switch.
+ * - Out of scope: the hits of GI bounce rays, ST_MODE_REFERENCE and heatmap frames, shadow rays, a per-material normal scale (glTF's
+ *   normalTexture.scale is ignored), and vertex tangents.
+ * - The tangent frame is DERIVED from the winning triangle's world-space edges and uv corners — the frame three.js and the glTF sample
+ *   viewer use for a mesh without tangents. StMeshTriangle.tangents stay unused. The device keeps edges and uv corners current under every
+ *   refresh mode, skinning and morphing, so mapped normals follow deforming meshes at no extra store. Because supplied (MikkTSpace)
+ *   tangents are ignored, a map baked against them can show faint seams.
+ * - The texel: bilinear over the image, with the wrap, rectangle mapping, texel centres and clamp of every other texture; each byte decodes
+ *   as byte / 255. The sRGB curve is never applied to a normal map (st_image_insert_rgba8's `srgb` argument is ignored, as everywhere).
+ * - The definition, float32, no fused multiply-add, the same operations in both arithmetic builds. n: the hit's resolved normal (facing the
+ *   ray); s = copysign(1, 1/det), the flip that made it face the ray, so nf = s n is the front normal; uv: the hit's uv; e1, e2: the
+ *   triangle's world-space edges p1 - p0, p2 - p0; uv0..uv2 its uv corners; R the map's atlas rectangle.
+ *       (du1, dv1) = uv1 - uv0   (du2, dv2) = uv2 - uv0   d = du1 dv2 - du2 dv1
+ *       Pu = (e1 dv2 - e2 dv1) / d          Pv = (e2 du1 - e1 du2) / d
+ *       T  = normalize(Pu - nf (nf . Pu))   C = nf x T
+ *       h  = (C . Pv <= 0) ? +1 : -1        B = h C          (glTF's v runs down the image: an unmirrored layout has h = +1)
+ *       m  = the texel at uv                t = (2 m.x - 1, 2 m.y - 1, max(2 m.z - 1, 0))   (a texel pointing below the tangent plane is flattened onto it)
+ *       n' = s normalize(t.x T + t.y B + t.z nf)
+ *   normalize(v) is v * (1 / sqrt(v . v)); a dot product is ((x x + y y) + z z). n' is n itself, with identical bits, where R is zero (no
+ *   map, or a handle whose image is gone) or where |d| lies outside [1e-30, FLT_MAX] or |Pu - nf (nf . Pu)| or the last length outside [1e-18, 1e18] (zero and
+ *   not-finite values included: a length's bounds keep its square inside float32's normal range).
+ *   Pinned by hand: a quad in the xy-plane facing +z with u along +x and v along -y — texel (255, 128, 128) tilts the normal towards +x,
+ *   texel (128, 255, 128) towards +y.
+ * - Cost: off, one scalar test of a null kernel argument. On, per primary hit the material's rectangle; per mapped hit two 16-B edge records,
+ *   the triangle's attribute record again and four atlas texels. A scene copy whose tree the host built under a mode that keeps no edge
+ *   records on the device (ST_BVH_REBUILD, ST_BVH_REFIT, and ST_BVH_AUTO while the host's tree is in use) gets them with st_tick's own
+ *   upload while the switch is on and a material has a map: no host join. Where the switch, or a query with ST_RAY_MAPPED_NORMAL, comes
+ *   after that tick, the first call that maps normals sends them once and joins its stream. */
+int st_engine_set_normal_mapping(StEngine* e, int enabled);   /* host work: valid on a host-only engine */
+int st_engine_get_normal_mapping(StEngine* e, int* enabled);
 
 /* ---- morph targets (NEW seam): per-instance blend-shape weights applied on the device (k_skin.hip k_morph; glTF `targets` / `weights`).
  * Targets belong to a mesh, weights to an instance: instances share a morphed mesh and each carries weights of its own (Bevy's

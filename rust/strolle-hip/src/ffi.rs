@@ -136,6 +136,10 @@ pub struct StDistUniqueId {
 
 pub enum StEngine {}
 
+// st_scene_trace_rays flags
+pub const ST_RAY_COHERENT: u32 = 1;
+pub const ST_RAY_MAPPED_NORMAL: u32 = 2; // StRayHit.normal bent by the material's normal map
+
 extern "C" {
     pub fn st_engine_create(device_ordinal: i32, out: *mut *mut StEngine) -> i32; // Engine::new
     pub fn st_engine_destroy(e: *mut StEngine); // Drop
@@ -245,6 +249,8 @@ extern "C" {
 extern "C" {
     pub fn st_engine_set_deformation_motion(e: *mut StEngine, enabled: i32) -> i32;
     pub fn st_engine_get_deformation_motion(e: *mut StEngine, enabled: *mut i32) -> i32;
+    pub fn st_engine_set_normal_mapping(e: *mut StEngine, enabled: i32) -> i32;
+    pub fn st_engine_get_normal_mapping(e: *mut StEngine, enabled: *mut i32) -> i32;
     pub fn st_debug_deformation(e: *mut StEngine, instances_with_previous: *mut u64, previous_bytes: *mut u64) -> i32;
 }
 

@@ -397,6 +397,12 @@ where
         check(unsafe { ffi::st_engine_set_deformation_motion(self.raw, enabled as i32) });
     }
 
+    /// Not part of the reference's API: primary hits take the normal bent by the material's `normal_map_texture` (off by default; the tangent
+    /// frame is derived from the triangle, vertex tangents are not used). Takes effect with the next `render_camera`.
+    pub fn set_normal_mapping(&mut self, enabled: bool) {
+        check(unsafe { ffi::st_engine_set_normal_mapping(self.raw, enabled as i32) });
+    }
+
     /// Not part of the reference's API: the morph targets of a mesh (glTF `targets`; Bevy's `MorphTargetImage` unpacked). `deltas` holds
     /// `target_count` runs of one `StMorphDelta` per corner of the mesh as it was inserted (3 per triangle). Replaces earlier targets and
     /// drops the weights of the mesh's instances.

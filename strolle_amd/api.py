@@ -387,6 +387,7 @@ RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_max", "<f4"), ("direction", "
 HIT_DTYPE = np.dtype([("point", "<f4", (3,)), ("t", "<f4"), ("normal", "<f4", (3,)), ("triangle", "<u4"), ("uv", "<f4", (2,)),
                       ("barycentric", "<f4", (2,)), ("instance", "<u8"), ("hit", "<u4"), ("_pad", "<u4")])
 RAY_COHERENT = 1   # ST_RAY_COHERENT
+RAY_MAPPED_NORMAL = 2   # ST_RAY_MAPPED_NORMAL
 
 
 class Aov(enum.IntEnum):
@@ -723,6 +724,9 @@ class _Binding:
             self.engine_set_deformation_motion = fn("engine_set_deformation_motion", [vp, i32])
             self.engine_get_deformation_motion = fn("engine_get_deformation_motion", [vp, P(i32)])
             self.debug_deformation = fn("debug_deformation", [vp, P(u64), P(u64)])
+        if hasattr(lib, prefix + "engine_set_normal_mapping"):   # normal mapping (likewise)
+            self.engine_set_normal_mapping = fn("engine_set_normal_mapping", [vp, i32])
+            self.engine_get_normal_mapping = fn("engine_get_normal_mapping", [vp, P(i32)])
         if has_device:
             self.camera_set_rows = fn("camera_set_rows", [vp, u64, u32, u32])
             self.camera_set_output_format = fn("camera_set_output_format", [vp, u64, i32])
@@ -1075,10 +1079,12 @@ class Engine(EngineBase):
         self._check(self._b.render_camera(self._h, handle, out_device_ptr, stream))
 
     # ---- scene queries (include/strolle_hip.h "scene queries"): the scene of the last tick, enqueued on `stream`
-    def trace_rays(self, rays_ptr: int, count: int, hits_ptr: int, coherent: bool = False, stream: int = 0):
+    def trace_rays(self, rays_ptr: int, count: int, hits_ptr: int, coherent: bool = False, stream: int = 0, mapped_normal: bool = False):
         """st_scene_trace_rays: `count` StRay at device address `rays_ptr` -> StRayHit at `hits_ptr` (closest hits).
-        coherent=True: ST_RAY_COHERENT (runs of 64 rays are camera-like; changes only speed)."""
-        self._check(self._b.scene_trace_rays(self._h, rays_ptr, count, hits_ptr, RAY_COHERENT if coherent else 0, stream))
+        coherent=True: ST_RAY_COHERENT (runs of 64 rays are camera-like; changes only speed).
+        mapped_normal=True: ST_RAY_MAPPED_NORMAL (StRayHit.normal bent by the material's normal map, whatever the engine's switch says)."""
+        flags = (RAY_COHERENT if coherent else 0) | (RAY_MAPPED_NORMAL if mapped_normal else 0)
+        self._check(self._b.scene_trace_rays(self._h, rays_ptr, count, hits_ptr, flags, stream))
 
     def occluded(self, rays_ptr: int, count: int, out_ptr: int, stream: int = 0):
         """st_scene_occluded: one uint32 per ray at `out_ptr`, 1 where some triangle is hit at 0 < t < t_max."""
@@ -1156,6 +1162,17 @@ class Engine(EngineBase):
         """st_engine_get_deformation_motion."""
         on = C.c_int()
         self._check(self._b.engine_get_deformation_motion(self._h, C.byref(on)))
+        return bool(on.value)
+
+    # ---- normal mapping (include/strolle_hip.h "normal mapping"): takes effect with the next render, AOV, pick or query call
+    def set_normal_mapping(self, enabled: bool):
+        """st_engine_set_normal_mapping: primary hits, the NORMAL AOV and picks take the normal bent by the material's normal map."""
+        self._check(self._b.engine_set_normal_mapping(self._h, 1 if enabled else 0))
+
+    def get_normal_mapping(self) -> bool:
+        """st_engine_get_normal_mapping."""
+        on = C.c_int()
+        self._check(self._b.engine_get_normal_mapping(self._h, C.byref(on)))
         return bool(on.value)
 
     def deformation_stats(self):

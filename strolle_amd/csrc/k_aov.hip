@@ -12,7 +12,7 @@ namespace ST_KNS {
 // The planes are width x height, row-major; only owned pixels are written.
 template <bool LDS_SCENE, class SE>
 __global__ ST_KERNEL_BOUNDS void k_aov(const KArgs a_in, float* depth, float4* normal, float4* albedo, float2* motion, uint64_t* instance,
-                                       uint32_t* triangle, const uint4* table, const float* deform_posed) {
+                                       uint32_t* triangle, const uint4* table, const float* deform_posed, const float4* nm_tri_geo) {
     ST_QUERY_PROLOGUE
     ST_STACK_LDS(SE, lds);
     U2 pos;
@@ -31,7 +31,11 @@ __global__ ST_KERNEL_BOUNDS void k_aov(const KArgs a_in, float* depth, float4* n
 #endif
     const size_t i = (size_t)pos.y * a.width + pos.x;
     if (depth) depth[i] = any ? distance(ray.origin, h.point) : kF32Max;   // the G-buffer's d0.x (k_prim_visibility g.depth)
-    if (normal) normal[i] = any ? make_float4(h.normal.x, h.normal.y, h.normal.z, 0.0f) : f4z();
+    if (normal) {   // "the normal as the frame resolved it": mapped where the frame's is (nm_tri_geo is null while normal mapping is not active, as in k_prim_visibility)
+        V3 n = h.normal;
+        if (any && nm_tri_geo != nullptr) n = normal_map_apply(a, nm_tri_geo, c.tri, h.material_id, c.inv_det, h.uv, n);
+        normal[i] = any ? make_float4(n.x, n.y, n.z, 0.0f) : f4z();
+    }
     if (albedo) {
         float4 base = f4z();
         if (any) {
@@ -60,8 +64,8 @@ __global__ ST_KERNEL_BOUNDS void k_aov(const KArgs a_in, float* depth, float4* n
 }
 
 void launch_aov(const KArgs& a, float* depth, float4* normal, float4* albedo, float2* motion, uint64_t* instance, uint32_t* triangle, const uint4* table,
-                const float* deform_posed, hipStream_t s) {
-    ST_LAUNCH_TRACE(k_aov, (), false, s, a, depth, normal, albedo, motion, instance, triangle, table, deform_posed);
+                const float* deform_posed, const float4* nm_tri_geo, hipStream_t s) {
+    ST_LAUNCH_TRACE(k_aov, (), false, s, a, depth, normal, albedo, motion, instance, triangle, table, deform_posed, nm_tri_geo);
 }
 
 }  // namespace ST_KNS

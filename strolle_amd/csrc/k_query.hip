@@ -32,7 +32,7 @@ ST_D void store_hit(float4* hits, uint32_t i, const TriangleHit& h, const Candid
 // contract stream; `packets` (ST_RAY_COHERENT, wide stream present): the wave walks its 64 rays as one packet. Exact build: the contract walk.
 // The walks are unbounded; a hit at t >= t_max is a miss, which is exactly the closest hit of the bounded ray.
 template <bool LDS_SCENE, class SE>
-__global__ ST_KERNEL_BOUNDS void k_query_closest(const KArgs a_in, const float4* rays, uint32_t count, float4* hits, const uint4* table, uint32_t packets) {
+__global__ ST_KERNEL_BOUNDS void k_query_closest(const KArgs a_in, const float4* rays, uint32_t count, float4* hits, const uint4* table, uint32_t packets, const float4* nm_tri_geo) {
     ST_QUERY_PROLOGUE
     ST_STACK_LDS(SE, lds);
     const uint32_t i = blockIdx.x * (uint32_t)kBlockThreads + threadIdx.x;
@@ -46,9 +46,12 @@ __global__ ST_KERNEL_BOUNDS void k_query_closest(const KArgs a_in, const float4*
         ST_CLOSEST_WALK(true, false, a, ray, lane_stack(a, lds), !LDS_SCENE && packets && a.bvh_w != nullptr, &c, any, used);
     }
     const bool hit = any && c.t < ray.len;
-    store_hit(hits, i, closest_resolve(a, ray, c, hit), c, hit, table);
+    TriangleHit h = closest_resolve(a, ray, c, hit);
+    // ST_RAY_MAPPED_NORMAL (nm_tri_geo is null without the flag): StRayHit::normal bent by the material's map, every other field as without it
+    if (hit && nm_tri_geo != nullptr) h.normal = normal_map_apply(a, nm_tri_geo, c.tri, h.material_id, c.inv_det, h.uv, h.normal);
+    store_hit(hits, i, h, c, hit, table);
 }
-void launch_query_closest(const KArgs& a, const float4* rays, uint32_t count, float4* hits, const uint4* table, uint32_t packets, hipStream_t s);
+void launch_query_closest(const KArgs& a, const float4* rays, uint32_t count, float4* hits, const uint4* table, uint32_t packets, const float4* nm_tri_geo, hipStream_t s);
 
 // Occlusion: the shadow rays' any-hit walk (trace_any: wide / compact / fast contract loop in the fast build, traverse<true> in exact) with len = t_max.
 template <bool LDS_SCENE, class SE>
@@ -68,7 +71,7 @@ __global__ ST_KERNEL_BOUNDS void k_query_occluded(const KArgs a_in, const float4
 // otherwise trace_closest's choice of stream), so a pick carries the bits of REF_HITS at that pixel. KArgs::cam / width / height: the camera as
 // its last frame saw it (st_query.cpp).
 template <bool LDS_SCENE, class SE>
-__global__ ST_KERNEL_BOUNDS void k_query_pick(const KArgs a_in, const uint32_t* pixels, uint32_t count, float4* hits, const uint4* table) {
+__global__ ST_KERNEL_BOUNDS void k_query_pick(const KArgs a_in, const uint32_t* pixels, uint32_t count, float4* hits, const uint4* table, const float4* nm_tri_geo) {
     ST_QUERY_PROLOGUE
     ST_STACK_LDS(SE, lds);
     const uint32_t i = blockIdx.x * (uint32_t)kBlockThreads + threadIdx.x;
@@ -81,7 +84,9 @@ __global__ ST_KERNEL_BOUNDS void k_query_pick(const KArgs a_in, const uint32_t* 
         // k_ref_tracing's depth 0, whose bits a pick owes: trace_closest's fast leaf test and ablation switch, the packet where the frame's primary rays take it
         ST_CLOSEST_WALK(false, true, a, ray, lane_stack(a, lds), !LDS_SCENE && a.bvh_w != nullptr && a.primary_packets, &c, any, used);
     }
-    store_hit(hits, i, closest_resolve(a, ray, c, any), c, any, table);
+    TriangleHit h = closest_resolve(a, ray, c, any);
+    if (any && nm_tri_geo != nullptr) h.normal = normal_map_apply(a, nm_tri_geo, c.tri, h.material_id, c.inv_det, h.uv, h.normal);   // a pick matches the frame on screen: mapped while normal mapping is active
+    store_hit(hits, i, h, c, any, table);
 }
 
 // grid ceil(count / 256); the scene picks the instantiation as ST_LAUNCH_TRACE does, the stack is the frame launches' (stack_lds_bytes)
@@ -94,14 +99,14 @@ __global__ ST_KERNEL_BOUNDS void k_query_pick(const KArgs a_in, const uint32_t* 
         else ST_KLAUNCH_SMEM((kernel_tmpl<false, uint32_t>), grid_, dim3(kBlockThreads), stack_lds_bytes(a, 4), stream, __VA_ARGS__);                            \
     } while (0)
 
-void launch_query_closest(const KArgs& a, const float4* rays, uint32_t count, float4* hits, const uint4* table, uint32_t packets, hipStream_t s) {
-    ST_QUERY_LAUNCH(k_query_closest, count, s, a, rays, count, hits, table, packets);
+void launch_query_closest(const KArgs& a, const float4* rays, uint32_t count, float4* hits, const uint4* table, uint32_t packets, const float4* nm_tri_geo, hipStream_t s) {
+    ST_QUERY_LAUNCH(k_query_closest, count, s, a, rays, count, hits, table, packets, nm_tri_geo);
 }
 void launch_query_occluded(const KArgs& a, const float4* rays, uint32_t count, uint32_t* occluded, hipStream_t s) {
     ST_QUERY_LAUNCH(k_query_occluded, count, s, a, rays, count, occluded);
 }
-void launch_query_pick(const KArgs& a, const uint32_t* pixels, uint32_t count, float4* hits, const uint4* table, hipStream_t s) {
-    ST_QUERY_LAUNCH(k_query_pick, count, s, a, pixels, count, hits, table);
+void launch_query_pick(const KArgs& a, const uint32_t* pixels, uint32_t count, float4* hits, const uint4* table, const float4* nm_tri_geo, hipStream_t s) {
+    ST_QUERY_LAUNCH(k_query_pick, count, s, a, pixels, count, hits, table, nm_tri_geo);
 }
 
 }  // namespace ST_KNS

@@ -164,7 +164,7 @@ ST_D void frame_reprojection_pixel(const KArgs& a, U2 pos, const Surface& surfac
 // REPROJECT: frame_reprojection runs in the same kernel (it needs this pixel's new surface + velocity and the PREVIOUS
 // frame's surfaces only).
 template <bool LDS_SCENE, bool REPROJECT, class SE>
-__global__ ST_KERNEL_BOUNDS void k_prim_visibility(const KArgs a_in, const uint4* deform_table, const float* deform_posed) {
+__global__ ST_KERNEL_BOUNDS void k_prim_visibility(const KArgs a_in, const uint4* deform_table, const float* deform_posed, const float4* nm_tri_geo) {
     ST_SCENE_PROLOGUE
     ST_STACK_LDS(SE, lds);
     uint32_t used_ = 0u;
@@ -197,6 +197,10 @@ __global__ ST_KERNEL_BOUNDS void k_prim_visibility(const KArgs a_in, const uint4
         if (REPROJECT) tex_write(a.reprojection, a, pos, f4z());
         return;
     }
+    // normal mapping (st_traverse.h normal_map_apply; one scalar test of a kernel argument, null while the feature is not active — an argument for deform_posed's
+    // reason below): from here on the mapped normal IS the hit's — the G-buffer's code, the surface planes (SVGF's edge-stopping reads them: fed the
+    // geometric normal it would blur the bumps out of the demodulated irradiance) and the reprojection's surface
+    if (nm_tri_geo != nullptr) hit.normal = normal_map_apply(a, nm_tri_geo, c.tri, hit.material_id, c.inv_det, hit.uv, hit.normal);
     const GpuMaterial material = a.materials[hit.material_id];
     const float4 mr = sample_atlas(a, hit.uv, make_float4(1.0f, material.roughness, material.metallic, 1.0f), material.metallic_roughness_texture);
     GBuffer g;
@@ -233,8 +237,8 @@ __global__ ST_KERNEL_BOUNDS void k_prim_visibility(const KArgs a_in, const uint4
         frame_reprojection_pixel(a, pos, surface, moving ? velocity : v2(0.0f, 0.0f));
     }
 }
-void launch_prim_visibility(const KArgs& a, bool reproject, const uint4* deform_table, const float* deform_posed, hipStream_t s) {
-    if (reproject) ST_LAUNCH_TRACE(k_prim_visibility, (true), false, s, a, deform_table, deform_posed); else ST_LAUNCH_TRACE(k_prim_visibility, (false), false, s, a, deform_table, deform_posed);
+void launch_prim_visibility(const KArgs& a, bool reproject, const uint4* deform_table, const float* deform_posed, const float4* nm_tri_geo, hipStream_t s) {
+    if (reproject) ST_LAUNCH_TRACE(k_prim_visibility, (true), false, s, a, deform_table, deform_posed, nm_tri_geo); else ST_LAUNCH_TRACE(k_prim_visibility, (false), false, s, a, deform_table, deform_posed, nm_tri_geo);
 }
 
 // Tabulates the byte decodes of st_device.h with the routines themselves (one launch at engine creation).

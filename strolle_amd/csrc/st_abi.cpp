@@ -225,6 +225,9 @@ int st_debug_morphing(StEngine* e, uint64_t* ticks, uint64_t* triangles, uint64_
 }
 int st_engine_set_deformation_motion(StEngine* e, int enabled) { ST_REQUIRE(e, "null engine"); E(e)->deform.motion_on = enabled != 0; return ST_OK; }
 int st_engine_get_deformation_motion(StEngine* e, int* enabled) { ST_REQUIRE(e && enabled, "null argument"); *enabled = E(e)->deform.motion_on ? 1 : 0; return ST_OK; }
+// normal mapping (st_engine.h normal_map_geo): only a flag, so a host-only engine takes it too
+int st_engine_set_normal_mapping(StEngine* e, int enabled) { ST_REQUIRE(e, "null engine"); E(e)->normal_mapping = enabled != 0; return ST_OK; }
+int st_engine_get_normal_mapping(StEngine* e, int* enabled) { ST_REQUIRE(e && enabled, "null argument"); *enabled = E(e)->normal_mapping ? 1 : 0; return ST_OK; }
 int st_debug_deformation(StEngine* e, uint64_t* instances_with_previous, uint64_t* previous_bytes) {
     ST_REQUIRE(e && instances_with_previous && previous_bytes, "null argument");
     return E(e)->deform.deformation_stats(instances_with_previous, previous_bytes);
@@ -498,7 +501,9 @@ int st_render_camera(StEngine* e, StHandle h, void* out, void* stream) {
 // ---- scene queries (st_query.cpp): argument checks first, so that a host-only engine answers them too
 int st_scene_trace_rays(StEngine* e, const StRay* rays, uint32_t count, StRayHit* hits, uint32_t flags, void* stream) {
     ST_REQUIRE(e, "null engine");
-    ST_REQUIRE((flags & ~(uint32_t)ST_RAY_COHERENT) == 0u, "unknown flag bits");
+    // ST_RAY_MAPPED_NORMAL is a bit only an engine with a device knows: a host-only engine has no records to map with and keeps answering it as it did before the flag existed
+    const uint32_t known = ST_RAY_COHERENT | (E(e)->has_device ? (uint32_t)ST_RAY_MAPPED_NORMAL : 0u);
+    ST_REQUIRE((flags & ~known) == 0u, "unknown flag bits");
     if (count == 0u) return ST_OK;
     ST_REQUIRE(rays && hits, "null argument");
     return E(e)->trace_rays(rays, count, hits, flags, static_cast<hipStream_t>(stream));

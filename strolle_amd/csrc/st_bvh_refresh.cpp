@@ -475,6 +475,8 @@ int SceneTree::write(SceneSet& set, TreePlan plan, hipStream_t up, bool* pageabl
         if ((rc = refresh_compact_stream(t, up))) return rc;   // the shadow rays' compact form follows every change of the contract stream
         if ((rc = refresh_wide_stream(t, up, !device_path, pageable))) return rc;   // and so does the wide form (its topology only when the tree itself was sent)
     }
+    // the hit-test records per slot are on this copy where the device builds, bakes or refits from them; a host tree under any other mode sent only its leaf entries
+    set.geo_current = build_now || device_refit_possible();
     return ST_OK;
 }
 int SceneTree::report_too_deep() {

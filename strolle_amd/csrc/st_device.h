@@ -259,13 +259,18 @@ ST_D float gamma8_eval(uint32_t v) { return pow_poly_((float)v / 255.0f, 2.2f); 
 ST_D float gamma6_eval(uint32_t v) { return pow_poly_((float)v / 63.0f, 2.2f); }   // ... and its 6-bit alpha
 ST_D float srgb_to_linear(const KArgs& a, uint32_t v) { return a.byte_luts[kLutSrgb + v]; }
 ST_D float unorm8(const KArgs& a, uint32_t v) { return a.byte_luts[kLutUnorm8 + v]; }
+// SRGB: a colour texture's texel (RGB through the sRGB curve). !SRGB: a normal map's (include/strolle_hip.h "normal mapping"): the bytes are a
+// direction, not a colour, and all decode as byte / 255. One definition of the clamp, the texel centres and the order of the bilinear blend for both.
+template <bool SRGB>
 ST_D float4 atlas_texel(const KArgs& a, int32_t x, int32_t y) {
     x = x < 0 ? 0 : (x >= (int32_t)a.atlas_w ? (int32_t)a.atlas_w - 1 : x);
     y = y < 0 ? 0 : (y >= (int32_t)a.atlas_h ? (int32_t)a.atlas_h - 1 : y);
     const uchar4 p = a.atlas[(uint32_t)y * a.atlas_w + (uint32_t)x];
+    if (!SRGB) return make_float4(unorm8(a, p.x), unorm8(a, p.y), unorm8(a, p.z), unorm8(a, p.w));
     return make_float4(srgb_to_linear(a, p.x), srgb_to_linear(a, p.y), srgb_to_linear(a, p.z), unorm8(a, p.w));
 }
 // gfx950 has no texture unit: bilinear, clamp-to-edge, lod 0, sRGB decode before filtering; NaN coordinates -> 0.
+template <bool SRGB = true>
 ST_D float4 atlas_sample(const KArgs& a, V2 uv) {
     if (a.atlas_w == 0u) return f4z();
     if (uv.x != uv.x) uv.x = 0.0f;
@@ -274,7 +279,7 @@ ST_D float4 atlas_sample(const KArgs& a, V2 uv) {
     const float x0 = floorf(fx), y0 = floorf(fy);
     const float tx = fx - x0, ty = fy - y0;
     const int32_t ix = f2i_sat(x0), iy = f2i_sat(y0);
-    const float4 p00 = atlas_texel(a, ix, iy), p10 = atlas_texel(a, ix + 1, iy), p01 = atlas_texel(a, ix, iy + 1), p11 = atlas_texel(a, ix + 1, iy + 1);
+    const float4 p00 = atlas_texel<SRGB>(a, ix, iy), p10 = atlas_texel<SRGB>(a, ix + 1, iy), p01 = atlas_texel<SRGB>(a, ix, iy + 1), p11 = atlas_texel<SRGB>(a, ix + 1, iy + 1);
     const float4 top = xe::add4(p00, xe::scale4(xe::sub4(p10, p00), tx));
     const float4 bot = xe::add4(p01, xe::scale4(xe::sub4(p11, p01), tx));
     return xe::add4(top, xe::scale4(xe::sub4(bot, top), ty));
@@ -284,13 +289,18 @@ ST_D float4 atlas_sample(const KArgs& a, V2 uv) {
 // divergent branches, six times per textured hit.
 ST_D float fmod1_nonneg(float x) { return x - floorf(x); }
 ST_D float mat_wrap(float t) { return t > 0.0f ? fmod1_nonneg(t) : 1.0f - fmod1_nonneg(-t); }
-ST_D float4 sample_atlas(const KArgs& a, V2 hit_uv, float4 multiplier, float4 texture) {
-    if (is_zero(texture)) return multiplier;
+// where hit_uv falls in the atlas: the wrap, then the texture's rectangle
+ST_D V2 atlas_uv(V2 hit_uv, float4 texture) {
     hit_uv.x = mat_wrap(hit_uv.x);
     hit_uv.y = mat_wrap(hit_uv.y);
-    const V2 uv = v2(texture.x + hit_uv.x * texture.z, texture.y + hit_uv.y * texture.w);
-    return xe::mul4(multiplier, atlas_sample(a, uv));
+    return v2(texture.x + hit_uv.x * texture.z, texture.y + hit_uv.y * texture.w);
 }
+ST_D float4 sample_atlas(const KArgs& a, V2 hit_uv, float4 multiplier, float4 texture) {
+    if (is_zero(texture)) return multiplier;
+    return xe::mul4(multiplier, atlas_sample(a, atlas_uv(hit_uv, texture)));
+}
+// the normal map's texel at hit_uv; the caller has tested that `texture` is not zero
+ST_D V3 sample_normal_map(const KArgs& a, V2 hit_uv, float4 texture) { return xyz(atlas_sample<false>(a, atlas_uv(hit_uv, texture))); }
 #if defined(ST_FAST_MATH)
 #pragma clang fp contract(fast)
 #endif

@@ -468,6 +468,7 @@ struct SceneSet {
     TreeCopy tree;   // the tree's half (st_bvh_refresh.h): the streams, the refit's index arrays, the device builder's scratch
     // per triangle slot the hit-test record and the bounds (ST_BVH_REFIT_DEVICE, ST_BVH_BUILD_DEVICE: k_bvh.hip and k_lbvh.hip read them)
     DeviceArray tri_geo, tri_bounds;
+    bool geo_current = false;   // tri_geo holds the hit-test record of every slot as this copy's tree has it (SceneTree::write); a host-tree path sends none — normal mapping asks (Engine::normal_map_geo)
     size_t dirty_lo = SIZE_MAX, dirty_hi = 0; bool tri_full = true;  // what this copy lacks of the host's triangle arrays
     std::vector<uint64_t> pending_moves;   // instances moved on the device whose current transform this copy has not baked yet
     DeviceArray bake_jobs, bake_starts;
@@ -781,6 +782,11 @@ struct Engine {
     int shafts_process(const StLightShaftsDesc* desc, const StDisplayDesc* display, const float* transform, const float* projection, const void* color, const void* depth,
                        uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
     FencedPlanes<1> shafts_scratch;   // st_light_shafts_process's cell plane: grown, never shrunk
+    // Normal mapping (include/strolle_hip.h "normal mapping"; st_traverse.h normal_map_apply). `normal_mapping` is the switch; any_normal_map: some material's
+    // normal_map_texture resolved to an atlas rectangle at the last st_tick (rebuild_gpu_materials). normal_map_geo: the argument primary visibility, the NORMAL AOV and
+    // picks get (`flagged`: a query with ST_RAY_MAPPED_NORMAL, which does not ask the switch) — the live copy's hit-test records, or null where nothing can be mapped.
+    bool normal_mapping = false, any_normal_map = false;
+    int normal_map_geo(hipStream_t stream, bool flagged, const float4** geo);
     int scene_args(KArgs& a, bool heatmap) const;   // the scene half of KArgs (st_render.cpp): render() and the scene queries
     void light_args(KArgs& a) const;                // its lights, LUT and environment half: render()
 

@@ -8,7 +8,7 @@ ST_LAUNCHER(launch_atmosphere_sky, (const float4* transmittance_lut, const float
 ST_LAUNCHER(launch_bvh_heatmap, (const KArgs& a, hipStream_t s))
 ST_LAUNCHER(launch_ref_tracing, (const KArgs& a, uint32_t depth, hipStream_t s))
 ST_LAUNCHER(launch_ref_shading, (const KArgs& a, uint32_t seed, uint32_t depth, hipStream_t s))
-ST_LAUNCHER(launch_prim_visibility, (const KArgs& a, bool fuse_frame_reprojection, const uint4* deform_table, const float* deform_posed, hipStream_t s))
+ST_LAUNCHER(launch_prim_visibility, (const KArgs& a, bool fuse_frame_reprojection, const uint4* deform_table, const float* deform_posed, const float4* nm_tri_geo, hipStream_t s))
 ST_LAUNCHER(launch_build_byte_luts, (float* out /* kByteLutFloats */, hipStream_t s))  // st_device.h byte decode tables
 ST_LAUNCHER(launch_frame_reprojection, (const KArgs& a, hipStream_t s))
 // ReSTIR DI
@@ -66,11 +66,11 @@ ST_LAUNCHER(launch_bvh_compact, (const float4* bvh, uint32_t n_entries, float4* 
 ST_LAUNCHER(launch_bvh_wide, (const float4* bvh, const uint32_t* topo, uint32_t n_nodes, const uint32_t* leaf_entry, uint32_t n_leaves, uint32_t links16, float4* nodes, float4* leaves, hipStream_t s))
 // scene queries (k_query.hip; st_query.cpp): one ray per lane, 256 per block. rays: 2 float4 per StRay; hits: 4 float4 per StRayHit;
 // table: per instance slot {StHandle lo, hi, first triangle slot, 0}; pixels: (x, y) pairs
-ST_LAUNCHER(launch_query_closest, (const KArgs& a, const float4* rays, uint32_t count, float4* hits, const uint4* table, uint32_t packets, hipStream_t s))
+ST_LAUNCHER(launch_query_closest, (const KArgs& a, const float4* rays, uint32_t count, float4* hits, const uint4* table, uint32_t packets, const float4* nm_tri_geo, hipStream_t s))
 ST_LAUNCHER(launch_query_occluded, (const KArgs& a, const float4* rays, uint32_t count, uint32_t* occluded, hipStream_t s))
-ST_LAUNCHER(launch_query_pick, (const KArgs& a, const uint32_t* pixels, uint32_t count, float4* hits, const uint4* table, hipStream_t s))
+ST_LAUNCHER(launch_query_pick, (const KArgs& a, const uint32_t* pixels, uint32_t count, float4* hits, const uint4* table, const float4* nm_tri_geo, hipStream_t s))
 // per-pixel AOVs (k_aov.hip; st_aov.cpp): over the window's 8x8 tiles like the frame's passes; each plane width x height, nullptr = not requested
-ST_LAUNCHER(launch_aov, (const KArgs& a, float* depth, float4* normal, float4* albedo, float2* motion, uint64_t* instance, uint32_t* triangle, const uint4* table, const float* deform_posed, hipStream_t s))
+ST_LAUNCHER(launch_aov, (const KArgs& a, float* depth, float4* normal, float4* albedo, float2* motion, uint64_t* instance, uint32_t* triangle, const uint4* table, const float* deform_posed, const float4* nm_tri_geo, hipStream_t s))
 // environment lighting (k_env.hip; st_env.cpp): a map's upload from device memory (pitched rows of 3 or 4 floats -> sanitised float4 texels,
 // `bad` counts texels that had a NaN, infinite or negative channel), the luminance grid of its importance table, the debug seams
 ST_LAUNCHER(launch_env_upload, (const void* src, size_t pitch, uint32_t w, uint32_t h, uint32_t channels, float4* texels, uint32_t* bad, hipStream_t s))

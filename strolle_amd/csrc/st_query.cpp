@@ -40,7 +40,9 @@ int Engine::trace_rays(const void* rays, uint32_t count, void* hits, uint32_t fl
     if (int rc = query_begin(stream, a, reader)) return rc;
     // ST_RAY_COHERENT: the packet walk needs the wide stream, and is given up for good once it overflowed (st_engine.h packets_overflowed)
     const uint32_t packets = (flags & ST_RAY_COHERENT) && a.bvh_w != nullptr && !packets_overflowed ? 1u : 0u;
-    L.launch_query_closest(a, static_cast<const float4*>(rays), count, static_cast<float4*>(hits), static_cast<const uint4*>(sets[live].instance_table.ptr), packets, stream);
+    const float4* nm_tri_geo = nullptr;   // ST_RAY_MAPPED_NORMAL: the flag alone decides, not the engine's switch
+    if (flags & ST_RAY_MAPPED_NORMAL) if (int rc = normal_map_geo(stream, true, &nm_tri_geo)) { (void)query_end(stream, reader); return rc; }   // (launches already queued on the stream still end their read)
+    L.launch_query_closest(a, static_cast<const float4*>(rays), count, static_cast<float4*>(hits), static_cast<const uint4*>(sets[live].instance_table.ptr), packets, nm_tri_geo, stream);
     return query_end(stream, reader);
 }
 
@@ -56,7 +58,9 @@ int Engine::pick(const CameraState& c, const uint32_t* pixels, uint32_t count, v
     if (int rc = query_begin(stream, a, true)) return rc;
     a.cam = c.has_shown ? c.shown : serialize_camera(c.desc);
     a.width = c.has_shown ? c.shown_width : c.desc.width; a.height = c.has_shown ? c.shown_height : c.desc.height;
-    L.launch_query_pick(a, pixels, count, static_cast<float4*>(hits), static_cast<const uint4*>(sets[live].instance_table.ptr), stream);
+    const float4* nm_tri_geo = nullptr;
+    if (int rc = normal_map_geo(stream, false, &nm_tri_geo)) { (void)query_end(stream, true); return rc; }
+    L.launch_query_pick(a, pixels, count, static_cast<float4*>(hits), static_cast<const uint4*>(sets[live].instance_table.ptr), nm_tri_geo, stream);
     return query_end(stream, true);
 }
 

@@ -89,6 +89,24 @@ int Engine::allocate_camera(CameraState& c) {
 // The scene half of KArgs (st_engine.h scene_args): what every launch that walks the live scene copy reads — its arrays, the stream its rays
 // walk (contract, compact or wide) and the stack they hold (SceneTree::walk_args), the walk flags. `heatmap`: the launch is a BVH heatmap pass, which observes the
 // contract stream. Shared by render() and the scene queries (st_query.cpp).
+// Normal mapping's launch argument (st_engine.h). The device keeps the hit-test records per slot wherever it bakes, refits or builds from them; a copy written from a
+// host tree alone holds them only inside its leaf entries, so the first reader that maps normals sends the host's array (current: such a copy was written from it)
+// and joins the stream — once per scene change, and only while a map is in use.
+int Engine::normal_map_geo(hipStream_t stream, bool flagged, const float4** geo) {
+    *geo = nullptr;
+    if (!(normal_mapping || flagged) || !any_normal_map || tri_geo.empty()) return ST_OK;
+    SceneSet& scene = sets[live];
+    if (!scene.geo_current) {
+        const size_t bytes = tri_geo.size() * sizeof(float4);
+        if (int rc = scene.tri_geo.reserve(bytes, std::max<size_t>(bytes * 3 / 2, 4096))) return rc;
+        ST_HIP(hipMemcpyAsync(scene.tri_geo.ptr, tri_geo.data(), bytes, hipMemcpyHostToDevice, stream));
+        ST_HIP(hipStreamSynchronize(stream));   // pageable source; and readers on other streams find the records there
+        scene.geo_current = true;
+    }
+    if (scene.tri_geo.capacity < tri_geo.size() * sizeof(float4)) return fail(ST_ERR_INVALID_ARGUMENT, "normal mapping: the live scene copy's hit-test records are short of the scene's triangle slots");
+    *geo = static_cast<const float4*>(scene.tri_geo.ptr);
+    return ST_OK;
+}
 int Engine::scene_args(KArgs& a, bool heatmap) const {
     const SceneSet& scene = sets[live];
     a.tri_attr = static_cast<const float4*>(scene.tri_attr.ptr); a.instance_xforms = static_cast<const float4*>(scene.xforms.ptr);
@@ -187,6 +205,7 @@ struct FrameSwitches {
 // visibility and the GI chain to the camera's side stream); the rest below `s` is launch bookkeeping.
 struct Frame {
     Engine& e; CameraState& c; void* const out; const hipStream_t stream; hipStream_t cur;
+    const float4* nm_tri_geo = nullptr;   // normal mapping's argument of primary visibility (Engine::normal_map_geo): null while nothing is mapped
     KArgs a{}; OutputRoute route; FrameSwitches s{}; HdrWork work;
     const uint32_t mode, pseed;   // pseed: one seed for both preview passes (passes/gi_preview_resampling.rs:60-74)
     bool mask_split = false, di_reprojected = false, gi_reprojected = false, composed = false, luts_generated_now = false; uint32_t launch_ordinal = 0u;
@@ -335,6 +354,7 @@ struct Frame {
         c.last_lean = 0u; c.last_lean_composed = false;
         a.cam = c.curr; a.prev_cam = c.prev;
         if (int rc = e.scene_args(a, mode == ST_MODE_BVH_HEATMAP)) return rc;
+        if (mode != ST_MODE_BVH_HEATMAP && mode != ST_MODE_REFERENCE) if (int rc = e.normal_map_geo(stream, false, &nm_tri_geo)) return rc;   // (those two modes run no primary visibility)
         c.shown = c.curr; c.shown_prev = c.prev; c.shown_width = c.desc.width; c.shown_height = c.desc.height; c.has_shown = true;   // what st_camera_pick casts through
         e.light_args(a);
         const bool alt = c.frame % 2u == 1u;
@@ -449,8 +469,8 @@ struct Frame {
     void prim() {
         // output-chain launches of the frame before last read the G-buffer this launch rewrites, behind that frame's composing launch (the node table's reads_depth)
         (void)c.gbuffer_depth_read[c.frame % 2u].wait(cur, Fence::OtherStreams, Fence::Clear);
-        if (e.tuning.fuse && s.any_objects) run(KS_PRIM_VISIBILITY_REPROJECTION, ST_PASS_PRIM_VISIBILITY | ST_PASS_FRAME_REPROJECTION, [&] { e.L.launch_prim_visibility(a, true, e.deform.deform_table(), e.deform.deform_posed(), cur); });
-        else run(KS_PRIM_VISIBILITY, ST_PASS_PRIM_VISIBILITY, [&] { e.L.launch_prim_visibility(a, false, e.deform.deform_table(), e.deform.deform_posed(), cur); });
+        if (e.tuning.fuse && s.any_objects) run(KS_PRIM_VISIBILITY_REPROJECTION, ST_PASS_PRIM_VISIBILITY | ST_PASS_FRAME_REPROJECTION, [&] { e.L.launch_prim_visibility(a, true, e.deform.deform_table(), e.deform.deform_posed(), nm_tri_geo, cur); });
+        else run(KS_PRIM_VISIBILITY, ST_PASS_PRIM_VISIBILITY, [&] { e.L.launch_prim_visibility(a, false, e.deform.deform_table(), e.deform.deform_posed(), nm_tri_geo, cur); });
         if (s.any_objects && !e.tuning.fuse) run(KS_FRAME_REPROJECTION, ST_PASS_FRAME_REPROJECTION, [&] { e.L.launch_frame_reprojection(a, cur); });
     }
     // DI up to temporal resampling touches only the DI reservoirs and read-only frame inputs ...

@@ -14,6 +14,7 @@ float4 Engine::image_rect(uint64_t h) const {
 
 void Engine::rebuild_gpu_materials() {
     gpu_materials.resize(materials.size()); material_base_packed.resize(materials.size());
+    any_normal_map = false;
     for (size_t i = 0; i < materials.size(); i++) {
         const StMaterial& m = materials[i]; GpuMaterial& g = gpu_materials[i];
         g.base_color = make_float4(m.base_color[0], m.base_color[1], m.base_color[2], m.base_color[3]);
@@ -24,6 +25,7 @@ void Engine::rebuild_gpu_materials() {
         g.metallic = m.metallic; g.reflectance = m.reflectance; g.ior = m.ior;
         g.metallic_roughness_texture = image_rect(m.metallic_roughness_texture);
         g.normal_map_texture = image_rect(m.normal_map_texture);
+        any_normal_map = any_normal_map || !is_zero(g.normal_map_texture);
         material_base_packed[i] = gbuffer_pack_base_color(g.base_color);  // st_math.h routines are bit-identical on host and device
     }
 }

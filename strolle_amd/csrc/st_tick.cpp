@@ -118,6 +118,13 @@ int Engine::upload_scene(TreePlan plan, TickIo& io) {
     bool attr_sent = false;
     if ((rc = tree.write(t, plan, c.up, c.pageable, &attr_sent))) return rc;
     if (!attr_sent && (rc = upload_tri_slots(t, TRI_ATTR, !t.valid || t.tri_full, c.up, c.pageable))) return rc;
+    // Normal mapping reads the hit-test records per slot, and a copy written from a host tree has none (SceneSet::geo_current): while the switch is on and a
+    // material has a map they travel with this upload, so that a moving scene pays no host join in its frames (Engine::normal_map_geo sends them only
+    // where the switch, or a flagged query, comes after the tick). The host's array is current here: such a copy was just written from it.
+    if (normal_mapping && any_normal_map && !t.geo_current && !tri_geo.empty()) {
+        if ((rc = t.tri_geo.upload(tri_geo.data(), tri_geo.size() * sizeof(float4), c.up, staging, c.pageable))) return rc;
+        t.geo_current = true;
+    }
     t.dirty_lo = SIZE_MAX; t.dirty_hi = 0; t.tri_full = false; t.valid = true;
     if ((rc = t.xforms.upload(instance_xforms.data(), instance_xforms.size() * sizeof(float4), c.up, staging, c.pageable))) return rc;
     // the scene queries' handle table follows the slots of this copy (a spawn, a despawn, a re-inserted mesh move triangle ranges)

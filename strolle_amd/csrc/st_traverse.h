@@ -239,6 +239,53 @@ ST_D V2 normal_encode_exact(V3 n) {  // normal.rs:9-24
     else r = v2(copysignf(1.0f - fabsf(n.y), n.x), copysignf(1.0f - fabsf(n.x), n.y));
     return v2(r.x * 0.5f + 0.5f, r.y * 0.5f + 0.5f);
 }
+// Normal mapping (include/strolle_hip.h "normal mapping" has the definition): the resolved normal `n` of the hit on triangle slot `tri`, bent by the
+// material's map. `inv_det` is Triangle::hit's (Candidate::inv_det): its sign is the flip closest_resolve applied to face the ray. `geo` is the live scene
+// copy's hit-test records (SceneSet::tri_geo: p0, e1, e2 per slot; Engine::normal_map_geo), an argument of the launch and null while the feature is not
+// active: callers test it first. Returns `n` itself, bit for bit, for a material without a map and wherever the frame is degenerate. Loads: the material's
+// rectangle; for a mapped material two hit-test texels, the four attribute texels again (L1-hot: closest_resolve just read them) and four atlas taps.
+// The float32 operations and their order, the same in both arithmetic builds (this island: no contraction; tests/normal_map_ref.py map_f32 restates them):
+//   s = copysign(1, inv_det)      nf = n * s                                             per component
+//   du1 = uv1.x - uv0.x   dv1 = uv1.y - uv0.y   du2 = uv2.x - uv0.x   dv2 = uv2.y - uv0.y
+//   d  = du1 * dv2 - du2 * dv1                                                           unchanged unless kNormalMapTiny <= |d| <= FLT_MAX
+//   Pu = (e1 * dv2 - e2 * dv1) / d        Pv = (e2 * du1 - e1 * du2) / d                 per component
+//   g  = (nf.x * Pu.x + nf.y * Pu.y) + nf.z * Pu.z          q = Pu - nf * g
+//   l2 = (q.x * q.x + q.y * q.y) + q.z * q.z     l = sqrt(l2)                            unchanged unless kNormalMapShort <= l <= kNormalMapLong
+//   T  = q * (1 / l)              C = cross(nf, T)   (a.y * b.z - b.y * a.z, ...)
+//   h  = ((C.x * Pv.x + C.y * Pv.y) + C.z * Pv.z) <= 0 ? 1 : -1        B = C * h
+//   m  = sample_normal_map(uv)    t = (2 * m.x - 1, 2 * m.y - 1, max(2 * m.z - 1, 0))
+//   w  = (T * t.x + B * t.y) + nf * t.z                                                  per component
+//   k  = sqrt((w.x * w.x + w.y * w.y) + w.z * w.z)                                       unchanged unless kNormalMapShort <= k <= kNormalMapLong
+//   n' = (w * (1 / k)) * s
+// (the tests are written so that zero, NaN and infinities fail them; a length's bounds keep its SQUARE a normal float32, which a bound at float32's own range would not)
+constexpr float kNormalMapTiny = 1e-30f, kNormalMapShort = 1e-18f, kNormalMapLong = 1e18f;
+ST_D bool normal_map_det_usable(float d) { return fabsf(d) >= kNormalMapTiny && fabsf(d) <= kF32Max; }
+ST_D bool normal_map_length_usable(float l) { return l >= kNormalMapShort && l <= kNormalMapLong; }
+ST_D V3 normal_map_apply(const KArgs& a, const float4* geo, uint32_t tri, uint32_t material, float inv_det, V2 uv, V3 n) {
+    const float4 rect = a.materials[material].normal_map_texture;
+    if (is_zero(rect) || tri >= a.tri_slots) return n;
+    const V3 e1 = xyz(geo[3u * tri + 1u]), e2 = xyz(geo[3u * tri + 2u]);
+    const TriAttr t = tri_attr_fetch(a, tri);
+    const float s = copysignf(1.0f, inv_det);
+    const V3 nf = xe::scale(n, s);
+    const float du1 = t.uv1.x - t.uv0.x, dv1 = t.uv1.y - t.uv0.y, du2 = t.uv2.x - t.uv0.x, dv2 = t.uv2.y - t.uv0.y;
+    const float d = du1 * dv2 - du2 * dv1;
+    if (!normal_map_det_usable(d)) return n;
+    const V3 pu = v3((e1.x * dv2 - e2.x * dv1) / d, (e1.y * dv2 - e2.y * dv1) / d, (e1.z * dv2 - e2.z * dv1) / d);
+    const V3 pv = v3((e2.x * du1 - e1.x * du2) / d, (e2.y * du1 - e1.y * du2) / d, (e2.z * du1 - e1.z * du2) / d);
+    const V3 q = xe::sub(pu, xe::scale(nf, xe::dot(nf, pu)));
+    const float l = sqrtf(xe::dot(q, q));
+    if (!normal_map_length_usable(l)) return n;
+    const V3 tangent = xe::scale(q, 1.0f / l);
+    const V3 c = xe::cross(nf, tangent);
+    const V3 bitangent = xe::scale(c, xe::dot(c, pv) <= 0.0f ? 1.0f : -1.0f);
+    const V3 m = sample_normal_map(a, uv, rect);
+    const float tx = 2.0f * m.x - 1.0f, ty = 2.0f * m.y - 1.0f, tz = fmax_(2.0f * m.z - 1.0f, 0.0f);
+    const V3 w = xe::add(xe::add(xe::scale(tangent, tx), xe::scale(bitangent, ty)), xe::scale(nf, tz));
+    const float k = sqrtf(xe::dot(w, w));
+    if (!normal_map_length_usable(k)) return n;
+    return xe::scale(xe::scale(w, 1.0f / k), s);
+}
 // Ray::intersect (shadow ray) as the contract states it: the reference's visiting order, arithmetic and `used_memory` count
 template <class SE>
 ST_D bool trace_any_contract(const KArgs& a, const Ray& ray, SE* stack, uint32_t* used_memory) {
