@@ -284,13 +284,13 @@ bool SceneTree::device_build_possible() const {
     // the device's LBVH (two rows: the device's by 1 and 6 %); at 3.7 the device's is 1-2 % faster; at 4.2-4.5 (the dungeon with its level split x16: runs of up to 140
     // coplanar triangles, a wide walk's step each) 5-17 % faster. A triangle COUNT does not separate them: 16 instanced copies of the level (139 k triangles, weight 1.8)
     // render 1-7 % faster on the host's tree, the x16-split level (134 k, weight 4.5) 12-17 % faster on the device's.
-    const bool automatic = bvh_refresh_mode == ST_BVH_AUTO && (e.scene_uploaded || auto_first_on_device) && e.live_prims_ > kLdsSceneTexels / 4u;
+    const bool automatic = bvh_refresh_mode == ST_BVH_AUTO && (e.copies.scene.written || auto_first_on_device) && e.live_prims_ > kLdsSceneTexels / 4u;
     if (!(bvh_refresh_mode == ST_BVH_BUILD_DEVICE || automatic) || !e.has_device || !e.wide_only_tuning() || e.heatmap_camera()) return false;
     return e.live_prims_ >= 2u && e.prims.size() < (1u << 23);
 }
 bool SceneTree::moves_stay_on_device() const {
     // (ST_BVH_BUILD_DEVICE: the same, with the tree rebuilt on the device from the device-baked arrays instead of refitted)
-    const bool build_mode = device_build_possible() && e.scene_uploaded;
+    const bool build_mode = device_build_possible() && e.copies.scene.written;
     return (device_refit_possible() && have_topology) || build_mode;
 }
 // The device builder's scratch and output arrays of one scene copy, for `slots` triangle slots of which `live` are live: grown with headroom, never shrunk.
@@ -397,8 +397,8 @@ TreePlan SceneTree::plan(bool instances_changed, bool moved_on_device, bool mate
         rebuild_host_tree(timing);
         if (refitting) { index_stream(); topology_signature = signature; have_topology = true; }
         // the first tree of this scene: the host's, unless it hangs long leaf runs on large faces — then the device builder's, from this very tick on.
-        // (finding 1: "first" is the first tick, !scene_uploaded — also when the scene is still empty or half loaded then)
-        if (!e.scene_uploaded && bvh_refresh_mode == ST_BVH_AUTO) {
+        // (finding 1: "first" is the first tick, !scene.written — also when the scene is still empty or half loaded then)
+        if (!e.copies.scene.written && bvh_refresh_mode == ST_BVH_AUTO) {
             auto_first_on_device = host_leaf_run_weight > kAutoLeafRunLimit;
             if (auto_first_on_device && device_build_possible()) { device_builds++; device_refits_since_build = 0; return TreePlan::device_build; }
         }
@@ -407,9 +407,9 @@ TreePlan SceneTree::plan(bool instances_changed, bool moved_on_device, bool mate
     // Nothing changed, the host's tree is current (a debug read rebuilt it) — but the live device copy still holds a device-built tree and no contract
     // stream, and an observer has appeared (heatmap camera, exact arithmetic, byte counting): the host's streams are uploaded now, so that the render
     // after THIS tick finds them (include/strolle_hip.h ST_BVH_BUILD_DEVICE: "a heatmap camera created later renders after the next st_tick").
-    if (e.scene_uploaded && e.sets[e.live].tree.device_built && !build_now) return TreePlan::host_to_observer;
+    if (e.copies.scene.written && e.copies.scene.current().tree.device_built && !build_now) return TreePlan::host_to_observer;
     // The tree is as it was; a material or atlas edit (or the first upload) still sends the scene. (finding 2: under ST_BVH_AUTO a material-only edit replaces a current host tree by the device's, without device_builds++)
-    return build_now && (materials_changed || !e.scene_uploaded) ? TreePlan::device_build : TreePlan::none;
+    return build_now && (materials_changed || !e.copies.scene.written) ? TreePlan::device_build : TreePlan::none;
 }
 
 // ---- the tree half of the scene's upload (st_tick.cpp upload_scene picked the copy and the stream)
@@ -418,7 +418,7 @@ int SceneTree::write(SceneSet& set, TreePlan plan, hipStream_t up, bool* pageabl
     TreeCopy& t = set.tree;
     const bool build_now = plan == TreePlan::device_build || plan == TreePlan::device_refit;
     // (finding 4: the reservation asks the tuning half of "nothing observes the contract stream", not the camera half)
-    if (!e.scene_uploaded && (bvh_refresh_mode == ST_BVH_AUTO || bvh_refresh_mode == ST_BVH_BUILD_DEVICE) && e.wide_only_tuning() && e.live_prims_ > kLdsSceneTexels / 4u && e.prims.size() < (1u << 23)) {
+    if (!e.copies.scene.written && (bvh_refresh_mode == ST_BVH_AUTO || bvh_refresh_mode == ST_BVH_BUILD_DEVICE) && e.wide_only_tuning() && e.live_prims_ > kLdsSceneTexels / 4u && e.prims.size() < (1u << 23)) {
         // this scene's changes (and, for a large scene, its first tree: device_build_possible) go to the device builder: its arrays are allocated NOW, while the
         // scene loads, for both copies — BEFORE the wide stream of this copy is written below (its allocation is one of them: growing it afterwards would throw the stream away: round 6's
         // first version did, and rendered an empty world). A failure here is not an error: the build allocates what it finds missing.
@@ -426,9 +426,9 @@ int SceneTree::write(SceneSet& set, TreePlan plan, hipStream_t up, bool* pageabl
         const size_t want = e.triangles.size() + e.triangles.size() / 8u;
         e.triangles.reserve(want); e.prims.reserve(want); e.prim_alive.reserve(want); e.tri_geo.reserve(3 * want); e.tri_attr.reserve(4 * want); e.tri_bounds.reserve(2 * want);
         bool reserved = true;
-        for (SceneSet& s : e.sets)
+        for (SceneSet& s : e.copies.scene.copy)
             if (reserve_device_builder(s.tree, e.prims.size() + e.prims.size() / 8u, (uint32_t)std::min<size_t>(e.live_prims_ + e.live_prims_ / 8u, e.prims.size() + e.prims.size() / 8u)) != ST_OK) { (void)hipGetLastError(); reserved = false; break; }
-        if (reserved && !build_now && e.sets[0].tree.lb_small.ptr) lbvh_warm(static_cast<int*>(e.sets[0].tree.lb_small.ptr), up);   // ... and the builder's code object is on the device before the first spawn
+        if (reserved && !build_now && e.copies.scene.copy[0].tree.lb_small.ptr) lbvh_warm(static_cast<int*>(e.copies.scene.copy[0].tree.lb_small.ptr), up);   // ... and the builder's code object is on the device before the first spawn
     }
     if (build_now) {
         // (instances the device moved stay stale on the host: this copy's pending list re-bakes them on the device even after a whole upload)
@@ -581,8 +581,8 @@ int SceneTree::debug_read(int what, const void** p, size_t* bytes) {
         case ContractStream: { const auto& s = host_stream(); *p = s.data(); *bytes = s.size() * sizeof(float4); break; }
         case DeviceForm: *p = device_form().data(); *bytes = (size_t)device_bvh_len * sizeof(float4); break;  // as st_tick would upload it now
         case LiveStream: {  // the device stream as it is on the device right now (the live copy): what a device refit left there
-            if (!e.has_device || !e.scene_uploaded) return fail(ST_ERR_NO_DEVICE, "no device copy of the scene");
-            const TreeCopy& t = e.sets[e.live].tree;
+            if (!e.has_device || !e.copies.scene.written) return fail(ST_ERR_NO_DEVICE, "no device copy of the scene");
+            const TreeCopy& t = e.copies.scene.current().tree;
             const size_t n = t.bvh.capacity ? (size_t)live_bvh_texels : 0;
             readback_.resize(n);
             ST_HIP(hipSetDevice(e.device)); ST_HIP(hipDeviceSynchronize());
@@ -608,8 +608,8 @@ int SceneTree::debug_read(int what, const void** p, size_t* bytes) {
             *p = v->data(); *bytes = v->size() * sizeof(uint32_t); break;
         }
         case LiveWideNodes: case LiveWideLeaves: {  // the wide stream as it is on the device right now (the live copy): nodes (64 B each) / leaf records (48 B each)
-            if (!e.has_device || !e.scene_uploaded) return fail(ST_ERR_NO_DEVICE, "no device copy of the scene");
-            const TreeCopy& t = e.sets[e.live].tree;
+            if (!e.has_device || !e.copies.scene.written) return fail(ST_ERR_NO_DEVICE, "no device copy of the scene");
+            const TreeCopy& t = e.copies.scene.current().tree;
             const size_t n = (t.wide_for_entries || t.device_built) ? (what == LiveWideNodes ? (size_t)t.wide_nodes * 4u : (size_t)t.wide_leaves * 3u) : 0;
             readback_.resize(n);
             ST_HIP(hipSetDevice(e.device)); ST_HIP(hipDeviceSynchronize());

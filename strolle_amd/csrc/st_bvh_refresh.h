@@ -14,7 +14,7 @@ struct SceneSet;
 // What upload_scene does with the tree (SceneTree::plan decides, SceneTree::write carries it out)
 enum class TreePlan { none, host_refit, host_rebuild, device_build, device_refit, host_to_observer };
 
-// The tree's half of one device copy of the scene (st_engine.h SceneSet)
+// The tree's half of one device copy of the scene (st_copies.h SceneSet)
 struct TreeCopy {
     DeviceArray bvh;   // the contract stream in its device form
     DeviceArray bvh_compact; uint32_t compact_entries = 0;   // k_bvh.hip k_bvh_compact: 48 B per entry, regenerated whenever `bvh` changed

@@ -206,7 +206,7 @@ const std::vector<StMeshTriangle>* Deformer::bake_source(uint64_t instance, cons
     return &mesh;   // (a pose that no tick has skinned yet: the instance still shows the bind pose)
 }
 
-const uint4* Deformer::deform_table() const { return live ? static_cast<const uint4*>(e.sets[e.live].instance_table.ptr) : nullptr; }
+const uint4* Deformer::deform_table() const { return live ? static_cast<const uint4*>(e.copies.scene.current().instance_table.ptr) : nullptr; }
 
 // Deformation motion: what the last tick left is forgotten before this one deforms — an instance has a previous pose for the frames of the tick
 // that deformed it again, no longer. With the switch off the second regions go back to the store.

@@ -2,7 +2,7 @@
 //   st_engine.cpp       construction, tuning (StTuning + environment), destruction
 //   st_scene.cpp        scene stores: materials, images, lights, instances -> world-space triangles (baking)
 //   st_bvh_refresh.cpp  the scene's BVH (st_bvh_refresh.h): the host's tree and its streams, refits, the wide topology, the device builder's input, the tick's tree plan
-//   st_tick.cpp         Engine::tick: refresh of the stores + uploads (double-buffered scene / light copies, page-locked staging)
+//   st_tick.cpp         Engine::tick: refresh of the stores + uploads (page-locked staging); the tick's device copies (st_copies.h): double-buffered scene / light copies, their readers, retirement
 //   st_render.cpp       per-camera buffers and Engine::render: the per-frame pass graph in phases, on two HIP streams; present hand-over
 //   st_display.cpp      display transforms: exposure, tone mapping, the auto-exposure state
 //   st_post.cpp         output post-processing: FXAA and the resampler
@@ -25,7 +25,7 @@
 // Ownership: every device allocation, event, stream and page-locked buffer of the host engine is a member of a move-only type that frees it
 // in its destructor (DeviceArray, Event, Stream, PinnedBuffer, below) — teardown lists nothing. A destructor runs with whatever device is
 // current, so whoever lets one of them go first makes the engine's device current and, where work may still use the resource, joins it
-// (~Engine, st_camera_delete, st_camera_update; st_tick for everything a tick replaces). st_dist.cpp keeps its own protocol.
+// (~Engine, st_camera_delete, st_camera_update; st_tick for everything a tick replaces: st_copies.h CopyPair, Retired). st_dist.cpp keeps its own protocol.
 // Stream order between users of one resource on different streams is a Fence (below): record / record_chained behind the users, wait
 // (from any stream or only from other streams than the recorder; keeping or clearing the recording), host_wait, poll, settled.
 #pragma once
@@ -331,6 +331,7 @@ inline double format_bytes(uint32_t format) { return format == ST_FORMAT_RGBA32F
 }  // namespace st
 #include "st_deform.h"
 #include "st_bvh_refresh.h"
+#include "st_copies.h"
 #include "st_output_chain.h"
 namespace st {
 
@@ -460,24 +461,6 @@ int dist_grid(uint32_t width, uint32_t height, uint32_t world, uint32_t cols, St
 int dist_grid_tile(const StDistGrid* g, uint32_t rank, StDistRect* owned);
 int dist_grid_rebalance(uint32_t width, uint32_t height, const StDistGrid* cur, const float* cost, uint32_t max_step, StDistGrid* out);
 
-// The arrays a scene change rewrites exist twice. A tick that changes the scene fills the copy no frame in flight reads,
-// on a stream of its own, while the previous frame still renders from the other one; the next frame switches over.
-// (Updating in place would have to wait for the previous frame, and the next frame's primary rays with it.)
-struct SceneSet {
-    DeviceArray tri_attr, xforms, materials, base_packed;
-    TreeCopy tree;   // the tree's half (st_bvh_refresh.h): the streams, the refit's index arrays, the device builder's scratch
-    // per triangle slot the hit-test record and the bounds (ST_BVH_REFIT_DEVICE, ST_BVH_BUILD_DEVICE: k_bvh.hip and k_lbvh.hip read them)
-    DeviceArray tri_geo, tri_bounds;
-    bool geo_current = false;   // tri_geo holds the hit-test record of every slot as this copy's tree has it (SceneTree::write); a host-tree path sends none — normal mapping asks (Engine::normal_map_geo)
-    size_t dirty_lo = SIZE_MAX, dirty_hi = 0; bool tri_full = true;  // what this copy lacks of the host's triangle arrays
-    std::vector<uint64_t> pending_moves;   // instances moved on the device whose current transform this copy has not baked yet
-    DeviceArray bake_jobs, bake_starts;
-    // per instance slot (tri_attr[4 t + 3].w): {StHandle lo, hi, first triangle slot, 0} — the scene queries' instance and mesh triangle (st_query.cpp)
-    DeviceArray instance_table;
-    Fence fence;   // reads of this copy enqueued since it was written end here (reader_end; pick_copy waits before it writes the copy again)
-    bool valid = false;
-};
-
 struct Engine {
     int device = -1;
     bool has_device = false;
@@ -524,7 +507,6 @@ struct Engine {
     std::vector<float4> tri_geo, tri_attr, tri_bounds;  // tri_bounds: (lo, hi) per triangle slot (device refit)
     // The scene's BVH — the host's tree, its streams, refits, the device builder, the tick's plan — has one owner (st_bvh_refresh.h)
     SceneTree tree{*this};
-    bool scene_uploaded = false;
 
     // images: a single linear RGBA8 atlas of the reference's extent (images.rs:28-29); rectangles from st_atlas.h
     static constexpr uint32_t kAtlasW = 8192, kAtlasMaxH = 8192;
@@ -537,7 +519,6 @@ struct Engine {
     struct DeviceImage { const void* pixels; size_t pitch; bool dynamic, pending; };
     std::map<uint64_t, DeviceImage> device_images;
     StagingRing staging;
-    Fence tick_done;   // a tick queued copies without joining the stream: this marks their end, the next frame's streams wait for it
 
     // lights (lights.rs): slot 0 is the sun
     std::vector<GpuLight> light_buffer; std::map<int64_t, uint32_t> light_slot;
@@ -552,38 +533,28 @@ struct Engine {
     std::vector<uint8_t> blue_noise; bool blue_noise_dirty = true;
     bool atmosphere_initialized = false, sky_known = false; float known_sun_altitude = 0.0f;  // passes/atmosphere.rs:14-15,78-110
 
+    // The tick's device copies — the scene's and the lights' pairs, their readers, the tick's streams and fences — have one owner (st_copies.h)
+    SceneCopies copies{*this};
     // environment lighting (include/strolle_hip.h "environment lighting"; st_env.cpp). An edit waits in env_edit / env_desc_next for the next
-    // tick (apply_environment on the host, upload_environment on the device). Every map the device holds is a fresh allocation: frames
-    // enqueued before a replacement keep reading theirs, which is released once its fence says they are done (env_retired).
+    // tick (apply_environment on the host, upload_environment on the device). Every map the device holds is a fresh allocation (env_retired).
     struct EnvMap { DeviceArray texels, table; uint32_t w = 0, h = 0, gw = 0, gh = 0; Fence fence; };
     enum EnvEditKind { ENV_EDIT_NONE, ENV_EDIT_HOST, ENV_EDIT_DEVICE, ENV_EDIT_CLEAR };
     struct EnvEdit { EnvEditKind kind = ENV_EDIT_NONE; std::vector<float4> texels; const void* src = nullptr; size_t pitch = 0; uint32_t w = 0, h = 0, channels = 0; };
     EnvEdit env_edit;
     StEnvironmentDesc env_desc{}, env_desc_next{};
     bool env_set = false, env_sun_off = false;   // a map is live (host-only engines too: light 0 follows it); light 0 is dark because of it
-    std::unique_ptr<EnvMap> env_live; std::vector<std::unique_ptr<EnvMap>> env_retired;
+    std::unique_ptr<EnvMap> env_live; Retired<EnvMap> env_retired{copies};
     DeviceArray d_env_grid, d_env_bad /* one u32: the texels the device upload sanitized */; uint64_t env_sanitized = 0;
     std::vector<float> env_grid_host; std::vector<EnvCell> env_table_host;
 
     // colour grading's look-up tables (include/strolle_hip.h "colour grading"; st_grade.cpp). st_lut_insert / st_lut_remove leave an edit
-    // per id for the next tick (a host-only engine drops them there). Every table the device holds is a fresh allocation of size^3 float4:
-    // frames enqueued before a replacement or removal keep reading theirs, which is released once its fence says they are done (luts_retired).
+    // per id for the next tick (a host-only engine drops them there). Every table the device holds is a fresh allocation of size^3 float4 (luts_retired).
     struct Lut { DeviceArray texels; uint32_t size = 0; Fence fence; };
     struct LutEdit { uint32_t size = 0; std::vector<float4> texels; };   // size 0: remove
     std::map<StHandle, LutEdit> lut_edits;
-    std::map<StHandle, std::unique_ptr<Lut>> luts_live; std::vector<std::unique_ptr<Lut>> luts_retired;
+    std::map<StHandle, std::unique_ptr<Lut>> luts_live; Retired<Lut> luts_retired{copies};
 
     DeviceArray d_byte_luts, d_atlas, d_blue_noise, d_transmittance, d_scattering, d_sky;
-    SceneSet sets[2]; int live = 0;
-    // the light table alternates the same way, on its own schedule (a light that moves every frame does not resend the scene)
-    struct LightSet { DeviceArray buf; Fence fence; };
-    LightSet light_sets[2]; int live_lights = 0; bool lights_uploaded = false, lights_alternating = false;
-    bool alternating = false, mixed_render_streams = false;
-    Stream copy_stream; hipStream_t last_render_stream = nullptr; bool rendered_before = false;
-    Fence copy_done;   // behind a tick's copies on copy_stream, like tick_done
-    struct CopyTarget { int index; hipStream_t up; bool* pageable; bool other; };   // the writer's side: st_tick.cpp pick_copy
-    int reader_begin(hipStream_t stream, bool reader);   // the readers' side: st_render.cpp
-    int reader_end(hipStream_t stream, bool lights, bool reads_previous = false);   // reads_previous: the reader can reach deform_prev_point (frames, the MOTION AOV)
 
     std::unordered_map<uint64_t, std::unique_ptr<CameraState>> cameras; uint64_t next_camera = 0;
 
@@ -666,21 +637,16 @@ struct Engine {
     enum TriArrays : unsigned { TRI_GEO = 1u /* hit-test records + bounds */, TRI_ATTR = 2u /* attribute records */ };   // a copy's triangle-slot arrays
     bool tri_fits(const SceneSet& t, unsigned arrays) const;
     int upload_tri_slots(SceneSet& t, unsigned arrays, bool whole, hipStream_t up, bool* pageable);
-    struct TickIo { hipStream_t stream; bool pageable = false, pageable_copy = false, copied = false, uploaded = false; };   // copied: on copy_stream; uploaded: on `stream`
     int tick(hipStream_t stream);
     TreePlan refresh_scene();
     void refresh_sun_and_lights();
     void apply_environment();
     int upload_environment(TickIo& io);
-    int retire_environment(std::unique_ptr<EnvMap> m);
-    void release_environments();
     void environment_args(KArgs& a) const;
     int environment_debug(uint32_t what, const float* in, uint32_t n, float* out, hipStream_t stream);
-    int pick_copy(TickIo& io, int live_index, Fence& live_fence, Fence& other_fence, bool written_before, bool& alternating_now, CopyTarget& c);
     int upload_scene(TreePlan plan, TickIo& io);
     int upload_images(TickIo& io);
     int upload_lights(TickIo& io);
-    int end_uploads(TickIo& io);
     int report_deep_bvh();
 
     static GpuCamera serialize_camera(const StCamera& c);
@@ -793,8 +759,7 @@ struct Engine {
     // ---- scene queries (st_query.cpp; include/strolle_hip.h "scene queries")
     std::vector<uint32_t> instance_table_;   // host image of SceneSet::instance_table, rebuilt by every scene upload
     void fill_instance_table();
-    int query_begin(hipStream_t stream, KArgs& a, bool reader);
-    int query_end(hipStream_t stream, bool reader);
+    int query_begin(hipStream_t stream, KArgs& a, unsigned reads);   // the checks, scene_args, copies.begin
     int trace_rays(const void* rays, uint32_t count, void* hits, uint32_t flags, hipStream_t stream, bool reader = true);
     int occluded(const void* rays, uint32_t count, uint32_t* out, hipStream_t stream);
     int pick(const CameraState& c, const uint32_t* pixels, uint32_t count, void* hits, hipStream_t stream);

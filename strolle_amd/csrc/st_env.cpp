@@ -50,7 +50,7 @@ void Engine::apply_environment() {
 
 // device part: the new map in an allocation of its own, on the tick's stream; the old one is retired behind the frames that read it
 int Engine::upload_environment(TickIo& io) {
-    release_environments();
+    env_retired.release();
     const EnvEditKind kind = env_edit.kind;
     if (kind == ENV_EDIT_NONE) return ST_OK;
     std::unique_ptr<EnvMap> m;
@@ -82,29 +82,11 @@ int Engine::upload_environment(TickIo& io) {
         if (int rc = m->table.reserve(cells * sizeof(EnvCell), cells * sizeof(EnvCell))) return rc;
         if (int rc = m->table.upload_range(env_table_host.data(), 0, cells * sizeof(EnvCell), io.stream, staging, &io.pageable)) return rc;
     }
-    if (env_live) if (int rc = retire_environment(std::move(env_live))) return rc;
+    if (env_live) if (int rc = env_retired.retire(std::move(env_live))) return rc;
     env_live = std::move(m);
     env_edit = EnvEdit();   // (the host texels went to the device before the synchronisation above)
     io.uploaded = true;
     return ST_OK;
-}
-
-// (the map goes when `m` does: at once, unless frames still read it)
-int Engine::retire_environment(std::unique_ptr<EnvMap> m) {
-    if (m->fence.pending) {
-        if (!mixed_render_streams) { env_retired.push_back(std::move(m)); return ST_OK; }
-        ST_HIP(hipDeviceSynchronize());   // cameras render on several streams: no single event ends their reads
-    }
-    return ST_OK;
-}
-
-// retired maps whose last reader has finished (st_tick: the device is current)
-void Engine::release_environments() {
-    for (size_t i = 0; i < env_retired.size();) {
-        if (env_retired[i]->fence.poll()) env_retired.erase(env_retired.begin() + (long)i);
-        else i++;
-    }
-    (void)hipGetLastError();   // hipErrorNotReady is not an error
 }
 
 void Engine::environment_args(KArgs& a) const {
@@ -122,12 +104,12 @@ int Engine::environment_debug(uint32_t what, const float* in, uint32_t n, float*
     if (n == 0) return ST_OK;
     if (!in || !out) return fail(ST_ERR_INVALID_ARGUMENT, "null argument");
     ST_HIP(hipSetDevice(device));
-    if (int rc = reader_begin(stream, true)) return rc;   // (a reader like a frame: a seam on another stream makes the streams mixed)
+    if (int rc = copies.begin(stream, kReadsEnvironment)) return rc;   // (a reader like a frame: a seam on another stream makes the streams mixed)
     KArgs a{};
     environment_args(a);
     L.launch_env_debug(a, what, in, n, out, stream);
     ST_HIP(hipGetLastError());
-    return env_live->fence.record(stream);
+    return copies.end(stream, kReadsEnvironment);
 }
 
 }  // namespace st

@@ -141,11 +141,7 @@ int Engine::lut_remove(StHandle id) {
 // The tick's device part: each edit becomes a fresh allocation filled on the tick's stream (frames rendered behind the tick on another stream
 // are ordered behind it as behind every upload); the table it replaces, or the one removed, is retired behind the frames that read it
 int Engine::upload_luts(TickIo& io) {
-    for (size_t i = 0; i < luts_retired.size();) {
-        if (luts_retired[i]->fence.poll()) luts_retired.erase(luts_retired.begin() + (long)i);
-        else i++;
-    }
-    (void)hipGetLastError();   // hipErrorNotReady is not an error
+    luts_retired.release();
     if (lut_edits.empty()) return ST_OK;
     for (auto& kv : lut_edits) {
         std::unique_ptr<Lut> fresh;
@@ -159,10 +155,7 @@ int Engine::upload_luts(TickIo& io) {
         }
         auto it = luts_live.find(kv.first);
         if (it != luts_live.end()) {
-            if (it->second->fence.pending) {
-                if (mixed_render_streams) { ST_HIP(hipDeviceSynchronize()); }   // cameras render on several streams: no single event ends their reads
-                else luts_retired.push_back(std::move(it->second));
-            }
+            if (int rc = luts_retired.retire(std::move(it->second))) return rc;
             luts_live.erase(it);
         }
         if (fresh) luts_live[kv.first] = std::move(fresh);

@@ -1,6 +1,6 @@
 // st_query.cpp — host engine of libstrolle_hip.so: scene queries (include/strolle_hip.h "scene queries"; k_query.hip). Rays of the
 // application walk the live scene copy the frames walk, with the same scene arguments (scene_args) and the same reader bookkeeping as
-// render(): a tick never refills a copy a query that is still in flight reads. See st_engine.h.
+// render() (st_copies.h): a tick never refills a copy a query that is still in flight reads. See st_engine.h.
 #include "st_engine.h"
 
 namespace st {
@@ -21,54 +21,52 @@ void Engine::fill_instance_table() {
     }
 }
 
-// What every query shares with render(): the frame's scene arguments and reader books. `reader`: in flight after the call returns (it reads no lights).
-int Engine::query_begin(hipStream_t stream, KArgs& a, bool reader) {
+// What every query shares with render(): the frame's scene arguments and reader books. `reads`: kReadsScene while in flight after the call returns, else kReadsNothing.
+int Engine::query_begin(hipStream_t stream, KArgs& a, unsigned reads) {
     if (!has_device) return fail(ST_ERR_NO_DEVICE, "scene query on a host-only engine");
-    if (!scene_uploaded) return fail(ST_ERR_INVALID_ARGUMENT, "st_tick must precede a scene query");
+    if (!copies.scene.written) return fail(ST_ERR_INVALID_ARGUMENT, "st_tick must precede a scene query");
     ST_HIP(hipSetDevice(device));
     a = KArgs{};
     if (int rc = scene_args(a, false)) return rc;
-    return reader_begin(stream, reader);
+    return copies.begin(stream, reads);
 }
-int Engine::query_end(hipStream_t stream, bool reader) {
-    ST_HIP(hipGetLastError());
-    return reader ? reader_end(stream, false) : ST_OK;
-}
+static int launched(Engine& e, hipStream_t stream, unsigned reads) { ST_HIP(hipGetLastError()); return e.copies.end(stream, reads); }   // behind a query's launch
 
 int Engine::trace_rays(const void* rays, uint32_t count, void* hits, uint32_t flags, hipStream_t stream, bool reader) {
     KArgs a;
-    if (int rc = query_begin(stream, a, reader)) return rc;
+    const unsigned reads = reader ? kReadsScene : kReadsNothing;
+    if (int rc = query_begin(stream, a, reads)) return rc;
     // ST_RAY_COHERENT: the packet walk needs the wide stream, and is given up for good once it overflowed (st_engine.h packets_overflowed)
     const uint32_t packets = (flags & ST_RAY_COHERENT) && a.bvh_w != nullptr && !packets_overflowed ? 1u : 0u;
     const float4* nm_tri_geo = nullptr;   // ST_RAY_MAPPED_NORMAL: the flag alone decides, not the engine's switch
-    if (flags & ST_RAY_MAPPED_NORMAL) if (int rc = normal_map_geo(stream, true, &nm_tri_geo)) { (void)query_end(stream, reader); return rc; }   // (launches already queued on the stream still end their read)
-    L.launch_query_closest(a, static_cast<const float4*>(rays), count, static_cast<float4*>(hits), static_cast<const uint4*>(sets[live].instance_table.ptr), packets, nm_tri_geo, stream);
-    return query_end(stream, reader);
+    if (flags & ST_RAY_MAPPED_NORMAL) if (int rc = normal_map_geo(stream, true, &nm_tri_geo)) { (void)launched(*this, stream, reads); return rc; }   // (launches already queued on the stream still end their read)
+    L.launch_query_closest(a, static_cast<const float4*>(rays), count, static_cast<float4*>(hits), static_cast<const uint4*>(copies.scene.current().instance_table.ptr), packets, nm_tri_geo, stream);
+    return launched(*this, stream, reads);
 }
 
 int Engine::occluded(const void* rays, uint32_t count, uint32_t* out, hipStream_t stream) {
     KArgs a;
-    if (int rc = query_begin(stream, a, true)) return rc;
+    if (int rc = query_begin(stream, a, kReadsScene)) return rc;
     L.launch_query_occluded(a, static_cast<const float4*>(rays), count, out, stream);
-    return query_end(stream, true);
+    return launched(*this, stream, kReadsScene);
 }
 
 int Engine::pick(const CameraState& c, const uint32_t* pixels, uint32_t count, void* hits, hipStream_t stream) {
     KArgs a;
-    if (int rc = query_begin(stream, a, true)) return rc;
+    if (int rc = query_begin(stream, a, kReadsScene)) return rc;
     a.cam = c.has_shown ? c.shown : serialize_camera(c.desc);
     a.width = c.has_shown ? c.shown_width : c.desc.width; a.height = c.has_shown ? c.shown_height : c.desc.height;
     const float4* nm_tri_geo = nullptr;
-    if (int rc = normal_map_geo(stream, false, &nm_tri_geo)) { (void)query_end(stream, true); return rc; }
-    L.launch_query_pick(a, pixels, count, static_cast<float4*>(hits), static_cast<const uint4*>(sets[live].instance_table.ptr), nm_tri_geo, stream);
-    return query_end(stream, true);
+    if (int rc = normal_map_geo(stream, false, &nm_tri_geo)) { (void)launched(*this, stream, kReadsScene); return rc; }
+    L.launch_query_pick(a, pixels, count, static_cast<float4*>(hits), static_cast<const uint4*>(copies.scene.current().instance_table.ptr), nm_tri_geo, stream);
+    return launched(*this, stream, kReadsScene);
 }
 
 // Blocking: host rays -> pinned -> device, the query on the engine's own stream, device -> pinned -> host. The call has finished with the
 // scene copy when it returns, so it does not count as one of its readers (no later tick can overlap it).
 int Engine::trace_rays_host(const void* rays, uint32_t count, void* hits) {
     if (!has_device) return fail(ST_ERR_NO_DEVICE, "scene query on a host-only engine");
-    if (!scene_uploaded) return fail(ST_ERR_INVALID_ARGUMENT, "st_tick must precede a scene query");
+    if (!copies.scene.written) return fail(ST_ERR_INVALID_ARGUMENT, "st_tick must precede a scene query");
     ST_HIP(hipSetDevice(device));
     if (!query_stream) ST_HIP(hipStreamCreateWithFlags(&query_stream.h, hipStreamNonBlocking));
     const size_t ray_bytes = (size_t)count * sizeof(StRay), hit_bytes = (size_t)count * sizeof(StRayHit);

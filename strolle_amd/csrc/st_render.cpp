@@ -91,11 +91,12 @@ int Engine::allocate_camera(CameraState& c) {
 // contract stream. Shared by render() and the scene queries (st_query.cpp).
 // Normal mapping's launch argument (st_engine.h). The device keeps the hit-test records per slot wherever it bakes, refits or builds from them; a copy written from a
 // host tree alone holds them only inside its leaf entries, so the first reader that maps normals sends the host's array (current: such a copy was written from it)
-// and joins the stream — once per scene change, and only while a map is in use.
+// and joins the stream — once per scene change, and only while a map is in use. It is the one writer of a live copy outside a tick; safe, because no launch in flight
+// reads these records of a copy that is not geo_current, and the join ends the write before any reader is handed the pointer (st_copies.h).
 int Engine::normal_map_geo(hipStream_t stream, bool flagged, const float4** geo) {
     *geo = nullptr;
     if (!(normal_mapping || flagged) || !any_normal_map || tri_geo.empty()) return ST_OK;
-    SceneSet& scene = sets[live];
+    SceneSet& scene = copies.scene.current();
     if (!scene.geo_current) {
         const size_t bytes = tri_geo.size() * sizeof(float4);
         if (int rc = scene.tri_geo.reserve(bytes, std::max<size_t>(bytes * 3 / 2, 4096))) return rc;
@@ -108,7 +109,7 @@ int Engine::normal_map_geo(hipStream_t stream, bool flagged, const float4** geo)
     return ST_OK;
 }
 int Engine::scene_args(KArgs& a, bool heatmap) const {
-    const SceneSet& scene = sets[live];
+    const SceneSet& scene = copies.scene.current();
     a.tri_attr = static_cast<const float4*>(scene.tri_attr.ptr); a.instance_xforms = static_cast<const float4*>(scene.xforms.ptr);
     a.materials = static_cast<const GpuMaterial*>(scene.materials.ptr); a.material_base_packed = tuning.packed_base ? static_cast<const uint32_t*>(scene.base_packed.ptr) : nullptr;
     a.atlas = static_cast<const uchar4*>(d_atlas.ptr); a.byte_luts = static_cast<const float*>(d_byte_luts.ptr);
@@ -123,32 +124,12 @@ int Engine::scene_args(KArgs& a, bool heatmap) const {
 }
 // The other half: the live copy of the lights, the blue noise, the atmosphere LUTs, the sun and the environment map — what a frame's shading reads.
 void Engine::light_args(KArgs& a) const {
-    a.lights = static_cast<const GpuLight*>(light_sets[live_lights].buf.ptr);
+    a.lights = static_cast<const GpuLight*>(copies.lights.current().buf.ptr);
     a.blue_noise = static_cast<const uchar4*>(d_blue_noise.ptr);
     a.transmittance_lut = static_cast<const float4*>(d_transmittance.ptr); a.sky_lut = static_cast<const float4*>(d_sky.ptr);
     a.n_lights_buf = (uint32_t)gpu_lights.size(); a.light_count = light_count;
     a.sun_altitude = sun_altitude; a.sun_dir[0] = sun_dir_.x; a.sun_dir[1] = sun_dir_.y; a.sun_dir[2] = sun_dir_.z;
     environment_args(a);
-}
-
-// The reader side of the double-buffered scene and light copies (st_tick.cpp pick_copy is the writer's), for render() and the scene queries.
-int Engine::reader_begin(hipStream_t stream, bool reader) {
-    if (int rc = tick_done.wait(stream, Fence::AnyStream, Fence::Keep)) return rc;  // a no-op when st_tick ran on this stream. Kept: every stream of every frame waits, until st_tick polls it away
-    if (int rc = copy_done.wait(stream, Fence::AnyStream, Fence::Keep)) return rc;  // likewise (st_tick already queued this wait on its own stream)
-    if (reader) {
-        if (rendered_before && last_render_stream != stream) mixed_render_streams = true;  // the null stream is a stream too
-        last_render_stream = stream; rendered_before = true;
-    }
-    return ST_OK;
-}
-int Engine::reader_end(hipStream_t stream, bool lights, bool reads_previous) {
-    if (alternating) if (int rc = sets[live].fence.record(stream)) return rc;
-    if (lights && lights_alternating) if (int rc = light_sets[live_lights].fence.record(stream)) return rc;
-    if (lights && env_live) if (int rc = env_live->fence.record(stream)) return rc;   // (frames: the map is freed behind its last reader)
-    // this reader (a frame, a MOTION AOV) may read previous regions of the posed store: the next skin launch waits for it (st_deform.h deform_read).
-    // Chained: readers on several streams, one event
-    if (reads_previous) if (int rc = deform.previous_read_by(stream)) return rc;
-    return ST_OK;
 }
 
 // ---- render (camera_controller.rs:87-174). Engine::render, at the end of this file, is a short sequence of phases over one Frame:
@@ -626,7 +607,7 @@ struct Frame {
         if (luts_generated_now) { if (int rc = c.ev_setup.record(stream)) return rc; if (int rc = c.ev_setup.wait(c.side_stream)) return rc; }
         // copies st_tick queued without joining the stream (staged uploads, dynamic images): they sit behind frame N on the tick's stream, so a frame that
         // follows a scene change gives up the prim(N+1) / denoiser(N) overlap
-        if (int rc = e.reader_begin(c.side_stream, false)) return rc;  // the tick's uploads: independent of frame N, the overlap stays
+        if (int rc = e.copies.begin(c.side_stream, kReadsNothing)) return rc;  // the tick's uploads: independent of frame N, the overlap stays
         if (c.have_prev_frame_events) { if (int rc = c.ev_prim_ok.wait(c.side_stream)) return rc; }
         if (c.have_prev_frame_events && c.have_lds_done) { if (int rc = c.ev_lds_done.wait(c.side_stream)) return rc; }
         c.have_lds_done = false;   // this frame's denoise() sets it again
@@ -699,9 +680,9 @@ struct Frame {
 
 int Engine::render(CameraState& c, void* out, hipStream_t stream) {
     if (!has_device) return fail(ST_ERR_NO_DEVICE, "render_camera on a host-only engine");
-    if (!scene_uploaded) return fail(ST_ERR_INVALID_ARGUMENT, "st_tick must precede st_render_camera");
+    if (!copies.scene.written) return fail(ST_ERR_INVALID_ARGUMENT, "st_tick must precede st_render_camera");
     ST_HIP(hipSetDevice(device));
-    if (int rc = reader_begin(stream, true)) return rc;
+    if (int rc = copies.begin(stream, kReadsFrame)) return rc;
     Frame f(*this, c, out, stream);
     if (int rc = f.route_output()) return rc;      // display, post-processing, the HDR nodes that are on: where the composing launch and each node write
     if (int rc = f.bind_args()) return rc;         // KArgs: scene, lights, the camera's planes
@@ -710,7 +691,7 @@ int Engine::render(CameraState& c, void* out, hipStream_t stream) {
     f.arm_output();                                // the HDR nodes' argument blocks and steps
     if (int rc = f.s.two_streams ? f.two_streams() : f.serial()) return rc;
     if (int rc = f.finish_output()) return rc;     // the HDR nodes' launches behind the composing launch, post-processing, the meter's finalize
-    if (int rc = reader_end(stream, true, true)) return rc;   // the end of the last frame that reads these copies of the scene and the lights
+    if (int rc = copies.end(stream, kReadsFrame)) return rc;   // the end of the last frame that reads these copies of the scene and the lights
     profile_close();
     ST_HIP(hipGetLastError());
     if (f.mask_split) return fail(ST_ERR_INVALID_ARGUMENT, "the pass mask splits a fused launch (st_debug_last_launches lists the launch groups)");

@@ -167,9 +167,9 @@ void Engine::bake_stale_on_host() {
         if (mesh == meshes.end() || have == instance_triangles.end() || have->second.second - have->second.first != mesh->second.size()) continue;  // the next refresh re-bakes it as dirty
         jobs.push_back({deform.bake_source(inst.id, mesh->second), &inst, inst.baked_material, have->second.first, mesh->second.size()});
         total += mesh->second.size();
-        for (SceneSet& t : sets) { t.dirty_lo = std::min(t.dirty_lo, have->second.first); t.dirty_hi = std::max(t.dirty_hi, have->second.second); }
+        for (SceneSet& t : copies.scene.copy) { t.dirty_lo = std::min(t.dirty_lo, have->second.first); t.dirty_hi = std::max(t.dirty_hi, have->second.second); }
     }
-    for (SceneSet& t : sets) t.pending_moves.clear();
+    for (SceneSet& t : copies.scene.copy) t.pending_moves.clear();
     if (!jobs.empty()) bake_jobs_on_host(jobs, total);
 }
 
@@ -198,7 +198,7 @@ bool Engine::refresh_instances() {
             for (auto& inst : instances) {
                 if (!inst.dirty) continue;
                 inst.dirty = false; inst.host_stale = true;
-                for (SceneSet& t : sets) if (std::find(t.pending_moves.begin(), t.pending_moves.end(), inst.id) == t.pending_moves.end()) t.pending_moves.push_back(inst.id);
+                for (SceneSet& t : copies.scene.copy) if (std::find(t.pending_moves.begin(), t.pending_moves.end(), inst.id) == t.pending_moves.end()) t.pending_moves.push_back(inst.id);
             }
             moved_on_device = true;
             return true;
@@ -243,11 +243,11 @@ bool Engine::refresh_instances() {
         else if (!triangle_free.take(count, &b, &e)) {
             b = triangles.size(); e = b + count;
             triangles.resize(e); prims.resize(e); prim_alive.resize(e, 0); tri_geo.resize(3 * e); tri_attr.resize(4 * e); tri_bounds.resize(2 * e);
-            for (SceneSet& t : sets) t.tri_full = true;
+            for (SceneSet& t : copies.scene.copy) t.tri_full = true;
         }
         jobs.push_back({deform.bake_source(inst.id, mesh->second), &inst, mat->second, b, count});
         total += count;
-        for (SceneSet& t : sets) { t.dirty_lo = std::min(t.dirty_lo, b); t.dirty_hi = std::max(t.dirty_hi, e); }  // slots each device copy still has to receive
+        for (SceneSet& t : copies.scene.copy) { t.dirty_lo = std::min(t.dirty_lo, b); t.dirty_hi = std::max(t.dirty_hi, e); }  // slots each device copy still has to receive
         tree.slots_changed(b, e);
         if (have == instance_triangles.end()) live_prims_ += count;   // (the bake below sets prim_alive for the whole range)
         instance_triangles[inst.id] = {b, e};

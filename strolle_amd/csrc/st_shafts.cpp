@@ -97,7 +97,7 @@ int Engine::shafts_process(const StLightShaftsDesc* desc, const StDisplayDesc* d
     if (int rc = process_target("st_light_shafts_process", display, dst, format, target)) return rc;
     // the live scene copy and light table, with the scene queries' reader bookkeeping (st_query.cpp)
     KArgs scene;
-    if (int rc = query_begin(stream, scene, true)) return rc;
+    if (int rc = query_begin(stream, scene, kReadsScene | kReadsShading)) return rc;
     light_args(scene);
     scene.tile_map = 0u;
     if (int rc = shafts_scratch.acquire({plan.cell_bytes}, shafts_scratch.Grow, stream)) return rc;
@@ -107,7 +107,7 @@ int Engine::shafts_process(const StLightShaftsDesc* desc, const StDisplayDesc* d
     for (uint32_t i = 0; i < 2u; i++) launch_shafts_step(scene, steps, i, stream);
     if (int rc = shafts_scratch.done(stream)) return rc;
     ST_HIP(hipGetLastError());
-    return reader_end(stream, true);
+    return copies.end(stream, kReadsScene | kReadsShading);
 }
 
 }  // namespace st

@@ -1,6 +1,6 @@
 // st_tick.cpp — host engine of libstrolle_hip.so: Engine::tick (lib.rs:301-395): refresh of the stores (materials, instances, lights) + uploads (the
-// triangle-slot arrays, the scene copy's records and tables, images, lights), double-buffered; the tree's decisions and its half of the upload are
-// st_bvh_refresh.cpp's. See st_engine.h.
+// triangle-slot arrays, the scene copy's records and tables, images, lights); the tree's decisions and its half of the upload are
+// st_bvh_refresh.cpp's. Behind it SceneCopies (st_copies.h): which copy a tick writes, what its readers wait for and record. See st_engine.h.
 #include "st_engine.h"
 
 namespace st {
@@ -46,14 +46,11 @@ int Engine::tick(hipStream_t stream) {
     if (has_device) {
         ST_HIP(hipSetDevice(device));
         if (walk_flags_host && (walk_flags_host[0] | walk_flags_host[1]) != 0u) note_walk_overflow();   // a wide walk of an earlier frame dropped a push
-        // Uploads of an earlier tick that no render has waited for yet stay pending until their event has completed: a
-        // tick that uploads nothing must not make a later render on another stream forget them.
-        (void)tick_done.poll(); (void)copy_done.poll();
-        (void)hipGetLastError();  // hipErrorNotReady from the queries is not an error
+        copies.begin_tick();
         if (!skinning) staging.begin_tick();
         TickIo io{stream};
         int rc;
-        if ((rc = upload_scene(plan, io)) || (rc = upload_images(io)) || (rc = upload_lights(io)) || (rc = upload_environment(io)) || (rc = upload_luts(io)) || (rc = end_uploads(io))) return rc;
+        if ((rc = upload_scene(plan, io)) || (rc = upload_images(io)) || (rc = upload_lights(io)) || (rc = upload_environment(io)) || (rc = upload_luts(io)) || (rc = copies.end_uploads(io))) return rc;
     }
     atlas_dirty = false;
     for (auto& kv : cameras) kv.second->frame = frame;  // CameraController::flush
@@ -93,28 +90,13 @@ void Engine::refresh_sun_and_lights() {
     }
     snapshot_lights();
 }
-// Which copy of a double-buffered resource (the scene, the lights) this tick writes, on which stream: the first upload and ST_NO_DOUBLE_BUFFER=1
-// write the live copy in place on the caller's stream (behind the frames queued there); every later change goes to the other copy on copy_stream.
-int Engine::pick_copy(TickIo& io, int live_index, Fence& live_fence, Fence& other_fence, bool written_before, bool& alternating_now, CopyTarget& c) {
-    c = CopyTarget{live_index, io.stream, &io.pageable, false};
-    if (tuning.double_buffer && written_before && !mixed_render_streams) {
-        if (!copy_stream) ST_HIP(hipStreamCreateWithFlags(&copy_stream.h, hipStreamNonBlocking));
-        if (!alternating_now) {  // frames enqueued so far read the live copy without marking their end: mark it now, behind them
-            alternating_now = true;
-            if (int rc = live_fence.record(io.stream)) return rc;
-        }
-        c = CopyTarget{live_index ^ 1, copy_stream, &io.pageable_copy, true};
-        if (int rc = other_fence.wait(copy_stream, Fence::AnyStream, Fence::Clear)) return rc;   // its readers are done first; cleared: the copy is written anew
-    } else if (mixed_render_streams) ST_HIP(hipDeviceSynchronize());  // cameras render on several streams: no single event ends their reads
-    return ST_OK;
-}
 // The scene's device copy: its tree as `plan` says (SceneTree::write), then the attribute records still owed, the transforms, tables and materials.
 int Engine::upload_scene(TreePlan plan, TickIo& io) {
-    if (plan == TreePlan::none && !materials_changed_this_tick && scene_uploaded) return ST_OK;   // (a material or atlas edit changes records, not the tree)
+    if (plan == TreePlan::none && !materials_changed_this_tick && copies.scene.written) return ST_OK;   // (a material or atlas edit changes records, not the tree)
     int rc;
     CopyTarget c;
-    if ((rc = pick_copy(io, live, sets[live].fence, sets[live ^ 1].fence, scene_uploaded, alternating, c))) return rc;
-    SceneSet& t = sets[c.index];
+    if ((rc = copies.pick(io, copies.scene, c))) return rc;
+    SceneSet& t = copies.scene.copy[c.index];
     bool attr_sent = false;
     if ((rc = tree.write(t, plan, c.up, c.pageable, &attr_sent))) return rc;
     if (!attr_sent && (rc = upload_tri_slots(t, TRI_ATTR, !t.valid || t.tri_full, c.up, c.pageable))) return rc;
@@ -132,9 +114,7 @@ int Engine::upload_scene(TreePlan plan, TickIo& io) {
     if ((rc = t.instance_table.upload(instance_table_.data(), instance_table_.size() * sizeof(uint32_t), c.up, staging, c.pageable))) return rc;
     if ((rc = t.materials.upload(gpu_materials.data(), gpu_materials.size() * sizeof(GpuMaterial), c.up, staging, c.pageable))) return rc;
     if ((rc = t.base_packed.upload(material_base_packed.data(), material_base_packed.size() * sizeof(uint32_t), c.up, staging, c.pageable))) return rc;
-    (c.other ? io.copied : io.uploaded) = true;   // (in-place uploads are work on the caller's stream)
-    live = c.index; tree.went_live(plan);
-    scene_uploaded = true;
+    copies.commit(io, copies.scene, c); tree.went_live(plan);
     return ST_OK;
 }
 // The atlas, the device images and the blue noise: in place, on the caller's stream.
@@ -165,24 +145,10 @@ int Engine::upload_images(TickIo& io) {
 int Engine::upload_lights(TickIo& io) {
     if (gpu_lights.size() == uploaded_lights.size() && memcmp(gpu_lights.data(), uploaded_lights.data(), gpu_lights.size() * sizeof(GpuLight)) == 0) return ST_OK;
     CopyTarget c;
-    if (int rc = pick_copy(io, live_lights, light_sets[live_lights].fence, light_sets[live_lights ^ 1].fence, lights_uploaded, lights_alternating, c)) return rc;
-    if (int rc = light_sets[c.index].buf.upload(gpu_lights.data(), gpu_lights.size() * sizeof(GpuLight), c.up, staging, c.pageable)) return rc;
-    live_lights = c.index; lights_uploaded = true;
+    if (int rc = copies.pick(io, copies.lights, c)) return rc;
+    if (int rc = copies.lights.copy[c.index].buf.upload(gpu_lights.data(), gpu_lights.size() * sizeof(GpuLight), c.up, staging, c.pageable)) return rc;
+    copies.commit(io, copies.lights, c);
     uploaded_lights = gpu_lights;
-    (c.other ? io.copied : io.uploaded) = true;
-    return ST_OK;
-}
-// What was uploaded went through page-locked staging, so the caller may change the scene again at once; the next frame's streams wait for these
-// copies' events (reader_begin). Only copies that touch pageable host memory directly (staging full or disabled) make the tick wait for their stream.
-int Engine::end_uploads(TickIo& io) {
-    if (io.copied) {
-        if (int rc = copy_done.record(copy_stream)) return rc;
-        if (int rc = copy_done.wait(io.stream, Fence::AnyStream, Fence::Keep)) return rc;  // the caller's stream: the next frame's kernels (and the staging slot's event) come after the copies; kept for reader_begin
-    }
-    if (int rc = staging.end_tick(io.stream)) return rc;
-    if (io.uploaded) if (int rc = tick_done.record(io.stream)) return rc;
-    if (io.pageable_copy) ST_HIP(hipStreamSynchronize(copy_stream));
-    if ((io.uploaded && io.pageable) || sync_every_tick) ST_HIP(hipStreamSynchronize(io.stream));
     return ST_OK;
 }
 // The tick did everything; these statuses say what the frames rendered so far may have missed, or what the uploaded tree can cost.
@@ -196,6 +162,50 @@ int Engine::report_deep_bvh() {
         fprintf(stderr, "[strolle-hip] warning: %s\n", msg.c_str());
     }
     return tree.report_too_deep();
+}
+// ---- SceneCopies (st_copies.h)
+// Which copy of `pair` this tick writes, on which stream: the first upload and ST_NO_DOUBLE_BUFFER=1 write the live copy in place on the caller's
+// stream (behind the frames queued there), and so do mixed streams, behind a join; every later change goes to the other copy on copy_stream.
+template <class T> int SceneCopies::pick(TickIo& io, CopyPair<T>& pair, CopyTarget& c) {
+    c = CopyTarget{pair.live, io.stream, &io.pageable, false};
+    if (!e.tuning.double_buffer || !pair.written || mixed()) return join_mixed();
+    if (!copy_stream) ST_HIP(hipStreamCreateWithFlags(&copy_stream.h, hipStreamNonBlocking));
+    if (!pair.alternating) {  // frames enqueued so far read the live copy without marking their end: mark it now, behind them
+        pair.alternating = true;
+        if (int rc = pair.current().fence.record(io.stream)) return rc;
+    }
+    c = CopyTarget{pair.live ^ 1, copy_stream, &io.pageable_copy, true};
+    return pair.other().fence.wait(copy_stream, Fence::AnyStream, Fence::Clear);   // its readers are done first; cleared: the copy is written anew
+}
+// What was uploaded went through page-locked staging, so the caller may change the scene again at once; the next frame's streams wait for these
+// copies' events (begin). Only copies that touch pageable host memory directly (staging full or disabled) make the tick wait for their stream.
+int SceneCopies::end_uploads(TickIo& io) {
+    if (io.copied) {
+        if (int rc = copy_done.record(copy_stream)) return rc;
+        if (int rc = copy_done.wait(io.stream, Fence::AnyStream, Fence::Keep)) return rc;  // the caller's stream: the next frame's kernels (and the staging slot's event) come after the copies; kept for begin
+    }
+    if (int rc = e.staging.end_tick(io.stream)) return rc;
+    if (io.uploaded) if (int rc = tick_done.record(io.stream)) return rc;
+    if (io.pageable_copy) ST_HIP(hipStreamSynchronize(copy_stream));
+    if ((io.uploaded && io.pageable) || e.sync_every_tick) ST_HIP(hipStreamSynchronize(io.stream));
+    return ST_OK;
+}
+// A reader's launches on `stream` come behind the tick's uploads, and a reader of its own (reads != 0) is one of the streams the writer has to know of; end: what it read is in use up to here on `stream`.
+int SceneCopies::begin(hipStream_t stream, unsigned reads) {
+    if (int rc = tick_done.wait(stream, Fence::AnyStream, Fence::Keep)) return rc;  // a no-op when st_tick ran on this stream. Kept: every stream of every frame waits, until st_tick polls it away
+    if (int rc = copy_done.wait(stream, Fence::AnyStream, Fence::Keep)) return rc;  // likewise (st_tick already queued this wait on its own stream)
+    if (reads) {
+        if (rendered_before && last_render_stream != stream) mixed_render_streams = true;  // the null stream is a stream too
+        last_render_stream = stream; rendered_before = true;
+    }
+    return ST_OK;
+}
+int SceneCopies::end(hipStream_t stream, unsigned reads) {
+    if ((reads & kReadsScene) && scene.alternating) if (int rc = scene.current().fence.record(stream)) return rc;
+    if ((reads & kReadsLights) && lights.alternating) if (int rc = lights.current().fence.record(stream)) return rc;
+    if ((reads & kReadsEnvironment) && e.env_live) if (int rc = e.env_live->fence.record(stream)) return rc;   // (the map is freed behind its last reader)
+    if (reads & kReadsPrevious) if (int rc = e.deform.previous_read_by(stream)) return rc;   // the next skin launch waits for it (st_deform.h deform_read). Chained: readers on several streams, one event
+    return ST_OK;
 }
 
 }  // namespace st

@@ -1,6 +1,8 @@
 """One fixed sequence of ABI calls for comparing the HIP calls two builds of the library issue (STROLLE_HIP_LIB picks the library):
 Cornell, then the dungeon, 1920 x 1080 Image{denoise}, 30 frames each with one spawn, one light move and one re-pose (a skinned tube,
-deformation motion on) in between, auto-exposure display and FXAA + resize for the last 10, then st_camera_delete and st_engine_destroy.
+deformation motion on) in between, an environment map set and replaced, a look-up table (colour grading on) inserted and replaced, auto-exposure
+display and FXAA + resize for the last 10, a second stream alternating with the first for the last 5 (mixed streams: the light moves back and the
+map and the table are replaced once more there, so that the writer and both retirements join the device), then st_camera_delete and st_engine_destroy.
 Run it under `rocprofv3 --hip-trace --stats -- python tools/ownership_trace.py` once per library; with --summarize DIR it prints the
 per-API call counts of the trace under DIR as one JSON object."""
 import csv
@@ -28,6 +30,9 @@ def run():
     stream = torch.cuda.current_stream().cuda_stream
     mesh, joints, weights = scenes.skinned_tube(24, 12, 6, length=1.2)
     places = {"cornell": ((-0.4, 0.0, 0.0), (0.4, 0.0, -0.3), (0.0, 1.2, 1.0)), "dungeon": ((-6.1, 0.0, -19.0), (-5.4, 0.0, -19.0), (-5.75, 0.8, -18.0))}
+    other = torch.cuda.Stream().cuda_stream
+    sky = lambda seed: (np.random.default_rng(seed).random((8, 16, 3)) * 2.0).astype(np.float32)
+    lut = lambda seed: np.random.default_rng(seed).random((5, 5, 5, 3)).astype(np.float32)
     at = lambda p: np.array([[1, 0, 0, p[0]], [0, 1, 0, p[1]], [0, 0, 1, p[2]]], np.float32)
     for scene in ("cornell", "dungeon"):
         e = Engine(device=0)
@@ -41,7 +46,16 @@ def run():
         e.set_deformation_motion(True)
         e.set_pose(tube, scenes.bend_pose(6, 1.6, 0.0, length=1.2))
         cam = e.create_camera((scenes.cornell_camera if scene == "cornell" else scenes.dungeon_camera)(size, CameraMode.IMAGE, denoise=True))
+        e.insert_lut(41, lut(1)); e.set_color_grading(cam, lut=41, contrast=1.2)         # the table inserted
         for frame in range(30):
+            if frame == 4:
+                e.set_environment(sky(1))                                                    # the map set
+            if frame in (10, 27):
+                e.set_environment(sky(frame))                                                # ... and replaced
+            if frame in (14, 27):
+                e.insert_lut(41, lut(frame))                                                 # the table replaced
+            if frame == 27:
+                e.insert_light(900, Light.point(lamp, 0.1, (2.0,) * 3, 20.0))
             if frame == 8:
                 e.insert_instance(tube + 1, Instance(tube, tube, at(second)))                       # the spawn
             if frame == 12:
@@ -51,8 +65,9 @@ def run():
             if frame == 20:
                 e.set_display(cam, tonemap=Tonemap.ACES_FITTED, auto_exposure=True)
                 e.set_post(cam, fxaa=True, output_size=out_size)
-            e.tick(stream)
-            e.render_camera(cam, out.data_ptr(), stream)
+            s = other if frame >= 25 and frame % 2 else stream
+            e.tick(s)
+            e.render_camera(cam, out.data_ptr(), s)
         torch.cuda.synchronize()
         assert bool(torch.isfinite(out).all())
         e.delete_camera(cam)
