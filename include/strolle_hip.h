@@ -611,7 +611,8 @@ int st_debug_camera_histogram(StEngine* e, StHandle camera, uint32_t bins[64]);
  * - Tiles: FXAA's edge search and the resampler read neighbours across tile edges, so a camera cannot have post-processing (any desc) and
  *   a window (st_camera_set_window, st_dist_set_partition, st_dist_set_grid) at once: ST_ERR_INVALID_ARGUMENT from whichever setter comes
  *   second. For tiled frames the ranks render RGBA32F without post-processing, st_dist_gather assembles the frame on rank 0, and rank 0
- *   runs st_post_process on it.
+ *   runs st_post_process on it. Tiled frames carry no upscaling either ("upscaling" below): rank 0 runs st_upscale_process on the
+ *   gathered frame, behind st_post_process when FXAA is wanted.
  * - Errors: ST_ERR_INVALID_ARGUMENT for a wrong struct_size, unknown flags or filter, exactly one of the two output sides 0, a side above
  *   16384, a threshold that is not finite or is negative, fxaa_subpixel outside [0, 1] (NaN included) and null pointers where they are not
  *   allowed. An unknown camera is ST_ERR_UNKNOWN_CAMERA. Set, get and st_camera_output_size are host work and valid on a host-only engine;
@@ -638,6 +639,82 @@ int st_camera_output_size(StEngine* e, StHandle camera, uint32_t* width, uint32_
  * larger one than any before it, and calls that use it on different streams are ordered by the engine. src and dst must not overlap. */
 int st_post_process(StEngine* e, const StPostDesc* desc, const void* src_rgba32f_device, uint32_t width, uint32_t height,
                     void* dst_device, int dst_format /* StOutputFormat */, void* hip_stream);
+
+/* ---- upscaling (NEW seam): an edge-adaptive upscaler and contrast-adaptive sharpening behind FXAA (st_upscale.cpp, k_upscale.hip). The
+ * construction of FidelityFX Super Resolution 1.0 (EASU and RCAS, publicly documented), restated here in this library's arithmetic rules;
+ * the sharpening step is what Bevy calls ContrastAdaptiveSharpening. The separable Catmull-Rom resampler of the post-processing section
+ * treats every edge as axis-aligned; the upscaler turns its kernel along the local edge, so slanted edges stay edges.
+ * - Order: rendering -> display transform -> FXAA -> upscale -> sharpen -> output format. With FXAA on (st_camera_set_post), the FXAA
+ *   launch writes the render-size RGBA32F plane the upscaler reads. The stage takes the resampler's place: a StPostDesc whose explicit
+ *   output size differs from the render size and this stage exclude each other (one stage owns the resize), ST_ERR_INVALID_ARGUMENT from
+ *   whichever setter comes second; FXAA alone is fine.
+ * - Output size: st_camera_output_size reports the descriptor's output size while the stage is on. output_width, output_height = 0, 0 (or
+ *   the render size) skips the upscale step: sharpen only. sharpness = 0 skips the sharpening step: upscale only. A descriptor that asks
+ *   for neither, like desc == NULL, launches nothing new and changes no argument of any existing launch. This is an upscaler: an output
+ *   side smaller than the render side is an error, and st_camera_update to a render size larger than a live descriptor's output size
+ *   (or, with this stage on, to one that would make a StPostDesc's explicit output size a resize) is refused and leaves the camera as it was.
+ * - Scope: the setting belongs to the camera, takes effect at its next st_render_camera and survives st_camera_update and
+ *   st_engine_set_arithmetic. It changes only what reaches `out_device`: AOVs, picks, planes, exposure metering and history are unchanged.
+ *   BVH-heatmap frames are false colour: they skip both steps and are brought to the output size by the NEAREST resampler, so the buffer
+ *   contract does not depend on the mode. Reference and orthographic frames go through the stage.
+ * - Display-referred: every texel either step reads goes through x' = x > 0 ? (x < 1 ? x : 1) : 0 first (NaN -> 0; the FXAA luma's
+ *   clamp). With ST_DISPLAY_NONE and an HDR output format the stage therefore clips at 1: HDR callers use ST_RESAMPLE_CATMULL_ROM instead.
+ *   Indices are clamped to the image. Alpha is written as 1.
+ * - Arithmetic: float32, evaluated left to right as written, no fused multiply-add, division and square root correctly rounded (plain
+ *   / and sqrt, where FSR uses approximate reciprocals), min and max the post-processing section's, in BOTH builds: tests/upscale_ref.py
+ *   restates all of it in numpy, is normative where this prose leaves a choice, and the kernels match it bit for bit.
+ * - Upscale: per axis i0 and f are the post-processing section's integer evaluation ("Resampling"); (x0, y0), (fx, fy) below. Twelve taps:
+ *         b c            b = (x0, y0 - 1), c = (x0 + 1, y0 - 1)
+ *       e f g h          e = (x0 - 1, y0), f = (x0, y0), g = (x0 + 1, y0), h = (x0 + 2, y0)
+ *       i j k l          i = (x0 - 1, y0 + 1), j = (x0, y0 + 1), k = (x0 + 1, y0 + 1), l = (x0 + 2, y0 + 1)
+ *         n o            n = (x0, y0 + 2), o = (x0 + 1, y0 + 2)
+ *   Luma L = 0.5 B + (0.5 R + G). Four plus-shaped stencils, in the order f, g, j, k, with weights w = (1 - fx)(1 - fy), fx (1 - fy),
+ *   (1 - fx) fy, fx fy and arms (top, left, right, bottom) = (b, e, g, j), (c, f, h, k), (f, i, k, n), (g, j, l, o), add to dir = (0, 0)
+ *   and len = 0; each along x first (p left, q centre, r right), then along y (p top, q centre, r bottom):
+ *     dir.x (dir.y) += (r - p) w;  m = max(|r - q|, |q - p|);  t = m > 0 ? min(|r - p| / m, 1) : 0;  len += (t t) w.
+ *   r2 = dir.x dir.x + dir.y dir.y; r2 < 1 / 32768: dir = (1, 0), else s = sqrt(r2), dir = (dir.x / s, dir.y / s). len = 0.5 len, then
+ *   len = len len. stretch = (dir.x dir.x + dir.y dir.y) / max(|dir.x|, |dir.y|); len2 = (1 + (stretch - 1) len, 1 - 0.5 len);
+ *   lob = 0.5 + ((0.25 - 0.04) - 0.5) len (the constant folded in float32); clp = 1 / lob.
+ *   A tap at (x0 + dx, y0 + dy) has o = (float(dx) - fx, float(dy) - fy); v = ((o.x dir.x + o.y dir.y) len2.x, (-o.x dir.y + o.y dir.x) len2.y);
+ *   d2 = min(v.x v.x + v.y v.y, clp); tb = 0.4 d2 - 1; wB = 1.5625 (tb tb) - 0.5625; ta = lob d2 - 1; wA = ta ta; w = wB wA.
+ *   Per channel sum = sum + c w and wsum = wsum + w, from 0, over the taps in the order b c e f g h i j k l n o; the result is
+ *   sum / wsum when wsum > 0, else tap f's channel, then clamped to the min / max of f, g, j, k: min(max(v, lo), hi).
+ * - Sharpen, at the output size: e the pixel, b, d, f, h its N (y - 1), W, E, S neighbours. Per channel: mn4 = min(min(min(b, d), f), h),
+ *   mx4 likewise; hitMin = mx4 == 0 ? 0 : min(mn4, e) / (4 mx4); den = 4 mn4 - 4; hitMax = den == 0 ? 0 : (1 - max(mx4, e)) / den;
+ *   lobe_c = max(-hitMin, hitMax). lobe = max(-0.1875, min(max(max(lobe_r, lobe_g), lobe_b), 0)) sharpness. With ST_UPSCALE_DENOISE, on
+ *   the lumas (L as above): range = max(max(max(max(bL, dL), fL), hL), eL) - the min likewise; nz = range == 0 ? 0 :
+ *   min(|(((0.25 bL + 0.25 dL) + 0.25 fL) + 0.25 hL) - eL| / range, 1); lobe = lobe (1 - 0.5 nz). Per channel the result is
+ *   ((((lobe b + lobe d) + lobe h) + lobe f) + e) / (4 lobe + 1).
+ * - Tiles: both steps read across tile edges, so the stage and a window (st_camera_set_window, st_dist_set_partition, st_dist_set_grid)
+ *   exclude each other like post-processing does. For tiled frames rank 0 runs st_upscale_process on the gathered frame.
+ * - Errors: ST_ERR_INVALID_ARGUMENT for a wrong struct_size, unknown flags, non-zero pads, exactly one output side 0, a side above 16384,
+ *   an output side smaller than the render side, sharpness outside [0, 1] (NaN included), null pointers where they are not allowed, and
+ *   src and dst overlapping. An unknown camera is ST_ERR_UNKNOWN_CAMERA. Set and get are host work and valid on a host-only engine;
+ *   st_upscale_process returns ST_ERR_NO_DEVICE there. */
+enum { ST_UPSCALE_DENOISE = 1 };           /* the sharpening step's noise limiter */
+typedef struct StUpscaleDesc {             /* 32 B */
+    uint32_t struct_size;                  /* sizeof(StUpscaleDesc) */
+    uint32_t flags;                        /* ST_UPSCALE_* */
+    uint32_t output_width, output_height;  /* 0, 0 = the render size: sharpen only */
+    float sharpness;                       /* 0..1; 0 = no sharpening step; NaN is an error */
+    uint32_t _pad[3];                      /* zero */
+} StUpscaleDesc;
+int st_camera_set_upscale(StEngine* e, StHandle camera, const StUpscaleDesc* desc);   /* NULL = off */
+/* the last desc set (a zeroed desc with struct_size when none was) and whether the stage is on; either pointer may be NULL */
+int st_camera_get_upscale(StEngine* e, StHandle camera, StUpscaleDesc* out, int* enabled);
+/* Stateless, like st_post_process: the same kernels over any RGBA32F device image of width x height, written to dst_device (the desc's
+ * output size, or width x height) in dst_format; a desc that asks for neither step copies the image into the format (unclamped, alpha 1) as
+ * st_post_process without flags does. src and dst must not overlap. A call that runs both steps uses an engine-owned output-size plane, allocated
+ * (with a device sync) only when a call needs a larger one than any before it; calls that use it on different streams are ordered by the
+ * engine. */
+int st_upscale_process(StEngine* e, const StUpscaleDesc* desc, const void* src_rgba32f_device, uint32_t width, uint32_t height,
+                       void* dst_device, int dst_format /* StOutputFormat */, void* hip_stream);
+
+/* Debug seam: how the stage runs when both steps are on. 0: two launches with an output-size RGBA32F plane between them; 1, 2, 3: one
+ * launch whose workgroups upscale an output tile of 64 x 8, 32 x 32 or 64 x 16 pixels plus a one-pixel ring into LDS and sharpen from
+ * there. The result is the same bit for bit (the per-pixel arithmetic is the same); the ring is computed twice. The environment
+ * variable ST_UPSCALE_FUSED sets the same at st_engine_create. Takes effect at the next frame or call. */
+int st_debug_set_upscale_fused(StEngine* e, int tile);
 
 /* ---- bloom (NEW seam): an HDR mip-pyramid glow in front of the display transform (st_bloom.cpp, k_bloom.hip). The first node of Bevy's
  * HDR post chain (bloom -> tonemapping -> FXAA -> upscaling): what tells a viewer how bright a clipped light is.
@@ -1369,7 +1446,7 @@ enum StPassBit {
     ST_PASS_DENOISE_REPROJECT_DI = 1u << 18, ST_PASS_DENOISE_REPROJECT_GI = 1u << 19, ST_PASS_DENOISE_VARIANCE = 1u << 20,
     ST_PASS_DENOISE_WAVELET_0 = 1u << 21, /* ... wavelet pass n = ST_PASS_DENOISE_WAVELET_0 << n, n < 5 */
     ST_PASS_COMPOSITION = 1u << 26, ST_PASS_BVH_HEATMAP = 1u << 27, ST_PASS_REF_TRACING = 1u << 28, ST_PASS_REF_SHADING = 1u << 29,
-    ST_PASS_POST = 1u << 30   /* the launches behind composition, one launch group: fog ("fog" above), depth of field ("depth of field"), motion blur ("motion blur"), bloom ("bloom"), then FXAA and / or the resampler ("post-processing") */
+    ST_PASS_POST = 1u << 30   /* the launches behind composition, one launch group: fog ("fog" above), depth of field ("depth of field"), motion blur ("motion blur"), bloom ("bloom"), then FXAA and / or the resampler ("post-processing"), then the upscaler and / or the sharpening step ("upscaling") */
 };
 int st_debug_set_pass_mask(StEngine* e, uint64_t mask);
 /* Measurement only (tools/pair_matrix.py): the frame's graph is built as always — every fusion of the whole frame — but only the launches

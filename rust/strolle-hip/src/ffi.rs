@@ -292,6 +292,25 @@ extern "C" {
     pub fn st_post_process(e: *mut StEngine, desc: *const StPostDesc, src_rgba32f_device: *const c_void, width: u32, height: u32, dst_device: *mut c_void, dst_format: i32, hip_stream: *mut c_void) -> i32;
 }
 
+// the upscale stage (include/strolle_hip.h "upscaling"): the edge-adaptive upscaler and contrast-adaptive sharpening behind FXAA
+pub const ST_UPSCALE_DENOISE: u32 = 1;
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct StUpscaleDesc {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub output_width: u32,
+    pub output_height: u32,
+    pub sharpness: f32,
+    pub _pad: [u32; 3],
+}
+extern "C" {
+    pub fn st_camera_set_upscale(e: *mut StEngine, camera: u64, desc: *const StUpscaleDesc) -> i32; // null = off
+    pub fn st_camera_get_upscale(e: *mut StEngine, camera: u64, out: *mut StUpscaleDesc, enabled: *mut i32) -> i32;
+    pub fn st_upscale_process(e: *mut StEngine, desc: *const StUpscaleDesc, src_rgba32f_device: *const c_void, width: u32, height: u32, dst_device: *mut c_void, dst_format: i32, hip_stream: *mut c_void) -> i32;
+    pub fn st_debug_set_upscale_fused(e: *mut StEngine, tile: i32) -> i32; // 0 = two launches, 1 / 2 / 3 = one launch over 64 x 8 / 32 x 32 / 64 x 16 tiles
+}
+
 // bloom (include/strolle_hip.h "bloom"): an HDR mip-pyramid glow in front of the display transform
 pub const ST_BLOOM_ADDITIVE: u32 = 1;
 pub const ST_BLOOM_FIREFLY_SUPPRESS: u32 = 2;

@@ -183,6 +183,21 @@ def post_desc(fxaa: bool = False, output_size=None, filter=ResampleFilter.BILINE
                       float(fxaa_edge_threshold_min), float(fxaa_subpixel))
 
 
+class StUpscaleDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("output_width", C.c_uint32), ("output_height", C.c_uint32),
+                ("sharpness", C.c_float), ("_pad", C.c_uint32 * 3)]
+
+
+UPSCALE_DENOISE = 1
+
+
+def upscale_desc(output_size=None, sharpness: float = 0.0, denoise: bool = False) -> StUpscaleDesc:
+    """A StUpscaleDesc: the edge-adaptive upscaler to output_size = (width, height) (None: the render size, sharpen only) and / or the
+    contrast-adaptive sharpening step at `sharpness` in 0..1 (0: none), `denoise`: its noise limiter (include/strolle_hip.h "upscaling")."""
+    ow, oh = output_size if output_size else (0, 0)
+    return StUpscaleDesc(C.sizeof(StUpscaleDesc), UPSCALE_DENOISE if denoise else 0, int(ow), int(oh), float(sharpness))
+
+
 class StMotionBlurDesc(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("samples", C.c_uint32), ("shutter", C.c_float), ("max_radius", C.c_float),
                 ("depth_softness", C.c_float)]
@@ -685,6 +700,11 @@ class _Binding:
             self.camera_get_post = fn("camera_get_post", [vp, u64, P(StPostDesc), P(i32)])
             self.camera_output_size = fn("camera_output_size", [vp, u64, P(u32), P(u32)])
             self.post_process = fn("post_process", [vp, P(StPostDesc), vp, u32, u32, vp, i32, vp])
+        if hasattr(lib, prefix + "camera_set_upscale"):   # the upscale stage (likewise)
+            self.camera_set_upscale = fn("camera_set_upscale", [vp, u64, P(StUpscaleDesc)])
+            self.camera_get_upscale = fn("camera_get_upscale", [vp, u64, P(StUpscaleDesc), P(i32)])
+            self.upscale_process = fn("upscale_process", [vp, P(StUpscaleDesc), vp, u32, u32, vp, i32, vp])
+            self.debug_set_upscale_fused = fn("debug_set_upscale_fused", [vp, i32])
         if hasattr(lib, prefix + "camera_set_bloom"):   # bloom (likewise)
             self.camera_set_bloom = fn("camera_set_bloom", [vp, u64, P(StBloomDesc)])
             self.camera_get_bloom = fn("camera_get_bloom", [vp, u64, P(StBloomDesc), P(i32)])
@@ -1232,6 +1252,23 @@ class Engine(EngineBase):
     def post_process(self, desc: StPostDesc, src_ptr: int, width: int, height: int, dst_ptr: int, dst_format: int = 0, stream: int = 0):
         """st_post_process: FXAA and / or resampling of any RGBA32F device image into dst (the desc's output size) in dst_format."""
         self._check(self._b.post_process(self._h, C.byref(desc), src_ptr, width, height, dst_ptr, int(dst_format), stream))
+
+    # ---- the upscale stage (include/strolle_hip.h "upscaling"): takes effect at the camera's next render
+    def set_upscale(self, camera: int, desc: Optional[StUpscaleDesc] = None, **kw):
+        """st_camera_set_upscale: a StUpscaleDesc, or upscale_desc(**kw) when keywords are given; neither = off."""
+        self._set_stage(self._b.camera_set_upscale, upscale_desc, camera, desc, kw)
+
+    def upscale(self, camera: int):
+        """st_camera_get_upscale: (the last StUpscaleDesc set, whether the stage is on)."""
+        return self._get_stage(self._b.camera_get_upscale, StUpscaleDesc, camera)
+
+    def set_upscale_fused(self, tile: int):
+        """st_debug_set_upscale_fused: 0 = the two steps as two launches, 1 / 2 / 3 = one launch over 64 x 8 / 32 x 32 / 64 x 16 output tiles."""
+        self._check(self._b.debug_set_upscale_fused(self._h, int(tile)))
+
+    def upscale_process(self, desc: StUpscaleDesc, src_ptr: int, width: int, height: int, dst_ptr: int, dst_format: int = 0, stream: int = 0):
+        """st_upscale_process: upscaling and / or sharpening of any RGBA32F device image into dst (the desc's output size) in dst_format."""
+        self._check(self._b.upscale_process(self._h, C.byref(desc), src_ptr, width, height, dst_ptr, int(dst_format), stream))
 
     # ---- bloom (include/strolle_hip.h "bloom"): takes effect at the camera's next render
     def set_bloom(self, camera: int, desc: Optional[StBloomDesc] = None, **kw):

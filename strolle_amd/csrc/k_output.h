@@ -20,6 +20,19 @@ ST_D int out_clampi(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
 ST_D float out_exp(float x) { return exp2_poly_(x * 1.44269504088896341f); }
 ST_D V3 out_colour(float4 c) { return v3(out_min(out_max(c.x, 0.0f), kColourMax), out_min(out_max(c.y, 0.0f), kColourMax), out_min(out_max(c.z, 0.0f), kColourMax)); }
 
+// What k_post.hip and k_upscale.hip both read a display-referred texel and an output pixel's source position with (include/strolle_hip.h
+// "post-processing"): the clamp into [0, 1], the integer evaluation of (o + 0.5) n_src / n_dst, the clamp to four texels' min / max
+ST_D float post_unit(float x) { return x > 0.0f ? (x < 1.0f ? x : 1.0f) : 0.0f; }   // NaN -> 0
+ST_D void post_resample_axis(uint32_t o, uint32_t n_src, uint32_t n_dst, int* i0, float* f) {
+    const int n = (int)((2u * o + 1u) * n_src) - (int)n_dst, d = (int)(2u * n_dst);   // n > -d: floor(n / d) is -1 for every negative n
+    *i0 = n >= 0 ? n / d : -1;
+    *f = (float)(n - *i0 * d) / (float)d;
+}
+ST_D float post_box(float v, float a, float b, float c, float d) {
+    const float lo = out_min(out_min(out_min(a, b), c), d), hi = out_max(out_max(out_max(a, b), c), d);
+    return out_min(out_max(v, lo), hi);
+}
+
 // D of a pixel: in a frame PRIM_GBUFFER_D0.x alone (4 of the texel's 16 B), 0 (sky) read as FLT_MAX; otherwise the float plane as it is
 ST_D float out_frame_depth(const void* depth, size_t at, bool frame) {
     if (frame) { const float d = reinterpret_cast<const float*>(static_cast<const float4*>(depth) + at)[0]; return d == 0.0f ? kFltMax : d; }

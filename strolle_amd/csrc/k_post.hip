@@ -12,7 +12,6 @@ namespace st {
 namespace ST_KNS {
 
 ST_D float4 post_texel(const PostArgs& p, int x, int y) { return p.src[(size_t)out_clampi(y, (int)p.height) * p.width + (size_t)out_clampi(x, (int)p.width)]; }
-ST_D float post_unit(float x) { return x > 0.0f ? (x < 1.0f ? x : 1.0f) : 0.0f; }   // NaN -> 0
 ST_D float post_luma(float4 c) { return sqrtf(display_luma(post_unit(c.x), post_unit(c.y), post_unit(c.z))); }
 ST_D float post_blend(float a, float b, float f) { return f == 0.0f ? a : a + (b - a) * f; }
 ST_D float4 post_blend4(float4 a, float4 b, float f) { return make_float4(post_blend(a.x, b.x, f), post_blend(a.y, b.y, f), post_blend(a.z, b.z, f), 1.0f); }
@@ -134,12 +133,7 @@ void launch_post_fxaa(const PostArgs& p, hipStream_t s) {
 }
 
 // ---- the resampler: one output pixel per thread, a workgroup a 64 x 4 tile of the output; writes the output format through store_output
-// (st_passes.h: the composing kernels' own conversion). Positions are evaluated in integers (post_ref.axis_resample).
-ST_D void post_resample_axis(uint32_t o, uint32_t n_src, uint32_t n_dst, int* i0, float* f) {
-    const int n = (int)((2u * o + 1u) * n_src) - (int)n_dst, d = (int)(2u * n_dst);   // n > -d: floor(n / d) is -1 for every negative n
-    *i0 = n >= 0 ? n / d : -1;
-    *f = (float)(n - *i0 * d) / (float)d;
-}
+// (st_passes.h: the composing kernels' own conversion). Positions are evaluated in integers (post_ref.axis_resample; k_output.h post_resample_axis).
 struct CrWeights { float w0, w1, w2, w3; };
 ST_D CrWeights post_cr_weights(float f) {
     CrWeights w;
@@ -152,10 +146,6 @@ ST_D CrWeights post_cr_weights(float f) {
 ST_D float post_cr1(float t0, float t1, float t2, float t3, const CrWeights& w, float f) { return f == 0.0f ? t1 : ((t0 * w.w0 + t1 * w.w1) + t2 * w.w2) + t3 * w.w3; }
 ST_D float4 post_cr4(float4 t0, float4 t1, float4 t2, float4 t3, const CrWeights& w, float f) {
     return make_float4(post_cr1(t0.x, t1.x, t2.x, t3.x, w, f), post_cr1(t0.y, t1.y, t2.y, t3.y, w, f), post_cr1(t0.z, t1.z, t2.z, t3.z, w, f), 1.0f);
-}
-ST_D float post_box(float v, float a, float b, float c, float d) {
-    const float lo = out_min(out_min(out_min(a, b), c), d), hi = out_max(out_max(out_max(a, b), c), d);
-    return out_min(out_max(v, lo), hi);
 }
 
 template <int FILTER>

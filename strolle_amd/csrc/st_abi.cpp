@@ -255,6 +255,7 @@ int st_camera_update(StEngine* e, StHandle h, const StCamera* c) {
     auto it = en->cameras.find(h);
     if (it == en->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
     CameraState& s = *it->second;
+    if (int rc = Engine::upscale_camera_update(s, c->width, c->height)) return rc;   // refused: the camera stays as it was
     const bool invalidated = s.desc.mode != c->mode || s.desc.denoise != c->denoise || s.desc.depth != c->depth || s.desc.width != c->width || s.desc.height != c->height;
     s.desc = *c;
     s.prev = s.curr;
@@ -287,7 +288,8 @@ int st_camera_set_window(StEngine* e, StHandle h, uint32_t x0, uint32_t y0, uint
     ST_REQUIRE(full || !s.display_auto(), "a window on a camera with auto-exposure would meter the tile alone (include/strolle_hip.h \"display transforms\")");
     // each stage's own rule (st_output_chain.h), as its setter states it; fog and colour grading carry none
     const std::initializer_list<std::pair<bool, const WindowRule*>> stages = {{s.post.on, s.post.window}, {s.bloom.on, s.bloom.window}, {s.mblur.on, s.mblur.window},
-                                                                              {s.dof.on, s.dof.window}, {s.fog.on, s.fog.window}, {s.shafts.on, s.shafts.window}, {s.grade.on, s.grade.window}};
+                                                                              {s.dof.on, s.dof.window}, {s.fog.on, s.fog.window}, {s.shafts.on, s.shafts.window}, {s.grade.on, s.grade.window},
+                                                                              {s.upscale.on, s.upscale.window}};
     for (const auto& st : stages) if (!full && st.first && st.second) return fail(ST_ERR_INVALID_ARGUMENT, window_refused_by(*st.second));
     s.row0 = y0; s.row1 = y1; s.col0 = x0; s.col1 = x1;
     return ST_OK;
@@ -351,6 +353,26 @@ int st_camera_output_size(StEngine* e, StHandle h, uint32_t* width, uint32_t* he
 int st_post_process(StEngine* e, const StPostDesc* desc, const void* src, uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
     ST_REQUIRE(e, "null engine");
     return E(e)->post_process(desc, src, width, height, dst, dst_format, static_cast<hipStream_t>(stream));
+}
+
+// ---- the upscale stage (st_upscale.cpp)
+int st_camera_set_upscale(StEngine* e, StHandle h, const StUpscaleDesc* desc) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    return E(e)->set_upscale(*it->second, desc);
+}
+int st_camera_get_upscale(StEngine* e, StHandle h, StUpscaleDesc* out, int* enabled) { return camera_get(e, h, &CameraState::upscale, out, enabled); }
+int st_upscale_process(StEngine* e, const StUpscaleDesc* desc, const void* src, uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
+    ST_REQUIRE(e, "null engine");
+    return E(e)->upscale_process(desc, src, width, height, dst, dst_format, static_cast<hipStream_t>(stream));
+}
+
+int st_debug_set_upscale_fused(StEngine* e, int tile) {
+    ST_REQUIRE(e, "null engine");
+    ST_REQUIRE(tile >= 0 && tile <= 3, "tile is 0 (two launches), 1 (64 x 8), 2 (32 x 32) or 3 (64 x 16)");
+    E(e)->upscale_fused = (uint32_t)tile;
+    return ST_OK;
 }
 
 // ---- bloom (st_bloom.cpp)

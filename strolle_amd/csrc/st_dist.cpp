@@ -288,6 +288,7 @@ static int display_window_check(const CameraState& c, const StDistRect& w) {
     const bool full = w.x0 == 0u && w.y0 == 0u && w.x1 == c.desc.width && w.y1 == c.desc.height;
     if (!full && c.display_auto()) return fail(ST_ERR_INVALID_ARGUMENT, "a tile window on a camera with auto-exposure would meter the tile alone");
     if (!full && c.post.on) return fail(ST_ERR_INVALID_ARGUMENT, "a tile window on a camera with post-processing: FXAA and the resampler read across tile edges (st_post_process serves gathered frames)");
+    if (!full && c.upscale.on) return fail(ST_ERR_INVALID_ARGUMENT, "a tile window on a camera with upscaling: both steps read across tile edges (st_upscale_process serves gathered frames)");
     if (!full && c.bloom.on) return fail(ST_ERR_INVALID_ARGUMENT, "a tile window on a camera with bloom: the pyramid reads far across tile edges (st_bloom_process serves gathered frames)");
     if (!full && c.mblur.on) return fail(ST_ERR_INVALID_ARGUMENT, "a tile window on a camera with motion blur: the gather reads up to 32 pixels across tile edges (st_motion_blur_process serves gathered frames)");
     if (!full && c.dof.on) return fail(ST_ERR_INVALID_ARGUMENT, "a tile window on a camera with depth of field: the gather reads up to 32 pixels across tile edges (st_dof_process serves gathered frames)");

@@ -54,6 +54,7 @@ Engine::Engine() {
     tuning_from_environment(tuning);
     staging.enabled = tuning.staging != 0u;
     if (const char* x = getenv("ST_BLOOM_TAIL_BYTES")) bloom_tail_wanted = atoi(x);   // -1 / n: the bloom chain's fused tail (st_bloom.cpp; off by default)
+    if (const char* x = getenv("ST_UPSCALE_FUSED")) upscale_fused = (uint32_t)atoi(x) <= 3u ? (uint32_t)atoi(x) : 0u;   // the upscale stage's two steps in one launch (st_upscale.cpp)
     if (const char* x = getenv("ST_EXP")) exp_flags = (uint32_t)strtoul(x, nullptr, 0);
     if (const char* ex = getenv("ST_EXACT")) if (atoi(ex) != 0) { arithmetic = ST_ARITH_EXACT; L = launchers_exact(); }
 }

@@ -6,6 +6,7 @@
 //   st_render.cpp       per-camera buffers and Engine::render: the per-frame pass graph in phases, on two HIP streams; present hand-over
 //   st_display.cpp      display transforms: exposure, tone mapping, the auto-exposure state
 //   st_post.cpp         output post-processing: FXAA and the resampler
+//   st_upscale.cpp      the upscale stage behind FXAA: the edge-adaptive upscaler and the sharpening step
 //   st_bloom.cpp        bloom: the plan, the chain of launches
 //   st_motion_blur.cpp  motion blur: the plan, its three launches
 //   st_dof.cpp          depth of field: the plan (host constants, tap table), its three launches
@@ -404,6 +405,11 @@ struct CameraState {
     NodeSetting<StMotionBlurDesc, 4> mblur{&kMBlurWindow};   // st_motion_blur.cpp. [0] the HDR plane, [1] (r, Z) per pixel, [2] the tile vectors, [3] their 3 x 3 neighbour maxima
     NodeSetting<StBloomDesc, 2> bloom{&kBloomWindow};        // st_bloom.cpp. [0] the HDR plane, [1] the pyramid (one allocation of float4 mips)
     NodeSetting<StColorGradingDesc, 1> grade{nullptr};       // st_grade.cpp. [0] the HDR plane. Pointwise: a window does not exclude it
+    // The upscale stage behind FXAA (st_upscale.cpp): it reads post.planes ([1] with FXAA on, else [0]); [0] here is the output-size RGBA32F plane
+    // between the upscaler and the sharpening step, grown, never shrunk
+    NodeSetting<StUpscaleDesc, 1> upscale{&kUpscaleWindow};
+    bool upscale_resizes() const { return upscale.on && upscale.desc.output_width != 0u && (upscale.desc.output_width != desc.width || upscale.desc.output_height != desc.height); }
+    bool upscale_sharpens() const { return upscale.on && upscale.desc.sharpness > 0.0f; }
     // Which frames run a node that is on. Heatmap frames are false colour; heatmap and reference frames run no primary-visibility pass, so they
     // have no G-buffer and no velocity map; the nodes that derive a pixel's ray or the focal length need a perspective projection.
     bool has_gbuffer() const { return desc.mode != ST_MODE_BVH_HEATMAP && desc.mode != ST_MODE_REFERENCE; }
@@ -413,8 +419,8 @@ struct CameraState {
     // gbuffer_depth_read[parity] is recorded behind the last of them and the next primary-visibility launch of that parity waits for it
     // (DESIGN.md "Fog", "Light shafts")
     Fence gbuffer_depth_read[2];
-    uint32_t out_width() const { return post.on && post.desc.output_width != 0u ? post.desc.output_width : desc.width; }
-    uint32_t out_height() const { return post.on && post.desc.output_width != 0u ? post.desc.output_height : desc.height; }
+    uint32_t out_width() const { return upscale_resizes() ? upscale.desc.output_width : post.on && post.desc.output_width != 0u ? post.desc.output_width : desc.width; }
+    uint32_t out_height() const { return upscale_resizes() ? upscale.desc.output_height : post.on && post.desc.output_width != 0u ? post.desc.output_height : desc.height; }
     // A present copy still in flight writes the caller's host memory: it lands before the stream goes. Everything else goes with its member —
     // the caller has made the device current and joined it (st_camera_delete, ~Engine).
     void join_present() { if (present_stream) (void)hipStreamSynchronize(present_stream); }
@@ -681,6 +687,15 @@ struct Engine {
     int set_post(CameraState& c, const StPostDesc* desc);
     int post_process(const StPostDesc* desc, const void* src, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
     FencedPlanes<1> post_scratch;   // st_post_process's intermediate plane (FXAA -> resampler): it only grows; calls on different streams take turns
+    // ---- the upscale stage (st_upscale.cpp): the upscaler, then the sharpening step; `mid` (output size, RGBA32F) carries one to the other
+    // `fused` (Engine::upscale_fused; 0 = two launches): both steps in one launch when both run — no plane between them
+    struct UpscalePlan { bool upscale = false, sharpen = false; uint32_t fused = 0; UpscaleArgs up{}, sh{}, fu{}; double upscale_bytes = 0.0, sharpen_bytes = 0.0, fused_bytes = 0.0; size_t mid_bytes = 0; };
+    static UpscalePlan upscale_plan(const StUpscaleDesc& d, const void* src, uint32_t w, uint32_t h, void* mid, void* dst, uint32_t format, uint32_t fused);
+    int set_upscale(CameraState& c, const StUpscaleDesc* desc);
+    static int upscale_camera_update(const CameraState& c, uint32_t new_width, uint32_t new_height);   // st_camera_update's question: may the render size become this?
+    int upscale_process(const StUpscaleDesc* desc, const void* src, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
+    uint32_t upscale_fused = 0u;   // st_debug_set_upscale_fused / ST_UPSCALE_FUSED: 0 two launches, 1 .. 3 the fused launch's tile (k_upscale.hip)
+    FencedPlanes<1> upscale_scratch;   // st_upscale_process's plane between the two steps: it only grows; calls on different streams take turns
     // ---- the HDR nodes (st_output_chain.h). Each has its checks, a plan where frames of a size share host work, `*_steps`: the argument
     // block(s) and the OutputStep list of its launches from a NodeSource into a NodeTarget, `launch_*_step`, the setter, and the stateless call
     // ---- bloom (st_bloom.cpp)

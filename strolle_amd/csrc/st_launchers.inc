@@ -109,3 +109,9 @@ ST_LAUNCHER(launch_shafts_march, (const KArgs& a, const ShaftsArgs& p, hipStream
 ST_LAUNCHER(launch_shafts_apply, (const ShaftsArgs& p, hipStream_t s))
 // colour grading (k_grade.hip; st_grade.cpp): one pointwise launch over the window, one workgroup per 32 x 8 pixels; the last HDR node
 ST_LAUNCHER(launch_grade, (const GradeArgs& p, hipStream_t s))
+// the upscale stage (k_upscale.hip; st_upscale.cpp): the edge-adaptive upscaler over a display-referred RGBA32F image (dst: out_width x out_height,
+// any output format) and the sharpening step at one size (src: RGBA32F; dst: any output format)
+ST_LAUNCHER(launch_upscale, (const UpscaleArgs& p, hipStream_t s))
+ST_LAUNCHER(launch_sharpen, (const UpscaleArgs& p, hipStream_t s))
+// ... and both steps in one launch, the upscaled tile and its one-pixel ring in LDS (`tile`: 1 = 64 x 8 output pixels per workgroup, 2 = 32 x 32, 3 = 64 x 16)
+ST_LAUNCHER(launch_upscale_sharpen, (const UpscaleArgs& p, uint32_t tile, hipStream_t s))

@@ -15,10 +15,16 @@ struct WindowRule { const char* node; const char* why; };
 inline std::string refuses_window(const WindowRule& r) { return std::string(r.node) + " on a camera with a window" + r.why; }
 inline std::string window_refused_by(const WindowRule& r) { return std::string("a window on a camera with ") + r.node + r.why; }
 constexpr WindowRule kPostWindow{"post-processing", ": FXAA and the resampler read across tile edges (include/strolle_hip.h \"post-processing\")"};
+constexpr WindowRule kUpscaleWindow{"upscaling", ": both steps read across tile edges (include/strolle_hip.h \"upscaling\")"};
 constexpr WindowRule kBloomWindow{"bloom", ": the pyramid reads far across tile edges (include/strolle_hip.h \"bloom\")"};
 constexpr WindowRule kMBlurWindow{"motion blur", ": the gather reads up to 32 pixels across tile edges (include/strolle_hip.h \"motion blur\")"};
 constexpr WindowRule kDofWindow{"depth of field", ": the gather reads up to 32 pixels across tile edges (include/strolle_hip.h \"depth of field\")"};
 constexpr WindowRule kShaftsWindow{"light shafts", ": the apply launch reads neighbouring cells across tile edges (include/strolle_hip.h \"light shafts\")"};
+
+// Why upscaling cannot serve a camera whose post-processing resizes, stated alike by st_camera_set_upscale and st_camera_set_post
+constexpr const char* kOneResizeWhy = ": one stage owns the resize (include/strolle_hip.h \"upscaling\")";
+inline std::string upscale_refuses_resize() { return std::string("upscaling on a camera with post-processing that resizes") + kOneResizeWhy; }
+inline std::string resize_refused_by_upscale() { return std::string("post-processing that resizes on a camera with upscaling") + kOneResizeWhy; }
 
 // A camera's setting of one stage of the output chain: the last descriptor set, whether it is on, and the scratch planes its frames use
 // (plane[0] of an HDR node: the render-size RGBA32F plane it reads). It survives st_camera_update; the planes are made by the first frame

@@ -23,7 +23,12 @@ static int check_post(const StPostDesc& d) {
 }
 
 int Engine::set_post(CameraState& c, const StPostDesc* desc) {
-    return set_node(c.windowed(), c.post, desc, check_post);
+    return set_node(c.windowed(), c.post, desc, [&](const StPostDesc& d) {
+        if (int rc = check_post(d)) return rc;
+        // the upscale stage takes the resampler's place (st_upscale.cpp): FXAA alone is fine
+        if (c.upscale.on && d.output_width != 0u && (d.output_width != c.desc.width || d.output_height != c.desc.height)) return fail(ST_ERR_INVALID_ARGUMENT, resize_refused_by_upscale());
+        return (int)ST_OK;
+    });
 }
 
 // FXAA (when `fxaa`) over src, then the resampler when the sizes differ — or when nothing else would write dst. FXAA alone writes dst in

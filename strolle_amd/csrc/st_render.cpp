@@ -165,6 +165,7 @@ struct HdrWork {   // what the nodes that are on hold for one frame: node_plan's
 // the frame's target, in its format, through the display transform (`target`).
 struct OutputRoute {
     bool post_fxaa = false, post = false, keep_velocity = false /* a node that is on reads the velocity map */;
+    bool up_steps = false /* the upscale stage runs behind FXAA (st_upscale.cpp) */, up_nearest = false /* a heatmap frame under it: the NEAREST resampler */;
     void* hdr_plane[kHdrNodes] = {};   // the render-size RGBA32F plane each node that is on reads, in chain order; null: the node is off
     Fence* planes_read[kHdrNodes] = {};   // ... and the fence of the node's planes
     bool on(int n) const { return hdr_plane[n] != nullptr; }
@@ -316,8 +317,14 @@ struct Frame {
         if (int rc = e.display_begin(c, stream, mode == ST_MODE_BVH_HEATMAP, disp)) return rc;
         const size_t plane = (size_t)c.desc.width * c.desc.height * sizeof(float4);
         const bool post_resample = out && c.post_resizes();
-        r.post_fxaa = out && c.post_fxaa(); r.post = r.post_fxaa || post_resample;
-        if (r.post) if (int rc = c.post.planes.acquire({plane, r.post_fxaa && post_resample ? plane : 0}, c.post.planes.Exact, stream)) return rc;
+        r.up_steps = out && mode != ST_MODE_BVH_HEATMAP && (c.upscale_resizes() || c.upscale_sharpens());
+        r.up_nearest = out && mode == ST_MODE_BVH_HEATMAP && c.upscale_resizes();
+        r.post_fxaa = out && c.post_fxaa(); r.post = r.post_fxaa || post_resample || r.up_steps || r.up_nearest;
+        if (r.post) if (int rc = c.post.planes.acquire({plane, r.post_fxaa && (post_resample || r.up_steps) ? plane : 0}, c.post.planes.Exact, stream)) return rc;
+        if (r.up_steps) {   // the output-size plane between the two steps, when both run
+            const size_t mid = Engine::upscale_plan(c.upscale.desc, nullptr, c.desc.width, c.desc.height, nullptr, nullptr, c.out_format, e.upscale_fused).mid_bytes;
+            if (int rc = c.upscale.planes.acquire({mid}, c.upscale.planes.Grow, stream)) return rc;
+        }
         for (int n = 0; n < kHdrNodes; n++) if (out && node_wanted(n)) if (int rc = node_plan(n)) return rc;
         for (int n = 0; n < kHdrNodes; n++) r.keep_velocity |= r.on(n) && kHdrNode[n].reads_velocity;
         r.frame_out = r.post ? c.post.planes.plane[0].ptr : out; r.frame_format = r.post ? (uint32_t)ST_FORMAT_RGBA32F : c.out_format;
@@ -666,10 +673,26 @@ struct Frame {
             if (n == kNodeGrade && work.grade_lut) if (int rc = work.grade_lut->fence.record(stream)) return rc;   // the table leaves behind its last reader (st_grade.cpp upload_luts)
             if (n == last_depth_reader) if (int rc = c.gbuffer_depth_read[c.frame % 2u].record(stream)) return rc;
         }
-        if (route.post) {   // at most two kernels
-            const Engine::PostPlan plan = Engine::post_plan(c.post.desc, route.post_fxaa, c.post.planes.plane[0].ptr, c.desc.width, c.desc.height, c.post.planes.plane[1].ptr, out, c.out_format);
-            if (plan.fxaa) run(KS_POST_FXAA, ST_PASS_POST, [&] { e.L.launch_post_fxaa(plan.fx, cur); }, plan.fxaa_bytes);
-            if (plan.resample) run(KS_POST_RESAMPLE, ST_PASS_POST, [&] { e.L.launch_post_resample(plan.rs, cur); }, plan.resample_bytes);
+        if (route.post) {   // at most two kernels; with the upscale stage (st_upscale.cpp) behind FXAA at most three
+            void* const composed = c.post.planes.plane[0].ptr; void* const fxaa_out = c.post.planes.plane[1].ptr;
+            const uint32_t w = c.desc.width, h = c.desc.height;
+            const bool up = route.up_steps;
+            if (route.up_nearest) {   // a heatmap frame under the upscale stage: false colour, brought to the output size and not sharpened
+                StPostDesc nearest{}; nearest.output_width = c.upscale.desc.output_width; nearest.output_height = c.upscale.desc.output_height; nearest.filter = ST_RESAMPLE_NEAREST;
+                const Engine::PostPlan plan = Engine::post_plan(nearest, false, composed, w, h, nullptr, out, c.out_format);
+                run(KS_POST_RESAMPLE, ST_PASS_POST, [&] { e.L.launch_post_resample(plan.rs, cur); }, plan.resample_bytes);
+            } else if (route.post_fxaa || !up) {   // under the upscale stage FXAA writes the render-size plane the upscaler reads
+                const Engine::PostPlan plan = Engine::post_plan(c.post.desc, route.post_fxaa, composed, w, h, fxaa_out, up ? fxaa_out : out, up ? (uint32_t)ST_FORMAT_RGBA32F : c.out_format);
+                if (plan.fxaa) run(KS_POST_FXAA, ST_PASS_POST, [&] { e.L.launch_post_fxaa(plan.fx, cur); }, plan.fxaa_bytes);
+                if (plan.resample) run(KS_POST_RESAMPLE, ST_PASS_POST, [&] { e.L.launch_post_resample(plan.rs, cur); }, plan.resample_bytes);
+            }
+            if (up) {
+                const Engine::UpscalePlan plan = Engine::upscale_plan(c.upscale.desc, route.post_fxaa ? fxaa_out : composed, w, h, c.upscale.planes.plane[0].ptr, out, c.out_format, e.upscale_fused);
+                if (plan.fused) run(KS_UPSCALE_SHARPEN, ST_PASS_POST, [&] { e.L.launch_upscale_sharpen(plan.fu, plan.fused, cur); }, plan.fused_bytes);
+                else if (plan.upscale) run(KS_UPSCALE, ST_PASS_POST, [&] { e.L.launch_upscale(plan.up, cur); }, plan.upscale_bytes);
+                if (plan.sharpen && !plan.fused) run(KS_SHARPEN, ST_PASS_POST, [&] { e.L.launch_sharpen(plan.sh, cur); }, plan.sharpen_bytes);
+                if (int rc = c.upscale.planes.done(stream)) return rc;
+            }
             if (int rc = c.post.planes.done(stream)) return rc;
         }
         if (route.comp_disp.meter && out) if (int rc = e.display_finalize(c, stream)) return rc;

@@ -94,6 +94,14 @@ struct PostArgs {
     float edge_threshold, edge_threshold_min, subpixel;   // FXAA, defaults resolved by the host
 };
 
+// The upscale stage (include/strolle_hip.h "upscaling"; st_upscale.cpp, k_upscale.hip): one launch's arguments. The upscaler reads `src`
+// (width x height RGBA32F) and writes out_width x out_height; the sharpening step reads and writes width x height. Both store `format`.
+struct UpscaleArgs {
+    const float4* src; void* dst;
+    uint32_t width, height, out_width, out_height, format, denoise;
+    float sharpness;
+};
+
 // Bloom (include/strolle_hip.h "bloom"; st_bloom.cpp, k_bloom.hip): one launch's arguments. A downsample reads `src` (sw x sh) and writes
 // `dst` (dw x dh float4, ceil(sw / 2) x ceil(sh / 2)); an upsample reads `src` (sw x sh) and blends it into `dst` (dw x dh float4) in place
 // with `factor`; the composite upsamples `src` (mip 0; sw == 0: no level, nothing is added) onto `base` (the dw x dh composed frame), runs
