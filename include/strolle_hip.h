@@ -1157,8 +1157,8 @@ int st_light_shafts_process(StEngine* e, const StLightShaftsDesc* desc, const St
  * it. The sixth and last HDR node: it reads its render-size RGBA32F plane, grades the scene-referred colour (A), applies the camera's
  * display transform as the last node of the chain always does (B), grades the display-referred result (C) and writes the frame's target
  * in its format: `out`, or the post-processing plane in front of FXAA. One pointwise launch (ST_PASS_POST, profile slot "color_grading").
- * - Order: rendering -> fog -> light shafts -> depth of field -> motion blur -> bloom -> colour grading (A, display transform, C) -> FXAA
- *   -> resample -> output format.
+ * - Order: rendering -> fog -> light shafts -> depth of field -> motion blur -> bloom -> lens effects ("lens effects" below) -> colour
+ *   grading (A, display transform, C) -> FXAA -> resample -> output format.
  * - Scope: as fog's. The setting belongs to the camera, takes effect at its next st_render_camera, survives st_camera_update and
  *   st_engine_set_arithmetic and changes only what is written to `out_device`: AOVs, picks, scene queries, st_camera_read_buffer, the HDR
  *   history and the auto-exposure metering (it meters the composed frame) are unchanged. desc == NULL turns it off: the frame then launches
@@ -1262,6 +1262,105 @@ int st_color_grading_process(StEngine* e, const StColorGradingDesc* desc, const 
  * tabs are fine. ST_ERR_UNSUPPORTED: LUT_1D_SIZE, any other domain, an unknown keyword. ST_ERR_PARSE: too few or too many rows, a
  * non-number, a non-finite value, a size outside 2..65. Own code (st_cube.h); no engine needed. */
 int st_decode_cube(const void* bytes, size_t size, float* out_rgb, size_t capacity_floats, uint32_t* lut_size);
+
+/* ---- lens effects (NEW seam): radial distortion, chromatic fringing, vignette and film grain between bloom and colour grading
+ * (st_lens.cpp, k_lens.hip). What Unity's and Unreal's stacks do in the pass between bloom and grading, and Bevy's ChromaticAberration: the
+ * seventh HDR node. It reads its render-size RGBA32F plane and writes the plane colour grading reads, else the frame's target in its format
+ * through the display transform: `out`, or the post-processing plane in front of FXAA. One launch (ST_PASS_POST, profile slot "lens"):
+ * a gather of up to 16 bilinear look-ups per pixel with the distortion or the fringe step, a pointwise pass without them.
+ * - Order: rendering -> fog -> light shafts -> depth of field -> motion blur -> bloom -> lens effects -> colour grading (A, display
+ *   transform, C) -> FXAA -> resample / upscale -> output format. The lens sees the glow bloom added (a real lens bends the bloomed
+ *   image) and grading sees the lens's result (grain is scene-referred and is graded like the light it rides on).
+ * - Scope: as fog's and grading's. The setting belongs to the camera, takes effect at its next st_render_camera, survives st_camera_update
+ *   and st_engine_set_arithmetic and changes only what is written to `out_device`: AOVs, picks, scene queries, st_camera_read_buffer, the
+ *   HDR history and the auto-exposure metering (it meters the composed frame) are unchanged. desc == NULL turns it off: the frame then
+ *   launches the kernels it launches without the setting, with the same arguments. A descriptor that is neutral in every step is on, but
+ *   writes what off writes: a skipped step leaves the bits alone. ST_MODE_BVH_HEATMAP frames skip the node (false colour);
+ *   ST_MODE_REFERENCE frames and non-perspective projections pass through it: it needs neither a G-buffer nor a projection.
+ * - Windows and tiles: distortion and fringing read far across tile edges, so a camera cannot have lens effects (any desc) and a window
+ *   (st_camera_set_window / st_camera_set_rows, st_dist_set_partition, st_dist_set_grid) at once: ST_ERR_INVALID_ARGUMENT from whichever
+ *   setter comes second. For tiled frames the ranks render without it, st_dist_gather assembles the frame on rank 0, and rank 0 runs
+ *   st_lens_process on the gathered plane (behind st_bloom_process, in front of st_color_grading_process). It needs the colour plane only.
+ * - Arithmetic: everything is float32, evaluated left to right as written, no fused multiply-add, division correctly rounded, in BOTH
+ *   builds; there is no transcendental. tests/lens_ref.py restates all of it in numpy (lens_f32) and the kernel matches it bit for bit.
+ *   min, max and clamp01 are the post-processing section's (NaN rule), BILINEAR is that section's look-up (indices clamped to the image, an
+ *   axis with f == 0 takes texel a itself), colour(c) = min(max(c, 0), 65504) per channel (NaN becomes 0).
+ * - Host constants (st_lens_plan; in double from the float fields, each rounded to float once): cx = W / 2, cy = H / 2,
+ *   inv_hd2 = 1 / (cx^2 + cy^2). Tap table: without the fringe step one tap, tap_scale 1, weights (1, 1, 1). With it n = fringe_taps,
+ *   t_i = i / (n - 1), tap_scale[i] = 1 + fringe (2 t_i - 1); the spectral tents wR = max(1 - 2 t, 0), wG = 1 - |2 t - 1|,
+ *   wB = max(2 t - 1, 0), each divided by its sum over the taps (summed in index order): n = 3 gives the classic three single-channel
+ *   taps, and a constant image stays constant within the weights' rounding. fit = 1 without ST_LENS_FIT. With it, over the centres of
+ *   the frame's border pixels and both axes, fit = min of cx / (|u| f(r2) scale T) for u != 0 and cy / (|v| f(r2) scale T) for v != 0,
+ *   with u, v, r2, f as below evaluated in double and T the largest tap_scale (as rounded): the largest factor at which no tap of any
+ *   output pixel has its source position outside [0, W] x [0, H]; the bound on k1, k2 makes |u| f(r2) grow with |u| along a row, so the
+ *   border binds. An axis with offset 0 constrains nothing: a 1 x 1 frame has fit 1. scale_eff = scale fit. steps = the steps whose
+ *   parameters are not neutral: distortion (k1 != 0 or k2 != 0 or scale_eff != 1), fringe (fringe != 0), vignette (vignette_intensity
+ *   != 0), grain (grain_intensity != 0).
+ * - Per output pixel (x, y), absolute coordinates: u = (x + 0.5) - cx, v = (y + 0.5) - cy (both exact in float);
+ *   r2 = (u u + v v) inv_hd2 (1 at the frame's corner); f = (k2 r2 + k1) r2 + 1; g = f scale_eff, and g = 1 without the distortion step.
+ * - Taps (distortion or fringe step): tap i reads BILINEAR of colour(texel) at the continuous position (u s + cx, v s + cy) with
+ *   s = g tap_scale[i]. Each channel's sum starts at 0 and runs over the taps in index order, sum = sum + tap weight; taps whose three
+ *   weights are all 0 are skipped. With g = 1 and tap_scale 1 the position is (x + 0.5, y + 0.5) exactly, both fractions are 0 and the
+ *   tap is colour(the pixel's own texel). With neither step the pixel takes its own texel, and keeps its four words, alpha and NaN
+ *   included, unless a later step runs; a later step starts from colour(texel).
+ * - Vignette, at the output pixel: m = r2 with ST_LENS_VIGNETTE_ROUND, else m = ((u / cx) (u / cx) + (v / cy) (v / cy)) 0.5, an ellipse
+ *   that follows the frame (both are 1 at the corner). q = 1 + m vignette_falloff; fall = 1 / (q q) (the cos^4 law with
+ *   tan^2 theta = m vignette_falloff); colour = colour ((1 - a) + a fall) per channel, a = vignette_intensity.
+ * - Grain, multiplicative in scene-referred light (photographic noise is relative to exposure): the cell is (x / grain_size,
+ *   y / grain_size) in integers; s = grain_seed, plus the camera's frame counter (the one the pass seeds take; st_debug_world's
+ *   next_frame - 1 behind a tick) under ST_LENS_GRAIN_ANIMATE, modulo 2^32; h = pcg(cell_x + pcg(cell_y + s)) in 32-bit unsigned
+ *   arithmetic with one PCG round pcg(v): v = v 747796405 + 2891336453; w = ((v >> ((v >> 28) + 4)) ^ v) 277803737; (w >> 22) ^ w.
+ *   eta = ((float(h & 0xffff) + float(h >> 16)) - 65535) / 65536: triangular in (-1, 1), exact. colour = colour (1 + grain_intensity eta).
+ * - Finish: alpha is 1 when any step ran. The colour is held at min(., 65504) and stored: the raw plane when grading follows, else the
+ *   frame's target through the display transform.
+ * - Deviations from the first statement, where building it showed a choice: (1) fit is rounded towards zero, not to nearest, so its own
+ *   rounding cannot push a tap out of the frame, and scale_eff is rounded from scale times that float; (2) the grain's hash nests two PCG
+ *   rounds, one per cell coordinate: one round over a linear mix of the two leaves visible diagonals; (3) BILINEAR's f == 0 rule needs
+ *   no branch here: every texel is clamped to a finite colour first, so a + (b - a) 0 is a itself; (4) a tap position just outside the
+ *   frame by float rounding of u s + cx reads the clamped border texel: harmless, and the plan's fit is stated for exact arithmetic.
+ * - Known limits: picks and AOVs stay in undistorted render-size pixel coordinates; there is no prefilter where distortion minifies
+ *   (scale_eff f > 1 undersamples and may alias); fringing is radial only (no lateral / axial split, no per-channel distortion
+ *   coefficients); grain is white per cell (no spatial correlation beyond grain_size, the same value in all three channels).
+ * - Errors: ST_ERR_INVALID_ARGUMENT for a wrong struct_size, unknown flags, k1 or k2 not finite or 3 |k1| + 5 |k2| > 0.95, scale outside
+ *   [0.25, 4], fringe outside [0, 0.1], fringe_taps outside 3..16 when fringe != 0, vignette_intensity outside [0, 1], vignette_falloff
+ *   not finite or <= 0 when the intensity is not 0, grain_intensity outside [0, 1), grain_size outside 1..8 when the intensity is not 0
+ *   (NaN is outside every range), null pointers where they are not allowed, image sides outside 1..16384, and for st_lens_process
+ *   ST_LENS_GRAIN_ANIMATE (a stateless call has no frame counter) and an auto-exposure display. An unknown camera is
+ *   ST_ERR_UNKNOWN_CAMERA. Set, get and plan are host work and valid on a host-only engine; st_lens_process returns ST_ERR_NO_DEVICE there. */
+enum { ST_LENS_FIT = 1, ST_LENS_VIGNETTE_ROUND = 2, ST_LENS_GRAIN_ANIMATE = 4 };
+enum { ST_LENS_STEP_DISTORTION = 1, ST_LENS_STEP_FRINGE = 2, ST_LENS_STEP_VIGNETTE = 4, ST_LENS_STEP_GRAIN = 8 };
+enum { ST_LENS_MAX_TAPS = 16 };
+typedef struct StLensDesc {                /* 48 B: twelve 4-B words, a multiple of 8 B without a pad */
+    uint32_t struct_size, flags;           /* sizeof(StLensDesc), ST_LENS_* */
+    float k1, k2;                          /* radial distortion; 0, 0 = none; finite, 3 |k1| + 5 |k2| <= 0.95 (keeps r f(r^2) increasing: no fold-over) */
+    float scale;                           /* source zoom, in [0.25, 4]; 1 = none; with ST_LENS_FIT multiplied by the plan's fit */
+    float fringe;                          /* [0, 0.1]; 0 = none: relative radial spread between the red and the blue end */
+    uint32_t fringe_taps;                  /* 3..16 when fringe != 0, else ignored */
+    float vignette_intensity;              /* [0, 1]; 0 = none */
+    float vignette_falloff;                /* finite, > 0 when the intensity is not 0 */
+    float grain_intensity;                 /* [0, 1); 0 = none */
+    uint32_t grain_size;                   /* 1..8 pixels per grain cell when the intensity is not 0 */
+    uint32_t grain_seed;
+} StLensDesc;
+typedef struct StLensPlan {                /* 284 B; host constants, each computed in double and rounded once */
+    uint32_t steps, taps;                  /* ST_LENS_STEP_*; taps = 1 without the fringe step */
+    float cx, cy, inv_hd2;                 /* W / 2, H / 2, 1 / (cx^2 + cy^2) */
+    float fit, scale_eff;                  /* fit = 1 without ST_LENS_FIT */
+    float tap_scale[16];                   /* [ST_LENS_MAX_TAPS]; entries past `taps` are 0 */
+    float tap_weight[16][3];               /* r, g, b */
+} StLensPlan;
+int st_camera_set_lens(StEngine* e, StHandle camera, const StLensDesc* desc);   /* NULL = off */
+/* the last desc set (a zeroed desc with struct_size when none was) and whether the node is on; either pointer may be NULL */
+int st_camera_get_lens(StEngine* e, StHandle camera, StLensDesc* out, int* enabled);
+/* host only, no engine: the host constants of a descriptor for a width x height frame; out may be NULL (the checks alone) */
+int st_lens_plan(const StLensDesc* desc, uint32_t width, uint32_t height, StLensPlan* out);
+/* Stateless, like st_bloom_process: the same launch over any RGBA32F device plane. display NULL = none, manual exposure only. Needs a
+ * device engine; no camera, no tick, no scratch memory. Enqueued on hip_stream without a host sync. src may not overlap dst. */
+int st_lens_process(StEngine* e, const StLensDesc* desc, const StDisplayDesc* display, const void* src_rgba32f_device, uint32_t width,
+                    uint32_t height, void* dst_device, int dst_format /* StOutputFormat */, void* hip_stream);
+/* measurement and tests: force != 0 sends descriptors without the distortion and the fringe step through the gather instantiation (one
+ * tap at the pixel's own centre) instead of the pointwise one; steps that run give the same bits either way */
+int st_debug_set_lens_gather(StEngine* e, int force);
 
 /* ---- multi-GPU behind the boundary (NEW seam; SURVEY.md section 8e, BASELINE.json configs 4 and 5). One process per GPU, one
  * engine per process, the scene replicated; the frame is cut into tiles, every rank renders its tile (+ an apron of redundant
@@ -1446,7 +1545,7 @@ enum StPassBit {
     ST_PASS_DENOISE_REPROJECT_DI = 1u << 18, ST_PASS_DENOISE_REPROJECT_GI = 1u << 19, ST_PASS_DENOISE_VARIANCE = 1u << 20,
     ST_PASS_DENOISE_WAVELET_0 = 1u << 21, /* ... wavelet pass n = ST_PASS_DENOISE_WAVELET_0 << n, n < 5 */
     ST_PASS_COMPOSITION = 1u << 26, ST_PASS_BVH_HEATMAP = 1u << 27, ST_PASS_REF_TRACING = 1u << 28, ST_PASS_REF_SHADING = 1u << 29,
-    ST_PASS_POST = 1u << 30   /* the launches behind composition, one launch group: fog ("fog" above), depth of field ("depth of field"), motion blur ("motion blur"), bloom ("bloom"), then FXAA and / or the resampler ("post-processing"), then the upscaler and / or the sharpening step ("upscaling") */
+    ST_PASS_POST = 1u << 30   /* the launches behind composition, one launch group: fog ("fog" above), light shafts ("light shafts"), depth of field ("depth of field"), motion blur ("motion blur"), bloom ("bloom"), lens effects ("lens effects"), colour grading ("colour grading"), then FXAA and / or the resampler ("post-processing"), then the upscaler and / or the sharpening step ("upscaling") */
 };
 int st_debug_set_pass_mask(StEngine* e, uint64_t mask);
 /* Measurement only (tools/pair_matrix.py): the frame's graph is built as always — every fusion of the whole frame — but only the launches

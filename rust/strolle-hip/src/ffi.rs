@@ -490,6 +490,52 @@ extern "C" {
     pub fn st_decode_cube(bytes: *const c_void, size: usize, out_rgb: *mut f32, capacity_floats: usize, lut_size: *mut u32) -> i32;
 }
 
+// lens effects (include/strolle_hip.h "lens effects"): distortion, fringing, vignette and film grain between bloom and colour grading
+pub const ST_LENS_FIT: u32 = 1;
+pub const ST_LENS_VIGNETTE_ROUND: u32 = 2;
+pub const ST_LENS_GRAIN_ANIMATE: u32 = 4;
+pub const ST_LENS_STEP_DISTORTION: u32 = 1;
+pub const ST_LENS_STEP_FRINGE: u32 = 2;
+pub const ST_LENS_STEP_VIGNETTE: u32 = 4;
+pub const ST_LENS_STEP_GRAIN: u32 = 8;
+pub const ST_LENS_MAX_TAPS: u32 = 16;
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct StLensDesc {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub k1: f32,
+    pub k2: f32,
+    pub scale: f32,
+    pub fringe: f32,
+    pub fringe_taps: u32,
+    pub vignette_intensity: f32,
+    pub vignette_falloff: f32,
+    pub grain_intensity: f32,
+    pub grain_size: u32,
+    pub grain_seed: u32,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct StLensPlan {
+    pub steps: u32,
+    pub taps: u32,
+    pub cx: f32,
+    pub cy: f32,
+    pub inv_hd2: f32,
+    pub fit: f32,
+    pub scale_eff: f32,
+    pub tap_scale: [f32; 16],
+    pub tap_weight: [[f32; 3]; 16],
+}
+extern "C" {
+    pub fn st_camera_set_lens(e: *mut StEngine, camera: u64, desc: *const StLensDesc) -> i32; // null = off
+    pub fn st_camera_get_lens(e: *mut StEngine, camera: u64, out: *mut StLensDesc, enabled: *mut i32) -> i32;
+    pub fn st_lens_plan(desc: *const StLensDesc, width: u32, height: u32, out: *mut StLensPlan) -> i32; // pure host
+    pub fn st_lens_process(e: *mut StEngine, desc: *const StLensDesc, display: *const StDisplayDesc, src_rgba32f_device: *const c_void, width: u32, height: u32, dst_device: *mut c_void, dst_format: i32, hip_stream: *mut c_void) -> i32;
+    pub fn st_debug_set_lens_gather(e: *mut StEngine, force: i32) -> i32;
+}
+
 // ---- the HIP runtime, as far as the staging-copy present needs it (libamdhip64)
 pub type hipStream_t = *mut c_void;
 extern "C" {

@@ -285,6 +285,20 @@ where
         }
     }
 
+    /// Not part of the reference's API: lens effects on a camera (include/strolle_hip.h "lens effects"): radial distortion, chromatic
+    /// fringing (Bevy's `ChromaticAberration`), vignette and film grain between bloom and colour grading; `None` turns the node off.
+    /// A default descriptor needs `scale: 1.0` to be neutral. The node and a window exclude each other, as bloom and a window do.
+    pub fn set_lens(&mut self, handle: CameraHandle, desc: Option<ffi::StLensDesc>) {
+        let raw = self.cameras.get(&handle).unwrap_or_else(|| panic!("camera does not exist: {:?}", handle)).raw;
+        match desc {
+            None => check(unsafe { ffi::st_camera_set_lens(self.raw, raw, std::ptr::null()) }),
+            Some(mut d) => {
+                d.struct_size = std::mem::size_of::<ffi::StLensDesc>() as u32;
+                check(unsafe { ffi::st_camera_set_lens(self.raw, raw, &d) });
+            }
+        }
+    }
+
     /// Not part of the reference's API: colour grading on a camera (include/strolle_hip.h "colour grading"); `None` turns the node off.
     /// `desc.lut` names a table by the id `insert_lut` was given (0: none); Bevy's `ColorGrading` / `DebandDither` map as INTEGRATION.md says.
     pub fn set_color_grading(&mut self, handle: CameraHandle, desc: Option<ffi::StColorGradingDesc>) {

@@ -278,6 +278,49 @@ def fog_desc(falloff=FogFalloff.EXPONENTIAL, color=(1.0, 1.0, 1.0, 1.0), start: 
                      f3(*[float(v) for v in light_direction]), 0.0)
 
 
+class StLensDesc(C.Structure):
+    """include/strolle_hip.h "lens effects": 48 B"""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("k1", C.c_float), ("k2", C.c_float), ("scale", C.c_float), ("fringe", C.c_float),
+                ("fringe_taps", C.c_uint32), ("vignette_intensity", C.c_float), ("vignette_falloff", C.c_float), ("grain_intensity", C.c_float),
+                ("grain_size", C.c_uint32), ("grain_seed", C.c_uint32)]
+
+
+class StLensPlan(C.Structure):
+    """include/strolle_hip.h "lens effects": 284 B"""
+    _fields_ = [("steps", C.c_uint32), ("taps", C.c_uint32), ("cx", C.c_float), ("cy", C.c_float), ("inv_hd2", C.c_float), ("fit", C.c_float), ("scale_eff", C.c_float),
+                ("tap_scale", C.c_float * 16), ("tap_weight", (C.c_float * 3) * 16)]
+
+
+LENS_FIT, LENS_VIGNETTE_ROUND, LENS_GRAIN_ANIMATE = 1, 2, 4
+LENS_STEP_DISTORTION, LENS_STEP_FRINGE, LENS_STEP_VIGNETTE, LENS_STEP_GRAIN = 1, 2, 4, 8
+LENS_MAX_TAPS = 16
+
+
+def lens_desc(k1: float = 0.0, k2: float = 0.0, scale: float = 1.0, fit: bool = False, fringe: float = 0.0, fringe_taps: int = 3, vignette_intensity: float = 0.0,
+              vignette_falloff: float = 1.0, vignette_round: bool = False, grain_intensity: float = 0.0, grain_size: int = 1, grain_seed: int = 0,
+              grain_animate: bool = False) -> StLensDesc:
+    """A StLensDesc (include/strolle_hip.h "lens effects"); the defaults are neutral. k1, k2: radial distortion (k1 < 0 barrel, > 0
+    pincushion), 3 |k1| + 5 |k2| <= 0.95; scale: source zoom, with fit multiplied by the largest factor that keeps every tap inside the
+    frame; fringe: the radial spread between red and blue over fringe_taps taps; the vignette follows the frame's ellipse unless
+    vignette_round; grain: multiplicative noise of grain_size pixels per cell, a new pattern every frame with grain_animate."""
+    flags = (LENS_FIT if fit else 0) | (LENS_VIGNETTE_ROUND if vignette_round else 0) | (LENS_GRAIN_ANIMATE if grain_animate else 0)
+    return StLensDesc(C.sizeof(StLensDesc), flags, float(k1), float(k2), float(scale), float(fringe), int(fringe_taps), float(vignette_intensity), float(vignette_falloff),
+                      float(grain_intensity), int(grain_size), int(grain_seed) & 0xffffffff)
+
+
+def lens_plan(desc: StLensDesc, width: int, height: int) -> StLensPlan:
+    """st_lens_plan: the host constants of a descriptor for a width x height frame (steps, taps, cx, cy, inv_hd2, fit, scale_eff, the tap table)."""
+    lib = load_library()
+    lib.st_lens_plan.restype = C.c_int
+    lib.st_lens_plan.argtypes = [C.POINTER(StLensDesc), C.c_uint32, C.c_uint32, C.POINTER(StLensPlan)]
+    plan = StLensPlan()
+    rc = lib.st_lens_plan(C.byref(desc), int(width), int(height), C.byref(plan))
+    if rc != 0:
+        lib.st_last_error.restype = C.c_char_p
+        raise StrolleError(f"{_STATUS.get(rc, 'error')} (status {rc}): {lib.st_last_error().decode(errors='replace')}")
+    return plan
+
+
 class StColorGradingDesc(C.Structure):
     """include/strolle_hip.h "colour grading": 96 B"""
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("temperature", C.c_float), ("tint", C.c_float), ("contrast", C.c_float),
@@ -724,6 +767,12 @@ class _Binding:
             self.camera_set_fog = fn("camera_set_fog", [vp, u64, P(StFogDesc)])
             self.camera_get_fog = fn("camera_get_fog", [vp, u64, P(StFogDesc), P(i32)])
             self.fog_process = fn("fog_process", [vp, P(StFogDesc), P(StDisplayDesc), P(C.c_float), P(C.c_float), vp, vp, u32, u32, vp, i32, vp])
+        if hasattr(lib, prefix + "camera_set_lens"):   # lens effects (likewise)
+            self.camera_set_lens = fn("camera_set_lens", [vp, u64, P(StLensDesc)])
+            self.camera_get_lens = fn("camera_get_lens", [vp, u64, P(StLensDesc), P(i32)])
+            self.lens_plan = fn("lens_plan", [P(StLensDesc), u32, u32, P(StLensPlan)])
+            self.lens_process = fn("lens_process", [vp, P(StLensDesc), P(StDisplayDesc), vp, u32, u32, vp, i32, vp])
+            self.debug_set_lens_gather = fn("debug_set_lens_gather", [vp, i32])
         if hasattr(lib, prefix + "camera_set_color_grading"):   # colour grading (likewise)
             self.camera_set_color_grading = fn("camera_set_color_grading", [vp, u64, P(StColorGradingDesc)])
             self.camera_get_color_grading = fn("camera_get_color_grading", [vp, u64, P(StColorGradingDesc), P(i32)])
@@ -1346,6 +1395,29 @@ class Engine(EngineBase):
         xf, proj = (C.c_float * 16)(*[float(v) for v in transform]), (C.c_float * 16)(*[float(v) for v in projection])
         self._check(self._b.fog_process(self._h, C.byref(desc), C.byref(display) if display is not None else None, xf, proj, color_ptr, depth_ptr, width, height,
                                         dst_ptr, int(dst_format), stream))
+
+    # ---- lens effects (include/strolle_hip.h "lens effects"): takes effect at the camera's next render
+    def set_lens(self, camera: int, desc: Optional[StLensDesc] = None, **kw):
+        """st_camera_set_lens: a StLensDesc, or lens_desc(**kw) when keywords are given; neither = off."""
+        self._set_stage(self._b.camera_set_lens, lens_desc, camera, desc, kw)
+
+    def get_lens(self, camera: int):
+        """st_camera_get_lens: (the last StLensDesc set, whether the node is on)."""
+        return self._get_stage(self._b.camera_get_lens, StLensDesc, camera)
+
+    def lens_plan(self, desc: StLensDesc, width: int, height: int) -> StLensPlan:
+        """st_lens_plan (the module's lens_plan)."""
+        return lens_plan(desc, width, height)
+
+    def lens_process(self, desc: StLensDesc, src_ptr: int, width: int, height: int, dst_ptr: int, dst_format: int = 0, display: Optional[StDisplayDesc] = None,
+                     stream: int = 0):
+        """st_lens_process: the node's launch over any RGBA32F device plane, through the (manual) display transform, into dst (width x
+        height) in dst_format."""
+        self._check(self._b.lens_process(self._h, C.byref(desc), C.byref(display) if display is not None else None, src_ptr, width, height, dst_ptr, int(dst_format), stream))
+
+    def set_lens_gather(self, force: bool):
+        """st_debug_set_lens_gather: descriptors without taps run the gather instantiation (measurement and tests)."""
+        self._check(self._b.debug_set_lens_gather(self._h, 1 if force else 0))
 
     # ---- colour grading (include/strolle_hip.h "colour grading"): takes effect at the camera's next render; tables at the next tick
     def set_color_grading(self, camera: int, desc: Optional[StColorGradingDesc] = None, **kw):

@@ -288,7 +288,7 @@ int st_camera_set_window(StEngine* e, StHandle h, uint32_t x0, uint32_t y0, uint
     ST_REQUIRE(full || !s.display_auto(), "a window on a camera with auto-exposure would meter the tile alone (include/strolle_hip.h \"display transforms\")");
     // each stage's own rule (st_output_chain.h), as its setter states it; fog and colour grading carry none
     const std::initializer_list<std::pair<bool, const WindowRule*>> stages = {{s.post.on, s.post.window}, {s.bloom.on, s.bloom.window}, {s.mblur.on, s.mblur.window},
-                                                                              {s.dof.on, s.dof.window}, {s.fog.on, s.fog.window}, {s.shafts.on, s.shafts.window}, {s.grade.on, s.grade.window},
+                                                                              {s.dof.on, s.dof.window}, {s.fog.on, s.fog.window}, {s.shafts.on, s.shafts.window}, {s.grade.on, s.grade.window}, {s.lens.on, s.lens.window},
                                                                               {s.upscale.on, s.upscale.window}};
     for (const auto& st : stages) if (!full && st.first && st.second) return fail(ST_ERR_INVALID_ARGUMENT, window_refused_by(*st.second));
     s.row0 = y0; s.row1 = y1; s.col0 = x0; s.col1 = x1;
@@ -372,6 +372,31 @@ int st_debug_set_upscale_fused(StEngine* e, int tile) {
     ST_REQUIRE(e, "null engine");
     ST_REQUIRE(tile >= 0 && tile <= 3, "tile is 0 (two launches), 1 (64 x 8), 2 (32 x 32) or 3 (64 x 16)");
     E(e)->upscale_fused = (uint32_t)tile;
+    return ST_OK;
+}
+
+// ---- lens effects (st_lens.cpp)
+int st_camera_set_lens(StEngine* e, StHandle h, const StLensDesc* desc) {
+    ST_REQUIRE(e, "null engine");
+    auto it = E(e)->cameras.find(h);
+    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    return E(e)->set_lens(*it->second, desc);
+}
+int st_camera_get_lens(StEngine* e, StHandle h, StLensDesc* out, int* enabled) { return camera_get(e, h, &CameraState::lens, out, enabled); }
+int st_lens_plan(const StLensDesc* desc, uint32_t width, uint32_t height, StLensPlan* out) {
+    ST_REQUIRE(desc, "null desc");
+    StLensPlan plan;
+    if (int rc = Engine::lens_plan(*desc, width, height, plan)) return rc;
+    if (out) *out = plan;
+    return ST_OK;
+}
+int st_lens_process(StEngine* e, const StLensDesc* desc, const StDisplayDesc* display, const void* src, uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
+    ST_REQUIRE(e, "null engine");
+    return E(e)->lens_process(desc, display, src, width, height, dst, dst_format, static_cast<hipStream_t>(stream));
+}
+int st_debug_set_lens_gather(StEngine* e, int force) {
+    ST_REQUIRE(e, "null engine");
+    E(e)->lens_force_gather = force != 0;
     return ST_OK;
 }
 

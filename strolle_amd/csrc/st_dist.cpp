@@ -293,6 +293,7 @@ static int display_window_check(const CameraState& c, const StDistRect& w) {
     if (!full && c.mblur.on) return fail(ST_ERR_INVALID_ARGUMENT, "a tile window on a camera with motion blur: the gather reads up to 32 pixels across tile edges (st_motion_blur_process serves gathered frames)");
     if (!full && c.dof.on) return fail(ST_ERR_INVALID_ARGUMENT, "a tile window on a camera with depth of field: the gather reads up to 32 pixels across tile edges (st_dof_process serves gathered frames)");
     if (!full && c.shafts.on) return fail(ST_ERR_INVALID_ARGUMENT, "a tile window on a camera with light shafts: the apply launch reads neighbouring cells across tile edges (st_light_shafts_process serves gathered frames)");
+    if (!full && c.lens.on) return fail(ST_ERR_INVALID_ARGUMENT, "a tile window on a camera with lens effects: distortion and fringing read far across tile edges (st_lens_process serves gathered frames)");
     return ST_OK;
 }
 

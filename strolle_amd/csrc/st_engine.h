@@ -404,6 +404,7 @@ struct CameraState {
     NodeSetting<StDofDesc, 4> dof{&kDofWindow};              // st_dof.cpp. [0] the HDR plane, [1] (coc, Z) per pixel, [2] the tiles' near-field maxima, [3] their 3 x 3 neighbour maxima
     NodeSetting<StMotionBlurDesc, 4> mblur{&kMBlurWindow};   // st_motion_blur.cpp. [0] the HDR plane, [1] (r, Z) per pixel, [2] the tile vectors, [3] their 3 x 3 neighbour maxima
     NodeSetting<StBloomDesc, 2> bloom{&kBloomWindow};        // st_bloom.cpp. [0] the HDR plane, [1] the pyramid (one allocation of float4 mips)
+    NodeSetting<StLensDesc, 1> lens{&kLensWindow};           // st_lens.cpp. [0] the HDR plane (between bloom and the grade)
     NodeSetting<StColorGradingDesc, 1> grade{nullptr};       // st_grade.cpp. [0] the HDR plane. Pointwise: a window does not exclude it
     // The upscale stage behind FXAA (st_upscale.cpp): it reads post.planes ([1] with FXAA on, else [0]); [0] here is the output-size RGBA32F plane
     // between the upscaler and the sharpening step, grown, never shrunk
@@ -753,6 +754,14 @@ struct Engine {
     int lut_remove(StHandle id);
     int upload_luts(TickIo& io);   // the tick's: edits -> fresh device tables; retired ones are released behind their readers
     Lut* live_lut(StHandle id) const { auto it = luts_live.find(id); return it == luts_live.end() ? nullptr : it->second.get(); }
+    // ---- lens effects (st_lens.cpp)
+    struct LensStep { LensArgs args; OutputStep step; };
+    static int lens_plan(const StLensDesc& d, uint32_t w, uint32_t h, StLensPlan& out);   // checks the desc and the sides
+    // `frame`: the camera's frame counter (ST_LENS_GRAIN_ANIMATE adds it to the seed); `force_gather`: st_debug_set_lens_gather
+    static void lens_step(const StLensDesc& d, const StLensPlan& plan, const NodeSource& src, uint32_t frame, bool force_gather, const NodeTarget& target, LensStep& out);
+    int set_lens(CameraState& c, const StLensDesc* desc);
+    int lens_process(const StLensDesc* desc, const StDisplayDesc* display, const void* src, uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
+    bool lens_force_gather = false;   // st_debug_set_lens_gather: a descriptor without taps runs the gather instantiation (one tap at the pixel's own centre)
     // ---- light shafts (st_shafts.cpp)
     struct ShaftsPlan { uint32_t cells_w = 0, cells_h = 0; size_t cell_bytes = 0; float jitter[16] = {}; };
     struct ShaftsSteps { ShaftsArgs args; OutputStep step[2]; };   // march, apply

@@ -47,6 +47,7 @@ enum KernelSlot {
     KS_SHAFTS_MARCH, KS_SHAFTS_APPLY,  // light shafts between fog and depth of field (k_shafts.hip); render() credits their bytes itself
     KS_GRADE,  // colour grading behind bloom (k_grade.hip); render() credits its bytes itself
     KS_UPSCALE, KS_SHARPEN, KS_UPSCALE_SHARPEN,  // the upscale stage behind FXAA (k_upscale.hip); their bytes depend on the output size and format: render() credits them itself
+    KS_LENS,  // lens effects between bloom and colour grading (k_lens.hip); render() credits its bytes itself
     KS_COUNT
 };
 struct KernelInfo { const char* name; float bytes_per_unit; bool half; };
@@ -84,6 +85,7 @@ inline const KernelInfo& kernel_info(int slot) {
         {"shafts_march", 0.f, false},        {"shafts_apply", 0.f, false},
         {"color_grading", 0.f, false},
         {"upscale", 0.f, false},             {"sharpen", 0.f, false},              {"upscale+sharpen", 0.f, false},
+        {"lens", 0.f, false},
     };
     return k[slot];
 }

@@ -115,3 +115,5 @@ ST_LAUNCHER(launch_upscale, (const UpscaleArgs& p, hipStream_t s))
 ST_LAUNCHER(launch_sharpen, (const UpscaleArgs& p, hipStream_t s))
 // ... and both steps in one launch, the upscaled tile and its one-pixel ring in LDS (`tile`: 1 = 64 x 8 output pixels per workgroup, 2 = 32 x 32, 3 = 64 x 16)
 ST_LAUNCHER(launch_upscale_sharpen, (const UpscaleArgs& p, uint32_t tile, hipStream_t s))
+// lens effects (k_lens.hip; st_lens.cpp): one launch over the whole frame, one workgroup per 32 x 8 pixels; a gather with the distortion or the fringe step, else pointwise
+ST_LAUNCHER(launch_lens, (const LensArgs& p, hipStream_t s))

@@ -17,6 +17,7 @@ inline std::string window_refused_by(const WindowRule& r) { return std::string("
 constexpr WindowRule kPostWindow{"post-processing", ": FXAA and the resampler read across tile edges (include/strolle_hip.h \"post-processing\")"};
 constexpr WindowRule kUpscaleWindow{"upscaling", ": both steps read across tile edges (include/strolle_hip.h \"upscaling\")"};
 constexpr WindowRule kBloomWindow{"bloom", ": the pyramid reads far across tile edges (include/strolle_hip.h \"bloom\")"};
+constexpr WindowRule kLensWindow{"lens effects", ": distortion and fringing read far across tile edges (include/strolle_hip.h \"lens effects\")"};
 constexpr WindowRule kMBlurWindow{"motion blur", ": the gather reads up to 32 pixels across tile edges (include/strolle_hip.h \"motion blur\")"};
 constexpr WindowRule kDofWindow{"depth of field", ": the gather reads up to 32 pixels across tile edges (include/strolle_hip.h \"depth of field\")"};
 constexpr WindowRule kShaftsWindow{"light shafts", ": the apply launch reads neighbouring cells across tile edges (include/strolle_hip.h \"light shafts\")"};

@@ -142,7 +142,7 @@ namespace {
 // reads_depth: its launches in finish_output read the G-buffer depth of the frame's parity, which the frame after next rewrites: the camera's
 //        gbuffer_depth_read fence is recorded once, behind the last such node that is on, and prim() of that parity waits for it.
 // reads_velocity: the lean frame keeps the velocity map for it (kLeanKeepVelocity).
-enum HdrNode { kNodeFog, kNodeShafts, kNodeDof, kNodeMBlur, kNodeBloom, kNodeGrade, kHdrNodes };   // chain order
+enum HdrNode { kNodeFog, kNodeShafts, kNodeDof, kNodeMBlur, kNodeBloom, kNodeLens, kNodeGrade, kHdrNodes };   // chain order
 struct HdrNodeRow { uint32_t early; bool reads_depth, reads_velocity; };
 constexpr HdrNodeRow kHdrNode[kHdrNodes] = {
     /* fog (st_fog.cpp): one launch; pointwise, so windows are honoured */       {0u, true, false},
@@ -150,12 +150,13 @@ constexpr HdrNodeRow kHdrNode[kHdrNodes] = {
     /* depth of field (st_dof.cpp): pack | neighbour maximum, gather */           {1u, false, false},
     /* motion blur (st_motion_blur.cpp): pack | neighbour maximum, gather */      {1u, false, true},
     /* bloom (st_bloom.cpp): the pyramid's chain, the composite */                {0u, false, false},
+    /* lens effects (st_lens.cpp): one launch; a gather over the whole plane */   {0u, false, false},
     /* colour grading (st_grade.cpp): one launch; pointwise, windows honoured */  {0u, false, false},
 };
 struct HdrWork {   // what the nodes that are on hold for one frame: node_plan's plans, node_arm's argument blocks and steps
-    Engine::ShaftsPlan shafts_plan; Engine::DofPlan dof_plan; Engine::MBlurPlan mblur_plan; Engine::BloomPlan bloom_plan; Engine::GradePlan grade_plan;
+    Engine::ShaftsPlan shafts_plan; Engine::DofPlan dof_plan; Engine::MBlurPlan mblur_plan; Engine::BloomPlan bloom_plan; Engine::GradePlan grade_plan; StLensPlan lens_plan;
     Engine::Lut* grade_lut = nullptr;   // the live table the descriptor names, if any: its fence is recorded behind the launch
-    Engine::GradeStep grade; Engine::FogStep fog; Engine::ShaftsSteps shafts; Engine::DofSteps dof; Engine::MBlurSteps mblur; Engine::BloomSteps bloom;
+    Engine::GradeStep grade; Engine::LensStep lens; Engine::FogStep fog; Engine::ShaftsSteps shafts; Engine::DofSteps dof; Engine::MBlurSteps mblur; Engine::BloomSteps bloom;
 };
 // ---- end of the node table
 // The frame's output chain, decided once. Output post-processing (st_post.cpp): while the frame needs it, the frame's target is the camera's
@@ -233,6 +234,7 @@ struct Frame {
         case kNodeDof: return c.dof.on && perspective;
         case kNodeMBlur: return c.mblur.on && c.has_gbuffer();
         case kNodeGrade: return c.grade.on && c.desc.mode != ST_MODE_BVH_HEATMAP;   // (needs neither a G-buffer nor a projection)
+        case kNodeLens: return c.lens.on && c.desc.mode != ST_MODE_BVH_HEATMAP;     // (likewise)
         default: return c.bloom.on && c.desc.mode != ST_MODE_BVH_HEATMAP;
         }
     }
@@ -257,6 +259,9 @@ struct Frame {
         case kNodeMBlur:
             if (int rc = Engine::mblur_plan(c.mblur.desc, w, h, work.mblur_plan)) return rc;
             return node_planes(n, c.mblur.planes, {plane, work.mblur_plan.packed_bytes, work.mblur_plan.tile_bytes, work.mblur_plan.tile_bytes});
+        case kNodeLens:
+            if (int rc = Engine::lens_plan(c.lens.desc, w, h, work.lens_plan)) return rc;
+            return node_planes(n, c.lens.planes, {plane});
         case kNodeGrade:
             if (int rc = Engine::grade_plan(c.grade.desc, work.grade_plan)) return rc;
             work.grade_lut = e.live_lut(c.grade.desc.lut);
@@ -276,6 +281,7 @@ struct Frame {
         case kNodeFog: Engine::fog_step(c.fog.desc, view, src, c.row0, c.row1, c.col0, c.col1, t, work.fog); break;
         case kNodeShafts: e.shafts_steps(c.shafts.desc, work.shafts_plan, view, src, c.shafts.planes.plane[1].as<float4>(), t, true, work.shafts); break;
         case kNodeDof: { const auto& p = c.dof.planes.plane; Engine::dof_steps(c.dof.desc, work.dof_plan, c.desc.projection, src, p[1].as<float2>(), p[2].as<float>(), p[3].as<float>(), t, work.dof); break; }
+        case kNodeLens: Engine::lens_step(c.lens.desc, work.lens_plan, src, c.frame, e.lens_force_gather, t, work.lens); break;
         case kNodeGrade:
             Engine::grade_step(c.grade.desc, work.grade_plan, work.grade_lut ? work.grade_lut->texels.as<float4>() : nullptr, work.grade_lut ? work.grade_lut->size : 0u, src,
                                c.row0, c.row1, c.col0, c.col1, t, work.grade);
@@ -284,11 +290,12 @@ struct Frame {
         default: work.bloom = Engine::bloom_steps(c.bloom.desc, work.bloom_plan, src.color, src.w, src.h, c.bloom.planes.plane[1].as<float4>(), t, e.bloom_tail_bytes()); break;
         }
     }
-    uint32_t node_steps(int n) const { return (n == kNodeFog || n == kNodeGrade) ? 1u : n == kNodeShafts ? 2u : n == kNodeBloom ? work.bloom.count : 3u; }
+    uint32_t node_steps(int n) const { return (n == kNodeFog || n == kNodeGrade || n == kNodeLens) ? 1u : n == kNodeShafts ? 2u : n == kNodeBloom ? work.bloom.count : 3u; }
     const OutputStep& node_step(int n, uint32_t i) const {
         switch (n) {
         case kNodeFog: return work.fog.step;
         case kNodeGrade: return work.grade.step;
+        case kNodeLens: return work.lens.step;
         case kNodeShafts: return work.shafts.step[i];
         case kNodeDof: return work.dof.step[i];
         case kNodeMBlur: return work.mblur.step[i];
@@ -299,6 +306,7 @@ struct Frame {
         switch (n) {
         case kNodeFog: e.L.launch_fog(work.fog.args, cur); break;
         case kNodeGrade: e.L.launch_grade(work.grade.args, cur); break;
+        case kNodeLens: e.L.launch_lens(work.lens.args, cur); break;
         case kNodeShafts: e.launch_shafts_step(a, work.shafts, i, cur); break;   // the march reads the live scene copy and the light table too
         case kNodeDof: e.launch_dof_step(work.dof, i, cur); break;
         case kNodeMBlur: e.launch_mblur_step(work.mblur, i, cur); break;

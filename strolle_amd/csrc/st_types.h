@@ -195,6 +195,22 @@ struct GradeArgs {
     DisplayArgs display;
 };
 
+// Lens effects (include/strolle_hip.h "lens effects"; st_lens.cpp, k_lens.hip): the arguments of its one launch over the whole width x
+// height frame (the node excludes windows). It reads `color` — with the distortion or the fringe step at up to `taps` bilinear look-ups per
+// pixel anywhere in the plane, indices clamped — and stores `dst` as fog's launch does. `steps`: ST_LENS_STEP_* of the steps that run;
+// force_gather: the debug seam that sends a descriptor without taps through the gather instantiation. cx, cy, inv_hd2, scale_eff,
+// tap_scale and tap_weight are st_lens_plan's; seed: grain_seed plus the camera's frame counter under ST_LENS_GRAIN_ANIMATE. All wave-uniform.
+constexpr uint32_t kLensDistortion = 1u, kLensFringe = 2u, kLensVignette = 4u, kLensGrain = 8u;   // ST_LENS_STEP_*
+constexpr uint32_t kLensMaxTaps = 16u;
+struct LensArgs {
+    const float4* color; void* dst;
+    uint32_t width, height, format, raw;
+    uint32_t steps, taps, round, grain_size, seed, force_gather;
+    float cx, cy, inv_hd2, k1, k2, scale_eff, vignette_intensity, vignette_falloff, grain_intensity;
+    float tap_scale[kLensMaxTaps], tap_weight[kLensMaxTaps][3];
+    DisplayArgs display;
+};
+
 // Everything a per-pixel kernel can touch, passed by value as the kernel argument (scalar loads).
 struct KArgs {
     GpuCamera cam, prev_cam;
