@@ -5,13 +5,23 @@
 using namespace st;
 static Engine* E(StEngine* e) { return reinterpret_cast<Engine*>(e); }
 #define ST_REQUIRE(cond, msg) do { if (!(cond)) return fail(ST_ERR_INVALID_ARGUMENT, msg); } while (0)
+// `CameraState& c`: camera `h` of engine `e`, or the function returns ST_ERR_UNKNOWN_CAMERA
+#define ST_CAMERA(c, e, h)                                                                                        \
+    const auto c##_it = E(e)->cameras.find(h);                                                                    \
+    if (c##_it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");               \
+    CameraState& c = *c##_it->second
 
+// st_camera_set_<stage>: the stage's setter (its checks are there) on camera `h`
+template <class Desc> static int camera_set(StEngine* e, StHandle h, int (Engine::*set)(CameraState&, const Desc*), const Desc* desc) {
+    ST_REQUIRE(e, "null engine");
+    ST_CAMERA(cam, e, h);
+    return (E(e)->*set)(cam, desc);
+}
 // st_camera_get_<stage>: the last descriptor set and whether the stage is on, for every stage a CameraState holds as a NodeSetting
 template <class Desc, int N> static int camera_get(StEngine* e, StHandle h, NodeSetting<Desc, N> CameraState::*setting, Desc* out, int* enabled) {
     ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    const NodeSetting<Desc, N>& s = (*it->second).*setting;
+    ST_CAMERA(cam, e, h);
+    const NodeSetting<Desc, N>& s = cam.*setting;
     if (out) { *out = s.desc; out->struct_size = sizeof(Desc); }
     if (enabled) *enabled = s.on ? 1 : 0;
     return ST_OK;
@@ -60,137 +70,44 @@ int st_engine_create(int device_ordinal, StEngine** out) {
 }
 void st_engine_destroy(StEngine* e) { delete E(e); }
 
+// ---- the scene stores (st_stores.h; st_scene.cpp)
 int st_mesh_insert(StEngine* e, StHandle id, const StMeshTriangle* t, size_t count) {
     ST_REQUIRE(e && (t || count == 0), "null argument");
     if (count == 0) return fail(ST_ERR_EMPTY_MESH, "mesh contains no triangles");
-    E(e)->deform.drop_skin(id);   // skinned meshes: a new mesh drops the skin and the poses of its instances
-    E(e)->deform.drop_morph(id);  // morph targets: likewise the targets and the weights
-    E(e)->meshes[id].assign(t, t + count);
-    E(e)->mesh_version[id] = E(e)->next_mesh_version++;   // an instance baked from the earlier mesh of this handle is re-baked by the host
+    E(e)->insert_mesh(id, t, count);
     return ST_OK;
 }
-int st_mesh_remove(StEngine* e, StHandle id) { ST_REQUIRE(e, "null engine"); E(e)->deform.drop_skin(id); E(e)->deform.drop_morph(id); E(e)->meshes.erase(id); E(e)->mesh_version.erase(id); return ST_OK; }
+int st_mesh_remove(StEngine* e, StHandle id) { ST_REQUIRE(e, "null engine"); E(e)->remove_mesh(id); return ST_OK; }
 
-int st_material_insert(StEngine* e, StHandle id, const StMaterial* m) {
-    ST_REQUIRE(e && m, "null argument");
-    Engine* en = E(e);
-    auto it = en->material_slot.find(id);
-    if (it != en->material_slot.end()) en->materials[it->second] = *m;
-    else {
-        size_t b, end_;
-        uint32_t slot;
-        if (en->material_free.take(1, &b, &end_)) slot = (uint32_t)b;  // materials.rs:48-50 (the slot keeps its previous contents)
-        else { en->materials.push_back(*m); slot = (uint32_t)en->materials.size() - 1u; }
-        en->material_slot[id] = slot;
-    }
-    en->materials_dirty = true;
-    return ST_OK;
-}
-int st_material_has(StEngine* e, StHandle id) { return e && E(e)->material_slot.count(id) ? 1 : 0; }
-int st_material_remove(StEngine* e, StHandle id) {
-    ST_REQUIRE(e, "null engine");
-    Engine* en = E(e);
-    auto it = en->material_slot.find(id);
-    if (it == en->material_slot.end()) return ST_OK;
-    en->material_free.give(it->second, it->second);  // `give(id..id)`: an empty range, as in materials.rs:74
-    en->material_slot.erase(it);
-    en->materials_dirty = true;
-    return ST_OK;
-}
-
-// Images::insert (images.rs:54-105): finds the rectangle for image `id` and makes the host copy of the atlas tall enough.
-static int place_image(Engine* en, StHandle id, uint32_t w, uint32_t h, Engine::ImageRec* out) {
-    constexpr uint32_t kAtlasW = Engine::kAtlasW;
-    if (w > kAtlasW) return fail(ST_ERR_ATLAS_FULL, "image wider than the atlas");
-    auto it = en->images.find(id);
-    Engine::ImageRec rec;
-    if (it != en->images.end() && it->second.w == w && it->second.h == h) rec = it->second;  // same size: rewritten in place (images.rs:61-63)
-    else {
-        if (it != en->images.end()) {  // another size: the old rectangle is given back first (images.rs:64-66)
-            en->atlas_rects.release(it->second.x, it->second.y, it->second.w);
-            en->images.erase(it);
-            en->device_images.erase(id);
-            en->materials_dirty = true;
-        }
-        rec = {0, 0, w, h};
-        if (!en->atlas_rects.allocate(w, h, &rec.x, &rec.y)) return fail(ST_ERR_ATLAS_FULL, "no more space in the atlas");
-    }
-    const uint32_t need_h = rec.y + h;
-    if (en->atlas_w == 0) en->atlas_w = kAtlasW;
-    if (need_h > en->atlas_h) {
-        // grow in 256-row steps; rects are stored in texels, so existing materials stay valid after a rebuild
-        en->atlas_h = (need_h + 255u) & ~255u;
-        en->atlas.resize((size_t)en->atlas_w * en->atlas_h * 4, 0);
-    }
-    en->images[id] = rec;
-    en->atlas_dirty = true; en->materials_dirty = true;
-    *out = rec;
-    return ST_OK;
-}
+int st_material_insert(StEngine* e, StHandle id, const StMaterial* m) { ST_REQUIRE(e && m, "null argument"); E(e)->materials.insert(id, *m); return ST_OK; }
+int st_material_has(StEngine* e, StHandle id) { return e && E(e)->materials.has(id) ? 1 : 0; }
+int st_material_remove(StEngine* e, StHandle id) { ST_REQUIRE(e, "null engine"); E(e)->materials.remove(id); return ST_OK; }
 
 int st_image_insert_rgba8(StEngine* e, StHandle id, uint32_t w, uint32_t h, const uint8_t* rgba, int /*srgb*/) {
     ST_REQUIRE(e && rgba && w && h && id, "bad image");
-    Engine* en = E(e);
-    Engine::ImageRec rec;
-    if (int rc = place_image(en, id, w, h, &rec)) return rc;
-    en->device_images.erase(id);
-    for (uint32_t y = 0; y < h; y++) memcpy(&en->atlas[((size_t)(rec.y + y) * en->atlas_w + rec.x) * 4], rgba + (size_t)y * w * 4, (size_t)w * 4);
-    return ST_OK;
+    return E(e)->images.insert_rgba8(id, w, h, rgba);
 }
 int st_image_insert_device_rgba8(StEngine* e, StHandle id, uint32_t w, uint32_t h, const void* device_rgba, size_t row_pitch_bytes, int is_dynamic) {
     ST_REQUIRE(e && device_rgba && w && h && id, "bad image");
     ST_REQUIRE(row_pitch_bytes >= (size_t)w * 4, "row pitch smaller than a row");
-    Engine* en = E(e);
-    if (!en->has_device) return fail(ST_ERR_NO_DEVICE, "device images need a device engine");
-    Engine::ImageRec rec;
-    if (int rc = place_image(en, id, w, h, &rec)) return rc;
-    en->device_images[id] = Engine::DeviceImage{device_rgba, row_pitch_bytes, is_dynamic != 0, true};
-    return ST_OK;
+    if (!E(e)->has_device) return fail(ST_ERR_NO_DEVICE, "device images need a device engine");
+    return E(e)->images.insert_device(id, w, h, device_rgba, row_pitch_bytes, is_dynamic != 0);
 }
-int st_image_remove(StEngine* e, StHandle id) {  // images.rs:107-113
-    ST_REQUIRE(e, "null engine");
-    Engine* en = E(e);
-    auto it = en->images.find(id);
-    if (it == en->images.end()) return ST_OK;
-    en->atlas_rects.release(it->second.x, it->second.y, it->second.w);
-    en->images.erase(it);
-    en->device_images.erase(id);
-    en->materials_dirty = true;
-    return ST_OK;
-}
+int st_image_remove(StEngine* e, StHandle id) { ST_REQUIRE(e, "null engine"); E(e)->images.remove(id); return ST_OK; }
 int st_debug_image_rect(StEngine* e, StHandle id, uint32_t out_xywh[4]) {
     ST_REQUIRE(e && out_xywh, "null argument");
-    auto it = E(e)->images.find(id);
-    if (it == E(e)->images.end()) return fail(ST_ERR_INVALID_ARGUMENT, "no such image");
-    out_xywh[0] = it->second.x; out_xywh[1] = it->second.y; out_xywh[2] = it->second.w; out_xywh[3] = it->second.h;
+    const ImageAtlas::Rect* r = E(e)->images.rect_texels(id);
+    if (!r) return fail(ST_ERR_INVALID_ARGUMENT, "no such image");
+    out_xywh[0] = r->x; out_xywh[1] = r->y; out_xywh[2] = r->w; out_xywh[3] = r->h;
     return ST_OK;
 }
 
 int st_instance_insert(StEngine* e, StHandle id, StHandle mesh, StHandle material, const float xform[12]) {
     ST_REQUIRE(e && xform, "null argument");
-    Engine* en = E(e);
-    const Affine x = affine_from12(xform);
-    if (Engine::InstanceRec* r = en->find_instance(id)) {
-        if (r->mesh != mesh) en->deform.drop_instance(id, false);
-        r->prev_xform = r->xform; r->mesh = mesh; r->material = material; r->xform = x; r->xform_inv = affine_inverse(x); r->dirty = true; en->instances_dirty = true;
-        return ST_OK;
-    }
-    uint32_t xslot;
-    if (!en->xslot_free.empty()) { xslot = en->xslot_free.back(); en->xslot_free.pop_back(); }
-    else { xslot = (uint32_t)(en->instance_xforms.size() / 8u); en->instance_xforms.resize(en->instance_xforms.size() + 8u, make_float4(0, 0, 0, 0)); }
-    en->instances.push_back({id, mesh, material, x, affine_inverse(x), x, true, xslot});
-    en->instances_dirty = true;
+    E(e)->insert_instance(id, mesh, material, affine_from12(xform));
     return ST_OK;
 }
-int st_instance_remove(StEngine* e, StHandle id) {
-    ST_REQUIRE(e, "null engine");
-    Engine* en = E(e);
-    for (size_t i = 0; i < en->instances.size(); i++)
-        if (en->instances[i].id == id) { en->xslot_free.push_back(en->instances[i].xslot); en->instances.erase(en->instances.begin() + i); en->instances_dirty = true; en->instance_removed = true; break; }
-    en->drop_instance_triangles(id);
-    en->deform.drop_instance(id, false);
-    return ST_OK;
-}
+int st_instance_remove(StEngine* e, StHandle id) { ST_REQUIRE(e, "null engine"); E(e)->remove_instance(id); return ST_OK; }
 
 // ---- skinned meshes (st_deform.cpp)
 int st_mesh_set_skin(StEngine* e, StHandle mesh, const StSkinVertex* corners, size_t corner_count, uint32_t joint_count) {
@@ -232,8 +149,8 @@ int st_debug_deformation(StEngine* e, uint64_t* instances_with_previous, uint64_
     ST_REQUIRE(e && instances_with_previous && previous_bytes, "null argument");
     return E(e)->deform.deformation_stats(instances_with_previous, previous_bytes);
 }
-int st_light_insert(StEngine* e, StHandle id, const StLight* l) { ST_REQUIRE(e && l, "null argument"); E(e)->insert_light(id, *l); return ST_OK; }
-int st_light_remove(StEngine* e, StHandle id) { ST_REQUIRE(e, "null engine"); E(e)->remove_light(id); return ST_OK; }
+int st_light_insert(StEngine* e, StHandle id, const StLight* l) { ST_REQUIRE(e && l, "null argument"); E(e)->lights.insert(id, *l); return ST_OK; }
+int st_light_remove(StEngine* e, StHandle id) { ST_REQUIRE(e, "null engine"); E(e)->lights.remove(id); return ST_OK; }
 int st_sun_update(StEngine* e, float azimuth, float altitude) { ST_REQUIRE(e, "null engine"); E(e)->sun_azimuth = azimuth; E(e)->sun_altitude = altitude; E(e)->sun_dirty = true; return ST_OK; }
 
 int st_camera_create(StEngine* e, const StCamera* c, StHandle* out) {
@@ -252,9 +169,7 @@ int st_camera_create(StEngine* e, const StCamera* c, StHandle* out) {
 int st_camera_update(StEngine* e, StHandle h, const StCamera* c) {
     ST_REQUIRE(e && c && c->width && c->height, "bad camera");
     Engine* en = E(e);
-    auto it = en->cameras.find(h);
-    if (it == en->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    CameraState& s = *it->second;
+    ST_CAMERA(s, e, h);
     if (int rc = Engine::upscale_camera_update(s, c->width, c->height)) return rc;   // refused: the camera stays as it was
     const bool invalidated = s.desc.mode != c->mode || s.desc.denoise != c->denoise || s.desc.depth != c->depth || s.desc.width != c->width || s.desc.height != c->height;
     s.desc = *c;
@@ -275,9 +190,7 @@ int st_camera_delete(StEngine* e, StHandle h) {
 }
 int st_camera_set_window(StEngine* e, StHandle h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) {
     ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    CameraState& s = *it->second;
+    ST_CAMERA(s, e, h);
     if (x0 == 0 && x1 == 0) x1 = s.desc.width;
     if (y0 == 0 && y1 == 0) y1 = s.desc.height;
     ST_REQUIRE(y0 < y1 && y1 <= s.desc.height, "bad row window");
@@ -298,56 +211,40 @@ int st_camera_set_rows(StEngine* e, StHandle h, uint32_t y0, uint32_t y1) { retu
 
 int st_camera_set_output_format(StEngine* e, StHandle h, int format) {
     ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    ST_CAMERA(cam, e, h);
     ST_REQUIRE(format >= ST_FORMAT_RGBA32F && format <= ST_FORMAT_BGRA8_UNORM_SRGB, "unknown output format");
-    it->second->out_format = (uint32_t)format;
+    cam.out_format = (uint32_t)format;
     return ST_OK;
 }
 
 // ---- display transforms (st_display.cpp)
-int st_camera_set_display(StEngine* e, StHandle h, const StDisplayDesc* desc) {
-    ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->set_display(*it->second, desc);
-}
+int st_camera_set_display(StEngine* e, StHandle h, const StDisplayDesc* desc) { return camera_set(e, h, &Engine::set_display, desc); }
 int st_camera_get_display(StEngine* e, StHandle h, StDisplayDesc* out, int* enabled) {
     ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    const CameraState& s = *it->second;
+    ST_CAMERA(s, e, h);
     if (out) { *out = s.display; out->struct_size = sizeof(StDisplayDesc); }
     if (enabled) *enabled = s.display_on ? 1 : 0;
     return ST_OK;
 }
 int st_camera_exposure(StEngine* e, StHandle h, float* scale, float* metered_ev, float* adapted_ev) {
     ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->display_exposure(*it->second, scale, metered_ev, adapted_ev);
+    ST_CAMERA(cam, e, h);
+    return E(e)->display_exposure(cam, scale, metered_ev, adapted_ev);
 }
 int st_debug_camera_histogram(StEngine* e, StHandle h, uint32_t bins[64]) {
     ST_REQUIRE(e && bins, "null argument");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->display_histogram(*it->second, bins);
+    ST_CAMERA(cam, e, h);
+    return E(e)->display_histogram(cam, bins);
 }
 
 // ---- output post-processing (st_post.cpp)
-int st_camera_set_post(StEngine* e, StHandle h, const StPostDesc* desc) {
-    ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->set_post(*it->second, desc);
-}
+int st_camera_set_post(StEngine* e, StHandle h, const StPostDesc* desc) { return camera_set(e, h, &Engine::set_post, desc); }
 int st_camera_get_post(StEngine* e, StHandle h, StPostDesc* out, int* enabled) { return camera_get(e, h, &CameraState::post, out, enabled); }
 int st_camera_output_size(StEngine* e, StHandle h, uint32_t* width, uint32_t* height) {
     ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    if (width) *width = it->second->out_width();
-    if (height) *height = it->second->out_height();
+    ST_CAMERA(cam, e, h);
+    if (width) *width = cam.out_width();
+    if (height) *height = cam.out_height();
     return ST_OK;
 }
 int st_post_process(StEngine* e, const StPostDesc* desc, const void* src, uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
@@ -356,12 +253,7 @@ int st_post_process(StEngine* e, const StPostDesc* desc, const void* src, uint32
 }
 
 // ---- the upscale stage (st_upscale.cpp)
-int st_camera_set_upscale(StEngine* e, StHandle h, const StUpscaleDesc* desc) {
-    ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->set_upscale(*it->second, desc);
-}
+int st_camera_set_upscale(StEngine* e, StHandle h, const StUpscaleDesc* desc) { return camera_set(e, h, &Engine::set_upscale, desc); }
 int st_camera_get_upscale(StEngine* e, StHandle h, StUpscaleDesc* out, int* enabled) { return camera_get(e, h, &CameraState::upscale, out, enabled); }
 int st_upscale_process(StEngine* e, const StUpscaleDesc* desc, const void* src, uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
     ST_REQUIRE(e, "null engine");
@@ -376,12 +268,7 @@ int st_debug_set_upscale_fused(StEngine* e, int tile) {
 }
 
 // ---- lens effects (st_lens.cpp)
-int st_camera_set_lens(StEngine* e, StHandle h, const StLensDesc* desc) {
-    ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->set_lens(*it->second, desc);
-}
+int st_camera_set_lens(StEngine* e, StHandle h, const StLensDesc* desc) { return camera_set(e, h, &Engine::set_lens, desc); }
 int st_camera_get_lens(StEngine* e, StHandle h, StLensDesc* out, int* enabled) { return camera_get(e, h, &CameraState::lens, out, enabled); }
 int st_lens_plan(const StLensDesc* desc, uint32_t width, uint32_t height, StLensPlan* out) {
     ST_REQUIRE(desc, "null desc");
@@ -401,12 +288,7 @@ int st_debug_set_lens_gather(StEngine* e, int force) {
 }
 
 // ---- bloom (st_bloom.cpp)
-int st_camera_set_bloom(StEngine* e, StHandle h, const StBloomDesc* desc) {
-    ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->set_bloom(*it->second, desc);
-}
+int st_camera_set_bloom(StEngine* e, StHandle h, const StBloomDesc* desc) { return camera_set(e, h, &Engine::set_bloom, desc); }
 int st_camera_get_bloom(StEngine* e, StHandle h, StBloomDesc* out, int* enabled) { return camera_get(e, h, &CameraState::bloom, out, enabled); }
 int st_bloom_plan(const StBloomDesc* desc, uint32_t width, uint32_t height, uint32_t* levels, uint32_t sizes_wh[16], float factors[8]) {
     ST_REQUIRE(desc, "null desc");
@@ -425,12 +307,7 @@ int st_bloom_process(StEngine* e, const StBloomDesc* desc, const StDisplayDesc* 
 }
 
 // ---- motion blur (st_motion_blur.cpp)
-int st_camera_set_motion_blur(StEngine* e, StHandle h, const StMotionBlurDesc* desc) {
-    ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->set_motion_blur(*it->second, desc);
-}
+int st_camera_set_motion_blur(StEngine* e, StHandle h, const StMotionBlurDesc* desc) { return camera_set(e, h, &Engine::set_motion_blur, desc); }
 int st_camera_get_motion_blur(StEngine* e, StHandle h, StMotionBlurDesc* out, int* enabled) { return camera_get(e, h, &CameraState::mblur, out, enabled); }
 int st_motion_blur_process(StEngine* e, const StMotionBlurDesc* desc, const StDisplayDesc* display, const void* color, const void* velocity, const void* depth,
                            uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
@@ -439,12 +316,7 @@ int st_motion_blur_process(StEngine* e, const StMotionBlurDesc* desc, const StDi
 }
 
 // ---- depth of field (st_dof.cpp)
-int st_camera_set_dof(StEngine* e, StHandle h, const StDofDesc* desc) {
-    ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->set_dof(*it->second, desc);
-}
+int st_camera_set_dof(StEngine* e, StHandle h, const StDofDesc* desc) { return camera_set(e, h, &Engine::set_dof, desc); }
 int st_camera_get_dof(StEngine* e, StHandle h, StDofDesc* out, int* enabled) { return camera_get(e, h, &CameraState::dof, out, enabled); }
 int st_dof_plan(const StDofDesc* desc, uint32_t width, uint32_t height, uint32_t* samples, uint32_t tiles_xy[2], float taps_xyr[64 * 3]) {
     ST_REQUIRE(desc, "null desc");
@@ -462,12 +334,7 @@ int st_dof_process(StEngine* e, const StDofDesc* desc, const StDisplayDesc* disp
 }
 
 // ---- fog (st_fog.cpp)
-int st_camera_set_fog(StEngine* e, StHandle h, const StFogDesc* desc) {
-    ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->set_fog(*it->second, desc);
-}
+int st_camera_set_fog(StEngine* e, StHandle h, const StFogDesc* desc) { return camera_set(e, h, &Engine::set_fog, desc); }
 int st_camera_get_fog(StEngine* e, StHandle h, StFogDesc* out, int* enabled) { return camera_get(e, h, &CameraState::fog, out, enabled); }
 int st_fog_process(StEngine* e, const StFogDesc* desc, const StDisplayDesc* display, const float transform[16], const float projection[16], const void* color, const void* depth,
                    uint32_t width, uint32_t height, void* dst, int dst_format, void* stream) {
@@ -476,12 +343,7 @@ int st_fog_process(StEngine* e, const StFogDesc* desc, const StDisplayDesc* disp
 }
 
 // ---- colour grading (st_grade.cpp)
-int st_camera_set_color_grading(StEngine* e, StHandle h, const StColorGradingDesc* desc) {
-    ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->set_grade(*it->second, desc);
-}
+int st_camera_set_color_grading(StEngine* e, StHandle h, const StColorGradingDesc* desc) { return camera_set(e, h, &Engine::set_grade, desc); }
 int st_camera_get_color_grading(StEngine* e, StHandle h, StColorGradingDesc* out, int* enabled) { return camera_get(e, h, &CameraState::grade, out, enabled); }
 int st_color_grading_plan(const StColorGradingDesc* desc, StColorGradingPlan* out) {
     ST_REQUIRE(desc, "null desc");
@@ -508,12 +370,7 @@ int st_lut_remove(StEngine* e, StHandle id) {
 }
 
 // ---- light shafts (st_shafts.cpp)
-int st_camera_set_light_shafts(StEngine* e, StHandle h, const StLightShaftsDesc* desc) {
-    ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->set_shafts(*it->second, desc);
-}
+int st_camera_set_light_shafts(StEngine* e, StHandle h, const StLightShaftsDesc* desc) { return camera_set(e, h, &Engine::set_shafts, desc); }
 int st_camera_get_light_shafts(StEngine* e, StHandle h, StLightShaftsDesc* out, int* enabled) { return camera_get(e, h, &CameraState::shafts, out, enabled); }
 int st_light_shafts_plan(const StLightShaftsDesc* desc, uint32_t width, uint32_t height, uint32_t cells_wh[2], float jitter[16]) {
     ST_REQUIRE(desc, "null desc");
@@ -540,9 +397,8 @@ int st_debug_set_bloom_tail(StEngine* e, int lds_bytes, uint32_t* in_force) {
 int st_tick(StEngine* e, void* stream) { ST_REQUIRE(e, "null engine"); return E(e)->tick(static_cast<hipStream_t>(stream)); }
 int st_render_camera(StEngine* e, StHandle h, void* out, void* stream) {
     ST_REQUIRE(e, "null engine");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->render(*it->second, out, static_cast<hipStream_t>(stream));
+    ST_CAMERA(cam, e, h);
+    return E(e)->render(cam, out, static_cast<hipStream_t>(stream));
 }
 
 // ---- scene queries (st_query.cpp): argument checks first, so that a host-only engine answers them too
@@ -565,9 +421,8 @@ int st_camera_pick(StEngine* e, StHandle h, const uint32_t* pixels_xy, uint32_t 
     ST_REQUIRE(e, "null engine");
     if (count == 0u) return ST_OK;
     ST_REQUIRE(pixels_xy && hits, "null argument");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->pick(*it->second, pixels_xy, count, hits, static_cast<hipStream_t>(stream));
+    ST_CAMERA(cam, e, h);
+    return E(e)->pick(cam, pixels_xy, count, hits, static_cast<hipStream_t>(stream));
 }
 int st_scene_trace_rays_host(StEngine* e, const StRay* rays, uint32_t count, StRayHit* hits) {
     ST_REQUIRE(e, "null engine");
@@ -583,23 +438,20 @@ int st_camera_render_aovs(StEngine* e, StHandle h, const StAovTargets* targets, 
     bool any = false;
     for (int k = 0; k < ST_AOV_COUNT; k++) any |= targets->planes[k] != nullptr;
     ST_REQUIRE(any, "no AOV plane requested");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->render_aovs(*it->second, *targets, static_cast<hipStream_t>(stream));
+    ST_CAMERA(cam, e, h);
+    return E(e)->render_aovs(cam, *targets, static_cast<hipStream_t>(stream));
 }
 
 int st_debug_keep_all_planes(StEngine* e, int keep) { ST_REQUIRE(e, "null engine"); E(e)->tuning.lean_frame = keep == 0 ? 1u : 0u; return ST_OK; }
 int st_camera_present_copy(StEngine* e, StHandle h, const void* src_device, void* dst_host, size_t bytes, void* stream) {
     ST_REQUIRE(e && src_device && dst_host && bytes, "null argument");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->present_copy(*it->second, src_device, dst_host, bytes, static_cast<hipStream_t>(stream));
+    ST_CAMERA(cam, e, h);
+    return E(e)->present_copy(cam, src_device, dst_host, bytes, static_cast<hipStream_t>(stream));
 }
 int st_camera_present_ready(StEngine* e, StHandle h, const void* dst_host, int wait, int* ready) {
     ST_REQUIRE(e && ready, "null argument");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    return E(e)->present_ready(*it->second, dst_host, wait, ready);
+    ST_CAMERA(cam, e, h);
+    return E(e)->present_ready(cam, dst_host, wait, ready);
 }
 
 int st_set_seed(StEngine* e, uint64_t seed) { ST_REQUIRE(e, "null engine"); E(e)->base_seed = seed; return ST_OK; }
@@ -626,10 +478,8 @@ int st_debug_read_lut(StEngine* e, int what, float* out, size_t capacity_floats,
 int st_camera_read_buffer(StEngine* e, StHandle h, int id, void* out, size_t capacity, size_t* written) {
     ST_REQUIRE(e && id >= 0 && id < ST_BUF_COUNT, "bad buffer id");
     Engine* en = E(e);
-    auto it = en->cameras.find(h);
-    if (it == en->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    ST_CAMERA(c, e, h);
     if (!en->has_device) return fail(ST_ERR_NO_DEVICE, "host-only engine has no camera buffers");
-    CameraState& c = *it->second;
     if (written) *written = c.plane_bytes[id];
     if (!out) return ST_OK;
     ST_REQUIRE(capacity >= c.plane_bytes[id], "buffer too small");
@@ -643,9 +493,7 @@ int st_camera_read_buffer(StEngine* e, StHandle h, int id, void* out, size_t cap
 // earlier launch or frame stored there.
 int st_camera_buffer_stale(StEngine* e, StHandle h, int id, int* stale) {
     ST_REQUIRE(e && stale && id >= 0 && id < ST_BUF_COUNT, "bad argument");
-    auto it = E(e)->cameras.find(h);
-    if (it == E(e)->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
-    const CameraState& c = *it->second;
+    ST_CAMERA(c, e, h);
     const uint32_t lean = c.last_lean;
     bool s = false;
     if (lean & kLeanPrim) s |= (id == ST_BUF_VELOCITY_MAP && !(lean & kLeanKeepVelocity)) || id == ST_BUF_PRIM_SURFACE_MAP_A || id == ST_BUF_PRIM_SURFACE_MAP_B;   // (a frame that blurs keeps the velocity map)
@@ -659,10 +507,8 @@ int st_camera_buffer_stale(StEngine* e, StHandle h, int id, int* stale) {
 int st_camera_write_buffer(StEngine* e, StHandle h, int id, const void* data, size_t bytes) {
     ST_REQUIRE(e && data && id >= 0 && id < ST_BUF_COUNT, "bad buffer id");
     Engine* en = E(e);
-    auto it = en->cameras.find(h);
-    if (it == en->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    ST_CAMERA(c, e, h);
     if (!en->has_device) return fail(ST_ERR_NO_DEVICE, "host-only engine has no camera buffers");
-    CameraState& c = *it->second;
     ST_REQUIRE(bytes == c.plane_bytes[id], "size does not match the buffer");
     ST_HIP(hipSetDevice(en->device));
     ST_HIP(hipDeviceSynchronize());
@@ -675,10 +521,8 @@ int st_camera_write_buffer(StEngine* e, StHandle h, int id, const void* data, si
 int st_debug_variance_flags(StEngine* e, StHandle h, uint64_t* tile_mask_out, size_t capacity_tiles, size_t* tiles) {
     ST_REQUIRE(e && tiles, "null argument");
     Engine* en = E(e);
-    auto it = en->cameras.find(h);
-    if (it == en->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    ST_CAMERA(c, e, h);
     if (!en->has_device) return fail(ST_ERR_NO_DEVICE, "host-only engine");
-    CameraState& c = *it->second;
     *tiles = c.tile_mask_tiles();
     if (!tile_mask_out) return ST_OK;
     ST_REQUIRE(capacity_tiles >= c.tile_mask_tiles(), "buffer too small");
@@ -728,17 +572,16 @@ int st_engine_get_arithmetic(StEngine* e, int* out) { ST_REQUIRE(e && out, "null
 int st_camera_ray_count(StEngine* e, StHandle h, uint64_t* out, int reset) {
     ST_REQUIRE(e && out, "null argument");
     Engine* en = E(e);
-    auto it = en->cameras.find(h);
-    if (it == en->cameras.end()) return fail(ST_ERR_UNKNOWN_CAMERA, "camera does not exist");
+    ST_CAMERA(cam, e, h);
     if (!en->has_device) return fail(ST_ERR_NO_DEVICE, "host-only engine");
     unsigned long long host[2 * KS_COUNT];
     ST_HIP(hipSetDevice(en->device));
     ST_HIP(hipDeviceSynchronize());
-    { const int rc2 = read_counters(*it->second, host); if (rc2) return rc2; }
+    { const int rc2 = read_counters(cam, host); if (rc2) return rc2; }
     uint64_t total = 0;
     for (int i = 0; i < KS_COUNT; i++) total += host[2 * i];
     *out = total;
-    if (reset) { ST_HIP(hipMemset(it->second->counters.ptr, 0, kCounterBytes)); memset(it->second->profiled_traversal_bytes, 0, sizeof(it->second->profiled_traversal_bytes)); ST_HIP(hipDeviceSynchronize()); }
+    if (reset) { ST_HIP(hipMemset(cam.counters.ptr, 0, kCounterBytes)); memset(cam.profiled_traversal_bytes, 0, sizeof(cam.profiled_traversal_bytes)); ST_HIP(hipDeviceSynchronize()); }
     return ST_OK;
 }
 int st_debug_read_scene(StEngine* e, int what, void* out, size_t capacity, size_t* written) {
@@ -748,12 +591,12 @@ int st_debug_read_scene(StEngine* e, int what, void* out, size_t capacity, size_
     if (SceneTree::debug_reads(what)) {   // the tree's buffers (0, 4, 6 - 17): it brings them up to date itself
         if (int rc = en->tree.debug_read(what, &p, &bytes)) return rc;
     } else {
-        if (what == 1 && en->any_host_stale()) en->bake_stale_on_host();   // instances the device moved: the host arrays catch up
+        if (what == 1 && en->instances.any_host_stale()) en->bake_stale_on_host();   // instances the device moved: the host arrays catch up
         if (int rc = en->take_deferred_status()) return rc;   // (their posed triangles could not be read back)
         switch (what) {
-            case 1: p = en->triangles.data(); bytes = en->triangles.size() * sizeof(HostTriangle); break;
-            case 2: p = en->gpu_lights.data(); bytes = en->gpu_lights.size() * sizeof(GpuLight); break;
-            case 3: p = en->gpu_materials.data(); bytes = en->gpu_materials.size() * sizeof(GpuMaterial); break;
+            case 1: p = en->slots.triangles().data(); bytes = en->slots.size() * sizeof(HostTriangle); break;
+            case 2: p = en->lights.table().data(); bytes = en->lights.table().size() * sizeof(GpuLight); break;
+            case 3: p = en->materials.gpu().data(); bytes = en->materials.gpu().size() * sizeof(GpuMaterial); break;
             default: return fail(ST_ERR_INVALID_ARGUMENT, "unknown scene buffer");
         }
     }
@@ -765,7 +608,7 @@ int st_debug_read_scene(StEngine* e, int what, void* out, size_t capacity, size_
 }
 int st_debug_world(StEngine* e, uint32_t* light_count, uint32_t* next_frame) {
     ST_REQUIRE(e && light_count && next_frame, "null argument");
-    *light_count = E(e)->light_count; *next_frame = E(e)->frame;
+    *light_count = E(e)->lights.count(); *next_frame = E(e)->frame;
     return ST_OK;
 }
 

@@ -47,7 +47,7 @@ void SceneTree::expand_stream() {
         } else {
             const uint32_t tri = f2b(bvh_stream[p].y);
             bvh_upload_[o] = bvh_stream[p];
-            for (int k = 0; k < 3; k++) bvh_upload_[o + 1 + k] = e.tri_geo[3 * (size_t)tri + k];
+            for (int k = 0; k < 3; k++) bvh_upload_[o + 1 + k] = e.slots.geo()[3 * (size_t)tri + k];
             p += 1;
         }
     }
@@ -66,7 +66,7 @@ void SceneTree::expand_stream() {
 // of an internal node, bit 31 set on a task's root.
 void SceneTree::index_device_tree() {
     const uint32_t n_entries = device_bvh_len / 4u;
-    entry_of_tri_.assign(e.tri_geo.size() / 3u, 0xffffffffu);
+    entry_of_tri_.assign(e.slots.size(), 0xffffffffu);
     parent_.assign(std::max<uint32_t>(n_entries, 1u), 0xffffffffu);
     refit_local_.assign(std::max<uint32_t>(n_entries, 1u), 0u);
     refit_items_.clear(); refit_batch_off_.assign(1, 0u); refit_levels_.clear();
@@ -196,7 +196,7 @@ void SceneTree::mark_internal_starts() {
 uint64_t SceneTree::topology_of(const std::vector<uint8_t>& blend) const {
     uint64_t h = 0x9e3779b97f4a7c15ull;
     auto mix = [&h](uint64_t v) { h = (h ^ v) * 0x100000001b3ull; h ^= h >> 29; };
-    for (size_t i = 0; i < e.prims.size(); i++) if (e.prim_alive[i]) mix(((uint64_t)i << 32) | e.prims[i].material_id);
+    for (size_t i = 0; i < e.slots.size(); i++) if (e.slots.alive()[i]) mix(((uint64_t)i << 32) | e.slots.prims()[i].material_id);
     mix(0xffffffffffffffffull);
     for (uint8_t b : blend) mix(b);
     return h;
@@ -221,7 +221,7 @@ Aabb SceneTree::subtree_box(size_t p) const {
         return box;
     }
     for (;; p++) {
-        const float4* b = &e.tri_bounds[2u * (size_t)f2b(bvh_stream[p].y)];  // = prims[...].bounds, 32 B apart instead of 56
+        const float4* b = &e.slots.bounds()[2u * (size_t)f2b(bvh_stream[p].y)];  // = prims[...].bounds, 32 B apart instead of 56
         box.grow(v3(b[0].x, b[0].y, b[0].z)); box.grow(v3(b[1].x, b[1].y, b[1].z));
         if (!(f2b(bvh_stream[p].x) & 1u)) return box;
     }
@@ -246,11 +246,11 @@ void SceneTree::refit_span(size_t begin, size_t end) {
 // ---- the host tree and the device builder
 // The host's binned-SAH tree of the scene as it is now (st_bvh.h: the reference's tree, with unchanged subtrees reused) and its flattened stream.
 void SceneTree::rebuild_host_tree(bool timing) {
-    if (e.any_host_stale()) e.bake_stale_on_host();
-    const std::vector<uint8_t> blend = e.blend_flags();
+    if (e.instances.any_host_stale()) e.bake_stale_on_host();
+    const std::vector<uint8_t> blend = e.materials.blend_flags();
     const auto t1 = TickClock::now();
     bvh.begin_refresh();  // keeps the previous tree: unchanged subtrees are copied, not rebuilt (same result as a fresh build)
-    for (size_t i = 0; i < e.prims.size(); i++) if (e.prim_alive[i]) bvh.prims.push_back(e.prims[i]);
+    for (size_t i = 0; i < e.slots.size(); i++) if (e.slots.alive()[i]) bvh.prims.push_back(e.slots.prims()[i]);
     const auto t2 = TickClock::now();
     bvh.run();
     const auto t3 = TickClock::now();
@@ -284,9 +284,9 @@ bool SceneTree::device_build_possible() const {
     // the device's LBVH (two rows: the device's by 1 and 6 %); at 3.7 the device's is 1-2 % faster; at 4.2-4.5 (the dungeon with its level split x16: runs of up to 140
     // coplanar triangles, a wide walk's step each) 5-17 % faster. A triangle COUNT does not separate them: 16 instanced copies of the level (139 k triangles, weight 1.8)
     // render 1-7 % faster on the host's tree, the x16-split level (134 k, weight 4.5) 12-17 % faster on the device's.
-    const bool automatic = bvh_refresh_mode == ST_BVH_AUTO && (e.copies.scene.written || auto_first_on_device) && e.live_prims_ > kLdsSceneTexels / 4u;
+    const bool automatic = bvh_refresh_mode == ST_BVH_AUTO && (e.copies.scene.written || auto_first_on_device) && e.slots.live() > kLdsSceneTexels / 4u;
     if (!(bvh_refresh_mode == ST_BVH_BUILD_DEVICE || automatic) || !e.has_device || !e.wide_only_tuning() || e.heatmap_camera()) return false;
-    return e.live_prims_ >= 2u && e.prims.size() < (1u << 23);
+    return e.slots.live() >= 2u && e.slots.size() < (1u << 23);
 }
 bool SceneTree::moves_stay_on_device() const {
     // (ST_BVH_BUILD_DEVICE: the same, with the tree rebuilt on the device from the device-baked arrays instead of refitted)
@@ -311,19 +311,18 @@ int SceneTree::reserve_device_builder(TreeCopy& t, size_t slots, uint32_t live) 
 int SceneTree::build_on_device(SceneSet& set, hipStream_t up, bool* pageable) {
     int rc;
     TreeCopy& t = set.tree;
-    const size_t slots = e.prims.size();
+    const size_t slots = e.slots.size();
     const auto t0 = TickClock::now();
     if (tri_info_built_for_ != tri_info_serial_ || tri_info_.size() != slots) {   // (a tick in which instances only moved changes none of this)
         auto word = [&](size_t i) {
-            const uint32_t mat = e.prims[i].material_id;
-            const uint32_t blend = mat < e.materials.size() && e.materials[mat].alpha_mode == 1u ? 2u : 0u;
-            return (e.prim_alive[i] ? 1u : 0u) | blend | (mat << 2);
+            const uint32_t mat = e.slots.prims()[i].material_id;
+            return (e.slots.alive()[i] ? 1u : 0u) | (e.materials.is_blend(mat) ? 2u : 0u) | (mat << 2);
         };
         if (info_full_ || tri_info_.size() != slots) {
             tri_info_.resize(slots);
             tri_info_live_ = 0;
             for (size_t i = 0; i < slots; i++) { tri_info_[i] = word(i); tri_info_live_ += tri_info_[i] & 1u; }
-            e.live_prims_ = tri_info_live_;
+            e.slots.set_live(tri_info_live_);
         } else {   // only the slots an instance took or gave back since the last listing (208 k slots: the full listing was 0.25-0.35 ms of a 0.45-ms tick)
             for (size_t i = info_dirty_lo_; i < std::min(info_dirty_hi_, slots); i++) { const uint32_t w = word(i); tri_info_live_ += (w & 1u) - (tri_info_[i] & 1u); tri_info_[i] = w; }
         }
@@ -385,7 +384,7 @@ TreePlan SceneTree::plan(bool instances_changed, bool moved_on_device, bool mate
         const auto t1 = TickClock::now();
         const bool refitting = bvh_refresh_mode == ST_BVH_REFIT || bvh_refresh_mode == ST_BVH_REFIT_DEVICE;
         // (moved_on_device: refresh_instances saw nothing but transforms change — slots, materials and Blend flags are what the last build saw)
-        const uint64_t signature = moved_on_device ? topology_signature : (refitting ? topology_of(e.blend_flags()) : 0);
+        const uint64_t signature = moved_on_device ? topology_signature : (refitting ? topology_of(e.materials.blend_flags()) : 0);
         if (refitting && have_topology && !host_tree_stale && signature == topology_signature) {
             // ST_BVH_REFIT_DEVICE: the boxes are recomputed on the device from the moved triangles' bounds (k_bvh.hip); the host's
             // copy of the stream is brought up to date only when something reads it
@@ -418,16 +417,15 @@ int SceneTree::write(SceneSet& set, TreePlan plan, hipStream_t up, bool* pageabl
     TreeCopy& t = set.tree;
     const bool build_now = plan == TreePlan::device_build || plan == TreePlan::device_refit;
     // (finding 4: the reservation asks the tuning half of "nothing observes the contract stream", not the camera half)
-    if (!e.copies.scene.written && (bvh_refresh_mode == ST_BVH_AUTO || bvh_refresh_mode == ST_BVH_BUILD_DEVICE) && e.wide_only_tuning() && e.live_prims_ > kLdsSceneTexels / 4u && e.prims.size() < (1u << 23)) {
+    if (!e.copies.scene.written && (bvh_refresh_mode == ST_BVH_AUTO || bvh_refresh_mode == ST_BVH_BUILD_DEVICE) && e.wide_only_tuning() && e.slots.live() > kLdsSceneTexels / 4u && e.slots.size() < (1u << 23)) {
         // this scene's changes (and, for a large scene, its first tree: device_build_possible) go to the device builder: its arrays are allocated NOW, while the
         // scene loads, for both copies — BEFORE the wide stream of this copy is written below (its allocation is one of them: growing it afterwards would throw the stream away: round 6's
         // first version did, and rendered an empty world). A failure here is not an error: the build allocates what it finds missing.
         // ... and the host's triangle arrays get the same headroom now, so that the first spawn does not reallocate and copy them (60 MB at 208 k triangles: 7 ms)
-        const size_t want = e.triangles.size() + e.triangles.size() / 8u;
-        e.triangles.reserve(want); e.prims.reserve(want); e.prim_alive.reserve(want); e.tri_geo.reserve(3 * want); e.tri_attr.reserve(4 * want); e.tri_bounds.reserve(2 * want);
+        e.slots.reserve(e.slots.size() + e.slots.size() / 8u);
         bool reserved = true;
         for (SceneSet& s : e.copies.scene.copy)
-            if (reserve_device_builder(s.tree, e.prims.size() + e.prims.size() / 8u, (uint32_t)std::min<size_t>(e.live_prims_ + e.live_prims_ / 8u, e.prims.size() + e.prims.size() / 8u)) != ST_OK) { (void)hipGetLastError(); reserved = false; break; }
+            if (reserve_device_builder(s.tree, e.slots.size() + e.slots.size() / 8u, (uint32_t)std::min<size_t>(e.slots.live() + e.slots.live() / 8u, e.slots.size() + e.slots.size() / 8u)) != ST_OK) { (void)hipGetLastError(); reserved = false; break; }
         if (reserved && !build_now && e.copies.scene.copy[0].tree.lb_small.ptr) lbvh_warm(static_cast<int*>(e.copies.scene.copy[0].tree.lb_small.ptr), up);   // ... and the builder's code object is on the device before the first spawn
     }
     if (build_now) {
@@ -439,7 +437,7 @@ int SceneTree::write(SceneSet& set, TreePlan plan, hipStream_t up, bool* pageabl
     const bool device_path = !build_now && device_refit_possible() && set.valid && !set.tri_full && t.tree_version == tree_version && e.tri_fits(set, Engine::TRI_GEO);
     *attr_sent = build_now;   // (build_on_device sent them)
     // a copy that cannot be brought up to date in place is sent whole, from the host's arrays: instances the device moved must be in them
-    if (!device_path && !build_now && e.any_host_stale()) e.bake_stale_on_host();
+    if (!device_path && !build_now && e.instances.any_host_stale()) e.bake_stale_on_host();
     if (device_path) {
         // This copy holds the current tree; only boxes and moved triangles are behind. Send the records and bounds of the
         // triangle slots baked since it was written and let the device patch its leaf entries and refit its boxes.
@@ -574,7 +572,7 @@ int SceneTree::walk_args(const TreeCopy& scene, KArgs& a, bool heatmap) const {
 // ---- st_debug_read_scene's tree cases
 int SceneTree::debug_read(int what, const void** p, size_t* bytes) {
     const bool live_copy = what == LiveStream || what == LiveWideNodes || what == LiveWideLeaves;   // read from the device as it is: the host catches up with nothing
-    if (!live_copy && e.any_host_stale()) e.bake_stale_on_host();   // instances the device moved: the host arrays catch up
+    if (!live_copy && e.instances.any_host_stale()) e.bake_stale_on_host();   // instances the device moved: the host arrays catch up
     if (int rc = e.take_deferred_status()) return rc;   // (their posed triangles could not be read back)
     if (!live_copy && host_tree_stale) rebuild_host_tree(false);   // ST_BVH_BUILD_DEVICE left the host's tree behind
     switch (what) {
@@ -595,7 +593,7 @@ int SceneTree::debug_read(int what, const void** p, size_t* bytes) {
             for (const auto& l : refit_levels_) { readback_levels_.push_back(l.first); readback_levels_.push_back(l.second); }
             const std::vector<uint32_t>* v = what == RefitParent ? &parent_ : what == RefitLocal ? &refit_local_ : what == RefitItems ? &refit_items_ : what == RefitBatchOff ? &refit_batch_off_
                                            : what == RefitLevels ? &readback_levels_ : &entry_of_tri_;
-            if (what == RefitBounds) { *p = e.tri_bounds.data(); *bytes = e.tri_bounds.size() * sizeof(float4); }
+            if (what == RefitBounds) { *p = e.slots.bounds().data(); *bytes = e.slots.bounds().size() * sizeof(float4); }
             else { *p = v->data(); *bytes = v->size() * sizeof(uint32_t); }
             break;
         }

@@ -39,7 +39,7 @@ struct TreeCopy {
 };
 
 struct SceneTree {
-    Engine& e;   // its triangle-slot store, its materials and instances, its scene copies and their fences, its tuning, its staging ring, its device
+    Engine& e;   // its triangle slots (read through TriangleSlots' accessors; set_live is the one call that changes them), its materials and instances, its scene copies and their fences, its tuning, its staging ring, its device
     explicit SceneTree(Engine& engine) : e(engine) {}
 
     // ---- the host's binned-SAH tree, its contract stream and the stream's device form

@@ -63,6 +63,11 @@ struct SceneCopies {
         (c.other ? io.copied : io.uploaded) = true;   // (in-place uploads are work on the caller's stream)
     }
     int end_uploads(TickIo& io);
+    // ---- what the refresh of the host's triangle slots leaves for both copies (st_scene.cpp)
+    void owe_slots(size_t b, size_t end) { for (SceneSet& t : scene.copy) { t.dirty_lo = std::min(t.dirty_lo, b); t.dirty_hi = std::max(t.dirty_hi, end); } }   // slots [b, end) are owed to every copy
+    void owe_whole_arrays() { for (SceneSet& t : scene.copy) t.tri_full = true; }   // the host's arrays grew: every copy's triangle arrays are sent whole
+    void instance_moved(uint64_t id) { for (SceneSet& t : scene.copy) if (std::find(t.pending_moves.begin(), t.pending_moves.end(), id) == t.pending_moves.end()) t.pending_moves.push_back(id); }
+    void void_pending_moves() { for (SceneSet& t : scene.copy) t.pending_moves.clear(); }   // the host baked what the device had moved
     // ---- the readers
     int begin(hipStream_t stream, unsigned reads);
     int end(hipStream_t stream, unsigned reads);

@@ -21,15 +21,15 @@ using SkinRec = Deformer::SkinRec;
 
 // what st_mesh_set_skin and st_mesh_set_morph_targets ask of their mesh: it exists, and `corner_count` is its corners
 int mesh_triangles(const Engine& e, uint64_t mesh, size_t corner_count, size_t* triangles) {
-    auto m = e.meshes.find(mesh);
-    if (m == e.meshes.end()) return fail(ST_ERR_INVALID_ARGUMENT, "no such mesh");
-    if (corner_count != 3u * m->second.size()) return fail(ST_ERR_INVALID_ARGUMENT, "corner_count is not 3 x the mesh's triangles");
-    *triangles = m->second.size();
+    const std::vector<StMeshTriangle>* m = e.meshes.find(mesh);
+    if (!m) return fail(ST_ERR_INVALID_ARGUMENT, "no such mesh");
+    if (corner_count != 3u * m->size()) return fail(ST_ERR_INVALID_ARGUMENT, "corner_count is not 3 x the mesh's triangles");
+    *triangles = m->size();
     return ST_OK;
 }
 
 // the deformation of this instance, created if absent
-DeformRec& record_of(Deformer& d, const Engine::InstanceRec& inst) {
+DeformRec& record_of(Deformer& d, const InstanceRec& inst) {
     auto it = d.deforms.find(inst.id);
     if (it == d.deforms.end()) {
         it = d.deforms.emplace(inst.id, DeformRec{}).first;
@@ -38,9 +38,8 @@ DeformRec& record_of(Deformer& d, const Engine::InstanceRec& inst) {
     return it->second;
 }
 
-void mark_instance(Engine& e, Engine::InstanceRec* inst) { if (inst) { inst->dirty = true; e.instances_dirty = true; } }
 // the next tick computes `r` again; xform and prev_xform stay: a deformation that changes is a "move" (refresh_instances)
-void mark(Engine& e, DeformRec& r, Engine::InstanceRec* inst) { r.reskin = true; r.changed = true; mark_instance(e, inst); }
+void mark(Engine& e, DeformRec& r, InstanceRec* inst) { r.reskin = true; r.changed = true; e.instances.mark_dirty(inst); }
 
 // The one release path of a deformation's regions (frames still reading a second region: deform_read). The second region goes with what it was
 // computed from; `whole`: the current one goes too.
@@ -61,7 +60,7 @@ void drop_part(Deformer& d, uint64_t instance, bool palette, bool weights, bool 
     if (weights) r.weights.clear();
     if (r.palette.empty() && r.weights.empty()) { d.drop_instance(instance, true); return; }   // back to the base mesh
     if (forget) release(d, r, false);
-    mark(d.e, r, d.e.find_instance(instance));
+    mark(d.e, r, d.e.instances.find(instance));
 }
 
 uint32_t padded_to_block(size_t triangles) { return (uint32_t)((triangles + kSkinBlock - 1u) / kSkinBlock * kSkinBlock); }
@@ -91,7 +90,7 @@ int Deformer::set_skin(uint64_t mesh, const StSkinVertex* corners, size_t corner
 
 int Deformer::set_pose(uint64_t instance, const float* joint_xforms, uint32_t joint_count) {
     if (!e.has_device) return fail(ST_ERR_NO_DEVICE, "skinning runs on the device: a host-only engine has no poses");
-    Engine::InstanceRec* inst = e.find_instance(instance);
+    InstanceRec* inst = e.instances.find(instance);
     if (!inst) return fail(ST_ERR_INVALID_ARGUMENT, "no such instance");
     auto skin = skins.find(inst->mesh);
     if (skin == skins.end()) return fail(ST_ERR_INVALID_ARGUMENT, "the instance's mesh has no skin");
@@ -113,7 +112,7 @@ void Deformer::drop_instance(uint64_t instance, bool make_dirty) {
     if (it == deforms.end()) return;
     release(*this, it->second, true);   // (deformation motion: the previous positions go with the deformation)
     deforms.erase(it);
-    if (make_dirty) mark_instance(e, e.find_instance(instance));
+    if (make_dirty) e.instances.mark_dirty(instance);
 }
 
 void Deformer::drop_skin(uint64_t mesh) {
@@ -159,7 +158,7 @@ int Deformer::set_morph_targets(uint64_t mesh, const StMorphDelta* deltas, size_
 
 int Deformer::set_morph_weights(uint64_t instance, const float* weights, uint32_t target_count) {
     if (!e.has_device) return fail(ST_ERR_NO_DEVICE, "morphing runs on the device: a host-only engine has no morph weights");
-    Engine::InstanceRec* inst = e.find_instance(instance);
+    InstanceRec* inst = e.instances.find(instance);
     if (!inst) return fail(ST_ERR_INVALID_ARGUMENT, "no such instance");
     auto morph = morphs.find(inst->mesh);
     if (morph == morphs.end()) return fail(ST_ERR_INVALID_ARGUMENT, "the instance's mesh has no morph targets");

@@ -44,10 +44,6 @@ static void tuning_from_environment(StTuning& t) {
 }
 
 Engine::Engine() {
-    GpuLight sun{};
-    sun.d0 = make_float4(0, 0, 0, 25.0f); sun.d1 = make_float4(0, 0, 0, INFINITY); sun.d2 = make_float4(b2f(1u), 0, 0, 0);
-    light_buffer.push_back(sun);
-    light_slot[-1] = 0;
     blue_noise.assign(256 * 256 * 4, 0);
     reset_profile_totals();
     tuning = default_tuning();

@@ -1,6 +1,6 @@
 // st_engine.h — the host engine of libstrolle_hip.so: state and interfaces shared by its translation units
 //   st_engine.cpp       construction, tuning (StTuning + environment), destruction
-//   st_scene.cpp        scene stores: materials, images, lights, instances -> world-space triangles (baking)
+//   st_scene.cpp        the scene stores (st_stores.h): lights, materials, the image atlas, meshes, instances, triangle slots; the tick's phases that connect them (baking)
 //   st_bvh_refresh.cpp  the scene's BVH (st_bvh_refresh.h): the host's tree and its streams, refits, the wide topology, the device builder's input, the tick's tree plan
 //   st_tick.cpp         Engine::tick: refresh of the stores + uploads (page-locked staging); the tick's device copies (st_copies.h): double-buffered scene / light copies, their readers, retirement
 //   st_render.cpp       per-camera buffers and Engine::render: the per-frame pass graph in phases, on two HIP streams; present hand-over
@@ -330,6 +330,7 @@ inline int grow_store(DeviceArray& a, size_t bytes, bool* fresh, std::initialize
 inline double format_bytes(uint32_t format) { return format == ST_FORMAT_RGBA32F ? 16.0 : (format == ST_FORMAT_RGBA16F ? 8.0 : 4.0); }   // of one pixel (StOutputFormat)
 
 }  // namespace st
+#include "st_stores.h"
 #include "st_deform.h"
 #include "st_bvh_refresh.h"
 #include "st_copies.h"
@@ -474,19 +475,11 @@ struct Engine {
     uint64_t base_seed = 0;
     uint32_t frame = 1;  // lib.rs:152
 
-    // meshes / materials / instances / triangles
-    std::unordered_map<uint64_t, std::vector<StMeshTriangle>> meshes;
-    // Device bake (StTuning::device_bake; k_bvh.hip k_bvh_bake): object-space meshes live on the device too (24 floats per triangle, appended
-    // when an instance of the mesh is first moved on the device; a re-inserted mesh is a new version and is appended again).
-    std::unordered_map<uint64_t, uint64_t> mesh_version; uint64_t next_mesh_version = 1;
-    struct DeviceMeshRec { size_t first, count; uint64_t version; };
-    std::unordered_map<uint64_t, DeviceMeshRec> device_meshes;
-    std::vector<float> mesh_store_host; DeviceArray d_mesh_store; size_t mesh_store_uploaded = 0;   // floats
+    // The scene stores (st_stores.h), one owner each; the members below connect them in a tick
+    MeshStore meshes; MaterialStore materials; ImageAtlas images; LightStore lights; InstanceStore instances; TriangleSlots slots;
     bool moved_on_device = false;      // this tick's refresh left the moved instances to the device
     bool materials_changed_this_tick = false;
-    bool instance_removed = false;     // since the last refresh: the set of triangle slots changed, the tree will be rebuilt
     uint64_t device_bakes = 0, device_baked_triangles = 0;
-    bool any_host_stale() const { for (const auto& i : instances) if (i.host_stale) return true; return false; }
     void bake_stale_on_host();         // brings the host arrays up to date (rebuilds, host refits, full uploads and debug reads need them)
 
     // Mesh deformation — skinned meshes, morph targets, deformation motion — has one owner (st_deform.h)
@@ -494,48 +487,14 @@ struct Engine {
     int deferred_status = ST_OK;      // a read-back that failed inside a refresh or bake_stale_on_host (message in g_last_error): st_tick / st_debug_read_scene return it
     int take_deferred_status() { const int rc = deferred_status; deferred_status = ST_OK; return rc; }
 
-    std::vector<StMaterial> materials; std::unordered_map<uint64_t, uint32_t> material_slot; SlotRanges material_free; bool materials_dirty = false;
-    std::vector<GpuMaterial> gpu_materials; std::vector<uint32_t> material_base_packed;
-    struct InstanceRec {
-        uint64_t id, mesh, material; Affine xform, xform_inv, prev_xform; bool dirty; uint32_t xslot;
-        // what the triangle slots of this instance were baked from (device bake: a later change of the transform alone can be baked on the device)
-        uint64_t baked_mesh = 0, baked_mesh_version = 0; uint32_t baked_material = 0xffffffffu; bool baked = false;
-        bool host_stale = false;   // moved on the device since the host arrays (triangles, prims, tri_geo / attr / bounds) were last baked
-    };
-    std::vector<InstanceRec> instances; bool instances_dirty = false;
-    InstanceRec* find_instance(uint64_t id) { for (auto& r : instances) if (r.id == id) return &r; return nullptr; }
-    // per-instance transforms for primary visibility's prev_point (the reference's per-draw push constants,
-    // passes/prim_raster.rs:196-230): 8 float4 per stable slot — curr_xform_inv (x, y, z axes, translation), then prev_xform.
-    // tri_attr[4 t + 3].w holds the slot of the instance that owns triangle t.
-    std::vector<float4> instance_xforms; std::vector<uint32_t> xslot_free;
-    std::map<uint64_t, std::pair<size_t, size_t>> instance_triangles; SlotRanges triangle_free;
-    std::vector<HostTriangle> triangles; std::vector<BuildPrim> prims; std::vector<uint8_t> prim_alive;
-    size_t live_prims_ = 0;   // how many of prim_alive are set (kept by refresh_instances / drop_instance_triangles: device_build_possible asks every tick)
-    std::vector<float4> tri_geo, tri_attr, tri_bounds;  // tri_bounds: (lo, hi) per triangle slot (device refit)
     // The scene's BVH — the host's tree, its streams, refits, the device builder, the tick's plan — has one owner (st_bvh_refresh.h)
     SceneTree tree{*this};
 
-    // images: a single linear RGBA8 atlas of the reference's extent (images.rs:28-29); rectangles from st_atlas.h
-    static constexpr uint32_t kAtlasW = 8192, kAtlasMaxH = 8192;
-    uint32_t atlas_w = 0, atlas_h = 0; std::vector<uint8_t> atlas; bool atlas_dirty = false;
-    struct ImageRec { uint32_t x, y, w, h; };
-    std::unordered_map<uint64_t, ImageRec> images; AtlasShelves atlas_rects{kAtlasW, kAtlasMaxH};
-    // ImageData::Texture (image.rs:46-59): pixels that live in device memory. Static ones are copied into the atlas once
-    // (and mirrored into the host copy, which stays the source of every later re-upload); dynamic ones at every tick
-    // (images.rs:187-213). std::map: copies are issued in handle order.
-    struct DeviceImage { const void* pixels; size_t pitch; bool dynamic, pending; };
-    std::map<uint64_t, DeviceImage> device_images;
     StagingRing staging;
 
-    // lights (lights.rs): slot 0 is the sun
-    std::vector<GpuLight> light_buffer; std::map<int64_t, uint32_t> light_slot;
-    std::vector<int64_t> lights_created, lights_updated; std::map<int64_t, uint32_t> lights_remapped; std::vector<uint32_t> lights_killed;
-    uint32_t next_light_id = 1;
-    std::vector<GpuLight> gpu_lights, uploaded_lights;
-    std::map<int64_t, uint32_t> light_slot_uploaded;   // light_slot as gpu_lights was snapshot (snapshot_lights): which slot of the device's table a handle has
     bool sync_every_tick = false;
     float sun_azimuth = 0.0f, sun_altitude = 0.35f; bool sun_dirty = true;
-    uint32_t light_count = 0; V3 sun_dir_ = v3s(0.0f);
+    V3 sun_dir_ = v3s(0.0f);
 
     std::vector<uint8_t> blue_noise; bool blue_noise_dirty = true;
     bool atmosphere_initialized = false, sky_known = false; float known_sun_altitude = 0.0f;  // passes/atmosphere.rs:14-15,78-110
@@ -608,24 +567,18 @@ struct Engine {
     int present_copy(CameraState& c, const void* src, void* dst, size_t bytes, hipStream_t stream);
     int present_ready(CameraState& c, const void* dst, int wait, int* ready);
 
-    float4 image_rect(uint64_t h) const;
-    void rebuild_gpu_materials();
-
-    // ---- lights (lights.rs:49-172, light.rs:25-79)
-    static void note(std::vector<int64_t>& v, int64_t k) { if (std::find(v.begin(), v.end(), k) == v.end()) v.push_back(k); }
-    void overwrite_light(uint32_t slot, int64_t key, GpuLight g);
-    void insert_light(uint64_t id, const StLight& l);
-    void remove_light(uint64_t id);
-    void snapshot_lights();
+    // ---- the entry points that touch more than one owner (st_scene.cpp): a store and the deformer, the tree
+    void insert_mesh(uint64_t id, const StMeshTriangle* t, size_t count);
+    void remove_mesh(uint64_t id);
+    void insert_instance(uint64_t id, uint64_t mesh, uint64_t material, const Affine& x);
+    void remove_instance(uint64_t id);
 
     void drop_instance_triangles(uint64_t id);
-    void bake(const StMeshTriangle& t, const InstanceRec& inst, uint32_t material, size_t slot);
     struct BakeJob { const std::vector<StMeshTriangle>* mesh; const InstanceRec* inst; uint32_t material; size_t first, count; };
     bool refresh_instances();
     void bake_jobs_on_host(const std::vector<BakeJob>& jobs, size_t total);
     int bake_on_device(SceneSet& t, hipStream_t up, bool* pageable);
 
-    std::vector<uint8_t> blend_flags() const { std::vector<uint8_t> b(materials.size()); for (size_t i = 0; i < materials.size(); i++) b[i] = materials[i].alpha_mode == 1u; return b; }
     // Nothing observes the contract stream (a device-built tree can replace it) while every ray walks the wide stream: the fast build with the
     // wide stream and what it rests on, no traversal bytes counted (this part: wide_only_tuning) — and no camera draws the heatmap.
     bool wide_only_tuning() const { return arithmetic == ST_ARITH_FAST && tuning.wide_bvh && tuning.compact_bvh && tuning.anyhit_fast && !count_bytes; }
@@ -772,10 +725,10 @@ struct Engine {
     int shafts_process(const StLightShaftsDesc* desc, const StDisplayDesc* display, const float* transform, const float* projection, const void* color, const void* depth,
                        uint32_t w, uint32_t h, void* dst, int format, hipStream_t stream);
     FencedPlanes<1> shafts_scratch;   // st_light_shafts_process's cell plane: grown, never shrunk
-    // Normal mapping (include/strolle_hip.h "normal mapping"; st_traverse.h normal_map_apply). `normal_mapping` is the switch; any_normal_map: some material's
-    // normal_map_texture resolved to an atlas rectangle at the last st_tick (rebuild_gpu_materials). normal_map_geo: the argument primary visibility, the NORMAL AOV and
+    // Normal mapping (include/strolle_hip.h "normal mapping"; st_traverse.h normal_map_apply). `normal_mapping` is the switch (MaterialStore::any_normal_map: whether
+    // anything can be mapped). normal_map_geo: the argument primary visibility, the NORMAL AOV and
     // picks get (`flagged`: a query with ST_RAY_MAPPED_NORMAL, which does not ask the switch) — the live copy's hit-test records, or null where nothing can be mapped.
-    bool normal_mapping = false, any_normal_map = false;
+    bool normal_mapping = false;
     int normal_map_geo(hipStream_t stream, bool flagged, const float4** geo);
     int scene_args(KArgs& a, bool heatmap) const;   // the scene half of KArgs (st_render.cpp): render() and the scene queries
     void light_args(KArgs& a) const;                // its lights, LUT and environment half: render()

@@ -6,18 +6,18 @@
 namespace st {
 
 // The handle table of the scene queries: per instance slot {StHandle lo, StHandle hi, first triangle slot, 0}. Instance slot ranges are
-// contiguous (instance_triangles), so `triangle slot - first` is the index into the mesh's own array. The fourth word belongs to deformation
+// contiguous (TriangleSlots::range_of), so `triangle slot - first` is the index into the mesh's own array. The fourth word belongs to deformation
 // motion (st_traverse.h deform_prev_point): the first triangle of the instance's previous region of the posed store + 1, for the instances this
 // tick re-skinned while the switch is on; 0 for every other one, and always while it is off.
 void Engine::fill_instance_table() {
-    const size_t slots = std::max<size_t>(instance_xforms.size() / 8u, 1u);
-    instance_table_.assign(4 * slots, 0u);
-    for (const auto& inst : instances) {
-        const auto r = instance_triangles.find(inst.id);
-        if (r == instance_triangles.end() || inst.xslot >= slots) continue;
+    const size_t rows = std::max<size_t>(instances.xforms.size() / 8u, 1u);
+    instance_table_.assign(4 * rows, 0u);
+    for (const auto& inst : instances.records) {
+        size_t b, e;
+        if (!slots.range_of(inst.id, &b, &e) || inst.xslot >= rows) continue;
         uint32_t* w = instance_table_.data() + 4 * (size_t)inst.xslot;
-        w[0] = (uint32_t)inst.id; w[1] = (uint32_t)(inst.id >> 32); w[2] = (uint32_t)r->second.first;
-        w[3] = deform.previous_word(inst.id, r->second.second - r->second.first);
+        w[0] = (uint32_t)inst.id; w[1] = (uint32_t)(inst.id >> 32); w[2] = (uint32_t)b;
+        w[3] = deform.previous_word(inst.id, e - b);
     }
 }
 

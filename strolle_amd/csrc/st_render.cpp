@@ -95,7 +95,8 @@ int Engine::allocate_camera(CameraState& c) {
 // reads these records of a copy that is not geo_current, and the join ends the write before any reader is handed the pointer (st_copies.h).
 int Engine::normal_map_geo(hipStream_t stream, bool flagged, const float4** geo) {
     *geo = nullptr;
-    if (!(normal_mapping || flagged) || !any_normal_map || tri_geo.empty()) return ST_OK;
+    const std::vector<float4>& tri_geo = slots.geo();
+    if (!(normal_mapping || flagged) || !materials.any_normal_map || tri_geo.empty()) return ST_OK;
     SceneSet& scene = copies.scene.current();
     if (!scene.geo_current) {
         const size_t bytes = tri_geo.size() * sizeof(float4);
@@ -113,13 +114,13 @@ int Engine::scene_args(KArgs& a, bool heatmap) const {
     a.tri_attr = static_cast<const float4*>(scene.tri_attr.ptr); a.instance_xforms = static_cast<const float4*>(scene.xforms.ptr);
     a.materials = static_cast<const GpuMaterial*>(scene.materials.ptr); a.material_base_packed = tuning.packed_base ? static_cast<const uint32_t*>(scene.base_packed.ptr) : nullptr;
     a.atlas = static_cast<const uchar4*>(d_atlas.ptr); a.byte_luts = static_cast<const float*>(d_byte_luts.ptr);
-    a.tri_slots = (uint32_t)(tri_geo.size() / 3u);
+    a.tri_slots = (uint32_t)slots.size();
     a.count_bytes = count_bytes ? 1u : 0u;
     a.exp_flags = exp_flags;
     if (int rc = tree.walk_args(scene.tree, a, heatmap)) return rc;   // which stream its rays walk, and with what stack
     a.walk_flags = walk_flags_dev;
     a.anyhit_contract = (count_bytes || !tuning.anyhit_fast) ? 1u : 0u;   // the reference's used_memory is the contract loop's
-    a.atlas_w = atlas_w; a.atlas_h = atlas_h;
+    a.atlas_w = images.width(); a.atlas_h = images.height();
     return ST_OK;
 }
 // The other half: the live copy of the lights, the blue noise, the atmosphere LUTs, the sun and the environment map — what a frame's shading reads.
@@ -127,7 +128,7 @@ void Engine::light_args(KArgs& a) const {
     a.lights = static_cast<const GpuLight*>(copies.lights.current().buf.ptr);
     a.blue_noise = static_cast<const uchar4*>(d_blue_noise.ptr);
     a.transmittance_lut = static_cast<const float4*>(d_transmittance.ptr); a.sky_lut = static_cast<const float4*>(d_sky.ptr);
-    a.n_lights_buf = (uint32_t)gpu_lights.size(); a.light_count = light_count;
+    a.n_lights_buf = (uint32_t)lights.table().size(); a.light_count = lights.count();
     a.sun_altitude = sun_altitude; a.sun_dir[0] = sun_dir_.x; a.sun_dir[1] = sun_dir_.y; a.sun_dir[2] = sun_dir_.z;
     environment_args(a);
 }
@@ -386,7 +387,7 @@ struct Frame {
         const StTuning& t = e.tuning; const bool fast = e.arithmetic == ST_ARITH_FAST;
         s.needs_di = mode == ST_MODE_IMAGE || mode == ST_MODE_DI_DIFFUSE || mode == ST_MODE_DI_SPECULAR;
         s.needs_gi = mode == ST_MODE_IMAGE || mode == ST_MODE_GI_DIFFUSE || mode == ST_MODE_GI_SPECULAR;
-        s.denoise = c.desc.denoise != 0u; s.any_objects = !e.instances.empty();
+        s.denoise = c.desc.denoise != 0u; s.any_objects = !e.instances.records.empty();
         s.tracing = c.frame % 6u < 4u; s.gi_source = (s.tracing && c.frame % 2u == 1u) ? 1u : 0u;
         s.whole_graph = e.pass_mask == ~0ull;  // a row window (multi-GPU band) changes which pixels a pass owns, not which passes follow it
         s.gi_runs = s.needs_gi && s.any_objects;

@@ -1,43 +1,24 @@
-// st_scene.cpp — host engine of libstrolle_hip.so: scene stores: materials (materials.rs, material.rs), lights (lights.rs, light.rs), instances -> world-space triangles (instances.rs, mesh_triangle.rs, triangle.rs). See st_engine.h.
+// st_scene.cpp — host engine of libstrolle_hip.so: the scene stores of st_stores.h — lights (lights.rs, light.rs), the image atlas (images.rs), materials (materials.rs, material.rs), meshes, instances and the triangle slots they are baked into (instances.rs, mesh_triangle.rs, triangle.rs) — and the tick's phases that connect them to the tree, the copies and the deformer. See st_engine.h.
 #include "st_engine.h"
 
 namespace st {
 
-// ---- materials (materials.rs:33-96, material.rs:29-50)
-float4 Engine::image_rect(uint64_t h) const {
-    if (!h) return make_float4(0, 0, 0, 0);
-    auto it = images.find(h);
-    if (it == images.end() || atlas_w == 0) return make_float4(0, 0, 0, 0);
-    const ImageRec& r = it->second;
-    return make_float4((float)r.x / (float)atlas_w, (float)r.y / (float)atlas_h, (float)r.w / (float)atlas_w, (float)r.h / (float)atlas_h);
+// ---- lights (lights.rs:49-172, light.rs:25-79)
+LightStore::LightStore() {
+    GpuLight sun{};
+    sun.d0 = make_float4(0, 0, 0, 25.0f); sun.d1 = make_float4(0, 0, 0, INFINITY); sun.d2 = make_float4(b2f(1u), 0, 0, 0);
+    buffer_.push_back(sun);
+    slot_[-1] = 0;
 }
 
-void Engine::rebuild_gpu_materials() {
-    gpu_materials.resize(materials.size()); material_base_packed.resize(materials.size());
-    any_normal_map = false;
-    for (size_t i = 0; i < materials.size(); i++) {
-        const StMaterial& m = materials[i]; GpuMaterial& g = gpu_materials[i];
-        g.base_color = make_float4(m.base_color[0], m.base_color[1], m.base_color[2], m.base_color[3]);
-        g.base_color_texture = image_rect(m.base_color_texture);
-        g.emissive = make_float4(m.emissive[0], m.emissive[1], m.emissive[2], m.emissive[3]);
-        g.emissive_texture = image_rect(m.emissive_texture);
-        g.roughness = pow2_(m.perceptual_roughness);
-        g.metallic = m.metallic; g.reflectance = m.reflectance; g.ior = m.ior;
-        g.metallic_roughness_texture = image_rect(m.metallic_roughness_texture);
-        g.normal_map_texture = image_rect(m.normal_map_texture);
-        any_normal_map = any_normal_map || !is_zero(g.normal_map_texture);
-        material_base_packed[i] = gbuffer_pack_base_color(g.base_color);  // st_math.h routines are bit-identical on host and device
-    }
-}
-
-void Engine::overwrite_light(uint32_t slot, int64_t key, GpuLight g) {
-    const GpuLight old = light_buffer[slot];
+void LightStore::overwrite(uint32_t slot, int64_t key, GpuLight g) {
+    const GpuLight old = buffer_[slot];
     g.prev_d0 = old.d0; g.prev_d1 = old.d1; g.prev_d2 = old.d2;
-    note(lights_updated, key);
-    light_buffer[slot] = g;
+    note(updated_, key);
+    buffer_[slot] = g;
 }
 
-void Engine::insert_light(uint64_t id, const StLight& l) {
+void LightStore::insert(uint64_t id, const StLight& l) {
     GpuLight g{};
     g.d0 = make_float4(l.position[0], l.position[1], l.position[2], l.radius);
     g.d1 = make_float4(l.color[0], l.color[1], l.color[2], l.range);
@@ -50,54 +31,202 @@ void Engine::insert_light(uint64_t id, const StLight& l) {
         g.d2 = make_float4(b2f(2u), e.x, e.y, l.angle);
     }
     const int64_t key = (int64_t)id;
-    auto it = light_slot.find(key);
-    if (it != light_slot.end()) { overwrite_light(it->second, key, g); return; }
-    if (next_light_id < light_buffer.size()) { light_buffer[next_light_id] = g; light_slot[key] = next_light_id; }
-    else { light_slot[key] = (uint32_t)light_buffer.size(); light_buffer.push_back(g); }
-    note(lights_created, key);
-    next_light_id += 1;
+    auto it = slot_.find(key);
+    if (it != slot_.end()) { overwrite(it->second, key, g); return; }
+    if (next_id_ < buffer_.size()) { buffer_[next_id_] = g; slot_[key] = next_id_; }
+    else { slot_[key] = (uint32_t)buffer_.size(); buffer_.push_back(g); }
+    note(created_, key);
+    next_id_ += 1;
 }
 
-void Engine::remove_light(uint64_t id) {
+void LightStore::remove(uint64_t id) {
     const int64_t key = (int64_t)id;
-    auto it = light_slot.find(key);
-    if (it == light_slot.end()) return;  // silent no-op like the reference
+    auto it = slot_.find(key);
+    if (it == slot_.end()) return;
     const uint32_t slot = it->second;
-    light_slot.erase(it);
-    light_buffer.erase(light_buffer.begin() + slot);
-    light_buffer.push_back(GpuLight{});
-    lights_created.erase(std::remove(lights_created.begin(), lights_created.end(), key), lights_created.end());
-    lights_updated.erase(std::remove(lights_updated.begin(), lights_updated.end(), key), lights_updated.end());
-    lights_remapped.erase(key);
-    if (std::find(lights_killed.begin(), lights_killed.end(), slot) == lights_killed.end()) lights_killed.push_back(slot);
-    next_light_id -= 1;
-    for (auto& kv : light_slot)
-        if (kv.second > slot) { if (!lights_remapped.count(kv.first)) lights_remapped[kv.first] = kv.second; kv.second -= 1; }
+    slot_.erase(it);
+    buffer_.erase(buffer_.begin() + slot);
+    buffer_.push_back(GpuLight{});
+    created_.erase(std::remove(created_.begin(), created_.end(), key), created_.end());
+    updated_.erase(std::remove(updated_.begin(), updated_.end(), key), updated_.end());
+    remapped_.erase(key);
+    if (std::find(killed_.begin(), killed_.end(), slot) == killed_.end()) killed_.push_back(slot);
+    next_id_ -= 1;
+    for (auto& kv : slot_)
+        if (kv.second > slot) { if (!remapped_.count(kv.first)) remapped_[kv.first] = kv.second; kv.second -= 1; }
 }
 
-void Engine::snapshot_lights() {  // lights.rs:128-154: what the device sees this frame, then commit prev_* for the next one
-    for (uint32_t s : lights_killed) light_buffer[s].d3.x = b2f(0xcafebabeu);
-    for (auto& kv : lights_remapped) light_buffer[kv.second].d3.x = b2f(light_slot[kv.first] + 1u);
-    gpu_lights = light_buffer; light_slot_uploaded = light_slot;
-    auto commit = [&](int64_t k) { GpuLight& l = light_buffer[light_slot[k]]; l.prev_d0 = l.d0; l.prev_d1 = l.d1; l.prev_d2 = l.d2; };
-    for (int64_t k : lights_created) commit(k);
-    for (int64_t k : lights_updated) commit(k);
-    for (uint32_t s : lights_killed) light_buffer[s].d3.x = b2f(0u);
-    for (auto& kv : lights_remapped) light_buffer[kv.second].d3.x = b2f(0u);
-    lights_created.clear(); lights_updated.clear(); lights_remapped.clear(); lights_killed.clear();
+void LightStore::snapshot() {
+    count_ = next_id_;
+    for (uint32_t s : killed_) buffer_[s].d3.x = b2f(0xcafebabeu);
+    for (auto& kv : remapped_) buffer_[kv.second].d3.x = b2f(slot_[kv.first] + 1u);
+    gpu_ = buffer_; slot_uploaded_ = slot_;
+    auto commit = [&](int64_t k) { GpuLight& l = buffer_[slot_[k]]; l.prev_d0 = l.d0; l.prev_d1 = l.d1; l.prev_d2 = l.d2; };
+    for (int64_t k : created_) commit(k);
+    for (int64_t k : updated_) commit(k);
+    for (uint32_t s : killed_) buffer_[s].d3.x = b2f(0u);
+    for (auto& kv : remapped_) buffer_[kv.second].d3.x = b2f(0u);
+    created_.clear(); updated_.clear(); remapped_.clear(); killed_.clear();
 }
 
-// ---- instances -> world-space triangles (instances.rs:69-139, mesh_triangle.rs:47-86, triangle.rs:16-37)
-void Engine::drop_instance_triangles(uint64_t id) {
-    auto it = instance_triangles.find(id);
-    if (it == instance_triangles.end()) return;
-    triangle_free.give(it->second.first, it->second.second);
-    for (size_t i = it->second.first; i < it->second.second; i++) { live_prims_ -= prim_alive[i]; prim_alive[i] = 0; }
-    tree.slots_changed(it->second.first, it->second.second);
-    instance_triangles.erase(it);
+// ---- images (images.rs)
+bool ImageAtlas::release(uint64_t id) {
+    auto it = rects_.find(id);
+    if (it == rects_.end()) return false;
+    shelves_.release(it->second.x, it->second.y, it->second.w);
+    rects_.erase(it);
+    device_.erase(id);
+    rects_dirty = true;
+    return true;
+}
+void ImageAtlas::remove(uint64_t id) { (void)release(id); }
+
+// finds the rectangle for image `id` and makes the host copy of the atlas tall enough
+int ImageAtlas::place(uint64_t id, uint32_t w, uint32_t h, Rect* out) {
+    if (w > kW) return fail(ST_ERR_ATLAS_FULL, "image wider than the atlas");
+    auto it = rects_.find(id);
+    Rect rec;
+    if (it != rects_.end() && it->second.w == w && it->second.h == h) rec = it->second;  // same size: rewritten in place (images.rs:61-63)
+    else {
+        (void)release(id);  // another size: the old rectangle is given back first (images.rs:64-66)
+        rec = {0, 0, w, h};
+        if (!shelves_.allocate(w, h, &rec.x, &rec.y)) return fail(ST_ERR_ATLAS_FULL, "no more space in the atlas");
+    }
+    const uint32_t need_h = rec.y + h;
+    if (w_ == 0) w_ = kW;
+    if (need_h > h_) {
+        // grow in 256-row steps; rects are stored in texels, so existing materials stay valid after a rebuild
+        h_ = (need_h + 255u) & ~255u;
+        texels_.resize((size_t)w_ * h_ * 4, 0);
+    }
+    rects_[id] = rec;
+    dirty = true; rects_dirty = true;
+    *out = rec;
+    return ST_OK;
 }
 
-void Engine::bake(const StMeshTriangle& t, const InstanceRec& inst, uint32_t material, size_t slot) {
+int ImageAtlas::insert_rgba8(uint64_t id, uint32_t w, uint32_t h, const uint8_t* rgba) {
+    Rect rec;
+    if (int rc = place(id, w, h, &rec)) return rc;
+    device_.erase(id);
+    for (uint32_t y = 0; y < h; y++) memcpy(texel(rec.x, rec.y + y), rgba + (size_t)y * w * 4, (size_t)w * 4);
+    return ST_OK;
+}
+int ImageAtlas::insert_device(uint64_t id, uint32_t w, uint32_t h, const void* pixels, size_t pitch, bool dynamic) {
+    Rect rec;
+    if (int rc = place(id, w, h, &rec)) return rc;
+    device_[id] = DeviceImage{pixels, pitch, dynamic, true};
+    return ST_OK;
+}
+
+float4 ImageAtlas::rect_uv(uint64_t id) const {
+    const Rect* r = id ? rect_texels(id) : nullptr;
+    if (!r || w_ == 0) return make_float4(0, 0, 0, 0);
+    return make_float4((float)r->x / (float)w_, (float)r->y / (float)h_, (float)r->w / (float)w_, (float)r->h / (float)h_);
+}
+
+// ---- materials (materials.rs:33-96, material.rs:29-50)
+void MaterialStore::insert(uint64_t id, const StMaterial& m) {
+    auto it = slot_.find(id);
+    if (it != slot_.end()) materials_[it->second] = m;
+    else {
+        size_t b, end_;
+        uint32_t slot;
+        if (free_.take(1, &b, &end_)) slot = (uint32_t)b;  // materials.rs:48-50 (the slot keeps its previous contents)
+        else { materials_.push_back(m); slot = (uint32_t)materials_.size() - 1u; }
+        slot_[id] = slot;
+    }
+    dirty = true;
+}
+void MaterialStore::remove(uint64_t id) {
+    auto it = slot_.find(id);
+    if (it == slot_.end()) return;
+    free_.give(it->second, it->second);  // `give(id..id)`: an empty range, as in materials.rs:74
+    slot_.erase(it);
+    dirty = true;
+}
+void MaterialStore::rebuild(const ImageAtlas& images) {
+    gpu_.resize(materials_.size()); base_packed_.resize(materials_.size());
+    any_normal_map = false;
+    for (size_t i = 0; i < materials_.size(); i++) {
+        const StMaterial& m = materials_[i]; GpuMaterial& g = gpu_[i];
+        g.base_color = make_float4(m.base_color[0], m.base_color[1], m.base_color[2], m.base_color[3]);
+        g.base_color_texture = images.rect_uv(m.base_color_texture);
+        g.emissive = make_float4(m.emissive[0], m.emissive[1], m.emissive[2], m.emissive[3]);
+        g.emissive_texture = images.rect_uv(m.emissive_texture);
+        g.roughness = pow2_(m.perceptual_roughness);
+        g.metallic = m.metallic; g.reflectance = m.reflectance; g.ior = m.ior;
+        g.metallic_roughness_texture = images.rect_uv(m.metallic_roughness_texture);
+        g.normal_map_texture = images.rect_uv(m.normal_map_texture);
+        any_normal_map = any_normal_map || !is_zero(g.normal_map_texture);
+        base_packed_[i] = gbuffer_pack_base_color(g.base_color);  // st_math.h routines are bit-identical on host and device
+    }
+}
+
+// ---- meshes
+void MeshStore::insert(uint64_t id, const StMeshTriangle* t, size_t count) { meshes_[id].assign(t, t + count); version_[id] = next_version_++; }
+void MeshStore::remove(uint64_t id) { meshes_.erase(id); version_.erase(id); }
+std::pair<size_t, size_t> MeshStore::device_range(uint64_t id, uint64_t version, const std::vector<StMeshTriangle>& tris) {
+    auto dm = device_.find(id);
+    if (dm == device_.end() || dm->second.version != version) {
+        const DeviceRec rec{store_host_.size() / kTriangleFloats, tris.size(), version};
+        store_host_.resize(kTriangleFloats * (rec.first + rec.count));
+        for (size_t i = 0; i < rec.count; i++) pack_triangle(tris[i], &store_host_[kTriangleFloats * (rec.first + i)]);
+        dm = device_.insert_or_assign(id, rec).first;
+    }
+    return {dm->second.first, dm->second.count};
+}
+int MeshStore::upload(hipStream_t up, StagingRing& ring, bool* pageable) {
+    if (store_uploaded_ == store_host_.size()) return ST_OK;
+    const size_t bytes = store_host_.size() * sizeof(float);
+    if (bytes > d_store_.capacity) {   // a new allocation: everything again (hipFree waits for the kernels that read the old one)
+        if (int rc = d_store_.upload(store_host_.data(), bytes, up, ring, pageable)) return rc;
+    } else if (int rc = d_store_.upload_range(store_host_.data(), store_uploaded_ * sizeof(float), (store_host_.size() - store_uploaded_) * sizeof(float), up, ring, pageable)) return rc;
+    store_uploaded_ = store_host_.size();
+    return ST_OK;
+}
+
+// ---- instances (instances.rs:69-99)
+void InstanceStore::insert(uint64_t id, uint64_t mesh, uint64_t material, const Affine& x) {
+    dirty = true;
+    if (InstanceRec* r = find(id)) { r->prev_xform = r->xform; r->mesh = mesh; r->material = material; r->xform = x; r->xform_inv = affine_inverse(x); r->dirty = true; return; }
+    uint32_t xslot;
+    if (!xslot_free_.empty()) { xslot = xslot_free_.back(); xslot_free_.pop_back(); }
+    else { xslot = (uint32_t)(xforms.size() / 8u); xforms.resize(xforms.size() + 8u, make_float4(0, 0, 0, 0)); }
+    records.push_back({id, mesh, material, x, affine_inverse(x), x, true, xslot});
+}
+void InstanceStore::remove(uint64_t id) {
+    for (size_t i = 0; i < records.size(); i++)
+        if (records[i].id == id) { xslot_free_.push_back(records[i].xslot); records.erase(records.begin() + i); dirty = true; removed = true; break; }
+}
+void InstanceStore::fill_xforms() {
+    for (const auto& inst : records) {
+        float4* x = xforms.data() + 8u * inst.xslot;
+        const Affine* src[2] = {&inst.xform_inv, &inst.prev_xform};
+        for (int k = 0; k < 2; k++) { x[4 * k] = f4(src[k]->x, 0.0f); x[4 * k + 1] = f4(src[k]->y, 0.0f); x[4 * k + 2] = f4(src[k]->z, 0.0f); x[4 * k + 3] = f4(src[k]->t, 0.0f); }
+    }
+}
+
+// ---- triangle slots (triangles.rs)
+void TriangleSlots::reserve(size_t want) { triangles_.reserve(want); prims_.reserve(want); alive_.reserve(want); geo_.reserve(3 * want); attr_.reserve(4 * want); bounds_.reserve(2 * want); }
+void TriangleSlots::grow_to(size_t end) { triangles_.resize(end); prims_.resize(end); alive_.resize(end, 0); geo_.resize(3 * end); attr_.resize(4 * end); bounds_.resize(2 * end); }
+void TriangleSlots::take(uint64_t instance, size_t count, size_t* b, size_t* e, bool* appended) {
+    *appended = false;
+    if (range_of(instance, b, e)) return;
+    if (!free_.take(count, b, e)) { *b = size(); *e = *b + count; grow_to(*e); *appended = true; }
+    live_ += count;   // (the bake that follows sets alive() for the whole range)
+    ranges_[instance] = {*b, *e};
+}
+bool TriangleSlots::drop(uint64_t instance, size_t* b, size_t* e) {
+    auto it = ranges_.find(instance);
+    if (it == ranges_.end()) return false;
+    *b = it->second.first; *e = it->second.second;
+    free_.give(*b, *e);
+    for (size_t i = *b; i < *e; i++) { live_ -= alive_[i]; alive_[i] = 0; }
+    ranges_.erase(it);
+    return true;
+}
+void TriangleSlots::write(size_t slot, const StMeshTriangle& t, const InstanceRec& inst, uint32_t material) {
     // normals use transpose(inverse(xform)) (Mat4::transform_vector3 order); tangents follow the forward matrix
     const Affine& inv = inst.xform_inv;
     const V3 r0 = v3(inv.x.x, inv.y.x, inv.z.x), r1 = v3(inv.x.y, inv.y.y, inv.z.y), r2 = v3(inv.x.z, inv.y.z, inv.z.z);
@@ -118,19 +247,41 @@ void Engine::bake(const StMeshTriangle& t, const InstanceRec& inst, uint32_t mat
     h.d0 = f4(p[0], t.uvs[0][0]); h.d1 = f4(n[0], t.uvs[0][1]); h.d2 = tg[0];
     h.d3 = f4(p[1], t.uvs[1][0]); h.d4 = f4(n[1], t.uvs[1][1]); h.d5 = tg[1];
     h.d6 = f4(p[2], t.uvs[2][0]); h.d7 = f4(n[2], t.uvs[2][1]); h.d8 = tg[2];
-    triangles[slot] = h;
+    triangles_[slot] = h;
     BuildPrim bp;
     bp.triangle_id = (uint32_t)slot; bp.material_id = material;
     bp.center = (((v3s(0.0f) + p[0]) + p[1]) + p[2]) / 3.0f;
     bp.bounds = Aabb(); bp.bounds.grow(p[0]); bp.bounds.grow(p[1]); bp.bounds.grow(p[2]);
-    prims[slot] = bp; prim_alive[slot] = 1;
-    tri_geo[3 * slot] = f4(p[0], 0.0f); tri_geo[3 * slot + 1] = f4(p[1] - p[0], 0.0f); tri_geo[3 * slot + 2] = f4(p[2] - p[0], 0.0f);
-    tri_bounds[2 * slot] = f4(bp.bounds.lo, 0.0f); tri_bounds[2 * slot + 1] = f4(bp.bounds.hi, 0.0f);
-    tri_attr[4 * slot] = f4(n[0], t.uvs[0][0]); tri_attr[4 * slot + 1] = f4(n[1], t.uvs[0][1]); tri_attr[4 * slot + 2] = f4(n[2], t.uvs[1][0]);
-    tri_attr[4 * slot + 3] = make_float4(t.uvs[1][1], t.uvs[2][0], t.uvs[2][1], b2f(inst.xslot));
+    prims_[slot] = bp; alive_[slot] = 1;
+    geo_[3 * slot] = f4(p[0], 0.0f); geo_[3 * slot + 1] = f4(p[1] - p[0], 0.0f); geo_[3 * slot + 2] = f4(p[2] - p[0], 0.0f);
+    bounds_[2 * slot] = f4(bp.bounds.lo, 0.0f); bounds_[2 * slot + 1] = f4(bp.bounds.hi, 0.0f);
+    attr_[4 * slot] = f4(n[0], t.uvs[0][0]); attr_[4 * slot + 1] = f4(n[1], t.uvs[0][1]); attr_[4 * slot + 2] = f4(n[2], t.uvs[1][0]);
+    attr_[4 * slot + 3] = make_float4(t.uvs[1][1], t.uvs[2][0], t.uvs[2][1], b2f(inst.xslot));
 }
 
-// Baking (instances.rs:100-139) writes disjoint slots and reads nothing it writes, so once every range is assigned — the arrays
+// ---- the engine's entry points over more than one owner
+void Engine::insert_mesh(uint64_t id, const StMeshTriangle* t, size_t count) {
+    deform.drop_skin(id);   // skinned meshes: a new mesh drops the skin and the poses of its instances
+    deform.drop_morph(id);  // morph targets: likewise the targets and the weights
+    meshes.insert(id, t, count);
+}
+void Engine::remove_mesh(uint64_t id) { deform.drop_skin(id); deform.drop_morph(id); meshes.remove(id); }
+void Engine::insert_instance(uint64_t id, uint64_t mesh, uint64_t material, const Affine& x) {
+    if (const InstanceRec* r = instances.find(id)) if (r->mesh != mesh) deform.drop_instance(id, false);
+    instances.insert(id, mesh, material, x);
+}
+void Engine::remove_instance(uint64_t id) {
+    instances.remove(id);
+    drop_instance_triangles(id);
+    deform.drop_instance(id, false);
+}
+void Engine::drop_instance_triangles(uint64_t id) {
+    size_t b, e;
+    if (slots.drop(id, &b, &e)) tree.slots_changed(b, e);
+}
+
+// ---- instances -> world-space triangles (instances.rs:100-139)
+// Baking writes disjoint slots and reads nothing it writes, so once every range is assigned — the arrays
 // do not move any more — large refreshes are spread over the BVH builder's worker pool in chunks.
 void Engine::bake_jobs_on_host(const std::vector<BakeJob>& jobs, size_t total) {
     const auto tb0 = TickClock::now();
@@ -139,13 +290,13 @@ void Engine::bake_jobs_on_host(const std::vector<BakeJob>& jobs, size_t total) {
     if (threads > 16u) threads = 16u;
     if (total < kParallelFrom || threads < 2u) {
         for (const BakeJob& j : jobs)
-            for (size_t i = 0; i < j.count; i++) bake((*j.mesh)[i], *j.inst, j.material, j.first + i);
+            for (size_t i = 0; i < j.count; i++) slots.write(j.first + i, (*j.mesh)[i], *j.inst, j.material);
     } else {
         TaskPool pool(threads);
         for (const BakeJob& j : jobs)
             for (size_t at = 0; at < j.count; at += kChunk) {
                 const size_t end = std::min(j.count, at + kChunk);
-                pool.push([this, j, at, end] { for (size_t i = at; i < end; i++) bake((*j.mesh)[i], *j.inst, j.material, j.first + i); });
+                pool.push([this, j, at, end] { for (size_t i = at; i < end; i++) slots.write(j.first + i, (*j.mesh)[i], *j.inst, j.material); });
             }
         pool.finish();
     }
@@ -153,52 +304,50 @@ void Engine::bake_jobs_on_host(const std::vector<BakeJob>& jobs, size_t total) {
 }
 
 // Instances the device has moved (StTuning::device_bake) are baked on the host only when the host arrays are needed again: a rebuild
-// (its primitives), a host refit or a debug read of the stream (tri_bounds), a full upload. Both device copies then receive those slots from
+// (its primitives), a host refit or a debug read of the stream (the bounds), a full upload. Both device copies then receive those slots from
 // the host like any other baked range, and their lists of pending device moves are void.
 void Engine::bake_stale_on_host() {
     // posed instances bake from their posed regions (st_deform.cpp); a failed read-back is reported by the next st_tick or debug read
     if (int rc = deform.read_back()) deferred_status = rc;
     std::vector<BakeJob> jobs; size_t total = 0;
-    for (auto& inst : instances) {
+    for (auto& inst : instances.records) {
         if (!inst.host_stale) continue;
         inst.host_stale = false;
-        auto mesh = meshes.find(inst.mesh);
-        auto have = instance_triangles.find(inst.id);
-        if (mesh == meshes.end() || have == instance_triangles.end() || have->second.second - have->second.first != mesh->second.size()) continue;  // the next refresh re-bakes it as dirty
-        jobs.push_back({deform.bake_source(inst.id, mesh->second), &inst, inst.baked_material, have->second.first, mesh->second.size()});
-        total += mesh->second.size();
-        for (SceneSet& t : copies.scene.copy) { t.dirty_lo = std::min(t.dirty_lo, have->second.first); t.dirty_hi = std::max(t.dirty_hi, have->second.second); }
+        const std::vector<StMeshTriangle>* mesh = meshes.find(inst.mesh);
+        size_t b, e;
+        if (!mesh || !slots.range_of(inst.id, &b, &e) || e - b != mesh->size()) continue;  // the next refresh re-bakes it as dirty
+        jobs.push_back({deform.bake_source(inst.id, *mesh), &inst, inst.baked_material, b, mesh->size()});
+        total += mesh->size();
+        copies.owe_slots(b, e);
     }
-    for (SceneSet& t : copies.scene.copy) t.pending_moves.clear();
+    copies.void_pending_moves();
     if (!jobs.empty()) bake_jobs_on_host(jobs, total);
 }
 
 bool Engine::refresh_instances() {
     moved_on_device = false;
-    if (!instances_dirty) return false;
-    instances_dirty = false;
+    if (!instances.dirty) return false;
+    instances.dirty = false;
     // Device bake: when every dirty instance only MOVED — same mesh (and version of it), same material, its slots already assigned —
     // under ST_BVH_REFIT_DEVICE with the tree's topology on record, the host bakes nothing: the device copies do (Engine::bake_on_device).
-    const bool removed = instance_removed; instance_removed = false;
+    const bool removed = instances.removed; instances.removed = false;
     const bool tree_follows = tree.moves_stay_on_device();
     if (tuning.device_bake && tree_follows && !materials_changed_this_tick && !removed) {
         bool only_moves = true; size_t moved = 0;
-        for (const auto& inst : instances) {
+        for (const auto& inst : instances.records) {
             if (!inst.dirty) continue;
             moved++;
-            auto mv = mesh_version.find(inst.mesh);
-            auto mat = material_slot.find(inst.material);
-            auto have = instance_triangles.find(inst.id);
-            auto mesh = meshes.find(inst.mesh);
-            if (!inst.baked || mv == mesh_version.end() || mat == material_slot.end() || have == instance_triangles.end() || mesh == meshes.end() ||
-                inst.baked_mesh != inst.mesh || inst.baked_mesh_version != mv->second || inst.baked_material != mat->second ||
-                have->second.second - have->second.first != mesh->second.size()) { only_moves = false; break; }
+            const std::vector<StMeshTriangle>* mesh = meshes.find(inst.mesh);
+            uint32_t mat; size_t b, e;
+            if (!inst.baked || !mesh || !materials.slot_of(inst.material, &mat) || !slots.range_of(inst.id, &b, &e) ||
+                inst.baked_mesh != inst.mesh || inst.baked_mesh_version != meshes.version_of(inst.mesh) || inst.baked_material != mat ||
+                e - b != mesh->size()) { only_moves = false; break; }
         }
         if (only_moves && moved) {
-            for (auto& inst : instances) {
+            for (auto& inst : instances.records) {
                 if (!inst.dirty) continue;
                 inst.dirty = false; inst.host_stale = true;
-                for (SceneSet& t : copies.scene.copy) if (std::find(t.pending_moves.begin(), t.pending_moves.end(), inst.id) == t.pending_moves.end()) t.pending_moves.push_back(inst.id);
+                copies.instance_moved(inst.id);
             }
             moved_on_device = true;
             return true;
@@ -207,52 +356,40 @@ bool Engine::refresh_instances() {
     // the host bakes this refresh: posed instances from their posed regions, read back in one batch (st_deform.cpp)
     if (int rc = deform.read_back()) deferred_status = rc;
     // instances the device moved earlier and that are not dirty now must catch up first (a rebuild reads every primitive)
-    if (any_host_stale()) {
+    if (instances.any_host_stale()) {
         // re-baked below anyway — but only those whose bake job WILL be queued: an instance whose mesh or material is missing is retried at a
         // later tick, and until then its host arrays must still count as stale (debug reads catch up through bake_stale_on_host)
-        for (auto& inst : instances)
-            if (inst.host_stale && inst.dirty && meshes.count(inst.mesh) && material_slot.count(inst.material)) inst.host_stale = false;
+        for (auto& inst : instances.records)
+            if (inst.host_stale && inst.dirty && meshes.find(inst.mesh) && materials.has(inst.material)) inst.host_stale = false;
         bake_stale_on_host();
     }
     std::vector<BakeJob> jobs; size_t total = 0;
     {   // one reallocation at most for everything this refresh appends (a scene load appends every instance)
-        size_t fresh = 0;
-        for (const auto& inst : instances) {
-            if (!inst.dirty || instance_triangles.count(inst.id)) continue;
-            auto mesh = meshes.find(inst.mesh);
-            if (mesh != meshes.end()) fresh += mesh->second.size();
+        size_t fresh = 0, b, e;
+        for (const auto& inst : instances.records) {
+            if (!inst.dirty || slots.range_of(inst.id, &b, &e)) continue;
+            if (const std::vector<StMeshTriangle>* mesh = meshes.find(inst.mesh)) fresh += mesh->size();
         }
-        if (fresh && triangles.size() + fresh > triangles.capacity()) {
-            // (geometric: reserve(size + fresh) at EVERY spawn reallocated and copied all five arrays — 60 MB at 208 k triangles, 7 ms of a spawn tick
-            // that otherwise costs 0.2 ms, profiles/r06_spawn_cost.txt — although the free list usually serves the new instance)
-            const size_t want = std::max(triangles.size() + fresh, triangles.capacity() + triangles.capacity() / 2);
-            triangles.reserve(want); prims.reserve(want); prim_alive.reserve(want); tri_geo.reserve(3 * want); tri_attr.reserve(4 * want); tri_bounds.reserve(2 * want);
-        }
+        // (geometric: reserve(size + fresh) at EVERY spawn reallocated and copied all the arrays — 60 MB at 208 k triangles, 7 ms of a spawn tick
+        // that otherwise costs 0.2 ms, profiles/r06_spawn_cost.txt — although the free list usually serves the new instance)
+        if (fresh && slots.size() + fresh > slots.capacity()) slots.reserve(std::max(slots.size() + fresh, slots.capacity() + slots.capacity() / 2));
     }
-    for (auto& inst : instances) {
+    for (auto& inst : instances.records) {
         if (!inst.dirty) continue;
         inst.dirty = false;
-        auto mesh = meshes.find(inst.mesh);
-        auto mat = material_slot.find(inst.material);
-        if (mesh == meshes.end() || mat == material_slot.end()) { inst.dirty = true; instances_dirty = true; continue; }  // retry next tick
-        const size_t count = mesh->second.size();
-        auto have = instance_triangles.find(inst.id);
-        if (have != instance_triangles.end() && have->second.second - have->second.first != count) { drop_instance_triangles(inst.id); have = instance_triangles.end(); }
-        size_t b, e;
-        if (have != instance_triangles.end()) { b = have->second.first; e = have->second.second; }
-        else if (!triangle_free.take(count, &b, &e)) {
-            b = triangles.size(); e = b + count;
-            triangles.resize(e); prims.resize(e); prim_alive.resize(e, 0); tri_geo.resize(3 * e); tri_attr.resize(4 * e); tri_bounds.resize(2 * e);
-            for (SceneSet& t : copies.scene.copy) t.tri_full = true;
-        }
-        jobs.push_back({deform.bake_source(inst.id, mesh->second), &inst, mat->second, b, count});
+        const std::vector<StMeshTriangle>* mesh = meshes.find(inst.mesh);
+        uint32_t mat;
+        if (!mesh || !materials.slot_of(inst.material, &mat)) { inst.dirty = true; instances.dirty = true; continue; }  // retry next tick
+        const size_t count = mesh->size();
+        size_t b, e; bool appended;
+        if (slots.range_of(inst.id, &b, &e) && e - b != count) drop_instance_triangles(inst.id);
+        slots.take(inst.id, count, &b, &e, &appended);
+        if (appended) copies.owe_whole_arrays();
+        jobs.push_back({deform.bake_source(inst.id, *mesh), &inst, mat, b, count});
         total += count;
-        for (SceneSet& t : copies.scene.copy) { t.dirty_lo = std::min(t.dirty_lo, b); t.dirty_hi = std::max(t.dirty_hi, e); }  // slots each device copy still has to receive
+        copies.owe_slots(b, e);
         tree.slots_changed(b, e);
-        if (have == instance_triangles.end()) live_prims_ += count;   // (the bake below sets prim_alive for the whole range)
-        instance_triangles[inst.id] = {b, e};
-        auto mv = mesh_version.find(inst.mesh);
-        inst.baked = true; inst.baked_mesh = inst.mesh; inst.baked_mesh_version = mv == mesh_version.end() ? 0 : mv->second; inst.baked_material = mat->second; inst.host_stale = false;
+        inst.baked = true; inst.baked_mesh = inst.mesh; inst.baked_mesh_version = meshes.version_of(inst.mesh); inst.baked_material = mat; inst.host_stale = false;
     }
     bake_jobs_on_host(jobs, total);
     return true;
@@ -264,51 +401,39 @@ bool Engine::refresh_instances() {
 int Engine::bake_on_device(SceneSet& t, hipStream_t up, bool* pageable) {
     if (t.pending_moves.empty()) return ST_OK;
     std::unordered_map<uint64_t, const InstanceRec*> by_id;
-    for (const auto& inst : instances) by_id[inst.id] = &inst;
+    for (const auto& inst : instances.records) by_id[inst.id] = &inst;
     struct Job { float4 x, y, z, t, r0, r1, r2; uint32_t mesh_first, count, slot_first, xslot; };
     static_assert(sizeof(Job) == 128, "k_bvh.hip BakeJobDevice");
     std::vector<Job> jobs; std::vector<uint32_t> starts{0u};
-    bool store_grew = false, reads_posed = false;
+    bool reads_posed = false;
     for (uint64_t id : t.pending_moves) {
         auto it = by_id.find(id);
         if (it == by_id.end()) continue;   // removed since: that tick rebuilt the tree and voided the lists
         const InstanceRec& inst = *it->second;
-        auto have = instance_triangles.find(id);
-        auto mesh = meshes.find(inst.mesh);
-        if (have == instance_triangles.end() || mesh == meshes.end()) continue;
+        const std::vector<StMeshTriangle>* mesh = meshes.find(inst.mesh);
+        size_t b, e;
+        if (!slots.range_of(id, &b, &e) || !mesh) continue;
         // a posed instance (skinned mesh) reads its region of the posed store, which this tick's skin launch brought up to date (st_deform.cpp)
         size_t posed_first = 0;
-        const bool posed = deform.bake_region(id, have->second.second - have->second.first, &posed_first);
-        auto dm = device_meshes.find(inst.mesh);
-        if (!posed && (dm == device_meshes.end() || dm->second.version != inst.baked_mesh_version)) {
-            DeviceMeshRec rec{mesh_store_host.size() / kTriangleFloats, mesh->second.size(), inst.baked_mesh_version};
-            mesh_store_host.resize(kTriangleFloats * (rec.first + rec.count));
-            for (size_t i = 0; i < rec.count; i++) pack_triangle(mesh->second[i], &mesh_store_host[kTriangleFloats * (rec.first + i)]);
-            device_meshes[inst.mesh] = rec; dm = device_meshes.find(inst.mesh); store_grew = true;
-        }
+        const bool posed = deform.bake_region(id, e - b, &posed_first);
+        const std::pair<size_t, size_t> range = posed ? std::make_pair(posed_first, e - b) : meshes.device_range(inst.mesh, inst.baked_mesh_version, *mesh);
         const Affine& inv = inst.xform_inv;
         Job j;
         j.x = f4(inst.xform.x, 0.0f); j.y = f4(inst.xform.y, 0.0f); j.z = f4(inst.xform.z, 0.0f); j.t = f4(inst.xform.t, 0.0f);
         j.r0 = make_float4(inv.x.x, inv.y.x, inv.z.x, 0.0f); j.r1 = make_float4(inv.x.y, inv.y.y, inv.z.y, 0.0f); j.r2 = make_float4(inv.x.z, inv.y.z, inv.z.z, 0.0f);
-        j.mesh_first = posed ? (uint32_t)posed_first : (uint32_t)dm->second.first; j.count = posed ? (uint32_t)(have->second.second - have->second.first) : (uint32_t)dm->second.count; j.slot_first = (uint32_t)have->second.first; j.xslot = inst.xslot;
+        j.mesh_first = (uint32_t)range.first; j.count = (uint32_t)range.second; j.slot_first = (uint32_t)b; j.xslot = inst.xslot;
         if (posed) { j.x.w = b2f(1u); reads_posed = true; }
         jobs.push_back(j); starts.push_back(starts.back() + j.count);
     }
     t.pending_moves.clear();
     if (jobs.empty()) return ST_OK;
     int rc;
-    if (store_grew) {
-        const size_t bytes = mesh_store_host.size() * sizeof(float);
-        if (bytes > d_mesh_store.capacity) {   // a new allocation: everything again (hipFree waits for the kernels that read the old one)
-            if ((rc = d_mesh_store.upload(mesh_store_host.data(), bytes, up, staging, pageable))) return rc;
-        } else if ((rc = d_mesh_store.upload_range(mesh_store_host.data(), mesh_store_uploaded * sizeof(float), (mesh_store_host.size() - mesh_store_uploaded) * sizeof(float), up, staging, pageable))) return rc;
-        mesh_store_uploaded = mesh_store_host.size();
-    }
+    if ((rc = meshes.upload(up, staging, pageable))) return rc;
     if ((rc = t.bake_jobs.upload(jobs.data(), jobs.size() * sizeof(Job), up, staging, pageable))) return rc;
     if ((rc = t.bake_starts.upload(starts.data(), starts.size() * sizeof(uint32_t), up, staging, pageable))) return rc;
     if (reads_posed) if ((rc = deform.wait_skinned(up))) return rc;   // the skin launch (skin stream) wrote the posed regions
     // the EXACT build's kernel, whatever arithmetic the frames use: the baked arrays are the host's bits
-    launchers_exact().launch_bvh_bake(t.bake_jobs.ptr, static_cast<const uint32_t*>(t.bake_starts.ptr), (uint32_t)jobs.size(), starts.back(), static_cast<const float*>(d_mesh_store.ptr),
+    launchers_exact().launch_bvh_bake(t.bake_jobs.ptr, static_cast<const uint32_t*>(t.bake_starts.ptr), (uint32_t)jobs.size(), starts.back(), meshes.device_store(),
                                       deform.posed_store(), static_cast<float4*>(t.tri_geo.ptr), static_cast<float4*>(t.tri_bounds.ptr), static_cast<float4*>(t.tri_attr.ptr),
                                       t.tree.patch_stream(), t.tree.patch_index(), up);
     // the next skin launch overwrites the regions after this bake — and after an earlier one still pending on another stream:

@@ -50,7 +50,7 @@ int Engine::set_shafts(CameraState& c, const StLightShaftsDesc* desc) {
 }
 
 // Both launches' arguments. view.sun: the direction ST_SHAFTS_FOLLOW_SUN takes. The handles become slots of
-// the light table of the last st_tick (light_slot_uploaded); a handle without a light there is skipped. Bytes: the march reads a pixel's
+// the light table of the last st_tick (LightStore::uploaded_slot); a handle without a light there is skipped. Bytes: the march reads a pixel's
 // depth and writes 16 B a cell (its time is the walks'); the apply launch reads 16 B of colour, the depth and a cell's 16 B that
 // divisor^2 pixels share, and writes the format's bytes.
 void Engine::shafts_steps(const StLightShaftsDesc& d, const ShaftsPlan& plan, const NodeView& view, const NodeSource& src, float4* cells, const NodeTarget& target, bool count, ShaftsSteps& out) const {
@@ -69,9 +69,8 @@ void Engine::shafts_steps(const StLightShaftsDesc& d, const ShaftsPlan& plan, co
     a.density = d.density; a.max_distance = d.max_distance; a.intensity = d.intensity;
     for (int i = 0; i < 3; i++) { a.scatter[i] = d.scatter[i]; a.sun_color[i] = d.sun_color[i]; }
     for (uint32_t i = 0; i < d.light_count; i++) {
-        const auto it = light_slot_uploaded.find((int64_t)d.lights[i]);
-        if (it ==light_slot_uploaded.end() || it->second >= gpu_lights.size()) continue;
-        a.lights[a.light_count++] = it->second;
+        uint32_t slot;
+        if (lights.uploaded_slot(d.lights[i], &slot)) a.lights[a.light_count++] = slot;
     }
     const double n = (double)src.w * src.h, cells_n = (double)plan.cells_w * plan.cells_h;
     out.step[0] = {KS_SHAFTS_MARCH, n * 4.0 + cells_n * 16.0};

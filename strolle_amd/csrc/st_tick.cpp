@@ -7,13 +7,14 @@ namespace st {
 
 // Whether copy `t`'s device arrays hold the host's triangle-slot arrays as they are now (otherwise they are sent whole, into a larger allocation).
 bool Engine::tri_fits(const SceneSet& t, unsigned arrays) const {
-    if ((arrays & TRI_GEO) && (t.tri_geo.capacity < tri_geo.size() * sizeof(float4) || t.tri_bounds.capacity < tri_bounds.size() * sizeof(float4))) return false;
-    return !(arrays & TRI_ATTR) || t.tri_attr.capacity >= tri_attr.size() * sizeof(float4);
+    if ((arrays & TRI_GEO) && (t.tri_geo.capacity < slots.geo().size() * sizeof(float4) || t.tri_bounds.capacity < slots.bounds().size() * sizeof(float4))) return false;
+    return !(arrays & TRI_ATTR) || t.tri_attr.capacity >= slots.attr().size() * sizeof(float4);
 }
 // The triangle slots copy `t` lacks: all when `whole` or an array outgrew its allocation (attribute records then follow the hit-test records), else
 // [dirty_lo, dirty_hi). Attribute records go BEFORE a device bake of the copy: an instance the host baked a tick ago and the device moves now ends with the device's.
 int Engine::upload_tri_slots(SceneSet& t, unsigned arrays, bool whole, hipStream_t up, bool* pageable) {
     int rc;
+    const std::vector<float4>& tri_geo = slots.geo(), & tri_attr = slots.attr(), & tri_bounds = slots.bounds();   // (3, 4 and 2 float4 per slot)
     const size_t lo = t.dirty_lo, n = t.dirty_lo < t.dirty_hi ? t.dirty_hi - t.dirty_lo : 0;
     if (arrays & TRI_GEO) {
         whole = whole || !tri_fits(t, TRI_GEO);
@@ -52,7 +53,7 @@ int Engine::tick(hipStream_t stream) {
         int rc;
         if ((rc = upload_scene(plan, io)) || (rc = upload_images(io)) || (rc = upload_lights(io)) || (rc = upload_environment(io)) || (rc = upload_luts(io)) || (rc = copies.end_uploads(io))) return rc;
     }
-    atlas_dirty = false;
+    images.dirty = false;
     for (auto& kv : cameras) kv.second->frame = frame;  // CameraController::flush
     frame += 1;
     if (int rc = take_deferred_status()) return rc;   // a read-back of posed triangles failed: the host baked their bind pose
@@ -60,23 +61,16 @@ int Engine::tick(hipStream_t stream) {
 }
 // Materials and instances (baked) on the host, the instances' transform table; then the tree's plan: what upload_scene does with the tree (st_bvh_refresh.h).
 TreePlan Engine::refresh_scene() {
-    materials_changed_this_tick = materials_dirty || atlas_dirty;   // a Blend flag may have changed: the tree's topology signature has to be looked at
-    if (materials_changed_this_tick) { materials_dirty = false; rebuild_gpu_materials(); }
+    materials_changed_this_tick = materials.dirty || images.rects_dirty || images.dirty;   // a Blend flag may have changed: the tree's topology signature has to be looked at
+    if (materials_changed_this_tick) { materials.dirty = images.rects_dirty = false; materials.rebuild(images); }
     const auto t0 = TickClock::now();
     const bool instances_changed = refresh_instances();
-    if (instances_changed) {
-        for (const auto& inst : instances) {
-            float4* x = instance_xforms.data() + 8u * inst.xslot;
-            const Affine* src[2] = {&inst.xform_inv, &inst.prev_xform};
-            for (int k = 0; k < 2; k++) { x[4 * k] = f4(src[k]->x, 0.0f); x[4 * k + 1] = f4(src[k]->y, 0.0f); x[4 * k + 2] = f4(src[k]->z, 0.0f); x[4 * k + 3] = f4(src[k]->t, 0.0f); }
-        }
-    }
+    if (instances_changed) instances.fill_xforms();
     // slots, liveness, materials or Blend flags may have changed (a Blend flag under any slot)
     if ((instances_changed && !moved_on_device) || materials_changed_this_tick) tree.slots_changed(materials_changed_this_tick);
     return tree.plan(instances_changed, moved_on_device, materials_changed_this_tick, t0);
 }
 void Engine::refresh_sun_and_lights() {
-    light_count = next_light_id;
     float sa, ca, sz, cz;   // World::sun_dir (world.rs:18-24)
     sincos_(sun_altitude, &sa, &ca); sincos_(sun_azimuth, &sz, &cz);
     sun_dir_ = v3(ca * sz, sa, -ca * cz);
@@ -86,9 +80,9 @@ void Engine::refresh_sun_and_lights() {
         const V3 color = env_sun_off ? v3s(0.0f) : sun_transmittance(v3(0.0f, 6.360f + 0.0002f, 0.0f), sun_dir_) * 20.0f * 5.0f;
         GpuLight sun{};
         sun.d0 = f4(sun_dir_ * 1000.0f, 25.0f); sun.d1 = f4(color, INFINITY); sun.d2 = make_float4(b2f(1u), 0, 0, 0);
-        overwrite_light(0, -1, sun);
+        lights.set_sun(sun);
     }
-    snapshot_lights();
+    lights.snapshot();
 }
 // The scene's device copy: its tree as `plan` says (SceneTree::write), then the attribute records still owed, the transforms, tables and materials.
 int Engine::upload_scene(TreePlan plan, TickIo& io) {
@@ -103,32 +97,33 @@ int Engine::upload_scene(TreePlan plan, TickIo& io) {
     // Normal mapping reads the hit-test records per slot, and a copy written from a host tree has none (SceneSet::geo_current): while the switch is on and a
     // material has a map they travel with this upload, so that a moving scene pays no host join in its frames (Engine::normal_map_geo sends them only
     // where the switch, or a flagged query, comes after the tick). The host's array is current here: such a copy was just written from it.
-    if (normal_mapping && any_normal_map && !t.geo_current && !tri_geo.empty()) {
-        if ((rc = t.tri_geo.upload(tri_geo.data(), tri_geo.size() * sizeof(float4), c.up, staging, c.pageable))) return rc;
+    if (normal_mapping && materials.any_normal_map && !t.geo_current && !slots.geo().empty()) {
+        if ((rc = t.tri_geo.upload(slots.geo().data(), slots.geo().size() * sizeof(float4), c.up, staging, c.pageable))) return rc;
         t.geo_current = true;
     }
     t.dirty_lo = SIZE_MAX; t.dirty_hi = 0; t.tri_full = false; t.valid = true;
-    if ((rc = t.xforms.upload(instance_xforms.data(), instance_xforms.size() * sizeof(float4), c.up, staging, c.pageable))) return rc;
+    if ((rc = t.xforms.upload(instances.xforms.data(), instances.xforms.size() * sizeof(float4), c.up, staging, c.pageable))) return rc;
     // the scene queries' handle table follows the slots of this copy (a spawn, a despawn, a re-inserted mesh move triangle ranges)
     fill_instance_table();
     if ((rc = t.instance_table.upload(instance_table_.data(), instance_table_.size() * sizeof(uint32_t), c.up, staging, c.pageable))) return rc;
-    if ((rc = t.materials.upload(gpu_materials.data(), gpu_materials.size() * sizeof(GpuMaterial), c.up, staging, c.pageable))) return rc;
-    if ((rc = t.base_packed.upload(material_base_packed.data(), material_base_packed.size() * sizeof(uint32_t), c.up, staging, c.pageable))) return rc;
+    if ((rc = t.materials.upload(materials.gpu().data(), materials.gpu().size() * sizeof(GpuMaterial), c.up, staging, c.pageable))) return rc;
+    if ((rc = t.base_packed.upload(materials.base_packed().data(), materials.base_packed().size() * sizeof(uint32_t), c.up, staging, c.pageable))) return rc;
     copies.commit(io, copies.scene, c); tree.went_live(plan);
     return ST_OK;
 }
 // The atlas, the device images and the blue noise: in place, on the caller's stream.
 int Engine::upload_images(TickIo& io) {
-    if (atlas_dirty || blue_noise_dirty) io.uploaded = true;
-    if (atlas_dirty) if (int rc = d_atlas.upload(atlas.data(), atlas.size(), io.stream, staging, &io.pageable)) return rc;
-    for (auto& kv : device_images) {
-        DeviceImage& di = kv.second;
+    if (images.dirty || blue_noise_dirty) io.uploaded = true;
+    if (images.dirty) if (int rc = d_atlas.upload(images.texels().data(), images.texels().size(), io.stream, staging, &io.pageable)) return rc;
+    const size_t atlas_pitch = (size_t)images.width() * 4;
+    for (auto& kv : images.device()) {
+        ImageAtlas::DeviceImage& di = kv.second;
         if (!di.pending && !di.dynamic) continue;
-        const ImageRec& r = images.at(kv.first);
-        uint8_t* dst = static_cast<uint8_t*>(d_atlas.ptr) + ((size_t)r.y * atlas_w + r.x) * 4;
-        ST_HIP(hipMemcpy2DAsync(dst, (size_t)atlas_w * 4, di.pixels, di.pitch, (size_t)r.w * 4, r.h, hipMemcpyDeviceToDevice, io.stream));
+        const ImageAtlas::Rect& r = *images.rect_texels(kv.first);
+        uint8_t* dst = static_cast<uint8_t*>(d_atlas.ptr) + ((size_t)r.y * images.width() + r.x) * 4;
+        ST_HIP(hipMemcpy2DAsync(dst, atlas_pitch, di.pixels, di.pitch, (size_t)r.w * 4, r.h, hipMemcpyDeviceToDevice, io.stream));
         if (!di.dynamic) {  // keep the host copy complete: it is what a later full upload sends
-            ST_HIP(hipMemcpy2DAsync(&atlas[((size_t)r.y * atlas_w + r.x) * 4], (size_t)atlas_w * 4, di.pixels, di.pitch, (size_t)r.w * 4, r.h, hipMemcpyDeviceToHost, io.stream));
+            ST_HIP(hipMemcpy2DAsync(images.texel(r.x, r.y), atlas_pitch, di.pixels, di.pitch, (size_t)r.w * 4, r.h, hipMemcpyDeviceToHost, io.stream));
             io.pageable = true;  // joins the stream below before the host copy is read again
         }
         di.pending = false;
@@ -143,12 +138,12 @@ int Engine::upload_images(TickIo& io) {
 // Lights change rarely; skipping the identical re-upload also skips the stream sync of end_uploads, so the host can run a frame ahead of
 // the GPU (the reference re-uploads only dirty buffers too: mapped_storage_buffer.rs:103-121). They alternate like the scene, on their own schedule.
 int Engine::upload_lights(TickIo& io) {
-    if (gpu_lights.size() == uploaded_lights.size() && memcmp(gpu_lights.data(), uploaded_lights.data(), gpu_lights.size() * sizeof(GpuLight)) == 0) return ST_OK;
+    if (!lights.changed()) return ST_OK;
     CopyTarget c;
     if (int rc = copies.pick(io, copies.lights, c)) return rc;
-    if (int rc = copies.lights.copy[c.index].buf.upload(gpu_lights.data(), gpu_lights.size() * sizeof(GpuLight), c.up, staging, c.pageable)) return rc;
+    if (int rc = copies.lights.copy[c.index].buf.upload(lights.table().data(), lights.table().size() * sizeof(GpuLight), c.up, staging, c.pageable)) return rc;
     copies.commit(io, copies.lights, c);
-    uploaded_lights = gpu_lights;
+    lights.mark_uploaded();
     return ST_OK;
 }
 // The tick did everything; these statuses say what the frames rendered so far may have missed, or what the uploaded tree can cost.

@@ -1,6 +1,6 @@
 """What the renderer reads off the winning triangle, defined in float64 from what the caller handed to the API — mesh positions, normals and uvs, each
 instance's 3x4 transform and its previous one, Material fields, image pixels as uint8, cameras. Nothing here reads read_scene records, atlas rectangles
-or anything else an engine derived: the bake (Engine::bake, the device bake) and the atlas placement are under test, not trusted. No tree is built:
+or anything else an engine derived: the bake (TriangleSlots::write, the device bake) and the atlas placement are under test, not trusted. No tree is built:
 which triangle wins, its (u, v), t, the point and the ambiguity margin are walk_ref.trace's, over world vertices formed here as M . p in float64 and
 rounded to float32 (the engine intersects float32 records; tests/test_surface_ref.py holds the baked positions to these within 2 ulp of the extent).
 

@@ -3,6 +3,8 @@ Cornell, then the dungeon, 1920 x 1080 Image{denoise}, 30 frames each with one s
 deformation motion on) in between, an environment map set and replaced, a look-up table (colour grading on) inserted and replaced, auto-exposure
 display and FXAA + resize for the last 10, a second stream alternating with the first for the last 5 (mixed streams: the light moves back and the
 map and the table are replaced once more there, so that the writer and both retirements join the device), then st_camera_delete and st_engine_destroy.
+The scene stores' paths too: an image inserted and later replaced at another size, a material edited to point at it, the spawned instance removed, one
+static and one dynamic device image.
 Run it under `rocprofv3 --hip-trace --stats -- python tools/ownership_trace.py` once per library; with --summarize DIR it prints the
 per-API call counts of the trace under DIR as one JSON object."""
 import csv
@@ -34,6 +36,8 @@ def run():
     sky = lambda seed: (np.random.default_rng(seed).random((8, 16, 3)) * 2.0).astype(np.float32)
     lut = lambda seed: np.random.default_rng(seed).random((5, 5, 5, 3)).astype(np.float32)
     at = lambda p: np.array([[1, 0, 0, p[0]], [0, 1, 0, p[1]], [0, 0, 1, p[2]]], np.float32)
+    texels = lambda side, seed: np.random.default_rng(seed).integers(0, 256, (side, side, 4), dtype=np.uint8)
+    static_px, dynamic_px = (torch.full((32, 32, 4), v, dtype=torch.uint8, device="cuda:0") for v in (90, 160))
     for scene in ("cornell", "dungeon"):
         e = Engine(device=0)
         (scenes.build_cornell if scene == "cornell" else scenes.build_dungeon)(e)
@@ -48,6 +52,16 @@ def run():
         cam = e.create_camera((scenes.cornell_camera if scene == "cornell" else scenes.dungeon_camera)(size, CameraMode.IMAGE, denoise=True))
         e.insert_lut(41, lut(1)); e.set_color_grading(cam, lut=41, contrast=1.2)         # the table inserted
         for frame in range(30):
+            if frame == 2:
+                e.insert_image(5001, texels(48, 1))                                          # an image inserted
+                e.insert_device_image(5002, static_px.data_ptr(), 32, 32)                    # a static device image
+                e.insert_device_image(5003, dynamic_px.data_ptr(), 32, 32, dynamic=True)     # ... and a dynamic one
+            if frame == 6:
+                e.insert_image(5001, texels(96, 2))                                          # ... and replaced at another size
+            if frame == 18:
+                e.insert_material(tube, Material(base_color=(0.7, 0.3, 0.2, 1.0), base_color_texture=5001))   # the material edit
+            if frame == 22:
+                e.remove_instance(tube + 1)                                                  # the instance removed
             if frame == 4:
                 e.set_environment(sky(1))                                                    # the map set
             if frame in (10, 27):
